@@ -2,6 +2,13 @@
 """bench.py -- cell-updates/s of full time steps of the reference's models on MI355X (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W [--workload box|config4|config5] [--size 512] [--math fast|strict]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps (ms_per_step = their wall time / K) and prints the result line.  --dump-outputs DIR
+then also writes what the timed steps left in the model (see dump_outputs).  --full adds everything else the line can carry: the
+state checksum and finiteness check, the strict_ms_per_step leg, the event-timed dominant kernel with its roofline figures, the
+per-exchange times of a partitioned run (comm_stats) and the CPU baseline; --no-strict, --no-kernel-timing and --no-cpu-baseline
+drop single parts of it.
 
 Workloads (config.workload):
   box      (default; the configuration the metric is quoted on, BASELINE.json configs[1]/[2] at --size 256 / 512): N^3 triply
@@ -53,6 +60,11 @@ def parse():
     ap.add_argument("--size", dest="n", type=int, default=512, help="grid points per dimension (512 = the metric's config)")
     ap.add_argument("--math", choices=("fast", "strict"), default="fast")
     ap.add_argument("--workload", choices=("box", "config4", "config5"), default="box")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check what the headline does not need: state checksum, strict leg, "
+                         "dominant-kernel roofline, comm_stats, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the prognostic fields after the last timed step as DIR/<name>.npy (float64, whole or a fixed sample)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-strict", action="store_true", help="skip the strict_ms_per_step leg (3 steps of the bit-exact build)")
     ap.add_argument("--no-kernel-timing", action="store_true",
@@ -73,7 +85,10 @@ def parse():
     ap.add_argument("--all-gather", choices=("direct", "collective"), default=None,
                     help="the xtri solve's one exchange: direct = R - 1 grouped point-to-point transfers, one per xGMI link (default), "
                          "collective = ncclAllGather")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def self_launch(a):
@@ -230,6 +245,45 @@ def event_time(fn, reps=10):
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps
+
+
+DUMP_BUDGET_BYTES = 60_000_000   # all arrays of --dump-outputs together (float64)
+DUMP_MAX_POINTS = 1 << 20        # per array: a larger interior is sampled at this many points
+
+
+def dump_outputs(path, named, rank, world, dist):
+    """--dump-outputs: each (name, interior view [k, j, i] or [j, i] of this rank's x-slab) as path/<name>.npy in float64.  An interior
+    of at most DUMP_MAX_POINTS points (and its share of DUMP_BUDGET_BYTES) is written whole, in its global [k, j, i] shape; a larger one
+    as the 1-D values at a fixed sample of global points (drawn with replacement from a generator seeded by the field's name, sorted).
+    The points do not depend on the run or on the number of ranks: every rank fills the points of its slab, a sum over the ranks
+    completes the array, and rank 0 writes it."""
+    import zlib
+    import numpy as np
+    import torch
+    per_array = min(DUMP_MAX_POINTS, DUMP_BUDGET_BYTES // 8 // max(1, len(named)))
+    if rank == 0:
+        os.makedirs(path, exist_ok=True)
+    for name, view in named:
+        nx = view.shape[-1]
+        shape = tuple(view.shape[:-1]) + (nx * world,)
+        total = int(np.prod(shape))
+        whole = total <= per_array
+        if whole:
+            flat = np.arange(total)
+        else:
+            rng = np.random.default_rng([1234, zlib.crc32(name.encode())])
+            flat = np.sort(rng.integers(0, total, per_array))
+        idx = list(np.unravel_index(flat, shape))
+        idx[-1] = idx[-1] - rank * nx
+        mine = (idx[-1] >= 0) & (idx[-1] < nx)
+        dev = view.device
+        vals = torch.zeros(flat.size, dtype=torch.float64, device=dev)
+        vals[torch.from_numpy(mine).to(dev)] = view[tuple(torch.from_numpy(c[mine]).to(dev) for c in idx)].to(torch.float64)
+        if world > 1:
+            vals = dist.allreduce_sum(vals)
+        if rank == 0:
+            out = vals.cpu().numpy()
+            np.save(os.path.join(path, f"{name}.npy"), out.reshape(shape) if whole else out)
 
 
 def mapped_libraries(pattern):
@@ -605,18 +659,28 @@ def main():
     el = timed(a.steps, mark=True)
     if dist is not None:
         el = float(dist.allreduce_max(torch.tensor([el], device="cuda", dtype=torch.float64))[0])
-    finite = bool(all(torch.isfinite(f.data).all() for f in prognostic))
-    # state checksum after warm-up + timed steps: sum of squares of every prognostic field over the global interior.  The synthetic
-    # initial fields do not depend on the number of ranks, so a --gpus N line can be checked against the --gpus 1 line of the same
-    # command (agreement to ~1e-9 relative: the pressure solvers of the two paths differ in rounding).
-    sums = torch.stack([(f.interior_view() ** 2).sum() for f in prognostic])
-    checksum_global = True
-    if dist is not None:
-        if hasattr(dist, "allreduce_sum"):
-            sums = dist.allreduce_sum(sums)
-        else:
-            checksum_global = False  # a transport without a sum all-reduce: the sums are this rank's only
-    checksum = [float(v) for v in sums]
+    if a.dump_outputs is not None:
+        # what a caller of the timed path receives: the model's velocities and tracers (and the free surface of config 5)
+        named = [(n, f.interior_view()) for n, f in zip(["u", "v", "w"] + list(model.tracer_names), list(model.velocities) + list(model.tracers))]
+        if hydro:
+            mg = model.grid
+            named.append(("eta", model.eta[mg.Hy:mg.Hy + mg.Ny, mg.Hx:mg.Hx + mg.Nx]))
+        dump_outputs(a.dump_outputs, named, rank, world, dist)
+    # the checks below need the state only: a plain run skips them unless the two sequences of a partitioned run must be compared
+    finite, checksum, checksum_global = None, None, None
+    if a.full or conservative is not None:
+        finite = bool(all(torch.isfinite(f.data).all() for f in prognostic))
+        # state checksum after warm-up + timed steps: sum of squares of every prognostic field over the global interior.  The synthetic
+        # initial fields do not depend on the number of ranks, so a --gpus N line can be checked against the --gpus 1 line of the same
+        # command (agreement to ~1e-9 relative: the pressure solvers of the two paths differ in rounding).
+        sums = torch.stack([(f.interior_view() ** 2).sum() for f in prognostic])
+        checksum_global = True
+        if dist is not None:
+            if hasattr(dist, "allreduce_sum"):
+                sums = dist.allreduce_sum(sums)
+            else:
+                checksum_global = False  # a transport without a sum all-reduce: the sums are this rank's only
+        checksum = [float(v) for v in sums]
     legs_rel_diff = None
     if conservative is not None:
         # the two sequences started from the same state and took the same steps: their global sums agree to rounding (~1e-12 measured on
@@ -629,7 +693,7 @@ def main():
 
     # where a multi-GPU step spends its exchange time, measured on the device by the library (ocn_comm_enable_stats): 3 more steps
     comm_stats = None
-    if dist is not None and hasattr(dist, "_h"):
+    if a.full and dist is not None and hasattr(dist, "_h"):
         try:
             import ctypes as C
             ocn._lib.call("ocn_comm_enable_stats", dist._h, 1)
@@ -655,7 +719,7 @@ def main():
 
     # the bit-exact (strict IEEE, reference operand order) build of the same step, driver-visible
     strict_ms = None
-    if a.math == "fast" and not a.no_strict and world == 1:
+    if a.full and a.math == "fast" and not a.no_strict and world == 1:
         # (one GPU only: on a node the extra leg would put more collectives behind the measurement for a number the N = 1 line carries)
         try:
             ocn.set_math_mode(ocn.MATH_STRICT)
@@ -669,7 +733,7 @@ def main():
     cells = Nx * (Nx if hydro else N) * Nz
     value = cells * a.steps / el
     roofline, step_roofline = None, None
-    if a.no_kernel_timing:
+    if a.no_kernel_timing or not a.full:
         pass
     elif not hydro:
         # dominant kernel: the fused WENO5 momentum-tendency launch, timed live with events on the launching stream, (a) plain
@@ -812,6 +876,8 @@ def main():
         "roofline": roofline,
         "step_roofline": step_roofline,
         "driver": a.driver,
+        "full": a.full,
+        "dumped_outputs": a.dump_outputs,
     }
     if a.workload == "box" and step_roofline is not None:
         # north_star's unit, "the WENO5 tendency + pressure-correction step" = one RK3 substage (substep + projection + tendencies):
@@ -838,7 +904,7 @@ def main():
         end.daemon = True
         end.start()
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             if a.workload == "box":
                 out["cpu_baseline"] = cpu_baseline(a.cpu_n, a.cpu_steps)
             elif hydro:

@@ -5,7 +5,7 @@
 # Usage: tools/ab_bench.sh "<bench args>" name[:lib.so[:ENV=V,ENV2=V2]] ...     (empty lib = the default library)
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $ROOT
-ARGS=$1; shift
+ARGS="$1 --full"; shift   # (the roofline figures printed below come with --full)
 mkdir -p gpurun_out/ab
 for rep in 1 2; do
 for spec in "$@"; do
