@@ -349,8 +349,14 @@ int ocn_divergence(const ocn_grid *grid, const double *u, const double *v, const
 typedef struct ocn_poisson *ocn_poisson_t;
 int ocn_poisson_create(ocn_poisson_t *solver, const ocn_grid *grid);
 int ocn_poisson_destroy(ocn_poisson_t solver);
+/* FourierTridiagonalPoissonSolver along x (dim 0) or y (dim 1): that direction Bounded, N >= 2, grid->dzc == NULL (one stretched
+ * direction, like YZRegularRG / XZRegularRG).  dc, df: DEVICE Δᶜ / Δᶠ of that direction in the ocn_grid.dzc / dzf layout (element 0
+ * <-> index 1 - H, N + 2H elements); the handle copies them.  grid->dx (dy) is not read.  The other two directions are transformed
+ * (cosine transforms along Bounded, Fourier along Periodic, none along Flat).  The handle's other entry points work on it unchanged;
+ * ocn_poisson_solve_shifted refuses it. */
+int ocn_poisson_create_stretched(ocn_poisson_t *solver, const ocn_grid *grid, int32_t dim, const double *dc, const double *df);
 /* introspection: kind 0 = FFT-based, 1 = Fourier-tridiagonal, 2 = FFT-based with cosine transforms (a Bounded / Flat x or y),
- * 3 = Fourier-tridiagonal on such a grid; r2c = real-to-complex transforms in use;
+ * 3 = Fourier-tridiagonal on such a grid, 4 / 5 = Fourier-tridiagonal along a stretched x / y (ocn_poisson_create_stretched); r2c = real-to-complex transforms in use;
  * direct_out = bit 0: inverse transform writes straight into the pressure interior (no copy_real_component! pass); bit 1: the fused
  * FFT_z / division / IFFT_z column pass; bit 2: the library's own row / column kernels for x and y; bit 3: kind 1 on a REGULAR z of a
  * column-kernel length -- the Thomas sweep replaced by its exact spectral twin, cosine transform / division / inverse cosine transform in
@@ -537,6 +543,11 @@ int ocn_model_driver_field(ocn_model_driver_t driver, int32_t f, double **field,
 /* solve!(ϕ, ::BatchedTridiagonalSolver, rhs), z direction (src/Solvers/batched_tridiagonal_solver.jl:100-123,
  * 203-235).  a, c: real Nz-1; b: real Nx*Ny*Nz; f, phi: complex interleaved Nx*Ny*Nz; t: real scratch. */
 int ocn_batched_tridiagonal_solve_z(int32_t Nx, int32_t Ny, int32_t Nz, const double *a, const double *b, const double *c,
+                                    const double *f, double *t, double *phi, void *stream);
+/* the same along x (a, c: Nx-1) and along y (a, c: Ny-1), same array layouts */
+int ocn_batched_tridiagonal_solve_x(int32_t Nx, int32_t Ny, int32_t Nz, const double *a, const double *b, const double *c,
+                                    const double *f, double *t, double *phi, void *stream);
+int ocn_batched_tridiagonal_solve_y(int32_t Nx, int32_t Ny, int32_t Nz, const double *a, const double *b, const double *c,
                                     const double *f, double *t, double *phi, void *stream);
 
 /* ---- Distributed slab-x support (src/DistributedComputations/) ----

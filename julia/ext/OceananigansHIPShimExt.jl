@@ -118,12 +118,15 @@ topo_code(::Type{FullyConnected}) = Int32(3)
 topo_code(::Type{RightConnected}) = Int32(4)   # the first slab of a Bounded partitioned x: wall on its west side
 topo_code(::Type{LeftConnected}) = Int32(5)    # the last one: wall on its east side
 const HIPGrid = RectilinearGrid{<:Any, <:Any, <:Any, <:Any, <:Any, <:Any, <:Any, <:HIPGPU}
+# a stretched x / y is 0.0 in ocn_grid: only ocn_poisson_create_stretched takes its spacings
+regular_spacing(Δ::Number) = Float64(Δ)
+regular_spacing(Δ) = 0.0
 function OcnGrid(g::RectilinearGrid)
     TX, TY, TZ = topology(g)
     stretched = !(g.z.Δᵃᵃᶜ isa Number)
     # `math`: 0 = the process default (set_math_mode!), 1 = strict, 2 = fast -- a per-grid / per-model choice (HIP_MATH_MODE[] here)
     OcnGrid(g.Nx, g.Ny, g.Nz, g.Hx, g.Hy, g.Hz, topo_code(TX), topo_code(TY), topo_code(TZ), HIP_MATH_MODE[],
-            g.Δxᶜᵃᵃ, g.Δyᵃᶜᵃ, stretched ? 0.0 : g.z.Δᵃᵃᶜ, g.Lx, g.Ly, g.Lz,
+            regular_spacing(g.Δxᶜᵃᵃ), regular_spacing(g.Δyᵃᶜᵃ), stretched ? 0.0 : g.z.Δᵃᵃᶜ, g.Lx, g.Ly, g.Lz,
             stretched ? parent(g.z.Δᵃᵃᶜ).ptr : Ptr{Float64}(C_NULL),          # element 0 <-> k = 1-Hz
             stretched ? parent(g.z.Δᵃᵃᶠ).ptr + 8 : Ptr{Float64}(C_NULL))      # parent starts at k = -Hz -> skip one
 end
@@ -196,12 +199,22 @@ mutable struct HIPPoissonSolver
 end
 function nonhydrostatic_pressure_solver(::HIPGPU, grid::RectilinearGrid)
     h = Ref{Ptr{Cvoid}}(C_NULL)
-    check(ccall((:ocn_poisson_create, lib), Cint, (Ptr{Ptr{Cvoid}}, Ref{OcnGrid}), h, Ref(OcnGrid(grid))))
+    if !(grid.Δxᶜᵃᵃ isa Number) || !(grid.Δyᵃᶜᵃ isa Number)
+        # YZRegularRG / XZRegularRG: FourierTridiagonalPoissonSolver along the stretched x (dim 0) / y (dim 1); Δᶜ element 0 <-> index
+        # 1 - H, the parent of Δᶠ starts one element earlier (as for z in OcnGrid)
+        dim = grid.Δxᶜᵃᵃ isa Number ? Int32(1) : Int32(0)
+        Δᶜ, Δᶠ = dim == 0 ? (grid.Δxᶜᵃᵃ, grid.Δxᶠᵃᵃ) : (grid.Δyᵃᶜᵃ, grid.Δyᵃᶠᵃ)
+        GC.@preserve grid check(ccall((:ocn_poisson_create_stretched, lib), Cint,
+            (Ptr{Ptr{Cvoid}}, Ref{OcnGrid}, Int32, Ptr{Float64}, Ptr{Float64}),
+            h, Ref(OcnGrid(grid)), dim, parent(Δᶜ).ptr, parent(Δᶠ).ptr + 8))
+    else
+        check(ccall((:ocn_poisson_create, lib), Cint, (Ptr{Ptr{Cvoid}}, Ref{OcnGrid}), h, Ref(OcnGrid(grid))))
+    end
     s = HIPPoissonSolver(h[], grid)
     finalizer(x -> ccall((:ocn_poisson_destroy, lib), Cint, (Ptr{Cvoid},), x.handle), s)
     return s
 end
-"kind 0 FFT-based, 1 Fourier-tridiagonal, 2 FFT-based with cosine transforms; r2c; inverse transform writes p directly"
+"kind 0 FFT-based, 1 Fourier-tridiagonal, 2 FFT-based with cosine transforms, 3 Fourier-tridiagonal along z with a Bounded / Flat x or y, 4 / 5 Fourier-tridiagonal along a stretched x / y; r2c; inverse transform writes p directly"
 function solver_info(s::HIPPoissonSolver)
     kind = Ref{Int32}(0); r2c = Ref{Int32}(0); direct = Ref{Int32}(0)
     check(ccall((:ocn_poisson_info, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}), s.handle, kind, r2c, direct))

@@ -24,8 +24,8 @@ from .output import (AdvectiveCFL, DiffusiveCFL, NaNChecker, TimeStepWizard, cel
 from .physics import (AnisotropicMinimumDissipation, BetaPlane, BoundaryCondition, BuoyancyTracer, Centered, FieldBoundaryConditions, FluxBoundaryCondition, FPlane,
                       GradientBoundaryCondition, LinearEquationOfState, OpenBoundaryCondition, ScalarDiffusivity, SeawaterBuoyancy,
                       ValueBoundaryCondition)
-from .solvers import (BatchedTridiagonalSolver, FFTBasedPoissonSolver, FourierTridiagonalPoissonSolver,
-                      nonhydrostatic_pressure_solver, solve)
+from .solvers import (BatchedTridiagonalSolver, FFTBasedPoissonSolver, FourierTridiagonalPoissonSolver, XDirection, YDirection, ZDirection,
+                      nonhydrostatic_pressure_solver, solve, stretched_direction)
 
 
 from .hydrostatic import (AdamsBashforth3Scheme, ExplicitFreeSurface, ForwardBackwardScheme, HydrostaticFreeSurfaceModel, ImplicitFreeSurface, SplitExplicitFreeSurface,  # noqa: E402

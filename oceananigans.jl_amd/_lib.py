@@ -117,6 +117,7 @@ _SIGS = {
     "ocn_divergence": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _vp],
     "ocn_poisson_create": [C.POINTER(_vp), C.POINTER(CGrid)],
     "ocn_poisson_destroy": [_vp],
+    "ocn_poisson_create_stretched": [C.POINTER(_vp), C.POINTER(CGrid), _i32, _vp, _vp],
     "ocn_poisson_info": [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)],
     "ocn_poisson_compute_source_term": [_vp, _vp, _vp, _vp, _dbl, _vp],
     "ocn_poisson_set_source_term": [_vp, _vp, _vp],
@@ -126,6 +127,8 @@ _SIGS = {
     "ocn_implicit_free_surface_rhs": [C.POINTER(CGrid), _vp, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp, _vp],
     "ocn_barotropic_pressure_correction": [C.POINTER(CGrid), _vp, _vp, _vp, _dbl, _dbl, _vp],
     "ocn_batched_tridiagonal_solve_z": [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ocn_batched_tridiagonal_solve_x": [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ocn_batched_tridiagonal_solve_y": [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ocn_halo_pack_x": [C.POINTER(CGrid), _vp, _i32, _vp, _vp, _vp],
     "ocn_halo_unpack_x": [C.POINTER(CGrid), _vp, _i32, _vp, _vp, _vp],
     "ocn_add_momentum_terms": [C.POINTER(CGrid), C.POINTER(CModelTerms), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32), _vp],

@@ -1095,6 +1095,24 @@ int ocn_batched_tridiagonal_solve_z(int32_t Nx, int32_t Ny, int32_t Nz, const do
     return launch_tridiag_z(Nx, Ny, Nz, a, b, c, f, t, phi, as_stream(stream), /*keep_storage=*/1);
 }
 
+// XDirection / YDirection of the same solver: a, c of length N - 1 of the tridiagonal direction, the arrays in the same (Nx, Ny, Nz) layout
+int ocn_batched_tridiagonal_solve_x(int32_t Nx, int32_t Ny, int32_t Nz, const double *a, const double *b, const double *c,
+                                    const double *f, double *t, double *phi, void *stream)
+{
+    OCN_REQUIRE(Nx >= 1 && Ny >= 1 && Nz >= 1, "bad sizes (%d, %d, %d)", Nx, Ny, Nz);
+    OCN_REQUIRE(a && b && c && f && t && phi, "ocn_batched_tridiagonal_solve_x: null pointer");
+    return launch_tridiag_x(Nx, (long long)Ny * Nz, a, b, c, f, t, phi, as_stream(stream), /*keep_storage=*/1);
+}
+
+int ocn_batched_tridiagonal_solve_y(int32_t Nx, int32_t Ny, int32_t Nz, const double *a, const double *b, const double *c,
+                                    const double *f, double *t, double *phi, void *stream)
+{
+    OCN_REQUIRE(Nx >= 1 && Ny >= 1 && Nz >= 1, "bad sizes (%d, %d, %d)", Nx, Ny, Nz);
+    OCN_REQUIRE(a && b && c && f && t && phi, "ocn_batched_tridiagonal_solve_y: null pointer");
+    // lanes along x (coalesced), the sweep along y: planes Nx apart, columns (i, k) at i + Nx Ny k
+    return launch_tridiag_z_strided(Nx, Nz, (long long)Nx * Ny, Nx, Ny, a, b, c, f, t, phi, as_stream(stream), /*keep_storage=*/1);
+}
+
 int ocn_halo_pack_x(const ocn_grid *grid, const double *field, int32_t loc, double *send_west, double *send_east, void *stream)
 {
     int st = validate_grid_any(grid);

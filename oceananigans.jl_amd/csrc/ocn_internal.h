@@ -62,6 +62,16 @@ int launch_tridiag_z_strided(int ni, int nj, long long sj, long long sk, int Nz,
 int launch_main_diagonal_strided(const ocn_grid *grid, int ni, int nj, long long sj, long long sk, const double *lx, const double *ly,
                                  double *D, hipStream_t stream);
 int launch_remove_mean_mode(long long s3, int Nz, double *phi, hipStream_t stream);
+// stretched.hip: the Fourier-tridiagonal solver along a stretched x (dim 0) or y (dim 1)
+int launch_tridiag_x(int N, long long nlines, const double *a, const double *b, const double *c, const double *f, double *t, double *phi,
+                     hipStream_t stream, int keep_storage = 0);
+int launch_tridiag_x_real(int N, long long nlines, const double *a, const double *b, const double *c, const double *f, double *t, double *phi,
+                          hipStream_t stream, int keep_storage = 0);
+int launch_main_diagonal_xy(int dim, int Nx, int Ny, int Nz, int H, const double *dc, const double *df, const double *l1, const double *l2,
+                            double *D, hipStream_t stream);
+int launch_source_term_stretched(const ocn_grid *grid, int dim, const double *dc, const double *u, const double *v, const double *w, double dt,
+                                 double *out, int perm_dim, hipStream_t stream);
+int launch_set_source_stretched(int Nx, int Ny, int Nz, const double *R, int dim, const double *dc, int H, double *out, hipStream_t stream);
 // column FFTs (colfft.hip): mode 0 forward (natural -> stage order), 1 inverse (stage order -> natural),
 // 2 forward + spectral solve + inverse.  N in {64, 128, 256, 512}.
 bool colfft_supported(int N);

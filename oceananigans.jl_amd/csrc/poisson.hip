@@ -177,6 +177,11 @@ struct ocn_poisson {
     // with a Bounded / Flat x or y (XYRegularRG with any (x, y) topology: fourier_tridiagonal_poisson_solver.jl:82-147) -- the only solver
     // of a channel with a stretched z
     bool gtri = false;
+    // ... and the dimension of that sweep: 2 (z), or 0 / 1 for a stretched x / y (YZRegularRG / XZRegularRG, ocn_poisson_create_stretched):
+    // the other two directions are transformed, the sweep runs along `tdim` with the handle's own copies of its spacings (tdc, tdf, the
+    // ocn_grid.dzc / dzf layout); the packed and all-real variants below assume a sweep along z and stay off
+    int tdim = 2;
+    double *tdc = nullptr, *tdf = nullptr;
     // x Periodic (even Nx) next to a Bounded y / z: the source term is REAL and a cosine transform maps reals to reals, so the transforms
     // along the Bounded y / z run on the real array VIEWED as complex numbers of x-adjacent pairs (Nx / 2 complex columns: the complex
     // transform of a line is the transform of its real and of its imaginary part, separated by the Hermitian symmetry the twiddle passes
@@ -206,7 +211,7 @@ static void free_all(ocn_poisson *s)
         if (s->gpartner[d]) (void)hipFree(s->gpartner[d]);
         s->gpartner[d] = nullptr;
     }
-    double **ptrs[] = {&s->dzc, &s->dzf, &s->lx, &s->ly, &s->lz, &s->rhs, &s->spec, &s->spec2, &s->diag, &s->tscr, &s->lower, &s->tw, &s->lz_stage, &s->twMx, &s->twNx, &s->twy, &s->ly_stage, &s->wdz, &s->lz_bounded,
+    double **ptrs[] = {&s->dzc, &s->dzf, &s->tdc, &s->tdf, &s->lx, &s->ly, &s->lz, &s->rhs, &s->spec, &s->spec2, &s->diag, &s->tscr, &s->lower, &s->tw, &s->lz_stage, &s->twMx, &s->twNx, &s->twy, &s->ly_stage, &s->wdz, &s->lz_bounded,
                        &s->tab[0][0], &s->tab[0][1], &s->tab[1][0], &s->tab[1][1], &s->tab[2][0], &s->tab[2][1]};
     for (auto p : ptrs)
         if (*p) {
@@ -430,12 +435,13 @@ static int exec_line_plan(ocn_poisson *s, int d, int inverse, double *a, const i
 static thread_local bool g_no_packed = false;  // the retry of poisson_create_general after a failed self test of the real x plans
 static int packed_plans_self_test(ocn_poisson *s);
 
-static int poisson_create_general(ocn_poisson_t *out, const ocn_grid *grid)
+static int poisson_create_general(ocn_poisson_t *out, const ocn_grid *grid, int tdim = 2, const double *tdc = nullptr, const double *tdf = nullptr)
 {
-    // a stretched z (or OCN_POISSON_GENERAL_TRI=1 on a regular Bounded z): transforms along x and y, tridiagonal solve along z
+    // a stretched z (or OCN_POISSON_GENERAL_TRI=1 on a regular Bounded z): transforms along x and y, tridiagonal solve along z;
+    // tdim 0 / 1 (ocn_poisson_create_stretched, arguments validated there): tridiagonal solve along the stretched x / y
     const char *etri = std::getenv("OCN_POISSON_GENERAL_TRI");
-    const bool gtri = grid->dzc != nullptr || (etri && etri[0] == '1' && grid->tz == OCN_BOUNDED);
-    if (gtri && (grid->tz != OCN_BOUNDED || grid->Nz < 2)) {
+    const bool gtri = tdim != 2 || grid->dzc != nullptr || (etri && etri[0] == '1' && grid->tz == OCN_BOUNDED);
+    if (gtri && tdim == 2 && (grid->tz != OCN_BOUNDED || grid->Nz < 2)) {
         ocn::set_error("`FourierTridiagonalPoissonSolver` can only be used when the stretched direction's topology is `Bounded` (and Nz >= 2)");
         return OCN_ERR_UNSUPPORTED;
     }
@@ -448,9 +454,12 @@ static int poisson_create_general(ocn_poisson_t *out, const ocn_grid *grid)
     s->grid = *grid;
     s->kind = 2;
     s->gtri = gtri;
+    s->tdim = tdim;
     s->c2c = true;
     s->direct_out = false;
-    const int N[3] = {grid->Nx, grid->Ny, grid->Nz}, topo[3] = {grid->tx, grid->ty, gtri ? OCN_FLAT : grid->tz};  // (no transform along z)
+    int topo[3] = {grid->tx, grid->ty, grid->tz};
+    if (gtri) topo[tdim] = OCN_FLAT;  // (no transform along the tridiagonal direction)
+    const int N[3] = {grid->Nx, grid->Ny, grid->Nz};
     const double Ls[3] = {grid->Lx, grid->Ly, grid->Lz};
     s->nxh = N[0];
     const size_t n = (size_t)N[0] * N[1] * N[2];
@@ -475,9 +484,9 @@ static int poisson_create_general(ocn_poisson_t *out, const ocn_grid *grid)
         s->fft_dct = !(nv && nv[0] == '1');
         {
             const char *ep = std::getenv("OCN_POISSON_PACKED");
-            s->gpacked = s->fft_dct && !g_no_packed && topo[0] == OCN_PERIODIC && N[0] % 2 == 0 && N[0] >= 4 &&
+            s->gpacked = s->fft_dct && !g_no_packed && tdim == 2 && topo[0] == OCN_PERIODIC && N[0] % 2 == 0 && N[0] >= 4 &&
                          (topo[1] == OCN_BOUNDED || topo[2] == OCN_BOUNDED) && !(ep && ep[0] == '0');
-            s->gallreal = s->fft_dct && topo[0] == OCN_BOUNDED && topo[1] == OCN_BOUNDED && (topo[2] == OCN_BOUNDED || topo[2] == OCN_FLAT) &&
+            s->gallreal = s->fft_dct && tdim == 2 && topo[0] == OCN_BOUNDED && topo[1] == OCN_BOUNDED && (topo[2] == OCN_BOUNDED || topo[2] == OCN_FLAT) &&
                           N[0] % 2 == 0 && N[1] % 2 == 0 && !(ep && ep[0] == '0');
         }
         if (s->fft_dct && st == OCN_SUCCESS) {
@@ -567,12 +576,39 @@ static int poisson_create_general(ocn_poisson_t *out, const ocn_grid *grid)
             free_all(s);
             delete s;
             g_no_packed = true;
-            const int st2 = poisson_create_general(out, grid);
+            const int st2 = poisson_create_general(out, grid, tdim, tdc, tdf);
             g_no_packed = false;
             return st2;
         }
     }
-    if (st == OCN_SUCCESS && gtri) {
+    if (st == OCN_SUCCESS && gtri && tdim != 2) {
+        // own copies of Δᶜ / Δᶠ of the stretched x / y; lower = upper = 1/Δξᶠ[q], q = 2..N; main diagonal of XDirection / YDirection with the
+        // (stored-order) eigenvalues of the two transformed directions (fourier_tridiagonal_poisson_solver.jl:17-39, 97-99)
+        const int Nt = N[tdim], Ht = tdim == 0 ? grid->Hx : grid->Hy;
+        const size_t nf = (size_t)Nt + 2 * Ht;
+        std::vector<double> hf(nf);
+        const bool ok = hipMalloc((void **)&s->tdc, nf * sizeof(double)) == hipSuccess && hipMalloc((void **)&s->tdf, nf * sizeof(double)) == hipSuccess &&
+                        hipMemcpy(s->tdc, tdc, nf * sizeof(double), hipMemcpyDeviceToDevice) == hipSuccess &&
+                        hipMemcpy(s->tdf, tdf, nf * sizeof(double), hipMemcpyDeviceToDevice) == hipSuccess &&
+                        hipMemcpy(hf.data(), tdf, nf * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
+                        hipMalloc((void **)&s->diag, n * sizeof(double)) == hipSuccess && hipMalloc((void **)&s->tscr, n * sizeof(double)) == hipSuccess;
+        if (!ok) {
+            ocn::set_error("ocn_poisson_create_stretched: out of device memory (tridiagonal arrays)");
+            st = OCN_ERR_ALLOC;
+        }
+        if (st == OCN_SUCCESS) {
+            std::vector<double> low(Nt - 1, 0.0);
+            for (int q = 2; q <= Nt; ++q) low[q - 2] = 1 / hf[q + Ht - 1];
+            st = upload(low, &s->lower);
+        }
+        if (st == OCN_SUCCESS)
+            st = ocn::launch_main_diagonal_xy(tdim, N[0], N[1], N[2], Ht, s->tdc, s->tdf, tdim == 0 ? s->ly : s->lx, s->lz, s->diag, nullptr);
+        if (st == OCN_SUCCESS && hipDeviceSynchronize() != hipSuccess) {
+            ocn::set_error("ocn_poisson_create_stretched: main diagonal kernel failed");
+            st = OCN_ERR_HIP;
+        }
+    }
+    if (st == OCN_SUCCESS && gtri && tdim == 2) {
         // own copies of the spacings, lower = upper = 1/Δzᶠ[q], q = 2..Nz, main diagonal with the (stored-order) eigenvalues of x and y
         // (fourier_tridiagonal_poisson_solver.jl:41-51, 97-99)
         const int Nz = grid->Nz, Hz = grid->Hz;
@@ -624,7 +660,9 @@ static bool general_fuse_shuffles()
 static int poisson_solve_general(ocn_poisson *s, double *p, hipStream_t stream)
 {
     const ocn_grid *g = &s->grid;
-    const int N[3] = {g->Nx, g->Ny, g->Nz}, topo[3] = {g->tx, g->ty, s->gtri ? OCN_FLAT : g->tz};
+    const int N[3] = {g->Nx, g->Ny, g->Nz};
+    int topo[3] = {g->tx, g->ty, g->tz};
+    if (s->gtri) topo[s->tdim] = OCN_FLAT;
     double *a = s->spec, *b = s->spec2;
     int order[3], no = 0;
     for (int d = 0; d < 3; ++d) if (topo[d] == OCN_BOUNDED) order[no++] = d;
@@ -675,6 +713,18 @@ static int poisson_solve_general(ocn_poisson *s, double *p, hipStream_t stream)
     };
     auto solve = [&](int nx) {  // the division by the eigenvalues, or the Thomas sweep along z, on an (nx, Ny, Nz) spectrum
         int st;
+        if (s->gtri && s->tdim == 0) {  // the sweep along x (LDS-staged lines), then the zero-mean gauge on the (ky, kz) = (0, 0) line
+            st = ocn::launch_tridiag_x(N[0], (long long)N[1] * N[2], s->lower, s->diag, s->lower, a, s->tscr, b, stream);
+            if (st != OCN_SUCCESS) return st;
+            std::swap(a, b);
+            return ocn::launch_remove_mean_mode(1, N[0], a, stream);
+        }
+        if (s->gtri && s->tdim == 1) {  // the sweep along y: the z kernel with lanes along x and planes Nx apart; gauge on the (kx, kz) = (0, 0) line
+            st = ocn::launch_tridiag_z_strided(nx, N[2], (long long)nx * N[1], nx, N[1], s->lower, s->diag, s->lower, a, s->tscr, b, stream);
+            if (st != OCN_SUCCESS) return st;
+            std::swap(a, b);
+            return ocn::launch_remove_mean_mode(nx, N[1], a, stream);
+        }
         if (s->gtri) {  // batched Thomas sweep along z, then the zero-mean gauge on the (kx, ky) = (0, 0) column (stored position 0 in either order)
             st = ocn::launch_tridiag_z(nx, N[1], N[2], s->lower, s->diag, s->lower, a, s->tscr, b, stream);
             if (st != OCN_SUCCESS) return st;
@@ -1314,6 +1364,25 @@ static int poisson_plans_self_test(ocn_poisson *s)
 
 extern "C" int ocn_poisson_create(ocn_poisson_t *out, const ocn_grid *grid) { return poisson_create_impl(out, grid, false); }
 
+extern "C" int ocn_poisson_create_stretched(ocn_poisson_t *out, const ocn_grid *grid, int32_t dim, const double *dc, const double *df)
+{
+    // every argument is checked before the first HIP call
+    OCN_REQUIRE(out && grid, "ocn_poisson_create_stretched: null argument");
+    OCN_REQUIRE(dim == 0 || dim == 1, "ocn_poisson_create_stretched: dim must be 0 (x) or 1 (y), got %d", dim);
+    OCN_REQUIRE(dc && df, "ocn_poisson_create_stretched: null spacing array");
+    OCN_REQUIRE(grid->dzc == nullptr && grid->dzf == nullptr,
+                "ocn_poisson_create_stretched: z must be regular (grid->dzc == NULL): one stretched direction per solver");
+    OCN_REQUIRE((dim == 0 ? grid->tx : grid->ty) == OCN_BOUNDED,
+                "`FourierTridiagonalPoissonSolver` can only be used when the stretched direction's topology is `Bounded`.");
+    OCN_REQUIRE((dim == 0 ? grid->Nx : grid->Ny) >= 2, "ocn_poisson_create_stretched: the stretched direction needs N >= 2");
+    for (int t : {grid->tx, grid->ty, grid->tz})
+        OCN_REQUIRE(t == OCN_PERIODIC || t == OCN_BOUNDED || t == OCN_FLAT, "ocn_poisson_create_stretched: topology code %d is not supported", t);
+    OCN_REQUIRE(grid->Nx >= 1 && grid->Ny >= 1 && grid->Nz >= 1 && grid->Hx >= 0 && grid->Hy >= 0 && grid->Hz >= 0, "bad grid size / halo");
+    OCN_REQUIRE((dim == 1 || grid->dy > 0) && (dim == 0 || grid->dx > 0) && grid->dz > 0 && grid->Lx > 0 && grid->Ly > 0 && grid->Lz > 0,
+                "spacings and extents must be positive");
+    return poisson_create_general(out, grid, dim, dc, df);
+}
+
 extern "C" int ocn_poisson_destroy(ocn_poisson_t s)
 {
     if (!s) return OCN_SUCCESS;
@@ -1325,7 +1394,8 @@ extern "C" int ocn_poisson_destroy(ocn_poisson_t s)
 extern "C" int ocn_poisson_info(ocn_poisson_t s, int32_t *kind, int32_t *r2c, int32_t *direct_out)
 {
     OCN_REQUIRE(s, "ocn_poisson_info: null solver");
-    if (kind) *kind = s->gtri ? 3 : s->kind;  // 3: Fourier-tridiagonal on a grid with a Bounded / Flat x or y
+    // 3: Fourier-tridiagonal on a grid with a Bounded / Flat x or y; 4 / 5: Fourier-tridiagonal along a stretched x / y
+    if (kind) *kind = s->gtri ? (s->tdim == 0 ? 4 : s->tdim == 1 ? 5 : 3) : s->kind;
     if (r2c) *r2c = !s->c2c;
     if (direct_out) *direct_out = (!s->c2c && s->direct_out) + 2 * (s->fused_z ? 1 : 0) + 4 * (s->custom_xy ? 1 : 0) + 8 * (s->dct_z ? 1 : 0);
     return OCN_SUCCESS;
@@ -1343,9 +1413,15 @@ extern "C" int ocn_poisson_compute_source_term(ocn_poisson_t s, const double *u,
         // folded into this store
         int first = -1;
         if (s->fft_dct && general_fuse_shuffles())
-            for (int d = s->gtri ? 1 : 2; d >= (s->gallreal ? 1 : 0); --d)  // (all-real boxes transform y first: their x lines pair rows)
-                if ((d == 0 ? g->tx : d == 1 ? g->ty : g->tz) == OCN_BOUNDED) first = d;
+            for (int d = 2; d >= (s->gallreal ? 1 : 0); --d)  // (all-real boxes transform y first: their x lines pair rows)
+                if (!(s->gtri && d == s->tdim) && (d == 0 ? g->tx : d == 1 ? g->ty : g->tz) == OCN_BOUNDED) first = d;
         if (first >= 0 && s->gdct[first]) first = -1;  // (the fused cosine transform gathers on its own load)
+        if (s->gtri && s->tdim != 2) {  // Δξᶜ div(U) / Δt on the stretched x / y spacing
+            st = ocn::launch_source_term_stretched(g, s->tdim, s->tdc, u, v, w, dt, s->spec, first, ocn::as_stream(stream));
+            s->gathered = (st == OCN_SUCCESS) && first >= 0;
+            s->source_set = (st == OCN_SUCCESS);
+            return st;
+        }
         // (the tridiagonal flavour's right-hand side carries Δzᶜ: _fourier_tridiagonal_source_term!, solve_for_pressure.jl:33-38)
         // (packed: the source stays a REAL array -- modes 3 / 4 -- whose x-adjacent pairs the cosine transforms read as complex numbers)
         const int mode = (s->gpacked || s->gallreal) ? (s->gtri ? 4 : 3) : (s->gtri ? 2 : 1);
@@ -1377,7 +1453,9 @@ extern "C" int ocn_poisson_set_source_term(ocn_poisson_t s, const double *R, voi
     const bool tri = (s->kind == 1 && !s->dct_z) || s->gtri;
     const double *dzc = tri ? g->dzc : nullptr;
     int st;
-    if (tri && !g->dzc) {
+    if (s->gtri && s->tdim != 2) {  // multiply_by_stretched_spacing! of YZRegularRG / XZRegularRG: R Δxᶜ or R Δyᶜ
+        st = ocn::launch_set_source_stretched(g->Nx, g->Ny, g->Nz, R, s->tdim, s->tdc, s->tdim == 0 ? g->Hx : g->Hy, s->spec, ocn::as_stream(stream));
+    } else if (tri && !g->dzc) {
         // regular Bounded z: Δz is a scalar; scale on the fly through a constant array is not needed -- use a tiny device array
         std::vector<double> h(g->Nz + 2 * g->Hz, g->dz);
         double *d = nullptr;

@@ -94,19 +94,39 @@ def CenterField(grid, boundary_conditions=None):
     return Field(_lib.LOC_CCC, grid, boundary_conditions=boundary_conditions)
 
 
+def _fill_grid_ref(grid):
+    """The ocn_grid a halo fill gets.  The library checks Δx, Δy > 0; a stretched x / y is 0.0 in ocn_grid, and the fills that run on such a
+    grid (periodic images, no flux, impenetrable walls: conditions on a stretched wall are refused below) read no spacing, so they get a copy
+    with the direction's smallest spacing there."""
+    stretched = [d for d in getattr(grid, "stretched_dimensions", ()) if d < 2]
+    if not stretched:
+        return grid.cref
+    import ctypes as C
+    c = _lib.CGrid.from_buffer_copy(grid.c)
+    for d in stretched:
+        setattr(c, "dx" if d == 0 else "dy", grid.spacing_extrema(d)[0])
+    return C.byref(c)
+
+
 def local_fill_halo_regions(grid, fields, fill_boundary_normal_velocities=True):
     """The rank-local part of fill_halo_regions! (one launch for the whole tuple): Periodic copies, no-flux / impenetrable
     walls, and the fields' own bottom / top Value / Gradient conditions."""
     bcs = [getattr(f, "boundary_conditions", None) for f in fields]
+    walls = {0: ("west", "east"), 1: ("south", "north")}
+    for d in getattr(grid, "stretched_dimensions", ()):
+        for b in bcs:
+            if d < 2 and b is not None and any(b.sides[side] is not None for side in walls[d]):
+                # (the kernels take ocn_grid's Δx / Δy, a placeholder on such a grid)
+                raise NotImplementedError(f"a boundary condition on the {' / '.join(walls[d])} walls of a grid stretched in {'xy'[d]}")
     if any(b is not None and not b.is_default() for b in bcs):
         import ctypes as C
         arr = (C.POINTER(_lib.CFieldBcs) * len(fields))(*[
             (C.pointer(b.c_struct(grid)) if b is not None and not b.is_default() else C.POINTER(_lib.CFieldBcs)()) for b in bcs])
-        _lib.call("ocn_fill_halo_regions_bcs", grid.cref, _lib.ptr_array([f.ptr for f in fields]),
+        _lib.call("ocn_fill_halo_regions_bcs", _fill_grid_ref(grid), _lib.ptr_array([f.ptr for f in fields]),
                   _lib.i32_array([f.loc for f in fields]), arr, len(fields), int(bool(fill_boundary_normal_velocities)),
                   stream_ptr())
         return
-    _lib.call("ocn_fill_halo_regions", grid.cref, _lib.ptr_array([f.ptr for f in fields]),
+    _lib.call("ocn_fill_halo_regions", _fill_grid_ref(grid), _lib.ptr_array([f.ptr for f in fields]),
               _lib.i32_array([f.loc for f in fields]), len(fields), int(bool(fill_boundary_normal_velocities)), stream_ptr())
 
 

@@ -1,5 +1,5 @@
 """RectilinearGrid: mirrors src/Grids/rectilinear_grid.jl:248-275 and grid_generation.jl:34-155
-for x, y regular and z regular or stretched; topologies (Periodic, Periodic, Periodic|Bounded|Flat).
+for x, y, z each regular or (Bounded) stretched; topologies (Periodic, Periodic, Periodic|Bounded|Flat).
 """
 import ctypes as C
 import math
@@ -103,11 +103,21 @@ class _JuliaRange:
         return hi + (lo + (u * self.step_lo + self.ref_lo))
 
 
+def require_regular_xy(grid, who):
+    """What time-steps a grid (tendency kernels, halo fills with boundary fluxes, drivers) reads a regular x and y from ocn_grid:
+    refuse a grid stretched in x or y before anything is allocated (only the Poisson solvers run on such grids)."""
+    dims = [d for d in getattr(grid, "stretched_dimensions", ()) if d < 2]
+    if dims:
+        raise NotImplementedError(f"{who} on a grid stretched in {' and '.join('xy'[d] for d in dims)}: time stepping needs a regular x and y "
+                                  "(only the Poisson solvers support stretched x / y)")
+
+
 class RectilinearGrid:
     """RectilinearGrid(arch; size, x, y, z, topology, halo).
 
-    `size`/`halo` omit Flat dimensions like the reference (input_validation.jl:61-95).  `z` may be a
-    2-tuple (regular) or an array of Nz+1 increasing face positions (stretched, needs Bounded z)."""
+    `size`/`halo` omit Flat dimensions like the reference (input_validation.jl:61-95).  `x`, `y`, `z` may each be a
+    2-tuple (regular), an array of N+1 increasing face positions or a function of the face index (stretched, needs that
+    direction Bounded).  Only the Poisson solvers run on a grid stretched in x or y; the models need a regular x and y."""
 
     def __init__(self, architecture, size, x=None, y=None, z=None, topology=(Periodic, Periodic, Bounded), halo=None,
                  extent=None, _local=False):
@@ -124,6 +134,8 @@ class RectilinearGrid:
             y = None if Ls[1] is None else (0.0, Ls[1])
             z = None if Ls[2] is None else (-Ls[2], 0.0)
         if hasattr(architecture, "partition") and not _local:
+            if any(callable(e) or (e is not None and np.ndim(e) == 1 and len(e) != 2) for e in (x, y)):
+                raise NotImplementedError("a Distributed grid stretched in x or y: the distributed solvers need a regular x and y")
             # RectilinearGrid(arch::Distributed, ...) returns the rank-local grid (distributed_grids.jl:75-118)
             from .distributed import distributed_rectilinear_grid
             g = distributed_rectilinear_grid(architecture, tuple(size), x=x, y=y, z=z, topology=tuple(topology), halo=halo)
@@ -160,8 +172,8 @@ class RectilinearGrid:
         self.Hx, self.Hy, self.Hz = H
         ext = [x, y, z]
         L, D = [1.0] * 3, [1.0] * 3
-        self.z_faces = None
-        self._dzc_host = self._dzf_host = None
+        self.x_faces = self.y_faces = self.z_faces = None
+        self._dxc_host = self._dxf_host = self._dyc_host = self._dyf_host = self._dzc_host = self._dzf_host = None
         self._interval = [(0.0, 1.0)] * 3  # end points of each regular dimension (for node coordinates)
         self._ranges = {}
         for d in range(3):
@@ -181,31 +193,40 @@ class RectilinearGrid:
                 L[d] = float(Lx)                 # FT(L)
                 D[d] = float(Lx / N[d])          # FT(BigFloat(L)/N), grid_generation.jl:105-133
             else:
-                if d != 2:
-                    raise NotImplementedError("only the z direction may be stretched")
-                L[d] = self._generate_stretched_z(np.asarray(e, dtype=np.float64), N[d], H[d], topo[d])
+                L[d] = self._generate_stretched(d, np.asarray(e, dtype=np.float64), N[d], H[d], topo[d])
                 D[d] = float("nan")
         self.Lx, self.Ly, self.Lz = L
         self.dx, self.dy, self.dz = D
-        self._dzc = self._dzf = None
+        self._dxc = self._dxf = self._dyc = self._dyf = self._dzc = self._dzf = None
         dev = None if architecture is None else device(child_architecture(architecture))  # None: metadata only (tests)
-        if self._dzc_host is not None and dev is not None:
-            self._dzc = torch.from_numpy(self._dzc_host).to(dev)
-            self._dzf = torch.from_numpy(self._dzf_host).to(dev)
+        if dev is not None:
+            for n in ("x", "y", "z"):
+                if getattr(self, f"_d{n}c_host") is not None:
+                    setattr(self, f"_d{n}c", torch.from_numpy(getattr(self, f"_d{n}c_host")).to(dev))
+                    setattr(self, f"_d{n}f", torch.from_numpy(getattr(self, f"_d{n}f_host")).to(dev))
+        # (ocn_grid carries the stretched z only; a stretched x / y is 0.0 there and reaches the solvers through their own entry point)
         self.c = _lib.CGrid(self.Nx, self.Ny, self.Nz, self.Hx, self.Hy, self.Hz,
                             _CODE[topo[0]], _CODE[topo[1]], _CODE[topo[2]], 0,
-                            self.dx, self.dy, 0.0 if self._dzc is not None else self.dz, self.Lx, self.Ly, self.Lz,
+                            0.0 if self.x_faces is not None else self.dx, 0.0 if self.y_faces is not None else self.dy,
+                            0.0 if self._dzc is not None else self.dz, self.Lx, self.Ly, self.Lz,
                             None if self._dzc is None else self._dzc.data_ptr(),
                             None if self._dzf is None else self._dzf.data_ptr())
 
-    def _generate_stretched_z(self, faces, N, H, topo):
-        """generate_coordinate for explicit faces (grid_generation.jl:34-95)."""
+    @property
+    def stretched_dimensions(self):
+        """stretched_dimensions(grid): the dimensions (0 x, 1 y, 2 z) given as explicit faces"""
+        return tuple(d for d, F in enumerate((self.x_faces, self.y_faces, self.z_faces)) if F is not None)
+
+    def _generate_stretched(self, d, faces, N, H, topo):
+        """generate_coordinate for explicit faces (grid_generation.jl:34-95) of dimension d: faces with halos, Δᶜ and Δᶠ with element 0
+        <-> index 1 - H (the ocn_grid.dzc / dzf layout)."""
+        n = "xyz"[d]
         if topo != Bounded:
-            raise NotImplementedError("a stretched z direction must be Bounded")
+            raise NotImplementedError(f"a stretched {n} direction must be Bounded")
         if faces.shape != (N + 1,):
-            raise ValueError(f"z must hold Nz+1 = {N + 1} face positions")
+            raise ValueError(f"{n} must hold N{n}+1 = {N + 1} face positions")
         if not np.all(np.diff(faces) > 0):
-            raise ValueError("The elements of z must be increasing!")
+            raise ValueError(f"The elements of {n} must be increasing!")
         F = faces
         dlo = [F[1] - F[0]] * H
         dhi = [F[-1] - F[-2]] * H
@@ -217,10 +238,12 @@ class RectilinearGrid:
         d0 = list(Cc[1:] - Cc[:-1])
         dzc = Fall[1:] - Fall[:-1]                   # Δzᵃᵃᶜ[k], k = 1-H .. N+H
         dzf_full = np.array([d0[0], d0[0]] + d0)     # Δzᵃᵃᶠ[k], k = -H .. N+H (shifted copy, :72-75)
-        self.z_faces = Fall
-        self._dzc_host = np.ascontiguousarray(dzc[:N + 2 * H])
-        self._dzf_host = np.ascontiguousarray(dzf_full[1:])  # element 0 <-> k = 1-H
-        assert self._dzf_host.size == N + 2 * H and self._dzc_host.size == N + 2 * H
+        dc = np.ascontiguousarray(dzc[:N + 2 * H])
+        df = np.ascontiguousarray(dzf_full[1:])  # element 0 <-> k = 1-H
+        assert df.size == N + 2 * H and dc.size == N + 2 * H
+        setattr(self, f"{n}_faces", Fall)
+        setattr(self, f"_d{n}c_host", dc)
+        setattr(self, f"_d{n}f_host", df)
         return float(F[N] - F[0])
 
     # -- node coordinates: the elements of the reference's coordinate ranges (grid_generation.jl:98-135) --------------------------
@@ -254,8 +277,9 @@ class RectilinearGrid:
         if topo == Flat:
             return np.zeros(1)
         n = N + 1 if (face and topo in _EAST_FACE) else N
-        if d == 2 and self.z_faces is not None:
-            Fall = np.asarray(self.z_faces)
+        faces = (self.x_faces, self.y_faces, self.z_faces)[d]
+        if faces is not None:
+            Fall = np.asarray(faces)
             if with_halos:
                 return Fall.copy() if face else 0.5 * (Fall[1:] + Fall[:-1])
             F = Fall[H:H + N + 1]
@@ -269,16 +293,19 @@ class RectilinearGrid:
         """x_domain / y_domain / z_domain: (ξ[1], ξ[N+1]) of the Face coordinate (grid_utils.jl:120), what `show(grid)` prints"""
         N = (self.Nx, self.Ny, self.Nz)[d]
         H = (self.Hx, self.Hy, self.Hz)[d]
-        if d == 2 and self.z_faces is not None:
-            F = np.asarray(self.z_faces)
+        faces = (self.x_faces, self.y_faces, self.z_faces)[d]
+        if faces is not None:
+            F = np.asarray(faces)
             return float(F[H]), float(F[H + N])
         r = self._coordinate_range(d, True)
         return r[1 + H], r[N + 1 + H]
 
     def spacing_extrema(self, d, face=False):
         """(min, max) of the interior cell spacings along d: `min(Δz)=…, max(Δz)=…` of the reference's `show` (Center spacings)"""
-        if d == 2 and self._dzc_host is not None:
-            a = (self._dzf_host if face else self._dzc_host)[self.Hz:self.Hz + self.Nz + (1 if face else 0)]
+        n = "xyz"[d]
+        if getattr(self, f"_d{n}c_host") is not None:
+            H, N = (self.Hx, self.Hy, self.Hz)[d], (self.Nx, self.Ny, self.Nz)[d]
+            a = getattr(self, f"_d{n}f_host" if face else f"_d{n}c_host")[H:H + N + (1 if face else 0)]
             return float(a.min()), float(a.max())
         D = (self.dx, self.dy, self.dz)[d]
         return D, D

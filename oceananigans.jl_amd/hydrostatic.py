@@ -156,7 +156,8 @@ class HydrostaticFreeSurfaceModel:
         substep loop, one pass for the barotropic corrector + w, one halo launch, the hydrostatic pressure; the tendency evaluation
         that closes the reference's time_step! is deferred into the next step's fused launches (`flush_tendencies` completes it).
         fused = False keeps the reference's launch sequence.  Both are bit-identical in strict math."""
-        from .grids import FullyConnected
+        from .grids import FullyConnected, require_regular_xy
+        require_regular_xy(grid, "HydrostaticFreeSurfaceModel")
         timestepper = str(timestepper).lstrip(":")
         if timestepper not in ("QuasiAdamsBashforth2", "SplitRungeKutta3"):
             raise ValueError(f"timestepper must be :QuasiAdamsBashforth2 or :SplitRungeKutta3, got {timestepper!r}")

@@ -28,7 +28,7 @@ from .physics import (AnisotropicMinimumDissipation, BetaPlane, BuoyancyTracer, 
                       SeawaterBuoyancy)
 from .architectures import stream_ptr
 from .fields import CenterField, Field, XFaceField, YFaceField, ZFaceField, fill_halo_regions
-from .grids import Bounded, Flat
+from .grids import Bounded, Flat, require_regular_xy
 from .solvers import nonhydrostatic_pressure_solver
 
 
@@ -85,6 +85,7 @@ class NonhydrostaticModel:
                  hydrostatic_pressure_anomaly="default", pressure_solver="default", math_mode=None):
         """math_mode: None keeps the grid's (default: the process default, ocn.set_math_mode); MATH_STRICT / MATH_FAST pin this
         model's arithmetic variant whatever other models of the process use (ocn_grid.math)."""
+        require_regular_xy(grid, "NonhydrostaticModel")
         for name, val in (("forcing", forcing), ("stokes_drift", stokes_drift)):
             if val is not None:
                 raise NotImplementedError(f"{name} != nothing is outside the MI355X hot-path scope (see DESIGN.md)")
@@ -753,6 +754,7 @@ class RK3Driver:
     step's first fused launch; between time_step() and flush() the model's velocity fields are then NOT the corrected ones."""
 
     def __init__(self, model, own_solver=False, defer_correction=None):
+        require_regular_xy(model.grid, "RK3Driver")
         if model.tracers or model.general_terms:
             raise NotImplementedError("RK3Driver: WENO advection only (no tracers / extra terms)")
         if not isinstance(model.timestepper, RungeKutta3TimeStepper) or not isinstance(model.advection, WENO):
@@ -811,6 +813,7 @@ class ModelRK3Driver:
     array-valued boundary conditions (functions of time are refused)."""
 
     def __init__(self, model, own_solver=False):
+        require_regular_xy(model.grid, "ModelRK3Driver")
         if not isinstance(model.timestepper, RungeKutta3TimeStepper):
             raise NotImplementedError("ModelRK3Driver: RungeKutta3")
         xy_periodic = model.grid.topology[0] in ("Periodic", "FullyConnected") and model.grid.topology[1] == "Periodic"

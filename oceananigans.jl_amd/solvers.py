@@ -10,11 +10,46 @@ from .architectures import on_architecture, stream_ptr
 from .grids import Bounded, Flat, Periodic
 
 
+class XDirection:
+    """the tridiagonal direction of a BatchedTridiagonalSolver / FourierTridiagonalPoissonSolver (Solvers.jl)"""
+    dim = 0
+
+
+class YDirection:
+    dim = 1
+
+
+class ZDirection:
+    dim = 2
+
+
+def _direction_dim(direction):
+    d = getattr(direction, "dim", None)
+    if d not in (0, 1, 2):
+        raise ValueError(f"tridiagonal_direction must be XDirection(), YDirection() or ZDirection(), got {direction!r}")
+    return d
+
+
+def stretched_direction(grid):
+    """stretched_direction (fourier_tridiagonal_poisson_solver.jl:53-55): YZRegularRG -> XDirection, XZRegularRG -> YDirection, otherwise
+    ZDirection"""
+    dims = grid.stretched_dimensions
+    if len(dims) > 1:
+        raise NotImplementedError(f"a grid stretched in {' and '.join('xyz'[d] for d in dims)}: the Fourier-tridiagonal solver needs "
+                                  "two regular directions")
+    return (XDirection, YDirection, ZDirection)[dims[0] if dims else 2]()
+
+
 class _PoissonHandle:
-    def __init__(self, grid):
+    def __init__(self, grid, stretched_dim=None):
         self.grid = grid
         self._h = C.c_void_p()
-        _lib.call("ocn_poisson_create", C.byref(self._h), grid.cref)
+        if stretched_dim is None:
+            _lib.call("ocn_poisson_create", C.byref(self._h), grid.cref)
+        else:
+            n = "xy"[stretched_dim]
+            dc, df = getattr(grid, f"_d{n}c"), getattr(grid, f"_d{n}f")
+            _lib.call("ocn_poisson_create_stretched", C.byref(self._h), grid.cref, stretched_dim, dc.data_ptr(), df.data_ptr())
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -59,7 +94,7 @@ class FFTBasedPoissonSolver(_PoissonHandle):
     def __init__(self, grid, general=False):
         import os
         bounded_xy = Bounded in grid.topology[:2] or Flat in grid.topology[:2]  # (the library routes every non-Periodic x / y to the general solver)
-        if grid._dzc is not None:
+        if grid.stretched_dimensions:
             raise ValueError("FFTBasedPoissonSolver requires a regular grid")
         if grid.topology[2] == Bounded and not (bounded_xy or general):
             raise NotImplementedError("(Periodic, Periodic, Bounded): FourierTridiagonalPoissonSolver in this backend (an exact solver of the "
@@ -79,11 +114,19 @@ class FFTBasedPoissonSolver(_PoissonHandle):
 
 
 class FourierTridiagonalPoissonSolver(_PoissonHandle):
-    """src/Solvers/fourier_tridiagonal_poisson_solver.jl:82-147, tridiagonal direction z (Bounded, regular or stretched); x and y regular
-    with any topology (XYRegularRG): Periodic -> Fourier, Bounded -> cosine transforms, Flat -> none."""
+    """src/Solvers/fourier_tridiagonal_poisson_solver.jl:82-147.  The tridiagonal direction is the stretched one (stretched_direction):
+    z (Bounded, regular or stretched) with x and y regular (XYRegularRG), or a stretched Bounded x (YZRegularRG) / y (XZRegularRG) with the
+    other two regular; the regular directions are transformed with any topology: Periodic -> Fourier, Bounded -> cosine transforms,
+    Flat -> none."""
 
     def __init__(self, grid):
         import os
+        t = stretched_direction(grid).dim
+        if grid.topology[t] != Bounded:
+            raise ValueError("`FourierTridiagonalPoissonSolver` can only be used when the stretched direction's topology is `Bounded`.")
+        if t != 2:
+            super().__init__(grid, stretched_dim=t)
+            return
         if grid.topology[2] != Bounded:
             raise ValueError("`FourierTridiagonalPoissonSolver` can only be used when the stretched direction's topology is `Bounded`.")
         if (Bounded in grid.topology[:2] or Flat in grid.topology[:2]) and grid._dzc is None:
@@ -106,6 +149,8 @@ def nonhydrostatic_pressure_solver(grid):
     hook = getattr(grid.architecture, "pressure_solver", None)
     if hook is not None:
         return hook(grid)
+    if any(d < 2 for d in grid.stretched_dimensions):  # YZRegularRG / XZRegularRG: GridWithFourierTridiagonalSolver (Solvers.jl:51-52)
+        return FourierTridiagonalPoissonSolver(grid)
     if Bounded in grid.topology[:2] or Flat in grid.topology[:2]:
         if grid._dzc is not None:  # XYRegularRG with a stretched z: GridWithFourierTridiagonalSolver (Solvers.jl:51-52)
             return FourierTridiagonalPoissonSolver(grid)
@@ -116,27 +161,47 @@ def nonhydrostatic_pressure_solver(grid):
 
 
 class BatchedTridiagonalSolver:
-    """BatchedTridiagonalSolver(grid; lower_diagonal, diagonal, upper_diagonal), z direction
-    (src/Solvers/batched_tridiagonal_solver.jl:11-79).  a, c: (Nz-1,), b: [i,j,k] real."""
+    """BatchedTridiagonalSolver(grid; lower_diagonal, diagonal, upper_diagonal, tridiagonal_direction)
+    (src/Solvers/batched_tridiagonal_solver.jl:11-79).  a, c: (N-1,) along the tridiagonal direction (ZDirection by default); b: [i,j,k]
+    real, or 1-D (N,) along that direction -- the same diagonal for every line, broadcast on the host over the batch of the first rhs."""
 
-    def __init__(self, arch, lower_diagonal, diagonal, upper_diagonal):
-        b = np.asarray(diagonal, dtype=np.float64)
-        self.Nx, self.Ny, self.Nz = b.shape
+    def __init__(self, arch, lower_diagonal, diagonal, upper_diagonal, tridiagonal_direction=None):
+        self.dim = 2 if tridiagonal_direction is None else _direction_dim(tridiagonal_direction)
+        self.arch = arch
         self.a = on_architecture(arch, np.ascontiguousarray(lower_diagonal, dtype=np.float64))
         self.c = on_architecture(arch, np.ascontiguousarray(upper_diagonal, dtype=np.float64))
-        self.b = on_architecture(arch, np.ascontiguousarray(b.T))
+        b = np.asarray(diagonal, dtype=np.float64)
+        self._b1 = None
+        if b.ndim == 1:
+            self._b1 = b
+            self.b = self.t = None
+        else:
+            self._set_diagonal(b)
+
+    def _set_diagonal(self, b):
+        self.Nx, self.Ny, self.Nz = b.shape
+        n = b.shape[self.dim]
+        if self.a.numel() != n - 1 or self.c.numel() != n - 1:
+            raise ValueError(f"lower / upper diagonals must have {n - 1} elements along {'xyz'[self.dim]}")
+        self.b = on_architecture(self.arch, np.ascontiguousarray(b.T))
         self.t = torch.zeros_like(self.b)
-        self.arch = arch
 
     def solve(self, rhs, phi0=None):
         """solve!(ϕ, solver, rhs): rhs complex [i,j,k]; returns complex [i,j,k] (host)."""
-        f = np.ascontiguousarray(np.asarray(rhs, dtype=np.complex128).T)
+        rhs = np.asarray(rhs, dtype=np.complex128)
+        if self.b is None:
+            shape = [1, 1, 1]
+            shape[self.dim] = self._b1.size
+            self._set_diagonal(np.broadcast_to(self._b1.reshape(shape), rhs.shape))
+        if rhs.shape != (self.Nx, self.Ny, self.Nz):
+            raise ValueError(f"rhs shape {rhs.shape} != {(self.Nx, self.Ny, self.Nz)}")
+        f = np.ascontiguousarray(rhs.T)
         fd = on_architecture(self.arch, f.view(np.float64))
         if phi0 is None:
             phi = torch.zeros_like(fd)
         else:
             phi = on_architecture(self.arch, np.ascontiguousarray(np.asarray(phi0, dtype=np.complex128).T).view(np.float64))
-        _lib.call("ocn_batched_tridiagonal_solve_z", self.Nx, self.Ny, self.Nz, self.a.data_ptr(), self.b.data_ptr(),
+        _lib.call("ocn_batched_tridiagonal_solve_" + "xyz"[self.dim], self.Nx, self.Ny, self.Nz, self.a.data_ptr(), self.b.data_ptr(),
                   self.c.data_ptr(), fd.data_ptr(), self.t.data_ptr(), phi.data_ptr(), stream_ptr())
         out = phi.cpu().numpy().view(np.complex128)
         return out.T
