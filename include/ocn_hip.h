@@ -171,6 +171,10 @@ int ocn_compute_momentum_tendencies_rk3_strips(const ocn_grid *grid, const doubl
                                                double *u_out, double *v_out, double *w_out, double dt, double gamma, double zeta,
                                                int32_t has_zeta, const double *p_correct, double dt_correct, double *strip_west,
                                                double *strip_east, int64_t field_doubles, void *stream);
+/* Which kernel a correction-on-load launch (p_correct != NULL) for this grid takes: *selected = 1 for the one with 32-bit buffer offsets
+ * (every field's parent array below 2^31 bytes, halos of at least 3, OCN_TEND_ADDR32 not 0), 0 for the one with 64-bit addresses.
+ * Host only: no device memory is touched. */
+int ocn_momentum_tendencies_addr32(const ocn_grid *grid, int32_t *selected);
 /* compute_Gc! (compute_nonhydrostatic_tendencies.jl:186-195; tracer_tendency :228-259) */
 int ocn_compute_tracer_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w,
                                 const double *c, double *Gc, const int32_t *range, void *stream);

@@ -291,6 +291,13 @@ int ocn_compute_momentum_tendencies_rk3_strips(const ocn_grid *grid, const doubl
     return ocn_fast::launch_momentum_tendencies(grid, u, v, w, Gu, Gv, Gw, nullptr, &fz, as_stream(stream));
 }
 
+int ocn_momentum_tendencies_addr32(const ocn_grid *grid, int32_t *selected)
+{
+    OCN_REQUIRE(grid && selected, "ocn_momentum_tendencies_addr32: null argument");
+    *selected = (tendency_addr32_enabled() && tendency_addr32_fits(*grid)) ? 1 : 0;
+    return OCN_SUCCESS;
+}
+
 int ocn_cell_advection_timescale(const ocn_grid *grid, const double *u, const double *v, const double *w, double *result_device,
                                  void *stream)
 {

@@ -6,6 +6,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 
 #include "../../include/ocn_hip.h"
 
@@ -39,6 +40,20 @@ struct GridDev {
     // slab of a grid whose partitioned x is Bounded; tx is OCN_BOUNDED for all three (kernels that never meet an x wall ignore these)
     int xw, xe;
 };
+
+// The correction-on-load tendency kernel addresses every field with 32-bit byte offsets (momentum_tendencies_pc32): usable when the
+// parent array of a (Periodic | FullyConnected, Periodic, Periodic) field -- the one layout of u, v, w, p and G there -- spans fewer than
+// 2^31 bytes and the halos hold the full WENO stencil.  OCN_TEND_ADDR32=0 keeps the 64-bit kernel (same-box A/B runs).
+inline bool tendency_addr32_fits(const ocn_grid &g)
+{
+    const long long bytes = 8LL * (g.Nx + 2LL * g.Hx) * (g.Ny + 2LL * g.Hy) * (g.Nz + 2LL * g.Hz);
+    return g.Hx >= 3 && g.Hy >= 3 && g.Hz >= 3 && bytes < (1LL << 31);
+}
+inline bool tendency_addr32_enabled()
+{
+    static const bool on = !(getenv("OCN_TEND_ADDR32") && atoi(getenv("OCN_TEND_ADDR32")) == 0);
+    return on;
+}
 
 // x walls of a host-side grid description
 inline bool x_wall_west(const ocn_grid &g) { return g.tx == OCN_BOUNDED || g.tx == OCN_RIGHT_CONNECTED; }

@@ -36,10 +36,10 @@ struct Range {
 // stencil rings (a 32 x 8 patch reads 37 x 13 cells), so with the plain mapping every ring is fetched by up to 8 different L2s.
 // With r.xcd set, hardware workgroup b (XCD b % 8) takes the logical tile start_{b % 8} + b / 8: every XCD walks its own contiguous
 // range of tiles in x-fastest order and finds its neighbours' rings in its own L2.  A bijection for any grid size.
-__device__ __forceinline__ void block_coords(const Range &r, int &bx, int &by, int &bz)
+__device__ __forceinline__ void block_coords(int xcd, int &bx, int &by, int &bz)
 {
     bx = blockIdx.x; by = blockIdx.y; bz = blockIdx.z;
-    if (!r.xcd) return;
+    if (!xcd) return;
     const unsigned nx = gridDim.x, ny = gridDim.y, n = nx * ny * gridDim.z;
     const unsigned b = bx + nx * (by + ny * bz);
     const unsigned q = b & 7u, chunk = n >> 3, rem = n & 7u;
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(TX *TY, W) void momentum_tendencies_tiled(GridDev g
     const int Nx = g.Nx, Ny = g.Ny, Nz = g.Nz;
     const int tid = threadIdx.x, tx = tid % TX, ty = tid / TX;
     int bx, by, bz;
-    block_coords(r, bx, by, bz);
+    block_coords(r.xcd, bx, by, bz);
     const int ti0 = r.i0 + bx * (TX - 1), tj0 = r.j0 + by * (TY - 1);
     const int k_start = r.k0 + bz * KZ;
     const int k_end = min(k_start + KZ - 1, r.k1);
@@ -609,6 +609,339 @@ __global__ __launch_bounds__(TX *TY, W) void momentum_tendencies_tiled(GridDev g
 #undef OCN_STRIP
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The correction-on-load kernel of a periodic box or slab (momentum_tendencies_tiled<Periodic, TX, TY, W, PC, OB>, no strips, no acc) with
+// 32-bit addressing.  Under PC every field -- u, v, w, p, G, G⁻ and the stepped velocities -- has the one parent layout, so a lane's
+// address is   field base (scalar) + column (32-bit lane offset, loop invariant) + plane (wave-uniform, SALU once per plane)
+// and the plane loop does no 64-bit address arithmetic.  u, v, w and p go through buffer descriptors (voffset = column, soffset = plane);
+// the once-per-plane streams of the epilogue (G, G⁻, U_out) through global accesses with a scalar base (plane start) and the 32-bit column
+// offset -- nine more descriptors do not fit the scalar file next to the plane offsets (they spilled into VGPR lanes: a v_readlane per
+// use), nine base pairs do.  The arguments carry only what the kernel reads, with every loop invariant derived on the host.  The
+// arithmetic is the tiled kernel's expression for expression (strict: bit-identical to the oracle; fast: bitwise equal to the tiled kernel).
+// Valid while every field's byte extent is below 2^31 (ocn::tendency_addr32_fits); the host keeps the 64-bit kernel otherwise.
+// ---------------------------------------------------------------------------------------------------
+struct PcArgs {
+    const double *u, *v, *w, *p;
+    double *G[3];
+    const double *Gm[3];
+    double *Uo[3];
+    int bytes;               // byte extent of one field (every field has this layout)
+    int Nx, Ny, Nz, Hx, Hy, Hz;
+    int s2, s3;              // element strides of j and k
+    int KZ, xcd, xhalo;
+    double hx, hy, hz;       // strict: dx, dy, dz; fast: pc_dt / dx, pc_dt / dy, pc_dt / dz
+    double pcdt;             // the previous stage's dt (strict expression)
+    double dt, gamma, zeta, dtg;  // the substep (always fused here): dt (gamma G + zeta G⁻) with Z, (dt gamma) G = dtg G without
+    double ax, ay, az, V;    // Ax = dy dz, Ay = dx dz, Az = dx dy, V = Az dz (its reciprocal is taken on the device, as in the tiled kernel)
+};
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t field_rsrc(const double *p, int bytes)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(p), (short)0, bytes, 0x00020000);
+}
+__device__ __forceinline__ double bload(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff)
+{
+    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
+}
+__device__ __forceinline__ void bstore(double x, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff)
+{
+    using B = decltype(__builtin_amdgcn_raw_buffer_load_b64(r, 0u, 0u, 0));
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(B, x), r, voff, soff, 0);
+}
+// the epilogue's streams: global access with a scalar base (the plane's start, SALU) and the 32-bit lane offset (saddr form)
+// (the empty asm keeps the plane pointer opaque in SGPRs: otherwise the compiler hoists base + lane offset out of the loop as a 64-bit VGPR
+// pair per stream and adds the plane to it with VALU)
+template <class T>
+__device__ __forceinline__ T *plane_of(T *f, unsigned soff)
+{
+    auto *p = reinterpret_cast<T *>(reinterpret_cast<char *>(const_cast<double *>(f)) + soff);
+    asm volatile("" : "+s"(p));
+    return p;
+}
+typedef __attribute__((address_space(1))) char gchar;
+__device__ __forceinline__ double gload(const double *plane, unsigned voff)
+{
+    asm volatile("" : "+v"(voff));
+    return *reinterpret_cast<const __attribute__((address_space(1))) double *>((const gchar *)plane + voff);
+}
+__device__ __forceinline__ void gstore(double x, double *plane, unsigned voff)
+{
+    asm volatile("" : "+v"(voff));
+    *reinterpret_cast<__attribute__((address_space(1))) double *>((gchar *)plane + voff) = x;
+}
+
+// U + increment with the increment rounded on its own: the tiled kernel selects its increment at run time (has_zeta), which keeps the
+// compiler from contracting this sum into an FMA; the same rounding here keeps the two kernels bitwise equal in fast math (the empty
+// asm hides the product from the contraction, which -ffp-contract=fast applies regardless of a pragma)
+__device__ __forceinline__ double substep(double U, double inc)
+{
+    asm volatile("" : "+v"(inc));
+    return U + inc;
+}
+
+template <int TX, int TY, int W, bool Z>
+__global__ __launch_bounds__(TX *TY, W) void momentum_tendencies_pc32(PcArgs a)
+{
+    constexpr int P = OCN_PERIODIC;
+    constexpr int LX = TX + 5, LY = TY + 5, NT = TX * TY;
+    constexpr int LXP = LX + (TX == 17 ? OCN_NARROW_PAD : 0);
+    constexpr int NRING = LX * LY - NT;
+    constexpr int RPT = (NRING + NT - 1) / NT;
+    static_assert(RPT <= 2, "tile too small for its ring");
+    // one barrier per plane (the tiled kernel's OB): planes k, k+1 of u, v and k, k+1, k+2 of w resident, flux exchange double-buffered
+    __shared__ double su_[2][LY][LXP], sv_[2][LY][LXP], sw[3][LY][LXP];
+    __shared__ double ex_[2][6][NT];
+    auto uvslot = [](int kk) { return kk & 1; };
+    auto wslot = [](int kk) { return kk % 3; };
+
+    const int Nx = a.Nx, Ny = a.Ny, Nz = a.Nz;
+    const int tid = threadIdx.x, tx = tid % TX, ty = tid / TX;
+    int bx, by, bz;
+    block_coords(a.xcd, bx, by, bz);
+    const int ti0 = 1 + bx * (TX - 1), tj0 = 1 + by * (TY - 1);
+    const int k_start = 1 + bz * a.KZ;
+    const int k_end = min(k_start + a.KZ - 1, Nz);
+    const int imax = Nx + a.Hx, jmax = Ny + a.Hy;
+    const int i = min(ti0 + tx, imax), j = min(tj0 + ty, jmax);
+    const bool writes = (tx < TX - 1) && (ty < TY - 1) && (ti0 + tx <= Nx) && (tj0 + ty <= Ny);
+    const int lx = tx + 3, ly = ty + 3;
+
+    // byte offsets: col = a parent column (plane 0), pl = a parent plane; both non-negative and below a.bytes
+    auto col = [&](int ii, int jj) { return 8u * (unsigned)((ii - 1 + a.Hx) + a.s2 * (jj - 1 + a.Hy)); };
+    auto pl = [&](int kk) { return (unsigned)(kk - 1 + a.Hz) * (8u * (unsigned)a.s3); };
+    auto wrp = [](int q, int N) { return q < 1 ? q + N : (q > N ? q - N : q); };
+    const bool xhalo = a.xhalo;
+    auto wrx = [&](int q) { return xhalo ? q : (q < 1 ? q + Nx : (q > Nx ? q - Nx : q)); };
+    auto zz = [&](int kk) { return pl(wrp(kk, Nz)); };  // plane of p: z wraps
+    const __amdgpu_buffer_rsrc_t ru = field_rsrc(a.u, a.bytes), rv = field_rsrc(a.v, a.bytes), rw = field_rsrc(a.w, a.bytes),
+                                 rp = field_rsrc(a.p, a.bytes);
+    const unsigned own = col(i, j);
+    const unsigned oC = col(wrx(i), wrp(j, Ny)), oW = col(wrx(i - 1), wrp(j, Ny)), oS = col(wrx(i), wrp(j - 1, Ny));
+
+    const double pcdt = a.pcdt, hx = a.hx, hy = a.hy, hz = a.hz;
+    (void)pcdt;
+#if OCN_STRICT
+#define OCN_PC_APPLY(raw, d, h) ((raw) - ((d) / (h)) * pcdt)
+#else
+#define OCN_PC_APPLY(raw, d, h) __builtin_fma(-(d), h, raw)
+#endif
+    auto own_u = [&](int kk) { return OCN_PC_APPLY(bload(ru, own, pl(kk)), bload(rp, oC, zz(kk)) - bload(rp, oW, zz(kk)), hx); };
+    auto own_v = [&](int kk) { return OCN_PC_APPLY(bload(rv, own, pl(kk)), bload(rp, oC, zz(kk)) - bload(rp, oS, zz(kk)), hy); };
+    auto own_w = [&](int kk) { return OCN_PC_APPLY(bload(rw, own, pl(kk)), bload(rp, oC, zz(kk)) - bload(rp, oC, zz(kk - 1)), hz); };
+
+    // static ring assignment (as in momentum_tendencies_tiled)
+    int rcx[RPT], rcy[RPT];
+    bool ron[RPT];
+    unsigned roff[RPT], rpc[RPT], rpw[RPT], rps[RPT];
+#pragma unroll
+    for (int s = 0; s < RPT; ++s) {
+        const int q = tid + s * NT;
+        ron[s] = q < NRING;
+        int cx, cy;
+        if (q < 3 * LX) {
+            cx = q % LX; cy = q / LX;
+        } else if (q < 5 * LX) {
+            cx = (q - 3 * LX) % LX; cy = 3 + TY + (q - 3 * LX) / LX;
+        } else {
+            const int t = q - 5 * LX, c = t % 5;
+            cy = 3 + t / 5;
+            cx = c < 3 ? c : TX + c;
+        }
+        if (!ron[s]) { cx = 0; cy = 0; }
+        rcx[s] = cx; rcy[s] = cy;
+        const int gi = min(ti0 - 3 + cx, imax), gj = min(tj0 - 3 + cy, jmax);
+        roff[s] = col(gi, gj);
+        rpc[s] = col(wrx(gi), wrp(gj, Ny));
+        // the westmost halo column of u on a slab (gi = 1 - Hx) was corrected by its owner (p[-Hx] is not here): zero gradient
+        rpw[s] = (xhalo && gi - 1 < 1 - a.Hx) ? rpc[s] : col(wrx(gi - 1), wrp(gj, Ny));
+        rps[s] = col(wrx(gi), wrp(gj - 1, Ny));
+    }
+    auto ring_u = [&](int s, int kk) { return OCN_PC_APPLY(bload(ru, roff[s], pl(kk)), bload(rp, rpc[s], zz(kk)) - bload(rp, rpw[s], zz(kk)), hx); };
+    auto ring_v = [&](int s, int kk) { return OCN_PC_APPLY(bload(rv, roff[s], pl(kk)), bload(rp, rpc[s], zz(kk)) - bload(rp, rps[s], zz(kk)), hy); };
+    auto ring_w = [&](int s, int kk) {
+        return OCN_PC_APPLY(bload(rw, roff[s], pl(kk)), bload(rp, rpc[s], zz(kk)) - bload(rp, rpc[s], zz(kk - 1)), hz);
+    };
+
+    double zu[6], zv[6], zw[6];
+    int k = k_start;
+#pragma unroll
+    for (int m = 0; m < 6; ++m) {
+        zu[m] = own_u(k - 2 + m);
+        zv[m] = own_v(k - 2 + m);
+        zw[m] = own_w(k - 2 + m);
+    }
+    double fwu_bot, fwv_bot, fww_prev;
+    double nu[RPT], nv[RPT], nw[RPT];
+    double pc_prev, rp_prev[RPT] = {};
+    {
+        sw[wslot(k)][ly][lx] = zw[2];
+        su_[uvslot(k)][ly][lx] = zu[2];
+        sv_[uvslot(k)][ly][lx] = zv[2];
+        sw[wslot(k + 1)][ly][lx] = zw[3];
+#pragma unroll
+        for (int s = 0; s < RPT; ++s)
+            if (ron[s]) {
+                sw[wslot(k)][rcy[s]][rcx[s]] = ring_w(s, k);
+                su_[uvslot(k)][rcy[s]][rcx[s]] = ring_u(s, k);
+                sv_[uvslot(k)][rcy[s]][rcx[s]] = ring_v(s, k);
+                sw[wslot(k + 1)][rcy[s]][rcx[s]] = ring_w(s, k + 1);
+            }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < RPT; ++s) nu[s] = nv[s] = nw[s] = 0.0;
+        pc_prev = bload(rp, oC, zz(k + 3));
+#pragma unroll
+        for (int s = 0; s < RPT; ++s) rp_prev[s] = ron[s] ? bload(rp, rpc[s], zz(k + 1)) : 0.0;
+        const double um3 = own_u(k - 3), vm3 = own_v(k - 3), wm3 = own_w(k - 3);
+        const double(*swk)[LXP] = sw[wslot(k)];
+        const double az = a.az;
+        {   // Fwu(k): sym x-face of Az*w at plane k ; biased z-face of u
+            const double wt = sym_interp_scaled<P, false>([&](int m) { return swk[ly][lx + m]; }, az, i, Nx);
+            const double S[6] = {um3, zu[0], zu[1], zu[2], zu[3], zu[4]};
+            fwu_bot = wt * bias_interp<P, false>([&](int m) { return S[m + 3]; }, k, Nz, wt > 0);
+        }
+        {   // Fwv(k): sym y-face of Az*w ; biased z-face of v
+            const double wt = sym_interp_scaled<P, false>([&](int m) { return swk[ly + m][lx]; }, az, j, Ny);
+            const double S[6] = {vm3, zv[0], zv[1], zv[2], zv[3], zv[4]};
+            fwv_bot = wt * bias_interp<P, false>([&](int m) { return S[m + 3]; }, k, Nz, wt > 0);
+        }
+        {   // Fww(k-1): sym/biased z-centre of w at centre k-1 (line shifted to face k): w[k-3..k+2]
+            const double S[6] = {wm3, zw[0], zw[1], zw[2], zw[3], zw[4]};
+            const double wt = sym_interp_scaled<P, true>([&](int m) { return S[m + 3]; }, az, k - 1, Nz);
+            fww_prev = wt * bias_interp<P, true>([&](int m) { return S[m + 3]; }, k - 1, Nz, wt > 0);
+        }
+    }
+    const double rV = recip_volume(a.V);  // (rVc = rVf: a Periodic z is never stretched)
+    // the face areas live in vector registers: the scalar file holds the descriptors, the plane bases and the plane offsets (in scalar
+    // registers as well, the substep's coefficients push it over its budget: spills into VGPR lanes, a v_readlane each per plane)
+    double ax_ = a.ax, ay_ = a.ay, az_ = a.az;
+    asm volatile("" : "+v"(ax_), "+v"(ay_), "+v"(az_));
+
+    for (; k <= k_end; ++k) {
+        double(*su)[LXP] = su_[uvslot(k)];
+        double(*sv)[LXP] = sv_[uvslot(k)];
+        double(*ex)[NT] = ex_[uvslot(k)];
+        // ---- prefetch the next plane's corrected values, re-using last plane's pressure values (6 p loads instead of 8)
+        double zu_n, zv_n, zw_n;
+        if (k < k_end) {
+            const unsigned o4 = zz(k + 4), o1 = zz(k + 1), o2 = zz(k + 2), s4 = pl(k + 4);
+            const double pc4 = bload(rp, oC, o4), pw4 = bload(rp, oW, o4), ps4 = bload(rp, oS, o4);
+            zu_n = OCN_PC_APPLY(bload(ru, own, s4), pc4 - pw4, hx);
+            zv_n = OCN_PC_APPLY(bload(rv, own, s4), pc4 - ps4, hy);
+            zw_n = OCN_PC_APPLY(bload(rw, own, s4), pc4 - pc_prev, hz);
+            pc_prev = pc4;
+#pragma unroll
+            for (int s = 0; s < RPT; ++s)
+                if (ron[s]) {
+                    const double pr1 = rp_prev[s], pr2 = bload(rp, rpc[s], o2);
+                    nu[s] = OCN_PC_APPLY(bload(ru, roff[s], pl(k + 1)), pr1 - bload(rp, rpw[s], o1), hx);
+                    nv[s] = OCN_PC_APPLY(bload(rv, roff[s], pl(k + 1)), pr1 - bload(rp, rps[s], o1), hy);
+                    nw[s] = OCN_PC_APPLY(bload(rw, roff[s], pl(k + 2)), pr2 - pr1, hz);
+                    rp_prev[s] = pr2;
+                }
+        }
+        const unsigned sk = pl(k);
+        double gmu, gmv, gmw;
+        if (Z && writes) {
+            gmu = gload(plane_of(a.Gm[0], sk), own);
+            gmv = gload(plane_of(a.Gm[1], sk), own);
+            gmw = gload(plane_of(a.Gm[2], sk), own);
+        }
+        const double(*swk)[LXP] = sw[wslot(k)];
+        const double(*swt)[LXP] = sw[wslot(k + 1)];
+        const double ax = ax_, ay = ay_, az = az_;
+
+        // (this thread's own fluxes come back from LDS: each read pairs with the neighbour's into one ds_read2_b64)
+        {   // Fuu(i-1)
+            const double ut = sym_interp_scaled<P, true>([&](int m) { return su[ly][lx + m]; }, ax, i - 1, Nx);
+#if OCN_LDS_SELECT == 2
+            const double f = ut * bias_interp<P, true>([&](int m) { return su[ly][lx + m]; }, i - 1, Nx, ut > 0);
+#else
+            const double f = ut * bias_interp_lds(&su[ly][lx], 1, ut > 0);
+#endif
+            ex[0][tid] = f;
+        }
+        {   // Fuv(i)
+            const double ut = sym_interp_scaled<P, false>([&](int m) { return su[ly + m][lx]; }, ax, j, Ny);
+            ex[1][tid] = ut * bias_interp_lds(&sv[ly][lx], 1, ut > 0);
+        }
+        {   // Fuw(i)
+            const double ut = sym_interp_scaled<P, false>([&](int m) { return zu[2 + m]; }, ax, k, Nz);
+            ex[2][tid] = ut * bias_interp_lds(&swk[ly][lx], 1, ut > 0);
+        }
+        {   // Fvv(j-1)
+            const double vt = sym_interp_scaled<P, true>([&](int m) { return sv[ly + m][lx]; }, ay, j - 1, Ny);
+#if OCN_LDS_SELECT == 2
+            const double f = vt * bias_interp<P, true>([&](int m) { return sv[ly + m][lx]; }, j - 1, Ny, vt > 0);
+#else
+            const double f = vt * bias_interp_lds(&sv[ly][lx], LXP, vt > 0);
+#endif
+            ex[3][tid] = f;
+        }
+        {   // Fvu(j)
+            const double vt = sym_interp_scaled<P, false>([&](int m) { return sv[ly][lx + m]; }, ay, i, Nx);
+            ex[4][tid] = vt * bias_interp_lds(&su[ly][lx], LXP, vt > 0);
+        }
+        {   // Fvw(j)
+            const double vt = sym_interp_scaled<P, false>([&](int m) { return zv[2 + m]; }, ay, k, Nz);
+            ex[5][tid] = vt * bias_interp_lds(&swk[ly][lx], LXP, vt > 0);
+        }
+        double fwu_top, fwv_top, fww;
+        {
+            const double wt = sym_interp_scaled<P, false>([&](int m) { return swt[ly][lx + m]; }, az, i, Nx);
+            fwu_top = wt * bias_interp<P, false>([&](int m) { return zu[3 + m]; }, k + 1, Nz, wt > 0);
+        }
+        {
+            const double wt = sym_interp_scaled<P, false>([&](int m) { return swt[ly + m][lx]; }, az, j, Ny);
+            fwv_top = wt * bias_interp<P, false>([&](int m) { return zv[3 + m]; }, k + 1, Nz, wt > 0);
+        }
+        {
+            const double wt = sym_interp_scaled<P, true>([&](int m) { return zw[3 + m]; }, az, k, Nz);
+            fww = wt * bias_interp<P, true>([&](int m) { return zw[3 + m]; }, k, Nz, wt > 0);
+        }
+        if (k < k_end) {  // stage plane k+1 of u, v and plane k+2 of w: their slots were last read before the previous barrier
+            su_[uvslot(k + 1)][ly][lx] = zu[3];
+            sv_[uvslot(k + 1)][ly][lx] = zv[3];
+            sw[wslot(k + 2)][ly][lx] = zw[4];
+#pragma unroll
+            for (int s = 0; s < RPT; ++s)
+                if (ron[s]) {
+                    su_[uvslot(k + 1)][rcy[s]][rcx[s]] = nu[s];
+                    sv_[uvslot(k + 1)][rcy[s]][rcx[s]] = nv[s];
+                    sw[wslot(k + 2)][rcy[s]][rcx[s]] = nw[s];
+                }
+        }
+        __syncthreads();
+        if (writes) {
+            const int e = tid + 1, n = tid + TX;
+            {
+                double G = -(rV * (((ex[0][e] - ex[0][tid]) + (ex[4][n] - ex[4][tid])) + (fwu_top - fwu_bot)));
+                gstore(G, plane_of(a.G[0], sk), own);
+                gstore(substep(zu[2], Z ? a.dt * (a.gamma * G + a.zeta * gmu) : a.dtg * G), plane_of(a.Uo[0], sk), own);
+            }
+            {
+                double G = -(rV * (((ex[1][e] - ex[1][tid]) + (ex[3][n] - ex[3][tid])) + (fwv_top - fwv_bot)));
+                gstore(G, plane_of(a.G[1], sk), own);
+                gstore(substep(zv[2], Z ? a.dt * (a.gamma * G + a.zeta * gmv) : a.dtg * G), plane_of(a.Uo[1], sk), own);
+            }
+            {
+                double G = -(rV * (((ex[2][e] - ex[2][tid]) + (ex[5][n] - ex[5][tid])) + (fww - fww_prev)));
+                gstore(G, plane_of(a.G[2], sk), own);
+                gstore(substep(zw[2], Z ? a.dt * (a.gamma * G + a.zeta * gmw) : a.dtg * G), plane_of(a.Uo[2], sk), own);
+            }
+        }
+        fwu_bot = fwu_top; fwv_bot = fwv_top; fww_prev = fww;
+#pragma unroll
+        for (int m = 0; m < 5; ++m) {
+            zu[m] = zu[m + 1];
+            zv[m] = zv[m + 1];
+            zw[m] = zw[m + 1];
+        }
+        if (k < k_end) { zu[5] = zu_n; zv[5] = zv_n; zw[5] = zw_n; }
+    }
+#undef OCN_PC_APPLY
+}
+
 // K4 tracer: flux = (A * U[i,j,k]) * cR   (upwind_biased_advective_fluxes.jl:99-121)
 template <int TB>
 __device__ __forceinline__ double tracer_flux(double area, double ut, const double *__restrict__ pc, long long sc, int idx,
@@ -734,7 +1067,7 @@ __global__ __launch_bounds__(TX *TY, W) void tracer_tendency_tiled(GridDev g, co
     const int Nx = g.Nx, Ny = g.Ny, Nz = g.Nz;
     const int tid = threadIdx.x, tx = tid % TX, ty = tid / TX;
     int bx, by, bz;
-    block_coords(r, bx, by, bz);
+    block_coords(r.xcd, bx, by, bz);
     const int ti0 = r.i0 + bx * (TX - 1), tj0 = r.j0 + by * (TY - 1);
     const int k_start = r.k0 + bz * KZ, k_end = min(k_start + KZ - 1, r.k1);
     const int imax = Nx + g.Hx, jmax = Ny + g.Hy;
@@ -915,7 +1248,7 @@ __global__ __launch_bounds__(TX *TY) void tracer_pair_tendency_tiled(GridDev g, 
     const int Nx = g.Nx, Ny = g.Ny, Nz = g.Nz;
     const int tid = threadIdx.x, tx = tid % TX, ty = tid / TX;
     int bx, by, bz;
-    block_coords(r, bx, by, bz);
+    block_coords(r.xcd, bx, by, bz);
     const int ti0 = r.i0 + bx * (TX - 1), tj0 = r.j0 + by * (TY - 1);
     const int k_start = r.k0 + bz * KZ, k_end = min(k_start + KZ - 1, r.k1);
     const int imax = Nx + g.Hx, jmax = Ny + g.Hy;
@@ -1187,6 +1520,36 @@ static void launch_tiled(const GridDev &g, const double *u, const double *v, con
     hipLaunchKernelGGL((momentum_tendencies_tiled<TZ, TX, TY, 3, PC, OB, false, ST>), nbt, dim3(TX * TY), 0, stream, g, u, v, w, Gu, Gv, Gw, r, KZ, fz);
 }
 
+// the same launch (full range, periodic z, correction on load, one barrier) through momentum_tendencies_pc32 (ocn::tendency_addr32_fits)
+template <int TX, int TY>
+static void launch_pc32(const ocn_grid &grid, const double *u, const double *v, const double *w, double *Gu, double *Gv, double *Gw,
+                        const Range &r, const ocn::FuseArgs &fz, int wx, int wy, int wz, hipStream_t stream)
+{
+    const int tiles = ((wx + TX - 2) / (TX - 1)) * ((wy + TY - 2) / (TY - 1));
+    int KZ = wz;
+    while (KZ > 16 && tiles * ((wz + KZ - 1) / KZ) < min_blocks()) KZ = (KZ + 1) / 2;
+    dim3 nbt((wx + TX - 2) / (TX - 1), (wy + TY - 2) / (TY - 1), (wz + KZ - 1) / KZ);
+    PcArgs a;
+    a.u = u; a.v = v; a.w = w; a.p = fz.pc_p;
+    a.G[0] = Gu; a.G[1] = Gv; a.G[2] = Gw;
+    for (int q = 0; q < 3; ++q) { a.Gm[q] = fz.Gm[q]; a.Uo[q] = fz.Uo[q]; }
+    a.Nx = grid.Nx; a.Ny = grid.Ny; a.Nz = grid.Nz; a.Hx = grid.Hx; a.Hy = grid.Hy; a.Hz = grid.Hz;
+    a.s2 = grid.Nx + 2 * grid.Hx;
+    a.s3 = a.s2 * (grid.Ny + 2 * grid.Hy);
+    a.bytes = (int)(8LL * a.s3 * (grid.Nz + 2 * grid.Hz));
+    a.KZ = KZ; a.xcd = r.xcd; a.xhalo = fz.pc_xhalo;
+#if OCN_STRICT
+    a.hx = grid.dx; a.hy = grid.dy; a.hz = grid.dz;
+#else
+    a.hx = fz.pc_dt * (1.0 / grid.dx); a.hy = fz.pc_dt * (1.0 / grid.dy); a.hz = fz.pc_dt * (1.0 / grid.dz);
+#endif
+    a.pcdt = fz.pc_dt;
+    a.dt = fz.dt; a.gamma = fz.gamma; a.zeta = fz.zeta; a.dtg = fz.dt * fz.gamma;
+    a.az = grid.dx * grid.dy; a.ax = grid.dy * grid.dz; a.ay = grid.dx * grid.dz; a.V = a.az * grid.dz;
+    if (fz.has_zeta) hipLaunchKernelGGL((momentum_tendencies_pc32<TX, TY, 3, true>), nbt, dim3(TX * TY), 0, stream, a);
+    else hipLaunchKernelGGL((momentum_tendencies_pc32<TX, TY, 3, false>), nbt, dim3(TX * TY), 0, stream, a);
+}
+
 static int make_range(const ocn_grid *grid, const int32_t *range, Range &r)
 {
     r.xcd = xcd_remap();
@@ -1316,7 +1679,9 @@ int launch_momentum_tendencies(const ocn_grid *grid, const double *u, const doub
             // 17 x 15 patches (16 x 14 cells owned: 87.8 % of the lanes useful against 84.8 % of 32 x 8) also on full boxes: 24.42 against
             // 24.56 ms per 512^3 step, six same-box pairs (round 4; 16 x 16 patches: 24.9 - 25.4); OCN_PC_TILE=32 selects the 32 x 8 patches
             static const int pc_tile = getenv("OCN_PC_TILE") ? atoi(getenv("OCN_PC_TILE")) : 17;
-            if (narrow || pc_tile == 17)
+            if ((narrow || pc_tile == 17) && fz.on && !fz.acc && ocn::tendency_addr32_enabled() && ocn::tendency_addr32_fits(*grid))
+                launch_pc32<17, 15>(*grid, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
+            else if (narrow || pc_tile == 17)
                 launch_tiled<OCN_PERIODIC, 17, 15, true, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
             else if (one_barrier() & 1)
                 launch_tiled<OCN_PERIODIC, 32, 8, true, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
