@@ -17,7 +17,7 @@
 //
 // Compiled twice like tendencies.hip (namespaces via ocn_weno.h): strict / fast, WENO5 or UpwindBiased(order = 5).
 #include <algorithm>
-#include <cstring>
+#include <cstdlib>
 
 #include "ocn_weno.h"
 
@@ -570,18 +570,11 @@ static gen::GFrames frames_around(const ocn_grid *grid, const int32_t box[4], co
     }
     return F;
 }
-// launch `kernel(args..., F)` over the ranges of F -- or, OCN_GENERAL_FRAMES=separate, one launch per range as before round 4's last change
+// launch `kernel(args..., F)` over the ranges of F as one grid (nothing when F is empty)
 #define OCN_GEN_LAUNCH(kernel, F_, ...)                                                                                              \
     do {                                                                                                                             \
-        static const bool sep_ = [] { const char *e = getenv("OCN_GENERAL_FRAMES"); return e && !strcmp(e, "separate"); }();         \
-        if ((F_).n > 0 && !sep_) {                                                                                                   \
+        if ((F_).n > 0)                                                                                                              \
             hipLaunchKernelGGL(kernel, dim3((F_).first[(F_).n], (F_).r[0].k1 - (F_).r[0].k0 + 1), dim3(256), 0, stream, __VA_ARGS__, (F_)); \
-        } else {                                                                                                                     \
-            for (int f_ = 0; f_ < (F_).n; ++f_) {                                                                                    \
-                const gen::GFrames one_ = whole_range((F_).r[f_]);                                                                   \
-                hipLaunchKernelGGL(kernel, dim3(one_.first[1], one_.r[0].k1 - one_.r[0].k0 + 1), dim3(256), 0, stream, __VA_ARGS__, one_); \
-            }                                                                                                                        \
-        }                                                                                                                            \
     } while (0)
 
 // fin != NULL (a model without extra terms): the next substep rides on this launch -- the epilogue of the tiled kernel on the box, the

@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256) void momentum_tendencies_direct(GridDev g, con
 // box is at least a full stencil away from the walls, where the topology-conditional reconstructions are the Periodic ones.
 // ST ("strips"): the epilogue also writes the stepped velocities of the Hx westmost / eastmost columns into the send buffers of the next
 // x-halo exchange of a slab-x rank (FuseArgs::strip_w / strip_e): the exchange then needs no pack launch.
-template <int TZ, int TX, int TY, int W, bool PC, bool OB = false, bool GL = false, bool ST = false>
+template <int TZ, int TX, int TY, int W, bool PC, bool GL = false, bool ST = false>
 __global__ __launch_bounds__(TX *TY, W) void momentum_tendencies_tiled(GridDev g, const double *__restrict__ u,
                                                                        const double *__restrict__ v,
                                                                        const double *__restrict__ w, double *__restrict__ Gu,
@@ -199,8 +199,10 @@ __global__ __launch_bounds__(TX *TY, W) void momentum_tendencies_tiled(GridDev g
     constexpr int NRING = LX * LY - NT;         // ring cells of one tile
     constexpr int RPT = (NRING + NT - 1) / NT;  // ring cells per thread (1 or 2)
     static_assert(RPT <= 2, "tile too small for its ring");
-    // OB ("one barrier"): planes k and k+1 of u, v and k, k+1, k+2 of w are resident and the flux exchange is double-buffered, so the
-    // staging of the NEXT plane moves behind this plane's flux evaluation and shares its barrier with the flux exchange.
+    // OB ("one barrier", the correction-on-load variants): planes k and k+1 of u, v and k, k+1, k+2 of w are resident and the flux exchange
+    // is double-buffered, so the staging of the NEXT plane moves behind this plane's flux evaluation and shares its barrier with the flux
+    // exchange.
+    constexpr bool OB = PC;
     constexpr int NUV = OB ? 2 : 1, NW_ = OB ? 3 : 2, NEX = OB ? 2 : 1;
     __shared__ double su_[NUV][LY][LXP], sv_[NUV][LY][LXP], sw[NW_][LY][LXP];
     __shared__ double ex_[NEX][6][NT];  // Fuu_w, Fuv, Fuw (read by the west neighbour), Fvv_s, Fvu, Fvw (by the south one)
@@ -610,7 +612,7 @@ __global__ __launch_bounds__(TX *TY, W) void momentum_tendencies_tiled(GridDev g
 }
 
 // ---------------------------------------------------------------------------------------------------
-// The correction-on-load kernel of a periodic box or slab (momentum_tendencies_tiled<Periodic, TX, TY, W, PC, OB>, no strips, no acc) with
+// The correction-on-load kernel of a periodic box or slab (momentum_tendencies_tiled<Periodic, TX, TY, W, PC>, no strips, no acc) with
 // 32-bit addressing.  Under PC every field -- u, v, w, p, G, G⁻ and the stepped velocities -- has the one parent layout, so a lane's
 // address is   field base (scalar) + column (32-bit lane offset, loop invariant) + plane (wave-uniform, SALU once per plane)
 // and the plane loop does no 64-bit address arithmetic.  u, v, w and p go through buffer descriptors (voffset = column, soffset = plane);
@@ -1047,8 +1049,8 @@ __global__ __launch_bounds__(256) void tracer_tendency_direct(GridDev g, const d
 //  * thread (i, j) evaluates the west-face and south-face fluxes of its cell and the top-face flux; the east / north ones come
 //    from the neighbouring threads through LDS, the bottom one is last iteration's top flux.
 // 3 flux evaluations per thread and plane instead of 6; the flux expressions are those of the direct kernel (bit-identical).
-template <int TZ, int TX, int TY, int W = 1, bool GL = false>
-__global__ __launch_bounds__(TX *TY, W) void tracer_tendency_tiled(GridDev g, const double *__restrict__ u, const double *__restrict__ v,
+template <int TZ, int TX, int TY, bool GL = false>
+__global__ __launch_bounds__(TX *TY, 1) void tracer_tendency_tiled(GridDev g, const double *__restrict__ u, const double *__restrict__ v,
                                                                const double *__restrict__ w, const double *__restrict__ c,
                                                                double *__restrict__ Gc, Range r, int KZ, ocn::TracerFuse tf)
 {
@@ -1457,12 +1459,6 @@ int launch_pressure_planes(const ocn_grid *grid, double *p, double *u, double dt
     return OCN_SUCCESS;
 }
 
-static int tile_variant()
-{
-    const char *e = getenv("OCN_TILE");
-    return e ? atoi(e) : 0;
-}
-
 // z-chunking target: the launch should have at least this many workgroups (768 run concurrently: 256 CUs x 3)
 static int min_blocks()
 {
@@ -1475,15 +1471,6 @@ static int min_blocks()
 static int strip_min_kz()
 {
     static const int v = getenv("OCN_STRIP_MIN_KZ") ? atoi(getenv("OCN_STRIP_MIN_KZ")) : 8;
-    return v;
-}
-
-// One barrier per plane (template parameter OB of momentum_tendencies_tiled): bit 0 = the correction-on-load variant, bit 1 = the plain
-// Periodic-z one, bit 2 = Bounded z.  Measured on one box, 512^3 step: 27.21 ms without, 27.06 with bit 0, 27.33 with bit 1, 27.09 with
-// both; config 4 (bit 2) +0.45 ms.  The variant that waits for the most loads per plane is the one that gains from the missing barrier.
-static int one_barrier()
-{
-    static const int v = getenv("OCN_TEND_ONE_BARRIER") ? atoi(getenv("OCN_TEND_ONE_BARRIER")) : 1;
     return v;
 }
 
@@ -1509,26 +1496,35 @@ static bool narrow_tile(int wx, int wy)
     return lanes_per_column(17, 15, wx, wy) * 1.08 < lanes_per_column(32, 8, wx, wy);
 }
 
-template <int TZ, int TX, int TY, bool PC, bool OB, bool ST = false>
+// Workgroups of a TX x TY patch launch over wx x wy x wz cells (patches overlap by one column / row) and its z-chunk KZ: halved from the
+// full depth while the launch has fewer than min_wg workgroups and the chunk is longer than min_kz -- enough workgroups to fill the chip,
+// chunks long enough to amortise the prologue.  Full launches: min_blocks() and 16; the halo-wide strips: 2048 and strip_min_kz().
+struct PatchGrid {
+    dim3 blocks;
+    int KZ;
+};
+static PatchGrid patch_grid(int TX, int TY, int wx, int wy, int wz, int min_wg, int min_kz)
+{
+    const int nx = (wx + TX - 2) / (TX - 1), ny = (wy + TY - 2) / (TY - 1);
+    int KZ = wz;
+    while (KZ > min_kz && nx * ny * ((wz + KZ - 1) / KZ) < min_wg) KZ = (KZ + 1) / 2;
+    return {dim3(nx, ny, (wz + KZ - 1) / KZ), KZ};
+}
+
+template <int TZ, int TX, int TY, bool PC, bool GL = false, bool ST = false>
 static void launch_tiled(const GridDev &g, const double *u, const double *v, const double *w, double *Gu, double *Gv, double *Gw, const Range &r,
                          const ocn::FuseArgs &fz, int wx, int wy, int wz, hipStream_t stream)
 {
-    const int tiles = ((wx + TX - 2) / (TX - 1)) * ((wy + TY - 2) / (TY - 1));
-    int KZ = wz;  // z-chunk: enough workgroups to fill the chip, long enough to amortise the 3-flux prologue
-    while (KZ > 16 && tiles * ((wz + KZ - 1) / KZ) < min_blocks()) KZ = (KZ + 1) / 2;
-    dim3 nbt((wx + TX - 2) / (TX - 1), (wy + TY - 2) / (TY - 1), (wz + KZ - 1) / KZ);
-    hipLaunchKernelGGL((momentum_tendencies_tiled<TZ, TX, TY, 3, PC, OB, false, ST>), nbt, dim3(TX * TY), 0, stream, g, u, v, w, Gu, Gv, Gw, r, KZ, fz);
+    const PatchGrid pg = patch_grid(TX, TY, wx, wy, wz, min_blocks(), 16);
+    hipLaunchKernelGGL((momentum_tendencies_tiled<TZ, TX, TY, 3, PC, GL, ST>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, Gu, Gv, Gw, r, pg.KZ, fz);
 }
 
-// the same launch (full range, periodic z, correction on load, one barrier) through momentum_tendencies_pc32 (ocn::tendency_addr32_fits)
+// the same launch (full range, periodic z, correction on load) through momentum_tendencies_pc32 (ocn::tendency_addr32_fits)
 template <int TX, int TY>
 static void launch_pc32(const ocn_grid &grid, const double *u, const double *v, const double *w, double *Gu, double *Gv, double *Gw,
                         const Range &r, const ocn::FuseArgs &fz, int wx, int wy, int wz, hipStream_t stream)
 {
-    const int tiles = ((wx + TX - 2) / (TX - 1)) * ((wy + TY - 2) / (TY - 1));
-    int KZ = wz;
-    while (KZ > 16 && tiles * ((wz + KZ - 1) / KZ) < min_blocks()) KZ = (KZ + 1) / 2;
-    dim3 nbt((wx + TX - 2) / (TX - 1), (wy + TY - 2) / (TY - 1), (wz + KZ - 1) / KZ);
+    const PatchGrid pg = patch_grid(TX, TY, wx, wy, wz, min_blocks(), 16);
     PcArgs a;
     a.u = u; a.v = v; a.w = w; a.p = fz.pc_p;
     a.G[0] = Gu; a.G[1] = Gv; a.G[2] = Gw;
@@ -1537,7 +1533,7 @@ static void launch_pc32(const ocn_grid &grid, const double *u, const double *v, 
     a.s2 = grid.Nx + 2 * grid.Hx;
     a.s3 = a.s2 * (grid.Ny + 2 * grid.Hy);
     a.bytes = (int)(8LL * a.s3 * (grid.Nz + 2 * grid.Hz));
-    a.KZ = KZ; a.xcd = r.xcd; a.xhalo = fz.pc_xhalo;
+    a.KZ = pg.KZ; a.xcd = r.xcd; a.xhalo = fz.pc_xhalo;
 #if OCN_STRICT
     a.hx = grid.dx; a.hy = grid.dy; a.hz = grid.dz;
 #else
@@ -1546,8 +1542,8 @@ static void launch_pc32(const ocn_grid &grid, const double *u, const double *v, 
     a.pcdt = fz.pc_dt;
     a.dt = fz.dt; a.gamma = fz.gamma; a.zeta = fz.zeta; a.dtg = fz.dt * fz.gamma;
     a.az = grid.dx * grid.dy; a.ax = grid.dy * grid.dz; a.ay = grid.dx * grid.dz; a.V = a.az * grid.dz;
-    if (fz.has_zeta) hipLaunchKernelGGL((momentum_tendencies_pc32<TX, TY, 3, true>), nbt, dim3(TX * TY), 0, stream, a);
-    else hipLaunchKernelGGL((momentum_tendencies_pc32<TX, TY, 3, false>), nbt, dim3(TX * TY), 0, stream, a);
+    if (fz.has_zeta) hipLaunchKernelGGL((momentum_tendencies_pc32<TX, TY, 3, true>), pg.blocks, dim3(TX * TY), 0, stream, a);
+    else hipLaunchKernelGGL((momentum_tendencies_pc32<TX, TY, 3, false>), pg.blocks, dim3(TX * TY), 0, stream, a);
 }
 
 static int make_range(const ocn_grid *grid, const int32_t *range, Range &r)
@@ -1587,15 +1583,10 @@ int launch_momentum_tendencies_box(const ocn_grid *grid, const double *u, const 
     GridDev g = ocn::to_dev(*grid);
     ocn::FuseArgs fz{};
     if (fuse) fz = *fuse;  // (the next substep as the epilogue: per-field offsets like the G stores)
-    constexpr int TX = 32, TY = 8;
-    const int tiles = ((wx + TX - 2) / (TX - 1)) * ((wy + TY - 2) / (TY - 1));
-    int KZ = wz;
-    while (KZ > 16 && tiles * ((wz + KZ - 1) / KZ) < min_blocks()) KZ = (KZ + 1) / 2;
-    dim3 nbt((wx + TX - 2) / (TX - 1), (wy + TY - 2) / (TY - 1), (wz + KZ - 1) / KZ);
     if (grid->tz == OCN_PERIODIC)
-        hipLaunchKernelGGL((momentum_tendencies_tiled<OCN_PERIODIC, TX, TY, 3, false, false, true>), nbt, dim3(TX * TY), 0, stream, g, u, v, w, Gu, Gv, Gw, r, KZ, fz);
+        launch_tiled<OCN_PERIODIC, 32, 8, false, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
     else
-        hipLaunchKernelGGL((momentum_tendencies_tiled<OCN_BOUNDED, TX, TY, 3, false, false, true>), nbt, dim3(TX * TY), 0, stream, g, u, v, w, Gu, Gv, Gw, r, KZ, fz);
+        launch_tiled<OCN_BOUNDED, 32, 8, false, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
     OCN_CHECK_HIP(hipGetLastError());
     *launched = 1;
     return OCN_SUCCESS;
@@ -1616,19 +1607,22 @@ int launch_tracer_tendency_box(const ocn_grid *grid, const double *u, const doub
     ocn::TracerFuse tf{};
     if (fuse) tf = *fuse;  // (diffusion, bottom / top fluxes, the next substep: all on centre fields, whose layout has no walls in it)
     constexpr int TX = 32, TY = 8;
-    const int tiles = ((wx + TX - 2) / (TX - 1)) * ((wy + TY - 2) / (TY - 1));
-    int KZ = wz;
-    while (KZ > 16 && tiles * ((wz + KZ - 1) / KZ) < min_blocks()) KZ = (KZ + 1) / 2;
-    dim3 nbt((wx + TX - 2) / (TX - 1), (wy + TY - 2) / (TY - 1), (wz + KZ - 1) / KZ);
+    const PatchGrid pg = patch_grid(TX, TY, wx, wy, wz, min_blocks(), 16);
     if (grid->tz == OCN_PERIODIC)
-        hipLaunchKernelGGL((tracer_tendency_tiled<OCN_PERIODIC, TX, TY, 1, true>), nbt, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, KZ, tf);
+        hipLaunchKernelGGL((tracer_tendency_tiled<OCN_PERIODIC, TX, TY, true>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, pg.KZ, tf);
     else
-        hipLaunchKernelGGL((tracer_tendency_tiled<OCN_BOUNDED, TX, TY, 1, true>), nbt, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, KZ, tf);
+        hipLaunchKernelGGL((tracer_tendency_tiled<OCN_BOUNDED, TX, TY, true>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, pg.KZ, tf);
     OCN_CHECK_HIP(hipGetLastError());
     *launched = 1;
     return OCN_SUCCESS;
 }
 
+// Which kernel runs (none of the tiled ones on a Flat z):
+//  * range at least 16 x 8 x 4, correction on load: the strips of a slab rank through the 32 x 8 or 17 x 15 ST kernel; otherwise 17 x 15
+//    patches, through momentum_tendencies_pc32 when it applies (fused substep, no acc, every field below 2^31 bytes, OCN_TEND_ADDR32);
+//  * range at least 16 x 8 x 4, plain: 17 x 15 patches where narrow_tile() says so, else 32 x 8;
+//  * the halo-wide x-strips of a distributed run (wx <= 3, wy >= 64, plain): 4 x 64 patches;
+//  * anything else, or OCN_TENDENCY_KERNEL=direct: momentum_tendencies_direct.
 int launch_momentum_tendencies(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
                                double *Gv, double *Gw, const int32_t *range, const ocn::FuseArgs *fuse, hipStream_t stream)
 {
@@ -1641,113 +1635,57 @@ int launch_momentum_tendencies(const ocn_grid *grid, const double *u, const doub
     GridDev g = ocn::to_dev(*grid);
     const int wx = r.i1 - r.i0 + 1, wy = r.j1 - r.j0 + 1, wz = r.k1 - r.k0 + 1;
     static const int force_direct = (getenv("OCN_TENDENCY_KERNEL") && !strcmp(getenv("OCN_TENDENCY_KERNEL"), "direct"));
+    constexpr int P = OCN_PERIODIC, B = OCN_BOUNDED;
     if (!force_direct && grid->tz != OCN_FLAT && wx >= 16 && wy >= 8 && wz >= 4) {
-        // tile variants (TX, TY, min waves/SIMD); OCN_TILE selects one at run time for tuning
-        static const int variant = tile_variant();
-#define OCN_LAUNCH_TILED(TX, TY, W)                                                                                        \
-    do {                                                                                                                   \
-        const int tiles = ((wx + TX - 2) / (TX - 1)) * ((wy + TY - 2) / (TY - 1));                                           \
-        int KZ = wz; /* z-chunk: enough workgroups to fill the chip, long enough to amortise the 3-flux prologue */        \
-        while (KZ > 16 && tiles * ((wz + KZ - 1) / KZ) < min_blocks()) KZ = (KZ + 1) / 2;                                    \
-        dim3 nbt((wx + TX - 2) / (TX - 1), (wy + TY - 2) / (TY - 1), (wz + KZ - 1) / KZ);                                   \
-        if (grid->tz == OCN_PERIODIC)                                                                                      \
-            hipLaunchKernelGGL((momentum_tendencies_tiled<OCN_PERIODIC, TX, TY, W, false>), nbt, dim3(TX * TY), 0, stream, g, \
-                               u, v, w, Gu, Gv, Gw, r, KZ, fz);                                                             \
-        else                                                                                                               \
-            hipLaunchKernelGGL((momentum_tendencies_tiled<OCN_BOUNDED, TX, TY, W, false>), nbt, dim3(TX * TY), 0, stream, g,  \
-                               u, v, w, Gu, Gv, Gw, r, KZ, fz);                                                             \
-    } while (0)
         // narrow ranges (the 64-wide slab of one rank of eight): 32 x 8 patches own 31 columns each, so 64 columns take 3 patches (69 %
         // of the lanes useful in x); 17 x 15 patches own 16 x 14 and fit 64 = 4 x 16 exactly
-        const bool narrow = variant == 0 && narrow_tile(wx, wy);
+        const bool narrow = narrow_tile(wx, wy);
         if (fz.pc_on) {  // pressure correction on load: periodic z; x Periodic (wrapped) or FullyConnected (p halos exchanged), full range
             if ((grid->tx != OCN_PERIODIC && grid->tx != OCN_FULLY_CONNECTED) || grid->tz != OCN_PERIODIC || range != nullptr) {
                 ocn::set_error("pressure correction on load needs a (Periodic | FullyConnected, Periodic, Periodic) grid and the full range");
                 return OCN_ERR_UNSUPPORTED;
             }
             fz.pc_xhalo = grid->tx == OCN_FULLY_CONNECTED;
+            // without strips, 17 x 15 patches (16 x 14 cells owned: 87.8 % of the lanes useful against 84.8 % of 32 x 8) also on full boxes:
+            // 24.42 against 24.56 ms per 512^3 step, six same-box pairs (round 4; 16 x 16 patches: 24.9 - 25.4)
             if (fz.strip_w) {  // slab-x rank whose next exchange takes its strips from this launch
                 if (!fz.pc_xhalo || !fz.strip_e || !fz.on || wx < 2 * g.Hx) {
                     ocn::set_error("strips are written by the correction-on-load stage of a slab at least 2 Hx wide");
                     return OCN_ERR_INVALID_ARGUMENT;
                 }
-                if (narrow) launch_tiled<OCN_PERIODIC, 17, 15, true, true, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
-                else launch_tiled<OCN_PERIODIC, 32, 8, true, true, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
-                OCN_CHECK_HIP(hipGetLastError());
-                return OCN_SUCCESS;
-            }
-            // 17 x 15 patches (16 x 14 cells owned: 87.8 % of the lanes useful against 84.8 % of 32 x 8) also on full boxes: 24.42 against
-            // 24.56 ms per 512^3 step, six same-box pairs (round 4; 16 x 16 patches: 24.9 - 25.4); OCN_PC_TILE=32 selects the 32 x 8 patches
-            static const int pc_tile = getenv("OCN_PC_TILE") ? atoi(getenv("OCN_PC_TILE")) : 17;
-            if ((narrow || pc_tile == 17) && fz.on && !fz.acc && ocn::tendency_addr32_enabled() && ocn::tendency_addr32_fits(*grid))
+                if (narrow) launch_tiled<P, 17, 15, true, false, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
+                else launch_tiled<P, 32, 8, true, false, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
+            } else if (fz.on && !fz.acc && ocn::tendency_addr32_enabled() && ocn::tendency_addr32_fits(*grid))
                 launch_pc32<17, 15>(*grid, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
-            else if (narrow || pc_tile == 17)
-                launch_tiled<OCN_PERIODIC, 17, 15, true, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
-            else if (one_barrier() & 1)
-                launch_tiled<OCN_PERIODIC, 32, 8, true, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
             else
-                launch_tiled<OCN_PERIODIC, 32, 8, true, false>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
-            OCN_CHECK_HIP(hipGetLastError());
-            return OCN_SUCCESS;
+                launch_tiled<P, 17, 15, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
+        } else if (narrow) {
+            if (grid->tz == OCN_PERIODIC) launch_tiled<P, 17, 15, false>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
+            else launch_tiled<B, 17, 15, false>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
+        } else {  // fastest measured at 512^3 (6.9 ms vs 9.7 ms direct)
+            if (grid->tz == OCN_PERIODIC) launch_tiled<P, 32, 8, false>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
+            else launch_tiled<B, 32, 8, false>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
         }
-        if (narrow) {
-            if (grid->tz == OCN_PERIODIC)
-                launch_tiled<OCN_PERIODIC, 17, 15, false, false>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
-            else
-                launch_tiled<OCN_BOUNDED, 17, 15, false, false>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
-            OCN_CHECK_HIP(hipGetLastError());
-            return OCN_SUCCESS;
-        }
-        if (variant == 0 && (one_barrier() & (grid->tz == OCN_PERIODIC ? 2 : 4))) {  // the default 32 x 8 tile with one barrier per plane (see the kernel)
-            if (grid->tz == OCN_PERIODIC)
-                launch_tiled<OCN_PERIODIC, 32, 8, false, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
-            else
-                launch_tiled<OCN_BOUNDED, 32, 8, false, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
-            OCN_CHECK_HIP(hipGetLastError());
-            return OCN_SUCCESS;
-        }
-        switch (variant) {
-            case 1: OCN_LAUNCH_TILED(32, 16, 4); break;
-            case 7: OCN_LAUNCH_TILED(32, 16, 2); break;
-            case 3: OCN_LAUNCH_TILED(64, 4, 3); break;
-            case 4: OCN_LAUNCH_TILED(16, 16, 3); break;
-            case 5: OCN_LAUNCH_TILED(64, 8, 2); break;
-            case 6: OCN_LAUNCH_TILED(32, 8, 4); break;
-            default: OCN_LAUNCH_TILED(32, 8, 3); break;  // fastest measured at 512^3 (6.9 ms vs 9.7 ms direct)
-        }
-#undef OCN_LAUNCH_TILED
-        OCN_CHECK_HIP(hipGetLastError());
-        return OCN_SUCCESS;
-    }
-    static const int strip_tiles = !(getenv("OCN_STRIP_TILES") && !strcmp(getenv("OCN_STRIP_TILES"), "0"));
-    if (strip_tiles && !force_direct && !fz.pc_on && grid->tz != OCN_FLAT && wx <= 3 && wy >= 64 && wz >= 4) {
+    } else if (!force_direct && !fz.pc_on && grid->tz != OCN_FLAT && wx <= 3 && wy >= 64 && wz >= 4) {
         // the halo-wide x-strips of a distributed run (buffer tendencies): the same shared-flux kernel with a 4 x 64 patch of
         // columns (3 x 63 owned), i.e. tiled in y instead of x
-#define OCN_LAUNCH_STRIP(TZV)                                                                                                    \
-    do {                                                                                                                         \
-        constexpr int TX = 4, TY = 64;                                                                                           \
-        const int tiles = ((wx + TX - 2) / (TX - 1)) * ((wy + TY - 2) / (TY - 1));                                                \
-        int KZ = wz;                                                                                                             \
-        while (KZ > strip_min_kz() && tiles * ((wz + KZ - 1) / KZ) < 2048) KZ = (KZ + 1) / 2;                                     \
-        dim3 nbt((wx + TX - 2) / (TX - 1), (wy + TY - 2) / (TY - 1), (wz + KZ - 1) / KZ);                                        \
-        hipLaunchKernelGGL((momentum_tendencies_tiled<TZV, TX, TY, 3, false>), nbt, dim3(TX * TY), 0, stream, g, u, v, w, Gu, Gv, \
-                           Gw, r, KZ, fz);                                                                                        \
-    } while (0)
-        if (grid->tz == OCN_PERIODIC) OCN_LAUNCH_STRIP(OCN_PERIODIC); else OCN_LAUNCH_STRIP(OCN_BOUNDED);
-#undef OCN_LAUNCH_STRIP
-        OCN_CHECK_HIP(hipGetLastError());
-        return OCN_SUCCESS;
-    }
-    if (fz.pc_on) {
+        constexpr int TX = 4, TY = 64;
+        const PatchGrid pg = patch_grid(TX, TY, wx, wy, wz, 2048, strip_min_kz());
+        if (grid->tz == OCN_PERIODIC)
+            hipLaunchKernelGGL((momentum_tendencies_tiled<P, TX, TY, 3, false>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, Gu, Gv, Gw, r, pg.KZ, fz);
+        else
+            hipLaunchKernelGGL((momentum_tendencies_tiled<B, TX, TY, 3, false>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, Gu, Gv, Gw, r, pg.KZ, fz);
+    } else if (fz.pc_on) {
         ocn::set_error("pressure correction on load needs the tiled kernel (non-Flat z, range at least 16 x 8 x 4)");
         return OCN_ERR_UNSUPPORTED;
-    }
-    const dim3 block = ocn::range_block(wx), nb = ocn::range_grid(block, wx, wy, wz);
-    switch (grid->tz) {
-        case OCN_PERIODIC: hipLaunchKernelGGL(momentum_tendencies_direct<OCN_PERIODIC>, nb, block, 0, stream, g, u, v, w, Gu, Gv, Gw, r, fz); break;
-        case OCN_BOUNDED: hipLaunchKernelGGL(momentum_tendencies_direct<OCN_BOUNDED>, nb, block, 0, stream, g, u, v, w, Gu, Gv, Gw, r, fz); break;
-        case OCN_FLAT: hipLaunchKernelGGL(momentum_tendencies_direct<OCN_FLAT>, nb, block, 0, stream, g, u, v, w, Gu, Gv, Gw, r, fz); break;
-        default: ocn::set_error("unsupported z topology %d", grid->tz); return OCN_ERR_UNSUPPORTED;
+    } else {
+        const dim3 block = ocn::range_block(wx), nb = ocn::range_grid(block, wx, wy, wz);
+        switch (grid->tz) {
+            case OCN_PERIODIC: hipLaunchKernelGGL(momentum_tendencies_direct<OCN_PERIODIC>, nb, block, 0, stream, g, u, v, w, Gu, Gv, Gw, r, fz); break;
+            case OCN_BOUNDED: hipLaunchKernelGGL(momentum_tendencies_direct<OCN_BOUNDED>, nb, block, 0, stream, g, u, v, w, Gu, Gv, Gw, r, fz); break;
+            case OCN_FLAT: hipLaunchKernelGGL(momentum_tendencies_direct<OCN_FLAT>, nb, block, 0, stream, g, u, v, w, Gu, Gv, Gw, r, fz); break;
+            default: ocn::set_error("unsupported z topology %d", grid->tz); return OCN_ERR_UNSUPPORTED;
+        }
     }
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
@@ -1767,43 +1705,26 @@ int launch_tracer_tendency(const ocn_grid *grid, const double *u, const double *
     static const int tracer_direct = (getenv("OCN_TRACER_KERNEL") && !strcmp(getenv("OCN_TRACER_KERNEL"), "direct"));
     if (!tracer_direct && grid->tz != OCN_FLAT && wx >= 16 && wy >= 8 && wz >= 4) {
         constexpr int TX = 32, TY = 8;
-        const int tiles = ((wx + TX - 2) / (TX - 1)) * ((wy + TY - 2) / (TY - 1));
-        int KZ = wz;  // z-chunk: enough workgroups to fill the chip, long enough to amortise the bottom-flux prologue
-        while (KZ > 16 && tiles * ((wz + KZ - 1) / KZ) < min_blocks()) KZ = (KZ + 1) / 2;
-        dim3 nbt((wx + TX - 2) / (TX - 1), (wy + TY - 2) / (TY - 1), (wz + KZ - 1) / KZ);
-        static const int waves = getenv("OCN_TRACER_WAVES") ? atoi(getenv("OCN_TRACER_WAVES")) : 3;  // min waves / SIMD the build targets
-        if (waves >= 4) {
-            if (grid->tz == OCN_PERIODIC)
-                hipLaunchKernelGGL((tracer_tendency_tiled<OCN_PERIODIC, TX, TY, 4>), nbt, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, KZ, tf);
-            else
-                hipLaunchKernelGGL((tracer_tendency_tiled<OCN_BOUNDED, TX, TY, 4>), nbt, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, KZ, tf);
-        } else if (grid->tz == OCN_PERIODIC)
-            hipLaunchKernelGGL((tracer_tendency_tiled<OCN_PERIODIC, TX, TY>), nbt, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, KZ, tf);
-        else
-            hipLaunchKernelGGL((tracer_tendency_tiled<OCN_BOUNDED, TX, TY>), nbt, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, KZ, tf);
-        OCN_CHECK_HIP(hipGetLastError());
-        return OCN_SUCCESS;
-    }
-    static const int strip_tiles = !(getenv("OCN_STRIP_TILES") && !strcmp(getenv("OCN_STRIP_TILES"), "0"));
-    if (strip_tiles && !tracer_direct && grid->tz != OCN_FLAT && wx <= 3 && wy >= 64 && wz >= 4) {  // halo-wide x-strips: 4 x 64 patches
-        constexpr int TX = 4, TY = 64;
-        const int tiles = ((wx + TX - 2) / (TX - 1)) * ((wy + TY - 2) / (TY - 1));
-        int KZ = wz;
-        while (KZ > strip_min_kz() && tiles * ((wz + KZ - 1) / KZ) < 2048) KZ = (KZ + 1) / 2;
-        dim3 nbt((wx + TX - 2) / (TX - 1), (wy + TY - 2) / (TY - 1), (wz + KZ - 1) / KZ);
+        const PatchGrid pg = patch_grid(TX, TY, wx, wy, wz, min_blocks(), 16);
         if (grid->tz == OCN_PERIODIC)
-            hipLaunchKernelGGL((tracer_tendency_tiled<OCN_PERIODIC, TX, TY>), nbt, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, KZ, tf);
+            hipLaunchKernelGGL((tracer_tendency_tiled<OCN_PERIODIC, TX, TY>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, pg.KZ, tf);
         else
-            hipLaunchKernelGGL((tracer_tendency_tiled<OCN_BOUNDED, TX, TY>), nbt, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, KZ, tf);
-        OCN_CHECK_HIP(hipGetLastError());
-        return OCN_SUCCESS;
-    }
-    const dim3 block = ocn::range_block(wx), nb = ocn::range_grid(block, wx, wy, wz);
-    switch (grid->tz) {
-        case OCN_PERIODIC: hipLaunchKernelGGL(tracer_tendency_direct<OCN_PERIODIC>, nb, block, 0, stream, g, u, v, w, c, Gc, r, tf); break;
-        case OCN_BOUNDED: hipLaunchKernelGGL(tracer_tendency_direct<OCN_BOUNDED>, nb, block, 0, stream, g, u, v, w, c, Gc, r, tf); break;
-        case OCN_FLAT: hipLaunchKernelGGL(tracer_tendency_direct<OCN_FLAT>, nb, block, 0, stream, g, u, v, w, c, Gc, r, tf); break;
-        default: ocn::set_error("unsupported z topology %d", grid->tz); return OCN_ERR_UNSUPPORTED;
+            hipLaunchKernelGGL((tracer_tendency_tiled<OCN_BOUNDED, TX, TY>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, pg.KZ, tf);
+    } else if (!tracer_direct && grid->tz != OCN_FLAT && wx <= 3 && wy >= 64 && wz >= 4) {  // halo-wide x-strips: 4 x 64 patches
+        constexpr int TX = 4, TY = 64;
+        const PatchGrid pg = patch_grid(TX, TY, wx, wy, wz, 2048, strip_min_kz());
+        if (grid->tz == OCN_PERIODIC)
+            hipLaunchKernelGGL((tracer_tendency_tiled<OCN_PERIODIC, TX, TY>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, pg.KZ, tf);
+        else
+            hipLaunchKernelGGL((tracer_tendency_tiled<OCN_BOUNDED, TX, TY>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, pg.KZ, tf);
+    } else {
+        const dim3 block = ocn::range_block(wx), nb = ocn::range_grid(block, wx, wy, wz);
+        switch (grid->tz) {
+            case OCN_PERIODIC: hipLaunchKernelGGL(tracer_tendency_direct<OCN_PERIODIC>, nb, block, 0, stream, g, u, v, w, c, Gc, r, tf); break;
+            case OCN_BOUNDED: hipLaunchKernelGGL(tracer_tendency_direct<OCN_BOUNDED>, nb, block, 0, stream, g, u, v, w, c, Gc, r, tf); break;
+            case OCN_FLAT: hipLaunchKernelGGL(tracer_tendency_direct<OCN_FLAT>, nb, block, 0, stream, g, u, v, w, c, Gc, r, tf); break;
+            default: ocn::set_error("unsupported z topology %d", grid->tz); return OCN_ERR_UNSUPPORTED;
+        }
     }
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
@@ -1827,14 +1748,11 @@ int launch_tracer_pair_tendency(const ocn_grid *grid, const double *u, const dou
     TracerPair tp{};
     for (int t = 0; t < 2; ++t) { tp.c[t] = c[t]; tp.G[t] = Gc[t]; tp.tf[t] = fuse[t]; }
     constexpr int TX = 32, TY = 8;
-    const int tiles = ((wx + TX - 2) / (TX - 1)) * ((wy + TY - 2) / (TY - 1));
-    int KZ = wz;
-    while (KZ > 16 && tiles * ((wz + KZ - 1) / KZ) < min_blocks()) KZ = (KZ + 1) / 2;
-    dim3 nbt((wx + TX - 2) / (TX - 1), (wy + TY - 2) / (TY - 1), (wz + KZ - 1) / KZ);
+    const PatchGrid pg = patch_grid(TX, TY, wx, wy, wz, min_blocks(), 16);
     if (grid->tz == OCN_PERIODIC)
-        hipLaunchKernelGGL((tracer_pair_tendency_tiled<OCN_PERIODIC, TX, TY>), nbt, dim3(TX * TY), 0, stream, g, u, v, w, tp, r, KZ);
+        hipLaunchKernelGGL((tracer_pair_tendency_tiled<OCN_PERIODIC, TX, TY>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, tp, r, pg.KZ);
     else
-        hipLaunchKernelGGL((tracer_pair_tendency_tiled<OCN_BOUNDED, TX, TY>), nbt, dim3(TX * TY), 0, stream, g, u, v, w, tp, r, KZ);
+        hipLaunchKernelGGL((tracer_pair_tendency_tiled<OCN_BOUNDED, TX, TY>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, tp, r, pg.KZ);
     OCN_CHECK_HIP(hipGetLastError());
     *launched = 1;
     return OCN_SUCCESS;

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the momentum-tendency launch alone (HIP events on the launching stream). Env: OCN_TILE, OCN_TENDENCY_KERNEL."""
+"""Times the momentum-tendency launch alone (HIP events on the launching stream). Env: OCN_NARROW_TILE, OCN_TENDENCY_KERNEL."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -22,4 +22,4 @@ for _ in range(reps):
 e1.record(); torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / reps
 chk = float(sum(f.interior_view().abs().sum() for f in m.timestepper.Gn))
-print(f"tile={os.environ.get('OCN_TILE','0')} kernel={os.environ.get('OCN_TENDENCY_KERNEL','tiled')} n={n} {mode}: {ms:.3f} ms  ({n**3/ms/1e6:.2f} Gcell/s)  checksum={chk:.10e}")
+print(f"narrow_tile={os.environ.get('OCN_NARROW_TILE','auto')} kernel={os.environ.get('OCN_TENDENCY_KERNEL','tiled')} n={n} {mode}: {ms:.3f} ms  ({n**3/ms/1e6:.2f} Gcell/s)  checksum={chk:.10e}")
