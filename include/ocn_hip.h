@@ -299,6 +299,32 @@ int ocn_compute_momentum_tendencies_terms_rk3(const ocn_grid *grid, const ocn_mo
                                               double *Gu, double *Gv, double *Gw, const double *Gmu, const double *Gmv,
                                               const double *Gmw, double *u_out, double *v_out, double *w_out, double dt,
                                               double gamma, double zeta, int32_t has_zeta, const int32_t *range, void *stream);
+
+/* stokes_drift = UniformStokesDrift(; ∂z_uˢ, ∂z_vˢ, ∂t_uˢ, ∂t_vˢ) (src/StokesDrifts.jl:36-180): the horizontally uniform profiles, sampled by
+ * the host on the grid's z nodes.  DEVICE vectors, element 0 <-> k = 1: Nz values at z centres, Nz + 1 at z faces; NULL = zero.
+ *   dz_us_center[k-1] = ∂z_uˢ(znode(k, Center), t)  (array form: ℑzᵃᵃᶜ of the Face array),  dz_us_face[k-1] = ∂z_uˢ(znode(k, Face), t),
+ *   dt_us[k-1] = ∂t_uˢ(znode(k, Center), t); the same for vˢ.  The vectors are only read. */
+typedef struct ocn_stokes_drift {
+    const double *dz_us_center, *dz_vs_center;
+    const double *dz_us_face, *dz_vs_face;
+    const double *dt_us, *dt_vs;
+} ocn_stokes_drift;
+/* ocn_compute_momentum_tendencies_terms / ..._terms_rk3 with the Stokes-drift terms added LAST, as the reference does after the closure term
+ * (nonhydrostatic_tendency_kernel_functions.jl:73-74, 135-136, 197-198):
+ *   Gu <- (Gu + ℑxzᶠᵃᶜ(w) dz_us_center[k]) + dt_us[k],   Gv <- (Gv + ℑyzᵃᶠᶜ(w) dz_vs_center[k]) + dt_vs[k],
+ *   Gw <- (Gw + (-ℑxzᶜᵃᶠ(u) dz_us_face[k] - ℑyzᵃᶜᶠ(v) dz_vs_face[k])) + 0
+ * inside the finishing pass (which is launched even when `terms` holds nothing but the advection scheme).  In the _rk3 form the bottom /
+ * top flux contributions follow the Stokes terms, as compute_boundary_tendency_contributions! follows the tendency kernels.  z must not be
+ * Flat.  stokes == NULL: exactly the entry point without the suffix. */
+int ocn_compute_momentum_tendencies_terms_stokes(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_stokes_drift *stokes,
+                                                 const double *u, const double *v, const double *w, double *Gu, double *Gv, double *Gw,
+                                                 const int32_t *range, void *stream);
+int ocn_compute_momentum_tendencies_terms_rk3_stokes(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_stokes_drift *stokes,
+                                                     const ocn_field_bcs *bcs_u, const ocn_field_bcs *bcs_v, const double *u, const double *v,
+                                                     const double *w, double *Gu, double *Gv, double *Gw, const double *Gmu,
+                                                     const double *Gmv, const double *Gmw, double *u_out, double *v_out, double *w_out,
+                                                     double dt, double gamma, double zeta, int32_t has_zeta, const int32_t *range,
+                                                     void *stream);
 /* same for one tracer; advection must be OCN_ADVECTION_WENO5 or OCN_ADVECTION_UPWIND5 (advection, diffusion, boundary flux
  * and substep are ONE kernel -- on grids with walls in x / y: on the interior box; three per-cell kernels on the frames) */
 int ocn_compute_tracer_tendency_terms_rk3(const ocn_grid *grid, const ocn_model_terms *terms, double kappa, const double *kappa_e,
@@ -541,6 +567,11 @@ int ocn_model_driver_destroy(ocn_model_driver_t driver);
 int ocn_model_driver_time_step(ocn_model_driver_t driver, double dt, void *stream);
 /* completes the deferred compute_tendencies! and brings every prognostic field into the caller's arrays */
 int ocn_model_driver_flush(ocn_model_driver_t driver, void *stream);
+/* A STEADY UniformStokesDrift for every following time step (the vectors are the caller's and must outlive the driver; NULL switches the
+ * terms off again).  Call before the first time step or after ocn_model_driver_flush (OCN_ERR_INVALID_ARGUMENT while a step's tendencies
+ * are deferred); the next time step recomputes the tendencies of the current state.  time_dependent != 0 (profiles that the host must resample at every stage) is refused with OCN_ERR_INVALID_ARGUMENT: that
+ * case needs the Python host (time_step(model, dt)), which samples the profiles at clock.time of every tendency evaluation. */
+int ocn_model_driver_set_stokes_drift(ocn_model_driver_t driver, const ocn_stokes_drift *stokes, int32_t time_dependent);
 /* where field f (0, 1, 2 = u, v, w; 3 + n = tracer n) and its G^n are right now */
 int ocn_model_driver_field(ocn_model_driver_t driver, int32_t f, double **field, double **G);
 

@@ -284,6 +284,29 @@ function compute_tendencies_with_terms!(model::HIPModel, t::OcnModelTerms, κ::V
         end
     end
 end
+# ---- stokes_drift = UniformStokesDrift (StokesDrifts.jl:36-180): struct ocn_stokes_drift, six device vectors sampled on the host ------
+struct OcnStokesDrift
+    dz_us_center::Ptr{Float64}; dz_vs_center::Ptr{Float64}
+    dz_us_face::Ptr{Float64}; dz_vs_face::Ptr{Float64}
+    dt_us::Ptr{Float64}; dt_vs::Ptr{Float64}
+end
+"one profile at the z nodes `z` at time t: functions (z, t[, parameters]) are evaluated on the host, `nothing` stays NULL (zero)"
+sample_profile(::Nothing, z, t, p) = nothing
+sample_profile(f, z, t, ::Nothing) = Float64[f(zk, t) for zk in z]
+sample_profile(f, z, t, p) = Float64[f(zk, t, p) for zk in z]
+"host vectors (centres: Nz, faces: Nz + 1) of a UniformStokesDrift with function profiles, in the field order of OcnStokesDrift"
+function sample_stokes_drift(sd, zc, zf, t)
+    p = sd.parameters
+    return (sample_profile(sd.∂z_uˢ, zc, t, p), sample_profile(sd.∂z_vˢ, zc, t, p), sample_profile(sd.∂z_uˢ, zf, t, p),
+            sample_profile(sd.∂z_vˢ, zf, t, p), sample_profile(sd.∂t_uˢ, zc, t, p), sample_profile(sd.∂t_vˢ, zc, t, p))
+end
+"compute_Gu!/Gv!/Gw! with the Stokes-drift terms last; `s` holds device copies of sample_stokes_drift at clock.time"
+function compute_momentum_tendencies_with_stokes_drift!(model::HIPModel, t::OcnModelTerms, s::OcnStokesDrift, kernel_parameters)
+    g = Ref(OcnGrid(model.grid)); U = model.velocities; G = model.timestepper.Gⁿ; r = range6(kernel_parameters)
+    GC.@preserve model r check(ccall((:ocn_compute_momentum_tendencies_terms_stokes, lib), Cint,
+        (Ref{OcnGrid}, Ref{OcnModelTerms}, Ref{OcnStokesDrift}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}),
+        g, Ref(t), Ref(s), dptr(U.u), dptr(U.v), dptr(U.w), dptr(G.u), dptr(G.v), dptr(G.w), r, C_NULL))
+end
 update_hydrostatic_pressure!(pHY′, grid::HIPGrid, t::OcnModelTerms) = GC.@preserve pHY′ check(ccall(
     (:ocn_update_hydrostatic_pressure, lib), Cint, (Ref{OcnGrid}, Ref{OcnModelTerms}, Ptr{Float64}, Ptr{Cvoid}),
     Ref(OcnGrid(grid)), Ref(t), dptr(pHY′), C_NULL))
@@ -454,6 +477,9 @@ end
 "time_step!(model, Δt) with tracers, closures, buoyancy and boundary fluxes: halo fills, compute_auxiliaries!, tendencies, projection"
 time_step!(d::HIPModelDriver, Δt) = check(ccall((:ocn_model_driver_time_step, lib), Cint, (Ptr{Cvoid}, Float64, Ptr{Cvoid}), d.handle, Δt, C_NULL))
 flush!(d::HIPModelDriver) = check(ccall((:ocn_model_driver_flush, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), d.handle, C_NULL))
+"a STEADY UniformStokesDrift for every following step (the vectors must outlive the driver); time-dependent profiles are refused by the library"
+set_stokes_drift!(d::HIPModelDriver, s::OcnStokesDrift; time_dependent::Bool = false) = check(ccall((:ocn_model_driver_set_stokes_drift, lib), Cint,
+    (Ptr{Cvoid}, Ref{OcnStokesDrift}, Int32), d.handle, Ref(s), time_dependent))
 function driver_field(d::HIPModelDriver, n::Integer)              # 0, 1, 2 = u, v, w; 3 + n = tracer n
     f = Ref{Ptr{Float64}}(C_NULL); G = Ref{Ptr{Float64}}(C_NULL)
     check(ccall((:ocn_model_driver_field, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}), d.handle, n, f, G))

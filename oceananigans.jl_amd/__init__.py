@@ -24,6 +24,7 @@ from .output import (AdvectiveCFL, DiffusiveCFL, NaNChecker, TimeStepWizard, cel
 from .physics import (AnisotropicMinimumDissipation, BetaPlane, BoundaryCondition, BuoyancyTracer, Centered, FieldBoundaryConditions, FluxBoundaryCondition, FPlane,
                       GradientBoundaryCondition, LinearEquationOfState, OpenBoundaryCondition, ScalarDiffusivity, SeawaterBuoyancy,
                       ValueBoundaryCondition)
+from .stokes import StokesDrift, UniformStokesDrift
 from .solvers import (BatchedTridiagonalSolver, FFTBasedPoissonSolver, FourierTridiagonalPoissonSolver, XDirection, YDirection, ZDirection,
                       nonhydrostatic_pressure_solver, solve, stretched_direction)
 

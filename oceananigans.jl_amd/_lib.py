@@ -39,6 +39,12 @@ class CModelTerms(C.Structure):
                 ("coriolis_beta", C.c_double), ("yc", C.c_void_p), ("yf", C.c_void_p)]
 
 
+class CStokesDrift(C.Structure):
+    """struct ocn_stokes_drift: device vectors of a UniformStokesDrift (element 0 <-> k = 1; NULL = zero)"""
+    _fields_ = [("dz_us_center", C.c_void_p), ("dz_vs_center", C.c_void_p), ("dz_us_face", C.c_void_p), ("dz_vs_face", C.c_void_p),
+                ("dt_us", C.c_void_p), ("dt_vs", C.c_void_p)]
+
+
 class CBc(C.Structure):
     """struct ocn_bc"""
     _fields_ = [("kind", C.c_int32), ("_pad", C.c_int32), ("value", C.c_double), ("coeff", C.c_double), ("values", C.c_void_p)]
@@ -98,6 +104,10 @@ _SIGS = {
     "ocn_compute_amd_diffusivity": [C.POINTER(CGrid), _dbl, _vp, _vp, _vp, _vp, _vp, _vp],
     "ocn_compute_momentum_tendencies_terms_rk3": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CFieldBcs), C.POINTER(CFieldBcs)]
                                                  + [_vp] * 12 + [_dbl, _dbl, _dbl, _i32, C.POINTER(_i32), _vp],
+    "ocn_compute_momentum_tendencies_terms_stokes": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CStokesDrift), _vp, _vp, _vp, _vp, _vp, _vp,
+                                                     C.POINTER(_i32), _vp],
+    "ocn_compute_momentum_tendencies_terms_rk3_stokes": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CStokesDrift), C.POINTER(CFieldBcs),
+                                                         C.POINTER(CFieldBcs)] + [_vp] * 12 + [_dbl, _dbl, _dbl, _i32, C.POINTER(_i32), _vp],
     "ocn_compute_tracer_tendency_terms_rk3": [C.POINTER(CGrid), C.POINTER(CModelTerms), _dbl, _vp, C.POINTER(CFieldBcs)]
                                              + [_vp] * 7 + [_dbl, _dbl, _dbl, _i32, C.POINTER(_i32), _vp],
     "ocn_compute_tracer_pair_tendency_terms_rk3": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(_dbl), C.POINTER(_vp),
@@ -160,6 +170,7 @@ _SIGS = {
     "ocn_model_driver_time_step": [_vp, _dbl, _vp],
     "ocn_model_driver_flush": [_vp, _vp],
     "ocn_model_driver_field": [_vp, _i32, C.POINTER(_vp), C.POINTER(_vp)],
+    "ocn_model_driver_set_stokes_drift": [_vp, C.POINTER(CStokesDrift), _i32],
     "ocn_halo_plane_x": [C.POINTER(CGrid), _vp, _i32, _i32, _vp, _i32, _vp],
     "ocn_halo_pack_pressure": [C.POINTER(CGrid), _vp, _vp, _dbl, _vp, _vp, _vp],
     "ocn_halo_unpack_pressure": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _vp],

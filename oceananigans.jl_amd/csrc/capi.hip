@@ -386,25 +386,54 @@ static int launch_advective_tracer(int advection, const ocn_grid *grid, const do
     }
 }
 
-int ocn_compute_momentum_tendencies_terms(const ocn_grid *grid, const ocn_model_terms *terms, const double *u, const double *v,
-                                          const double *w, double *Gu, double *Gv, double *Gw, const int32_t *range,
-                                          void *stream)
+// stokes_drift = UniformStokesDrift: the device vectors of the profiles (NULL = zero); a vertical shear needs a z direction
+static int validate_stokes(const ocn_grid *grid, const ocn_stokes_drift *stokes, const char *who)
+{
+    OCN_REQUIRE(stokes != nullptr, "%s: stokes is NULL", who);
+    OCN_REQUIRE(grid->tz != OCN_FLAT, "%s: UniformStokesDrift needs a non-Flat z", who);
+    return OCN_SUCCESS;
+}
+
+static int momentum_tendencies_terms(const char *who, const ocn_grid *grid, const ocn_model_terms *terms, const ocn_stokes_drift *stokes,
+                                     const double *u, const double *v, const double *w, double *Gu, double *Gv, double *Gw,
+                                     const int32_t *range, void *stream)
 {
     int st = validate_terms(grid, terms);
     if (st != OCN_SUCCESS) return st;
-    OCN_REQUIRE(u && v && w && Gu && Gv && Gw, "ocn_compute_momentum_tendencies_terms: null field pointer");
+    OCN_REQUIRE(u && v && w && Gu && Gv && Gw, "%s: null field pointer", who);
     OCN_REQUIRE((grid->tx == OCN_FLAT || grid->Hx >= 1) && (grid->ty == OCN_FLAT || grid->Hy >= 1) && (grid->tz == OCN_FLAT || grid->Hz >= 1), "halo >= 1 required");
     const bool strict = strict_math(grid);
     hipStream_t s = as_stream(stream);
     st = launch_advective_momentum(terms->advection, grid, u, v, w, Gu, Gv, Gw, range, s);
     if (st != OCN_SUCCESS) return st;
-    if (!(terms->coriolis || terms->closure || terms->buoyancy)) return OCN_SUCCESS;
+    if (!(terms->coriolis || terms->closure || terms->buoyancy || stokes)) return OCN_SUCCESS;
     TermsDev t = to_dev(*terms);
+    ocn::StokesDev sd{};
+    if (stokes) sd = ocn::to_dev(*stokes);
+    const ocn::StokesDev *psd = stokes ? &sd : nullptr;
     if (!xy_periodic(grid))
-        return strict ? ocn_strict::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, range, s)
-                      : ocn_fast::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, range, s);
-    return strict ? ocn_strict::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s)
-                  : ocn_fast::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s);
+        return strict ? ocn_strict::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, psd)
+                      : ocn_fast::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, psd);
+    return strict ? ocn_strict::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, psd)
+                  : ocn_fast::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, psd);
+}
+
+int ocn_compute_momentum_tendencies_terms(const ocn_grid *grid, const ocn_model_terms *terms, const double *u, const double *v,
+                                          const double *w, double *Gu, double *Gv, double *Gw, const int32_t *range,
+                                          void *stream)
+{
+    return momentum_tendencies_terms("ocn_compute_momentum_tendencies_terms", grid, terms, nullptr, u, v, w, Gu, Gv, Gw, range, stream);
+}
+
+int ocn_compute_momentum_tendencies_terms_stokes(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_stokes_drift *stokes,
+                                                 const double *u, const double *v, const double *w, double *Gu, double *Gv, double *Gw,
+                                                 const int32_t *range, void *stream)
+{
+    if (!stokes) return momentum_tendencies_terms("ocn_compute_momentum_tendencies_terms_stokes", grid, terms, nullptr, u, v, w, Gu, Gv, Gw, range, stream);
+    OCN_REQUIRE(grid != nullptr, "grid is NULL");
+    int st = validate_stokes(grid, stokes, "ocn_compute_momentum_tendencies_terms_stokes");
+    if (st != OCN_SUCCESS) return st;
+    return momentum_tendencies_terms("ocn_compute_momentum_tendencies_terms_stokes", grid, terms, stokes, u, v, w, Gu, Gv, Gw, range, stream);
 }
 
 // the extra terms alone, added to a G that already holds what precedes them in the reference's sum (used by the hydrostatic
@@ -674,18 +703,18 @@ static int flux_side(const ocn_grid *grid, const ocn_field_bcs *b, const char *n
     return OCN_SUCCESS;
 }
 
-int ocn_compute_momentum_tendencies_terms_rk3(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_field_bcs *bcs_u,
-                                              const ocn_field_bcs *bcs_v, const double *u, const double *v, const double *w,
-                                              double *Gu, double *Gv, double *Gw, const double *Gmu, const double *Gmv,
-                                              const double *Gmw, double *u_out, double *v_out, double *w_out, double dt,
-                                              double gamma, double zeta, int32_t has_zeta, const int32_t *range, void *stream)
+static int momentum_tendencies_terms_rk3(const char *who, const ocn_grid *grid, const ocn_model_terms *terms, const ocn_stokes_drift *stokes,
+                                         const ocn_field_bcs *bcs_u, const ocn_field_bcs *bcs_v, const double *u, const double *v,
+                                         const double *w, double *Gu, double *Gv, double *Gw, const double *Gmu, const double *Gmv,
+                                         const double *Gmw, double *u_out, double *v_out, double *w_out, double dt, double gamma,
+                                         double zeta, int32_t has_zeta, const int32_t *range, void *stream)
 {
     int st = validate_terms(grid, terms);
     if (st != OCN_SUCCESS) return st;
-    OCN_REQUIRE(xy_periodic(grid) || !range, "ocn_compute_momentum_tendencies_terms_rk3: ranges need Periodic x and y");
-    OCN_REQUIRE(u && v && w && Gu && Gv && Gw && u_out && v_out && w_out, "ocn_compute_momentum_tendencies_terms_rk3: null field pointer");
-    OCN_REQUIRE(!has_zeta || (Gmu && Gmv && Gmw), "ocn_compute_momentum_tendencies_terms_rk3: G⁻ pointers are required when has_zeta != 0");
-    OCN_REQUIRE(u_out != u && v_out != v && w_out != w, "ocn_compute_momentum_tendencies_terms_rk3: outputs must not alias the inputs");
+    OCN_REQUIRE(xy_periodic(grid) || !range, "%s: ranges need Periodic x and y", who);
+    OCN_REQUIRE(u && v && w && Gu && Gv && Gw && u_out && v_out && w_out, "%s: null field pointer", who);
+    OCN_REQUIRE(!has_zeta || (Gmu && Gmv && Gmw), "%s: G⁻ pointers are required when has_zeta != 0", who);
+    OCN_REQUIRE(u_out != u && v_out != v && w_out != w, "%s: outputs must not alias the inputs", who);
     MomentumFinal mf{};
     st = flux_side(grid, bcs_u, "u", mf.bottom[0], mf.top[0]);
     if (st != OCN_SUCCESS) return st;
@@ -698,13 +727,16 @@ int ocn_compute_momentum_tendencies_terms_rk3(const ocn_grid *grid, const ocn_mo
     const bool strict = strict_math(grid);
     hipStream_t s = as_stream(stream);
     TermsDev t = to_dev(*terms);
+    ocn::StokesDev sd{};
+    if (stokes) sd = ocn::to_dev(*stokes);
+    const ocn::StokesDev *psd = stokes ? &sd : nullptr;
     if (!xy_periodic(grid)) {
         // walls in x / y: advection (box + frames), then the finishing pass in the reference's order with the boundary fluxes and the substep --
         // inside the tiled kernel on the interior box, as per-cell kernels on the frames (general.hip)
         st = launch_advective_momentum(terms->advection, grid, u, v, w, Gu, Gv, Gw, nullptr, s);
         if (st != OCN_SUCCESS) return st;
-        return strict ? ocn_strict::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, nullptr, s, &mf)
-                      : ocn_fast::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, nullptr, s, &mf);
+        return strict ? ocn_strict::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, nullptr, s, &mf, psd)
+                      : ocn_fast::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, nullptr, s, &mf, psd);
     }
     static const bool extra_first = !(std::getenv("OCN_EXTRA_FIRST") && std::getenv("OCN_EXTRA_FIRST")[0] == '0');
     if (!strict && extra_first && terms->advection != OCN_ADVECTION_CENTERED2) {
@@ -716,7 +748,7 @@ int ocn_compute_momentum_tendencies_terms_rk3(const ocn_grid *grid, const ocn_mo
         MomentumFinal pre = mf;
         pre.pre = 1;
         pre.sc.on = 0;
-        st = ocn_fast::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, &pre);
+        st = ocn_fast::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, &pre, psd);
         if (st != OCN_SUCCESS) return st;
         FuseArgs fz{};
         fz.Gm[0] = Gmu; fz.Gm[1] = Gmv; fz.Gm[2] = Gmw;
@@ -728,8 +760,35 @@ int ocn_compute_momentum_tendencies_terms_rk3(const ocn_grid *grid, const ocn_mo
     }
     st = launch_advective_momentum(terms->advection, grid, u, v, w, Gu, Gv, Gw, range, s);
     if (st != OCN_SUCCESS) return st;
-    return strict ? ocn_strict::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, &mf)
-                  : ocn_fast::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, &mf);
+    return strict ? ocn_strict::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, &mf, psd)
+                  : ocn_fast::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, &mf, psd);
+}
+
+int ocn_compute_momentum_tendencies_terms_rk3(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_field_bcs *bcs_u,
+                                              const ocn_field_bcs *bcs_v, const double *u, const double *v, const double *w,
+                                              double *Gu, double *Gv, double *Gw, const double *Gmu, const double *Gmv,
+                                              const double *Gmw, double *u_out, double *v_out, double *w_out, double dt,
+                                              double gamma, double zeta, int32_t has_zeta, const int32_t *range, void *stream)
+{
+    return momentum_tendencies_terms_rk3("ocn_compute_momentum_tendencies_terms_rk3", grid, terms, nullptr, bcs_u, bcs_v, u, v, w, Gu, Gv, Gw, Gmu,
+                                         Gmv, Gmw, u_out, v_out, w_out, dt, gamma, zeta, has_zeta, range, stream);
+}
+
+int ocn_compute_momentum_tendencies_terms_rk3_stokes(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_stokes_drift *stokes,
+                                                     const ocn_field_bcs *bcs_u, const ocn_field_bcs *bcs_v, const double *u, const double *v,
+                                                     const double *w, double *Gu, double *Gv, double *Gw, const double *Gmu,
+                                                     const double *Gmv, const double *Gmw, double *u_out, double *v_out, double *w_out,
+                                                     double dt, double gamma, double zeta, int32_t has_zeta, const int32_t *range,
+                                                     void *stream)
+{
+    const char *who = "ocn_compute_momentum_tendencies_terms_rk3_stokes";
+    if (stokes) {
+        OCN_REQUIRE(grid != nullptr, "grid is NULL");
+        int st = validate_stokes(grid, stokes, who);
+        if (st != OCN_SUCCESS) return st;
+    }
+    return momentum_tendencies_terms_rk3(who, grid, terms, stokes, bcs_u, bcs_v, u, v, w, Gu, Gv, Gw, Gmu, Gmv, Gmw, u_out, v_out, w_out, dt,
+                                         gamma, zeta, has_zeta, range, stream);
 }
 
 int ocn_compute_tracer_tendency_terms_rk3(const ocn_grid *grid, const ocn_model_terms *terms, double kappa, const double *kappa_e,

@@ -38,6 +38,9 @@ struct ocn_model_driver {
     const ocn_field_bcs *bcs[NF] = {};  // NULL = defaults
     bool any_bcs = false, any_flux = false, momentum_extra = false;
     bool pending = false, started = false;
+    // stokes_drift = UniformStokesDrift with steady profiles (ocn_model_driver_set_stokes_drift): the caller's device vectors
+    ocn_stokes_drift stokes{};
+    bool has_stokes = false, base_momentum_extra = false;
     long long iteration = 0;
     // slab-x rank (ocn_model_driver_create_distributed): RCCL communicator + distributed Poisson handle, both borrowed
     ocn_comm_t comm = nullptr;
@@ -144,7 +147,7 @@ int update_state(ocn_model_driver *d, void *stream)
 // compute_tendencies! (compute_nonhydrostatic_tendencies.jl:17-54) with the boundary contributions (:204-213)
 int compute_tendencies(ocn_model_driver *d, void *stream)
 {
-    int st = ocn_compute_momentum_tendencies_terms(&d->grid, &d->terms, d->U[0], d->U[1], d->U[2], d->Gn[0], d->Gn[1], d->Gn[2], nullptr, stream);
+    int st = ocn_compute_momentum_tendencies_terms_stokes(&d->grid, &d->terms, d->has_stokes ? &d->stokes : nullptr, d->U[0], d->U[1], d->U[2], d->Gn[0], d->Gn[1], d->Gn[2], nullptr, stream);
     if (st != OCN_SUCCESS) return st;
     for (int t = 0; t < d->nt; ++t) {
         st = ocn_compute_tracer_tendency_terms(&d->grid, &d->terms, d->terms.closure == 1 ? d->kappa[t] : 0.0,
@@ -168,7 +171,7 @@ int launch_tendencies(ocn_model_driver *d, double dt, double gamma, double zeta,
 {
     int st;
     if (d->momentum_extra)
-        st = ocn_compute_momentum_tendencies_terms_rk3(&d->grid, &d->terms, flux_bcs(d, 0), flux_bcs(d, 1), d->U[0], d->U[1], d->U[2], d->Gn[0],
+        st = ocn_compute_momentum_tendencies_terms_rk3_stokes(&d->grid, &d->terms, d->has_stokes ? &d->stokes : nullptr, flux_bcs(d, 0), flux_bcs(d, 1), d->U[0], d->U[1], d->U[2], d->Gn[0],
                                                        d->Gn[1], d->Gn[2], d->Gm[0], d->Gm[1], d->Gm[2], d->A[0], d->A[1], d->A[2], dt, gamma, zeta,
                                                        has_zeta, range, stream);
     else
@@ -426,6 +429,7 @@ static int model_driver_create(ocn_model_driver_t *out, const ocn_grid *grid, co
     }
     d->momentum_extra = t.coriolis != 0 || t.closure != 0 || t.buoyancy != OCN_BUOYANCY_NONE || t.advection != OCN_ADVECTION_WENO5 ||
                         has_flux(d->bcs[0]) || has_flux(d->bcs[1]);
+    d->base_momentum_extra = d->momentum_extra;
     GridDev g = ocn::to_dev(*grid);
     for (int f = 0; f < d->n; ++f) {
         const Lay L = ocn::make_lay(g, d->locs[f]);
@@ -532,6 +536,21 @@ extern "C" int ocn_model_driver_flush(ocn_model_driver_t d, void *stream)
         }
         refresh_terms(d);
     }
+    return OCN_SUCCESS;
+}
+
+extern "C" int ocn_model_driver_set_stokes_drift(ocn_model_driver_t d, const ocn_stokes_drift *stokes, int32_t time_dependent)
+{
+    OCN_REQUIRE(d, "ocn_model_driver_set_stokes_drift: null driver");
+    OCN_REQUIRE(!time_dependent, "ocn_model_driver_set_stokes_drift: a time-dependent UniformStokesDrift needs the Python host (time_step(model, dt) "
+                                 "samples the profiles at every tendency evaluation); the driver takes steady profiles only");
+    OCN_REQUIRE(!d->comm, "ocn_model_driver_set_stokes_drift: not on a slab-x rank (stokes_drift on a Distributed architecture is not implemented)");
+    OCN_REQUIRE(!stokes || d->grid.tz != OCN_FLAT, "ocn_model_driver_set_stokes_drift: UniformStokesDrift needs a non-Flat z");
+    OCN_REQUIRE(!d->pending, "ocn_model_driver_set_stokes_drift: call before the first time step or after ocn_model_driver_flush");
+    d->has_stokes = stokes != nullptr;
+    d->stokes = stokes ? *stokes : ocn_stokes_drift{};
+    d->momentum_extra = d->base_momentum_extra || d->has_stokes;
+    d->started = false;  // the next time step begins with update_state! and a fresh compute_tendencies!, as at iteration 0
     return OCN_SUCCESS;
 }
 

@@ -179,6 +179,20 @@ inline TermsDev to_dev(const ocn_model_terms &m)
     return t;
 }
 
+// device-side copy of ocn_stokes_drift (UniformStokesDrift, StokesDrifts.jl:36-180): the six per-level profiles, element 0 <-> k = 1
+// (Nz values at centres, Nz + 1 at faces); NULL: the profile is zero.  Wave-uniform in every kernel that reads them (k is), so they are
+// read through the constant address space like dzc / dzf.  Only the kernels compiled with the Stokes terms take this struct as an argument.
+struct StokesDev {
+    const double *dzu_c, *dzv_c;  // ∂z uˢ, ∂z vˢ at z centres (x / y components of (∇ × uˢ) × u)
+    const double *dzu_f, *dzv_f;  // ... at z faces (z component)
+    const double *dtu, *dtv;      // ∂t uˢ, ∂t vˢ at z centres
+};
+__device__ __forceinline__ double stokes_at(const double *p, int k) { return p ? uniform_load(p, k - 1) : 0.0; }
+inline StokesDev to_dev(const ocn_stokes_drift &s)
+{
+    return StokesDev{s.dz_us_center, s.dz_vs_center, s.dz_us_face, s.dz_vs_face, s.dt_us, s.dt_vs};
+}
+
 // bottom / top boundary condition of one field (kind 0: default fill / no flux)
 struct ZBc {
     int kind;

@@ -9,7 +9,7 @@ Mirrors, call for call:
   time_step!(model::RungeKutta3, Δt)                              src/TimeSteppers/runge_kutta_3.jl:77-151
   time_step!(model::QuasiAdamsBashforth2, Δt)                     src/TimeSteppers/quasi_adams_bashforth_2.jl:74-115
   cache_previous_tendencies!                                      src/TimeSteppers/store_tendencies.jl:12-22
-Julia's `f!` names are spelled `f` here.  forcing, stokes_drift, background_fields are `nothing`; advection is WENO()
+Julia's `f!` names are spelled `f` here.  forcing, background_fields are `nothing`; stokes_drift is UniformStokesDrift (stokes.py); advection is WENO()
 or Centered(); coriolis = FPlane, closure = ScalarDiffusivity, buoyancy = BuoyancyTracer / SeawaterBuoyancy and bottom /
 top Flux / Value / Gradient boundary conditions are the SURVEY §8(f) rank-1 terms (physics.py); anything else raises.
 """
@@ -30,6 +30,7 @@ from .architectures import stream_ptr
 from .fields import CenterField, Field, XFaceField, YFaceField, ZFaceField, fill_halo_regions
 from .grids import Bounded, Flat, require_regular_xy
 from .solvers import nonhydrostatic_pressure_solver
+from .stokes import DeviceStokesDrift, UniformStokesDrift
 
 
 class Clock:
@@ -86,9 +87,18 @@ class NonhydrostaticModel:
         """math_mode: None keeps the grid's (default: the process default, ocn.set_math_mode); MATH_STRICT / MATH_FAST pin this
         model's arithmetic variant whatever other models of the process use (ocn_grid.math)."""
         require_regular_xy(grid, "NonhydrostaticModel")
-        for name, val in (("forcing", forcing), ("stokes_drift", stokes_drift)):
-            if val is not None:
-                raise NotImplementedError(f"{name} != nothing is outside the MI355X hot-path scope (see DESIGN.md)")
+        if forcing is not None:
+            raise NotImplementedError("forcing != nothing is outside the MI355X hot-path scope (see DESIGN.md)")
+        # stokes_drift: UniformStokesDrift on one GPU (refused here, before anything is allocated, otherwise)
+        if stokes_drift is not None:
+            if not isinstance(stokes_drift, UniformStokesDrift):
+                raise NotImplementedError("stokes_drift must be UniformStokesDrift(...); the x- / y-dependent StokesDrift is not implemented (see DESIGN.md)")
+            if hasattr(grid.architecture, "partition"):
+                raise NotImplementedError("stokes_drift on a Distributed architecture is not implemented (see DESIGN.md)")
+            if grid.topology[2] == Flat:
+                raise NotImplementedError("UniformStokesDrift needs a non-Flat z")
+            if stokes_drift.grid is not None and (stokes_drift.grid.Nz, stokes_drift.grid.topology[2]) != (grid.Nz, grid.topology[2]):
+                raise ValueError("UniformStokesDrift(grid, ...) was built for another vertical grid")
         if advection is None:
             advection = Centered()  # the reference default (nonhydrostatic_model.jl:117)
         if not isinstance(advection, (WENO, Centered, UpwindBiased)):
@@ -126,6 +136,7 @@ class NonhydrostaticModel:
         self.advection = advection
         self.coriolis, self.closure, self.buoyancy = coriolis, closure, buoyancy
         self.clock = Clock()
+        self.stokes_drift = stokes_drift
         bcs = dict(boundary_conditions or {})
         # boundary conditions of the diffusivity fields: {"νₑ": FieldBoundaryConditions, "κₑ": {tracer: FieldBoundaryConditions}}
         # (build_diffusivity_fields, anisotropic_minimum_dissipation.jl:333-341); ASCII aliases nu_e / kappa_e
@@ -189,7 +200,10 @@ class NonhydrostaticModel:
         self._has_user_bcs = any(not b.is_default() for b in list(bcs.values()) + list(kappa_bcs.values()) + ([nu_bcs] if nu_bcs else []))
         self._has_flux_bcs = any(b.has_flux() for b in bcs.values())
         self.general_terms = (isinstance(advection, (Centered, UpwindBiased)) or coriolis is not None or closure is not None
-                              or buoyancy is not None or self._has_user_bcs)
+                              or buoyancy is not None or self._has_user_bcs or stokes_drift is not None)
+        # the profiles sampled on this grid's z nodes, as device vectors (struct ocn_stokes_drift); a model whose only extra term is the Stokes
+        # drift takes the general-terms route too (tiled WENO launch + finishing pass), not the correction-on-load kernel
+        self._stokes = DeviceStokesDrift(stokes_drift, grid) if stokes_drift is not None else None
         if self._has_user_bcs and hasattr(grid.architecture, "partition") and any(
                 s is not None and (s.values is not None or s.func is not None) for b in bcs.values() for s in b.sides.values()):
             raise NotImplementedError("array / function boundary conditions on a Distributed architecture are not implemented")
@@ -424,8 +438,13 @@ def compute_tendencies_(model, rng=None, boundary_contributions=True):
     s = stream_ptr()
     if model.general_terms:
         t = C.byref(model._terms)
-        _lib.call("ocn_compute_momentum_tendencies_terms", g.cref, t, model.u.ptr, model.v.ptr, model.w.ptr, Gn[0].ptr,
-                  Gn[1].ptr, Gn[2].ptr, r, s)
+        if model._stokes is not None:
+            model._stokes.refresh(model.clock.time)  # profiles that depend on t: sampled at the time of this tendency evaluation
+            _lib.call("ocn_compute_momentum_tendencies_terms_stokes", g.cref, t, C.byref(model._stokes.c), model.u.ptr, model.v.ptr, model.w.ptr,
+                      Gn[0].ptr, Gn[1].ptr, Gn[2].ptr, r, s)
+        else:
+            _lib.call("ocn_compute_momentum_tendencies_terms", g.cref, t, model.u.ptr, model.v.ptr, model.w.ptr, Gn[0].ptr,
+                      Gn[1].ptr, Gn[2].ptr, r, s)
         for n, c in enumerate(model.tracers):
             kappa, kappa_e = 0.0, None
             if model.diffusivity_fields is not None:
@@ -608,12 +627,19 @@ def _update_state_and_rk3_substep_general(model, dt, gamma, zeta, fill_halos=Tru
     z, hz = (0.0, 0) if zeta is None else (float(zeta), 1)
     t = C.byref(model._terms)
     momentum_extra = (model.coriolis is not None or model.closure is not None or model.buoyancy is not None
-                      or isinstance(model.advection, (Centered, UpwindBiased)) or _bcs_ref(model.u, g) is not None or _bcs_ref(model.v, g) is not None)
+                      or isinstance(model.advection, (Centered, UpwindBiased)) or _bcs_ref(model.u, g) is not None or _bcs_ref(model.v, g) is not None
+                      or model._stokes is not None)
+    if model._stokes is not None:
+        model._stokes.refresh(model.clock.time)
 
     def launch(rng=None):
         s = stream_ptr()  # read HERE: the Distributed hook runs the east buffer strip under torch.cuda.stream(side stream)
         r = None if rng is None else _lib.i32_array(list(rng))
-        if momentum_extra:
+        if model._stokes is not None:
+            _lib.call("ocn_compute_momentum_tendencies_terms_rk3_stokes", g.cref, t, C.byref(model._stokes.c), _bcs_ref(model.u, g),
+                      _bcs_ref(model.v, g), model.u.ptr, model.v.ptr, model.w.ptr, Gn[0].ptr, Gn[1].ptr, Gn[2].ptr, Gm[0].ptr, Gm[1].ptr,
+                      Gm[2].ptr, alt[0].data_ptr(), alt[1].data_ptr(), alt[2].data_ptr(), float(dt), float(gamma), z, hz, r, s)
+        elif momentum_extra:
             _lib.call("ocn_compute_momentum_tendencies_terms_rk3", g.cref, t, _bcs_ref(model.u, g), _bcs_ref(model.v, g),
                       model.u.ptr, model.v.ptr, model.w.ptr, Gn[0].ptr, Gn[1].ptr, Gn[2].ptr, Gm[0].ptr, Gm[1].ptr, Gm[2].ptr,
                       alt[0].data_ptr(), alt[1].data_ptr(), alt[2].data_ptr(), float(dt), float(gamma), z, hz, r, s)
@@ -842,6 +868,9 @@ class ModelRK3Driver:
                 b = getattr(f, "boundary_conditions", None)
                 if b is not None and not b.is_default():
                     raise NotImplementedError("ModelRK3Driver: boundary conditions on the diffusivity fields need the Python host")
+        if model._stokes is not None and not model.stokes_drift.steady:
+            raise NotImplementedError("ModelRK3Driver: a time-dependent UniformStokesDrift needs the Python host (time_step(model, dt) samples the "
+                                      "profiles at every tendency evaluation); pass steady=True for profiles that do not depend on t")
         flush_tendencies(model)
         self.model = model
         desc = _lib.CModelDriverDesc()
@@ -886,6 +915,8 @@ class ModelRK3Driver:
         else:
             _lib.call("ocn_model_driver_create", C.byref(self._h), model.grid.cref, C.byref(desc), model.u.ptr, model.v.ptr, model.w.ptr,
                       model.pNHS.ptr, None if own_solver else model.pressure_solver._h, stream_ptr())
+        if model._stokes is not None:  # steady profiles: the device vectors stay the model's
+            _lib.call("ocn_model_driver_set_stokes_drift", self._h, C.byref(model._stokes.c), 0)
 
     def time_step(self, dt):
         _lib.call("ocn_model_driver_time_step", self._h, float(dt), stream_ptr())
