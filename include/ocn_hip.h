@@ -332,6 +332,45 @@ int ocn_compute_tracer_tendency_terms_rk3(const ocn_grid *grid, const ocn_model_
                                           const double *c, double *Gc, const double *Gmc, double *c_out, double dt, double gamma,
                                           double zeta, int32_t has_zeta, const int32_t *range, void *stream);
 
+/* forcing = (u = ..., T = ...) (src/Forcings): what the host sampled of the forcing of ONE field, up to OCN_FORCING_MAX_TERMS terms summed
+ * left to right as MultipleForcings does (multiple_forcings.jl:34-46):  F = t1; F = F + t2; ...  The device never evaluates a user function. */
+#define OCN_FORCING_MAX_TERMS 4
+#define OCN_FORCING_ARRAY 1        /* F = values[offset of (i, j, k) in the field's parent array] */
+#define OCN_FORCING_RELAXATION 2   /* F = (rate * mask) * (target - field[i, j, k])   (relaxation.jl:95-101) */
+/* mask_dim / target_dim: -1 the number (mask 1 / target_value); 0, 1, 2: a DEVICE vector along x / y / z indexed like the parent array along
+ * that direction (element 0 <-> index 1 - H, as terms.yc / yf); 3: a DEVICE array in the field's parent layout */
+typedef struct ocn_forcing_term { int32_t kind, mask_dim, target_dim, _pad; double rate, target_value;
+                                  const double *values, *mask, *target; } ocn_forcing_term;
+typedef struct ocn_forcing { int32_t n_terms, _pad; ocn_forcing_term term[OCN_FORCING_MAX_TERMS]; } ocn_forcing;   /* of ONE field */
+/* ocn_compute_momentum_tendencies_terms_stokes / ..._rk3_stokes with the forcing of u, v, w added after the Stokes-drift terms, as the last
+ * addend of the reference's tendency functions (nonhydrostatic_tendency_kernel_functions.jl:77, 137, 199):  G <- G + F  inside the finishing
+ * pass, on the cells that pass writes (not the wall faces); in the _rk3 form the bottom / top flux contributions and the substep follow.
+ * forcing: NULL, or three entries (u, v, w), each NULL or an ocn_forcing.  stokes may be NULL.  All-NULL forcing is exactly the _stokes entry
+ * point.  OCN_ERR_INVALID_ARGUMENT (no device memory touched) for n_terms outside 0 .. OCN_FORCING_MAX_TERMS, an unknown kind, a NULL
+ * pointer where a kind / dim says there is one, a dim outside -1 .. 3, or a vector along a Flat direction. */
+int ocn_compute_momentum_tendencies_terms_forced(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_stokes_drift *stokes,
+                                                 const ocn_forcing *const *forcing, const double *u, const double *v, const double *w,
+                                                 double *Gu, double *Gv, double *Gw, const int32_t *range, void *stream);
+int ocn_compute_momentum_tendencies_terms_rk3_forced(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_stokes_drift *stokes,
+                                                     const ocn_forcing *const *forcing, const ocn_field_bcs *bcs_u, const ocn_field_bcs *bcs_v,
+                                                     const double *u, const double *v, const double *w, double *Gu, double *Gv, double *Gw,
+                                                     const double *Gmu, const double *Gmv, const double *Gmw, double *u_out, double *v_out,
+                                                     double *w_out, double dt, double gamma, double zeta, int32_t has_zeta,
+                                                     const int32_t *range, void *stream);
+/* ocn_compute_tracer_tendency_terms / ..._terms_rk3 with the forcing of the tracer added after the diffusion term
+ * (nonhydrostatic_tendency_kernel_functions.jl:258), before the bottom / top flux contributions and the substep: inside the tracer kernels
+ * (the _rk3 form stays ONE launch on Periodic x, y and on the interior box; the frames run their per-cell kernels).  Only Centered(order=2)
+ * advection on Periodic x, y, whose kernel has no epilogue, adds F in a small kernel of its own after the diffusion kernel.  forcing == NULL
+ * is exactly the entry point without the suffix.  There is no forced form of ocn_compute_tracer_pair_tendency_terms_rk3 (an option that is
+ * off by default): a tracer pair in which either tracer is forced runs as two single launches. */
+int ocn_compute_tracer_tendency_terms_forced(const ocn_grid *grid, const ocn_model_terms *terms, double kappa, const double *kappa_e,
+                                             const ocn_forcing *forcing, const double *u, const double *v, const double *w, const double *c,
+                                             double *Gc, const int32_t *range, void *stream);
+int ocn_compute_tracer_tendency_terms_rk3_forced(const ocn_grid *grid, const ocn_model_terms *terms, double kappa, const double *kappa_e,
+                                                 const ocn_forcing *forcing, const ocn_field_bcs *bcs_c, const double *u, const double *v,
+                                                 const double *w, const double *c, double *Gc, const double *Gmc, double *c_out, double dt,
+                                                 double gamma, double zeta, int32_t has_zeta, const int32_t *range, void *stream);
+
 /* ---- NaN check ----
  * hasnan(field) = any(isnan, parent(field)) (src/Models/nan_checker.jl:33).  Scans n_elements doubles (the whole parent array)
  * and sets *flag_device (a DEVICE int32 the caller zeroed) to 1 if any is NaN; asynchronous, the caller reads the flag when
@@ -572,6 +611,12 @@ int ocn_model_driver_flush(ocn_model_driver_t driver, void *stream);
  * are deferred); the next time step recomputes the tendencies of the current state.  time_dependent != 0 (profiles that the host must resample at every stage) is refused with OCN_ERR_INVALID_ARGUMENT: that
  * case needs the Python host (time_step(model, dt)), which samples the profiles at clock.time of every tendency evaluation. */
 int ocn_model_driver_set_stokes_drift(ocn_model_driver_t driver, const ocn_stokes_drift *stokes, int32_t time_dependent);
+/* A STEADY forcing for every following time step: 3 + n_tracers entries (u, v, w, the tracers in the driver's order), each NULL or an
+ * ocn_forcing whose device vectors / arrays are the caller's and must outlive the driver (the structs themselves are copied); forcing == NULL
+ * switches every term off again.  Same preconditions as ocn_model_driver_set_stokes_drift: not while a step's tendencies are deferred, not on
+ * a slab-x rank; time_dependent != 0 (a Forcing(func) or a Relaxation target that the host must resample at every stage) is refused with
+ * OCN_ERR_INVALID_ARGUMENT -- that case needs the Python host (time_step(model, dt)). */
+int ocn_model_driver_set_forcing(ocn_model_driver_t driver, const ocn_forcing *const *forcing, int32_t time_dependent);
 /* where field f (0, 1, 2 = u, v, w; 3 + n = tracer n) and its G^n are right now */
 int ocn_model_driver_field(ocn_model_driver_t driver, int32_t f, double **field, double **G);
 

@@ -25,6 +25,7 @@ from .physics import (AnisotropicMinimumDissipation, BetaPlane, BoundaryConditio
                       GradientBoundaryCondition, LinearEquationOfState, OpenBoundaryCondition, ScalarDiffusivity, SeawaterBuoyancy,
                       ValueBoundaryCondition)
 from .stokes import StokesDrift, UniformStokesDrift
+from .forcings import AdvectiveForcing, Forcing, GaussianMask, LinearTarget, Relaxation
 from .solvers import (BatchedTridiagonalSolver, FFTBasedPoissonSolver, FourierTridiagonalPoissonSolver, XDirection, YDirection, ZDirection,
                       nonhydrostatic_pressure_solver, solve, stretched_direction)
 

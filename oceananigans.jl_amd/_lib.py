@@ -45,6 +45,20 @@ class CStokesDrift(C.Structure):
                 ("dt_us", C.c_void_p), ("dt_vs", C.c_void_p)]
 
 
+FORCING_MAX_TERMS = 4
+
+
+class CForcingTerm(C.Structure):
+    """struct ocn_forcing_term: one sampled term (kind 1 array, 2 relaxation; *_dim -1 number, 0 / 1 / 2 vector along x / y / z, 3 parent array)"""
+    _fields_ = [("kind", C.c_int32), ("mask_dim", C.c_int32), ("target_dim", C.c_int32), ("_pad", C.c_int32), ("rate", C.c_double),
+                ("target_value", C.c_double), ("values", C.c_void_p), ("mask", C.c_void_p), ("target", C.c_void_p)]
+
+
+class CForcing(C.Structure):
+    """struct ocn_forcing: the forcing of ONE field"""
+    _fields_ = [("n_terms", C.c_int32), ("_pad", C.c_int32), ("term", CForcingTerm * FORCING_MAX_TERMS)]
+
+
 class CBc(C.Structure):
     """struct ocn_bc"""
     _fields_ = [("kind", C.c_int32), ("_pad", C.c_int32), ("value", C.c_double), ("coeff", C.c_double), ("values", C.c_void_p)]
@@ -108,6 +122,15 @@ _SIGS = {
                                                      C.POINTER(_i32), _vp],
     "ocn_compute_momentum_tendencies_terms_rk3_stokes": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CStokesDrift), C.POINTER(CFieldBcs),
                                                          C.POINTER(CFieldBcs)] + [_vp] * 12 + [_dbl, _dbl, _dbl, _i32, C.POINTER(_i32), _vp],
+    "ocn_compute_momentum_tendencies_terms_forced": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CStokesDrift),
+                                                     C.POINTER(C.POINTER(CForcing)), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32), _vp],
+    "ocn_compute_momentum_tendencies_terms_rk3_forced": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CStokesDrift),
+                                                         C.POINTER(C.POINTER(CForcing)), C.POINTER(CFieldBcs), C.POINTER(CFieldBcs)]
+                                                        + [_vp] * 12 + [_dbl, _dbl, _dbl, _i32, C.POINTER(_i32), _vp],
+    "ocn_compute_tracer_tendency_terms_forced": [C.POINTER(CGrid), C.POINTER(CModelTerms), _dbl, _vp, C.POINTER(CForcing), _vp, _vp, _vp, _vp, _vp,
+                                                 C.POINTER(_i32), _vp],
+    "ocn_compute_tracer_tendency_terms_rk3_forced": [C.POINTER(CGrid), C.POINTER(CModelTerms), _dbl, _vp, C.POINTER(CForcing), C.POINTER(CFieldBcs)]
+                                                    + [_vp] * 7 + [_dbl, _dbl, _dbl, _i32, C.POINTER(_i32), _vp],
     "ocn_compute_tracer_tendency_terms_rk3": [C.POINTER(CGrid), C.POINTER(CModelTerms), _dbl, _vp, C.POINTER(CFieldBcs)]
                                              + [_vp] * 7 + [_dbl, _dbl, _dbl, _i32, C.POINTER(_i32), _vp],
     "ocn_compute_tracer_pair_tendency_terms_rk3": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(_dbl), C.POINTER(_vp),
@@ -171,6 +194,7 @@ _SIGS = {
     "ocn_model_driver_flush": [_vp, _vp],
     "ocn_model_driver_field": [_vp, _i32, C.POINTER(_vp), C.POINTER(_vp)],
     "ocn_model_driver_set_stokes_drift": [_vp, C.POINTER(CStokesDrift), _i32],
+    "ocn_model_driver_set_forcing": [_vp, C.POINTER(C.POINTER(CForcing)), _i32],
     "ocn_halo_plane_x": [C.POINTER(CGrid), _vp, _i32, _i32, _vp, _i32, _vp],
     "ocn_halo_pack_pressure": [C.POINTER(CGrid), _vp, _vp, _dbl, _vp, _vp, _vp],
     "ocn_halo_unpack_pressure": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _vp],
@@ -251,6 +275,11 @@ def call(name, *args):
 
 def ptr_array(ptrs):
     return (C.c_void_p * len(ptrs))(*ptrs)
+
+
+def forcing_array(refs):
+    """const ocn_forcing *const[]: one entry per field, None = the field is not forced"""
+    return (C.POINTER(CForcing) * len(refs))(*[(r if r is not None else C.POINTER(CForcing)()) for r in refs])
 
 
 def i32_array(vals):

@@ -365,22 +365,22 @@ static int launch_advective_momentum(int advection, const ocn_grid *grid, const 
     }
 }
 static int launch_advective_tracer(int advection, const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c,
-                                   double *Gc, const int32_t *range, hipStream_t s, const TracerFuse *tf)
+                                   double *Gc, const int32_t *range, hipStream_t s, const TracerFuse *tf, const ocn::ForcingDev *frc = nullptr)
 {
     const bool strict = strict_math(grid);
     if (!xy_periodic(grid)) {  // (tf: diffusion / bottom and top fluxes / the next substep ride along, general.hip)
         const int c2 = advection == OCN_ADVECTION_CENTERED2;
         if (advection == OCN_ADVECTION_UPWIND5)
-            return strict ? ocn_strict_up::launch_tracer_tendency_general(grid, 0, u, v, w, c, Gc, range, s, tf)
-                          : ocn_fast_up::launch_tracer_tendency_general(grid, 0, u, v, w, c, Gc, range, s, tf);
-        return strict ? ocn_strict::launch_tracer_tendency_general(grid, c2, u, v, w, c, Gc, range, s, tf)
-                      : ocn_fast::launch_tracer_tendency_general(grid, c2, u, v, w, c, Gc, range, s, tf);
+            return strict ? ocn_strict_up::launch_tracer_tendency_general(grid, 0, u, v, w, c, Gc, range, s, tf, frc)
+                          : ocn_fast_up::launch_tracer_tendency_general(grid, 0, u, v, w, c, Gc, range, s, tf, frc);
+        return strict ? ocn_strict::launch_tracer_tendency_general(grid, c2, u, v, w, c, Gc, range, s, tf, frc)
+                      : ocn_fast::launch_tracer_tendency_general(grid, c2, u, v, w, c, Gc, range, s, tf, frc);
     }
     switch (advection) {
         case OCN_ADVECTION_WENO5:
-            return strict ? ocn_strict::launch_tracer_tendency(grid, u, v, w, c, Gc, range, s, tf) : ocn_fast::launch_tracer_tendency(grid, u, v, w, c, Gc, range, s, tf);
+            return strict ? ocn_strict::launch_tracer_tendency(grid, u, v, w, c, Gc, range, s, tf, frc) : ocn_fast::launch_tracer_tendency(grid, u, v, w, c, Gc, range, s, tf, frc);
         case OCN_ADVECTION_UPWIND5:
-            return strict ? ocn_strict_up::launch_tracer_tendency(grid, u, v, w, c, Gc, range, s, tf) : ocn_fast_up::launch_tracer_tendency(grid, u, v, w, c, Gc, range, s, tf);
+            return strict ? ocn_strict_up::launch_tracer_tendency(grid, u, v, w, c, Gc, range, s, tf, frc) : ocn_fast_up::launch_tracer_tendency(grid, u, v, w, c, Gc, range, s, tf, frc);
         default:
             return strict ? ocn_strict::launch_tracer_centered2(grid, u, v, w, c, Gc, range, s) : ocn_fast::launch_tracer_centered2(grid, u, v, w, c, Gc, range, s);
     }
@@ -394,9 +394,54 @@ static int validate_stokes(const ocn_grid *grid, const ocn_stokes_drift *stokes,
     return OCN_SUCCESS;
 }
 
+// forcing of one field: only the descriptor is looked at (host memory), never what its device pointers point to
+}  // extern "C"
+int ocn::validate_forcing(const ocn_grid *grid, const ocn_forcing *f, const char *who, const char *field)
+{
+    if (!f) return OCN_SUCCESS;
+    OCN_REQUIRE(f->n_terms >= 0 && f->n_terms <= OCN_FORCING_MAX_TERMS, "%s: forcing of %s has n_terms = %d outside 0..%d", who, field, f->n_terms,
+                OCN_FORCING_MAX_TERMS);
+    const int topo[3] = {grid->tx, grid->ty, grid->tz};
+    for (int q = 0; q < f->n_terms; ++q) {
+        const ocn_forcing_term &t = f->term[q];
+        OCN_REQUIRE(t.kind == OCN_FORCING_ARRAY || t.kind == OCN_FORCING_RELAXATION, "%s: forcing of %s, term %d: unknown kind %d", who, field, q, t.kind);
+        if (t.kind == OCN_FORCING_ARRAY) {
+            OCN_REQUIRE(t.values != nullptr, "%s: forcing of %s, term %d: values is NULL", who, field, q);
+            continue;
+        }
+        const int dims[2] = {t.mask_dim, t.target_dim};
+        const double *ptrs[2] = {t.mask, t.target};
+        for (int m = 0; m < 2; ++m) {
+            const char *what = m ? "target" : "mask";
+            OCN_REQUIRE(dims[m] >= -1 && dims[m] <= 3, "%s: forcing of %s, term %d: %s_dim = %d outside -1..3", who, field, q, what, dims[m]);
+            OCN_REQUIRE(dims[m] < 0 || ptrs[m] != nullptr, "%s: forcing of %s, term %d: %s is NULL but %s_dim = %d", who, field, q, what, what, dims[m]);
+            OCN_REQUIRE(dims[m] < 0 || dims[m] > 2 || topo[dims[m]] != OCN_FLAT, "%s: forcing of %s, term %d: %s varies along a Flat direction (%d)", who,
+                        field, q, what, dims[m]);
+        }
+    }
+    return OCN_SUCCESS;
+}
+extern "C" {
+// u, v, w: *md is filled and *any says whether a term is present
+static int momentum_forcing(const ocn_grid *grid, const ocn_forcing *const *forcing, const char *who, ocn::MomentumForcingDev *md, bool *any)
+{
+    static const char *names[3] = {"u", "v", "w"};
+    *any = false;
+    *md = ocn::MomentumForcingDev{};
+    if (!forcing) return OCN_SUCCESS;
+    OCN_REQUIRE(grid != nullptr, "grid is NULL");
+    for (int f = 0; f < 3; ++f) {
+        int st = validate_forcing(grid, forcing[f], who, names[f]);
+        if (st != OCN_SUCCESS) return st;
+        md->f[f] = ocn::to_dev(forcing[f]);
+        *any = *any || md->f[f].n > 0;
+    }
+    return OCN_SUCCESS;
+}
+
 static int momentum_tendencies_terms(const char *who, const ocn_grid *grid, const ocn_model_terms *terms, const ocn_stokes_drift *stokes,
                                      const double *u, const double *v, const double *w, double *Gu, double *Gv, double *Gw,
-                                     const int32_t *range, void *stream)
+                                     const int32_t *range, void *stream, const ocn::MomentumForcingDev *pfd = nullptr)
 {
     int st = validate_terms(grid, terms);
     if (st != OCN_SUCCESS) return st;
@@ -406,16 +451,16 @@ static int momentum_tendencies_terms(const char *who, const ocn_grid *grid, cons
     hipStream_t s = as_stream(stream);
     st = launch_advective_momentum(terms->advection, grid, u, v, w, Gu, Gv, Gw, range, s);
     if (st != OCN_SUCCESS) return st;
-    if (!(terms->coriolis || terms->closure || terms->buoyancy || stokes)) return OCN_SUCCESS;
+    if (!(terms->coriolis || terms->closure || terms->buoyancy || stokes || pfd)) return OCN_SUCCESS;
     TermsDev t = to_dev(*terms);
     ocn::StokesDev sd{};
     if (stokes) sd = ocn::to_dev(*stokes);
     const ocn::StokesDev *psd = stokes ? &sd : nullptr;
     if (!xy_periodic(grid))
-        return strict ? ocn_strict::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, psd)
-                      : ocn_fast::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, psd);
-    return strict ? ocn_strict::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, psd)
-                  : ocn_fast::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, psd);
+        return strict ? ocn_strict::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, psd, pfd)
+                      : ocn_fast::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, psd, pfd);
+    return strict ? ocn_strict::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, psd, pfd)
+                  : ocn_fast::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, psd, pfd);
 }
 
 int ocn_compute_momentum_tendencies_terms(const ocn_grid *grid, const ocn_model_terms *terms, const double *u, const double *v,
@@ -434,6 +479,23 @@ int ocn_compute_momentum_tendencies_terms_stokes(const ocn_grid *grid, const ocn
     int st = validate_stokes(grid, stokes, "ocn_compute_momentum_tendencies_terms_stokes");
     if (st != OCN_SUCCESS) return st;
     return momentum_tendencies_terms("ocn_compute_momentum_tendencies_terms_stokes", grid, terms, stokes, u, v, w, Gu, Gv, Gw, range, stream);
+}
+
+int ocn_compute_momentum_tendencies_terms_forced(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_stokes_drift *stokes,
+                                                 const ocn_forcing *const *forcing, const double *u, const double *v, const double *w,
+                                                 double *Gu, double *Gv, double *Gw, const int32_t *range, void *stream)
+{
+    const char *who = "ocn_compute_momentum_tendencies_terms_forced";
+    ocn::MomentumForcingDev md;
+    bool any;
+    int st = momentum_forcing(grid, forcing, who, &md, &any);
+    if (st != OCN_SUCCESS) return st;
+    if (!any) return ocn_compute_momentum_tendencies_terms_stokes(grid, terms, stokes, u, v, w, Gu, Gv, Gw, range, stream);
+    if (stokes) {
+        st = validate_stokes(grid, stokes, who);
+        if (st != OCN_SUCCESS) return st;
+    }
+    return momentum_tendencies_terms(who, grid, terms, stokes, u, v, w, Gu, Gv, Gw, range, stream, &md);
 }
 
 // the extra terms alone, added to a G that already holds what precedes them in the reference's sum (used by the hydrostatic
@@ -707,7 +769,8 @@ static int momentum_tendencies_terms_rk3(const char *who, const ocn_grid *grid, 
                                          const ocn_field_bcs *bcs_u, const ocn_field_bcs *bcs_v, const double *u, const double *v,
                                          const double *w, double *Gu, double *Gv, double *Gw, const double *Gmu, const double *Gmv,
                                          const double *Gmw, double *u_out, double *v_out, double *w_out, double dt, double gamma,
-                                         double zeta, int32_t has_zeta, const int32_t *range, void *stream)
+                                         double zeta, int32_t has_zeta, const int32_t *range, void *stream,
+                                         const ocn::MomentumForcingDev *pfd = nullptr)
 {
     int st = validate_terms(grid, terms);
     if (st != OCN_SUCCESS) return st;
@@ -735,8 +798,8 @@ static int momentum_tendencies_terms_rk3(const char *who, const ocn_grid *grid, 
         // inside the tiled kernel on the interior box, as per-cell kernels on the frames (general.hip)
         st = launch_advective_momentum(terms->advection, grid, u, v, w, Gu, Gv, Gw, nullptr, s);
         if (st != OCN_SUCCESS) return st;
-        return strict ? ocn_strict::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, nullptr, s, &mf, psd)
-                      : ocn_fast::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, nullptr, s, &mf, psd);
+        return strict ? ocn_strict::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, nullptr, s, &mf, psd, pfd)
+                      : ocn_fast::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, nullptr, s, &mf, psd, pfd);
     }
     static const bool extra_first = !(std::getenv("OCN_EXTRA_FIRST") && std::getenv("OCN_EXTRA_FIRST")[0] == '0');
     if (!strict && extra_first && terms->advection != OCN_ADVECTION_CENTERED2) {
@@ -748,7 +811,7 @@ static int momentum_tendencies_terms_rk3(const char *who, const ocn_grid *grid, 
         MomentumFinal pre = mf;
         pre.pre = 1;
         pre.sc.on = 0;
-        st = ocn_fast::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, &pre, psd);
+        st = ocn_fast::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, &pre, psd, pfd);
         if (st != OCN_SUCCESS) return st;
         FuseArgs fz{};
         fz.Gm[0] = Gmu; fz.Gm[1] = Gmv; fz.Gm[2] = Gmw;
@@ -760,8 +823,8 @@ static int momentum_tendencies_terms_rk3(const char *who, const ocn_grid *grid, 
     }
     st = launch_advective_momentum(terms->advection, grid, u, v, w, Gu, Gv, Gw, range, s);
     if (st != OCN_SUCCESS) return st;
-    return strict ? ocn_strict::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, &mf, psd)
-                  : ocn_fast::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, &mf, psd);
+    return strict ? ocn_strict::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, &mf, psd, pfd)
+                  : ocn_fast::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, &mf, psd, pfd);
 }
 
 int ocn_compute_momentum_tendencies_terms_rk3(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_field_bcs *bcs_u,
@@ -789,6 +852,29 @@ int ocn_compute_momentum_tendencies_terms_rk3_stokes(const ocn_grid *grid, const
     }
     return momentum_tendencies_terms_rk3(who, grid, terms, stokes, bcs_u, bcs_v, u, v, w, Gu, Gv, Gw, Gmu, Gmv, Gmw, u_out, v_out, w_out, dt,
                                          gamma, zeta, has_zeta, range, stream);
+}
+
+int ocn_compute_momentum_tendencies_terms_rk3_forced(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_stokes_drift *stokes,
+                                                     const ocn_forcing *const *forcing, const ocn_field_bcs *bcs_u, const ocn_field_bcs *bcs_v,
+                                                     const double *u, const double *v, const double *w, double *Gu, double *Gv, double *Gw,
+                                                     const double *Gmu, const double *Gmv, const double *Gmw, double *u_out, double *v_out,
+                                                     double *w_out, double dt, double gamma, double zeta, int32_t has_zeta,
+                                                     const int32_t *range, void *stream)
+{
+    const char *who = "ocn_compute_momentum_tendencies_terms_rk3_forced";
+    ocn::MomentumForcingDev md;
+    bool any;
+    int st = momentum_forcing(grid, forcing, who, &md, &any);
+    if (st != OCN_SUCCESS) return st;
+    if (!any)
+        return ocn_compute_momentum_tendencies_terms_rk3_stokes(grid, terms, stokes, bcs_u, bcs_v, u, v, w, Gu, Gv, Gw, Gmu, Gmv, Gmw, u_out, v_out,
+                                                                w_out, dt, gamma, zeta, has_zeta, range, stream);
+    if (stokes) {
+        st = validate_stokes(grid, stokes, who);
+        if (st != OCN_SUCCESS) return st;
+    }
+    return momentum_tendencies_terms_rk3(who, grid, terms, stokes, bcs_u, bcs_v, u, v, w, Gu, Gv, Gw, Gmu, Gmv, Gmw, u_out, v_out, w_out, dt,
+                                         gamma, zeta, has_zeta, range, stream, &md);
 }
 
 int ocn_compute_tracer_tendency_terms_rk3(const ocn_grid *grid, const ocn_model_terms *terms, double kappa, const double *kappa_e,
@@ -853,6 +939,71 @@ int ocn_compute_tracer_pair_tendency_terms_rk3(const ocn_grid *grid, const ocn_m
                     : ocn_fast_up::launch_tracer_pair_tendency(grid, u, v, w, c, Gc, range, s, tf, &did);
     *launched = did;
     return st;
+}
+
+// A forced tracer: F rides inside the tracer kernels (tracer_finish / tracer_finish_general compiled with ocn::TracerFuseForced), between the
+// diffusion and the boundary fluxes.  Only Centered(order=2) advection on a (Periodic, Periodic, *) grid, whose kernel has no epilogue, takes
+// the small tracer_forcing_kernel after the diffusion kernel.
+int ocn_compute_tracer_tendency_terms_forced(const ocn_grid *grid, const ocn_model_terms *terms, double kappa, const double *kappa_e,
+                                             const ocn_forcing *forcing, const double *u, const double *v, const double *w, const double *c,
+                                             double *Gc, const int32_t *range, void *stream)
+{
+    if (forcing) {
+        OCN_REQUIRE(grid != nullptr, "grid is NULL");
+        int st = validate_forcing(grid, forcing, "ocn_compute_tracer_tendency_terms_forced", "the tracer");
+        if (st != OCN_SUCCESS) return st;
+    }
+    if (!forcing || forcing->n_terms == 0) return ocn_compute_tracer_tendency_terms(grid, terms, kappa, kappa_e, u, v, w, c, Gc, range, stream);
+    int st = validate_terms(grid, terms);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(u && v && w && c && Gc, "ocn_compute_tracer_tendency_terms_forced: null field pointer");
+    OCN_REQUIRE(!kappa_e || terms->closure == 2, "kappa_e is only meaningful with closure == 2");
+    const ocn::ForcingDev fd = ocn::to_dev(forcing);
+    if (terms->advection == OCN_ADVECTION_CENTERED2 && xy_periodic(grid)) {
+        st = ocn_compute_tracer_tendency_terms(grid, terms, kappa, kappa_e, u, v, w, c, Gc, range, stream);
+        if (st != OCN_SUCCESS) return st;
+        return strict_math(grid) ? ocn_strict::launch_tracer_forcing(grid, fd, c, Gc, range, nullptr, as_stream(stream))
+                                 : ocn_fast::launch_tracer_forcing(grid, fd, c, Gc, range, nullptr, as_stream(stream));
+    }
+    TracerFuse tf{};  // advection, diffusion and F in one pass
+    tf.diffusion = terms->closure != 0;
+    tf.kappa = kappa;
+    tf.kappa_e = kappa_e;
+    return launch_advective_tracer(terms->advection, grid, u, v, w, c, Gc, range, as_stream(stream), &tf, &fd);
+}
+
+int ocn_compute_tracer_tendency_terms_rk3_forced(const ocn_grid *grid, const ocn_model_terms *terms, double kappa, const double *kappa_e,
+                                                 const ocn_forcing *forcing, const ocn_field_bcs *bcs_c, const double *u, const double *v,
+                                                 const double *w, const double *c, double *Gc, const double *Gmc, double *c_out, double dt,
+                                                 double gamma, double zeta, int32_t has_zeta, const int32_t *range, void *stream)
+{
+    const char *who = "ocn_compute_tracer_tendency_terms_rk3_forced";
+    if (forcing) {
+        OCN_REQUIRE(grid != nullptr, "grid is NULL");
+        int st = validate_forcing(grid, forcing, who, "the tracer");
+        if (st != OCN_SUCCESS) return st;
+    }
+    if (!forcing || forcing->n_terms == 0)
+        return ocn_compute_tracer_tendency_terms_rk3(grid, terms, kappa, kappa_e, bcs_c, u, v, w, c, Gc, Gmc, c_out, dt, gamma, zeta, has_zeta, range,
+                                                     stream);
+    int st = validate_terms(grid, terms);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(xy_periodic(grid) || !range, "%s: ranges need Periodic x and y", who);
+    OCN_REQUIRE(terms->advection != OCN_ADVECTION_CENTERED2, "%s: advection must be WENO5 or UpwindBiased5", who);
+    OCN_REQUIRE(u && v && w && c && Gc && c_out, "%s: null field pointer", who);
+    OCN_REQUIRE(!has_zeta || Gmc, "%s: G⁻ is required when has_zeta != 0", who);
+    OCN_REQUIRE(c_out != c, "%s: the output must not alias the input", who);
+    OCN_REQUIRE(!kappa_e || terms->closure == 2, "kappa_e is only meaningful with closure == 2");
+    TracerFuse tf{};
+    tf.diffusion = terms->closure != 0;
+    tf.kappa = kappa;
+    tf.kappa_e = kappa_e;
+    st = flux_side(grid, bcs_c, "tracer", tf.bottom, tf.top);
+    if (st != OCN_SUCCESS) return st;
+    tf.sub = SubstepDev{Gmc, c_out};
+    tf.sc = SubstepCoef{dt, gamma, zeta, 1, has_zeta ? 1 : 0};
+    const ocn::ForcingDev fd = ocn::to_dev(forcing);
+    return launch_advective_tracer(terms->advection, grid, u, v, w, c, Gc, range, as_stream(stream), &tf, &fd);  // ONE launch, as without forcing
 }
 
 int ocn_split_explicit_substeps_blocked(const ocn_grid *grid, int32_t n, const double *weights, double dtau, double gravitational_acceleration,

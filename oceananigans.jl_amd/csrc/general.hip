@@ -258,6 +258,7 @@ __device__ __forceinline__ double gen_buoyancy(const ocn::TermsDev &t, long long
 // the kernel without and with the Stokes-drift terms (see momentum_extra_general.inc)
 #define OCN_EXTRA_GENERAL momentum_extra_general
 #define OCN_EXTRA_STK 0
+#define OCN_EXTRA_FRC 0
 #define OCN_EXTRA_SD_PARAM
 #include "momentum_extra_general.inc"
 #undef OCN_EXTRA_GENERAL
@@ -268,7 +269,16 @@ __device__ __forceinline__ double gen_buoyancy(const ocn::TermsDev &t, long long
 #define OCN_EXTRA_SD_PARAM ocn::StokesDev sd,
 #include "momentum_extra_general.inc"
 #undef OCN_EXTRA_GENERAL
+#undef OCN_EXTRA_FRC
+#undef OCN_EXTRA_SD_PARAM
+// ... and the one variant with the forcing terms (both descriptors, either may be empty)
+#define OCN_EXTRA_GENERAL momentum_extra_general_forced
+#define OCN_EXTRA_FRC 1
+#define OCN_EXTRA_SD_PARAM ocn::StokesDev sd, ocn::MomentumForcingDev fd,
+#include "momentum_extra_general.inc"
+#undef OCN_EXTRA_GENERAL
 #undef OCN_EXTRA_STK
+#undef OCN_EXTRA_FRC
 #undef OCN_EXTRA_SD_PARAM
 
 // Gc <- Gc - ∇_dot_qᶜ (closure_kernel_operators.jl:48-53), κ a number or the eddy diffusivity field interpolated to the faces
@@ -347,7 +357,9 @@ __global__ __launch_bounds__(256) void momentum_finish_general(gen::Fields F, do
     }
 }
 
-__global__ __launch_bounds__(256) void tracer_finish_general(GridDev g, const double *__restrict__ c, double *__restrict__ Gc, ocn::TracerFuse tf,
+// TF = ocn::TracerFuseForced: the sampled forcing of the tracer first (after the diffusion kernel, before the fluxes: the order of tracer_finish)
+template <class TF = ocn::TracerFuse>
+__global__ __launch_bounds__(256) void tracer_finish_general(GridDev g, const double *__restrict__ c, double *__restrict__ Gc, TF tf,
                                                              gen::GFrames fr)
 {
     gen::GRange r;
@@ -358,6 +370,12 @@ __global__ __launch_bounds__(256) void tracer_finish_general(GridDev g, const do
     const long long o = ocn::at(ocn::make_lay(g, OCN_LOC_CCC), i, j, k);
     const double c0 = c[o];
     double G = Gc[o];
+    if constexpr (TF::forced) {
+        if (tf.frc.n) {
+            G = G + ocn::forcing_at(tf.frc, i - 1 + g.Hx, j - 1 + g.Hy, k - 1 + g.Hz, o, c0);
+            Gc[o] = G;
+        }
+    }
     if (g.tz == OCN_BOUNDED) {
         bool touched = false;
         if (k == 1 && tf.bottom.kind == OCN_BC_FLUX) { G += ocn::bc_condition(tf.bottom, i, j, g.Nx, c0) * az / (az * M.dzC(1)); touched = true; }
@@ -406,12 +424,13 @@ static gen::Fields make_fields(const ocn_grid *grid, const double *u, const doub
 int launch_momentum_tendencies_box(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu, double *Gv, double *Gw,
                                    const int32_t box[4], int *launched, hipStream_t stream, const ocn::FuseArgs *fuse = nullptr, int ranged = 0);
 int launch_tracer_tendency_box(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c, double *Gc,
-                               const int32_t box[4], int *launched, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr, int ranged = 0);
+                               const int32_t box[4], int *launched, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr, int ranged = 0,
+                               const ocn::ForcingDev *forcing = nullptr);
 #if !OCN_UPWIND
 // physics.hip (compiled for the WENO namespaces only; the extra terms do not depend on the advection scheme): the tiled finishing pass
 int launch_momentum_extra_box(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w, double *Gu, double *Gv,
                               double *Gw, const int32_t box[4], int *launched, hipStream_t stream, const ocn::MomentumFinal *fin, int ranged = 0,
-                              const ocn::StokesDev *stokes = nullptr);
+                              const ocn::StokesDev *stokes = nullptr, const ocn::MomentumForcingDev *forcing = nullptr);
 #endif
 
 // Interior box + wall frames.  The topology-conditional reconstructions of a Bounded direction differ from the Periodic ones only within
@@ -514,7 +533,7 @@ int launch_momentum_tendencies_general(const ocn_grid *grid, int centered2, cons
 // bottom / top flux contributions, the next substep -- in the same call: the box kernel takes the whole TracerFuse (centre fields: their
 // layout has no walls in it), the frames run the per-cell kernels one after the other (same sums in the same order)
 int launch_tracer_tendency_general(const ocn_grid *grid, int centered2, const double *u, const double *v, const double *w, const double *c,
-                                   double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse)
+                                   double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse, const ocn::ForcingDev *forcing)
 {
     gen::GRange r;
     int st = make_grange(grid, range, r);
@@ -528,13 +547,19 @@ int launch_tracer_tendency_general(const ocn_grid *grid, int centered2, const do
     int32_t box[4];
     if (interior_box(grid, centered2, range, box)) {
         int launched = 0;
-        st = launch_tracer_tendency_box(grid, u, v, w, c, Gc, box, &launched, stream, fuse ? &tf : nullptr, range != nullptr);
+        st = launch_tracer_tendency_box(grid, u, v, w, c, Gc, box, &launched, stream, fuse ? &tf : nullptr, range != nullptr, forcing);
         if (st != OCN_SUCCESS) return st;
         if (launched) cells = frames_around(grid, box, r);
     }
     OCN_GEN_LAUNCH(tracer_tendency_general, cells, F, c, Gc);
     if (diffusion) OCN_GEN_LAUNCH(tracer_diffusion_general, cells, gd, tf.kappa, tf.kappa_e, c, Gc);
-    if (finish) OCN_GEN_LAUNCH(tracer_finish_general, cells, gd, c, Gc, tf);
+    if (forcing) {
+        ocn::TracerFuseForced tff{};
+        static_cast<ocn::TracerFuse &>(tff) = tf;
+        tff.frc = *forcing;
+        OCN_GEN_LAUNCH(tracer_finish_general<ocn::TracerFuseForced>, cells, gd, c, Gc, tff);
+    } else if (finish)
+        OCN_GEN_LAUNCH(tracer_finish_general<>, cells, gd, c, Gc, tf);
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
 }
@@ -543,7 +568,7 @@ int launch_tracer_tendency_general(const ocn_grid *grid, int centered2, const do
 // the Periodic grids): inside the tiled kernel on the box, as one more per-cell kernel on the frames
 int launch_momentum_extra_general(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w, double *Gu,
                                   double *Gv, double *Gw, const int32_t *range, hipStream_t stream, const ocn::MomentumFinal *fin,
-                                  const ocn::StokesDev *stokes)
+                                  const ocn::StokesDev *stokes, const ocn::MomentumForcingDev *forcing)
 {
     const bool finish = fin && (fin->sc.on || fin->bottom[0].kind || fin->bottom[1].kind || fin->top[0].kind || fin->top[1].kind);
     gen::GRange r;
@@ -556,12 +581,16 @@ int launch_momentum_extra_general(const ocn_grid *grid, const ocn::TermsDev &t, 
     int32_t box[4];
     if (interior_box(grid, 0, range, box)) {
         int launched = 0;
-        st = launch_momentum_extra_box(grid, t, u, v, w, Gu, Gv, Gw, box, &launched, stream, fin, range != nullptr, stokes);
+        st = launch_momentum_extra_box(grid, t, u, v, w, Gu, Gv, Gw, box, &launched, stream, fin, range != nullptr, stokes, forcing);
         if (st != OCN_SUCCESS) return st;
         if (launched) cells = frames_around(grid, box, r);
     }
 #endif
-    if (stokes)
+    if (forcing) {
+        ocn::MomentumForcingDev fd = *forcing;
+        fd.stokes = stokes != nullptr;
+        OCN_GEN_LAUNCH(momentum_extra_general_forced, cells, F, t, Gu, Gv, Gw, stokes ? *stokes : ocn::StokesDev{}, fd);
+    } else if (stokes)
         OCN_GEN_LAUNCH(momentum_extra_general_stokes, cells, F, t, Gu, Gv, Gw, *stokes);
     else
         OCN_GEN_LAUNCH(momentum_extra_general, cells, F, t, Gu, Gv, Gw);

@@ -41,6 +41,10 @@ struct ocn_model_driver {
     // stokes_drift = UniformStokesDrift with steady profiles (ocn_model_driver_set_stokes_drift): the caller's device vectors
     ocn_stokes_drift stokes{};
     bool has_stokes = false, base_momentum_extra = false;
+    // forcing with steady terms (ocn_model_driver_set_forcing): copies of the descriptors, the device vectors / arrays stay the caller's
+    ocn_forcing forcing_store[NF];
+    const ocn_forcing *forcing[NF] = {};  // NULL = the field is not forced
+    bool momentum_forced = false;
     long long iteration = 0;
     // slab-x rank (ocn_model_driver_create_distributed): RCCL communicator + distributed Poisson handle, both borrowed
     ocn_comm_t comm = nullptr;
@@ -147,12 +151,14 @@ int update_state(ocn_model_driver *d, void *stream)
 // compute_tendencies! (compute_nonhydrostatic_tendencies.jl:17-54) with the boundary contributions (:204-213)
 int compute_tendencies(ocn_model_driver *d, void *stream)
 {
-    int st = ocn_compute_momentum_tendencies_terms_stokes(&d->grid, &d->terms, d->has_stokes ? &d->stokes : nullptr, d->U[0], d->U[1], d->U[2], d->Gn[0], d->Gn[1], d->Gn[2], nullptr, stream);
+    int st = ocn_compute_momentum_tendencies_terms_forced(&d->grid, &d->terms, d->has_stokes ? &d->stokes : nullptr,
+                                                          d->momentum_forced ? d->forcing : nullptr, d->U[0], d->U[1], d->U[2], d->Gn[0], d->Gn[1],
+                                                          d->Gn[2], nullptr, stream);
     if (st != OCN_SUCCESS) return st;
     for (int t = 0; t < d->nt; ++t) {
-        st = ocn_compute_tracer_tendency_terms(&d->grid, &d->terms, d->terms.closure == 1 ? d->kappa[t] : 0.0,
-                                               d->terms.closure == 2 ? d->kappa_e[t] : nullptr, d->U[0], d->U[1], d->U[2], d->U[3 + t],
-                                               d->Gn[3 + t], nullptr, stream);
+        st = ocn_compute_tracer_tendency_terms_forced(&d->grid, &d->terms, d->terms.closure == 1 ? d->kappa[t] : 0.0,
+                                                      d->terms.closure == 2 ? d->kappa_e[t] : nullptr, d->forcing[3 + t], d->U[0], d->U[1],
+                                                      d->U[2], d->U[3 + t], d->Gn[3 + t], nullptr, stream);
         if (st != OCN_SUCCESS) return st;
     }
     if (d->any_flux) {
@@ -171,9 +177,10 @@ int launch_tendencies(ocn_model_driver *d, double dt, double gamma, double zeta,
 {
     int st;
     if (d->momentum_extra)
-        st = ocn_compute_momentum_tendencies_terms_rk3_stokes(&d->grid, &d->terms, d->has_stokes ? &d->stokes : nullptr, flux_bcs(d, 0), flux_bcs(d, 1), d->U[0], d->U[1], d->U[2], d->Gn[0],
-                                                       d->Gn[1], d->Gn[2], d->Gm[0], d->Gm[1], d->Gm[2], d->A[0], d->A[1], d->A[2], dt, gamma, zeta,
-                                                       has_zeta, range, stream);
+        st = ocn_compute_momentum_tendencies_terms_rk3_forced(&d->grid, &d->terms, d->has_stokes ? &d->stokes : nullptr,
+                                                              d->momentum_forced ? d->forcing : nullptr, flux_bcs(d, 0), flux_bcs(d, 1), d->U[0],
+                                                              d->U[1], d->U[2], d->Gn[0], d->Gn[1], d->Gn[2], d->Gm[0], d->Gm[1], d->Gm[2], d->A[0],
+                                                              d->A[1], d->A[2], dt, gamma, zeta, has_zeta, range, stream);
     else
         st = ocn_compute_momentum_tendencies_rk3(&d->grid, d->U[0], d->U[1], d->U[2], d->Gn[0], d->Gn[1], d->Gn[2], d->Gm[0], d->Gm[1], d->Gm[2],
                                                  d->A[0], d->A[1], d->A[2], dt, gamma, zeta, has_zeta, nullptr, 0.0, range, stream);
@@ -181,7 +188,7 @@ int launch_tendencies(ocn_model_driver *d, double dt, double gamma, double zeta,
     int q = 0;
     while (q < d->nt) {
         const double kap[2] = {d->terms.closure == 1 ? d->kappa[q] : 0.0, (q + 1 < d->nt && d->terms.closure == 1) ? d->kappa[q + 1] : 0.0};
-        if (q + 1 < d->nt) {  // pairs of tracers may share one launch (off by default in the library: *launched says)
+        if (q + 1 < d->nt && !d->forcing[3 + q] && !d->forcing[4 + q]) {  // pairs of (unforced) tracers may share one launch (off by default in the library: *launched says)
             const double *ke[2] = {d->terms.closure == 2 ? d->kappa_e[q] : nullptr, d->terms.closure == 2 ? d->kappa_e[q + 1] : nullptr};
             const ocn_field_bcs *fb[2] = {flux_bcs(d, 3 + q), flux_bcs(d, 4 + q)};
             const double *c[2] = {d->U[3 + q], d->U[4 + q]};
@@ -197,9 +204,9 @@ int launch_tendencies(ocn_model_driver *d, double dt, double gamma, double zeta,
                 continue;
             }
         }
-        st = ocn_compute_tracer_tendency_terms_rk3(&d->grid, &d->terms, kap[0], d->terms.closure == 2 ? d->kappa_e[q] : nullptr, flux_bcs(d, 3 + q),
-                                                   d->U[0], d->U[1], d->U[2], d->U[3 + q], d->Gn[3 + q], d->Gm[3 + q], d->A[3 + q], dt, gamma, zeta,
-                                                   has_zeta, range, stream);
+        st = ocn_compute_tracer_tendency_terms_rk3_forced(&d->grid, &d->terms, kap[0], d->terms.closure == 2 ? d->kappa_e[q] : nullptr,
+                                                          d->forcing[3 + q], flux_bcs(d, 3 + q), d->U[0], d->U[1], d->U[2], d->U[3 + q], d->Gn[3 + q],
+                                                          d->Gm[3 + q], d->A[3 + q], dt, gamma, zeta, has_zeta, range, stream);
         if (st != OCN_SUCCESS) return st;
         q += 1;
     }
@@ -549,7 +556,32 @@ extern "C" int ocn_model_driver_set_stokes_drift(ocn_model_driver_t d, const ocn
     OCN_REQUIRE(!d->pending, "ocn_model_driver_set_stokes_drift: call before the first time step or after ocn_model_driver_flush");
     d->has_stokes = stokes != nullptr;
     d->stokes = stokes ? *stokes : ocn_stokes_drift{};
-    d->momentum_extra = d->base_momentum_extra || d->has_stokes;
+    d->momentum_extra = d->base_momentum_extra || d->has_stokes || d->momentum_forced;
+    d->started = false;  // the next time step begins with update_state! and a fresh compute_tendencies!, as at iteration 0
+    return OCN_SUCCESS;
+}
+
+extern "C" int ocn_model_driver_set_forcing(ocn_model_driver_t d, const ocn_forcing *const *forcing, int32_t time_dependent)
+{
+    OCN_REQUIRE(d, "ocn_model_driver_set_forcing: null driver");
+    OCN_REQUIRE(!time_dependent, "ocn_model_driver_set_forcing: a forcing that depends on time needs the Python host (time_step(model, dt) samples it at "
+                                 "every tendency evaluation); the driver takes steady terms only");
+    OCN_REQUIRE(!d->comm, "ocn_model_driver_set_forcing: not on a slab-x rank (forcing on a Distributed architecture is not implemented)");
+    OCN_REQUIRE(!d->pending, "ocn_model_driver_set_forcing: call before the first time step or after ocn_model_driver_flush");
+    static const char *names[NF] = {"u", "v", "w", "tracer 0", "tracer 1", "tracer 2", "tracer 3"};
+    for (int f = 0; forcing && f < d->n; ++f) {
+        int st = ocn::validate_forcing(&d->grid, forcing[f], "ocn_model_driver_set_forcing", names[f]);
+        if (st != OCN_SUCCESS) return st;
+    }
+    d->momentum_forced = false;
+    for (int f = 0; f < NF; ++f) {
+        d->forcing[f] = nullptr;
+        if (!forcing || f >= d->n || !forcing[f] || forcing[f]->n_terms == 0) continue;
+        d->forcing_store[f] = *forcing[f];
+        d->forcing[f] = &d->forcing_store[f];
+        if (f < 3) d->momentum_forced = true;
+    }
+    d->momentum_extra = d->base_momentum_extra || d->has_stokes || d->momentum_forced;
     d->started = false;  // the next time step begins with update_state! and a fresh compute_tendencies!, as at iteration 0
     return OCN_SUCCESS;
 }

@@ -2,7 +2,9 @@
 // momentum_extra_general (the kernel and its arguments as they always were) and as momentum_extra_general_stokes, which takes one more
 // argument (ocn::StokesDev sd) and adds (∇ × uˢ) × u + ∂t uˢ last (StokesDrifts.jl:165-180), with the plain nested two-point averages of
 // interpolation_operators.jl:50-56 (the value itself along a Flat x / y).  The includer defines OCN_EXTRA_GENERAL (the kernel's name),
-// OCN_EXTRA_STK (1 / 0) and OCN_EXTRA_SD_PARAM (empty, or `ocn::StokesDev sd,`).
+// OCN_EXTRA_STK (1 / 0) and OCN_EXTRA_SD_PARAM (empty, or `ocn::StokesDev sd,`).  A THIRD inclusion, momentum_extra_general_forced
+// (OCN_EXTRA_FRC = 1, `ocn::StokesDev sd, ocn::MomentumForcingDev fd,`), adds the sampled forcing of each component after the Stokes terms
+// (which then run only when fd.stokes says the drift is in use).
 __global__ __launch_bounds__(256) void OCN_EXTRA_GENERAL(gen::Fields F, ocn::TermsDev t, double *__restrict__ Gu, double *__restrict__ Gv,
                                                               double *__restrict__ Gw, OCN_EXTRA_SD_PARAM gen::GFrames fr)
 {
@@ -71,11 +73,17 @@ __global__ __launch_bounds__(256) void OCN_EXTRA_GENERAL(gen::Fields F, ocn::Ter
             G = G - 1 / (Az * M.dzC(k)) * ((dxF + dyF) + dzF);
         }
 #if OCN_EXTRA_STK
+#if OCN_EXTRA_FRC
+        if (fd.stokes)
+#endif
         {  // ℑxzᶠᵃᶜ(w) ∂z_uˢ(z centre k) + ∂t_uˢ
             auto IX = [&](int c) { return fx ? W_(i, j, c) : 0.5 * (W_(i - 1, j, c) + W_(i, j, c)); };
             G = G + (0.5 * (IX(k) + IX(k + 1))) * ocn::stokes_at(sd.dzu_c, k);
             G = G + ocn::stokes_at(sd.dtu, k);
         }
+#endif
+#if OCN_EXTRA_FRC
+        if (fd.f[0].n) G = G + ocn::forcing_at(fd.f[0], i - 1 + g.Hx, j - 1 + g.Hy, k - 1 + g.Hz, o, u[o]);
 #endif
         Gu[o] = G;
     }
@@ -98,11 +106,17 @@ __global__ __launch_bounds__(256) void OCN_EXTRA_GENERAL(gen::Fields F, ocn::Ter
             G = G - 1 / (Az * M.dzC(k)) * ((dxF + dyF) + dzF);
         }
 #if OCN_EXTRA_STK
+#if OCN_EXTRA_FRC
+        if (fd.stokes)
+#endif
         {  // ℑyzᵃᶠᶜ(w) ∂z_vˢ(z centre k) + ∂t_vˢ
             auto IY = [&](int c) { return fy ? W_(i, j, c) : 0.5 * (W_(i, j - 1, c) + W_(i, j, c)); };
             G = G + (0.5 * (IY(k) + IY(k + 1))) * ocn::stokes_at(sd.dzv_c, k);
             G = G + ocn::stokes_at(sd.dtv, k);
         }
+#endif
+#if OCN_EXTRA_FRC
+        if (fd.f[1].n) G = G + ocn::forcing_at(fd.f[1], i - 1 + g.Hx, j - 1 + g.Hy, k - 1 + g.Hz, o, v[o]);
 #endif
         Gv[o] = G;
     }
@@ -124,6 +138,9 @@ __global__ __launch_bounds__(256) void OCN_EXTRA_GENERAL(gen::Fields F, ocn::Ter
             G = G - 1 / (Az * M.dzF(k)) * ((dxF + dyF) + dzF);
         }
 #if OCN_EXTRA_STK
+#if OCN_EXTRA_FRC
+        if (fd.stokes)
+#endif
         {  // -ℑxzᶜᵃᶠ(u) ∂z_uˢ(z face k) - ℑyzᵃᶜᶠ(v) ∂z_vˢ(z face k), ∂t_wˢ = 0
             auto IX = [&](int c) { return fx ? U_(i, j, c) : 0.5 * (U_(i, j, c) + U_(i + 1, j, c)); };
             auto IY = [&](int c) { return fy ? V_(i, j, c) : 0.5 * (V_(i, j, c) + V_(i, j + 1, c)); };
@@ -131,6 +148,9 @@ __global__ __launch_bounds__(256) void OCN_EXTRA_GENERAL(gen::Fields F, ocn::Ter
             G = G + (-(ui * ocn::stokes_at(sd.dzu_f, k)) - vi * ocn::stokes_at(sd.dzv_f, k));
             G = G + 0.0;
         }
+#endif
+#if OCN_EXTRA_FRC
+        if (fd.f[2].n) G = G + ocn::forcing_at(fd.f[2], i - 1 + g.Hx, j - 1 + g.Hy, k - 1 + g.Hz, o, w[o]);
 #endif
         Gw[o] = G;
     }

@@ -1,12 +1,13 @@
-// momentum_extra_kernels.inc -- the momentum finishing pass of physics.hip (direct and LDS-tiled kernels), included TWICE: once as
-// momentum_extra_kernel / momentum_extra_tiled (no Stokes drift: the kernels and their arguments as they always were) and once as
+// momentum_extra_kernels.inc -- the momentum finishing pass of physics.hip (direct and LDS-tiled kernels), included THREE times: as
+// momentum_extra_kernel / momentum_extra_tiled (no Stokes drift: the kernels and their arguments as they always were), as
 // momentum_extra_kernel_stokes / momentum_extra_tiled_stokes, which take one more argument (ocn::StokesDev) and compile the Stokes-drift
-// terms of momentum_extra_cell in.  The includer defines
+// terms of momentum_extra_cell in, and as momentum_extra_kernel_forced / momentum_extra_tiled_forced, which take ocn::StokesDev and
+// ocn::MomentumForcingDev and compile both in (either may be empty at run time).  The includer defines
 //   OCN_EXTRA_KERNEL, OCN_EXTRA_TILED   the kernel names
-//   OCN_EXTRA_STK                       true / false: momentum_extra_cell's STK
-//   OCN_EXTRA_SD_PARAM                  empty, or `, ocn::StokesDev sd` (the additional kernel parameter)
-//   OCN_EXTRA_SD                        nullptr, or &sd
-// One text for both keeps the two families identical except for the terms themselves.
+//   OCN_EXTRA_STK, OCN_EXTRA_FRC        true / false: momentum_extra_cell's STK and FRC
+//   OCN_EXTRA_SD_PARAM                  empty, `, ocn::StokesDev sd` or `, ocn::StokesDev sd, ocn::MomentumForcingDev fd` (additional parameters)
+//   OCN_EXTRA_SD, OCN_EXTRA_FD          nullptr, or &sd / &fd
+// One text for all keeps the families identical except for the terms themselves.
 
 // `mf`: the flux boundary contributions of u, v (apply_flux_bcs.jl:107-160) and the NEXT stage's rk3 substep of u, v, w into a
 // second storage, folded into this last pass over G (same operations as apply_flux_bcs_kernel / stepper_kernel).
@@ -26,10 +27,10 @@ __global__ __launch_bounds__(256) void OCN_EXTRA_KERNEL(GridDev g, TermsDev t, c
     const long long s2 = L.s2, s3 = ZF ? 0 : L.s3, o = ocn::at(L, i, j, k);
     const double *pu = u + o, *pv = v + o, *pw = w + o, *pn = t.nu_e ? t.nu_e + o : nullptr;
     const ExtraLoads ld = momentum_extra_loads<TZ>(t, mf, r, k, o, s2, s3, Gu, Gv, Gw);
-    momentum_extra_cell<TZ, false, OCN_EXTRA_STK>(
+    momentum_extra_cell<TZ, false, OCN_EXTRA_STK, OCN_EXTRA_FRC>(
         g, t, M, i, j, k, o, s2, s3, pn != nullptr, [&](int a, int b, int c) { return pu[a + b * s2 + c * s3]; },
         [&](int a, int b, int c) { return pv[a + b * s2 + c * s3]; }, [&](int a, int b, int c) { return pw[a + b * s2 + c * s3]; },
-        [&](int a, int b, int c) { return pn[a + b * s2 + c * s3]; }, Gu, Gv, Gw, r, mf, ld, 0.0, 0.0, nullptr, nullptr, nullptr, OCN_EXTRA_SD);
+        [&](int a, int b, int c) { return pn[a + b * s2 + c * s3]; }, Gu, Gv, Gw, r, mf, ld, 0.0, 0.0, nullptr, nullptr, nullptr, OCN_EXTRA_SD, OCN_EXTRA_FD);
 }
 
 // Tiled variant of the finishing pass: a workgroup owns a 32 x 8 patch of columns and marches KZ planes upward; planes
@@ -210,12 +211,12 @@ __global__ __launch_bounds__(256, SH ? 3 : 4) void OCN_EXTRA_TILED(GridDev g, Te
             t33_prev = o33;
         }
         if (active) {
-            momentum_extra_cell<TZ, false, OCN_EXTRA_STK>(
+            momentum_extra_cell<TZ, false, OCN_EXTRA_STK, OCN_EXTRA_FRC>(
                 g, t, M, i, j, k, o, s2, s3, has_nu, [&](int a, int b, int c) { return Lu[(base + c) % 3][c0 + a + b * SX]; },
                 [&](int a, int b, int c) { return Lv[(base + c) % 3][c0 + a + b * SX]; },
                 [&](int a, int b, int c) { return Lw[(base + c) % 3][c0 + a + b * SX]; },
                 [&](int a, int b, int c) { return Ln[(base + c) % 3][c0 + a + b * SX]; }, Gu, Gv, Gw, r, mf, ld, 0.0, 0.0, nullptr,
-                SH ? &sh : nullptr, fo, OCN_EXTRA_SD);
+                SH ? &sh : nullptr, fo, OCN_EXTRA_SD, OCN_EXTRA_FD);
         }
         // Unshared: everyone must be done with slot (k - 1) % 3 before the next iteration's commit overwrites it.  Shared: nothing reads plane
         // k - 1 after the first iteration's stress phase (T13, T23 of plane k and T33 of k - 1 are carried), which the barrier above already

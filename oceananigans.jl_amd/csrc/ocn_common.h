@@ -193,6 +193,64 @@ inline StokesDev to_dev(const ocn_stokes_drift &s)
     return StokesDev{s.dz_us_center, s.dz_vs_center, s.dz_us_face, s.dz_vs_face, s.dt_us, s.dt_vs};
 }
 
+// device-side copy of ocn_forcing (forcing = (u = ..., ...), src/Forcings): up to four sampled terms of ONE field, summed left to right
+// (multiple_forcings.jl:34-46).  The struct travels in the kernel arguments, so n, the kinds and the dims are wave-uniform scalars; vectors
+// along z are read through the constant address space (k is wave-uniform in every kernel that takes this), vectors along x / y and arrays
+// in the parent layout are per-lane loads.  Only the kernels compiled with the forcing terms take this struct as an argument.
+struct ForcingTermDev {
+    int kind, mask_dim, target_dim;
+    double rate, target_value;
+    const double *values, *mask, *target;
+};
+struct ForcingDev {
+    int n;
+    ForcingTermDev term[OCN_FORCING_MAX_TERMS];
+};
+inline ForcingDev to_dev(const ocn_forcing *f)
+{
+    ForcingDev d{};
+    if (!f) return d;
+    d.n = f->n_terms;
+    for (int q = 0; q < f->n_terms && q < OCN_FORCING_MAX_TERMS; ++q) {
+        const ocn_forcing_term &s = f->term[q];
+        d.term[q] = ForcingTermDev{s.kind, s.mask_dim, s.target_dim, s.rate, s.target_value, s.values, s.mask, s.target};
+    }
+    return d;
+}
+// the forcings of u, v, w for the momentum finishing pass compiled with them; `stokes`: the StokesDev argument next to it is in use
+struct MomentumForcingDev {
+    ForcingDev f[3];
+    int stokes;
+};
+// mask / target of a Relaxation term at a cell: ix, iy, iz = its indices along the parent array (i - 1 + Hx ...), o its parent offset
+__device__ __forceinline__ double forcing_profile(int dim, const double *p, double number, int ix, int iy, int iz, long long o)
+{
+    if (dim < 0) return number;
+    if (dim == 2) return uniform_load(p, iz);
+    if (dim == 3) return p[o];
+    return p[dim == 0 ? ix : iy];
+}
+// F of one field at one cell whose value is `c`:  F = t1; F = F + t2; ...   (f.n >= 1)
+__device__ __forceinline__ double forcing_at(const ForcingDev &f, int ix, int iy, int iz, long long o, double c)
+{
+    double F = 0.0;
+#pragma unroll
+    for (int q = 0; q < OCN_FORCING_MAX_TERMS; ++q) {
+        if (q >= f.n) break;
+        const ForcingTermDev &t = f.term[q];
+        double v;
+        if (t.kind == OCN_FORCING_ARRAY) {
+            v = t.values[o];
+        } else {  // Relaxation: (rate * mask(X)) * (target(X, t) - field[i, j, k])   (relaxation.jl:95-101)
+            const double m = forcing_profile(t.mask_dim, t.mask, 1.0, ix, iy, iz, o);
+            const double tg = forcing_profile(t.target_dim, t.target, t.target_value, ix, iy, iz, o);
+            v = (t.rate * m) * (tg - c);
+        }
+        F = q == 0 ? v : F + v;
+    }
+    return F;
+}
+
 // bottom / top boundary condition of one field (kind 0: default fill / no flux)
 struct ZBc {
     int kind;
@@ -217,12 +275,20 @@ struct SubstepCoef {
 };
 // everything the tracer tendency kernel can fold in besides advection (physics.hip / tendencies.hip)
 struct TracerFuse {
+    static constexpr bool forced = false;
     int diffusion;          // add -∇_dot_qᶜ
     double kappa;
     const double *kappa_e;  // eddy diffusivity field or NULL
     ZBc bottom, top;        // flux boundary conditions (kind OCN_BC_FLUX) folded into Gc
     SubstepDev sub;
     SubstepCoef sc;
+};
+// ... and the sampled forcing of the tracer (forcing = (T = ...)): the tracer kernels are templates on the descriptor type, so the
+// instantiations with TracerFuse keep their arguments and their code, and the ones with TracerFuseForced add F between the diffusion and
+// the boundary fluxes (tracer_finish)
+struct TracerFuseForced : TracerFuse {
+    static constexpr bool forced = true;
+    ForcingDev frc;
 };
 // flux boundary conditions of u, v and the substeps of u, v, w for the momentum "finaliser" (momentum_extra_kernel)
 struct MomentumFinal {

@@ -140,21 +140,28 @@ int launch_transpose(int mode, int nx, int Ny, int Nz, int R, const double *src,
 
 }  // namespace ocn
 
+namespace ocn {
+// the descriptor of one field's forcing (capi.hip): host memory only, no device pointer is followed
+int validate_forcing(const ocn_grid *grid, const ocn_forcing *f, const char *who, const char *field);
+}
+
 namespace ocn_strict {
 int launch_momentum_tendencies_general(const ocn_grid *grid, int centered2, const double *u, const double *v, const double *w, double *Gu,
                                        double *Gv, double *Gw, const int32_t *range, hipStream_t stream, const ocn::MomentumFinal *fin = nullptr);
 int launch_tracer_tendency_general(const ocn_grid *grid, int centered2, const double *u, const double *v, const double *w, const double *c,
-                                   double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr);
+                                   double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr,
+                                   const ocn::ForcingDev *forcing = nullptr);
 int launch_momentum_extra_general(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w, double *Gu,
                                   double *Gv, double *Gw, const int32_t *range, hipStream_t stream, const ocn::MomentumFinal *fin = nullptr,
-                                  const ocn::StokesDev *stokes = nullptr);
+                                  const ocn::StokesDev *stokes = nullptr, const ocn::MomentumForcingDev *forcing = nullptr);
 int launch_tracer_diffusion_general(const ocn_grid *grid, double kappa, const double *kappa_e, const double *c, double *Gc,
                                     const int32_t *range, hipStream_t stream);
 int launch_pressure_planes(const ocn_grid *grid, double *p, double *u, double dt, double *west, double *east, int unpack, hipStream_t stream);
 int launch_momentum_tendencies(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
                                double *Gv, double *Gw, const int32_t *range, const ocn::FuseArgs *fuse, hipStream_t stream);
 int launch_tracer_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c,
-                           double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr);
+                           double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr,
+                           const ocn::ForcingDev *forcing = nullptr);
 int launch_tracer_pair_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *const c[2],
                                 double *const Gc[2], const int32_t *range, hipStream_t stream, const ocn::TracerFuse fuse[2], int *launched);
 int launch_momentum_centered2(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu, double *Gv,
@@ -163,7 +170,10 @@ int launch_tracer_centered2(const ocn_grid *grid, const double *u, const double 
                             double *Gc, const int32_t *range, hipStream_t stream);
 int launch_momentum_extra(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w,
                           double *Gu, double *Gv, double *Gw, const int32_t *range, hipStream_t stream,
-                          const ocn::MomentumFinal *fin = nullptr, const ocn::StokesDev *stokes = nullptr);
+                          const ocn::MomentumFinal *fin = nullptr, const ocn::StokesDev *stokes = nullptr,
+                          const ocn::MomentumForcingDev *forcing = nullptr);
+int launch_tracer_forcing(const ocn_grid *grid, const ocn::ForcingDev &forcing, const double *c, double *Gc, const int32_t *range,
+                          const ocn::TracerFuse *fuse, hipStream_t stream);
 int launch_hydrostatic_momentum(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w, double *Gu,
                                 double *Gv, const ocn::MomentumFinal &mf, const ocn::HydroFuse &hf, hipStream_t stream);
 int launch_tracer_diffusion(const ocn_grid *grid, double kappa, const double *kappa_e, const double *c, double *Gc,
@@ -179,17 +189,19 @@ namespace ocn_fast {
 int launch_momentum_tendencies_general(const ocn_grid *grid, int centered2, const double *u, const double *v, const double *w, double *Gu,
                                        double *Gv, double *Gw, const int32_t *range, hipStream_t stream, const ocn::MomentumFinal *fin = nullptr);
 int launch_tracer_tendency_general(const ocn_grid *grid, int centered2, const double *u, const double *v, const double *w, const double *c,
-                                   double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr);
+                                   double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr,
+                                   const ocn::ForcingDev *forcing = nullptr);
 int launch_momentum_extra_general(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w, double *Gu,
                                   double *Gv, double *Gw, const int32_t *range, hipStream_t stream, const ocn::MomentumFinal *fin = nullptr,
-                                  const ocn::StokesDev *stokes = nullptr);
+                                  const ocn::StokesDev *stokes = nullptr, const ocn::MomentumForcingDev *forcing = nullptr);
 int launch_tracer_diffusion_general(const ocn_grid *grid, double kappa, const double *kappa_e, const double *c, double *Gc,
                                     const int32_t *range, hipStream_t stream);
 int launch_pressure_planes(const ocn_grid *grid, double *p, double *u, double dt, double *west, double *east, int unpack, hipStream_t stream);
 int launch_momentum_tendencies(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
                                double *Gv, double *Gw, const int32_t *range, const ocn::FuseArgs *fuse, hipStream_t stream);
 int launch_tracer_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c,
-                           double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr);
+                           double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr,
+                           const ocn::ForcingDev *forcing = nullptr);
 int launch_tracer_pair_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *const c[2],
                                 double *const Gc[2], const int32_t *range, hipStream_t stream, const ocn::TracerFuse fuse[2], int *launched);
 int launch_momentum_centered2(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu, double *Gv,
@@ -198,7 +210,10 @@ int launch_tracer_centered2(const ocn_grid *grid, const double *u, const double 
                             double *Gc, const int32_t *range, hipStream_t stream);
 int launch_momentum_extra(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w,
                           double *Gu, double *Gv, double *Gw, const int32_t *range, hipStream_t stream,
-                          const ocn::MomentumFinal *fin = nullptr, const ocn::StokesDev *stokes = nullptr);
+                          const ocn::MomentumFinal *fin = nullptr, const ocn::StokesDev *stokes = nullptr,
+                          const ocn::MomentumForcingDev *forcing = nullptr);
+int launch_tracer_forcing(const ocn_grid *grid, const ocn::ForcingDev &forcing, const double *c, double *Gc, const int32_t *range,
+                          const ocn::TracerFuse *fuse, hipStream_t stream);
 int launch_hydrostatic_momentum(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w, double *Gu,
                                 double *Gv, const ocn::MomentumFinal &mf, const ocn::HydroFuse &hf, hipStream_t stream);
 int launch_tracer_diffusion(const ocn_grid *grid, double kappa, const double *kappa_e, const double *c, double *Gc,
@@ -216,16 +231,18 @@ namespace ocn_strict_up {
 int launch_momentum_tendencies_general(const ocn_grid *grid, int centered2, const double *u, const double *v, const double *w, double *Gu,
                                        double *Gv, double *Gw, const int32_t *range, hipStream_t stream, const ocn::MomentumFinal *fin = nullptr);
 int launch_tracer_tendency_general(const ocn_grid *grid, int centered2, const double *u, const double *v, const double *w, const double *c,
-                                   double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr);
+                                   double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr,
+                                   const ocn::ForcingDev *forcing = nullptr);
 int launch_momentum_extra_general(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w, double *Gu,
                                   double *Gv, double *Gw, const int32_t *range, hipStream_t stream, const ocn::MomentumFinal *fin = nullptr,
-                                  const ocn::StokesDev *stokes = nullptr);
+                                  const ocn::StokesDev *stokes = nullptr, const ocn::MomentumForcingDev *forcing = nullptr);
 int launch_tracer_diffusion_general(const ocn_grid *grid, double kappa, const double *kappa_e, const double *c, double *Gc,
                                     const int32_t *range, hipStream_t stream);
 int launch_momentum_tendencies(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
                                double *Gv, double *Gw, const int32_t *range, const ocn::FuseArgs *fuse, hipStream_t stream);
 int launch_tracer_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c,
-                           double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr);
+                           double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr,
+                           const ocn::ForcingDev *forcing = nullptr);
 int launch_tracer_pair_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *const c[2],
                                 double *const Gc[2], const int32_t *range, hipStream_t stream, const ocn::TracerFuse fuse[2], int *launched);
 }
@@ -233,16 +250,18 @@ namespace ocn_fast_up {
 int launch_momentum_tendencies_general(const ocn_grid *grid, int centered2, const double *u, const double *v, const double *w, double *Gu,
                                        double *Gv, double *Gw, const int32_t *range, hipStream_t stream, const ocn::MomentumFinal *fin = nullptr);
 int launch_tracer_tendency_general(const ocn_grid *grid, int centered2, const double *u, const double *v, const double *w, const double *c,
-                                   double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr);
+                                   double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr,
+                                   const ocn::ForcingDev *forcing = nullptr);
 int launch_momentum_extra_general(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w, double *Gu,
                                   double *Gv, double *Gw, const int32_t *range, hipStream_t stream, const ocn::MomentumFinal *fin = nullptr,
-                                  const ocn::StokesDev *stokes = nullptr);
+                                  const ocn::StokesDev *stokes = nullptr, const ocn::MomentumForcingDev *forcing = nullptr);
 int launch_tracer_diffusion_general(const ocn_grid *grid, double kappa, const double *kappa_e, const double *c, double *Gc,
                                     const int32_t *range, hipStream_t stream);
 int launch_momentum_tendencies(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
                                double *Gv, double *Gw, const int32_t *range, const ocn::FuseArgs *fuse, hipStream_t stream);
 int launch_tracer_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c,
-                           double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr);
+                           double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr,
+                           const ocn::ForcingDev *forcing = nullptr);
 int launch_tracer_pair_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *const c[2],
                                 double *const Gc[2], const int32_t *range, hipStream_t stream, const ocn::TracerFuse fuse[2], int *launched);
 }

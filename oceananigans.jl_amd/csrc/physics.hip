@@ -238,16 +238,20 @@ struct Stresses {
 // (nonhydrostatic_tendency_kernel_functions.jl:73-74, 135-136, 197-198; StokesDrifts.jl:165-180), the four-point averages as the nested
 // two-point ones of interpolation_operators.jl:50-56 (x or y inside, z outside).  The six profile values of level k are wave-uniform
 // scalar loads.  Compiled out of every instantiation without STK.
-template <int TZ, bool HYD = false, bool STK = false, class FU, class FV, class FW, class FN>
+// FRC (forcing = (u = ..., v = ..., w = ...), `fd`): the sampled forcing of each component is the last addend, after the Stokes terms
+// (nonhydrostatic_tendency_kernel_functions.jl:77, 137, 199) and before the boundary fluxes; it reads the field, never G.  The kernels
+// compiled with FRC also carry STK and test fd->stokes (wave-uniform), so ONE variant serves forcing with and without a Stokes drift.
+template <int TZ, bool HYD = false, bool STK = false, bool FRC = false, class FU, class FV, class FW, class FN>
 __device__ __forceinline__ void momentum_extra_cell(const GridDev &g, const TermsDev &t, const Metrics &M, int i, int j, int k,
                                                     long long o, long long s2, long long s3, bool has_nu, FU Uf, FV Vf, FW Wf,
                                                     FN NEf, double *__restrict__ Gu, double *__restrict__ Gv,
                                                     double *__restrict__ Gw, const PRange &r, const ocn::MomentumFinal &mf,
                                                     const ExtraLoads &ld, double G0u = 0.0, double G0v = 0.0, double *res = nullptr,
                                                     const Stresses *sh = nullptr, const FieldOffs *fo = nullptr,
-                                                    const ocn::StokesDev *sd = nullptr)
+                                                    const ocn::StokesDev *sd = nullptr, const ocn::MomentumForcingDev *fd = nullptr)
 {
     constexpr bool ZF = (TZ == OCN_FLAT);
+    const bool stk = STK && (!FRC || fd->stokes);
     const long long o_u = fo ? fo->u : o, o_v = fo ? fo->v : o, o_w = fo ? fo->w : o, w3 = fo ? fo->w3 : s3;
     const double dx = M.dx, dy = M.dy, nu = t.nu;
     const double dzc = M.dzC(k), dzf = M.dzF(k), dzf1 = ZF ? dzf : M.dzF(k + 1), dzcm = ZF ? dzc : M.dzC(k - 1);
@@ -303,11 +307,12 @@ __device__ __forceinline__ void momentum_extra_cell(const GridDev &g, const Term
             }
             G = G - recip_volume(Az * dzc) * (((Axc * t11e - Axc * t11w) + (Ayc * t12n - Ayc * t12s)) + dzF);
         }
-        if (STK) {  // + x_curl_Uˢ_cross_U + ∂t_uˢ:  ℑxzᶠᵃᶜ(w) ∂z_uˢ(z centre k)
+        if (stk) {  // + x_curl_Uˢ_cross_U + ∂t_uˢ:  ℑxzᶠᵃᶜ(w) ∂z_uˢ(z centre k)
             const double wi = 0.5 * (0.5 * (Wf(-1, 0, 0) + Wf(0, 0, 0)) + 0.5 * (Wf(-1, 0, 1) + Wf(0, 0, 1)));
             G = G + wi * ocn::stokes_at(sd->dzu_c, k);
             G = G + ocn::stokes_at(sd->dtu, k);
         }
+        if (FRC && fd->f[0].n) G = G + ocn::forcing_at(fd->f[0], i - 1 + g.Hx, j - 1 + g.Hy, k - 1 + g.Hz, o_u, Uf(0, 0, 0));
         if (TZ == OCN_BOUNDED) {
             if (k == 1 && mf.bottom[0].kind == OCN_BC_FLUX) G += ocn::bc_condition(mf.bottom[0], i, j, g.Nx, Uf(0, 0, 0)) * Az / (Az * M.dzC(1));
             if (k == g.Nz && mf.top[0].kind == OCN_BC_FLUX) G -= ocn::bc_condition(mf.top[0], i, j, g.Nx, Uf(0, 0, 0)) * Az / (Az * M.dzC(g.Nz));
@@ -348,11 +353,12 @@ __device__ __forceinline__ void momentum_extra_cell(const GridDev &g, const Term
             }
             G = G - recip_volume(Az * dzc) * (((Axc * t12e - Axc * t12w) + (Ayc * t22n - Ayc * t22s)) + dzF);
         }
-        if (STK) {  // + y_curl_Uˢ_cross_U + ∂t_vˢ:  ℑyzᵃᶠᶜ(w) ∂z_vˢ(z centre k)
+        if (stk) {  // + y_curl_Uˢ_cross_U + ∂t_vˢ:  ℑyzᵃᶠᶜ(w) ∂z_vˢ(z centre k)
             const double wi = 0.5 * (0.5 * (Wf(0, -1, 0) + Wf(0, 0, 0)) + 0.5 * (Wf(0, -1, 1) + Wf(0, 0, 1)));
             G = G + wi * ocn::stokes_at(sd->dzv_c, k);
             G = G + ocn::stokes_at(sd->dtv, k);
         }
+        if (FRC && fd->f[1].n) G = G + ocn::forcing_at(fd->f[1], i - 1 + g.Hx, j - 1 + g.Hy, k - 1 + g.Hz, o_v, Vf(0, 0, 0));
         if (TZ == OCN_BOUNDED) {
             if (k == 1 && mf.bottom[1].kind == OCN_BC_FLUX) G += ocn::bc_condition(mf.bottom[1], i, j, g.Nx, Vf(0, 0, 0)) * Az / (Az * M.dzC(1));
             if (k == g.Nz && mf.top[1].kind == OCN_BC_FLUX) G -= ocn::bc_condition(mf.top[1], i, j, g.Nx, Vf(0, 0, 0)) * Az / (Az * M.dzC(g.Nz));
@@ -391,12 +397,13 @@ __device__ __forceinline__ void momentum_extra_cell(const GridDev &g, const Term
             }
             G = G - recip_volume(Az * dzf) * (((Axf * t13e - Axf * t13w) + (Ayf * t23n - Ayf * t23s)) + dzF);
         }
-        if (STK) {  // + z_curl_Uˢ_cross_U + ∂t_wˢ:  -ℑxzᶜᵃᶠ(u) ∂z_uˢ(z face k) - ℑyzᵃᶜᶠ(v) ∂z_vˢ(z face k),  ∂t_wˢ = 0
+        if (stk) {  // + z_curl_Uˢ_cross_U + ∂t_wˢ:  -ℑxzᶜᵃᶠ(u) ∂z_uˢ(z face k) - ℑyzᵃᶜᶠ(v) ∂z_vˢ(z face k),  ∂t_wˢ = 0
             const double ui = 0.5 * (0.5 * (Uf(0, 0, -1) + Uf(1, 0, -1)) + 0.5 * (Uf(0, 0, 0) + Uf(1, 0, 0)));
             const double vi = 0.5 * (0.5 * (Vf(0, 0, -1) + Vf(0, 1, -1)) + 0.5 * (Vf(0, 0, 0) + Vf(0, 1, 0)));
             G = G + (-(ui * ocn::stokes_at(sd->dzu_f, k)) - vi * ocn::stokes_at(sd->dzv_f, k));
             G = G + 0.0;
         }
+        if (FRC && fd->f[2].n) G = G + ocn::forcing_at(fd->f[2], i - 1 + g.Hx, j - 1 + g.Hy, k - 1 + g.Hz, o_w, Wf(0, 0, 0));
         Gw[o_w] = G;
         const bool wall = (TZ == OCN_BOUNDED) && k == 1 && g.Nz > 1;  // rk3_substep! never steps the wall face
         if (mf.sc.on) mf.sub[2].out[o_w] = wall ? Wf(0, 0, 0) : Wf(0, 0, 0) + (mf.sc.has_zeta ? mf.sc.dt * (mf.sc.gamma * G + mf.sc.zeta * gm_w) : (mf.sc.dt * mf.sc.gamma) * G);
@@ -410,8 +417,10 @@ __device__ __forceinline__ void momentum_extra_cell(const GridDev &g, const Term
 #define OCN_EXTRA_KERNEL momentum_extra_kernel
 #define OCN_EXTRA_TILED momentum_extra_tiled
 #define OCN_EXTRA_STK false
+#define OCN_EXTRA_FRC false
 #define OCN_EXTRA_SD_PARAM
 #define OCN_EXTRA_SD nullptr
+#define OCN_EXTRA_FD nullptr
 #include "momentum_extra_kernels.inc"
 #undef OCN_EXTRA_KERNEL
 #undef OCN_EXTRA_TILED
@@ -426,9 +435,23 @@ __device__ __forceinline__ void momentum_extra_cell(const GridDev &g, const Term
 #include "momentum_extra_kernels.inc"
 #undef OCN_EXTRA_KERNEL
 #undef OCN_EXTRA_TILED
+#undef OCN_EXTRA_SD_PARAM
+#undef OCN_EXTRA_FRC
+#undef OCN_EXTRA_FD
+// ... and the ONE variant with the forcing terms: it takes both descriptors, either of which may be empty (fd.stokes = 0: no Stokes terms)
+#define OCN_EXTRA_KERNEL momentum_extra_kernel_forced
+#define OCN_EXTRA_TILED momentum_extra_tiled_forced
+#define OCN_EXTRA_FRC true
+#define OCN_EXTRA_SD_PARAM , ocn::StokesDev sd, ocn::MomentumForcingDev fd
+#define OCN_EXTRA_FD &fd
+#include "momentum_extra_kernels.inc"
+#undef OCN_EXTRA_KERNEL
+#undef OCN_EXTRA_TILED
 #undef OCN_EXTRA_STK
+#undef OCN_EXTRA_FRC
 #undef OCN_EXTRA_SD_PARAM
 #undef OCN_EXTRA_SD
+#undef OCN_EXTRA_FD
 
 // ---------------------------------------------------------------------------------------------------
 // HydrostaticFreeSurfaceModel: the whole horizontal-momentum part of one QuasiAdamsBashforth2 step in ONE pass over the columns.
@@ -635,6 +658,30 @@ __global__ __launch_bounds__(256) void tracer_diffusion_kernel(GridDev g, double
 #undef TAU
 #undef NE
 
+// forcing of a tracer (forcing = (T = ...), nonhydrostatic_tendency_kernel_functions.jl:258) and what follows it in a stage boundary:
+//   Gc <- Gc + F,  then the bottom / top flux contributions (apply_flux_bcs.jl:107-160),  then the NEXT stage's rk3 substep
+// -- the operations of tracer_finish / tracer_tendency_direct in the same order, on a Gc that holds advection and diffusion.  Tracers live
+// at (c,c,c), whose parent layout is the same on grids with and without walls, so one kernel serves both.  k is uniform per workgroup.
+__global__ __launch_bounds__(256) void tracer_forcing_kernel(GridDev g, ocn::ForcingDev f, const double *__restrict__ c,
+                                                             double *__restrict__ Gc, PRange r, ocn::TracerFuse tf)
+{
+    const int i = r.i0 + blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = r.j0 + blockIdx.y * blockDim.y + threadIdx.y;
+    const int k = r.k0 + blockIdx.z;
+    if (i > r.i1 || j > r.j1) return;
+    const Metrics M = make_metrics(g);
+    const long long o = ocn::at(ocn::make_lay(g, OCN_LOC_CCC), i, j, k);
+    const double c0 = c[o], az = M.Az;
+    double G = Gc[o];
+    if (f.n) G = G + ocn::forcing_at(f, i - 1 + g.Hx, j - 1 + g.Hy, k - 1 + g.Hz, o, c0);
+    if (g.tz == OCN_BOUNDED) {
+        if (k == 1 && tf.bottom.kind == OCN_BC_FLUX) G += ocn::bc_condition(tf.bottom, i, j, g.Nx, c0) * az / (az * M.dzC(1));
+        if (k == g.Nz && tf.top.kind == OCN_BC_FLUX) G -= ocn::bc_condition(tf.top, i, j, g.Nx, c0) * az / (az * M.dzC(g.Nz));
+    }
+    Gc[o] = G;
+    if (tf.sc.on) tf.sub.out[o] = c0 + (tf.sc.has_zeta ? tf.sc.dt * (tf.sc.gamma * G + tf.sc.zeta * tf.sub.Gm[o]) : (tf.sc.dt * tf.sc.gamma) * G);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------------
@@ -677,7 +724,7 @@ int launch_tracer_centered2(const ocn_grid *grid, const double *u, const double 
 
 int launch_momentum_extra(const ocn_grid *grid, const TermsDev &t, const double *u, const double *v, const double *w,
                           double *Gu, double *Gv, double *Gw, const int32_t *range, hipStream_t stream,
-                          const ocn::MomentumFinal *fin, const ocn::StokesDev *stokes)
+                          const ocn::MomentumFinal *fin, const ocn::StokesDev *stokes, const ocn::MomentumForcingDev *forcing)
 {
     ocn::MomentumFinal mf{};
     if (fin) mf = *fin;
@@ -696,6 +743,24 @@ int launch_momentum_extra(const ocn_grid *grid, const TermsDev &t, const double 
         int KZ = wz;  // z-chunk: enough workgroups to fill the chip, long enough to amortise the two-plane prologue
         while (KZ > 16 && tiles * ((wz + KZ - 1) / KZ) < 4096) KZ = (KZ + 1) / 2;
         dim3 nbt((wx + 31) / 32, (wy + 7) / 8, (wz + KZ - 1) / KZ);
+        if (forcing) {  // the variant with the forcing terms (and the Stokes terms when fd.stokes says so)
+            const ocn::StokesDev sd = stokes ? *stokes : ocn::StokesDev{};
+            ocn::MomentumForcingDev fd = *forcing;
+            fd.stokes = stokes != nullptr;
+            if (grid->tz == OCN_PERIODIC) {
+                if (share)
+                    hipLaunchKernelGGL((momentum_extra_tiled_forced<OCN_PERIODIC, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd, fd);
+                else
+                    hipLaunchKernelGGL((momentum_extra_tiled_forced<OCN_PERIODIC, false>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd, fd);
+            } else {
+                if (share)
+                    hipLaunchKernelGGL((momentum_extra_tiled_forced<OCN_BOUNDED, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd, fd);
+                else
+                    hipLaunchKernelGGL((momentum_extra_tiled_forced<OCN_BOUNDED, false>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd, fd);
+            }
+            OCN_CHECK_HIP(hipGetLastError());
+            return OCN_SUCCESS;
+        }
         if (stokes) {  // the same four variants, compiled with the Stokes-drift terms
             const ocn::StokesDev sd = *stokes;
             if (grid->tz == OCN_PERIODIC) {
@@ -727,6 +792,13 @@ int launch_momentum_extra(const ocn_grid *grid, const TermsDev &t, const double 
         return OCN_SUCCESS;
     }
     const dim3 block = ocn::range_block(r.i1 - r.i0 + 1), nb = ocn::range_grid(block, r.i1 - r.i0 + 1, r.j1 - r.j0 + 1, r.k1 - r.k0 + 1);
+    if (forcing) {
+        const ocn::StokesDev sd = stokes ? *stokes : ocn::StokesDev{};
+        ocn::MomentumForcingDev fd = *forcing;
+        fd.stokes = stokes != nullptr;
+        OCN_LAUNCH_TZ(momentum_extra_kernel_forced, g, t, u, v, w, Gu, Gv, Gw, r, mf, sd, fd);
+        return OCN_SUCCESS;
+    }
     if (stokes) {  // (the C ABI refuses a Flat z with Stokes drift)
         const ocn::StokesDev sd = *stokes;
         if (grid->tz == OCN_PERIODIC)
@@ -745,7 +817,7 @@ int launch_momentum_extra(const ocn_grid *grid, const TermsDev &t, const double 
 // per-field parent layouts.  *launched = 0 when the box is too small for the tiles (the caller then runs the per-cell kernel everywhere).
 int launch_momentum_extra_box(const ocn_grid *grid, const TermsDev &t, const double *u, const double *v, const double *w, double *Gu, double *Gv,
                               double *Gw, const int32_t box[4], int *launched, hipStream_t stream, const ocn::MomentumFinal *fin, int ranged,
-                              const ocn::StokesDev *stokes)
+                              const ocn::StokesDev *stokes, const ocn::MomentumForcingDev *forcing)
 {
     *launched = 0;
     ocn::MomentumFinal mf{};
@@ -763,6 +835,25 @@ int launch_momentum_extra_box(const ocn_grid *grid, const TermsDev &t, const dou
     int KZ = wz;
     while (KZ > 16 && tiles * ((wz + KZ - 1) / KZ) < 4096) KZ = (KZ + 1) / 2;
     dim3 nbt((wx + 31) / 32, (wy + 7) / 8, (wz + KZ - 1) / KZ);
+    if (forcing) {  // the variant with the forcing terms (and the Stokes terms when fd.stokes says so)
+        const ocn::StokesDev sd = stokes ? *stokes : ocn::StokesDev{};
+        ocn::MomentumForcingDev fd = *forcing;
+        fd.stokes = stokes != nullptr;
+        if (grid->tz == OCN_PERIODIC) {
+            if (share)
+                hipLaunchKernelGGL((momentum_extra_tiled_forced<OCN_PERIODIC, true, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd, fd);
+            else
+                hipLaunchKernelGGL((momentum_extra_tiled_forced<OCN_PERIODIC, false, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd, fd);
+        } else {
+            if (share)
+                hipLaunchKernelGGL((momentum_extra_tiled_forced<OCN_BOUNDED, true, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd, fd);
+            else
+                hipLaunchKernelGGL((momentum_extra_tiled_forced<OCN_BOUNDED, false, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd, fd);
+        }
+        OCN_CHECK_HIP(hipGetLastError());
+        *launched = 1;
+        return OCN_SUCCESS;
+    }
     if (stokes) {
         const ocn::StokesDev sd = *stokes;
         if (grid->tz == OCN_PERIODIC) {
@@ -818,6 +909,23 @@ int launch_tracer_diffusion(const ocn_grid *grid, double kappa, const double *ka
     GridDev g = ocn::to_dev(*grid);
     const dim3 block = ocn::range_block(r.i1 - r.i0 + 1), nb = ocn::range_grid(block, r.i1 - r.i0 + 1, r.j1 - r.j0 + 1, r.k1 - r.k0 + 1);
     OCN_LAUNCH_TZ(tracer_diffusion_kernel, g, kappa, kappa_e, c, Gc, r);
+    return OCN_SUCCESS;
+}
+
+// fuse: bottom / top fluxes and substep to run after the forcing (NULL: the forcing alone)
+int launch_tracer_forcing(const ocn_grid *grid, const ocn::ForcingDev &forcing, const double *c, double *Gc, const int32_t *range,
+                          const ocn::TracerFuse *fuse, hipStream_t stream)
+{
+    PRange r;
+    int st = make_prange(grid, range, r);
+    if (st != OCN_SUCCESS) return st;
+    if (r.i1 < r.i0 || r.j1 < r.j0 || r.k1 < r.k0) return OCN_SUCCESS;
+    ocn::TracerFuse tf{};
+    if (fuse) tf = *fuse;
+    GridDev g = ocn::to_dev(*grid);
+    const dim3 block = ocn::range_block(r.i1 - r.i0 + 1), nb = ocn::range_grid(block, r.i1 - r.i0 + 1, r.j1 - r.j0 + 1, r.k1 - r.k0 + 1);
+    hipLaunchKernelGGL(tracer_forcing_kernel, nb, block, 0, stream, g, forcing, c, Gc, r, tf);
+    OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
 }
 

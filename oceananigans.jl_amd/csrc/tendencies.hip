@@ -968,8 +968,10 @@ __device__ __forceinline__ Kappa7 kappa_from_global(const ocn::TracerFuse &tf, l
     const double *pk = tf.kappa_e + o;
     return Kappa7{pk[0], pk[-1], pk[1], pk[-s2], pk[s2], pk[-s3], pk[s3]};
 }
-template <int TZ>
-__device__ __forceinline__ double tracer_finish(double G, const Metrics &M, const GridDev &g, const ocn::TracerFuse &tf, int i, int j,
+// TF = ocn::TracerFuseForced: the sampled forcing of the tracer is added after the diffusion and before the boundary fluxes, the reference's
+// last addend (nonhydrostatic_tendency_kernel_functions.jl:258); c0 is in a register already.  Compiled out for TF = ocn::TracerFuse.
+template <int TZ, class TF>
+__device__ __forceinline__ double tracer_finish(double G, const Metrics &M, const GridDev &g, const TF &tf, int i, int j,
                                                 int k, const Kappa7 &K, double c0, double cxm, double cxp, double cym, double cyp,
                                                 double czm, double czp, double ax, double ay, double az)
 {
@@ -996,6 +998,10 @@ __device__ __forceinline__ double tracer_finish(double G, const Metrics &M, cons
 #undef OCN_TD
         G = G - recip_volume(az * dzc) * (((ax * qxe - ax * qxw) + (ay * qyn - ay * qys)) + dzq);
     }
+    if constexpr (TF::forced) {
+        if (tf.frc.n)
+            G = G + ocn::forcing_at(tf.frc, i - 1 + g.Hx, j - 1 + g.Hy, k - 1 + g.Hz, ocn::at(ocn::make_lay(g, OCN_LOC_CCC), i, j, k), c0);
+    }
     if (TZ == OCN_BOUNDED) {  // apply_z_bcs!: k is uniform across the workgroup
         if (k == 1 && tf.bottom.kind == OCN_BC_FLUX) G += ocn::bc_condition(tf.bottom, i, j, g.Nx, c0) * az / (az * M.dzC(1));
         if (k == g.Nz && tf.top.kind == OCN_BC_FLUX) G -= ocn::bc_condition(tf.top, i, j, g.Nx, c0) * az / (az * M.dzC(g.Nz));
@@ -1005,11 +1011,11 @@ __device__ __forceinline__ double tracer_finish(double G, const Metrics &M, cons
 
 // Direct kernel: one thread per cell, all six face fluxes evaluated in place.  `tf` (see tracer_finish) additionally carries
 // the NEXT stage's rk3 substep into a second storage.
-template <int TZ>
+template <int TZ, class TF = ocn::TracerFuse>
 __global__ __launch_bounds__(256) void tracer_tendency_direct(GridDev g, const double *__restrict__ u,
                                                               const double *__restrict__ v, const double *__restrict__ w,
                                                               const double *__restrict__ c, double *__restrict__ Gc, Range r,
-                                                              ocn::TracerFuse tf)
+                                                              TF tf)
 {
     const int i = r.i0 + blockIdx.x * blockDim.x + threadIdx.x;
     const int j = r.j0 + blockIdx.y * blockDim.y + threadIdx.y;
@@ -1034,9 +1040,14 @@ __global__ __launch_bounds__(256) void tracer_tendency_direct(GridDev g, const d
     const double rV = recip_volume(M.Az * M.dzC(k));
     double G = -(rV * (((fx1 - fx0) + (fy1 - fy0)) + dzF));
     const long long o = ocn::at(Lc, i, j, k), s2 = Lc.s2, s3 = (TZ == OCN_FLAT) ? 0 : Lc.s3;
-    if (tf.diffusion || tf.bottom.kind || tf.top.kind)
-        G = tracer_finish<TZ>(G, M, g, tf, i, j, k, kappa_from_global(tf, o, s2, s3), pc[0], pc[-1], pc[1], pc[-s2], pc[s2], pc[-s3],
+    if constexpr (TF::forced) {
+        if (tf.diffusion || tf.bottom.kind || tf.top.kind || tf.frc.n)
+            G = tracer_finish<TZ>(G, M, g, tf, i, j, k, kappa_from_global(tf, o, s2, s3), pc[0], pc[-1], pc[1], pc[-s2], pc[s2], pc[-s3], pc[s3], ax, ay, az);
+    } else {
+        if (tf.diffusion || tf.bottom.kind || tf.top.kind)
+            G = tracer_finish<TZ>(G, M, g, tf, i, j, k, kappa_from_global(tf, o, s2, s3), pc[0], pc[-1], pc[1], pc[-s2], pc[s2], pc[-s3],
                               pc[s3], ax, ay, az);
+    }
     Gc[o] = G;
     if (tf.sc.on) tf.sub.out[o] = pc[0] + (tf.sc.has_zeta ? tf.sc.dt * (tf.sc.gamma * G + tf.sc.zeta * tf.sub.Gm[o]) : (tf.sc.dt * tf.sc.gamma) * G);
 }
@@ -1049,10 +1060,10 @@ __global__ __launch_bounds__(256) void tracer_tendency_direct(GridDev g, const d
 //  * thread (i, j) evaluates the west-face and south-face fluxes of its cell and the top-face flux; the east / north ones come
 //    from the neighbouring threads through LDS, the bottom one is last iteration's top flux.
 // 3 flux evaluations per thread and plane instead of 6; the flux expressions are those of the direct kernel (bit-identical).
-template <int TZ, int TX, int TY, bool GL = false>
+template <int TZ, int TX, int TY, bool GL = false, class TF = ocn::TracerFuse>
 __global__ __launch_bounds__(TX *TY, 1) void tracer_tendency_tiled(GridDev g, const double *__restrict__ u, const double *__restrict__ v,
                                                                const double *__restrict__ w, const double *__restrict__ c,
-                                                               double *__restrict__ Gc, Range r, int KZ, ocn::TracerFuse tf)
+                                                               double *__restrict__ Gc, Range r, int KZ, TF tf)
 {
     constexpr int P = OCN_PERIODIC;
     constexpr int LX = TX + 5, LY = TY + 5, NT = TX * TY;
@@ -1195,8 +1206,13 @@ __global__ __launch_bounds__(TX *TY, 1) void tracer_tendency_tiled(GridDev g, co
             const double fxe = ex[0][tid + 1], fyn = ex[1][tid + TX];
             const double rV = recip_volume(M.Az * M.dzC(k));
             double G = -(rV * (((fxe - fxw) + (fyn - fys)) + (fzt - fzb)));
-            if (tf.diffusion || tf.bottom.kind || tf.top.kind)
-                G = tracer_finish<TZ>(G, M, g, tf, i, j, k, K, zc[2], cxm, cxp, cym, cyp, zc[1], zc[3], ax, ay, az);
+            if constexpr (TF::forced) {
+                if (tf.diffusion || tf.bottom.kind || tf.top.kind || tf.frc.n)
+                    G = tracer_finish<TZ>(G, M, g, tf, i, j, k, K, zc[2], cxm, cxp, cym, cyp, zc[1], zc[3], ax, ay, az);
+            } else {
+                if (tf.diffusion || tf.bottom.kind || tf.top.kind)
+                    G = tracer_finish<TZ>(G, M, g, tf, i, j, k, K, zc[2], cxm, cxp, cym, cyp, zc[1], zc[3], ax, ay, az);
+            }
             Gc[o] = G;
             if (tf.sc.on) tf.sub.out[o] = zc[2] + (tf.sc.has_zeta ? tf.sc.dt * (tf.sc.gamma * G + tf.sc.zeta * gm) : (tf.sc.dt * tf.sc.gamma) * G);
         }
@@ -1592,8 +1608,9 @@ int launch_momentum_tendencies_box(const ocn_grid *grid, const double *u, const 
     return OCN_SUCCESS;
 }
 
-int launch_tracer_tendency_box(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c, double *Gc,
-                               const int32_t box[4], int *launched, hipStream_t stream, const ocn::TracerFuse *fuse, int ranged)
+template <class TF>
+static int launch_tracer_tendency_box_t(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c, double *Gc,
+                                        const int32_t box[4], int *launched, hipStream_t stream, const TF &tf, int ranged)
 {
     (void)ranged;  // (a centre field has no excluded periphery)
     *launched = 0;
@@ -1603,18 +1620,27 @@ int launch_tracer_tendency_box(const ocn_grid *grid, const double *u, const doub
     r.ou = r.ov = r.ow = 1;
     const int wx = r.i1 - r.i0 + 1, wy = r.j1 - r.j0 + 1, wz = grid->Nz;
     if (grid->tz == OCN_FLAT || wx < 16 || wy < 8 || wz < 4) return OCN_SUCCESS;
-    GridDev g = ocn::to_dev(*grid);
-    ocn::TracerFuse tf{};
-    if (fuse) tf = *fuse;  // (diffusion, bottom / top fluxes, the next substep: all on centre fields, whose layout has no walls in it)
+    GridDev g = ocn::to_dev(*grid);  // (tf: diffusion, bottom / top fluxes, the next substep: all on centre fields, whose layout has no walls in it)
     constexpr int TX = 32, TY = 8;
     const PatchGrid pg = patch_grid(TX, TY, wx, wy, wz, min_blocks(), 16);
     if (grid->tz == OCN_PERIODIC)
-        hipLaunchKernelGGL((tracer_tendency_tiled<OCN_PERIODIC, TX, TY, true>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, pg.KZ, tf);
+        hipLaunchKernelGGL((tracer_tendency_tiled<OCN_PERIODIC, TX, TY, true, TF>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, pg.KZ, tf);
     else
-        hipLaunchKernelGGL((tracer_tendency_tiled<OCN_BOUNDED, TX, TY, true>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, pg.KZ, tf);
+        hipLaunchKernelGGL((tracer_tendency_tiled<OCN_BOUNDED, TX, TY, true, TF>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, pg.KZ, tf);
     OCN_CHECK_HIP(hipGetLastError());
     *launched = 1;
     return OCN_SUCCESS;
+}
+// forcing != NULL: the instantiation with the tracer's sampled forcing in tracer_finish
+int launch_tracer_tendency_box(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c, double *Gc,
+                               const int32_t box[4], int *launched, hipStream_t stream, const ocn::TracerFuse *fuse, int ranged,
+                               const ocn::ForcingDev *forcing)
+{
+    ocn::TracerFuseForced tf{};
+    if (fuse) static_cast<ocn::TracerFuse &>(tf) = *fuse;
+    if (!forcing) return launch_tracer_tendency_box_t<ocn::TracerFuse>(grid, u, v, w, c, Gc, box, launched, stream, tf, ranged);
+    tf.frc = *forcing;
+    return launch_tracer_tendency_box_t(grid, u, v, w, c, Gc, box, launched, stream, tf, ranged);
 }
 
 // Which kernel runs (none of the tiled ones on a Flat z):
@@ -1691,11 +1717,10 @@ int launch_momentum_tendencies(const ocn_grid *grid, const double *u, const doub
     return OCN_SUCCESS;
 }
 
-int launch_tracer_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c,
-                           double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse)
+template <class TF>
+static int launch_tracer_tendency_t(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c,
+                                    double *Gc, const int32_t *range, hipStream_t stream, const TF &tf)
 {
-    ocn::TracerFuse tf{};
-    if (fuse) tf = *fuse;
     Range r;
     int st = make_range(grid, range, r);
     if (st != OCN_SUCCESS) return st;
@@ -1707,27 +1732,37 @@ int launch_tracer_tendency(const ocn_grid *grid, const double *u, const double *
         constexpr int TX = 32, TY = 8;
         const PatchGrid pg = patch_grid(TX, TY, wx, wy, wz, min_blocks(), 16);
         if (grid->tz == OCN_PERIODIC)
-            hipLaunchKernelGGL((tracer_tendency_tiled<OCN_PERIODIC, TX, TY>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, pg.KZ, tf);
+            hipLaunchKernelGGL((tracer_tendency_tiled<OCN_PERIODIC, TX, TY, false, TF>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, pg.KZ, tf);
         else
-            hipLaunchKernelGGL((tracer_tendency_tiled<OCN_BOUNDED, TX, TY>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, pg.KZ, tf);
+            hipLaunchKernelGGL((tracer_tendency_tiled<OCN_BOUNDED, TX, TY, false, TF>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, pg.KZ, tf);
     } else if (!tracer_direct && grid->tz != OCN_FLAT && wx <= 3 && wy >= 64 && wz >= 4) {  // halo-wide x-strips: 4 x 64 patches
         constexpr int TX = 4, TY = 64;
         const PatchGrid pg = patch_grid(TX, TY, wx, wy, wz, 2048, strip_min_kz());
         if (grid->tz == OCN_PERIODIC)
-            hipLaunchKernelGGL((tracer_tendency_tiled<OCN_PERIODIC, TX, TY>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, pg.KZ, tf);
+            hipLaunchKernelGGL((tracer_tendency_tiled<OCN_PERIODIC, TX, TY, false, TF>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, pg.KZ, tf);
         else
-            hipLaunchKernelGGL((tracer_tendency_tiled<OCN_BOUNDED, TX, TY>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, pg.KZ, tf);
+            hipLaunchKernelGGL((tracer_tendency_tiled<OCN_BOUNDED, TX, TY, false, TF>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, c, Gc, r, pg.KZ, tf);
     } else {
         const dim3 block = ocn::range_block(wx), nb = ocn::range_grid(block, wx, wy, wz);
         switch (grid->tz) {
-            case OCN_PERIODIC: hipLaunchKernelGGL(tracer_tendency_direct<OCN_PERIODIC>, nb, block, 0, stream, g, u, v, w, c, Gc, r, tf); break;
-            case OCN_BOUNDED: hipLaunchKernelGGL(tracer_tendency_direct<OCN_BOUNDED>, nb, block, 0, stream, g, u, v, w, c, Gc, r, tf); break;
-            case OCN_FLAT: hipLaunchKernelGGL(tracer_tendency_direct<OCN_FLAT>, nb, block, 0, stream, g, u, v, w, c, Gc, r, tf); break;
+            case OCN_PERIODIC: hipLaunchKernelGGL((tracer_tendency_direct<OCN_PERIODIC, TF>), nb, block, 0, stream, g, u, v, w, c, Gc, r, tf); break;
+            case OCN_BOUNDED: hipLaunchKernelGGL((tracer_tendency_direct<OCN_BOUNDED, TF>), nb, block, 0, stream, g, u, v, w, c, Gc, r, tf); break;
+            case OCN_FLAT: hipLaunchKernelGGL((tracer_tendency_direct<OCN_FLAT, TF>), nb, block, 0, stream, g, u, v, w, c, Gc, r, tf); break;
             default: ocn::set_error("unsupported z topology %d", grid->tz); return OCN_ERR_UNSUPPORTED;
         }
     }
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
+}
+
+int launch_tracer_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c,
+                           double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse, const ocn::ForcingDev *forcing)
+{
+    ocn::TracerFuseForced tf{};
+    if (fuse) static_cast<ocn::TracerFuse &>(tf) = *fuse;
+    if (!forcing) return launch_tracer_tendency_t<ocn::TracerFuse>(grid, u, v, w, c, Gc, range, stream, tf);
+    tf.frc = *forcing;
+    return launch_tracer_tendency_t(grid, u, v, w, c, Gc, range, stream, tf);
 }
 
 // both tracers must take the tiled path (the caller falls back to two single launches otherwise): returns 1 when launched

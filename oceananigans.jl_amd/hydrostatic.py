@@ -151,7 +151,7 @@ class SplitExplicitFreeSurface:
 class HydrostaticFreeSurfaceModel:
     def __init__(self, grid, momentum_advection=None, tracer_advection=None, tracers=(), free_surface=None, coriolis=None,
                  closure=None, buoyancy=None, boundary_conditions=None, fused=None, timestepper="QuasiAdamsBashforth2", math_mode=None,
-                 stokes_drift=None):
+                 stokes_drift=None, forcing=None):
         """fused (default: True with VectorInvariant() momentum): one QAB2 step = one pass for the horizontal momentum (tendency, AB2
         step, barotropic forcing and mode), one launch per WENO / UpwindBiased tracer (tendency + AB2 step), the temporally blocked
         substep loop, one pass for the barotropic corrector + w, one halo launch, the hydrostatic pressure; the tendency evaluation
@@ -160,6 +160,8 @@ class HydrostaticFreeSurfaceModel:
         from .grids import FullyConnected, require_regular_xy
         if stokes_drift is not None:
             raise NotImplementedError("stokes_drift on HydrostaticFreeSurfaceModel is not implemented (NonhydrostaticModel takes UniformStokesDrift)")
+        if forcing is not None:
+            raise NotImplementedError("forcing on HydrostaticFreeSurfaceModel is not implemented (NonhydrostaticModel takes forcing=; see DESIGN.md §10)")
         require_regular_xy(grid, "HydrostaticFreeSurfaceModel")
         timestepper = str(timestepper).lstrip(":")
         if timestepper not in ("QuasiAdamsBashforth2", "SplitRungeKutta3"):

@@ -9,7 +9,8 @@ Mirrors, call for call:
   time_step!(model::RungeKutta3, Δt)                              src/TimeSteppers/runge_kutta_3.jl:77-151
   time_step!(model::QuasiAdamsBashforth2, Δt)                     src/TimeSteppers/quasi_adams_bashforth_2.jl:74-115
   cache_previous_tendencies!                                      src/TimeSteppers/store_tendencies.jl:12-22
-Julia's `f!` names are spelled `f` here.  forcing, background_fields are `nothing`; stokes_drift is UniformStokesDrift (stokes.py); advection is WENO()
+Julia's `f!` names are spelled `f` here.  background_fields is `nothing`; forcing is a dict of arrays, Relaxation(...) and Forcing(func)
+(forcings.py); stokes_drift is UniformStokesDrift (stokes.py); advection is WENO()
 or Centered(); coriolis = FPlane, closure = ScalarDiffusivity, buoyancy = BuoyancyTracer / SeawaterBuoyancy and bottom /
 top Flux / Value / Gradient boundary conditions are the SURVEY §8(f) rank-1 terms (physics.py); anything else raises.
 """
@@ -31,6 +32,7 @@ from .fields import CenterField, Field, XFaceField, YFaceField, ZFaceField, fill
 from .grids import Bounded, Flat, require_regular_xy
 from .solvers import nonhydrostatic_pressure_solver
 from .stokes import DeviceStokesDrift, UniformStokesDrift
+from .forcings import DeviceForcing, field_location, validate_forcing
 
 
 class Clock:
@@ -87,8 +89,6 @@ class NonhydrostaticModel:
         """math_mode: None keeps the grid's (default: the process default, ocn.set_math_mode); MATH_STRICT / MATH_FAST pin this
         model's arithmetic variant whatever other models of the process use (ocn_grid.math)."""
         require_regular_xy(grid, "NonhydrostaticModel")
-        if forcing is not None:
-            raise NotImplementedError("forcing != nothing is outside the MI355X hot-path scope (see DESIGN.md)")
         # stokes_drift: UniformStokesDrift on one GPU (refused here, before anything is allocated, otherwise)
         if stokes_drift is not None:
             if not isinstance(stokes_drift, UniformStokesDrift):
@@ -114,6 +114,9 @@ class NonhydrostaticModel:
         if isinstance(tracers, str):
             tracers = (tracers,)
         tracers = tuple(tracers)
+        # forcing: parsed and refused here, before anything is allocated (bare functions, more than four terms, unknown fields, wrong array
+        # shapes, unsupported kinds, a Distributed architecture: forcings.py)
+        forcing_terms = validate_forcing(forcing, grid, ("u", "v", "w") + tracers) if forcing else {}
         if buoyancy is not None:  # validate_buoyancy (BuoyancyFormulations/buoyancy_force.jl:66-76)
             for req in buoyancy.required_tracers:
                 if req not in tracers:
@@ -200,10 +203,16 @@ class NonhydrostaticModel:
         self._has_user_bcs = any(not b.is_default() for b in list(bcs.values()) + list(kappa_bcs.values()) + ([nu_bcs] if nu_bcs else []))
         self._has_flux_bcs = any(b.has_flux() for b in bcs.values())
         self.general_terms = (isinstance(advection, (Centered, UpwindBiased)) or coriolis is not None or closure is not None
-                              or buoyancy is not None or self._has_user_bcs or stokes_drift is not None)
+                              or buoyancy is not None or self._has_user_bcs or stokes_drift is not None or bool(forcing_terms))
         # the profiles sampled on this grid's z nodes, as device vectors (struct ocn_stokes_drift); a model whose only extra term is the Stokes
         # drift takes the general-terms route too (tiled WENO launch + finishing pass), not the correction-on-load kernel
         self._stokes = DeviceStokesDrift(stokes_drift, grid) if stokes_drift is not None else None
+        # the sampled forcing of every forced field (struct ocn_forcing + its device vectors / arrays), in the order of prognostic_fields()
+        self.forcing = forcing_terms
+        self._forcing = [DeviceForcing(forcing_terms[n], grid, field_location(n)) if n in forcing_terms else None
+                         for n in ("u", "v", "w") + tracers]
+        self._momentum_forced = any(f is not None for f in self._forcing[:3])
+        self.forcing_steady = all(f is None or f.steady for f in self._forcing)
         if self._has_user_bcs and hasattr(grid.architecture, "partition") and any(
                 s is not None and (s.values is not None or s.func is not None) for b in bcs.values() for s in b.sides.values()):
             raise NotImplementedError("array / function boundary conditions on a Distributed architecture are not implemented")
@@ -438,8 +447,13 @@ def compute_tendencies_(model, rng=None, boundary_contributions=True):
     s = stream_ptr()
     if model.general_terms:
         t = C.byref(model._terms)
+        frc = _refresh_forcing(model)
         if model._stokes is not None:
             model._stokes.refresh(model.clock.time)  # profiles that depend on t: sampled at the time of this tendency evaluation
+        if model._momentum_forced:
+            _lib.call("ocn_compute_momentum_tendencies_terms_forced", g.cref, t, None if model._stokes is None else C.byref(model._stokes.c),
+                      _lib.forcing_array(frc[:3]), model.u.ptr, model.v.ptr, model.w.ptr, Gn[0].ptr, Gn[1].ptr, Gn[2].ptr, r, s)
+        elif model._stokes is not None:
             _lib.call("ocn_compute_momentum_tendencies_terms_stokes", g.cref, t, C.byref(model._stokes.c), model.u.ptr, model.v.ptr, model.w.ptr,
                       Gn[0].ptr, Gn[1].ptr, Gn[2].ptr, r, s)
         else:
@@ -451,6 +465,10 @@ def compute_tendencies_(model, rng=None, boundary_contributions=True):
                 kappa_e = model.diffusivity_fields["kappa_e"][n].ptr
             elif model.closure is not None:
                 kappa = model.closure.kappa_of(model.tracer_names[n])
+            if frc[3 + n] is not None:
+                _lib.call("ocn_compute_tracer_tendency_terms_forced", g.cref, t, kappa, kappa_e, frc[3 + n], model.u.ptr, model.v.ptr, model.w.ptr,
+                          c.ptr, Gn[3 + n].ptr, r, s)
+                continue
             _lib.call("ocn_compute_tracer_tendency_terms", g.cref, t, kappa, kappa_e, model.u.ptr, model.v.ptr, model.w.ptr, c.ptr,
                       Gn[3 + n].ptr, r, s)
         if boundary_contributions:
@@ -460,6 +478,16 @@ def compute_tendencies_(model, rng=None, boundary_contributions=True):
               Gn[2].ptr, r, s)
     for n, c in enumerate(model.tracers):
         _lib.call("ocn_compute_tracer_tendency", g.cref, model.u.ptr, model.v.ptr, model.w.ptr, c.ptr, Gn[3 + n].ptr, r, s)
+
+
+def _refresh_forcing(model):
+    """struct ocn_forcing references of the prognostic fields (None: not forced), the terms that depend on t sampled at clock.time"""
+    refs = []
+    for f in model._forcing:
+        if f is not None:
+            f.refresh(model.clock.time)
+        refs.append(None if f is None else f.ref)
+    return refs
 
 
 def compute_boundary_tendency_contributions(model):
@@ -584,14 +612,16 @@ def _bcs_ref(field, grid):
     return C.byref(b.c_struct(grid)) if b is not None and b.has_flux() else None
 
 
-def fused_tracer_launches(grid, terms_ref, u, v, w, tracers, kappas, kappa_es, Gn, Gm, outs, dt, gamma, zeta, has_zeta, rng, s):
+def fused_tracer_launches(grid, terms_ref, u, v, w, tracers, kappas, kappa_es, Gn, Gm, outs, dt, gamma, zeta, has_zeta, rng, s, forcing=None):
     """tendency + boundary flux + the next substep of every tracer: pairs of tracers share ONE launch
     (ocn_compute_tracer_pair_tendency_terms_rk3: u, v, w and the tile staging are read once for both), a remaining single tracer -- and
-    ranges too small for the tiled kernel -- take ocn_compute_tracer_tendency_terms_rk3."""
+    ranges too small for the tiled kernel -- take ocn_compute_tracer_tendency_terms_rk3.  forcing: one struct ocn_forcing reference (or None)
+    per tracer; a forced tracer takes ocn_compute_tracer_tendency_terms_rk3_forced, and a pair with a forced tracer runs as two single launches."""
     n, q = len(tracers), 0
+    forcing = forcing or [None] * n
     r = None if rng is None else _lib.i32_array(list(rng))
     while q < n:
-        if q + 1 < n:
+        if q + 1 < n and forcing[q] is None and forcing[q + 1] is None:
             pair = (q, q + 1)
             did = C.c_int32(0)
             bcs = (C.POINTER(_lib.CFieldBcs) * 2)(*[(C.pointer(tracers[t].boundary_conditions.c_struct(grid))
@@ -606,6 +636,11 @@ def fused_tracer_launches(grid, terms_ref, u, v, w, tracers, kappas, kappa_es, G
                 q += 2
                 continue
         c = tracers[q]
+        if forcing[q] is not None:
+            _lib.call("ocn_compute_tracer_tendency_terms_rk3_forced", grid.cref, terms_ref, float(kappas[q]), kappa_es[q], forcing[q], _bcs_ref(c, grid),
+                      u.ptr, v.ptr, w.ptr, c.ptr, Gn[q].ptr, Gm[q].ptr, outs[q].data_ptr(), float(dt), float(gamma), float(zeta), int(has_zeta), r, s)
+            q += 1
+            continue
         _lib.call("ocn_compute_tracer_tendency_terms_rk3", grid.cref, terms_ref, float(kappas[q]), kappa_es[q], _bcs_ref(c, grid), u.ptr, v.ptr,
                   w.ptr, c.ptr, Gn[q].ptr, Gm[q].ptr, outs[q].data_ptr(), float(dt), float(gamma), float(zeta), int(has_zeta), r, s)
         q += 1
@@ -631,11 +666,17 @@ def _update_state_and_rk3_substep_general(model, dt, gamma, zeta, fill_halos=Tru
                       or model._stokes is not None)
     if model._stokes is not None:
         model._stokes.refresh(model.clock.time)
+    frc = _refresh_forcing(model)
 
     def launch(rng=None):
         s = stream_ptr()  # read HERE: the Distributed hook runs the east buffer strip under torch.cuda.stream(side stream)
         r = None if rng is None else _lib.i32_array(list(rng))
-        if model._stokes is not None:
+        if model._momentum_forced:
+            _lib.call("ocn_compute_momentum_tendencies_terms_rk3_forced", g.cref, t, None if model._stokes is None else C.byref(model._stokes.c),
+                      _lib.forcing_array(frc[:3]), _bcs_ref(model.u, g), _bcs_ref(model.v, g), model.u.ptr, model.v.ptr, model.w.ptr, Gn[0].ptr,
+                      Gn[1].ptr, Gn[2].ptr, Gm[0].ptr, Gm[1].ptr, Gm[2].ptr, alt[0].data_ptr(), alt[1].data_ptr(), alt[2].data_ptr(), float(dt),
+                      float(gamma), z, hz, r, s)
+        elif model._stokes is not None:
             _lib.call("ocn_compute_momentum_tendencies_terms_rk3_stokes", g.cref, t, C.byref(model._stokes.c), _bcs_ref(model.u, g),
                       _bcs_ref(model.v, g), model.u.ptr, model.v.ptr, model.w.ptr, Gn[0].ptr, Gn[1].ptr, Gn[2].ptr, Gm[0].ptr, Gm[1].ptr,
                       Gm[2].ptr, alt[0].data_ptr(), alt[1].data_ptr(), alt[2].data_ptr(), float(dt), float(gamma), z, hz, r, s)
@@ -655,7 +696,8 @@ def _update_state_and_rk3_substep_general(model, dt, gamma, zeta, fill_halos=Tru
                     kappa_es[n] = model.diffusivity_fields["kappa_e"][n].ptr
                 elif model.closure is not None:
                     kappas[n] = model.closure.kappa_of(model.tracer_names[n])
-            fused_tracer_launches(g, t, model.u, model.v, model.w, model.tracers, kappas, kappa_es, Gn[3:], Gm[3:], alt[3:], dt, gamma, z, hz, rng, s)
+            fused_tracer_launches(g, t, model.u, model.v, model.w, model.tracers, kappas, kappa_es, Gn[3:], Gm[3:], alt[3:], dt, gamma, z, hz, rng, s,
+                                  forcing=frc[3:])
 
     hook = getattr(model.architecture, "update_state_general", None) if fill_halos else None
     if hook is not None:  # Distributed: halo exchange overlapped with the interior auxiliaries and tendencies (distributed.py)
@@ -871,6 +913,9 @@ class ModelRK3Driver:
         if model._stokes is not None and not model.stokes_drift.steady:
             raise NotImplementedError("ModelRK3Driver: a time-dependent UniformStokesDrift needs the Python host (time_step(model, dt) samples the "
                                       "profiles at every tendency evaluation); pass steady=True for profiles that do not depend on t")
+        if not getattr(model, "forcing_steady", True):
+            raise NotImplementedError("ModelRK3Driver: a forcing that depends on time needs the Python host (time_step(model, dt) samples it at "
+                                      "every tendency evaluation); pass steady=True for functions that do not depend on t")
         flush_tendencies(model)
         self.model = model
         desc = _lib.CModelDriverDesc()
@@ -917,6 +962,8 @@ class ModelRK3Driver:
                       model.pNHS.ptr, None if own_solver else model.pressure_solver._h, stream_ptr())
         if model._stokes is not None:  # steady profiles: the device vectors stay the model's
             _lib.call("ocn_model_driver_set_stokes_drift", self._h, C.byref(model._stokes.c), 0)
+        if any(f is not None for f in model._forcing):  # steady terms: the device vectors / arrays stay the model's
+            _lib.call("ocn_model_driver_set_forcing", self._h, _lib.forcing_array([None if f is None else f.ref for f in model._forcing]), 0)
 
     def time_step(self, dt):
         _lib.call("ocn_model_driver_time_step", self._h, float(dt), stream_ptr())

@@ -1,0 +1,388 @@
+"""forcing = {...} of NonhydrostaticModel on the GPU.
+
+The forcing of a field is the LAST addend of its tendency (nonhydrostatic_tendency_kernel_functions.jl:77, 137, 199, 258), so the reference
+result is G0 + F: G0 what the entry points without forcing return (ocn_compute_momentum_tendencies_terms_stokes,
+ocn_compute_tracer_tendency_terms: pinned to the oracle by test_gpu_kernels / test_gpu_physics / test_gpu_general / test_gpu_stokes_drift)
+and F restated below in NumPy from the host vectors the device was given, in the reference's operand order
+    Relaxation: (rate * mask) * (target - field)      several terms: F = t1; F = F + t2; ...      (relaxation.jl:95-101, multiple_forcings.jl:34-46)
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from helpers import from_dev, stretched_faces
+
+pytestmark = pytest.mark.gpu
+
+EPS = np.finfo(np.float64).eps
+NAME = {"P": "Periodic", "B": "Bounded", "F": "Flat"}
+G1, G2, G3, Z2, Z3 = 8 / 15, 5 / 12, 3 / 4, -17 / 60, -5 / 12
+
+
+def _grid(ocn, size, topo, z):
+    nonflat = [d for d in range(3) if topo[d] != "F"]
+    ext = {"x": (0, 2.0), "y": (0, 3.0), "z": z}
+    kw = {n: (None if topo[d] == "F" else ext[n]) for d, n in enumerate("xyz")}
+    return ocn.RectilinearGrid(ocn.GPU(), size=tuple(size[d] for d in nonflat), topology=tuple(NAME[t] for t in topo),
+                               halo=tuple(3 for _ in nonflat), **kw)
+
+
+def _random_field(ocn, pg, loc, rng, scale=1.0):
+    import torch
+    f = ocn.Field(loc, pg)
+    f.data.copy_(torch.from_numpy(scale * rng.uniform(-1, 1, tuple(f.data.shape))))
+    return f
+
+
+def _numpy_forcing(ocn, pg, terms, loc, field_parent, r):
+    """F on the window r = (i0, i1, j0, j1, k0, k1) (1-based interior indices) of a field at `loc` from the host samples of its terms"""
+    from oceananigans_jl_amd.forcings import sample_term
+    H = (pg.Hx, pg.Hy, pg.Hz)
+    sl = tuple(slice(r[2 * d] - 1, r[2 * d + 1]) for d in range(3))            # into interior-shaped arrays
+    c = field_parent[tuple(slice(H[d] + r[2 * d] - 1, H[d] + r[2 * d + 1]) for d in range(3))]
+
+    def profile(dim, a, number):
+        if dim < 0:
+            return number
+        if dim == 3:
+            return a[sl]
+        shape = [1, 1, 1]
+        shape[dim] = -1
+        return a[H[dim] + r[2 * dim] - 1:H[dim] + r[2 * dim + 1]].reshape(shape)   # a vector with halos: element 0 <-> index 1 - H
+
+    F = None
+    for term in terms:
+        h = sample_term(term, pg, loc, 0.0)
+        if h["kind"] == 1:
+            v = h["values"][sl]
+        else:
+            v = (h["rate"] * profile(h["mask_dim"], h["mask"], 1.0)) * (profile(h["target_dim"], h["target"], h["target_value"]) - c)
+        F = v if F is None else F + v
+    return np.broadcast_to(F, c.shape)
+
+
+def _forcing_set(ocn, pg, topo, rng):
+    """every code path: z-Gaussian sponge with a number target on u, x-LinearTarget with a 3-D mask on v, an array plus a Relaxation on w,
+    four terms on the tracer"""
+    from oceananigans_jl_amd.forcings import interior_shape
+    zmid = 0.5 * (pg.nodes_1d(2, True)[0] + pg.nodes_1d(2, True)[-1])
+    sh = {n: interior_shape(pg, loc) for n, loc in (("u", 1), ("v", 2), ("w", 4), ("c", 0))}
+    src = lambda *a: 0.2 * np.cos(3 * a[0]) + 0.1 * a[-2] + 0 * a[-1]   # (x, [y,] z, t): x first, z before t; Flat directions are omitted
+    src.__name__ = "src"
+    return {
+        "u": [ocn.Relaxation(0.7, mask=ocn.GaussianMask("z", center=zmid, width=1.3), target=0.25)],
+        "v": [ocn.Relaxation(0.4, mask=rng.uniform(0, 1, sh["v"]), target=ocn.LinearTarget("x", intercept=0.1, gradient=-0.3))],
+        "w": [rng.uniform(-1, 1, sh["w"]), ocn.Relaxation(0.9)],
+        "c": [rng.uniform(-1, 1, sh["c"]),
+              ocn.Relaxation(0.5, mask=ocn.GaussianMask("z", center=zmid, width=0.8),
+                             target=ocn.LinearTarget("z" if topo[1] == "F" else "y", intercept=0.3, gradient=0.05)),   # a vector along y where there is one
+              ocn.Forcing(src, steady=True),
+              ocn.Relaxation(0.2, mask=lambda *a: 0.5 + 0.5 * np.sin(2 * a[0]) + 0 * a[-1], target=rng.uniform(-1, 1, sh["c"]))],
+    }
+
+
+CASES = [((37, 21, 11), "PPP", (-4.0, 0.0)),         # tiled path; not multiples of the 32 x 8 patches
+         ((40, 19, 10), "PPB", "stretched"),         # tiled path, stretched z
+         ((41, 29, 9), "BBB", "stretched"),          # general path: tiled interior box + wall frames
+         ((24, 1, 10), "PFB", (-2.0, 0.0))]          # general path, per-cell kernel on a slice
+
+
+def _setup(ocn, size, topo, z, others, mode, rng):
+    import torch
+    from oceananigans_jl_amd.forcings import DeviceForcing
+    from oceananigans_jl_amd.stokes import FIELDS, z_nodes
+    if isinstance(z, str):
+        z = stretched_faces(size[2], 5.0)
+    pg = _grid(ocn, size, topo, z)
+    ocn.set_math_mode(ocn.MATH_STRICT if mode == "strict" else ocn.MATH_FAST)
+    L = ocn._lib
+    fields = {n: _random_field(ocn, pg, loc, rng) for n, loc in (("u", 1), ("v", 2), ("w", 4), ("c", 0))}
+    b = _random_field(ocn, pg, 0, rng, 1e-2)
+    terms = L.CModelTerms()
+    terms.advection = L.ADVECTION_WENO5
+    if others:
+        terms.coriolis, terms.f = 1, 0.7
+        terms.closure, terms.nu = 1, 3e-2
+        terms.buoyancy, terms.T = L.BUOYANCY_TRACER, b.ptr
+    zc, zf = z_nodes(pg)
+    prof = {"dz_us_center": 0.3 * np.exp(zc / 2.0), "dz_us_face": 0.3 * np.exp(zf / 2.0), "dz_vs_center": -0.2 * np.exp(zc / 1.5),
+            "dz_vs_face": -0.2 * np.exp(zf / 1.5), "dt_us": 0.05 * np.cos(zc), "dt_vs": 0.04 * np.sin(zc)}
+    dev = {n: torch.from_numpy(np.ascontiguousarray(prof[n])).cuda() for n in FIELDS}
+    sd = L.CStokesDrift(*[dev[n].data_ptr() for n in FIELDS])
+    fset = _forcing_set(ocn, pg, topo, rng)
+    dforce = {n: DeviceForcing(fset[n], pg, loc) for n, loc in (("u", 1), ("v", 2), ("w", 4), ("c", 0))}
+    keep = (b, dev)
+    return pg, L, fields, terms, sd, fset, dforce, keep
+
+
+def _ranges(pg, topo):
+    Nx, Ny, Nz = pg.Nx, pg.Ny, pg.Nz
+    return {"u": (2 if topo[0] == "B" else 1, Nx, 1, Ny, 1, Nz), "v": (1, Nx, 2 if topo[1] == "B" else 1, Ny, 1, Nz),
+            "w": (1, Nx, 1, Ny, 2 if topo[2] == "B" else 1, Nz), "c": (1, Nx, 1, Ny, 1, Nz)}
+
+
+@pytest.mark.parametrize("mode", ["strict", "fast"])
+@pytest.mark.parametrize("others", [False, True], ids=["stokes_only", "last_of_many"])
+@pytest.mark.parametrize("size,topo,z", CASES, ids=[c[1] + "_" + "x".join(map(str, c[0])) for c in CASES])
+def test_tendencies_equal_the_unforced_ones_plus_F(ocn, size, topo, z, others, mode):
+    """Strict: Gu, Gv, Gw, Gc bitwise equal to G0 + F.  Fast: within the per-launch bound 1e-12 max|G| of test_gpu_kernels."""
+    rng = np.random.default_rng(20261017)
+    pg, L, f, terms, sd, fset, dforce, keep = _setup(ocn, size, topo, z, others, mode, rng)
+    u, v, w, c = f["u"], f["v"], f["w"], f["c"]
+    kappa = 2e-2 if others else 0.0
+    G0 = {n: ocn.Field(loc, pg) for n, loc in (("u", 1), ("v", 2), ("w", 4), ("c", 0))}
+    G1 = {n: ocn.Field(loc, pg) for n, loc in (("u", 1), ("v", 2), ("w", 4), ("c", 0))}
+    L.call("ocn_compute_momentum_tendencies_terms_stokes", pg.cref, C.byref(terms), C.byref(sd), u.ptr, v.ptr, w.ptr, G0["u"].ptr, G0["v"].ptr,
+           G0["w"].ptr, None, 0)
+    L.call("ocn_compute_tracer_tendency_terms", pg.cref, C.byref(terms), kappa, None, u.ptr, v.ptr, w.ptr, c.ptr, G0["c"].ptr, None, 0)
+    L.call("ocn_compute_momentum_tendencies_terms_forced", pg.cref, C.byref(terms), C.byref(sd), L.forcing_array([dforce[n].ref for n in "uvw"]),
+           u.ptr, v.ptr, w.ptr, G1["u"].ptr, G1["v"].ptr, G1["w"].ptr, None, 0)
+    L.call("ocn_compute_tracer_tendency_terms_forced", pg.cref, C.byref(terms), kappa, None, dforce["c"].ref, u.ptr, v.ptr, w.ptr, c.ptr,
+           G1["c"].ptr, None, 0)
+    ocn.sync_device()
+    H = (pg.Hx, pg.Hy, pg.Hz)
+    for n, loc in (("u", 1), ("v", 2), ("w", 4), ("c", 0)):
+        r = _ranges(pg, topo)[n]
+        F = _numpy_forcing(ocn, pg, fset[n], loc, from_dev(f[n]), r)
+        a0, a1 = from_dev(G0[n]), from_dev(G1[n])
+        win = tuple(slice(H[d] + r[2 * d] - 1, H[d] + r[2 * d + 1]) for d in range(3))
+        expected = a0.copy()
+        expected[win] = a0[win] + F
+        scale, err = np.abs(expected).max(), np.abs(a1 - expected).max()
+        print(f"{topo} {size} {mode} others={others} G{n}: max|G| = {scale:.3e}, max|F| = {np.abs(F).max():.3e}, max err = {err:.3e}")
+        assert np.abs(F).max() > 0
+        if mode == "strict":
+            assert a1.tobytes() == expected.tobytes(), f"G{n} differs bitwise from G0 + F (max err {err:.3e})"
+        else:
+            assert err <= 1e-12 * scale, f"G{n}: {err:.3e} > 1e-12 * {scale:.3e}"
+
+
+def test_all_null_forcing_is_the_entry_point_without_the_suffix(ocn):
+    rng = np.random.default_rng(3)
+    pg, L, f, terms, sd, fset, dforce, keep = _setup(ocn, (40, 19, 10), "PPB", "stretched", True, "strict", rng)
+    Ga = [ocn.Field(loc, pg) for loc in (1, 2, 4)]
+    Gb = [ocn.Field(loc, pg) for loc in (1, 2, 4)]
+    L.call("ocn_compute_momentum_tendencies_terms_stokes", pg.cref, C.byref(terms), C.byref(sd), f["u"].ptr, f["v"].ptr, f["w"].ptr, Ga[0].ptr,
+           Ga[1].ptr, Ga[2].ptr, None, 0)
+    L.call("ocn_compute_momentum_tendencies_terms_forced", pg.cref, C.byref(terms), C.byref(sd), L.forcing_array([None, None, None]),
+           f["u"].ptr, f["v"].ptr, f["w"].ptr, Gb[0].ptr, Gb[1].ptr, Gb[2].ptr, None, 0)
+    ocn.sync_device()
+    for a, b in zip(Ga, Gb):
+        assert from_dev(a).tobytes() == from_dev(b).tobytes()
+
+
+@pytest.mark.parametrize("mode", ["strict", "fast"])
+@pytest.mark.parametrize("size,topo,z", CASES[1:3], ids=["PPB", "BBB"])
+def test_fused_stage_boundary_equals_the_unfused_sequence(ocn, size, topo, z, mode):
+    """_rk3_forced == _forced + ocn_apply_flux_bcs + ocn_rk3_substep, bit for bit in strict math, for momentum and one tracer, with top flux
+    conditions so that the order (forcing, then flux) is what is tested.  Fast math (on Periodic x, y the finishing pass then runs BEFORE
+    the advective launch, with the forcing in it): within the per-launch bound 1e-12 max|.| of test_gpu_kernels."""
+    rng = np.random.default_rng(11)
+    pg, L, f, terms, sd, fset, dforce, keep = _setup(ocn, size, topo, z, True, mode, rng)
+    names = (("u", 1), ("v", 2), ("w", 4), ("c", 0))
+    bcs = {"u": ocn.FieldBoundaryConditions(top=ocn.FluxBoundaryCondition(-3.7e-2)), "v": ocn.FieldBoundaryConditions(bottom=ocn.FluxBoundaryCondition(1.1e-2)),
+           "c": ocn.FieldBoundaryConditions(top=ocn.FluxBoundaryCondition(2.3e-2))}
+    cb = {n: b.c_struct(pg) for n, b in bcs.items()}
+    Gm = {n: _random_field(ocn, pg, loc, rng) for n, loc in names}
+    dt, gamma, zeta, kappa = 0.01, G2, Z2, 2e-2
+    # unfused
+    Ga = {n: ocn.Field(loc, pg) for n, loc in names}
+    Ua = {n: ocn.Field(loc, pg, data=f[n].data.clone()) for n, loc in names}
+    L.call("ocn_compute_momentum_tendencies_terms_forced", pg.cref, C.byref(terms), C.byref(sd), L.forcing_array([dforce[n].ref for n in "uvw"]),
+           f["u"].ptr, f["v"].ptr, f["w"].ptr, Ga["u"].ptr, Ga["v"].ptr, Ga["w"].ptr, None, 0)
+    L.call("ocn_compute_tracer_tendency_terms_forced", pg.cref, C.byref(terms), kappa, None, dforce["c"].ref, f["u"].ptr, f["v"].ptr, f["w"].ptr,
+           f["c"].ptr, Ga["c"].ptr, None, 0)
+    order = ["u", "v", "w", "c"]
+    arr = (C.POINTER(L.CFieldBcs) * 4)(*[(C.pointer(cb[n]) if n in cb else C.POINTER(L.CFieldBcs)()) for n in order])
+    locs = L.i32_array([1, 2, 4, 0])
+    L.call("ocn_apply_flux_bcs", pg.cref, L.ptr_array([Ga[n].ptr for n in order]), L.ptr_array([f[n].ptr for n in order]), locs, arr, 4, 0)
+    L.call("ocn_rk3_substep", pg.cref, 4, L.ptr_array([Ua[n].ptr for n in order]), L.ptr_array([Ga[n].ptr for n in order]),
+           L.ptr_array([Gm[n].ptr for n in order]), locs, dt, gamma, zeta, 1, 0)
+    # fused
+    Gb = {n: ocn.Field(loc, pg) for n, loc in names}
+    Ub = {n: ocn.Field(loc, pg, data=f[n].data.clone()) for n, loc in names}
+    L.call("ocn_compute_momentum_tendencies_terms_rk3_forced", pg.cref, C.byref(terms), C.byref(sd), L.forcing_array([dforce[n].ref for n in "uvw"]),
+           C.byref(cb["u"]), C.byref(cb["v"]), f["u"].ptr, f["v"].ptr, f["w"].ptr, Gb["u"].ptr, Gb["v"].ptr, Gb["w"].ptr, Gm["u"].ptr, Gm["v"].ptr,
+           Gm["w"].ptr, Ub["u"].ptr, Ub["v"].ptr, Ub["w"].ptr, dt, gamma, zeta, 1, None, 0)
+    L.call("ocn_compute_tracer_tendency_terms_rk3_forced", pg.cref, C.byref(terms), kappa, None, dforce["c"].ref, C.byref(cb["c"]), f["u"].ptr,
+           f["v"].ptr, f["w"].ptr, f["c"].ptr, Gb["c"].ptr, Gm["c"].ptr, Ub["c"].ptr, dt, gamma, zeta, 1, None, 0)
+    ocn.sync_device()
+    H = (pg.Hx, pg.Hy, pg.Hz)
+    for n, loc in names:
+        ga, gb, ua, ub = (from_dev(x) for x in (Ga[n], Gb[n], Ua[n], Ub[n]))
+        r = _ranges(pg, topo)[n]
+        win = tuple(slice(H[d] + r[2 * d] - 1, H[d] + r[2 * d + 1]) for d in range(3))
+        assert np.abs(ga[win]).max() > 0
+        inner = tuple(slice(H[d], ua.shape[d] - H[d]) for d in range(3))
+        dG, dU = np.abs(ga[win] - gb[win]).max(), np.abs(ua[inner] - ub[inner]).max()
+        print(f"{topo} {mode} {n}: max|G| = {np.abs(ga[win]).max():.3e}, fused - unfused: G {dG:.3e}, U_out {dU:.3e}")
+        if mode == "strict":
+            assert ga[win].tobytes() == gb[win].tobytes(), f"G{n}: fused != unfused (max diff {dG:.3e})"
+            assert ua[inner].tobytes() == ub[inner].tobytes(), f"{n}_out: fused != unfused (max diff {dU:.3e})"
+        else:
+            assert dG <= 1e-12 * np.abs(ga[win]).max() and dU <= 1e-12 * np.abs(ua[inner]).max()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# closed forms, whole models (strict math; bound 16 eps n_stages max|.| as in the Stokes time test)
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("stepper", ["RungeKutta3", "QuasiAdamsBashforth2"])
+def test_unit_forcing_of_a_tracer_at_rest(ocn, stepper):
+    """forcing = (T = 1), fluid at rest: T = 10 Δt after ten steps; with QAB2 the first step gives exactly Δt (the reference's property)"""
+    ocn.set_math_mode(ocn.MATH_STRICT)
+    g = ocn.RectilinearGrid(ocn.GPU(), size=(16, 8, 12), x=(0, 10), y=(0, 10), z=(-30, 0), topology=("Periodic", "Periodic", "Bounded"), halo=(3, 3, 3))
+    m = ocn.NonhydrostaticModel(g, advection=ocn.WENO(), tracers=("T",), timestepper=stepper, forcing={"T": np.ones((16, 8, 12))})
+    dt = 0.375
+    ocn.time_step(m, dt, euler=True) if stepper == "QuasiAdamsBashforth2" else ocn.time_step(m, dt)
+    ocn.flush_tendencies(m)
+    ocn.sync_device()
+    T1 = np.asarray(m.tracers[0].interior())
+    if stepper == "QuasiAdamsBashforth2":
+        assert np.all(T1 == dt), f"T after one QAB2 step: {T1.min()} .. {T1.max()} != {dt}"
+    for _ in range(9):
+        ocn.time_step(m, dt)
+    ocn.flush_tendencies(m)
+    ocn.sync_device()
+    T = np.asarray(m.tracers[0].interior())
+    bound = 16 * EPS * 30 * 10 * dt
+    err = np.abs(T - 10 * dt).max()
+    print(f"{stepper}: max|T - 10 dt| = {err:.3e}, bound = {bound:.3e}")
+    assert err <= bound
+    assert all(np.all(np.asarray(f.interior()) == 0) for f in m.velocities)
+
+
+def _rk3_relaxation(c0, rm, cstar, dt, n):
+    """c' = rm (c* - c) with the model's RK3 stage coefficients (runge_kutta_3.jl:77-151)"""
+    c = c0.copy()
+    for _ in range(n):
+        Ga = rm * (cstar - c)
+        c = c + dt * G1 * Ga
+        Gb = rm * (cstar - c)
+        c = c + dt * (G2 * Gb + Z2 * Ga)
+        Gc = rm * (cstar - c)
+        c = c + dt * (G3 * Gc + Z3 * Gb)
+    return c
+
+
+@pytest.mark.parametrize("name", ["c", "u"])
+def test_sponge_relaxes_every_level_like_the_scalar_ode(ocn, name):
+    """uniform c0 (or a horizontally uniform u(z): divergence-free, the projection leaves it alone), Relaxation(rate, GaussianMask("z"), c*),
+    fluid otherwise at rest, no closure: every level is c' = r m(z) (c* - c).  Dropping the mask must miss the bound by >= 1e6 (NumPy)."""
+    ocn.set_math_mode(ocn.MATH_STRICT)
+    g = ocn.RectilinearGrid(ocn.GPU(), size=(16, 8, 12), x=(0, 10), y=(0, 10), z=(-30, 0), topology=("Periodic", "Periodic", "Bounded"), halo=(3, 3, 3))
+    mask = ocn.GaussianMask("z", center=-30, width=8)
+    rate, cstar, c0, dt, n = 0.05, 0.7, 0.2, 1.5, 10
+    m = ocn.NonhydrostaticModel(g, advection=ocn.WENO(), tracers=("c",), forcing={name: ocn.Relaxation(rate, mask=mask, target=cstar)})
+    ocn.set(m, **{name: c0})
+    zc = g.nodes_1d(2, False)
+    expected = _rk3_relaxation(np.full(zc.shape, c0), rate * mask.along(zc), cstar, dt, n)
+    bound = 16 * EPS * 3 * n * np.abs(expected).max()
+    assert np.abs(_rk3_relaxation(np.full(zc.shape, c0), rate * np.ones(zc.shape), cstar, dt, n) - expected).max() >= 1e6 * bound
+    for _ in range(n):
+        ocn.time_step(m, dt)
+    ocn.flush_tendencies(m)
+    ocn.sync_device()
+    a = np.asarray(m.field(name).interior())
+    err = np.abs(a - expected[None, None, :]).max()
+    print(f"{name}: max err = {err:.3e}, bound = {bound:.3e}")
+    assert err <= bound
+    others = [f for f in m.prognostic_fields() if f is not m.field(name)]
+    assert all(np.all(np.asarray(f.interior()) == 0) for f in others)
+
+
+def test_time_dependent_forcing_is_sampled_at_the_stage_times(ocn):
+    """Forcing(a + b t) on u: RK3 is exact for a right-hand side linear in t; a one-stage shift of the sampling time misses by >= 1e6 bounds"""
+    from test_gpu_stokes_drift import _numpy_rk3
+    ocn.set_math_mode(ocn.MATH_STRICT)
+    g = ocn.RectilinearGrid(ocn.GPU(), size=(16, 8, 12), x=(0, 10), y=(0, 10), z=(-30, 0), topology=("Periodic",) * 3, halo=(3, 3, 3))
+    a, b, dt, n = 1e-3, 2e-5, 3.0, 10
+    exact = a * n * dt + b * (n * dt) ** 2 / 2
+    bound = 16 * EPS * 30 * abs(exact)
+    one = np.ones(1)
+    assert np.abs(_numpy_rk3(a * one, b * one, dt, n) - exact).max() <= bound
+    assert np.abs(_numpy_rk3(a * one, b * one, dt, n, shift=1) - exact).max() >= 1e6 * bound
+    frc = ocn.Forcing(lambda x, y, z, t: a + b * t)
+    assert not frc.steady
+    m = ocn.NonhydrostaticModel(g, advection=ocn.WENO(), forcing={"u": frc})
+    for _ in range(n):
+        ocn.time_step(m, dt)
+    ocn.flush_tendencies(m)
+    ocn.sync_device()
+    u = np.asarray(m.u.interior())
+    err = np.abs(u - exact).max()
+    print(f"max|u - exact| = {err:.3e}, bound = {bound:.3e}")
+    assert err <= bound
+    assert np.all(np.asarray(m.v.interior()) == 0) and np.all(np.asarray(m.w.interior()) == 0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# ModelRK3Driver
+# ---------------------------------------------------------------------------------------------------------------------------
+def _sponges(ocn, g, names, steady=True):
+    sponge = lambda target: ocn.Relaxation(1 / 50.0, mask=ocn.GaussianMask("z", center=g.nodes_1d(2, True)[0], width=g.Lz / 8), target=target)
+    out = {n: sponge(None) for n in "uvw"}
+    for n in names:
+        out[n] = sponge(ocn.LinearTarget("z", intercept=0.0, gradient=1.936e-5))
+    if not steady:
+        out["u"] = ocn.Forcing(lambda x, y, z, t: 1e-6 * t)
+    return out
+
+
+def _langmuir(ocn, steady=True):
+    g = ocn.RectilinearGrid(ocn.GPU(), size=(32, 32, 32), x=(0, 128), y=(0, 128), z=(-64, 0), topology=("Periodic", "Periodic", "Bounded"))
+    shear = lambda z, t: 0.0681 / 4.77 * np.exp(z / 4.77)
+    bcs = {"u": ocn.FieldBoundaryConditions(top=ocn.FluxBoundaryCondition(-3.72e-5)),
+           "b": ocn.FieldBoundaryConditions(top=ocn.FluxBoundaryCondition(2.307e-8), bottom=ocn.GradientBoundaryCondition(1.936e-5))}
+    return ocn.NonhydrostaticModel(g, coriolis=ocn.FPlane(f=1e-4), advection=ocn.WENO(), tracers=("b",), buoyancy=ocn.BuoyancyTracer(),
+                                   closure=ocn.AnisotropicMinimumDissipation(), boundary_conditions=bcs,
+                                   stokes_drift=ocn.UniformStokesDrift(dz_us=shear, steady=True), forcing=_sponges(ocn, g, ("b",), steady))
+
+
+def _closed_box(ocn):
+    g = ocn.RectilinearGrid(ocn.GPU(), size=(64, 64, 9), x=(0, 64), y=(0, 64), z=stretched_faces(9, 32.0), topology=("Bounded",) * 3)
+    return ocn.NonhydrostaticModel(g, advection=ocn.WENO(), tracers=("b",), buoyancy=ocn.BuoyancyTracer(), coriolis=ocn.FPlane(f=1e-4),
+                                   closure=ocn.ScalarDiffusivity(ν=1e-3, κ=2e-3),
+                                   stokes_drift=ocn.UniformStokesDrift(dz_us=lambda z, t: 5e-3 * np.exp(z / 6.0), dz_vs=lambda z, t: 2e-3 * np.exp(z / 9.0),
+                                                                       dt_us=lambda z, t: 1e-6 * np.exp(z / 6.0), steady=True),
+                                   forcing=_sponges(ocn, g, ("b",)))
+
+
+@pytest.mark.parametrize("build", [_langmuir, _closed_box], ids=["langmuir_32", "closed_box"])
+def test_model_driver_with_sponges_equals_the_python_host(ocn, build):
+    """5 steps behind ocn_model_driver_time_step == 5 x time_step(model, dt), bit for bit (strict math), Stokes drift and forcing both on"""
+    ocn.set_math_mode(ocn.MATH_STRICT)
+    rng = np.random.default_rng(7)
+    models = [build(ocn), build(ocn)]
+    g = models[0].grid
+    walls = g.topology[0] == "Bounded"
+    init = {"u": 1e-2 * rng.uniform(-1, 1, (g.Nx + walls, g.Ny, g.Nz)), "v": 1e-2 * rng.uniform(-1, 1, (g.Nx, g.Ny + walls, g.Nz)),
+            "b": 1e-4 * rng.uniform(-1, 1, (g.Nx, g.Ny, g.Nz))}
+    for m in models:
+        ocn.set(m, **init)
+    ref, m = models
+    for _ in range(5):
+        ocn.time_step(ref, 2.0)
+    Gref = [f.parent() for f in ref.timestepper.Gn]
+    drv = ocn.ModelRK3Driver(m)
+    for _ in range(5):
+        drv.time_step(2.0)
+    drv.flush()
+    ocn.sync_device()
+    assert m.clock.time == ref.clock.time and m.clock.iteration == 5
+    for name, fa, fb in zip(("u", "v", "w", "b"), ref.prognostic_fields(), m.prognostic_fields()):
+        assert np.abs(fa.parent()).max() > 0
+        assert fa.parent().tobytes() == fb.parent().tobytes(), f"{name} differs between the driver and the Python host"
+    for name, Ga, fb in zip(("Gu", "Gv", "Gw", "Gb"), Gref, m.timestepper.Gn):
+        assert np.asarray(Ga).tobytes() == fb.parent().tobytes(), f"{name} differs"
+
+
+def test_model_driver_refuses_a_time_dependent_forcing(ocn):
+    m = _langmuir(ocn, steady=False)
+    with pytest.raises(NotImplementedError, match="Python host"):
+        ocn.ModelRK3Driver(m)
+    ok = _langmuir(ocn)
+    drv = ocn.ModelRK3Driver(ok)
+    refs = ocn._lib.forcing_array([None if f is None else f.ref for f in ok._forcing])
+    with pytest.raises(ocn.OcnError, match="Python host"):
+        ocn._lib.call("ocn_model_driver_set_forcing", drv._h, refs, 1)
