@@ -15,6 +15,8 @@
 // (nonhydrostatic_tendency_kernel_functions.jl:47-259, momentum_advection_operators.jl:46-83, closure_kernel_operators.jl:27-53),
 // bit-identical to the CPU oracle.
 //
+// The Stokes-drift and forcing terms of momentum_extra_general are selected by its pack of descriptor arguments, as in physics.hip.
+//
 // Compiled twice like tendencies.hip (namespaces via ocn_weno.h): strict / fast, WENO5 or UpwindBiased(order = 5).
 #include <algorithm>
 #include <cstdlib>
@@ -255,31 +257,148 @@ __device__ __forceinline__ double gen_buoyancy(const ocn::TermsDev &t, long long
     }
 }
 
-// the kernel without and with the Stokes-drift terms (see momentum_extra_general.inc)
-#define OCN_EXTRA_GENERAL momentum_extra_general
-#define OCN_EXTRA_STK 0
-#define OCN_EXTRA_FRC 0
-#define OCN_EXTRA_SD_PARAM
-#include "momentum_extra_general.inc"
-#undef OCN_EXTRA_GENERAL
-#undef OCN_EXTRA_STK
-#undef OCN_EXTRA_SD_PARAM
-#define OCN_EXTRA_GENERAL momentum_extra_general_stokes
-#define OCN_EXTRA_STK 1
-#define OCN_EXTRA_SD_PARAM ocn::StokesDev sd,
-#include "momentum_extra_general.inc"
-#undef OCN_EXTRA_GENERAL
-#undef OCN_EXTRA_FRC
-#undef OCN_EXTRA_SD_PARAM
-// ... and the one variant with the forcing terms (both descriptors, either may be empty)
-#define OCN_EXTRA_GENERAL momentum_extra_general_forced
-#define OCN_EXTRA_FRC 1
-#define OCN_EXTRA_SD_PARAM ocn::StokesDev sd, ocn::MomentumForcingDev fd,
-#include "momentum_extra_general.inc"
-#undef OCN_EXTRA_GENERAL
-#undef OCN_EXTRA_STK
-#undef OCN_EXTRA_FRC
-#undef OCN_EXTRA_SD_PARAM
+// The trailing pack X selects the variant (ocn_common.h: extra_arg): nothing, ocn::StokesDev -- (∇ × uˢ) × u + ∂t uˢ added last
+// (StokesDrifts.jl:165-180), with the plain nested two-point averages of interpolation_operators.jl:50-56 (the value itself along a Flat
+// x / y) -- or ocn::StokesDev, ocn::MomentumForcingDev: the sampled forcing of each component after the Stokes terms (which then run only when
+// fd->stokes says the drift is in use).  The pack is not last (every kernel here ends with its frames), so X is never deduced: the launcher names it.
+template <class... X>
+__global__ __launch_bounds__(256) void momentum_extra_general(gen::Fields F, ocn::TermsDev t, double *__restrict__ Gu, double *__restrict__ Gv,
+                                                              double *__restrict__ Gw, X... x, gen::GFrames fr)
+{
+    using namespace gen;
+    constexpr bool STK = sizeof...(X) >= 1, FRC = sizeof...(X) == 2;
+    gen::GRange r;
+    int i, j, k;
+    if (!gen::frame_cell(fr, r, i, j, k)) return;
+    const GridDev &g = F.g;
+    const Metrics M = make_metrics(g);
+    const Lay &Lu = F.Lu, &Lv = F.Lv, &Lw = F.Lw, &Lc = F.Lc;
+    const double *u = F.u, *v = F.v, *w = F.w, *nu_e = t.nu_e;
+    const bool fx = g.tx == OCN_FLAT, fy = g.ty == OCN_FLAT, fz = g.tz == OCN_FLAT;
+    const double dx = M.dx, dy = M.dy, nu = t.nu;
+    const ocn::StokesDev *sd = ocn::extra_arg<ocn::StokesDev, 0>(x...);
+    const ocn::MomentumForcingDev *fd = ocn::extra_arg<ocn::MomentumForcingDev, 1>(x...);
+    auto stk = [&] { return STK && (!FRC || fd->stokes); };  // (read at each use, not hoisted: the kernels compile to what they always did)
+#define U_(a, b, c) u[ocn::at(Lu, a, b, c)]
+#define V_(a, b, c) v[ocn::at(Lv, a, b, c)]
+#define W_(a, b, c) w[ocn::at(Lw, a, b, c)]
+#define NE(a, b, c) nu_e[ocn::at(Lc, a, b, c)]
+    // derivative operators (derivative_operators.jl:20-30); a difference along a Flat direction is 0
+    auto DXU_C = [&](int a, int b, int c) { return fx ? 0.0 : (U_(a + 1, b, c) - U_(a, b, c)) / dx; };
+    auto DYV_C = [&](int a, int b, int c) { return fy ? 0.0 : (V_(a, b + 1, c) - V_(a, b, c)) / dy; };
+    auto DZW_C = [&](int a, int b, int c) { return fz ? 0.0 : (W_(a, b, c + 1) - W_(a, b, c)) / M.dzC(c); };
+    auto DYU_FF = [&](int a, int b, int c) { return fy ? 0.0 : (U_(a, b, c) - U_(a, b - 1, c)) / dy; };
+    auto DXV_FF = [&](int a, int b, int c) { return fx ? 0.0 : (V_(a, b, c) - V_(a - 1, b, c)) / dx; };
+    auto DZU_FF = [&](int a, int b, int c) { return fz ? 0.0 : (U_(a, b, c) - U_(a, b, c - 1)) / M.dzF(c); };
+    auto DXW_FF = [&](int a, int b, int c) { return fx ? 0.0 : (W_(a, b, c) - W_(a - 1, b, c)) / dx; };
+    auto DZV_FF = [&](int a, int b, int c) { return fz ? 0.0 : (V_(a, b, c) - V_(a, b, c - 1)) / M.dzF(c); };
+    auto DYW_FF = [&](int a, int b, int c) { return fy ? 0.0 : (W_(a, b, c) - W_(a, b - 1, c)) / dy; };
+    // viscosity at the stress locations (abstract_scalar_diffusivity_closure.jl:291-296)
+    auto NU_C = [&](int a, int b, int c) { return nu_e ? NE(a, b, c) : nu; };
+    auto NU_FFC = [&](int a, int b, int c) { return nu_e ? 0.5 * (0.5 * (NE(a - 1, b - 1, c) + NE(a, b - 1, c)) + 0.5 * (NE(a - 1, b, c) + NE(a, b, c))) : nu; };
+    auto NU_FCF = [&](int a, int b, int c) { return nu_e ? 0.5 * (0.5 * (NE(a - 1, b, c - 1) + NE(a, b, c - 1)) + 0.5 * (NE(a - 1, b, c) + NE(a, b, c))) : nu; };
+    auto NU_CFF = [&](int a, int b, int c) { return nu_e ? 0.5 * (0.5 * (NE(a, b - 1, c - 1) + NE(a, b, c - 1)) + 0.5 * (NE(a, b - 1, c) + NE(a, b, c))) : nu; };
+    auto T11 = [&](int a, int b, int c) { return -2 * (NU_C(a, b, c) * DXU_C(a, b, c)); };
+    auto T22 = [&](int a, int b, int c) { return -2 * (NU_C(a, b, c) * DYV_C(a, b, c)); };
+    auto T33 = [&](int a, int b, int c) { return -2 * (NU_C(a, b, c) * DZW_C(a, b, c)); };
+    auto T12 = [&](int a, int b, int c) { return -2 * (NU_FFC(a, b, c) * (0.5 * (DYU_FF(a, b, c) + DXV_FF(a, b, c)))); };
+    auto T13 = [&](int a, int b, int c) { return -2 * (NU_FCF(a, b, c) * (0.5 * (DZU_FF(a, b, c) + DXW_FF(a, b, c)))); };
+    auto T23 = [&](int a, int b, int c) { return -2 * (NU_CFF(a, b, c) * (0.5 * (DZV_FF(a, b, c) + DYW_FF(a, b, c)))); };
+    // inactive_cell (Grids/inactive_node.jl:35-95) and the peripheral-node tests of the Coriolis average
+    auto inactive = [&](int a, int b, int c) {
+        bool q = false;
+        if (g.tx == OCN_BOUNDED) q |= (g.xw && a < 1) | (g.xe && a > g.Nx);  // (inactive_node.jl:5-25: by side on the half-Bounded slabs)
+        if (g.ty == OCN_BOUNDED) q |= (b < 1) | (b > g.Ny);
+        if (g.tz == OCN_BOUNDED) q |= (c < 1) | (c > g.Nz);
+        return q;
+    };
+    auto act_cfc = [&](int a, int b, int c) { return (inactive(a, b, c) || inactive(a, b - 1, c)) ? 0.0 : 1.0; };
+    auto act_fcc = [&](int a, int b, int c) { return (inactive(a, b, c) || inactive(a - 1, b, c)) ? 0.0 : 1.0; };
+    const double Axc = M.Ax(k), Ayc = M.Ay(k), Az = M.Az;
+    if (i >= r.ou) {
+        const long long o = ocn::at(Lu, i, j, k);
+        double G = Gu[o];
+        if (t.buoyancy) G = G + 0.0;
+        if (t.coriolis) {  // x_f_cross_U = -f * active_weighted_ℑxyᶠᶜᶜ(v)
+            auto IXF = [&](int jj) { return fx ? V_(i, jj, k) : 0.5 * (V_(i - 1, jj, k) + V_(i, jj, k)); };
+            auto IXFa = [&](int jj) { return fx ? act_cfc(i, jj, k) : 0.5 * (act_cfc(i - 1, jj, k) + act_cfc(i, jj, k)); };
+            const double an = fy ? IXFa(j) : 0.5 * (IXFa(j) + IXFa(j + 1));
+            const double vi = (an == 0) ? 0.0 : (fy ? IXF(j) : 0.5 * (IXF(j) + IXF(j + 1))) / an;
+            G = G - (-ocn::coriolis_f_at(t, g.Hy, j, 0) * vi);
+        }
+        if (t.pHY) G = G - (fx ? 0.0 : (t.pHY[ocn::at(Lc, i, j, k)] - t.pHY[ocn::at(Lc, i - 1, j, k)]) / dx);
+        if (t.closure) {
+            const double dxF = fx ? 0.0 : Axc * T11(i, j, k) - Axc * T11(i - 1, j, k);
+            const double dyF = fy ? 0.0 : Ayc * T12(i, j + 1, k) - Ayc * T12(i, j, k);
+            const double dzF = fz ? 0.0 : Az * T13(i, j, k + 1) - Az * T13(i, j, k);
+            G = G - 1 / (Az * M.dzC(k)) * ((dxF + dyF) + dzF);
+        }
+        if (stk()) {  // ℑxzᶠᵃᶜ(w) ∂z_uˢ(z centre k) + ∂t_uˢ
+            auto IX = [&](int c) { return fx ? W_(i, j, c) : 0.5 * (W_(i - 1, j, c) + W_(i, j, c)); };
+            G = G + (0.5 * (IX(k) + IX(k + 1))) * ocn::stokes_at(sd->dzu_c, k);
+            G = G + ocn::stokes_at(sd->dtu, k);
+        }
+        if (FRC && fd->f[0].n) G = G + ocn::forcing_at(fd->f[0], i - 1 + g.Hx, j - 1 + g.Hy, k - 1 + g.Hz, o, u[o]);
+        Gu[o] = G;
+    }
+    if (j >= r.ov) {
+        const long long o = ocn::at(Lv, i, j, k);
+        double G = Gv[o];
+        if (t.buoyancy) G = G + 0.0;
+        if (t.coriolis) {  // y_f_cross_U = f * active_weighted_ℑxyᶜᶠᶜ(u)
+            auto IXC = [&](int jj) { return fx ? U_(i, jj, k) : 0.5 * (U_(i, jj, k) + U_(i + 1, jj, k)); };
+            auto IXCa = [&](int jj) { return fx ? act_fcc(i, jj, k) : 0.5 * (act_fcc(i, jj, k) + act_fcc(i + 1, jj, k)); };
+            const double an = fy ? IXCa(j) : 0.5 * (IXCa(j - 1) + IXCa(j));
+            const double ui = (an == 0) ? 0.0 : (fy ? IXC(j) : 0.5 * (IXC(j - 1) + IXC(j))) / an;
+            G = G - ocn::coriolis_f_at(t, g.Hy, j, 1) * ui;
+        }
+        if (t.pHY) G = G - (fy ? 0.0 : (t.pHY[ocn::at(Lc, i, j, k)] - t.pHY[ocn::at(Lc, i, j - 1, k)]) / dy);
+        if (t.closure) {
+            const double dxF = fx ? 0.0 : Axc * T12(i + 1, j, k) - Axc * T12(i, j, k);
+            const double dyF = fy ? 0.0 : Ayc * T22(i, j, k) - Ayc * T22(i, j - 1, k);
+            const double dzF = fz ? 0.0 : Az * T23(i, j, k + 1) - Az * T23(i, j, k);
+            G = G - 1 / (Az * M.dzC(k)) * ((dxF + dyF) + dzF);
+        }
+        if (stk()) {  // ℑyzᵃᶠᶜ(w) ∂z_vˢ(z centre k) + ∂t_vˢ
+            auto IY = [&](int c) { return fy ? W_(i, j, c) : 0.5 * (W_(i, j - 1, c) + W_(i, j, c)); };
+            G = G + (0.5 * (IY(k) + IY(k + 1))) * ocn::stokes_at(sd->dzv_c, k);
+            G = G + ocn::stokes_at(sd->dtv, k);
+        }
+        if (FRC && fd->f[1].n) G = G + ocn::forcing_at(fd->f[1], i - 1 + g.Hx, j - 1 + g.Hy, k - 1 + g.Hz, o, v[o]);
+        Gv[o] = G;
+    }
+    if (k >= r.ow) {
+        const long long o = ocn::at(Lw, i, j, k);
+        double G = Gw[o];
+        if (t.buoyancy) {
+            double zb = 0.0;
+            if (!t.pHY) zb = fz ? gen_buoyancy(t, ocn::at(Lc, i, j, k))
+                                : 1 * (0.5 * (gen_buoyancy(t, ocn::at(Lc, i, j, k - 1)) + gen_buoyancy(t, ocn::at(Lc, i, j, k))));
+            G = G + zb;
+        }
+        if (t.coriolis) G = G - 0.0;
+        if (t.closure) {
+            const double Axf = dy * M.dzF(k), Ayf = dx * M.dzF(k);
+            const double dxF = fx ? 0.0 : Axf * T13(i + 1, j, k) - Axf * T13(i, j, k);
+            const double dyF = fy ? 0.0 : Ayf * T23(i, j + 1, k) - Ayf * T23(i, j, k);
+            const double dzF = fz ? 0.0 : Az * T33(i, j, k) - Az * T33(i, j, k - 1);
+            G = G - 1 / (Az * M.dzF(k)) * ((dxF + dyF) + dzF);
+        }
+        if (stk()) {  // -ℑxzᶜᵃᶠ(u) ∂z_uˢ(z face k) - ℑyzᵃᶜᶠ(v) ∂z_vˢ(z face k), ∂t_wˢ = 0
+            auto IX = [&](int c) { return fx ? U_(i, j, c) : 0.5 * (U_(i, j, c) + U_(i + 1, j, c)); };
+            auto IY = [&](int c) { return fy ? V_(i, j, c) : 0.5 * (V_(i, j, c) + V_(i, j + 1, c)); };
+            const double ui = 0.5 * (IX(k - 1) + IX(k)), vi = 0.5 * (IY(k - 1) + IY(k));
+            G = G + (-(ui * ocn::stokes_at(sd->dzu_f, k)) - vi * ocn::stokes_at(sd->dzv_f, k));
+            G = G + 0.0;
+        }
+        if (FRC && fd->f[2].n) G = G + ocn::forcing_at(fd->f[2], i - 1 + g.Hx, j - 1 + g.Hy, k - 1 + g.Hz, o, w[o]);
+        Gw[o] = G;
+    }
+#undef U_
+#undef V_
+#undef W_
+#undef NE
+}
 
 // Gc <- Gc - ∇_dot_qᶜ (closure_kernel_operators.jl:48-53), κ a number or the eddy diffusivity field interpolated to the faces
 __global__ __launch_bounds__(256) void tracer_diffusion_general(GridDev g, double kappa, const double *__restrict__ kappa_e,
@@ -586,14 +705,10 @@ int launch_momentum_extra_general(const ocn_grid *grid, const ocn::TermsDev &t, 
         if (launched) cells = frames_around(grid, box, r);
     }
 #endif
-    if (forcing) {
-        ocn::MomentumForcingDev fd = *forcing;
-        fd.stokes = stokes != nullptr;
-        OCN_GEN_LAUNCH(momentum_extra_general_forced, cells, F, t, Gu, Gv, Gw, stokes ? *stokes : ocn::StokesDev{}, fd);
-    } else if (stokes)
-        OCN_GEN_LAUNCH(momentum_extra_general_stokes, cells, F, t, Gu, Gv, Gw, *stokes);
-    else
-        OCN_GEN_LAUNCH(momentum_extra_general, cells, F, t, Gu, Gv, Gw);
+    ocn::with_extra_descriptors(stokes, forcing, [&](auto... x) {
+        OCN_GEN_LAUNCH(momentum_extra_general<decltype(x)...>, cells, F, t, Gu, Gv, Gw, x...);
+        return OCN_SUCCESS;
+    });
     if (finish) OCN_GEN_LAUNCH(momentum_finish_general, cells, F, Gu, Gv, Gw, *fin);
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;

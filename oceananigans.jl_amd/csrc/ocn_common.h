@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <tuple>
 
 #include "../../include/ocn_hip.h"
 
@@ -222,6 +223,30 @@ struct MomentumForcingDev {
     ForcingDev f[3];
     int stokes;
 };
+// The momentum finishing-pass kernels (physics.hip, general.hip) are templates on a trailing pack X of descriptor arguments: {} (no extra
+// term: the kernels and their arguments as they always were), {StokesDev}, or {StokesDev, MomentumForcingDev} -- ONE variant for forcing
+// with and without a Stokes drift (fd.stokes = 0: `sd` is empty and its terms are skipped).
+// In a kernel: the I-th descriptor of the pack, or NULL in an instantiation that does not take it.
+template <class T, int I, class... X>
+__device__ __forceinline__ const T *extra_arg(const X &...x)
+{
+    if constexpr (I < (int)sizeof...(X))
+        return &std::get<I>(std::tie(x...));
+    else
+        return nullptr;
+}
+// In a launcher: launch(), launch(sd) or launch(sd, fd), whichever the model asks for.
+template <class L>
+inline int with_extra_descriptors(const StokesDev *stokes, const MomentumForcingDev *forcing, L launch)
+{
+    if (forcing) {
+        MomentumForcingDev fd = *forcing;
+        fd.stokes = stokes != nullptr;
+        return launch(stokes ? *stokes : StokesDev{}, fd);
+    }
+    if (stokes) return launch(*stokes);
+    return launch();
+}
 // mask / target of a Relaxation term at a cell: ix, iy, iz = its indices along the parent array (i - 1 + Hx ...), o its parent offset
 __device__ __forceinline__ double forcing_profile(int dim, const double *p, double number, int ix, int iy, int iz, long long o)
 {

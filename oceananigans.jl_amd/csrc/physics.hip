@@ -8,6 +8,8 @@
 //                                              src/Models/NonhydrostaticModels/update_hydrostatic_pressure.jl:12-53,
 //                                              BuoyancyFormulations/{buoyancy_tracer.jl:12, linear_equation_of_state.jl:58-66, g_dot_b.jl:1-8}
 //   * flux boundary conditions (top / bottom)  src/BoundaryConditions/apply_flux_bcs.jl:38-160
+//   * stokes_drift = UniformStokesDrift        src/StokesDrifts.jl:36-180   } compiled into the finishing-pass kernels that take their
+//   * forcing = (u = ..., v = ..., w = ...)    src/Forcings                 } descriptors: templates on a trailing argument pack
 //
 // The extra momentum terms are ADDED to a G that already holds the advective tendency, in the reference's order
 //   G = ((((-div_𝐯u - 0) + x_dot_g_b) - x_f_cross_U) - ∂x pHY′) - ∂ⱼτ₁ⱼ      (nonhydrostatic_tendency_kernel_functions.jl:66-75)
@@ -413,45 +415,228 @@ __device__ __forceinline__ void momentum_extra_cell(const GridDev &g, const Term
     if (mf.sc.on && TZ == OCN_BOUNDED && k == g.Nz) mf.sub[2].out[o_w + w3] = Wf(0, 0, 1);  // top wall face k = Nz+1
 }
 
-// the finishing-pass kernels, without and with the Stokes-drift terms (see momentum_extra_kernels.inc)
-#define OCN_EXTRA_KERNEL momentum_extra_kernel
-#define OCN_EXTRA_TILED momentum_extra_tiled
-#define OCN_EXTRA_STK false
-#define OCN_EXTRA_FRC false
-#define OCN_EXTRA_SD_PARAM
-#define OCN_EXTRA_SD nullptr
-#define OCN_EXTRA_FD nullptr
-#include "momentum_extra_kernels.inc"
-#undef OCN_EXTRA_KERNEL
-#undef OCN_EXTRA_TILED
-#undef OCN_EXTRA_STK
-#undef OCN_EXTRA_SD_PARAM
-#undef OCN_EXTRA_SD
-#define OCN_EXTRA_KERNEL momentum_extra_kernel_stokes
-#define OCN_EXTRA_TILED momentum_extra_tiled_stokes
-#define OCN_EXTRA_STK true
-#define OCN_EXTRA_SD_PARAM , ocn::StokesDev sd
-#define OCN_EXTRA_SD &sd
-#include "momentum_extra_kernels.inc"
-#undef OCN_EXTRA_KERNEL
-#undef OCN_EXTRA_TILED
-#undef OCN_EXTRA_SD_PARAM
-#undef OCN_EXTRA_FRC
-#undef OCN_EXTRA_FD
-// ... and the ONE variant with the forcing terms: it takes both descriptors, either of which may be empty (fd.stokes = 0: no Stokes terms)
-#define OCN_EXTRA_KERNEL momentum_extra_kernel_forced
-#define OCN_EXTRA_TILED momentum_extra_tiled_forced
-#define OCN_EXTRA_FRC true
-#define OCN_EXTRA_SD_PARAM , ocn::StokesDev sd, ocn::MomentumForcingDev fd
-#define OCN_EXTRA_FD &fd
-#include "momentum_extra_kernels.inc"
-#undef OCN_EXTRA_KERNEL
-#undef OCN_EXTRA_TILED
-#undef OCN_EXTRA_STK
-#undef OCN_EXTRA_FRC
-#undef OCN_EXTRA_SD_PARAM
-#undef OCN_EXTRA_SD
-#undef OCN_EXTRA_FD
+// The finishing-pass kernels, direct and LDS-tiled.  Their trailing pack X selects the variant (ocn_common.h: extra_arg): nothing, the
+// Stokes-drift terms of momentum_extra_cell (ocn::StokesDev), or those and the forcing terms (ocn::StokesDev, ocn::MomentumForcingDev).
+// `mf`: the flux boundary contributions of u, v (apply_flux_bcs.jl:107-160) and the NEXT stage's rk3 substep of u, v, w into a
+// second storage, folded into this last pass over G (same operations as apply_flux_bcs_kernel / stepper_kernel).
+template <int TZ, class... X>
+__global__ __launch_bounds__(256) void momentum_extra_kernel(GridDev g, TermsDev t, const double *__restrict__ u,
+                                                             const double *__restrict__ v, const double *__restrict__ w,
+                                                             double *__restrict__ Gu, double *__restrict__ Gv,
+                                                             double *__restrict__ Gw, PRange r, ocn::MomentumFinal mf, X... x)
+{
+    constexpr bool STK = sizeof...(X) >= 1, FRC = sizeof...(X) == 2;
+    const int i = r.i0 + blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = r.j0 + blockIdx.y * blockDim.y + threadIdx.y;
+    const int k = r.k0 + blockIdx.z;
+    if (i > r.i1 || j > r.j1) return;
+    constexpr bool ZF = (TZ == OCN_FLAT);
+    const Metrics M = make_metrics(g);
+    const Lay L = ocn::make_lay(g, OCN_LOC_CCC);
+    const long long s2 = L.s2, s3 = ZF ? 0 : L.s3, o = ocn::at(L, i, j, k);
+    const double *pu = u + o, *pv = v + o, *pw = w + o, *pn = t.nu_e ? t.nu_e + o : nullptr;
+    const ExtraLoads ld = momentum_extra_loads<TZ>(t, mf, r, k, o, s2, s3, Gu, Gv, Gw);
+    momentum_extra_cell<TZ, false, STK, FRC>(
+        g, t, M, i, j, k, o, s2, s3, pn != nullptr, [&](int a, int b, int c) { return pu[a + b * s2 + c * s3]; },
+        [&](int a, int b, int c) { return pv[a + b * s2 + c * s3]; }, [&](int a, int b, int c) { return pw[a + b * s2 + c * s3]; },
+        [&](int a, int b, int c) { return pn[a + b * s2 + c * s3]; }, Gu, Gv, Gw, r, mf, ld, 0.0, 0.0, nullptr, nullptr, nullptr,
+        ocn::extra_arg<ocn::StokesDev, 0>(x...), ocn::extra_arg<ocn::MomentumForcingDev, 1>(x...));
+}
+
+// Tiled variant of the finishing pass: a workgroup owns a 32 x 8 patch of columns and marches KZ planes upward; planes
+// k-1, k, k+1 of u, v, w (and νₑ) live in a 3-slot LDS ring with a one-cell rim, so every value enters the workgroup once per
+// plane (1.33x with the rim) instead of once per stencil tap (~60 taps per cell hit L2 in the direct kernel: the 3 planes x
+// 4 fields of a workgroup do not fit the 32 KB L1).  pHY′, G, G⁻ are touched once per cell and stay in global memory.
+// GL ("general layouts"): the interior box of a grid with a Bounded x / y (general.hip) -- u, v, w (and their G, G⁻, stepped copies) have
+// their own parent layouts; every cell of the box is a full stencil away from the walls, where the expressions are the Periodic ones.
+// With the Stokes-drift terms of momentum_extra_cell: w at k, k + 1 and u, v at k - 1, k are in the LDS ring already.
+template <int TZ, bool SH, bool GL, class... X>
+__global__ __launch_bounds__(256, SH ? 3 : 4) void momentum_extra_tiled(GridDev g, TermsDev t, const double *__restrict__ u,
+                                                            const double *__restrict__ v, const double *__restrict__ w,
+                                                            double *__restrict__ Gu, double *__restrict__ Gv,
+                                                            double *__restrict__ Gw, PRange r, ocn::MomentumFinal mf, int KZ, X... x)
+{
+    constexpr bool STK = sizeof...(X) >= 1, FRC = sizeof...(X) == 2;
+    constexpr int TX = 32, TY = 8, SX = TX + 2, SY = TY + 2, PL = SX * SY;
+    __shared__ double Lu[3][PL], Lv[3][PL], Lw[3][PL], Ln[3][PL];
+    // Stresses shared between the cells that read them (closure != 0): every cell evaluates the six stresses it OWNS -- T11, T22, T33 at
+    // its centre, T12 at its south-west edge, T13, T23 at its lower west / south edges -- once per plane instead of the 18 values its three
+    // components read (each stress is read by 2 to 4 cells); T33 stays in registers (same column), T13 / T23 of plane k + 1 become plane k
+    // of the next iteration.  Same expressions, same operands: bit-identical to the unshared evaluation.
+    constexpr int SPL = SH ? PL : 1;
+    __shared__ double S11[SPL], S22[SPL], S12[SPL], S13[2][SPL], S23[2][SPL];
+    const int tid = threadIdx.x, tx = tid % TX, ty = tid / TX;
+    int bx, by, bz;
+    xcd_block_coords(mf.xcd, bx, by, bz);
+    const int i0 = r.i0 + bx * TX, j0 = r.j0 + by * TY;
+    const int kb = r.k0 + bz * KZ, ke = min(kb + KZ - 1, r.k1);
+    const int i = i0 + tx, j = j0 + ty;
+    const bool active = (i <= r.i1) && (j <= r.j1);
+    const Metrics M = make_metrics(g);
+    const Lay L = ocn::make_lay(g, OCN_LOC_CCC);
+    const long long s2 = L.s2, s3 = L.s3;
+    const Lay LFu = GL ? ocn::make_lay(g, OCN_LOC_FCC) : L, LFv = GL ? ocn::make_lay(g, OCN_LOC_CFC) : L, LFw = GL ? ocn::make_lay(g, OCN_LOC_CCF) : L;
+    const bool has_nu = t.nu_e != nullptr;
+    // Staging of plane kk (tile + rim, indices clamped to the first halo cell) into ring slot kk % 3 is split in two so that the
+    // global loads of plane k+2 are in flight while plane k is being computed: fetch() -> registers, commit() -> LDS.
+    constexpr int NS = (PL + TX * TY - 1) / (TX * TY);  // cells staged per thread (2)
+    long long soff[NS], soffu[GL ? NS : 1], soffv[GL ? NS : 1], soffw[GL ? NS : 1];
+    bool son[NS];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) {
+        const int idx = tid + q * TX * TY;
+        son[q] = idx < PL;
+        const int li = son[q] ? idx % SX : 0, lj = son[q] ? idx / SX : 0;
+        const int si = min(i0 - 1 + li, g.Nx + 1), sj = min(j0 - 1 + lj, g.Ny + 1);
+        soff[q] = ocn::at(L, si, sj, 0);  // plane 0: add kk * s3
+        if (GL) {
+            soffu[q] = ocn::at(LFu, si, sj, 0);
+            soffv[q] = ocn::at(LFv, si, sj, 0);
+            soffw[q] = ocn::at(LFw, si, sj, 0);
+        }
+    }
+    double fu[NS], fv[NS], fw[NS], fn[NS];
+    auto fetch = [&](int kk) {
+#pragma unroll
+        for (int q = 0; q < NS; ++q) {
+            const long long oo = soff[q] + (long long)kk * s3;
+            fu[q] = son[q] ? u[GL ? soffu[q] + (long long)kk * LFu.s3 : oo] : 0.0;
+            fv[q] = son[q] ? v[GL ? soffv[q] + (long long)kk * LFv.s3 : oo] : 0.0;
+            fw[q] = son[q] ? w[GL ? soffw[q] + (long long)kk * LFw.s3 : oo] : 0.0;
+            fn[q] = (son[q] && has_nu) ? t.nu_e[oo] : 0.0;
+        }
+    };
+    auto commit = [&](int kk) {
+        const int slot = kk % 3;
+#pragma unroll
+        for (int q = 0; q < NS; ++q) {
+            if (!son[q]) continue;
+            const int idx = tid + q * TX * TY;
+            Lu[slot][idx] = fu[q];
+            Lv[slot][idx] = fv[q];
+            Lw[slot][idx] = fw[q];
+            if (has_nu) Ln[slot][idx] = fn[q];
+        }
+    };
+    fetch(kb - 1);
+    commit(kb - 1);
+    fetch(kb);
+    commit(kb);
+    fetch(kb + 1);
+    const int c0 = (ty + 1) * SX + (tx + 1);
+    // rim positions whose stresses the tile's cells read: one per lane of the first 32 / 32 / 8 / 8 lanes of waves 0 .. 3
+    //   wave 0: south row (T22 of row j0 - 1), wave 1: north row (T12, T23 of row j0 + TY), wave 2: west column (T11 of column i0 - 1),
+    //   wave 3: east column (T12, T13 of column i0 + TX)
+    const int wv = tid >> 6, ln = tid & 63;
+    const int rim = (wv == 0 && ln < TX) ? 1 : (wv == 1 && ln < TX) ? 2 : (wv == 2 && ln < TY) ? 3 : (wv == 3 && ln < TY) ? 4 : 0;
+    const int cr = rim == 1 ? (ln + 1) : rim == 2 ? (TY + 1) * SX + (ln + 1) : rim == 3 ? (ln + 1) * SX : rim == 4 ? (ln + 1) * SX + (TX + 1) : c0;
+    constexpr bool shared = SH;
+    const double dx = M.dx, dy = M.dy, nu = t.nu;
+#if !OCN_STRICT
+    const double rdx = fast_rcp(dx), rdy = fast_rcp(dy);
+#endif
+    double t33_prev = 0.0;
+    for (int k = kb; k <= ke; ++k) {
+        commit(k + 1);
+        __syncthreads();
+        const int ia = active ? i : r.i1, ja = active ? j : r.j1;
+        const long long o = ocn::at(L, ia, ja, k);
+        const FieldOffs fov{GL ? ocn::at(LFu, ia, ja, k) : o, GL ? ocn::at(LFv, ia, ja, k) : o, GL ? ocn::at(LFw, ia, ja, k) : o, GL ? LFw.s3 : s3};
+        const FieldOffs *fo = GL ? &fov : nullptr;
+        ExtraLoads ld{};
+        if (active) ld = momentum_extra_loads<TZ>(t, mf, r, k, o, s2, s3, Gu, Gv, Gw, fo);  // this plane's own values first ...
+        OCN_ISSUE_LOADS_HERE();
+        if (k < ke) fetch(k + 2);  // ... then the staging values of plane k + 2, consumed by the next iteration's commit
+        OCN_ISSUE_LOADS_HERE();
+        const int base = k + 3;  // (k + c) % 3 for c in {-1, 0, 1} without negative operands
+        Stresses sh{};
+        if (shared) {
+            const double dzc = M.dzC(k), dzf = M.dzF(k), dzf1 = M.dzF(k + 1), dzcm = M.dzC(k - 1);
+#if !OCN_STRICT
+            const double rdzc = fast_rcp(dzc), rdzf = fast_rcp(dzf), rdzf1 = fast_rcp(dzf1), rdzcm = fast_rcp(dzcm);
+#endif
+            auto sU = [&](int c, int a, int b, int d) { return Lu[(base + d) % 3][c + a + b * SX]; };
+            auto sV = [&](int c, int a, int b, int d) { return Lv[(base + d) % 3][c + a + b * SX]; };
+            auto sW = [&](int c, int a, int b, int d) { return Lw[(base + d) % 3][c + a + b * SX]; };
+            auto sN = [&](int c, int a, int b, int d) { return Ln[(base + d) % 3][c + a + b * SX]; };
+            auto nuC = [&](int c, int d) { return has_nu ? sN(c, 0, 0, d) : nu; };
+            auto nuFFC = [&](int c) {
+                return has_nu ? 0.5 * (0.5 * (sN(c, -1, -1, 0) + sN(c, 0, -1, 0)) + 0.5 * (sN(c, -1, 0, 0) + sN(c, 0, 0, 0))) : nu;
+            };
+            auto nuFCF = [&](int c, int d) {
+                return has_nu ? 0.5 * (0.5 * (sN(c, -1, 0, d - 1) + sN(c, 0, 0, d - 1)) + 0.5 * (sN(c, -1, 0, d) + sN(c, 0, 0, d))) : nu;
+            };
+            auto nuCFF = [&](int c, int d) {
+                return has_nu ? 0.5 * (0.5 * (sN(c, 0, -1, d - 1) + sN(c, 0, 0, d - 1)) + 0.5 * (sN(c, 0, -1, d) + sN(c, 0, 0, d))) : nu;
+            };
+            // the expressions of momentum_extra_cell, with the centre of evaluation as an argument (d: z-face k + d)
+            auto T11 = [&](int c) { return TAU(nuC(c, 0), DX(sU(c, 1, 0, 0), sU(c, 0, 0, 0))); };
+            auto T22 = [&](int c) { return TAU(nuC(c, 0), DY(sV(c, 0, 1, 0), sV(c, 0, 0, 0))); };
+            auto T12 = [&](int c) { return TAU(nuFFC(c), 0.5 * (DY(sU(c, 0, 0, 0), sU(c, 0, -1, 0)) + DX(sV(c, 0, 0, 0), sV(c, -1, 0, 0)))); };
+            auto T13 = [&](int c, int d) {
+                const double dzu = d ? OCN_DIV(sU(c, 0, 0, 1) - sU(c, 0, 0, 0), dzf1, rdzf1) : OCN_DIV(sU(c, 0, 0, 0) - sU(c, 0, 0, -1), dzf, rdzf);
+                return TAU(nuFCF(c, d), 0.5 * (dzu + DX(sW(c, 0, 0, d), sW(c, -1, 0, d))));
+            };
+            auto T23 = [&](int c, int d) {
+                const double dzv = d ? OCN_DIV(sV(c, 0, 0, 1) - sV(c, 0, 0, 0), dzf1, rdzf1) : OCN_DIV(sV(c, 0, 0, 0) - sV(c, 0, 0, -1), dzf, rdzf);
+                return TAU(nuCFF(c, d), 0.5 * (dzv + DY(sW(c, 0, 0, d), sW(c, 0, -1, d))));
+            };
+            const int cur = k & 1, nxt = cur ^ 1;
+            const bool first = (k == kb);
+            // own position (every thread, active or not: the neighbours of the last active column / row read these)
+            const double o11 = T11(c0), o22 = T22(c0), o12 = T12(c0), o13n = T13(c0, 1), o23n = T23(c0, 1);
+            double o13c, o23c;
+            if (first) {
+                o13c = T13(c0, 0);
+                o23c = T23(c0, 0);
+                S13[cur][c0] = o13c;
+                S23[cur][c0] = o23c;
+                t33_prev = TAU(nuC(c0, -1), OCN_DIV(sW(c0, 0, 0, 0) - sW(c0, 0, 0, -1), dzcm, rdzcm));
+            } else {
+                o13c = S13[cur][c0];  // (written by this thread in the previous iteration)
+                o23c = S23[cur][c0];
+            }
+            S11[c0] = o11; S22[c0] = o22; S12[c0] = o12; S13[nxt][c0] = o13n; S23[nxt][c0] = o23n;
+            const double o33 = TAU(nuC(c0, 0), OCN_DIV(sW(c0, 0, 0, 1) - sW(c0, 0, 0, 0), dzc, rdzc));
+            // rim positions
+            if (rim == 1) {
+                S22[cr] = T22(cr);
+            } else if (rim == 2) {
+                S12[cr] = T12(cr);
+                S23[nxt][cr] = T23(cr, 1);
+                if (first) S23[cur][cr] = T23(cr, 0);
+            } else if (rim == 3) {
+                S11[cr] = T11(cr);
+            } else if (rim == 4) {
+                S12[cr] = T12(cr);
+                S13[nxt][cr] = T13(cr, 1);
+                if (first) S13[cur][cr] = T13(cr, 0);
+            }
+            __syncthreads();
+            sh.t11e = o11; sh.t11w = S11[c0 - 1];
+            sh.t12c = o12; sh.t12n = S12[c0 + SX]; sh.t12e = S12[c0 + 1];
+            sh.t13t = o13n; sh.t13c = o13c; sh.t13e = S13[cur][c0 + 1];
+            sh.t22n = o22; sh.t22s = S22[c0 - SX];
+            sh.t23t = o23n; sh.t23c = o23c; sh.t23n = S23[cur][c0 + SX];
+            sh.t33t = o33; sh.t33b = t33_prev;
+            t33_prev = o33;
+        }
+        if (active) {
+            momentum_extra_cell<TZ, false, STK, FRC>(
+                g, t, M, i, j, k, o, s2, s3, has_nu, [&](int a, int b, int c) { return Lu[(base + c) % 3][c0 + a + b * SX]; },
+                [&](int a, int b, int c) { return Lv[(base + c) % 3][c0 + a + b * SX]; },
+                [&](int a, int b, int c) { return Lw[(base + c) % 3][c0 + a + b * SX]; },
+                [&](int a, int b, int c) { return Ln[(base + c) % 3][c0 + a + b * SX]; }, Gu, Gv, Gw, r, mf, ld, 0.0, 0.0, nullptr,
+                SH ? &sh : nullptr, fo, ocn::extra_arg<ocn::StokesDev, 0>(x...), ocn::extra_arg<ocn::MomentumForcingDev, 1>(x...));
+        }
+        // Unshared: everyone must be done with slot (k - 1) % 3 before the next iteration's commit overwrites it.  Shared: nothing reads plane
+        // k - 1 after the first iteration's stress phase (T13, T23 of plane k and T33 of k - 1 are carried), which the barrier above already
+        // closed; the plane-k stress arrays are next written after the NEXT iteration's first barrier, which every wave reaches only after its
+        // cell phase -- so two barriers per plane suffice.
+        // With the Stokes-drift terms the cell phase reads u, v of plane k - 1 again (Gw), so the shared variant keeps this barrier too.
+        if (!SH || STK) __syncthreads();
+    }
+}
 
 // ---------------------------------------------------------------------------------------------------
 // HydrostaticFreeSurfaceModel: the whole horizontal-momentum part of one QuasiAdamsBashforth2 step in ONE pass over the columns.
@@ -722,94 +907,86 @@ int launch_tracer_centered2(const ocn_grid *grid, const double *u, const double 
     return OCN_SUCCESS;
 }
 
-int launch_momentum_extra(const ocn_grid *grid, const TermsDev &t, const double *u, const double *v, const double *w,
-                          double *Gu, double *Gv, double *Gw, const int32_t *range, hipStream_t stream,
-                          const ocn::MomentumFinal *fin, const ocn::StokesDev *stokes, const ocn::MomentumForcingDev *forcing)
+// what the two finishing-pass launchers share: the MomentumFinal the kernels get, whether the stresses go through LDS, the tile geometry
+static ocn::MomentumFinal extra_final(const ocn::MomentumFinal *fin)
 {
     ocn::MomentumFinal mf{};
     if (fin) mf = *fin;
     mf.xcd = xcd_remap_on();
+    return mf;
+}
+static bool share_stresses(const TermsDev &t)
+{
     static const bool share_env = !(getenv("OCN_SHARE_STRESSES") && getenv("OCN_SHARE_STRESSES")[0] == '0');
-    const bool share = share_env && t.closure != 0;  // every stress evaluated once per face / centre and shared through LDS
+    return share_env && t.closure != 0;  // every stress evaluated once per face / centre and shared through LDS
+}
+// Launch geometry of momentum_extra_tiled over r: returns KZ, the planes a workgroup marches, and the grid of 32 x 8 tiles; 0 when the
+// range is too small for the tiles (or z is Flat, or has no halo): the tiled kernel does not apply.
+static int extra_tiles(const ocn_grid *grid, const PRange &r, dim3 &nbt)
+{
+    const int wx = r.i1 - r.i0 + 1, wy = r.j1 - r.j0 + 1, wz = r.k1 - r.k0 + 1;
+    if (grid->tz == OCN_FLAT || wx < 16 || wy < 8 || wz < 4 || grid->Hz < 1) return 0;
+    const int tiles = ((wx + 31) / 32) * ((wy + 7) / 8);
+    int KZ = wz;  // z-chunk: enough workgroups to fill the chip, long enough to amortise the two-plane prologue
+    while (KZ > 16 && tiles * ((wz + KZ - 1) / KZ) < 4096) KZ = (KZ + 1) / 2;
+    nbt = dim3((wx + 31) / 32, (wy + 7) / 8, (wz + KZ - 1) / KZ);
+    return KZ;
+}
+
+// the TZ x SH choice of the tiled kernel, for one layout (GL) and one set of descriptors (x...)
+template <bool GL, class... X>
+static int launch_extra_tiled(const ocn_grid *grid, bool share, dim3 nbt, hipStream_t stream, const GridDev &g, const TermsDev &t, const double *u,
+                              const double *v, const double *w, double *Gu, double *Gv, double *Gw, const PRange &r,
+                              const ocn::MomentumFinal &mf, int KZ, X... x)
+{
+    auto *kernel = grid->tz == OCN_PERIODIC
+                       ? (share ? momentum_extra_tiled<OCN_PERIODIC, true, GL, X...> : momentum_extra_tiled<OCN_PERIODIC, false, GL, X...>)
+                       : (share ? momentum_extra_tiled<OCN_BOUNDED, true, GL, X...> : momentum_extra_tiled<OCN_BOUNDED, false, GL, X...>);
+    hipLaunchKernelGGL(kernel, nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, x...);
+    OCN_CHECK_HIP(hipGetLastError());
+    return OCN_SUCCESS;
+}
+
+// ... and the TZ choice of the direct kernel
+template <class... X>
+static int launch_extra_direct(const ocn_grid *grid, hipStream_t stream, const GridDev &g, const TermsDev &t, const double *u, const double *v,
+                               const double *w, double *Gu, double *Gv, double *Gw, const PRange &r, const ocn::MomentumFinal &mf, X... x)
+{
+    decltype(&momentum_extra_kernel<OCN_PERIODIC, X...>) kernel = nullptr;
+    switch (grid->tz) {
+        case OCN_PERIODIC: kernel = momentum_extra_kernel<OCN_PERIODIC, X...>; break;
+        case OCN_BOUNDED: kernel = momentum_extra_kernel<OCN_BOUNDED, X...>; break;
+        case OCN_FLAT:  // (not compiled for a Stokes drift alone: the C ABI refuses it on a Flat z)
+            if constexpr (sizeof...(X) != 1) kernel = momentum_extra_kernel<OCN_FLAT, X...>;
+            break;
+    }
+    if (!kernel) {
+        ocn::set_error("unsupported z topology %d", grid->tz);
+        return OCN_ERR_UNSUPPORTED;
+    }
+    const dim3 block = ocn::range_block(r.i1 - r.i0 + 1), nb = ocn::range_grid(block, r.i1 - r.i0 + 1, r.j1 - r.j0 + 1, r.k1 - r.k0 + 1);
+    hipLaunchKernelGGL(kernel, nb, block, 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, x...);
+    OCN_CHECK_HIP(hipGetLastError());
+    return OCN_SUCCESS;
+}
+
+int launch_momentum_extra(const ocn_grid *grid, const TermsDev &t, const double *u, const double *v, const double *w,
+                          double *Gu, double *Gv, double *Gw, const int32_t *range, hipStream_t stream,
+                          const ocn::MomentumFinal *fin, const ocn::StokesDev *stokes, const ocn::MomentumForcingDev *forcing)
+{
     PRange r;
     int st = make_prange(grid, range, r);
     if (st != OCN_SUCCESS) return st;
     if (r.i1 < r.i0 || r.j1 < r.j0 || r.k1 < r.k0) return OCN_SUCCESS;
-    GridDev g = ocn::to_dev(*grid);
-    const int wx = r.i1 - r.i0 + 1, wy = r.j1 - r.j0 + 1, wz = r.k1 - r.k0 + 1;
+    const ocn::MomentumFinal mf = extra_final(fin);
+    const GridDev g = ocn::to_dev(*grid);
     static const int force_direct = (getenv("OCN_EXTRA_KERNEL") && !strcmp(getenv("OCN_EXTRA_KERNEL"), "direct"));
-    if (!force_direct && grid->tz != OCN_FLAT && wx >= 16 && wy >= 8 && wz >= 4 && grid->Hz >= 1) {
-        const int tiles = ((wx + 31) / 32) * ((wy + 7) / 8);
-        int KZ = wz;  // z-chunk: enough workgroups to fill the chip, long enough to amortise the two-plane prologue
-        while (KZ > 16 && tiles * ((wz + KZ - 1) / KZ) < 4096) KZ = (KZ + 1) / 2;
-        dim3 nbt((wx + 31) / 32, (wy + 7) / 8, (wz + KZ - 1) / KZ);
-        if (forcing) {  // the variant with the forcing terms (and the Stokes terms when fd.stokes says so)
-            const ocn::StokesDev sd = stokes ? *stokes : ocn::StokesDev{};
-            ocn::MomentumForcingDev fd = *forcing;
-            fd.stokes = stokes != nullptr;
-            if (grid->tz == OCN_PERIODIC) {
-                if (share)
-                    hipLaunchKernelGGL((momentum_extra_tiled_forced<OCN_PERIODIC, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd, fd);
-                else
-                    hipLaunchKernelGGL((momentum_extra_tiled_forced<OCN_PERIODIC, false>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd, fd);
-            } else {
-                if (share)
-                    hipLaunchKernelGGL((momentum_extra_tiled_forced<OCN_BOUNDED, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd, fd);
-                else
-                    hipLaunchKernelGGL((momentum_extra_tiled_forced<OCN_BOUNDED, false>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd, fd);
-            }
-            OCN_CHECK_HIP(hipGetLastError());
-            return OCN_SUCCESS;
-        }
-        if (stokes) {  // the same four variants, compiled with the Stokes-drift terms
-            const ocn::StokesDev sd = *stokes;
-            if (grid->tz == OCN_PERIODIC) {
-                if (share)
-                    hipLaunchKernelGGL((momentum_extra_tiled_stokes<OCN_PERIODIC, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd);
-                else
-                    hipLaunchKernelGGL((momentum_extra_tiled_stokes<OCN_PERIODIC, false>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd);
-            } else {
-                if (share)
-                    hipLaunchKernelGGL((momentum_extra_tiled_stokes<OCN_BOUNDED, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd);
-                else
-                    hipLaunchKernelGGL((momentum_extra_tiled_stokes<OCN_BOUNDED, false>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd);
-            }
-            OCN_CHECK_HIP(hipGetLastError());
-            return OCN_SUCCESS;
-        }
-        if (grid->tz == OCN_PERIODIC) {
-            if (share)
-                hipLaunchKernelGGL((momentum_extra_tiled<OCN_PERIODIC, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ);
-            else
-                hipLaunchKernelGGL((momentum_extra_tiled<OCN_PERIODIC, false>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ);
-        } else {
-            if (share)
-                hipLaunchKernelGGL((momentum_extra_tiled<OCN_BOUNDED, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ);
-            else
-                hipLaunchKernelGGL((momentum_extra_tiled<OCN_BOUNDED, false>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ);
-        }
-        OCN_CHECK_HIP(hipGetLastError());
-        return OCN_SUCCESS;
-    }
-    const dim3 block = ocn::range_block(r.i1 - r.i0 + 1), nb = ocn::range_grid(block, r.i1 - r.i0 + 1, r.j1 - r.j0 + 1, r.k1 - r.k0 + 1);
-    if (forcing) {
-        const ocn::StokesDev sd = stokes ? *stokes : ocn::StokesDev{};
-        ocn::MomentumForcingDev fd = *forcing;
-        fd.stokes = stokes != nullptr;
-        OCN_LAUNCH_TZ(momentum_extra_kernel_forced, g, t, u, v, w, Gu, Gv, Gw, r, mf, sd, fd);
-        return OCN_SUCCESS;
-    }
-    if (stokes) {  // (the C ABI refuses a Flat z with Stokes drift)
-        const ocn::StokesDev sd = *stokes;
-        if (grid->tz == OCN_PERIODIC)
-            hipLaunchKernelGGL(momentum_extra_kernel_stokes<OCN_PERIODIC>, nb, block, 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, sd);
-        else
-            hipLaunchKernelGGL(momentum_extra_kernel_stokes<OCN_BOUNDED>, nb, block, 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, sd);
-        OCN_CHECK_HIP(hipGetLastError());
-        return OCN_SUCCESS;
-    }
-    OCN_LAUNCH_TZ(momentum_extra_kernel, g, t, u, v, w, Gu, Gv, Gw, r, mf);
-    return OCN_SUCCESS;
+    dim3 nbt;
+    const int KZ = force_direct ? 0 : extra_tiles(grid, r, nbt);
+    return ocn::with_extra_descriptors(stokes, forcing, [&](auto... x) {
+        if (KZ) return launch_extra_tiled<false>(grid, share_stresses(t), nbt, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, x...);
+        return launch_extra_direct(grid, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, x...);
+    });
 }
 
 // The finishing pass on the INTERIOR BOX {i0, i1, j0, j1} of a grid with walls in x / y (general.hip: every cell at least a full stencil
@@ -820,71 +997,19 @@ int launch_momentum_extra_box(const ocn_grid *grid, const TermsDev &t, const dou
                               const ocn::StokesDev *stokes, const ocn::MomentumForcingDev *forcing)
 {
     *launched = 0;
-    ocn::MomentumFinal mf{};
-    if (fin) mf = *fin;
-    mf.xcd = xcd_remap_on();
-    static const bool share_env = !(getenv("OCN_SHARE_STRESSES") && getenv("OCN_SHARE_STRESSES")[0] == '0');
-    const bool share = share_env && t.closure != 0;
     PRange r;
     r.i0 = box[0]; r.i1 = box[1]; r.j0 = box[2]; r.j1 = box[3]; r.k0 = 1; r.k1 = grid->Nz;
     r.ow = (!ranged && grid->tz == OCN_BOUNDED && grid->Nz > 1) ? 2 : 1;  // (KernelParameters: periphery not excluded, as make_prange)
-    const int wx = r.i1 - r.i0 + 1, wy = r.j1 - r.j0 + 1, wz = grid->Nz;
-    if (grid->tz == OCN_FLAT || wx < 16 || wy < 8 || wz < 4 || grid->Hz < 1) return OCN_SUCCESS;
-    GridDev g = ocn::to_dev(*grid);
-    const int tiles = ((wx + 31) / 32) * ((wy + 7) / 8);
-    int KZ = wz;
-    while (KZ > 16 && tiles * ((wz + KZ - 1) / KZ) < 4096) KZ = (KZ + 1) / 2;
-    dim3 nbt((wx + 31) / 32, (wy + 7) / 8, (wz + KZ - 1) / KZ);
-    if (forcing) {  // the variant with the forcing terms (and the Stokes terms when fd.stokes says so)
-        const ocn::StokesDev sd = stokes ? *stokes : ocn::StokesDev{};
-        ocn::MomentumForcingDev fd = *forcing;
-        fd.stokes = stokes != nullptr;
-        if (grid->tz == OCN_PERIODIC) {
-            if (share)
-                hipLaunchKernelGGL((momentum_extra_tiled_forced<OCN_PERIODIC, true, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd, fd);
-            else
-                hipLaunchKernelGGL((momentum_extra_tiled_forced<OCN_PERIODIC, false, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd, fd);
-        } else {
-            if (share)
-                hipLaunchKernelGGL((momentum_extra_tiled_forced<OCN_BOUNDED, true, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd, fd);
-            else
-                hipLaunchKernelGGL((momentum_extra_tiled_forced<OCN_BOUNDED, false, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd, fd);
-        }
-        OCN_CHECK_HIP(hipGetLastError());
-        *launched = 1;
-        return OCN_SUCCESS;
-    }
-    if (stokes) {
-        const ocn::StokesDev sd = *stokes;
-        if (grid->tz == OCN_PERIODIC) {
-            if (share)
-                hipLaunchKernelGGL((momentum_extra_tiled_stokes<OCN_PERIODIC, true, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd);
-            else
-                hipLaunchKernelGGL((momentum_extra_tiled_stokes<OCN_PERIODIC, false, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd);
-        } else {
-            if (share)
-                hipLaunchKernelGGL((momentum_extra_tiled_stokes<OCN_BOUNDED, true, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd);
-            else
-                hipLaunchKernelGGL((momentum_extra_tiled_stokes<OCN_BOUNDED, false, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, sd);
-        }
-        OCN_CHECK_HIP(hipGetLastError());
-        *launched = 1;
-        return OCN_SUCCESS;
-    }
-    if (grid->tz == OCN_PERIODIC) {
-        if (share)
-            hipLaunchKernelGGL((momentum_extra_tiled<OCN_PERIODIC, true, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ);
-        else
-            hipLaunchKernelGGL((momentum_extra_tiled<OCN_PERIODIC, false, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ);
-    } else {
-        if (share)
-            hipLaunchKernelGGL((momentum_extra_tiled<OCN_BOUNDED, true, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ);
-        else
-            hipLaunchKernelGGL((momentum_extra_tiled<OCN_BOUNDED, false, true>), nbt, dim3(256), 0, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ);
-    }
-    OCN_CHECK_HIP(hipGetLastError());
-    *launched = 1;
-    return OCN_SUCCESS;
+    dim3 nbt;
+    const int KZ = extra_tiles(grid, r, nbt);
+    if (!KZ) return OCN_SUCCESS;
+    const ocn::MomentumFinal mf = extra_final(fin);
+    const GridDev g = ocn::to_dev(*grid);
+    const int st = ocn::with_extra_descriptors(stokes, forcing, [&](auto... x) {
+        return launch_extra_tiled<true>(grid, share_stresses(t), nbt, stream, g, t, u, v, w, Gu, Gv, Gw, r, mf, KZ, x...);
+    });
+    *launched = st == OCN_SUCCESS;
+    return st;
 }
 
 int launch_hydrostatic_momentum(const ocn_grid *grid, const TermsDev &t, const double *u, const double *v, const double *w, double *Gu,

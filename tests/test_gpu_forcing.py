@@ -85,7 +85,10 @@ def _forcing_set(ocn, pg, topo, rng):
 CASES = [((37, 21, 11), "PPP", (-4.0, 0.0)),         # tiled path; not multiples of the 32 x 8 patches
          ((40, 19, 10), "PPB", "stretched"),         # tiled path, stretched z
          ((41, 29, 9), "BBB", "stretched"),          # general path: tiled interior box + wall frames
-         ((24, 1, 10), "PFB", (-2.0, 0.0))]          # general path, per-cell kernel on a slice
+         ((24, 1, 10), "PFB", (-2.0, 0.0)),          # general path, per-cell kernel on a slice
+         ((40, 22, 6), "PBP", (-4.0, 0.0)),          # interior box 40 x 16 (a partial tile in x, two in y) with a Periodic z
+         ((13, 19, 5), "PPP", (-4.0, 0.0)),          # narrower than 16: the direct kernel, Periodic z
+         ((13, 19, 5), "PPB", "stretched")]          # ... and Bounded z
 
 
 def _setup(ocn, size, topo, z, others, mode, rng):

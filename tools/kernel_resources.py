@@ -24,9 +24,9 @@ def parse(path):
             cur["done"] = True
             continue
         if cur.get("done"):
-            m = re.match(r"^; (NumSgprs|NumVgprs|ScratchSize|Occupancy|LDSByteSize): (\d+)", line)
+            m = re.match(r"^; ((?:Total)?NumSgprs|NumVgprs|ScratchSize|Occupancy|LDSByteSize): (\d+)", line)
             if m:
-                cur["meta"][m.group(1)] = int(m.group(2))
+                cur["meta"][m.group(1).replace("Total", "")] = int(m.group(2))
             if line.startswith("; Occupancy") or line.startswith("\t.text") or line.startswith("\t.section"):
                 if "Occupancy" in cur["meta"]:
                     kernels.append(cur)
