@@ -2,7 +2,9 @@
 """The reference's examples/ocean_wind_mixing_and_convection.jl (:1-170) on the MI355X backend: same grid, physics, boundary
 conditions, initial condition, time-step wizard and progress message; plotting / JLD2 output left out.
 
-    python examples/ocean_wind_mixing_and_convection.py [--advection UpwindBiased] [--size 32 32 24] [--stop-minutes 40]
+    python examples/ocean_wind_mixing_and_convection.py [--advection UpwindBiased] [--size 32 32 24] [--stop-minutes 40] [--closure amd]
+
+--closure smagorinsky: SmagorinskyLilly() in AnisotropicMinimumDissipation's place, the alternative the reference's example names (:157).
 
 The example uses UpwindBiased(order=5) (the default here); BASELINE.json's config 4 swaps in WENO().
 """
@@ -22,6 +24,7 @@ ap.add_argument("--size", type=int, nargs=3, default=(32, 32, 24))
 ap.add_argument("--advection", choices=("UpwindBiased", "WENO", "Centered"), default="UpwindBiased")
 ap.add_argument("--stop-minutes", type=float, default=40.0)
 ap.add_argument("--math", choices=("fast", "strict"), default="fast")
+ap.add_argument("--closure", choices=("amd", "smagorinsky"), default="amd")
 a = ap.parse_args()
 ocn.set_math_mode(ocn.MATH_FAST if a.math == "fast" else ocn.MATH_STRICT)
 
@@ -49,7 +52,7 @@ evaporation_rate = 1e-3 / hour                  # m s⁻¹;  Jˢ(x, y, t, S, rat
 S_bcs = ocn.FieldBoundaryConditions(top=ocn.FluxBoundaryCondition(0.0, coeff=-evaporation_rate))
 
 model = ocn.NonhydrostaticModel(grid, buoyancy=buoyancy, advection={"UpwindBiased": ocn.UpwindBiased(order=5), "WENO": ocn.WENO(), "Centered": ocn.Centered()}[a.advection],
-                                tracers=("T", "S"), coriolis=ocn.FPlane(f=1e-4), closure=ocn.AnisotropicMinimumDissipation(),
+                                tracers=("T", "S"), coriolis=ocn.FPlane(f=1e-4), closure=ocn.SmagorinskyLilly() if a.closure == "smagorinsky" else ocn.AnisotropicMinimumDissipation(),
                                 boundary_conditions={"u": u_bcs, "T": T_bcs, "S": S_bcs})
 
 rng = np.random.default_rng(0)

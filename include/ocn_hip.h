@@ -617,6 +617,32 @@ int ocn_model_driver_set_stokes_drift(ocn_model_driver_t driver, const ocn_stoke
  * a slab-x rank; time_dependent != 0 (a Forcing(func) or a Relaxation target that the host must resample at every stage) is refused with
  * OCN_ERR_INVALID_ARGUMENT -- that case needs the Python host (time_step(model, dt)). */
 int ocn_model_driver_set_forcing(ocn_model_driver_t driver, const ocn_forcing *const *forcing, int32_t time_dependent);
+/* ---- Smagorinsky / SmagorinskyLilly (Smagorinskys/smagorinsky.jl:75-138, lilly_coefficient.jl:44-139; csrc/smagorinsky.hip) ----
+ *   Σ² = ΣᵢⱼΣᵢⱼᶜᶜᶜ,  Δᶠ = cbrt(Δx Δy Δz),  N² = ℑzᵃᵃᶜ(∂z_b),  ς = ifelse(Σ² == 0, 0, sqrt(1 - min(1, Cb max(0, N²) / Σ²))),
+ *   νₑ = (ς C C) (Δᶠ Δᶠ) sqrt(2 Σ²)     (number coefficient: ς = 1, no buoyancy read).
+ * Strict math: every operation IEEE and in the reference's order; cbrt is within 1 ulp.  One GPU.
+ * Tracers: the reference's face diffusivity is ℑ(νₑ) / Pr.  Where Pr[n] == 1 the tracer kernels take the nu_e array itself as kappa_e
+ * (bit-identical); where Pr[n] != 1 the kernel stores νₑ / Pr[n] into kappa_e[n], a Center field of its own, which the tracer kernels
+ * interpolate: ℑ(νₑ / Pr) instead of ℑ(νₑ) / Pr -- a difference of rounding only, none for Pr a power of two. */
+typedef struct ocn_smagorinsky {
+    double C;                          /* Cˢ */
+    double Cb;                         /* LillyCoefficient.reduction_factor; 0 with lilly == 0 */
+    int32_t lilly;                     /* 0: number coefficient (no buoyancy read); 1: LillyCoefficient */
+    int32_t n_tracers;                 /* 0 .. OCN_MODEL_MAX_TRACERS */
+    double Pr[OCN_MODEL_MAX_TRACERS];
+} ocn_smagorinsky;
+
+/* compute_diffusivities!(…, ::Smagorinsky, model) over the interior; the caller fills halos afterwards.
+ * terms: buoyancy kind, g, alpha, beta, T, S are read (nothing else).  kappa_e[n] is NULL or == nu_e where Pr[n] == 1.
+ * OCN_ERR_INVALID_ARGUMENT: a Flat z; lilly with a buoyancy kind whose tracer pointer is NULL; Pr[n] <= 0; a NULL kappa_e[n] where
+ * Pr[n] != 1. */
+int ocn_compute_smagorinsky_diffusivities(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_smagorinsky *closure,
+                                          const double *u, const double *v, const double *w,
+                                          double *nu_e, double *const *kappa_e, void *stream);
+/* ModelRK3Driver: fill nu_e / kappa_e with the above instead of the AMD kernel (desc.terms.closure stays 2; desc.kappa_e[n] may equal
+ * desc.nu_e).  The struct is copied; NULL returns to AMD.  Same preconditions as ocn_model_driver_set_stokes_drift: not while a step's
+ * tendencies are deferred, not on a slab-x rank.  The next time step begins with update_state! and fresh tendencies. */
+int ocn_model_driver_set_smagorinsky(ocn_model_driver_t driver, const ocn_smagorinsky *closure);
 /* where field f (0, 1, 2 = u, v, w; 3 + n = tracer n) and its G^n are right now */
 int ocn_model_driver_field(ocn_model_driver_t driver, int32_t f, double **field, double **G);
 

@@ -21,7 +21,7 @@ from .models import (NonhydrostaticModel, QuasiAdamsBashforth2TimeStepper, Runge
                      update_state)
 from .output import (AdvectiveCFL, DiffusiveCFL, NaNChecker, TimeStepWizard, cell_advection_timescale, cell_diffusion_timescale, hasnan, set_from_checkpoint,
                      write_checkpoint)
-from .physics import (AnisotropicMinimumDissipation, BetaPlane, BoundaryCondition, BuoyancyTracer, Centered, FieldBoundaryConditions, FluxBoundaryCondition, FPlane,
+from .physics import (AnisotropicMinimumDissipation, DynamicCoefficient, DynamicSmagorinsky, LillyCoefficient, Smagorinsky, SmagorinskyLilly, BetaPlane, BoundaryCondition, BuoyancyTracer, Centered, FieldBoundaryConditions, FluxBoundaryCondition, FPlane,
                       GradientBoundaryCondition, LinearEquationOfState, OpenBoundaryCondition, ScalarDiffusivity, SeawaterBuoyancy,
                       ValueBoundaryCondition)
 from .stokes import StokesDrift, UniformStokesDrift

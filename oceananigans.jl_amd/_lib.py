@@ -80,6 +80,11 @@ class CModelDriverDesc(C.Structure):
                 ("pHY", C.c_void_p), ("bcs", C.POINTER(CFieldBcs) * (3 + MODEL_MAX_TRACERS))]
 
 
+class CSmagorinsky(C.Structure):
+    """struct ocn_smagorinsky"""
+    _fields_ = [("C", C.c_double), ("Cb", C.c_double), ("lilly", C.c_int32), ("n_tracers", C.c_int32), ("Pr", C.c_double * MODEL_MAX_TRACERS)]
+
+
 class CCommOp(C.Structure):
     """struct ocn_comm_op"""
     _fields_ = [("is_recv", C.c_int32), ("peer", C.c_int32), ("slot", C.c_int32)]
@@ -195,6 +200,8 @@ _SIGS = {
     "ocn_model_driver_field": [_vp, _i32, C.POINTER(_vp), C.POINTER(_vp)],
     "ocn_model_driver_set_stokes_drift": [_vp, C.POINTER(CStokesDrift), _i32],
     "ocn_model_driver_set_forcing": [_vp, C.POINTER(C.POINTER(CForcing)), _i32],
+    "ocn_model_driver_set_smagorinsky": [_vp, C.POINTER(CSmagorinsky)],
+    "ocn_compute_smagorinsky_diffusivities": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CSmagorinsky), _vp, _vp, _vp, _vp, C.POINTER(_vp), _vp],
     "ocn_halo_plane_x": [C.POINTER(CGrid), _vp, _i32, _i32, _vp, _i32, _vp],
     "ocn_halo_pack_pressure": [C.POINTER(CGrid), _vp, _vp, _dbl, _vp, _vp, _vp],
     "ocn_halo_unpack_pressure": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _vp],

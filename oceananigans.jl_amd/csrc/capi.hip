@@ -685,6 +685,39 @@ int ocn_compute_amd_diffusivity(const ocn_grid *grid, double C_kappa, const doub
                                           : ocn_fast::launch_amd_diffusivity(grid, C_kappa, u, v, w, c, kappa_e, as_stream(stream));
 }
 
+int ocn_compute_smagorinsky_diffusivities(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_smagorinsky *closure,
+                                          const double *u, const double *v, const double *w, double *nu_e, double *const *kappa_e,
+                                          void *stream)
+{
+    int st = validate_grid_any(grid);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(grid->tz != OCN_FLAT, "Smagorinsky needs a non-Flat z");
+    OCN_REQUIRE((grid->tx == OCN_FLAT || grid->Hx >= 1) && (grid->ty == OCN_FLAT || grid->Hy >= 1) && grid->Hz >= 1, "Smagorinsky needs halo >= 1");
+    OCN_REQUIRE(terms && closure, "ocn_compute_smagorinsky_diffusivities: null terms / closure");
+    OCN_REQUIRE(u && v && w && nu_e, "ocn_compute_smagorinsky_diffusivities: null field pointer");
+    OCN_REQUIRE(closure->lilly == 0 || closure->lilly == 1, "ocn_compute_smagorinsky_diffusivities: lilly = %d is neither 0 nor 1", closure->lilly);
+    OCN_REQUIRE(closure->n_tracers >= 0 && closure->n_tracers <= OCN_MODEL_MAX_TRACERS, "ocn_compute_smagorinsky_diffusivities: n_tracers = %d outside 0..%d",
+                closure->n_tracers, OCN_MODEL_MAX_TRACERS);
+    if (closure->lilly) {
+        const int b = terms->buoyancy;
+        OCN_REQUIRE(b >= OCN_BUOYANCY_NONE && b <= OCN_BUOYANCY_SEAWATER_S, "ocn_compute_smagorinsky_diffusivities: unknown buoyancy %d", b);
+        if (b == OCN_BUOYANCY_TRACER || b == OCN_BUOYANCY_SEAWATER_TS || b == OCN_BUOYANCY_SEAWATER_T)
+            OCN_REQUIRE(terms->T != nullptr, "ocn_compute_smagorinsky_diffusivities: LillyCoefficient reads N²: T (or b) tracer is NULL");
+        if (b == OCN_BUOYANCY_SEAWATER_TS || b == OCN_BUOYANCY_SEAWATER_S)
+            OCN_REQUIRE(terms->S != nullptr, "ocn_compute_smagorinsky_diffusivities: LillyCoefficient reads N²: S tracer is NULL");
+    }
+    for (int n = 0; n < closure->n_tracers; ++n) {
+        OCN_REQUIRE(closure->Pr[n] > 0, "ocn_compute_smagorinsky_diffusivities: Pr[%d] = %g must be positive", n, closure->Pr[n]);
+        OCN_REQUIRE(closure->Pr[n] == 1.0 || (kappa_e && kappa_e[n]), "ocn_compute_smagorinsky_diffusivities: Pr[%d] != 1 needs a kappa_e field", n);
+        OCN_REQUIRE(closure->Pr[n] == 1.0 || kappa_e[n] != nu_e, "ocn_compute_smagorinsky_diffusivities: Pr[%d] != 1 needs a kappa_e field other than nu_e", n);
+        OCN_REQUIRE(closure->Pr[n] != 1.0 || !kappa_e || !kappa_e[n] || kappa_e[n] == nu_e,
+                    "ocn_compute_smagorinsky_diffusivities: Pr[%d] == 1: kappa_e must be NULL or the nu_e array (the tracer reads nu_e)", n);
+    }
+    const TermsDev t = to_dev(*terms);
+    return strict_math(grid) ? ocn_strict::launch_smagorinsky(grid, t, *closure, u, v, w, nu_e, kappa_e, as_stream(stream))
+                             : ocn_fast::launch_smagorinsky(grid, t, *closure, u, v, w, nu_e, kappa_e, as_stream(stream));
+}
+
 int ocn_update_hydrostatic_pressure(const ocn_grid *grid, const ocn_model_terms *terms, double *pHY, void *stream)
 {
     int st = validate_grid_any(grid);

@@ -5,8 +5,8 @@
 // Host code only: every device operation is one of the public entry points, issued in the order the Python host issues them on its
 // general fused path (models.py::_time_step_rk3, _update_state_and_rk3_substep_general) -- so the two are bit-identical
 // (tests/test_gpu_physics.py::test_c_model_driver_equals_python_host) -- without an interpreter between the launches:
-//   per stage boundary:  halo fill of every prognostic field (one launch) -> AMD diffusivities (one launch) -> pHY' -> halo fill of
-//   nu_e, kappa_e -> momentum: tiled advection launch + one finishing pass (extra terms, u / v boundary fluxes, next substep) ->
+//   per stage boundary:  halo fill of every prognostic field (one launch) -> AMD or Smagorinsky diffusivities (one launch) -> pHY' -> halo
+//   fill of nu_e, kappa_e (distinct arrays) -> momentum: tiled advection launch + one finishing pass (extra terms, u / v boundary fluxes, next substep) ->
 //   one launch per tracer (advection, diffusion, boundary flux, next substep) -> velocity halos -> Poisson solve -> pressure halos ->
 //   pressure correction.  Substep results land in a second set of arrays whose roles then alternate; G^n / G^- swap.
 #include <cstdlib>
@@ -45,6 +45,9 @@ struct ocn_model_driver {
     ocn_forcing forcing_store[NF];
     const ocn_forcing *forcing[NF] = {};  // NULL = the field is not forced
     bool momentum_forced = false;
+    // closure = Smagorinsky / SmagorinskyLilly (ocn_model_driver_set_smagorinsky): nu_e / kappa_e come from its kernel; kappa_e[t] may be nu_e
+    ocn_smagorinsky smagorinsky{};
+    bool has_smagorinsky = false;
     long long iteration = 0;
     // slab-x rank (ocn_model_driver_create_distributed): RCCL communicator + distributed Poisson handle, both borrowed
     ocn_comm_t comm = nullptr;
@@ -118,7 +121,9 @@ int compute_auxiliaries(ocn_model_driver *d, void *stream)
 {
     int st;
     if (d->terms.closure == 2) {
-        st = ocn_compute_amd_diffusivities(&d->grid, d->Cnu, d->U[0], d->U[1], d->U[2], d->nu_e, d->nt, d->Ck, d->U + 3, d->kappa_e, stream);
+        st = d->has_smagorinsky
+                 ? ocn_compute_smagorinsky_diffusivities(&d->grid, &d->terms, &d->smagorinsky, d->U[0], d->U[1], d->U[2], d->nu_e, d->kappa_e, stream)
+                 : ocn_compute_amd_diffusivities(&d->grid, d->Cnu, d->U[0], d->U[1], d->U[2], d->nu_e, d->nt, d->Ck, d->U + 3, d->kappa_e, stream);
         if (st != OCN_SUCCESS) return st;
     }
     if (d->pHY) {
@@ -128,13 +133,18 @@ int compute_auxiliaries(ocn_model_driver *d, void *stream)
     if (d->terms.closure == 2) {
         double *f[1 + OCN_MODEL_MAX_TRACERS];
         int32_t l[1 + OCN_MODEL_MAX_TRACERS];
+        int nf = 1;
         f[0] = d->nu_e;
         l[0] = OCN_LOC_CCC;
-        for (int t = 0; t < d->nt; ++t) {
-            f[1 + t] = d->kappa_e[t];
-            l[1 + t] = OCN_LOC_CCC;
+        for (int t = 0; t < d->nt; ++t) {  // distinct arrays only: a kappa_e may be the nu_e array (Smagorinsky, Pr == 1)
+            bool seen = false;
+            for (int q = 0; q < nf; ++q) seen = seen || f[q] == d->kappa_e[t];
+            if (seen) continue;
+            f[nf] = d->kappa_e[t];
+            l[nf] = OCN_LOC_CCC;
+            nf += 1;
         }
-        st = fill(d, f, l, nullptr, 1 + d->nt, 1, stream);
+        st = fill(d, f, l, nullptr, nf, 1, stream);
         if (st != OCN_SUCCESS) return st;
     }
     return OCN_SUCCESS;
@@ -582,6 +592,28 @@ extern "C" int ocn_model_driver_set_forcing(ocn_model_driver_t d, const ocn_forc
         if (f < 3) d->momentum_forced = true;
     }
     d->momentum_extra = d->base_momentum_extra || d->has_stokes || d->momentum_forced;
+    d->started = false;  // the next time step begins with update_state! and a fresh compute_tendencies!, as at iteration 0
+    return OCN_SUCCESS;
+}
+
+extern "C" int ocn_model_driver_set_smagorinsky(ocn_model_driver_t d, const ocn_smagorinsky *closure)
+{
+    OCN_REQUIRE(d, "ocn_model_driver_set_smagorinsky: null driver");
+    OCN_REQUIRE(!d->comm, "ocn_model_driver_set_smagorinsky: not on a slab-x rank (Smagorinsky on a Distributed architecture is not implemented)");
+    OCN_REQUIRE(!d->pending, "ocn_model_driver_set_smagorinsky: call before the first time step or after ocn_model_driver_flush");
+    if (closure) {
+        OCN_REQUIRE(d->terms.closure == 2, "ocn_model_driver_set_smagorinsky: the driver was created with closure %d, not 2 (eddy fields)", d->terms.closure);
+        OCN_REQUIRE(d->grid.tz != OCN_FLAT, "ocn_model_driver_set_smagorinsky: Smagorinsky needs a non-Flat z");
+        OCN_REQUIRE(closure->lilly == 0 || closure->lilly == 1, "ocn_model_driver_set_smagorinsky: lilly = %d is neither 0 nor 1", closure->lilly);
+        OCN_REQUIRE(closure->n_tracers == d->nt, "ocn_model_driver_set_smagorinsky: n_tracers = %d, the driver has %d", closure->n_tracers, d->nt);
+        for (int t = 0; t < d->nt; ++t) {
+            OCN_REQUIRE(closure->Pr[t] > 0, "ocn_model_driver_set_smagorinsky: Pr[%d] = %g must be positive", t, closure->Pr[t]);
+            OCN_REQUIRE((closure->Pr[t] == 1.0) == (d->kappa_e[t] == d->nu_e),
+                        "ocn_model_driver_set_smagorinsky: tracer %d: kappa_e must be the nu_e array where Pr == 1 and a field of its own otherwise", t);
+        }
+    }
+    d->has_smagorinsky = closure != nullptr;
+    d->smagorinsky = closure ? *closure : ocn_smagorinsky{};
     d->started = false;  // the next time step begins with update_state! and a fresh compute_tendencies!, as at iteration 0
     return OCN_SUCCESS;
 }

@@ -184,6 +184,8 @@ int launch_amd_viscosity(const ocn_grid *grid, double Cnu, const double *u, cons
                          hipStream_t stream);
 int launch_amd_diffusivity(const ocn_grid *grid, double Ck, const double *u, const double *v, const double *w, const double *c,
                            double *kappa_e, hipStream_t stream);
+int launch_smagorinsky(const ocn_grid *grid, const ocn::TermsDev &t, const ocn_smagorinsky &closure, const double *u, const double *v,
+                       const double *w, double *nu_e, double *const *kappa_e, hipStream_t stream);
 }
 namespace ocn_fast {
 int launch_momentum_tendencies_general(const ocn_grid *grid, int centered2, const double *u, const double *v, const double *w, double *Gu,
@@ -224,6 +226,8 @@ int launch_amd_viscosity(const ocn_grid *grid, double Cnu, const double *u, cons
                          hipStream_t stream);
 int launch_amd_diffusivity(const ocn_grid *grid, double Ck, const double *u, const double *v, const double *w, const double *c,
                            double *kappa_e, hipStream_t stream);
+int launch_smagorinsky(const ocn_grid *grid, const ocn::TermsDev &t, const ocn_smagorinsky &closure, const double *u, const double *v,
+                       const double *w, double *nu_e, double *const *kappa_e, hipStream_t stream);
 }
 
 // advection = UpwindBiased(order=5): tendencies.hip compiled with OCN_UPWIND=1

@@ -21,7 +21,7 @@ from .architectures import stream_ptr
 from .fields import fill_halo_regions
 from .grids import Bounded, Periodic
 from .models import NonhydrostaticModel, compute_boundary_tendency_contributions, update_hydrostatic_pressure
-from .physics import AnisotropicMinimumDissipation, Centered
+from .physics import Centered, owns_eddy_fields
 
 g_Earth = 9.80665  # Oceananigans.BuoyancyFormulations.g_Earth
 
@@ -194,7 +194,7 @@ class HydrostaticFreeSurfaceModel:
             if tracer_advection is not None and type(tracer_advection) is not type(momentum_advection):
                 raise NotImplementedError("with a flux-form momentum scheme, tracer_advection must be the same scheme in this slice")
             container_advection = momentum_advection
-        if isinstance(closure, AnisotropicMinimumDissipation):
+        if owns_eddy_fields(closure):
             raise NotImplementedError("eddy-viscosity closures are not part of this slice")
         # fields, physics descriptors, tendency storage and the Adams-Bashforth bookkeeping of the nonhydrostatic model are reused;
         # its pressure solver and w tendency are simply not used

@@ -11,7 +11,7 @@ Mirrors, call for call:
   cache_previous_tendencies!                                      src/TimeSteppers/store_tendencies.jl:12-22
 Julia's `f!` names are spelled `f` here.  background_fields is `nothing`; forcing is a dict of arrays, Relaxation(...) and Forcing(func)
 (forcings.py); stokes_drift is UniformStokesDrift (stokes.py); advection is WENO()
-or Centered(); coriolis = FPlane, closure = ScalarDiffusivity, buoyancy = BuoyancyTracer / SeawaterBuoyancy and bottom /
+or Centered(); coriolis = FPlane, closure = ScalarDiffusivity / AnisotropicMinimumDissipation / Smagorinsky(Lilly), buoyancy = BuoyancyTracer / SeawaterBuoyancy and bottom /
 top Flux / Value / Gradient boundary conditions are the SURVEY §8(f) rank-1 terms (physics.py); anything else raises.
 """
 import math
@@ -26,7 +26,7 @@ import ctypes as C
 
 from .advection import WENO, UpwindBiased
 from .physics import (AnisotropicMinimumDissipation, BetaPlane, BuoyancyTracer, Centered, FieldBoundaryConditions, FPlane, ScalarDiffusivity,
-                      SeawaterBuoyancy)
+                      SeawaterBuoyancy, Smagorinsky, owns_eddy_fields)
 from .architectures import stream_ptr
 from .fields import CenterField, Field, XFaceField, YFaceField, ZFaceField, fill_halo_regions
 from .grids import Bounded, Flat, require_regular_xy
@@ -107,8 +107,13 @@ class NonhydrostaticModel:
             raise NotImplementedError("only coriolis = FPlane(...) or BetaPlane(...) is implemented")
         if isinstance(coriolis, BetaPlane) and grid.topology[1] == Flat:
             raise NotImplementedError("BetaPlane needs a non-Flat y")
-        if closure is not None and not isinstance(closure, (ScalarDiffusivity, AnisotropicMinimumDissipation)):
-            raise NotImplementedError("only closure = ScalarDiffusivity(...) or AnisotropicMinimumDissipation(...) is implemented")
+        if closure is not None and not isinstance(closure, (ScalarDiffusivity, AnisotropicMinimumDissipation, Smagorinsky)):
+            raise NotImplementedError("only closure = ScalarDiffusivity(...), AnisotropicMinimumDissipation(...), Smagorinsky(...) or "
+                                      "SmagorinskyLilly(...) is implemented")
+        if isinstance(closure, Smagorinsky) and hasattr(grid.architecture, "partition"):
+            raise NotImplementedError("closure = Smagorinsky / SmagorinskyLilly on a Distributed architecture is not implemented (see DESIGN.md)")
+        if isinstance(closure, Smagorinsky) and grid.topology[2] == Flat:
+            raise NotImplementedError("Smagorinsky needs a non-Flat z")
         if buoyancy is not None and not isinstance(buoyancy, (BuoyancyTracer, SeawaterBuoyancy)):
             raise NotImplementedError("only buoyancy = BuoyancyTracer() or SeawaterBuoyancy(...) is implemented")
         if isinstance(tracers, str):
@@ -145,8 +150,15 @@ class NonhydrostaticModel:
         # (build_diffusivity_fields, anisotropic_minimum_dissipation.jl:333-341); ASCII aliases nu_e / kappa_e
         nu_bcs = bcs.pop("νₑ", bcs.pop("nu_e", None))
         kappa_bcs = dict(bcs.pop("κₑ", bcs.pop("kappa_e", None)) or {})
-        if (nu_bcs is not None or kappa_bcs) and not isinstance(closure, AnisotropicMinimumDissipation):
-            raise ValueError("νₑ / κₑ boundary conditions need closure = AnisotropicMinimumDissipation()")
+        if (nu_bcs is not None or kappa_bcs) and not owns_eddy_fields(closure):
+            raise ValueError("νₑ / κₑ boundary conditions need an eddy-viscosity closure (AnisotropicMinimumDissipation, Smagorinsky)")
+        if isinstance(closure, Smagorinsky):
+            if kappa_bcs:  # build_diffusivity_fields (smagorinsky.jl:125-134) has νₑ only
+                raise ValueError("Smagorinsky has no κₑ fields (κ = νₑ / Pr): κₑ boundary conditions cannot be set")
+            prandtl = [closure.Pr_of(n) for n in tracers]  # (a tracer missing from a dict Pr: ValueError)
+            if nu_bcs is not None and not nu_bcs.is_default() and any(p != 1 for p in prandtl):
+                raise NotImplementedError("a νₑ boundary condition together with a Prandtl number other than 1 is not implemented: the κₑ = νₑ / Pr "
+                                          "fields are filled with the default conditions (see DESIGN.md)")
         for name in bcs:
             if name not in ("u", "v", "w") + tracers:
                 raise ValueError(f"boundary conditions given for unknown field {name!r}")
@@ -183,11 +195,17 @@ class NonhydrostaticModel:
             raise ValueError("hydrostatic_pressure_anomaly must be 'default' or None")
         # build_diffusivity_fields (anisotropic_minimum_dissipation.jl:333-341): νₑ and one κₑ per tracer, default conditions
         self.diffusivity_fields = None
-        if isinstance(closure, AnisotropicMinimumDissipation):
+        if owns_eddy_fields(closure):
             if grid.topology[2] == Flat:
-                raise NotImplementedError("AnisotropicMinimumDissipation needs a non-Flat z")
-            self.diffusivity_fields = {"nu_e": CenterField(grid, nu_bcs),
-                                       "kappa_e": tuple(CenterField(grid, kappa_bcs.get(n)) for n in tracers)}
+                raise NotImplementedError(f"{type(closure).__name__} needs a non-Flat z")
+            nu_e = CenterField(grid, nu_bcs)
+            if isinstance(closure, Smagorinsky):
+                # build_diffusivity_fields (smagorinsky.jl:125-134): νₑ only.  κ = νₑ / Pr: a tracer with Pr == 1 reads the νₑ array itself,
+                # every other one a Center field of its own that compute_diffusivities fills in the same pass
+                kappa_e = tuple(nu_e if closure.Pr_of(n) == 1 else CenterField(grid) for n in tracers)
+            else:
+                kappa_e = tuple(CenterField(grid, kappa_bcs.get(n)) for n in tracers)
+            self.diffusivity_fields = {"nu_e": nu_e, "kappa_e": kappa_e}
         # (pressure_solver=None: no solver is built -- the HydrostaticFreeSurfaceModel reuses this class as its field container)
         self.pressure_solver = nonhydrostatic_pressure_solver(grid) if pressure_solver == "default" else pressure_solver
         prog = self.prognostic_fields()
@@ -280,7 +298,7 @@ class NonhydrostaticModel:
                 t.yc, t.yf = self._ynodes[0].data_ptr(), self._ynodes[1].data_ptr()
             else:
                 t.coriolis, t.f = 1, self.coriolis.f
-        if isinstance(self.closure, AnisotropicMinimumDissipation):
+        if owns_eddy_fields(self.closure):
             t.closure, t.nu_e = 2, self.diffusivity_fields["nu_e"].ptr
         elif self.closure is not None:
             t.closure, t.nu = 1, self.closure.nu
@@ -368,9 +386,7 @@ def update_boundary_conditions(model):
     if not getattr(model, "_has_user_bcs", False):
         return
     fields = list(model.prognostic_fields())
-    d = getattr(model, "diffusivity_fields", None)
-    if d is not None:
-        fields += [d["nu_e"]] + list(d["kappa_e"])
+    fields += list(distinct_diffusivity_fields(model))
     for f in fields:
         b = getattr(f, "boundary_conditions", None)
         if b is not None:
@@ -396,18 +412,41 @@ def compute_auxiliaries(model):
     compute_diffusivities(model)
     update_hydrostatic_pressure(model)
     if model.diffusivity_fields is not None:
-        d = model.diffusivity_fields
-        fill_halo_regions((d["nu_e"],) + d["kappa_e"])
+        fill_halo_regions(distinct_diffusivity_fields(model))
+
+
+def distinct_diffusivity_fields(model):
+    """νₑ and the κₑ fields as distinct arrays: with Smagorinsky the κₑ of a tracer with Pr == 1 IS the νₑ field (halo fills, boundary
+    condition refreshes and checkpoints walk each array once)"""
+    d = getattr(model, "diffusivity_fields", None)
+    if d is None:
+        return ()
+    out = [d["nu_e"]]
+    for k in d["kappa_e"]:
+        if not any(k is f for f in out):
+            out.append(k)
+    return tuple(out)
 
 
 def compute_diffusivities(model, irange=None):
-    """compute_diffusivities!(diffusivity_fields, closure::AnisotropicMinimumDissipation, model); irange = (i_first, i_last):
+    """compute_diffusivities!(diffusivity_fields, closure, model) -- the one place that branches on the kind of eddy-viscosity closure;
+    irange = (i_first, i_last) (AnisotropicMinimumDissipation only):
     those columns only, 0 and Nx+1 included (Distributed: interior during the halo exchange, edges and halo columns after it)."""
     d = model.diffusivity_fields
     if d is None:
         return
     g, s = model.grid, stream_ptr()
     nt = len(model.tracers)
+    if isinstance(model.closure, Smagorinsky):
+        if irange is not None:
+            raise NotImplementedError("column ranges of the Smagorinsky diffusivities are not implemented (one GPU only)")
+        if nt > _lib.MODEL_MAX_TRACERS:
+            raise NotImplementedError(f"Smagorinsky: at most {_lib.MODEL_MAX_TRACERS} tracers")
+        model._refresh_term_pointers()  # N² reads the buoyancy tracers where they are now
+        cs = model.closure.c_struct(model.tracer_names)
+        _lib.call("ocn_compute_smagorinsky_diffusivities", g.cref, C.byref(model._terms), C.byref(cs), model.u.ptr, model.v.ptr, model.w.ptr,
+                  d["nu_e"].ptr, _lib.ptr_array([k.ptr for k in d["kappa_e"]] or [None]), s)
+        return
     if nt <= 4:  # νₑ and every κₑ in one launch
         Ck = (C.c_double * max(nt, 1))(*[model.closure.Ckappa_of(n) for n in model.tracer_names])
         if irange is not None:
@@ -932,14 +971,15 @@ class ModelRK3Driver:
                 desc.tracer_T = names.index("T")
             if b.constant_salinity is None:
                 desc.tracer_S = names.index("S")
+        eddy = owns_eddy_fields(model.closure)
         amd = isinstance(model.closure, AnisotropicMinimumDissipation)
-        if amd:
-            desc.C_nu = model.closure.Cnu
+        if eddy:
+            desc.C_nu = model.closure.Cnu if amd else 0.0
             desc.nu_e = d["nu_e"].ptr
         for n, name in enumerate(names):
             desc.tracers[n] = model.tracers[n].ptr
-            if amd:
-                desc.C_kappa[n] = model.closure.Ckappa_of(name)
+            if eddy:
+                desc.C_kappa[n] = model.closure.Ckappa_of(name) if amd else 0.0
                 desc.kappa_e[n] = d["kappa_e"][n].ptr
             elif model.closure is not None:
                 desc.kappa[n] = model.closure.kappa_of(name)
@@ -960,6 +1000,11 @@ class ModelRK3Driver:
         else:
             _lib.call("ocn_model_driver_create", C.byref(self._h), model.grid.cref, C.byref(desc), model.u.ptr, model.v.ptr, model.w.ptr,
                       model.pNHS.ptr, None if own_solver else model.pressure_solver._h, stream_ptr())
+        if isinstance(model.closure, Smagorinsky):
+            # the library fills νₑ / κₑ with the Smagorinsky kernel from here on; its update_state! at creation ran before it knew: recompute
+            self._smagorinsky = model.closure.c_struct(model.tracer_names)
+            _lib.call("ocn_model_driver_set_smagorinsky", self._h, C.byref(self._smagorinsky))
+            compute_auxiliaries(model)
         if model._stokes is not None:  # steady profiles: the device vectors stay the model's
             _lib.call("ocn_model_driver_set_stokes_drift", self._h, C.byref(model._stokes.c), 0)
         if any(f is not None for f in model._forcing):  # steady terms: the device vectors / arrays stay the model's

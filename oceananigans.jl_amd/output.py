@@ -64,13 +64,13 @@ def cell_diffusion_timescale(model):
     """cell_diffusion_timescale(model) (src/TurbulenceClosures/turbulence_closure_diagnostics.jl:20-74): min(Δ² / max ν, Δ² / max κ) with
     Δ = the smallest cell spacing (1 along Flat directions); ScalarDiffusivity: the numbers ν, κ; AnisotropicMinimumDissipation: the maxima
     of the eddy-diffusivity fields' parents.  Inf without a closure."""
-    from .physics import AnisotropicMinimumDissipation
+    from .physics import owns_eddy_fields
     g, cl = model.grid, model.closure
     if cl is None:
         return float("inf")
     delta = min(g.spacing_extrema(d)[0] if g.topology[d] != "Flat" else 1.0 for d in range(3))
     div = lambda a, b: a / b if b != 0 else float("inf")
-    if isinstance(cl, AnisotropicMinimumDissipation):
+    if owns_eddy_fields(cl):
         d = model.diffusivity_fields
         max_nu = float(d["nu_e"].data.max())
         max_kappa = max((float(k.data.max()) for k in d["kappa_e"]), default=float("inf"))

@@ -3,6 +3,8 @@
   Centered(order=2)                               src/Advection/centered_reconstruction.jl:39-60 (the reference's default advection)
   FPlane(f=...) / FPlane(rotation_rate, latitude) src/Coriolis/f_plane.jl:8-42
   ScalarDiffusivity(ν=..., κ=...)                 src/TurbulenceClosures/turbulence_closure_implementations/scalar_diffusivity.jl
+  Smagorinsky(coefficient=..., Pr=...), SmagorinskyLilly(C=..., Cb=..., Pr=...), LillyCoefficient(...)
+                                                  .../turbulence_closure_implementations/Smagorinskys/{smagorinsky,lilly_coefficient}.jl
   BuoyancyTracer(), SeawaterBuoyancy(...), LinearEquationOfState(...)
                                                   src/BuoyancyFormulations/{buoyancy_tracer,seawater_buoyancy,linear_equation_of_state}.jl
   FluxBoundaryCondition, ValueBoundaryCondition, GradientBoundaryCondition, FieldBoundaryConditions, BetaPlane
@@ -158,6 +160,90 @@ class AnisotropicMinimumDissipation:
                 raise ValueError(f"no Poincaré constant Cκ given for tracer {name}")
             return float(self.Ckappa[name])
         return float(self.Ckappa)
+
+
+class LillyCoefficient:
+    """LillyCoefficient(; smagorinsky = 0.16, reduction_factor = 1) (Smagorinskys/lilly_coefficient.jl:44-45): the Smagorinsky coefficient
+    reduced by the stability function ς = sqrt(1 - min(1, Cb max(0, N²) / Σ²))."""
+
+    def __init__(self, smagorinsky=0.16, reduction_factor=1):
+        self.smagorinsky = float(smagorinsky)
+        self.reduction_factor = float(reduction_factor)
+
+    def __repr__(self):
+        return f"LillyCoefficient(smagorinsky = {self.smagorinsky}, reduction_factor = {self.reduction_factor})"
+
+
+class DynamicCoefficient:
+    """DynamicCoefficient(; averaging, ...) (Smagorinskys/dynamic_coefficient.jl): not implemented."""
+
+    def __init__(self, *args, **kw):
+        raise NotImplementedError("DynamicCoefficient (the scale-invariant dynamic Smagorinsky procedure) is not implemented")
+
+
+class Smagorinsky:
+    """Smagorinsky(; coefficient = 0.16, Pr = 1.0) (Smagorinskys/smagorinsky.jl:75-81): νₑ = (Cˢ Δᶠ)² sqrt(2 Σ²), κₑ = νₑ / Pr.
+    `coefficient` is a number or a LillyCoefficient; Pr is a number (every tracer) or a dict {tracer name: Pr}.
+    ExplicitTimeDiscretization only."""
+
+    def __init__(self, coefficient=0.16, Pr=1.0, time_discretization="Explicit"):
+        if time_discretization != "Explicit":
+            raise NotImplementedError("VerticallyImplicitTimeDiscretization is not implemented")
+        if isinstance(coefficient, type) or callable(coefficient):
+            raise NotImplementedError("only a number or a LillyCoefficient is implemented as the Smagorinsky coefficient")
+        if not isinstance(coefficient, LillyCoefficient):
+            if np.ndim(coefficient) > 0:
+                raise NotImplementedError("only a number or a LillyCoefficient is implemented as the Smagorinsky coefficient")
+            coefficient = float(coefficient)
+        if callable(Pr) or (not isinstance(Pr, dict) and np.ndim(Pr) > 0):
+            raise NotImplementedError("only number (or per-tracer dict) Prandtl numbers are implemented")
+        self.coefficient = coefficient
+        self.Pr = {k: float(v) for k, v in Pr.items()} if isinstance(Pr, dict) else float(Pr)
+
+    @property
+    def lilly(self):
+        return isinstance(self.coefficient, LillyCoefficient)
+
+    @property
+    def C(self):
+        return self.coefficient.smagorinsky if self.lilly else self.coefficient
+
+    @property
+    def Cb(self):
+        return self.coefficient.reduction_factor if self.lilly else 0.0
+
+    def Pr_of(self, name):
+        if isinstance(self.Pr, dict):
+            if name not in self.Pr:
+                raise ValueError(f"no Prandtl number Pr given for tracer {name}")
+            return self.Pr[name]
+        return self.Pr
+
+    def c_struct(self, tracer_names):
+        """struct ocn_smagorinsky for these tracers"""
+        s = _lib.CSmagorinsky()
+        s.C, s.Cb, s.lilly, s.n_tracers = self.C, self.Cb, int(self.lilly), len(tracer_names)
+        for n, name in enumerate(tracer_names):
+            s.Pr[n] = self.Pr_of(name)
+        return s
+
+    def __repr__(self):
+        return f"Smagorinsky(coefficient = {self.coefficient!r}, Pr = {self.Pr})"
+
+
+def SmagorinskyLilly(C=0.16, Cb=1, Pr=1, time_discretization="Explicit"):
+    """SmagorinskyLilly(; C = 0.16, Cb = 1, Pr = 1) = Smagorinsky(coefficient = LillyCoefficient(C, Cb), Pr = Pr) (lilly_coefficient.jl:106-111)"""
+    return Smagorinsky(coefficient=LillyCoefficient(smagorinsky=C, reduction_factor=Cb), Pr=Pr, time_discretization=time_discretization)
+
+
+def DynamicSmagorinsky(*args, **kw):
+    """DynamicSmagorinsky(; averaging, Pr, ...) (Smagorinskys/dynamic_coefficient.jl): not implemented."""
+    raise NotImplementedError("DynamicSmagorinsky is not implemented")
+
+
+def owns_eddy_fields(closure):
+    """closures whose diffusivity_fields hold a νₑ Center field (and κₑ fields) that compute_diffusivities fills"""
+    return isinstance(closure, (AnisotropicMinimumDissipation, Smagorinsky))
 
 
 class LinearEquationOfState:

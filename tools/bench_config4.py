@@ -5,7 +5,8 @@ spacing, examples/ocean_wind_mixing_and_convection.jl:38-62), WENO5, RK3, Fourie
   tools/bench_config4.py [Nx] [Nz] [steps] [physics] [--sponge | --sponge3d]
 physics = 0: advection only (SURVEY §8d first form);  1: the example's physics (:79-152) with the LES closure replaced by a
 constant ScalarDiffusivity: SeawaterBuoyancy(linear EOS), T and S tracers, FPlane(f=1e-4), wind stress, surface heat flux,
-bottom temperature gradient, evaporation;  2: the example as written, closure = AnisotropicMinimumDissipation().
+bottom temperature gradient, evaporation;  2: the example as written, closure = AnisotropicMinimumDissipation();  3: the example with
+SmagorinskyLilly() in AMD's place (the drop-in alternative the example names, :157).
 --sponge (physics >= 1): Relaxation(rate, GaussianMask("z")) sponges at the bottom on u, v, w and LinearTarget("z") sponges on T and S -- the cost of
 forcing = {...}; --sponge3d: the same masks as 3-D arrays (+8 B per cell and forced field).
 Prints ms/step and cell-updates/s."""
@@ -21,7 +22,7 @@ Nz = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 steps = int(sys.argv[3]) if len(sys.argv) > 3 else 5
 physics = int(sys.argv[4]) if len(sys.argv) > 4 else 0
 if sponge and not physics:
-    sys.exit(f"{sponge} needs physics = 1 or 2 (the sponges act on u, v, w, T and S)")
+    sys.exit(f"{sponge} needs physics = 1, 2 or 3 (the sponges act on u, v, w, T and S)")
 Lz, refinement, stretching = 32.0, 1.2, 12.0
 h = lambda k: (k - 1) / Nz
 zeta0 = lambda k: 1 + (h(k) - 1) / refinement
@@ -45,7 +46,7 @@ if physics:
         forcing["T"] = ocn.Relaxation(1 / 60.0, mask=mask(Nz), target=ocn.LinearTarget("z", intercept=20.0, gradient=dTdz))
         forcing["S"] = ocn.Relaxation(1 / 60.0, mask=mask(Nz), target=ocn.LinearTarget("z", intercept=35.0, gradient=0.0))
     m = ocn.NonhydrostaticModel(g, advection=ocn.WENO(), tracers=("T", "S"), coriolis=ocn.FPlane(f=1e-4), forcing=forcing,
-                                closure=ocn.AnisotropicMinimumDissipation() if physics == 2 else ocn.ScalarDiffusivity(ν=1e-4, κ=1e-4),
+                                closure={2: ocn.AnisotropicMinimumDissipation, 3: ocn.SmagorinskyLilly}.get(physics, lambda: ocn.ScalarDiffusivity(ν=1e-4, κ=1e-4))(),
                                 buoyancy=ocn.SeawaterBuoyancy(equation_of_state=ocn.LinearEquationOfState(2e-4, 8e-4)),
                                 boundary_conditions=bcs)
     zc = 0.5 * (z_faces[1:] + z_faces[:-1])
