@@ -171,6 +171,23 @@ int ocn_compute_momentum_tendencies_rk3_strips(const ocn_grid *grid, const doubl
                                                double *u_out, double *v_out, double *w_out, double dt, double gamma, double zeta,
                                                int32_t has_zeta, const double *p_correct, double dt_correct, double *strip_west,
                                                double *strip_east, int64_t field_doubles, void *stream);
+/* The correction-on-load launch (p_correct required, full range) of a (Periodic, Periodic, Periodic) box with work left out that a caller
+ * who orders the launches itself knows to be dead (ocn_rk3_driver_*); flags = 0 is ocn_compute_momentum_tendencies_rk3.
+ *   OCN_RK3_SKIP_G_STORE   G is computed and used by the substep but need not be stored: nobody reads it before the buffer is
+ *                          overwritten (the last launch of an RK3 step -- the next step's first launch has no G⁻ term and writes the
+ *                          same buffer).  A permission: honoured with has_zeta != 0 by the 32-bit kernel, ignored otherwise.
+ *   OCN_RK3_WRAPPED_LOADS  u, v, w are read by periodically wrapped indices like p: their halos are never touched, so no halo fill is
+ *                          needed in front of the launch.  Periodic x only.
+ *   OCN_RK3_CORRECT_ONLY   U_out = the corrected velocity itself (no substep; has_zeta = 0, dt / gamma unused), G = tendencies of the
+ *                          corrected velocity: pressure_correct_velocities! and compute_tendencies! in one pass, bit for bit.
+ * The last two are the 32-bit kernel's (ocn_momentum_tendencies_addr32 selects 1); OCN_ERR_UNSUPPORTED otherwise -- never a fallback. */
+#define OCN_RK3_SKIP_G_STORE 1
+#define OCN_RK3_WRAPPED_LOADS 2
+#define OCN_RK3_CORRECT_ONLY 4
+int ocn_compute_momentum_tendencies_rk3_flags(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
+                                              double *Gv, double *Gw, const double *Gmu, const double *Gmv, const double *Gmw,
+                                              double *u_out, double *v_out, double *w_out, double dt, double gamma, double zeta,
+                                              int32_t has_zeta, const double *p_correct, double dt_correct, int32_t flags, void *stream);
 /* Which kernel a correction-on-load launch (p_correct != NULL) for this grid takes: *selected = 1 for the one with 32-bit buffer offsets
  * (every field's parent array below 2^31 bytes, halos of at least 3, OCN_TEND_ADDR32 not 0), 0 for the one with 64-bit addresses.
  * Host only: no device memory is touched. */
@@ -431,6 +448,10 @@ int ocn_poisson_create_stretched(ocn_poisson_t *solver, const ocn_grid *grid, in
  * column-kernel length -- the Thomas sweep replaced by its exact spectral twin, cosine transform / division / inverse cosine transform in
  * one column pass (what the reference's FFTBasedPoissonSolver does on such a grid; OCN_POISSON_DCT_Z=0 keeps the sweep) */
 int ocn_poisson_info(ocn_poisson_t solver, int32_t *kind, int32_t *r2c, int32_t *direct_out);
+/* *wraps = 1 when the source-term pass of this handle reads u[i + 1], v[j + 1], w[k + 1] by periodically wrapped indices, i.e. reads no
+ * halo cell of u, v, w: every (Periodic, Periodic, Periodic) handle created without OCN_POISSON_SOURCE_WRAP=0 in the environment.  Same
+ * values as the filled halos hold, bit for bit. */
+int ocn_poisson_source_wraps(ocn_poisson_t solver, int32_t *wraps);
 /* compute_source_term! (src/Models/NonhydrostaticModels/solve_for_pressure.jl:12-17,33-38,57-76) */
 int ocn_poisson_compute_source_term(ocn_poisson_t solver, const double *u, const double *v, const double *w, double dt,
                                     void *stream);
@@ -572,7 +593,12 @@ int ocn_rk3_driver_fields(ocn_rk3_driver_t driver, double **u, double **v, doubl
  * pressure_correct_velocities! of the THIRD stage is not launched either -- the next step's first fused launch applies it on load
  * like stages 1 and 2 (three identical stage boundaries per step, no pressure-correction pass, no halo fill after it).  Between
  * time_step and flush the velocity arrays then hold the uncorrected u*, v*, w*; ocn_rk3_driver_flush applies the correction, fills
- * the halos and completes the tendencies -- the state it leaves is the reference's, bit for bit in strict math. */
+ * the halos and completes the tendencies -- the state it leaves is the reference's, bit for bit in strict math.
+ * On a one-GPU all-periodic box that takes the 32-bit tendency kernel the step also leaves out work nobody reads: the halo fills in front
+ * of the solves (the source pass and the fused launch wrap their indices: between time_step and flush the velocity HALOS are stale), the
+ * and the store of the third launch's G^n; OCN_DRIVER_WRAPPED_LOADS=0 / OCN_DRIVER_SKIP_G_STORE=0 in the environment at creation restore
+ * each.  OCN_DRIVER_FUSED_FLUSH=1 additionally runs the deferred correction and the deferred tendencies of a flush as ONE launch (off by
+ * default).  The state after flush is the same bit for bit whatever the switches. */
 int ocn_rk3_driver_configure(ocn_rk3_driver_t driver, int32_t defer_correction);
 
 /* ---- the same for a model with tracers and the SURVEY 8(f) terms (config 4's term set: WENO5 / UpwindBiased5 advection, FPlane,

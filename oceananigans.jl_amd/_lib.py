@@ -114,6 +114,7 @@ _SIGS = {
     "ocn_compute_momentum_tendencies": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32), _vp],
     "ocn_compute_momentum_tendencies_rk3": [C.POINTER(CGrid)] + [_vp] * 12 + [_dbl, _dbl, _dbl, _i32, _vp, _dbl, C.POINTER(_i32), _vp],
     "ocn_compute_momentum_tendencies_rk3_strips": [C.POINTER(CGrid)] + [_vp] * 12 + [_dbl, _dbl, _dbl, _i32, _vp, _dbl, _vp, _vp, C.c_int64, _vp],
+    "ocn_compute_momentum_tendencies_rk3_flags": [C.POINTER(CGrid)] + [_vp] * 12 + [_dbl, _dbl, _dbl, _i32, _vp, _dbl, _i32, _vp],
     "ocn_momentum_tendencies_addr32": [C.POINTER(CGrid), C.POINTER(_i32)],
     "ocn_compute_tracer_tendency": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32), _vp],
     "ocn_compute_momentum_tendencies_terms": [C.POINTER(CGrid), C.POINTER(CModelTerms), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32), _vp],
@@ -158,6 +159,7 @@ _SIGS = {
     "ocn_poisson_destroy": [_vp],
     "ocn_poisson_create_stretched": [C.POINTER(_vp), C.POINTER(CGrid), _i32, _vp, _vp],
     "ocn_poisson_info": [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)],
+    "ocn_poisson_source_wraps": [_vp, C.POINTER(_i32)],
     "ocn_poisson_compute_source_term": [_vp, _vp, _vp, _vp, _dbl, _vp],
     "ocn_poisson_set_source_term": [_vp, _vp, _vp],
     "ocn_poisson_solve": [_vp, _vp, _vp],

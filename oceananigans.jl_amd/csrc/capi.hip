@@ -233,11 +233,10 @@ int ocn_compute_momentum_tendencies(const ocn_grid *grid, const double *u, const
     return ocn_fast::launch_momentum_tendencies(grid, u, v, w, Gu, Gv, Gw, range, nullptr, as_stream(stream));
 }
 
-int ocn_compute_momentum_tendencies_rk3(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
-                                        double *Gv, double *Gw, const double *Gmu, const double *Gmv, const double *Gmw,
-                                        double *u_out, double *v_out, double *w_out, double dt, double gamma, double zeta,
-                                        int32_t has_zeta, const double *p_correct, double dt_correct, const int32_t *range,
-                                        void *stream)
+static int momentum_tendencies_rk3(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu, double *Gv,
+                                   double *Gw, const double *Gmu, const double *Gmv, const double *Gmw, double *u_out, double *v_out,
+                                   double *w_out, double dt, double gamma, double zeta, int32_t has_zeta, const double *p_correct,
+                                   double dt_correct, const int32_t *range, int32_t flags, void *stream)
 {
     int st = validate_weno(grid);
     if (st != OCN_SUCCESS) return st;
@@ -262,8 +261,33 @@ int ocn_compute_momentum_tendencies_rk3(const ocn_grid *grid, const double *u, c
     fz.Uo[0] = u_out; fz.Uo[1] = v_out; fz.Uo[2] = w_out;
     fz.dt = dt; fz.gamma = gamma; fz.zeta = zeta; fz.on = 1; fz.has_zeta = has_zeta ? 1 : 0;
     fz.pc_p = p_correct; fz.pc_dt = dt_correct; fz.pc_on = p_correct ? 1 : 0;
+    fz.skip_g = (flags & OCN_RK3_SKIP_G_STORE) ? 1 : 0;
+    fz.wrap_uvw = (flags & OCN_RK3_WRAPPED_LOADS) ? 1 : 0;
+    fz.no_step = (flags & OCN_RK3_CORRECT_ONLY) ? 1 : 0;
     if (strict_math(grid)) return ocn_strict::launch_momentum_tendencies(grid, u, v, w, Gu, Gv, Gw, range, &fz, as_stream(stream));
     return ocn_fast::launch_momentum_tendencies(grid, u, v, w, Gu, Gv, Gw, range, &fz, as_stream(stream));
+}
+
+int ocn_compute_momentum_tendencies_rk3(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
+                                        double *Gv, double *Gw, const double *Gmu, const double *Gmv, const double *Gmw,
+                                        double *u_out, double *v_out, double *w_out, double dt, double gamma, double zeta,
+                                        int32_t has_zeta, const double *p_correct, double dt_correct, const int32_t *range,
+                                        void *stream)
+{
+    return momentum_tendencies_rk3(grid, u, v, w, Gu, Gv, Gw, Gmu, Gmv, Gmw, u_out, v_out, w_out, dt, gamma, zeta, has_zeta, p_correct,
+                                   dt_correct, range, 0, stream);
+}
+
+int ocn_compute_momentum_tendencies_rk3_flags(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
+                                              double *Gv, double *Gw, const double *Gmu, const double *Gmv, const double *Gmw,
+                                              double *u_out, double *v_out, double *w_out, double dt, double gamma, double zeta,
+                                              int32_t has_zeta, const double *p_correct, double dt_correct, int32_t flags, void *stream)
+{
+    OCN_REQUIRE(!(flags & ~(OCN_RK3_SKIP_G_STORE | OCN_RK3_WRAPPED_LOADS | OCN_RK3_CORRECT_ONLY)),
+                "ocn_compute_momentum_tendencies_rk3_flags: unknown flag in %d", flags);
+    OCN_REQUIRE(p_correct, "ocn_compute_momentum_tendencies_rk3_flags: the flags belong to the correction-on-load launch (p_correct)");
+    return momentum_tendencies_rk3(grid, u, v, w, Gu, Gv, Gw, Gmu, Gmv, Gmw, u_out, v_out, w_out, dt, gamma, zeta, has_zeta, p_correct,
+                                   dt_correct, nullptr, flags, stream);
 }
 
 int ocn_compute_momentum_tendencies_rk3_strips(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,

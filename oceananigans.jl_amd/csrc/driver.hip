@@ -43,6 +43,15 @@ struct ocn_rk3_driver {
     // the last fused launch also wrote the x strips of its stepped velocities into the communicator's send buffers
     // (ocn_compute_momentum_tendencies_rk3_strips): the next exchange of U is posted without a pack launch
     bool use_strips = false, strips_ready = false;
+    // One GPU, all-periodic, correction on load through the 32-bit kernel (ocn_momentum_tendencies_addr32): work of a step whose result
+    // nobody reads is left out.  Each has its environment switch (= 0 restores the work), read at creation like OCN_CORRECT_ON_LOAD.
+    //   skip_g_store   OCN_DRIVER_SKIP_G_STORE: the third fused launch of a step does not store G^n -- the next step's first launch has no
+    //                  G^- term and overwrites the same buffer without a swap in between, and flush recomputes it (pending)
+    //   wrapped_loads  OCN_DRIVER_WRAPPED_LOADS: no halo fill of u*, v*, w* in front of the solve -- its two readers, the solver's source
+    //                  pass (ocn_poisson_source_wraps) and the next fused launch, wrap their indices instead
+    //   fused_flush    OCN_DRIVER_FUSED_FLUSH=1 (off by default: not yet measured against the two passes it replaces): the deferred
+    //                  correction and the deferred tendencies of a flush in ONE launch
+    bool skip_g_store = false, wrapped_loads = false, fused_flush = false;
 };
 
 namespace {
@@ -90,7 +99,7 @@ int solve(ocn_rk3_driver *d, double stage_dt, void *stream)
 
 // update_state! + the next rk3_substep! in one launch, then the two velocity sets trade places
 int fused_launch(ocn_rk3_driver *d, double dt, double gamma, double zeta, int has_zeta, const double *p_correct, double dt_correct,
-                 void *stream)
+                 int32_t flags, void *stream)
 {
     int st;
     d->strips_ready = false;
@@ -103,6 +112,10 @@ int fused_launch(ocn_rk3_driver *d, double dt, double gamma, double zeta, int ha
                                                         d->Gm[2], d->A[0], d->A[1], d->A[2], dt, gamma, zeta, has_zeta, p_correct, dt_correct,
                                                         sw, se, per_field, stream);
         d->strips_ready = st == OCN_SUCCESS;
+    } else if (flags && p_correct) {
+        st = ocn_compute_momentum_tendencies_rk3_flags(&d->grid, d->U[0], d->U[1], d->U[2], d->Gn[0], d->Gn[1], d->Gn[2], d->Gm[0], d->Gm[1],
+                                                       d->Gm[2], d->A[0], d->A[1], d->A[2], dt, gamma, zeta, has_zeta, p_correct, dt_correct,
+                                                       flags, stream);
     } else {
         st = ocn_compute_momentum_tendencies_rk3(&d->grid, d->U[0], d->U[1], d->U[2], d->Gn[0], d->Gn[1], d->Gn[2], d->Gm[0], d->Gm[1],
                                                  d->Gm[2], d->A[0], d->A[1], d->A[2], dt, gamma, zeta, has_zeta, p_correct, dt_correct,
@@ -122,9 +135,10 @@ void swap_tendencies(ocn_rk3_driver *d)  // cache_previous_tendencies! (store_te
 // The projection of a stage up to (not including) the correction, for a launch that corrects on load: halos of the uncorrected
 // velocities, pressure solve and -- on a slab -- the pressure planes of the neighbours.  On a slab the exchange of u*, v*, w* is posted
 // BEFORE the solve (only the plane the divergence reads is waited for) and flies under it on the communication stream.
+// wrapped_loads: no fill at all -- the halos of U stay stale until the next fill_velocities (flush), and nothing reads them before.
 int project_for_load(ocn_rk3_driver *d, double stage_dt, void *stream)
 {
-    int st = ocn_fill_halo_regions(&d->grid, d->U, LOCS, 3, 1, stream);
+    int st = d->wrapped_loads ? OCN_SUCCESS : ocn_fill_halo_regions(&d->grid, d->U, LOCS, 3, 1, stream);
     if (st != OCN_SUCCESS) return st;
     if (d->comm) {
         st = ocn_halo_exchange_plane(d->comm, &d->grid, d->U[0], OCN_LOC_FCC, 0, stream);  // u[nx+1] <- east neighbour's u[1]
@@ -163,20 +177,22 @@ int project_and_correct(ocn_rk3_driver *d, double stage_dt, bool solve_too, void
     return fill_velocities(d, 0, stream);
 }
 
-// everything between two substeps (runge_kutta_3.jl:103-118)
-int project_and_advance(ocn_rk3_driver *d, double dt, double stage_dt, double gamma_next, double zeta_next, void *stream)
+// everything between two substeps (runge_kutta_3.jl:103-118).  last_of_step: the launch is the last one of a step that ends with the
+// tendencies pending, so its G^n is dead (skip_g_store).
+int project_and_advance(ocn_rk3_driver *d, double dt, double stage_dt, double gamma_next, double zeta_next, bool last_of_step, void *stream)
 {
     int st;
     if (d->correct_on_load) {
         st = project_for_load(d, stage_dt, stream);
         if (st != OCN_SUCCESS) return st;
         swap_tendencies(d);
-        return fused_launch(d, dt, gamma_next, zeta_next, 1, d->p, stage_dt, stream);
+        const int32_t flags = (d->wrapped_loads ? OCN_RK3_WRAPPED_LOADS : 0) | (last_of_step && d->skip_g_store ? OCN_RK3_SKIP_G_STORE : 0);
+        return fused_launch(d, dt, gamma_next, zeta_next, 1, d->p, stage_dt, flags, stream);
     }
     st = project_and_correct(d, stage_dt, true, stream);
     if (st != OCN_SUCCESS) return st;
     swap_tendencies(d);
-    return fused_launch(d, dt, gamma_next, zeta_next, 1, nullptr, 0.0, stream);
+    return fused_launch(d, dt, gamma_next, zeta_next, 1, nullptr, 0.0, 0, stream);
 }
 }  // namespace
 
@@ -265,6 +281,21 @@ static int driver_create(ocn_rk3_driver_t *out, const ocn_grid *grid, double *u,
     d->use_strips = comm && d->correct_on_load && grid->Nx >= 2 * grid->Hx && es && es[0] == '1';
     const char *dc = std::getenv("OCN_DRIVER_DEFER_CORRECTION");
     d->defer_correction = d->correct_on_load && !(dc && dc[0] == '0');
+    // dead work left out (see the struct): the fused launches of a one-GPU box through the 32-bit kernel
+    int32_t addr32 = 0, wraps = 0;
+    if (!comm && d->correct_on_load) {
+        st = ocn_momentum_tendencies_addr32(grid, &addr32);
+        if (st == OCN_SUCCESS) st = ocn_poisson_source_wraps(d->solver, &wraps);
+        if (st != OCN_SUCCESS) {
+            ocn_rk3_driver_destroy(d);
+            return st;
+        }
+    }
+    auto enabled = [](const char *name) { const char *v = std::getenv(name); return !(v && v[0] == '0'); };
+    d->skip_g_store = addr32 && enabled("OCN_DRIVER_SKIP_G_STORE");
+    d->wrapped_loads = addr32 && wraps && enabled("OCN_DRIVER_WRAPPED_LOADS");
+    const char *ff = std::getenv("OCN_DRIVER_FUSED_FLUSH");
+    d->fused_flush = addr32 && ff && ff[0] == '1';
     st = fill_velocities(d, 0, stream);  // update_state!(model; compute_tendencies = false) of the constructor
     if (st != OCN_SUCCESS) {
         ocn_rk3_driver_destroy(d);
@@ -313,15 +344,16 @@ extern "C" int ocn_rk3_driver_time_step(ocn_rk3_driver_t d, double dt, void *str
     // ---- first stage
     if (d->pending) {
         const bool pc = d->correction_pending;  // the previous step's third-stage correction rides on this launch's loads
-        st = fused_launch(d, dt, g1, 0.0, 0, pc ? d->p : nullptr, pc ? d->correction_dt : 0.0, stream);
+        st = fused_launch(d, dt, g1, 0.0, 0, pc ? d->p : nullptr, pc ? d->correction_dt : 0.0,
+                          pc && d->wrapped_loads ? OCN_RK3_WRAPPED_LOADS : 0, stream);
         d->correction_pending = false;
     } else {
         st = ocn_rk3_substep(&d->grid, 3, d->U, d->Gn, d->Gm, LOCS, dt, g1, 0.0, 0, stream);
     }
     if (st != OCN_SUCCESS) return st;
-    st = project_and_advance(d, dt, first_stage_dt, g2, z2, stream);   // ... ends with the second substep
+    st = project_and_advance(d, dt, first_stage_dt, g2, z2, false, stream);  // ... ends with the second substep
     if (st != OCN_SUCCESS) return st;
-    st = project_and_advance(d, dt, second_stage_dt, g3, z3, stream);  // ... ends with the third substep
+    st = project_and_advance(d, dt, second_stage_dt, g3, z3, true, stream);  // ... ends with the third substep (d->pending = true below)
     if (st != OCN_SUCCESS) return st;
     // ---- third stage: projection; its compute_tendencies! is fused into the next step's first substep, and so is -- when the
     //      correction is deferred -- pressure_correct_velocities! itself
@@ -342,6 +374,20 @@ extern "C" int ocn_rk3_driver_time_step(ocn_rk3_driver_t d, double dt, void *str
 extern "C" int ocn_rk3_driver_flush(ocn_rk3_driver_t d, void *stream)
 {
     OCN_REQUIRE(d, "ocn_rk3_driver_flush: null driver");
+    if (d->correction_pending && d->pending && d->fused_flush) {
+        // both in one pass: the launch corrects on load, stores the corrected velocities into the other set and G^n of them; then the p
+        // halos a caller sees after the separate passes (fill_pressure) and the velocity halos
+        int st = ocn_compute_momentum_tendencies_rk3_flags(&d->grid, d->U[0], d->U[1], d->U[2], d->Gn[0], d->Gn[1], d->Gn[2], nullptr, nullptr,
+                                                           nullptr, d->A[0], d->A[1], d->A[2], 0.0, 0.0, 0.0, 0, d->p, d->correction_dt,
+                                                           OCN_RK3_CORRECT_ONLY | (d->wrapped_loads ? OCN_RK3_WRAPPED_LOADS : 0), stream);
+        if (st != OCN_SUCCESS) return st;
+        for (int f = 0; f < 3; ++f) std::swap(d->U[f], d->A[f]);
+        d->correction_pending = d->pending = false;
+        st = fill_pressure(d, stream);
+        if (st != OCN_SUCCESS) return st;
+        st = fill_velocities(d, 0, stream);
+        if (st != OCN_SUCCESS) return st;
+    }
     if (d->correction_pending) {  // the deferred third-stage correction: p halos, pressure_correct_velocities!, velocity halos
         int st = project_and_correct(d, d->correction_dt, false, stream);
         if (st != OCN_SUCCESS) return st;

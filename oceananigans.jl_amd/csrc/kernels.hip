@@ -1326,13 +1326,15 @@ __device__ __forceinline__ double dzF(const GridDev &g, int k) { return g.dzf ? 
 // divᶜᶜᶜ (divergence_operators.jl:16-19): 1/V * (δx(Ax u) + δy(Ay v) + δz(Az w)); δ along Flat is 0
 __device__ __forceinline__ double div_ccc(const GridDev &g, const double *__restrict__ u, const double *__restrict__ v,
                                           const double *__restrict__ w, const Lay &Lu, const Lay &Lv, const Lay &Lw, int i,
-                                          int j, int k)
+                                          int j, int k, int wrap = 0)
 {
     const double dzc = dzC(g, k);
     const double Ax = g.dy * dzc, Ay = g.dx * dzc, Az = g.dx * g.dy;
-    const double dxu = (g.tx == OCN_FLAT) ? 0.0 : Ax * u[at(Lu, i + 1, j, k)] - Ax * u[at(Lu, i, j, k)];
-    const double dyv = (g.ty == OCN_FLAT) ? 0.0 : Ay * v[at(Lv, i, j + 1, k)] - Ay * v[at(Lv, i, j, k)];
-    const double dzw = (g.tz == OCN_FLAT) ? 0.0 : Az * w[at(Lw, i, j, k + 1)] - Az * w[at(Lw, i, j, k)];
+    // wrap (all-periodic grids): the east / north / top neighbour of the last cell is the first one -- the value its halo image holds
+    const int ie = (wrap && i == g.Nx) ? 1 : i + 1, jn = (wrap && j == g.Ny) ? 1 : j + 1, kt = (wrap && k == g.Nz) ? 1 : k + 1;
+    const double dxu = (g.tx == OCN_FLAT) ? 0.0 : Ax * u[at(Lu, ie, j, k)] - Ax * u[at(Lu, i, j, k)];
+    const double dyv = (g.ty == OCN_FLAT) ? 0.0 : Ay * v[at(Lv, i, jn, k)] - Ay * v[at(Lv, i, j, k)];
+    const double dzw = (g.tz == OCN_FLAT) ? 0.0 : Az * w[at(Lw, i, j, kt)] - Az * w[at(Lw, i, j, k)];
     return (1 / (Az * dzc)) * ((dxu + dyv) + dzw);
 }
 
@@ -1345,14 +1347,14 @@ __device__ __forceinline__ int dct_perm(int q, int N) { return (q & 1) ? N - 1 -
 template <int OUT>
 __global__ __launch_bounds__(256) void source_term_kernel(GridDev g, const double *__restrict__ u, const double *__restrict__ v,
                                                           const double *__restrict__ w, double dt, double *__restrict__ out,
-                                                          long long ld1, long long ld2, int perm_dim)
+                                                          long long ld1, long long ld2, int perm_dim, int wrap)
 {
     const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x;
     const int j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
     const int k = 1 + blockIdx.z;
     if (i > g.Nx || j > g.Ny) return;
     const Lay Lu = make_lay(g, OCN_LOC_FCC), Lv = make_lay(g, OCN_LOC_CFC), Lw = make_lay(g, OCN_LOC_CCF);
-    const double d = div_ccc(g, u, v, w, Lu, Lv, Lw, i, j, k);
+    const double d = div_ccc(g, u, v, w, Lu, Lv, Lw, i, j, k, wrap);
     // perm_dim >= 0: the value of point s along that dimension is stored at the position the even / odd permutation of the FFT-based cosine
     // transform reads it from (index_permutations.jl:38-90: the gather pass of the general solver folded into this store)
     int c[3] = {i - 1, j - 1, k - 1};
@@ -1369,17 +1371,17 @@ __global__ __launch_bounds__(256) void source_term_kernel(GridDev g, const doubl
 }
 
 int launch_source_term(const ocn_grid *grid, const double *u, const double *v, const double *w, double dt, int out_mode,
-                       double *out, long long ld1, long long ld2, hipStream_t stream, int perm_dim)
+                       double *out, long long ld1, long long ld2, hipStream_t stream, int perm_dim, int wrap)
 {
     GridDev g = to_dev(*grid);
     dim3 block(64, 4, 1);
     dim3 nb((g.Nx + 63) / 64, (g.Ny + 3) / 4, g.Nz);
     switch (out_mode) {
-        case 0: hipLaunchKernelGGL(source_term_kernel<0>, nb, block, 0, stream, g, u, v, w, dt, out, ld1, ld2, perm_dim); break;
-        case 1: hipLaunchKernelGGL(source_term_kernel<1>, nb, block, 0, stream, g, u, v, w, dt, out, ld1, ld2, perm_dim); break;
-        case 2: hipLaunchKernelGGL(source_term_kernel<2>, nb, block, 0, stream, g, u, v, w, dt, out, ld1, ld2, perm_dim); break;
-        case 3: hipLaunchKernelGGL(source_term_kernel<3>, nb, block, 0, stream, g, u, v, w, dt, out, ld1, ld2, perm_dim); break;
-        default: hipLaunchKernelGGL(source_term_kernel<4>, nb, block, 0, stream, g, u, v, w, dt, out, ld1, ld2, perm_dim); break;
+        case 0: hipLaunchKernelGGL(source_term_kernel<0>, nb, block, 0, stream, g, u, v, w, dt, out, ld1, ld2, perm_dim, wrap); break;
+        case 1: hipLaunchKernelGGL(source_term_kernel<1>, nb, block, 0, stream, g, u, v, w, dt, out, ld1, ld2, perm_dim, wrap); break;
+        case 2: hipLaunchKernelGGL(source_term_kernel<2>, nb, block, 0, stream, g, u, v, w, dt, out, ld1, ld2, perm_dim, wrap); break;
+        case 3: hipLaunchKernelGGL(source_term_kernel<3>, nb, block, 0, stream, g, u, v, w, dt, out, ld1, ld2, perm_dim, wrap); break;
+        default: hipLaunchKernelGGL(source_term_kernel<4>, nb, block, 0, stream, g, u, v, w, dt, out, ld1, ld2, perm_dim, wrap); break;
     }
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;

@@ -152,6 +152,16 @@ struct FuseArgs {
     // the exchange needs no pack launch; only interior rows are written -- the receiver wraps (ocn_halo_exchange_begin_packed)
     double *strip_w, *strip_e;
     long long strip_field;
+    // The three below are taken by momentum_tendencies_pc32 only (all zero: today's launch).
+    // skip_g: G is computed and used by the substep but not stored -- for a caller that knows nobody reads it (the last launch of a step of
+    // ocn_rk3_driver_time_step: the next launch has no G⁻ term and overwrites the same buffer).  A permission: other kernels store G.
+    int skip_g;
+    // wrap_uvw: u, v, w are addressed like p, by periodically wrapped indices: their halos are never read (no halo fill in front of the
+    // launch).  Periodic x only; required, not a permission: a launch that cannot honour it is an error.
+    int wrap_uvw;
+    // no_step: Uo = the corrected velocity itself, no increment (ocn_rk3_driver_flush: pressure_correct_velocities! and compute_tendencies!
+    // in one pass).  Not U + 0 * G: that loses the sign of -0.0 and turns a non-finite G into a non-finite velocity.  Required as well.
+    int no_step;
 };
 
 // device-side copy of ocn_model_terms (physics.hip)

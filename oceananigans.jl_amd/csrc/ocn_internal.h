@@ -40,7 +40,7 @@ int wait_stream(hipStream_t stream, double seconds, const char *who);
 int launch_hydrostatic_pressure(const ocn_grid *grid, const TermsDev &t, double *pHY, hipStream_t stream, const int32_t *irange = nullptr);
 int launch_stepper(const ocn_grid *grid, const StepTuple &st, int mode, double dt, double c1, double c2, hipStream_t stream);
 int launch_source_term(const ocn_grid *grid, const double *u, const double *v, const double *w, double dt, int out_mode,
-                       double *out, long long ld1, long long ld2, hipStream_t stream, int perm_dim = -1);
+                       double *out, long long ld1, long long ld2, hipStream_t stream, int perm_dim = -1, int wrap = 0);
 int launch_set_source(int Nx, int Ny, int Nz, const double *R, const double *dzc, int Hz, double *out, int complex_out,
                       long long ld1, long long ld2, hipStream_t stream);
 int launch_spectral_solve(int nxh, int Ny, int Nz, const double *lx, const double *ly, const double *lz, double *b,
@@ -134,7 +134,7 @@ bool rowfft_supported(int Nx);
 void rowfft_twiddles(int Nx, std::vector<double> &twM, std::vector<double> &twN);
 int launch_rowfft(const ocn_grid *grid, int inverse, const double *u, const double *v, const double *w, const double *real_in,
                   double dt, double *spec, double *p, const double *twM, const double *twN, double scale, hipStream_t stream,
-                  int scale_dz = 0);
+                  int scale_dz = 0, int wrap = 0);
 int launch_halo_pack_x(const ocn_grid *grid, const double *field, int loc, double *west, double *east, int unpack, hipStream_t stream);
 int launch_transpose(int mode, int nx, int Ny, int Nz, int R, const double *src, double *dst, hipStream_t stream);
 

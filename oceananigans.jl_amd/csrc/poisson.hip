@@ -149,6 +149,9 @@ struct ocn_poisson {
     bool source_in_rhs = false; // custom_xy: the source was given as a real array (set_source_term!) and still needs its x transform
     bool direct_out = true;  // r2c path: inverse transform writes straight into the haloed pressure interior
     bool source_set = false;
+    // all-periodic grid: the source pass reads u[Nx + 1], v[Ny + 1], w[Nz + 1] as u[1], v[1], w[1], so the velocity halos need no fill in
+    // front of the solve (ocn_poisson_source_wraps; OCN_POISSON_SOURCE_WRAP=0 at creation restores the halo reads)
+    bool source_wrap = false;
     double shift = 0.0;         // ocn_poisson_solve_shifted: (∇² + m) ϕ = b for this solve
     bool shifted = false;
     // kind 2: FFTBasedPoissonSolver for ANY regular (Periodic | Bounded | Flat)^3 topology: separable transforms evaluated as direct sums
@@ -964,6 +967,10 @@ static int poisson_create_impl(ocn_poisson_t *out, const ocn_grid *grid, bool fo
     ensure_rocfft();
     ocn_poisson *s = new ocn_poisson();
     s->grid = *grid;
+    {
+        const char *ew = std::getenv("OCN_POISSON_SOURCE_WRAP");
+        s->source_wrap = grid->tx == OCN_PERIODIC && grid->ty == OCN_PERIODIC && grid->tz == OCN_PERIODIC && !(ew && ew[0] == '0');
+    }
     const int Nx = grid->Nx, Ny = grid->Ny, Nz = grid->Nz, Hz = grid->Hz;
     const char *env = std::getenv("OCN_POISSON_C2C");
     s->c2c = force_c2c || (env && env[0] == '1');
@@ -1401,6 +1408,13 @@ extern "C" int ocn_poisson_info(ocn_poisson_t s, int32_t *kind, int32_t *r2c, in
     return OCN_SUCCESS;
 }
 
+extern "C" int ocn_poisson_source_wraps(ocn_poisson_t s, int32_t *wraps)
+{
+    OCN_REQUIRE(s && wraps, "ocn_poisson_source_wraps: null argument");
+    *wraps = s->source_wrap ? 1 : 0;
+    return OCN_SUCCESS;
+}
+
 extern "C" int ocn_poisson_compute_source_term(ocn_poisson_t s, const double *u, const double *v, const double *w, double dt,
                                                void *stream)
 {
@@ -1432,15 +1446,17 @@ extern "C" int ocn_poisson_compute_source_term(ocn_poisson_t s, const double *u,
     }
     if (s->custom_xy) {  // K8 fused with the forward x transform: the divergence goes straight into the half spectrum
         st = ocn::launch_rowfft(g, 0, u, v, w, nullptr, dt, s->spec, nullptr, s->twMx, s->twNx, 1.0, ocn::as_stream(stream),
-                                (s->custom_tri && !s->dct_z) ? 1 : 0);  // (Δzᶜ rides on the tridiagonal system only)
+                                (s->custom_tri && !s->dct_z) ? 1 : 0, s->source_wrap);  // (Δzᶜ rides on the tridiagonal system only)
         s->source_in_rhs = false;
         s->source_set = (st == OCN_SUCCESS);
         return st;
     }
     if (s->c2c)
-        st = ocn::launch_source_term(g, u, v, w, dt, s->kind == 1 ? 2 : 1, s->spec, g->Nx, (long long)g->Nx * g->Ny, ocn::as_stream(stream));
+        st = ocn::launch_source_term(g, u, v, w, dt, s->kind == 1 ? 2 : 1, s->spec, g->Nx, (long long)g->Nx * g->Ny, ocn::as_stream(stream), -1,
+                                     s->source_wrap);
     else
-        st = ocn::launch_source_term(g, u, v, w, dt, s->kind == 1 ? 4 : 3, s->rhs, g->Nx, (long long)g->Nx * g->Ny, ocn::as_stream(stream));
+        st = ocn::launch_source_term(g, u, v, w, dt, s->kind == 1 ? 4 : 3, s->rhs, g->Nx, (long long)g->Nx * g->Ny, ocn::as_stream(stream), -1,
+                                     s->source_wrap);
     s->source_set = (st == OCN_SUCCESS);
     return st;
 }

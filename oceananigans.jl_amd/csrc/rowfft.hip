@@ -138,6 +138,7 @@ struct RowFFTArgs {
     long long nrows;          // Ny * Nz
     double scale;             // inverse: applied to the output
     int scale_dz;             // source mode: rhs = (Δzᶜ div) / dt, the Fourier-tridiagonal form (solve_for_pressure.jl:33-38)
+    int wrap;                 // source mode, all-periodic grid: u[Nx + 1], v[Ny + 1], w[Nz + 1] are read as u[1], v[1], w[1] (no halo is touched)
 };
 
 // ---- forward: rows of div(u,v,w)/dt -> half spectrum ------------------------------------------------------------------
@@ -160,6 +161,8 @@ __global__ __launch_bounds__(RB *(M / 8)) void rowfft_source_r2c_kernel(RowFFTAr
     const double dzc = g.dzc ? uniform_load(g.dzc, k + g.Hz - 1) : g.dz;
     const double Ax = g.dy * dzc, Ay = g.dx * dzc, Az = g.dx * g.dy, rV = 1 / (Az * dzc);
     const bool flatz = g.tz == OCN_FLAT;
+    // distances to the north / top neighbour's row and to u[i + 2] of the row's last pair: the periodic image inside the interior with wrap
+    const long long sn = (a.wrap && j == g.Ny) ? -(long long)(g.Ny - 1) * L.s2 : L.s2, st = (a.wrap && k == g.Nz) ? -(long long)(g.Nz - 1) * L.s3 : L.s3;
     cplx x[8];
     if (a.u != nullptr) {
     // The 11 values of every pair of cells are LOADED for four pairs at a time (44 doubles in flight per thread) before any divergence is
@@ -172,10 +175,10 @@ __global__ __launch_bounds__(RB *(M / 8)) void rowfft_source_r2c_kernel(RowFFTAr
         for (int q = 0; q < 4; ++q) {
             const int i = 2 * (t + T * (4 * h + q)) + 1;
             const long long o = at(L, i, j, k);
-            uu[q][0] = a.u[o]; uu[q][1] = a.u[o + 1]; uu[q][2] = a.u[o + 2];
-            vv[q][0] = a.v[o]; vv[q][1] = a.v[o + 1]; vv[q][2] = a.v[o + L.s2]; vv[q][3] = a.v[o + L.s2 + 1];
+            uu[q][0] = a.u[o]; uu[q][1] = a.u[o + 1]; uu[q][2] = a.u[(a.wrap && i == N - 1) ? o + 2 - N : o + 2];
+            vv[q][0] = a.v[o]; vv[q][1] = a.v[o + 1]; vv[q][2] = a.v[o + sn]; vv[q][3] = a.v[o + sn + 1];
             if (!flatz) {
-                ww[q][0] = a.w[o]; ww[q][1] = a.w[o + 1]; ww[q][2] = a.w[o + L.s3]; ww[q][3] = a.w[o + L.s3 + 1];
+                ww[q][0] = a.w[o]; ww[q][1] = a.w[o + 1]; ww[q][2] = a.w[o + st]; ww[q][3] = a.w[o + st + 1];
             } else {
                 ww[q][0] = ww[q][1] = ww[q][2] = ww[q][3] = 0.0;
             }
@@ -312,10 +315,11 @@ static int launch_m(int inverse, const RowFFTArgs &a, hipStream_t stream)
 
 int launch_rowfft(const ocn_grid *grid, int inverse, const double *u, const double *v, const double *w, const double *real_in,
                   double dt, double *spec, double *p, const double *twM, const double *twN, double scale, hipStream_t stream,
-                  int scale_dz)
+                  int scale_dz, int wrap)
 {
     RowFFTArgs a;
     a.scale_dz = scale_dz;
+    a.wrap = wrap;
     a.g = to_dev(*grid);
     a.u = u; a.v = v; a.w = w; a.real_in = real_in; a.dt = dt; a.spec = spec; a.p = p; a.twM = twM; a.twN = twN;
     a.nrows = (long long)grid->Ny * grid->Nz;

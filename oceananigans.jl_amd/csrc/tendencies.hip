@@ -681,9 +681,22 @@ __device__ __forceinline__ double substep(double U, double inc)
     return U + inc;
 }
 
-template <int TX, int TY, int W, bool Z>
+// Z: the substep has a G⁻ term.  WG: G is stored (false: the store nobody reads is left out, FuseArgs::skip_g).  WR: u, v, w are read
+// through the wrapped column / plane offsets of p instead of their own, so their halos are never touched (FuseArgs::wrap_uvw; every
+// offset involved is loop invariant or already formed per plane for p).  STEP: false stores the corrected velocity itself as U_out
+// (FuseArgs::no_step).
+// u - ((p - p⁻) / h) dt with every operation rounded on its own, whatever the contraction mode (pressure_correct_kernel, kernels.hip)
+__device__ __forceinline__ double corrected_exact(double raw, double d, double h, double dt)
+{
+    double t = (d / h) * dt;
+    asm volatile("" : "+v"(t));
+    return raw - t;
+}
+
+template <int TX, int TY, int W, bool Z, bool WG = true, bool WR = false, bool STEP = true>
 __global__ __launch_bounds__(TX *TY, W) void momentum_tendencies_pc32(PcArgs a)
 {
+    static_assert(STEP || !Z, "the store of the corrected velocity has no substep");
     constexpr int P = OCN_PERIODIC;
     constexpr int LX = TX + 5, LY = TY + 5, NT = TX * TY;
     constexpr int LXP = LX + (TX == 17 ? OCN_NARROW_PAD : 0);
@@ -719,17 +732,21 @@ __global__ __launch_bounds__(TX *TY, W) void momentum_tendencies_pc32(PcArgs a)
                                  rp = field_rsrc(a.p, a.bytes);
     const unsigned own = col(i, j);
     const unsigned oC = col(wrx(i), wrp(j, Ny)), oW = col(wrx(i - 1), wrp(j, Ny)), oS = col(wrx(i), wrp(j - 1, Ny));
+    // where u, v, w are LOADED from: their own column and plane (halos valid), or the wrapped ones of p (WR); stores go to own / pl
+    const unsigned lown = WR ? oC : own;
+    auto lpl = [&](int kk) { return WR ? zz(kk) : pl(kk); };
 
     const double pcdt = a.pcdt, hx = a.hx, hy = a.hy, hz = a.hz;
     (void)pcdt;
 #if OCN_STRICT
 #define OCN_PC_APPLY(raw, d, h) ((raw) - ((d) / (h)) * pcdt)
 #else
-#define OCN_PC_APPLY(raw, d, h) __builtin_fma(-(d), h, raw)
+    // (!STEP: the velocity this launch stores is the one pressure_correct_kernel would have stored: its expression, uncontracted)
+#define OCN_PC_APPLY(raw, d, h) (STEP ? __builtin_fma(-(d), h, raw) : corrected_exact(raw, d, h, pcdt))
 #endif
-    auto own_u = [&](int kk) { return OCN_PC_APPLY(bload(ru, own, pl(kk)), bload(rp, oC, zz(kk)) - bload(rp, oW, zz(kk)), hx); };
-    auto own_v = [&](int kk) { return OCN_PC_APPLY(bload(rv, own, pl(kk)), bload(rp, oC, zz(kk)) - bload(rp, oS, zz(kk)), hy); };
-    auto own_w = [&](int kk) { return OCN_PC_APPLY(bload(rw, own, pl(kk)), bload(rp, oC, zz(kk)) - bload(rp, oC, zz(kk - 1)), hz); };
+    auto own_u = [&](int kk) { return OCN_PC_APPLY(bload(ru, lown, lpl(kk)), bload(rp, oC, zz(kk)) - bload(rp, oW, zz(kk)), hx); };
+    auto own_v = [&](int kk) { return OCN_PC_APPLY(bload(rv, lown, lpl(kk)), bload(rp, oC, zz(kk)) - bload(rp, oS, zz(kk)), hy); };
+    auto own_w = [&](int kk) { return OCN_PC_APPLY(bload(rw, lown, lpl(kk)), bload(rp, oC, zz(kk)) - bload(rp, oC, zz(kk - 1)), hz); };
 
     // static ring assignment (as in momentum_tendencies_tiled)
     int rcx[RPT], rcy[RPT];
@@ -752,16 +769,16 @@ __global__ __launch_bounds__(TX *TY, W) void momentum_tendencies_pc32(PcArgs a)
         if (!ron[s]) { cx = 0; cy = 0; }
         rcx[s] = cx; rcy[s] = cy;
         const int gi = min(ti0 - 3 + cx, imax), gj = min(tj0 - 3 + cy, jmax);
-        roff[s] = col(gi, gj);
         rpc[s] = col(wrx(gi), wrp(gj, Ny));
+        roff[s] = WR ? rpc[s] : col(gi, gj);
         // the westmost halo column of u on a slab (gi = 1 - Hx) was corrected by its owner (p[-Hx] is not here): zero gradient
         rpw[s] = (xhalo && gi - 1 < 1 - a.Hx) ? rpc[s] : col(wrx(gi - 1), wrp(gj, Ny));
         rps[s] = col(wrx(gi), wrp(gj - 1, Ny));
     }
-    auto ring_u = [&](int s, int kk) { return OCN_PC_APPLY(bload(ru, roff[s], pl(kk)), bload(rp, rpc[s], zz(kk)) - bload(rp, rpw[s], zz(kk)), hx); };
-    auto ring_v = [&](int s, int kk) { return OCN_PC_APPLY(bload(rv, roff[s], pl(kk)), bload(rp, rpc[s], zz(kk)) - bload(rp, rps[s], zz(kk)), hy); };
+    auto ring_u = [&](int s, int kk) { return OCN_PC_APPLY(bload(ru, roff[s], lpl(kk)), bload(rp, rpc[s], zz(kk)) - bload(rp, rpw[s], zz(kk)), hx); };
+    auto ring_v = [&](int s, int kk) { return OCN_PC_APPLY(bload(rv, roff[s], lpl(kk)), bload(rp, rpc[s], zz(kk)) - bload(rp, rps[s], zz(kk)), hy); };
     auto ring_w = [&](int s, int kk) {
-        return OCN_PC_APPLY(bload(rw, roff[s], pl(kk)), bload(rp, rpc[s], zz(kk)) - bload(rp, rpc[s], zz(kk - 1)), hz);
+        return OCN_PC_APPLY(bload(rw, roff[s], lpl(kk)), bload(rp, rpc[s], zz(kk)) - bload(rp, rpc[s], zz(kk - 1)), hz);
     };
 
     double zu[6], zv[6], zw[6];
@@ -826,19 +843,20 @@ __global__ __launch_bounds__(TX *TY, W) void momentum_tendencies_pc32(PcArgs a)
         // ---- prefetch the next plane's corrected values, re-using last plane's pressure values (6 p loads instead of 8)
         double zu_n, zv_n, zw_n;
         if (k < k_end) {
-            const unsigned o4 = zz(k + 4), o1 = zz(k + 1), o2 = zz(k + 2), s4 = pl(k + 4);
+            const unsigned o4 = zz(k + 4), o1 = zz(k + 1), o2 = zz(k + 2);
+            const unsigned s4 = WR ? o4 : pl(k + 4), s1 = WR ? o1 : pl(k + 1), s2 = WR ? o2 : pl(k + 2);  // planes of u, v, w
             const double pc4 = bload(rp, oC, o4), pw4 = bload(rp, oW, o4), ps4 = bload(rp, oS, o4);
-            zu_n = OCN_PC_APPLY(bload(ru, own, s4), pc4 - pw4, hx);
-            zv_n = OCN_PC_APPLY(bload(rv, own, s4), pc4 - ps4, hy);
-            zw_n = OCN_PC_APPLY(bload(rw, own, s4), pc4 - pc_prev, hz);
+            zu_n = OCN_PC_APPLY(bload(ru, lown, s4), pc4 - pw4, hx);
+            zv_n = OCN_PC_APPLY(bload(rv, lown, s4), pc4 - ps4, hy);
+            zw_n = OCN_PC_APPLY(bload(rw, lown, s4), pc4 - pc_prev, hz);
             pc_prev = pc4;
 #pragma unroll
             for (int s = 0; s < RPT; ++s)
                 if (ron[s]) {
                     const double pr1 = rp_prev[s], pr2 = bload(rp, rpc[s], o2);
-                    nu[s] = OCN_PC_APPLY(bload(ru, roff[s], pl(k + 1)), pr1 - bload(rp, rpw[s], o1), hx);
-                    nv[s] = OCN_PC_APPLY(bload(rv, roff[s], pl(k + 1)), pr1 - bload(rp, rps[s], o1), hy);
-                    nw[s] = OCN_PC_APPLY(bload(rw, roff[s], pl(k + 2)), pr2 - pr1, hz);
+                    nu[s] = OCN_PC_APPLY(bload(ru, roff[s], s1), pr1 - bload(rp, rpw[s], o1), hx);
+                    nv[s] = OCN_PC_APPLY(bload(rv, roff[s], s1), pr1 - bload(rp, rps[s], o1), hy);
+                    nw[s] = OCN_PC_APPLY(bload(rw, roff[s], s2), pr2 - pr1, hz);
                     rp_prev[s] = pr2;
                 }
         }
@@ -918,18 +936,18 @@ __global__ __launch_bounds__(TX *TY, W) void momentum_tendencies_pc32(PcArgs a)
             const int e = tid + 1, n = tid + TX;
             {
                 double G = -(rV * (((ex[0][e] - ex[0][tid]) + (ex[4][n] - ex[4][tid])) + (fwu_top - fwu_bot)));
-                gstore(G, plane_of(a.G[0], sk), own);
-                gstore(substep(zu[2], Z ? a.dt * (a.gamma * G + a.zeta * gmu) : a.dtg * G), plane_of(a.Uo[0], sk), own);
+                if (WG) gstore(G, plane_of(a.G[0], sk), own);
+                gstore(STEP ? substep(zu[2], Z ? a.dt * (a.gamma * G + a.zeta * gmu) : a.dtg * G) : zu[2], plane_of(a.Uo[0], sk), own);
             }
             {
                 double G = -(rV * (((ex[1][e] - ex[1][tid]) + (ex[3][n] - ex[3][tid])) + (fwv_top - fwv_bot)));
-                gstore(G, plane_of(a.G[1], sk), own);
-                gstore(substep(zv[2], Z ? a.dt * (a.gamma * G + a.zeta * gmv) : a.dtg * G), plane_of(a.Uo[1], sk), own);
+                if (WG) gstore(G, plane_of(a.G[1], sk), own);
+                gstore(STEP ? substep(zv[2], Z ? a.dt * (a.gamma * G + a.zeta * gmv) : a.dtg * G) : zv[2], plane_of(a.Uo[1], sk), own);
             }
             {
                 double G = -(rV * (((ex[2][e] - ex[2][tid]) + (ex[5][n] - ex[5][tid])) + (fww - fww_prev)));
-                gstore(G, plane_of(a.G[2], sk), own);
-                gstore(substep(zw[2], Z ? a.dt * (a.gamma * G + a.zeta * gmw) : a.dtg * G), plane_of(a.Uo[2], sk), own);
+                if (WG) gstore(G, plane_of(a.G[2], sk), own);
+                gstore(STEP ? substep(zw[2], Z ? a.dt * (a.gamma * G + a.zeta * gmw) : a.dtg * G) : zw[2], plane_of(a.Uo[2], sk), own);
             }
         }
         fwu_bot = fwu_top; fwv_bot = fwv_top; fww_prev = fww;
@@ -1553,13 +1571,29 @@ static void launch_pc32(const ocn_grid &grid, const double *u, const double *v, 
 #if OCN_STRICT
     a.hx = grid.dx; a.hy = grid.dy; a.hz = grid.dz;
 #else
-    a.hx = fz.pc_dt * (1.0 / grid.dx); a.hy = fz.pc_dt * (1.0 / grid.dy); a.hz = fz.pc_dt * (1.0 / grid.dz);
+    if (fz.no_step) {  // (corrected_exact divides by the spacing)
+        a.hx = grid.dx; a.hy = grid.dy; a.hz = grid.dz;
+    } else {
+        a.hx = fz.pc_dt * (1.0 / grid.dx); a.hy = fz.pc_dt * (1.0 / grid.dy); a.hz = fz.pc_dt * (1.0 / grid.dz);
+    }
 #endif
     a.pcdt = fz.pc_dt;
     a.dt = fz.dt; a.gamma = fz.gamma; a.zeta = fz.zeta; a.dtg = fz.dt * fz.gamma;
     a.az = grid.dx * grid.dy; a.ax = grid.dy * grid.dz; a.ay = grid.dx * grid.dz; a.V = a.az * grid.dz;
-    if (fz.has_zeta) hipLaunchKernelGGL((momentum_tendencies_pc32<TX, TY, 3, true>), pg.blocks, dim3(TX * TY), 0, stream, a);
-    else hipLaunchKernelGGL((momentum_tendencies_pc32<TX, TY, 3, false>), pg.blocks, dim3(TX * TY), 0, stream, a);
+    // the variants a step takes: with / without G⁻, each with own or wrapped loads; the no-G form of the step's last launch (always with
+    // G⁻); the no-substep form of the flush (never with G⁻, always stores G)
+#define OCN_PC32(Z, WG, WR, STEP) hipLaunchKernelGGL((momentum_tendencies_pc32<TX, TY, 3, Z, WG, WR, STEP>), pg.blocks, dim3(TX * TY), 0, stream, a)
+    const bool wg = !(fz.skip_g && fz.has_zeta && !fz.no_step);
+    if (fz.no_step) {
+        if (fz.wrap_uvw) OCN_PC32(false, true, true, false); else OCN_PC32(false, true, false, false);
+    } else if (!fz.has_zeta) {
+        if (fz.wrap_uvw) OCN_PC32(false, true, true, true); else OCN_PC32(false, true, false, true);
+    } else if (wg) {
+        if (fz.wrap_uvw) OCN_PC32(true, true, true, true); else OCN_PC32(true, true, false, true);
+    } else {
+        if (fz.wrap_uvw) OCN_PC32(true, false, true, true); else OCN_PC32(true, false, false, true);
+    }
+#undef OCN_PC32
 }
 
 static int make_range(const ocn_grid *grid, const int32_t *range, Range &r)
@@ -1681,9 +1715,20 @@ int launch_momentum_tendencies(const ocn_grid *grid, const double *u, const doub
                 }
                 if (narrow) launch_tiled<P, 17, 15, true, false, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
                 else launch_tiled<P, 32, 8, true, false, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
-            } else if (fz.on && !fz.acc && ocn::tendency_addr32_enabled() && ocn::tendency_addr32_fits(*grid))
+            } else if (fz.on && !fz.acc && ocn::tendency_addr32_enabled() && ocn::tendency_addr32_fits(*grid)) {
+                if (fz.wrap_uvw && fz.pc_xhalo) {
+                    ocn::set_error("wrapped velocity loads need a Periodic x (the x halos of a slab hold the neighbours' columns)");
+                    return OCN_ERR_UNSUPPORTED;
+                }
+                if (fz.no_step && fz.has_zeta) {
+                    ocn::set_error("a launch that stores the corrected velocity takes no substep (has_zeta must be 0)");
+                    return OCN_ERR_INVALID_ARGUMENT;
+                }
                 launch_pc32<17, 15>(*grid, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
-            else
+            } else if (fz.wrap_uvw || fz.no_step) {  // (skip_g is a permission: the 64-bit kernel stores G)
+                ocn::set_error("wrapped velocity loads / the corrected-velocity store are the 32-bit kernel's (ocn_momentum_tendencies_addr32)");
+                return OCN_ERR_UNSUPPORTED;
+            } else
                 launch_tiled<P, 17, 15, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
         } else if (narrow) {
             if (grid->tz == OCN_PERIODIC) launch_tiled<P, 17, 15, false>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
