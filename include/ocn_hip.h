@@ -669,6 +669,42 @@ int ocn_compute_smagorinsky_diffusivities(const ocn_grid *grid, const ocn_model_
  * desc.nu_e).  The struct is copied; NULL returns to AMD.  Same preconditions as ocn_model_driver_set_stokes_drift: not while a step's
  * tendencies are deferred, not on a slab-x rank.  The next time step begins with update_state! and fresh tendencies. */
 int ocn_model_driver_set_smagorinsky(ocn_model_driver_t driver, const ocn_smagorinsky *closure);
+/* ---- Lagrangian particles (src/Models/LagrangianParticleTracking; csrc/particles.hip) ----
+ * What ocn_grid does not carry and the particle kernels need: where the nodes are.  Per direction (x, y, z; ignored along Flat):
+ * face0 = the first Face node = the left face of the domain, center0 = the first Center node, right = the face at N + 1 (the right
+ * edge of the domain, lagrangian_particle_advection.jl:140-151).  Stretched z (grid->dzc != NULL): zf, zc = DEVICE vectors of the
+ * interior z faces (Nz + 1) and z centres (Nz), znodes(grid, Face()) / znodes(grid, Center()); NULL on a regular z. */
+typedef struct ocn_particle_geometry {
+    double face0[3];
+    double center0[3];
+    double right[3];
+    const double *zf;
+    const double *zc;
+} ocn_particle_geometry;
+#define OCN_PARTICLES_MAX_TRACKED 8
+/* update_property! (update_lagrangian_particle_properties.jl:6-15) of up to OCN_PARTICLES_MAX_TRACKED fields in one launch, one thread
+ * per particle:  tracked_out[q][p] = interpolate((x[p], y[p], z[p]), tracked_fields[q], location tracked_locs[q])  (Fields/interpolate.jl:
+ * fractional indices -- (x - x₀) / Δ + 1 on a regular direction, index_binary_search + fractional_index on a stretched z --, interpolator
+ * = truncation towards zero and mod(·, 1), the eight-term trilinear sum ϕ₁ … ϕ₈ left to right; a Flat direction uses (1, 1, 0)).
+ * tracked_fields / tracked_locs / tracked_out are HOST arrays of n_tracked entries; locations are bitmasks 0 .. 7.
+ * Memory safety: every fractional index is clamped in floating point to the range whose two neighbours lie inside the parent array
+ * before it becomes an integer, so a NaN or far-away position reads inside the allocation (the reference's @inbounds would not);
+ * positions for which the reference is in bounds are not altered.  Compiled once, without FMA contraction: independent of the math mode.
+ * n == 0: OCN_SUCCESS, nothing launched.  OCN_ERR_INVALID_ARGUMENT: n < 0, a NULL position / field / output pointer with n > 0,
+ * n_tracked outside 0 .. OCN_PARTICLES_MAX_TRACKED, a location outside 0 .. 7, a stretched z without zf / zc.  OCN_ERR_UNSUPPORTED: a
+ * partitioned x.  All checked before any HIP call. */
+int ocn_sample_particle_properties(const ocn_grid *grid, const ocn_particle_geometry *geom, int64_t n, const double *x, const double *y,
+                                   const double *z, int32_t n_tracked, const double *const *tracked_fields, const int32_t *tracked_locs,
+                                   double *const *tracked_out, void *stream);
+/* _advect_particles! (lagrangian_particle_advection.jl:104-194) with the sampling above in the SAME launch (n_tracked may be 0): the
+ * tracked properties are interpolated at the position BEFORE the move, then
+ *   x⁺ = x + u Δt,  y⁺ = y + v Δt,  z⁺ = z + w Δt      with u, v, w interpolated from their (Face, Center, Center) ... locations,
+ * and per direction enforce_boundary_conditions: Periodic wraps by one period, Bounded bounces off the wall with the coefficient of
+ * `restitution`, Flat passes through.  x, y, z are updated in place.  u, v, w: parent arrays with filled halos.  Same status codes; a
+ * NULL velocity pointer with n > 0 is OCN_ERR_INVALID_ARGUMENT. */
+int ocn_advect_particles(const ocn_grid *grid, const ocn_particle_geometry *geom, int64_t n, double *x, double *y, double *z,
+                         double restitution, const double *u, const double *v, const double *w, double dt, int32_t n_tracked,
+                         const double *const *tracked_fields, const int32_t *tracked_locs, double *const *tracked_out, void *stream);
 /* where field f (0, 1, 2 = u, v, w; 3 + n = tracer n) and its G^n are right now */
 int ocn_model_driver_field(ocn_model_driver_t driver, int32_t f, double **field, double **G);
 

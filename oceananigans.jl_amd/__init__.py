@@ -25,6 +25,8 @@ from .physics import (AnisotropicMinimumDissipation, DynamicCoefficient, Dynamic
                       GradientBoundaryCondition, LinearEquationOfState, OpenBoundaryCondition, ScalarDiffusivity, SeawaterBuoyancy,
                       ValueBoundaryCondition)
 from .stokes import StokesDrift, UniformStokesDrift
+from .particles import (LagrangianParticles, advect_lagrangian_particles, step_lagrangian_particles,
+                        update_lagrangian_particle_properties)
 from .forcings import AdvectiveForcing, Forcing, GaussianMask, LinearTarget, Relaxation
 from .solvers import (BatchedTridiagonalSolver, FFTBasedPoissonSolver, FourierTridiagonalPoissonSolver, XDirection, YDirection, ZDirection,
                       nonhydrostatic_pressure_solver, solve, stretched_direction)

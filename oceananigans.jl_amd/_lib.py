@@ -85,6 +85,14 @@ class CSmagorinsky(C.Structure):
     _fields_ = [("C", C.c_double), ("Cb", C.c_double), ("lilly", C.c_int32), ("n_tracers", C.c_int32), ("Pr", C.c_double * MODEL_MAX_TRACERS)]
 
 
+PARTICLES_MAX_TRACKED = 8
+
+
+class CParticleGeometry(C.Structure):
+    """struct ocn_particle_geometry: first Face / Center node and the right edge per direction; interior z nodes of a stretched z"""
+    _fields_ = [("face0", C.c_double * 3), ("center0", C.c_double * 3), ("right", C.c_double * 3), ("zf", C.c_void_p), ("zc", C.c_void_p)]
+
+
 class CCommOp(C.Structure):
     """struct ocn_comm_op"""
     _fields_ = [("is_recv", C.c_int32), ("peer", C.c_int32), ("slot", C.c_int32)]
@@ -204,6 +212,10 @@ _SIGS = {
     "ocn_model_driver_set_forcing": [_vp, C.POINTER(C.POINTER(CForcing)), _i32],
     "ocn_model_driver_set_smagorinsky": [_vp, C.POINTER(CSmagorinsky)],
     "ocn_compute_smagorinsky_diffusivities": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CSmagorinsky), _vp, _vp, _vp, _vp, C.POINTER(_vp), _vp],
+    "ocn_sample_particle_properties": [C.POINTER(CGrid), C.POINTER(CParticleGeometry), C.c_int64, _vp, _vp, _vp, _i32, C.POINTER(_vp), C.POINTER(_i32),
+                                       C.POINTER(_vp), _vp],
+    "ocn_advect_particles": [C.POINTER(CGrid), C.POINTER(CParticleGeometry), C.c_int64, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _dbl, _i32, C.POINTER(_vp),
+                             C.POINTER(_i32), C.POINTER(_vp), _vp],
     "ocn_halo_plane_x": [C.POINTER(CGrid), _vp, _i32, _i32, _vp, _i32, _vp],
     "ocn_halo_pack_pressure": [C.POINTER(CGrid), _vp, _vp, _dbl, _vp, _vp, _vp],
     "ocn_halo_unpack_pressure": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _vp],

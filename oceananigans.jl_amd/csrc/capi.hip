@@ -742,6 +742,55 @@ int ocn_compute_smagorinsky_diffusivities(const ocn_grid *grid, const ocn_model_
                              : ocn_fast::launch_smagorinsky(grid, t, *closure, u, v, w, nu_e, kappa_e, as_stream(stream));
 }
 
+// ---- Lagrangian particles (csrc/particles.hip) --------------------------------------------------------
+// everything but the position / velocity pointers; *empty: nothing to launch
+static int validate_particles(const char *who, const ocn_grid *grid, const ocn_particle_geometry *geom, int64_t n, int32_t n_tracked,
+                              const double *const *tracked_fields, const int32_t *tracked_locs, double *const *tracked_out)
+{
+    OCN_REQUIRE(n >= 0, "%s: negative particle count %lld", who, (long long)n);
+    int st = validate_grid_any(grid);
+    if (st != OCN_SUCCESS) return st;
+    if (partitioned_x(grid)) {
+        set_error("%s: particles on a partitioned x (topology code %d) are not supported", who, grid->tx);
+        return OCN_ERR_UNSUPPORTED;
+    }
+    OCN_REQUIRE(n_tracked >= 0 && n_tracked <= OCN_PARTICLES_MAX_TRACKED, "%s: n_tracked = %d outside 0..%d", who, n_tracked,
+                OCN_PARTICLES_MAX_TRACKED);
+    if (n == 0) return OCN_SUCCESS;
+    OCN_REQUIRE(n <= (int64_t)1 << 39, "%s: more than 2^39 particles", who);
+    OCN_REQUIRE(geom != nullptr, "%s: geometry is NULL", who);
+    OCN_REQUIRE(!grid->dzc || grid->tz == OCN_FLAT || (geom->zf && geom->zc), "%s: a stretched z needs the node vectors zf, zc", who);
+    OCN_REQUIRE(n_tracked == 0 || (tracked_fields && tracked_locs && tracked_out), "%s: null tracked-field arrays", who);
+    for (int q = 0; q < n_tracked; ++q) {
+        OCN_REQUIRE(tracked_fields[q] && tracked_out[q], "%s: null tracked field / output pointer %d", who, q);
+        OCN_REQUIRE(tracked_locs[q] >= 0 && tracked_locs[q] <= 7, "%s: location mask %d of tracked field %d outside 0..7", who, tracked_locs[q], q);
+    }
+    return OCN_SUCCESS;
+}
+
+int ocn_sample_particle_properties(const ocn_grid *grid, const ocn_particle_geometry *geom, int64_t n, const double *x, const double *y,
+                                   const double *z, int32_t n_tracked, const double *const *tracked_fields, const int32_t *tracked_locs,
+                                   double *const *tracked_out, void *stream)
+{
+    int st = validate_particles("ocn_sample_particle_properties", grid, geom, n, n_tracked, tracked_fields, tracked_locs, tracked_out);
+    if (st != OCN_SUCCESS || n == 0 || n_tracked == 0) return st;
+    OCN_REQUIRE(x && y && z, "ocn_sample_particle_properties: null position pointer");
+    return launch_particles(grid, geom, n, const_cast<double *>(x), const_cast<double *>(y), const_cast<double *>(z), 0, 0.0, nullptr, nullptr,
+                            nullptr, 0.0, n_tracked, tracked_fields, tracked_locs, tracked_out, as_stream(stream));
+}
+
+int ocn_advect_particles(const ocn_grid *grid, const ocn_particle_geometry *geom, int64_t n, double *x, double *y, double *z,
+                         double restitution, const double *u, const double *v, const double *w, double dt, int32_t n_tracked,
+                         const double *const *tracked_fields, const int32_t *tracked_locs, double *const *tracked_out, void *stream)
+{
+    int st = validate_particles("ocn_advect_particles", grid, geom, n, n_tracked, tracked_fields, tracked_locs, tracked_out);
+    if (st != OCN_SUCCESS || n == 0) return st;
+    OCN_REQUIRE(x && y && z, "ocn_advect_particles: null position pointer");
+    OCN_REQUIRE(u && v && w, "ocn_advect_particles: null velocity pointer");
+    return launch_particles(grid, geom, n, x, y, z, 1, restitution, u, v, w, dt, n_tracked, tracked_fields, tracked_locs, tracked_out,
+                            as_stream(stream));
+}
+
 int ocn_update_hydrostatic_pressure(const ocn_grid *grid, const ocn_model_terms *terms, double *pHY, void *stream)
 {
     int st = validate_grid_any(grid);

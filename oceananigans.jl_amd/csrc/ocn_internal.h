@@ -35,6 +35,10 @@ int launch_apply_flux_bcs(const ocn_grid *grid, const FieldTuple &G, const Field
 int launch_apply_flux_bcs_lateral(const ocn_grid *grid, const FieldTuple &G, const FieldTuple &fields, const SideBcTuple &bcs, hipStream_t stream);
 int launch_advection_timescale(const ocn_grid *grid, const double *u, const double *v, const double *w, double *out, hipStream_t stream);
 int launch_hasnan(const double *a, long long n, int *flag, hipStream_t stream);
+// particles.hip: sample the tracked fields and (advect != 0) move the particles, one launch
+int launch_particles(const ocn_grid *grid, const ocn_particle_geometry *geom, long long n, double *x, double *y, double *z, int advect,
+                     double restitution, const double *u, const double *v, const double *w, double dt, int n_tracked,
+                     const double *const *tracked_fields, const int32_t *tracked_locs, double *const *tracked_out, hipStream_t stream);
 int launch_profile_marker(hipStream_t stream);
 int wait_stream(hipStream_t stream, double seconds, const char *who);
 int launch_hydrostatic_pressure(const ocn_grid *grid, const TermsDev &t, double *pHY, hipStream_t stream, const int32_t *irange = nullptr);

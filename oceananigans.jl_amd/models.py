@@ -10,7 +10,8 @@ Mirrors, call for call:
   time_step!(model::QuasiAdamsBashforth2, Δt)                     src/TimeSteppers/quasi_adams_bashforth_2.jl:74-115
   cache_previous_tendencies!                                      src/TimeSteppers/store_tendencies.jl:12-22
 Julia's `f!` names are spelled `f` here.  background_fields is `nothing`; forcing is a dict of arrays, Relaxation(...) and Forcing(func)
-(forcings.py); stokes_drift is UniformStokesDrift (stokes.py); advection is WENO()
+(forcings.py); stokes_drift is UniformStokesDrift (stokes.py); particles is LagrangianParticles (particles.py: stepped after every
+update_state! of a stage, as step_lagrangian_particles! in runge_kutta_3.jl:111, 127, 148 and quasi_adams_bashforth_2.jl:108); advection is WENO()
 or Centered(); coriolis = FPlane, closure = ScalarDiffusivity / AnisotropicMinimumDissipation / Smagorinsky(Lilly), buoyancy = BuoyancyTracer / SeawaterBuoyancy and bottom /
 top Flux / Value / Gradient boundary conditions are the SURVEY §8(f) rank-1 terms (physics.py); anything else raises.
 """
@@ -33,6 +34,7 @@ from .grids import Bounded, Flat, require_regular_xy
 from .solvers import nonhydrostatic_pressure_solver
 from .stokes import DeviceStokesDrift, UniformStokesDrift
 from .forcings import DeviceForcing, field_location, validate_forcing
+from .particles import LagrangianParticles, step_lagrangian_particles
 
 
 class Clock:
@@ -85,10 +87,17 @@ class QuasiAdamsBashforth2TimeStepper(_TendencyStore):
 class NonhydrostaticModel:
     def __init__(self, grid, advection=None, tracers=(), timestepper="RungeKutta3", closure=None, buoyancy=None,
                  coriolis=None, forcing=None, stokes_drift=None, boundary_conditions=None,
-                 hydrostatic_pressure_anomaly="default", pressure_solver="default", math_mode=None):
+                 hydrostatic_pressure_anomaly="default", pressure_solver="default", math_mode=None, particles=None):
         """math_mode: None keeps the grid's (default: the process default, ocn.set_math_mode); MATH_STRICT / MATH_FAST pin this
-        model's arithmetic variant whatever other models of the process use (ocn_grid.math)."""
+        model's arithmetic variant whatever other models of the process use (ocn_grid.math).
+        particles: None or LagrangianParticles(...): moved to the architecture here and stepped with the pressure-corrected, halo-filled
+        velocities after the update_state! of every RK3 stage / QAB2 step (one GPU; the C drivers refuse such a model)."""
         require_regular_xy(grid, "NonhydrostaticModel")
+        if particles is not None:
+            if not isinstance(particles, LagrangianParticles):
+                raise TypeError(f"particles must be LagrangianParticles(...) or None, got {type(particles).__name__}")
+            if hasattr(grid.architecture, "partition"):
+                raise NotImplementedError("particles on a Distributed architecture are not implemented (see DESIGN.md)")
         # stokes_drift: UniformStokesDrift on one GPU (refused here, before anything is allocated, otherwise)
         if stokes_drift is not None:
             if not isinstance(stokes_drift, UniformStokesDrift):
@@ -276,6 +285,12 @@ class NonhydrostaticModel:
                                 and grid.Nx >= 16 and grid.Ny >= 8 and grid.Nz >= 4
                                 and not hasattr(grid.architecture, "partition")
                                 and os.environ.get("OCN_CORRECT_ON_LOAD", "1") != "0")
+        # particles are moved with the corrected velocities of every stage, which the correction on load never writes to memory
+        self.particles = particles
+        if particles is not None:
+            self.correct_on_load = False
+            particles.to_architecture(grid.architecture)
+            particles._resolved = particles.resolve_tracked_fields(grid, self)
         self._pending_tendencies = False
         # slab-x ranks: the same folding with the pressure planes of the neighbours exchanged after the solve (distributed.py)
         sup = getattr(grid.architecture, "correct_on_load_supported", None)
@@ -613,12 +628,14 @@ def time_step(model, dt, euler=False):
     return _time_step_qab2(model, dt, euler)
 
 
-def update_state_and_rk3_substep(model, dt, gamma, zeta, fill_halos=True, p_correct=None, dt_correct=0.0):
+def update_state_and_rk3_substep(model, dt, gamma, zeta, fill_halos=True, p_correct=None, dt_correct=0.0, particles_dt=None):
     """update_state!(model) followed by the next stage's rk3_substep!, with compute_tendencies! and the substep fused into
     one launch (ocn_compute_momentum_tendencies_rk3).  The substep result lands in a second set of velocity arrays whose
-    storage is then swapped into the model's fields."""
+    storage is then swapped into the model's fields.
+    particles_dt: step_lagrangian_particles!(model, particles_dt) between the two -- before the swap, while model.u / v / w still are the
+    state update_state! saw (the fused launch only reads them)."""
     if model._general_fused:
-        return _update_state_and_rk3_substep_general(model, dt, gamma, zeta, fill_halos)
+        return _update_state_and_rk3_substep_general(model, dt, gamma, zeta, fill_halos, particles_dt)
     if model._alt_velocities is None:
         model._alt_velocities = tuple(torch.zeros_like(f.data) for f in model.velocities)
     alt = model._alt_velocities
@@ -640,6 +657,8 @@ def update_state_and_rk3_substep(model, dt, gamma, zeta, fill_halos=True, p_corr
         if fill_halos:
             fill_halo_regions(model.prognostic_fields(), fill_boundary_normal_velocities=False)
         launch()
+    if particles_dt is not None:
+        step_lagrangian_particles(model, particles_dt)
     old = tuple(f.data for f in model.velocities)
     for f, a in zip(model.velocities, alt):
         f.data = a
@@ -685,7 +704,7 @@ def fused_tracer_launches(grid, terms_ref, u, v, w, tracers, kappas, kappa_es, G
         q += 1
 
 
-def _update_state_and_rk3_substep_general(model, dt, gamma, zeta, fill_halos=True):
+def _update_state_and_rk3_substep_general(model, dt, gamma, zeta, fill_halos=True, particles_dt=None):
     """update_state! + the next rk3_substep! for models with tracers and / or the §8(f) terms: momentum = tiled WENO launch +
     one finishing pass (extra terms, u / v boundary fluxes, substep), or the plain fused launch when there is nothing to add;
     each tracer = ONE launch (WENO advection, diffusion, boundary flux, substep).  All substep results land in a second set
@@ -746,6 +765,8 @@ def _update_state_and_rk3_substep_general(model, dt, gamma, zeta, fill_halos=Tru
             fill_halo_regions(prog, fill_boundary_normal_velocities=False)
             compute_auxiliaries(model)
         launch()
+    if particles_dt is not None:  # before the swap: the fields still hold the state update_state! saw
+        step_lagrangian_particles(model, particles_dt)
     for n, f in enumerate(prog):
         f.data, alt[n] = alt[n], f.data
     model._refresh_term_pointers()
@@ -767,10 +788,13 @@ def _project_and_advance(model, dt, stage_dt, gamma_next, zeta_next):
     calculate_pressure_correction(model, stage_dt, minimal_exchange=True)
     pressure_correct_velocities(model, stage_dt)
     cache_previous_tendencies(model)
+    particles_dt = None if model.particles is None else stage_dt
     if model.fuse_stage_boundaries:
-        update_state_and_rk3_substep(model, dt, gamma_next, zeta_next)
+        update_state_and_rk3_substep(model, dt, gamma_next, zeta_next, particles_dt=particles_dt)
     else:
         update_state(model, compute_tendencies=True)
+        if particles_dt is not None:
+            step_lagrangian_particles(model, particles_dt)
         rk3_substep(model, dt, gamma_next, zeta_next)
 
 
@@ -810,6 +834,8 @@ def _time_step_rk3(model, dt):
         model._pending_tendencies = True
     else:
         update_state(model, compute_tendencies=True)
+    if model.particles is not None:
+        step_lagrangian_particles(model, third_stage_dt)  # (not the corrected third-stage Δt: runge_kutta_3.jl:135-148)
 
 
 def _time_step_qab2(model, dt, euler=False):
@@ -827,6 +853,8 @@ def _time_step_qab2(model, dt, euler=False):
     pressure_correct_velocities(model, dt)
     cache_previous_tendencies(model)
     update_state(model, compute_tendencies=True)
+    if model.particles is not None:
+        step_lagrangian_particles(model, dt)
 
 
 def _advance_clock_one_rk3_step(model, dt):
@@ -862,6 +890,9 @@ class RK3Driver:
 
     def __init__(self, model, own_solver=False, defer_correction=None):
         require_regular_xy(model.grid, "RK3Driver")
+        if getattr(model, "particles", None) is not None:
+            raise NotImplementedError("RK3Driver: a model with particles needs the Python host (time_step(model, dt)): the library's time step "
+                                      "does not step LagrangianParticles")
         if model.tracers or model.general_terms:
             raise NotImplementedError("RK3Driver: WENO advection only (no tracers / extra terms)")
         if not isinstance(model.timestepper, RungeKutta3TimeStepper) or not isinstance(model.advection, WENO):
@@ -921,6 +952,9 @@ class ModelRK3Driver:
 
     def __init__(self, model, own_solver=False):
         require_regular_xy(model.grid, "ModelRK3Driver")
+        if getattr(model, "particles", None) is not None:
+            raise NotImplementedError("ModelRK3Driver: a model with particles needs the Python host (time_step(model, dt)): the library's time "
+                                      "step does not step LagrangianParticles")
         if not isinstance(model.timestepper, RungeKutta3TimeStepper):
             raise NotImplementedError("ModelRK3Driver: RungeKutta3")
         xy_periodic = model.grid.topology[0] in ("Periodic", "FullyConnected") and model.grid.topology[1] == "Periodic"

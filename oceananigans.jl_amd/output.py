@@ -5,6 +5,7 @@
   write_checkpoint(model, filepath)     src/OutputWriters/checkpointer.jl:177-203: prognostic fields, Gⁿ, G⁻ (parent arrays,
                                         halos included) and the clock
   set_from_checkpoint(model, filepath)  set!(model, filepath) (:227-288)
+A model with LagrangianParticles also carries every particle property ("NonhydrostaticModel/particles/x", ...).
 
 The reference's container is JLD2 (HDF5); no HDF5 library exists in this image, so the same addresses
 ("NonhydrostaticModel/u/data", "NonhydrostaticModel/timestepper/Gⁿ/u/data", "NonhydrostaticModel/clock/...") are the keys
@@ -182,6 +183,10 @@ def write_checkpoint(model, filepath):
         out[f"{ADDR}/{name}/data"] = f.parent()
         out[f"{ADDR}/timestepper/Gⁿ/{name}/data"] = gn.parent()
         out[f"{ADDR}/timestepper/G⁻/{name}/data"] = gm.parent()
+    particles = getattr(model, "particles", None)
+    if particles is not None:  # every particle property (checkpointer.jl:21 lists :particles among the checkpointed properties)
+        for name, a in particles.properties.items():
+            out[f"{ADDR}/particles/{name}"] = a.cpu().numpy()
     c = model.clock
     out[f"{ADDR}/clock/time"] = np.float64(c.time)
     out[f"{ADDR}/clock/iteration"] = np.int64(c.iteration)
@@ -234,6 +239,15 @@ def set_from_checkpoint(model, filepath):
                 raise KeyError(f"Field {name} does not exist in checkpoint and could not be restored.")
             put(Gn, f"{ADDR}/timestepper/Gⁿ/{name}/data")
             put(Gm, f"{ADDR}/timestepper/G⁻/{name}/data")
+        particles = getattr(model, "particles", None)
+        if particles is not None:  # set!(model.particles, filepath): copyto!(model.particles.properties, file["$addr/particles"]) (checkpointer.jl:246-248)
+            for name, a in particles.properties.items():
+                key = f"{ADDR}/particles/{name}"
+                if key not in z.files:
+                    raise KeyError(f"Particle property {name} does not exist in checkpoint and could not be restored.")
+                if z[key].shape != tuple(a.shape):
+                    raise ValueError(f"{filepath} holds {z[key].shape[0]} particles, the model has {a.shape[0]}")
+                a.copy_(torch.from_numpy(np.ascontiguousarray(z[key], dtype=np.float64)))
         model.clock.time = float(z[f"{ADDR}/clock/time"])
         model.clock.iteration = int(z[f"{ADDR}/clock/iteration"])
         model.clock.last_dt = float(z[f"{ADDR}/clock/last_Δt"])
