@@ -2,10 +2,11 @@
 """The reference's examples/langmuir_turbulence.jl on the MI355X backend: same grid (32^3, extent (128, 128, 64)), wave parameters, Stokes
 drift, boundary conditions, Coriolis, closure, initial condition, time-step wizard and progress message; JLD2 output and plotting left out.
 
-    python examples/langmuir_turbulence.py [--stop-hours 4] [--max-steps N] [--math fast|strict] [--host]
+    python examples/langmuir_turbulence.py [--stop-hours 4] [--max-steps N] [--math fast|strict] [--host] [--averages]
 
 The whole RK3 step runs behind one C call (ocn.ModelRK3Driver) unless --host asks for the Python host.  --max-steps (or the environment
-variable LANGMUIR_MAX_STEPS) caps the number of time steps: the test suite runs 20.
+variable LANGMUIR_MAX_STEPS) caps the number of time steps: the test suite runs 20.  --averages builds the reference example's horizontal
+averages U, V, B, wu, wv (langmuir_turbulence.jl:221-225) once, computes them on the device at every progress message and prints them.
 """
 import argparse
 import math
@@ -28,6 +29,7 @@ def main(argv=None):
     ap.add_argument("--max-steps", type=int, default=int(os.environ.get("LANGMUIR_MAX_STEPS", "0")), help="0: no cap")
     ap.add_argument("--math", choices=("fast", "strict"), default="fast")
     ap.add_argument("--host", action="store_true", help="time_step(model, dt) from Python instead of ModelRK3Driver")
+    ap.add_argument("--averages", action="store_true", help="print the horizontal averages U, V, B, wu, wv with every progress message")
     a = ap.parse_args(argv)
     ocn.set_math_mode(ocn.MATH_FAST if a.math == "fast" else ocn.MATH_STRICT)
 
@@ -72,6 +74,12 @@ def main(argv=None):
     wizard = ocn.TimeStepWizard(cfl=1.0, max_dt=1 * minute)
     driver = None if a.host else ocn.ModelRK3Driver(model)
 
+    averages = {}
+    if a.averages:  # built once: lowering, validation and allocation happen here, compute() only enqueues kernels
+        u, v, w, b = model.u, model.v, model.w, model.field("b")
+        averages = {name: ocn.ComputedField(ocn.Average(op, dims=(1, 2))) for name, op in
+                    (("U", u), ("V", v), ("B", b), ("wu", w * u), ("wv", w * v))}
+
     def flush():
         if driver is not None:
             driver.flush()
@@ -87,6 +95,9 @@ def main(argv=None):
             umax = [float(f.data.abs().max()) for f in model.velocities]
             print(f"i: {it:04d}, t: {model.clock.time / minute:7.3f} min, Δt: {dt:6.2f} s, umax = ({umax[0]:.1e}, {umax[1]:.1e}, {umax[2]:.1e}) ms⁻¹, "
                   f"wall time: {time.perf_counter() - t0:.1f} s", flush=True)
+            for name, avg in averages.items():
+                profile = avg.compute().interior()[0, 0, :]
+                print(f"    {name:>2s}(z): " + " ".join(f"{x: .2e}" for x in profile[::max(1, len(profile) // 8)]), flush=True)
         step = min(dt, stop_time - model.clock.time)
         if driver is not None:
             driver.time_step(step)

@@ -915,6 +915,60 @@ int ocn_rk3_driver_create_distributed(ocn_rk3_driver_t *driver, const ocn_grid *
 int ocn_model_driver_create_distributed(ocn_model_driver_t *driver, const ocn_grid *local_grid, const ocn_model_driver_desc *desc, double *u,
                                         double *v, double *w, double *p, ocn_dist_poisson_t solver, ocn_comm_t comm, void *stream);                      /* MPI.Barrier; blocks the host */
 
+/* ---- On-device diagnostics: AbstractOperations (src/AbstractOperations/binary_operations.jl, unary_operations.jl, derivatives.jl),
+ *      compute!(Field(operation)) and the Average / Integral reductions (metric_field_reductions.jl:11-113).
+ *      The reference compiles one fused kernel per expression tree.  This library is compiled ahead of time, so the host lowers a tree to
+ *      a straight-line program in static single assignment form (instruction q defines value q and may only read values < q) and ONE
+ *      kernel evaluates it per cell, with the reduction fused in: no full-size temporary for w * u or ddz(u) - ddx(w).  The value of the
+ *      LAST instruction is the value of the tree.  Every value also names the register it lives in (the host's register allocation):
+ *      a register may be reused once its value has been read for the last time.
+ *      One arithmetic variant (no FMA contraction, IEEE division and square root) whatever ocn_grid.math says. ---- */
+#define OCN_OP_MAX_INSTRUCTIONS 128
+#define OCN_OP_MAX_REGISTERS 16
+#define OCN_OP_MAX_FIELDS 8
+/* opcodes */
+#define OCN_OP_LOAD 0     /* field[field] at (i + di, j + dj, k + dk); along a direction the field is reduced in: its one element */
+#define OCN_OP_CONST 1    /* value */
+#define OCN_OP_SPACING 2  /* field = kind: 0 Δx, 1 Δy, 2 Δzᵃᵃᶜ[k + dk], 3 Δzᵃᵃᶠ[k + dk] (ocn_grid.dz for both on a regular z) */
+#define OCN_OP_NEG 3      /* -a */
+#define OCN_OP_ABS 4
+#define OCN_OP_SQRT 5
+#define OCN_OP_ADD 6      /* a + b */
+#define OCN_OP_SUB 7
+#define OCN_OP_MUL 8
+#define OCN_OP_DIV 9
+typedef struct ocn_op_instruction {
+    int32_t opcode;
+    int32_t a, b;        /* operands of the unary (a) and binary (a, b) opcodes: indices of EARLIER instructions */
+    int32_t reg;         /* register of the result, 0 .. n_registers - 1 */
+    int32_t field;       /* LOAD: index into fields[]; SPACING: the kind */
+    int32_t di, dj, dk;  /* LOAD: index offsets; SPACING of Δz: dk */
+    double value;        /* CONST */
+} ocn_op_instruction;
+typedef struct ocn_op_program {
+    int32_t n_instructions, n_registers, n_fields;
+    int32_t loc;                                  /* location mask of the tree (all eight masks 0..7): its interior is the index space, N + 1
+                                                   * points along a Face & Bounded direction */
+    const double *fields[OCN_OP_MAX_FIELDS];      /* DEVICE parent arrays; halos are read as they are */
+    int32_t field_loc[OCN_OP_MAX_FIELDS];         /* location masks of the fields */
+    int32_t field_reduced[OCN_OP_MAX_FIELDS];     /* bit d: the field was reduced along d -- extent 1, no halo, broadcast along d */
+    ocn_op_instruction ins[OCN_OP_MAX_INSTRUCTIONS];
+} ocn_op_program;
+/* Every entry below validates the WHOLE program on the host before anything is launched (counts within the limits, operands earlier than
+ * their instruction, registers below n_registers and not overwritten while live, field indices in range, every LOAD / SPACING offset
+ * inside the field's parent array for every cell of the index space, non-null pointers): OCN_ERR_INVALID_ARGUMENT otherwise.
+ *
+ * compute!(Field(operation)): `out` is the parent array of a field at program->loc; its interior is written, its halos are not. */
+int ocn_op_compute(const ocn_grid *grid, const ocn_op_program *program, double *out, void *stream);
+/* Number of doubles of workspace ocn_op_reduce needs for a tree at `loc` reduced over `dims` (bit d: direction d; 1..7). */
+int ocn_op_reduce_workspace(const ocn_grid *grid, int32_t loc, int32_t dims, int64_t *n_doubles);
+/* sum! of the program over `dims`, fused with its evaluation.  `out` is the parent array of the reduced field: extent 1 and no halo along
+ * the reduced directions, the field's usual extent (halos included, not written) along the others.  Every element is the sum of the
+ * partial sums of a fixed decomposition, added in a fixed order by a second small launch and then divided by `divisor` (1.0 for an
+ * Integral; the number of points or Σ metric for an Average): no floating-point atomics, bit-identical from call to call. */
+int ocn_op_reduce(const ocn_grid *grid, const ocn_op_program *program, int32_t dims, double divisor, double *workspace,
+                  int64_t workspace_doubles, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

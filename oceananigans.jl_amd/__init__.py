@@ -28,6 +28,8 @@ from .stokes import StokesDrift, UniformStokesDrift
 from .particles import (LagrangianParticles, advect_lagrangian_particles, step_lagrangian_particles,
                         update_lagrangian_particle_properties)
 from .forcings import AdvectiveForcing, Forcing, GaussianMask, LinearTarget, Relaxation
+from .operations import (AbstractOperation, Average, BinaryOperation, ComputedField, CumulativeIntegral, Derivative, Integral,
+                         KernelFunctionOperation, UnaryOperation, abs, at, compute, ddx, ddy, ddz, exp, log, lower, sqrt, tanh)
 from .solvers import (BatchedTridiagonalSolver, FFTBasedPoissonSolver, FourierTridiagonalPoissonSolver, XDirection, YDirection, ZDirection,
                       nonhydrostatic_pressure_solver, solve, stretched_direction)
 

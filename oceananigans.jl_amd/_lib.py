@@ -93,6 +93,24 @@ class CParticleGeometry(C.Structure):
     _fields_ = [("face0", C.c_double * 3), ("center0", C.c_double * 3), ("right", C.c_double * 3), ("zf", C.c_void_p), ("zc", C.c_void_p)]
 
 
+OP_MAX_INSTRUCTIONS, OP_MAX_REGISTERS, OP_MAX_FIELDS = 128, 16, 8
+OP_LOAD, OP_CONST, OP_SPACING, OP_NEG, OP_ABS, OP_SQRT, OP_ADD, OP_SUB, OP_MUL, OP_DIV = range(10)
+SPACING_DX, SPACING_DY, SPACING_DZC, SPACING_DZF = range(4)
+
+
+class COpInstruction(C.Structure):
+    """struct ocn_op_instruction"""
+    _fields_ = [("opcode", C.c_int32), ("a", C.c_int32), ("b", C.c_int32), ("reg", C.c_int32), ("field", C.c_int32),
+                ("di", C.c_int32), ("dj", C.c_int32), ("dk", C.c_int32), ("value", C.c_double)]
+
+
+class COpProgram(C.Structure):
+    """struct ocn_op_program: an operation tree lowered to a straight-line program (operations.py)"""
+    _fields_ = [("n_instructions", C.c_int32), ("n_registers", C.c_int32), ("n_fields", C.c_int32), ("loc", C.c_int32),
+                ("fields", C.c_void_p * OP_MAX_FIELDS), ("field_loc", C.c_int32 * OP_MAX_FIELDS), ("field_reduced", C.c_int32 * OP_MAX_FIELDS),
+                ("ins", COpInstruction * OP_MAX_INSTRUCTIONS)]
+
+
 class CCommOp(C.Structure):
     """struct ocn_comm_op"""
     _fields_ = [("is_recv", C.c_int32), ("peer", C.c_int32), ("slot", C.c_int32)]
@@ -216,6 +234,9 @@ _SIGS = {
                                        C.POINTER(_vp), _vp],
     "ocn_advect_particles": [C.POINTER(CGrid), C.POINTER(CParticleGeometry), C.c_int64, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _dbl, _i32, C.POINTER(_vp),
                              C.POINTER(_i32), C.POINTER(_vp), _vp],
+    "ocn_op_compute": [C.POINTER(CGrid), C.POINTER(COpProgram), _vp, _vp],
+    "ocn_op_reduce_workspace": [C.POINTER(CGrid), _i32, _i32, C.POINTER(C.c_int64)],
+    "ocn_op_reduce": [C.POINTER(CGrid), C.POINTER(COpProgram), _i32, _dbl, _vp, C.c_int64, _vp, _vp],
     "ocn_halo_plane_x": [C.POINTER(CGrid), _vp, _i32, _i32, _vp, _i32, _vp],
     "ocn_halo_pack_pressure": [C.POINTER(CGrid), _vp, _vp, _dbl, _vp, _vp, _vp],
     "ocn_halo_unpack_pressure": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _vp],

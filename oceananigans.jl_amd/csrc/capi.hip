@@ -791,6 +791,26 @@ int ocn_advect_particles(const ocn_grid *grid, const ocn_particle_geometry *geom
                             as_stream(stream));
 }
 
+// ---- on-device diagnostics (diagnostics.hip validates the whole program before it launches anything) ----
+int ocn_op_compute(const ocn_grid *grid, const ocn_op_program *program, double *out, void *stream)
+{
+    return op_compute(grid, program, out, as_stream(stream));
+}
+
+int ocn_op_reduce_workspace(const ocn_grid *grid, int32_t loc, int32_t dims, int64_t *n_doubles)
+{
+    long long n = 0;
+    int st = op_reduce_workspace(grid, loc, dims, n_doubles ? &n : nullptr);
+    if (st == OCN_SUCCESS) *n_doubles = n;
+    return st;
+}
+
+int ocn_op_reduce(const ocn_grid *grid, const ocn_op_program *program, int32_t dims, double divisor, double *workspace,
+                  int64_t workspace_doubles, double *out, void *stream)
+{
+    return op_reduce(grid, program, dims, divisor, workspace, workspace_doubles, out, as_stream(stream));
+}
+
 int ocn_update_hydrostatic_pressure(const ocn_grid *grid, const ocn_model_terms *terms, double *pHY, void *stream)
 {
     int st = validate_grid_any(grid);

@@ -39,6 +39,11 @@ int launch_hasnan(const double *a, long long n, int *flag, hipStream_t stream);
 int launch_particles(const ocn_grid *grid, const ocn_particle_geometry *geom, long long n, double *x, double *y, double *z, int advect,
                      double restitution, const double *u, const double *v, const double *w, double dt, int n_tracked,
                      const double *const *tracked_fields, const int32_t *tracked_locs, double *const *tracked_out, hipStream_t stream);
+// diagnostics.hip: an operation tree lowered to a straight-line program, evaluated per cell; both validate the whole program first
+int op_compute(const ocn_grid *grid, const ocn_op_program *program, double *out, hipStream_t stream);
+int op_reduce_workspace(const ocn_grid *grid, int loc, int dims, long long *n_doubles);
+int op_reduce(const ocn_grid *grid, const ocn_op_program *program, int dims, double divisor, double *workspace, long long workspace_doubles,
+              double *out, hipStream_t stream);
 int launch_profile_marker(hipStream_t stream);
 int wait_stream(hipStream_t stream, double seconds, const char *who);
 int launch_hydrostatic_pressure(const ocn_grid *grid, const TermsDev &t, double *pHY, hipStream_t stream, const int32_t *irange = nullptr);

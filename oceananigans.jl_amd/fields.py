@@ -7,9 +7,17 @@ import torch
 
 from . import _lib
 from .architectures import on_architecture, stream_ptr, zeros
-from .grids import Bounded, Flat
+from .grids import Bounded, Center, Face, Flat
 
 LOC = {"u": _lib.LOC_FCC, "v": _lib.LOC_CFC, "w": _lib.LOC_CCF, "c": _lib.LOC_CCC}
+
+
+def _arithmetic(op, swap=False):
+    """`field op other` builds an operation tree (operations.py)"""
+    def method(self, other):
+        from .operations import binary_operation
+        return binary_operation(op, other, self) if swap else binary_operation(op, self, other)
+    return method
 
 
 class Field:
@@ -34,6 +42,26 @@ class Field:
     @property
     def ptr(self):
         return self.data.data_ptr()
+
+    @property
+    def location(self):
+        """(LX, LY, LZ) out of Center / Face"""
+        return tuple(Face if (self.loc >> d) & 1 else Center for d in range(3))
+
+    # arithmetic builds AbstractOperations (operations.py); a leaf's halos are read as they are
+    __array_ufunc__ = None  # np.float64(2) * field reaches __rmul__
+    __add__, __radd__ = _arithmetic("+"), _arithmetic("+", True)
+    __sub__, __rsub__ = _arithmetic("-"), _arithmetic("-", True)
+    __mul__, __rmul__ = _arithmetic("*"), _arithmetic("*", True)
+    __truediv__, __rtruediv__ = _arithmetic("/"), _arithmetic("/", True)
+
+    def __neg__(self):
+        from .operations import unary_operation
+        return unary_operation("neg", self)
+
+    def __pow__(self, n):
+        from .operations import power
+        return power(self, n)
 
     def interior_view(self):
         """interior(field): tensor view indexed [k, j, i] over 1:N (plus the extra boundary face where Face & Bounded)."""
