@@ -414,6 +414,22 @@ int ocn_split_rk3_substep(const ocn_grid *grid, int32_t n, double *const *U, con
 /* ab2_step_field! (src/TimeSteppers/quasi_adams_bashforth_2.jl:128-175) */
 int ocn_ab2_step(const ocn_grid *grid, int32_t n, double *const *U, const double *const *Gn, const double *const *Gm,
                  const int32_t *locs, double dt, double chi, void *stream);
+/* ---- ScalarDiffusivity(VerticallyImplicitTimeDiscretization(), ν, κ), constant ν and κ, z Bounded ----
+ * The EXPLICIT part of the closure term (abstract_scalar_diffusivity_closure.jl:214-260) ADDED to tendencies that hold every other term
+ * (the existing entry points called with terms->closure == 0): the horizontal fluxes and the x / y fluxes of w as for the explicit
+ * closure; diffusive_flux_z and viscous_flux_wz explicit at k == 1 | k == Nz+1 and zero elsewhere; viscous_flux_uz / vz explicit at
+ * k == 1 | k == Nz+1 and -ν ∂x w / -ν ∂y w elsewhere.  u == NULL: no momentum part (then v, w, Gu, Gv, Gw are NULL too); Gw == NULL: u and
+ * v only (HydrostaticFreeSurfaceModel).  kappa / c / Gc: HOST arrays of n_tracers numbers / device pointers.  range as for
+ * ocn_compute_momentum_tendencies_terms (NULL: the whole interior with the peripheries of Face fields excluded). */
+int ocn_add_vertically_implicit_explicit_fluxes(const ocn_grid *grid, double nu, const double *u, const double *v, const double *w, double *Gu,
+                                                double *Gv, double *Gw, int32_t n_tracers, const double *kappa, const double *const *c,
+                                                double *const *Gc, const int32_t *range, void *stream);
+/* implicit_step! (vertically_implicit_diffusion_solver.jl:55-110 + solve_batched_tridiagonal_system_z!, batched_tridiagonal_solver.jl)
+ * for n fields in one launch, in place:  (1 - dt ∂z κ ∂z) φ = φ  over columns i = 1..Nx, j = 1..Ny, rows k = 1..Nz -- the Center-in-z
+ * rows for locations without the z-Face bit, the Face-in-z rows for OCN_LOC_CCF.  fields / locs / kappa: HOST arrays of n device
+ * pointers / location masks / numbers (ν for velocities).  Nz <= 2048 (the multipliers of one column live in LDS). */
+int ocn_implicit_vertical_diffusion_step(const ocn_grid *grid, int32_t n, double *const *fields, const int32_t *locs, const double *kappa,
+                                         double dt, void *stream);
 /* cache_previous_tendencies! (src/TimeSteppers/store_tendencies.jl:6-22) */
 int ocn_cache_previous_tendencies(const ocn_grid *grid, int32_t n, double *const *Gm, const double *const *Gn,
                                   const int32_t *locs, void *stream);

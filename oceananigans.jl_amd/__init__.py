@@ -16,14 +16,14 @@ from .fields import CenterField, Field, XFaceField, YFaceField, ZFaceField, fill
 from .grids import Bounded, Center, Face, Flat, FullyConnected, LeftConnected, Periodic, RectilinearGrid, RightConnected
 from .models import (NonhydrostaticModel, QuasiAdamsBashforth2TimeStepper, RungeKutta3TimeStepper, ab2_step,
                      cache_previous_tendencies, calculate_pressure_correction, compute_auxiliaries, compute_diffusivities,
-                     compute_tendencies, flush_tendencies, RK3Driver, ModelRK3Driver,
+                     compute_tendencies, flush_tendencies, RK3Driver, ModelRK3Driver, implicit_step, add_vertically_implicit_explicit_fluxes,
                      pressure_correct_velocities, rk3_substep, set, solve_for_pressure, time_step, update_hydrostatic_pressure,
                      update_state)
 from .output import (AdvectiveCFL, DiffusiveCFL, NaNChecker, TimeStepWizard, cell_advection_timescale, cell_diffusion_timescale, hasnan, set_from_checkpoint,
                      write_checkpoint)
 from .physics import (AnisotropicMinimumDissipation, DynamicCoefficient, DynamicSmagorinsky, LillyCoefficient, Smagorinsky, SmagorinskyLilly, BetaPlane, BoundaryCondition, BuoyancyTracer, Centered, FieldBoundaryConditions, FluxBoundaryCondition, FPlane,
                       GradientBoundaryCondition, LinearEquationOfState, OpenBoundaryCondition, ScalarDiffusivity, SeawaterBuoyancy,
-                      ValueBoundaryCondition)
+                      ValueBoundaryCondition, ExplicitTimeDiscretization, VerticallyImplicitTimeDiscretization)
 from .stokes import StokesDrift, UniformStokesDrift
 from .particles import (LagrangianParticles, advect_lagrangian_particles, step_lagrangian_particles,
                         update_lagrangian_particle_properties)

@@ -1,5 +1,6 @@
 // capi.hip -- extern "C" entry points of libocn_hip.so (see include/ocn_hip.h for the contract).
 #include <atomic>
+#include <cmath>
 #include <cstring>
 #include <string>
 
@@ -1398,6 +1399,58 @@ int ocn_ab2_step(const ocn_grid *grid, int32_t n, double *const *U, const double
     if (st != OCN_SUCCESS) return st;
     const double not_euler = (chi != -0.5) ? 1.0 : 0.0;
     return launch_stepper(grid, t, 2, dt, chi, not_euler, as_stream(stream));
+}
+
+static int validate_vertically_implicit(const ocn_grid *grid, const char *who)
+{
+    int st = validate_grid_any(grid);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(grid->tz == OCN_BOUNDED, "%s: VerticallyImplicitTimeDiscretization can only be specified on grids that are Bounded in the z-direction.", who);
+    OCN_REQUIRE((grid->tx == OCN_FLAT || grid->Hx >= 1) && (grid->ty == OCN_FLAT || grid->Hy >= 1) && grid->Hz >= 1, "%s: halo >= 1 required", who);
+    return OCN_SUCCESS;
+}
+
+int ocn_add_vertically_implicit_explicit_fluxes(const ocn_grid *grid, double nu, const double *u, const double *v, const double *w, double *Gu,
+                                                double *Gv, double *Gw, int32_t n_tracers, const double *kappa, const double *const *c,
+                                                double *const *Gc, const int32_t *range, void *stream)
+{
+    const char *who = "ocn_add_vertically_implicit_explicit_fluxes";
+    int st = validate_vertically_implicit(grid, who);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(n_tracers >= 0 && n_tracers <= MAX_TUPLE, "%s: number of tracers %d outside 0..%d", who, n_tracers, MAX_TUPLE);
+    if (u) {
+        OCN_REQUIRE(v && w && Gu && Gv, "%s: null field pointer (u is given: v, w, Gu, Gv are needed; Gw may be NULL)", who);
+        OCN_REQUIRE(std::isfinite(nu) && nu >= 0, "%s: nu = %g must be finite and >= 0", who, nu);
+    } else {
+        OCN_REQUIRE(!v && !w && !Gu && !Gv && !Gw, "%s: u is NULL (no momentum part) but another momentum pointer is not", who);
+        OCN_REQUIRE(n_tracers >= 1, "%s: nothing to do (u is NULL and n_tracers is 0)", who);
+    }
+    if (n_tracers) OCN_REQUIRE(kappa && c && Gc, "%s: null tracer array", who);
+    for (int n = 0; n < n_tracers; ++n) {
+        OCN_REQUIRE(c[n] && Gc[n], "%s: tracer %d: null pointer", who, n);
+        OCN_REQUIRE(std::isfinite(kappa[n]) && kappa[n] >= 0, "%s: tracer %d: kappa = %g must be finite and >= 0", who, n, kappa[n]);
+    }
+    return launch_ivd_explicit_part(grid, nu, u, v, w, Gu, Gv, Gw, n_tracers, kappa, c, Gc, range, as_stream(stream));
+}
+
+int ocn_implicit_vertical_diffusion_step(const ocn_grid *grid, int32_t n, double *const *fields, const int32_t *locs, const double *kappa,
+                                         double dt, void *stream)
+{
+    const char *who = "ocn_implicit_vertical_diffusion_step";
+    int st = validate_vertically_implicit(grid, who);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(n >= 1 && n <= MAX_TUPLE, "%s: number of fields %d outside 1..%d", who, n, MAX_TUPLE);
+    OCN_REQUIRE(fields && locs && kappa, "%s: null tuple pointer", who);
+    OCN_REQUIRE(grid->Nz <= 2048, "%s: Nz = %d > 2048 (the multipliers of a column are kept in LDS)", who, grid->Nz);
+    OCN_REQUIRE(std::isfinite(dt) && dt >= 0, "%s: dt = %g must be finite and >= 0", who, dt);
+    for (int f = 0; f < n; ++f) {
+        OCN_REQUIRE(fields[f] != nullptr, "%s: field %d: null pointer", who, f);
+        OCN_REQUIRE(locs[f] == OCN_LOC_CCC || locs[f] == OCN_LOC_FCC || locs[f] == OCN_LOC_CFC || locs[f] == OCN_LOC_CCF,
+                    "%s: field %d: location %d is none of ccc, fcc, cfc, ccf", who, f, locs[f]);
+        OCN_REQUIRE(std::isfinite(kappa[f]) && kappa[f] >= 0, "%s: field %d: kappa = %g must be finite and >= 0", who, f, kappa[f]);
+        for (int q = 0; q < f; ++q) OCN_REQUIRE(fields[q] != fields[f], "%s: fields %d and %d are the same array", who, q, f);
+    }
+    return launch_ivd_implicit_step(grid, n, fields, locs, kappa, dt, as_stream(stream));
 }
 
 int ocn_cache_previous_tendencies(const ocn_grid *grid, int32_t n, double *const *Gm, const double *const *Gn,

@@ -44,6 +44,12 @@ int op_compute(const ocn_grid *grid, const ocn_op_program *program, double *out,
 int op_reduce_workspace(const ocn_grid *grid, int loc, int dims, long long *n_doubles);
 int op_reduce(const ocn_grid *grid, const ocn_op_program *program, int dims, double divisor, double *workspace, long long workspace_doubles,
               double *out, hipStream_t stream);
+// implicit_diffusion.hip: the explicit part of a vertically implicit ScalarDiffusivity added to G, and the implicit step of n fields
+int launch_ivd_explicit_part(const ocn_grid *grid, double nu, const double *u, const double *v, const double *w, double *Gu, double *Gv,
+                             double *Gw, int n_tracers, const double *kappa, const double *const *c, double *const *Gc, const int32_t *range,
+                             hipStream_t stream);
+int launch_ivd_implicit_step(const ocn_grid *grid, int n, double *const *fields, const int32_t *locs, const double *kappa, double dt,
+                             hipStream_t stream);
 int launch_profile_marker(hipStream_t stream);
 int wait_stream(hipStream_t stream, double seconds, const char *who);
 int launch_hydrostatic_pressure(const ocn_grid *grid, const TermsDev &t, double *pHY, hipStream_t stream, const int32_t *irange = nullptr);

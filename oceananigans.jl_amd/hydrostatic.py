@@ -8,8 +8,9 @@ flux-form momentum advection, QuasiAdamsBashforth2, static (Periodic, Periodic, 
 The horizontal momentum and tracer tendencies are the terms of the NonhydrostaticModel path (flux-form advection, FPlane,
 ∂x pHY′, ScalarDiffusivity, flux boundary conditions) plus the barotropic pressure gradient g ∇η; w is diagnosed from continuity;
 there is no pressure solve.  momentum_advection = VectorInvariant() (the reference's default: enstrophy-conserving vorticity flux,
-energy-conserving vertical advection and kinetic-energy gradient) or a flux-form scheme.  NOT in this slice (each raises):
-SplitExplicitFreeSurface / ImplicitFreeSurface, upwinding / WENO vector-invariant variants, z-star coordinates, vertically implicit diffusion, eddy-viscosity closures,
+energy-conserving vertical advection and kinetic-energy gradient) or a flux-form scheme.  closure = ScalarDiffusivity(...), explicit or
+with VerticallyImplicitTimeDiscretization() (QAB2, fused = False: implicit_step! of u, v and the tracers after their ab2 step).  NOT in this slice (each raises):
+SplitExplicitFreeSurface / ImplicitFreeSurface, upwinding / WENO vector-invariant variants, z-star coordinates, eddy-viscosity closures,
 a tracer advection scheme different from the momentum one, Distributed architectures.
 """
 import ctypes as C
@@ -21,7 +22,7 @@ from .architectures import stream_ptr
 from .fields import fill_halo_regions
 from .grids import Bounded, Periodic
 from .models import NonhydrostaticModel, compute_boundary_tendency_contributions, update_hydrostatic_pressure
-from .physics import Centered, owns_eddy_fields
+from .physics import Centered, is_vertically_implicit, owns_eddy_fields
 
 g_Earth = 9.80665  # Oceananigans.BuoyancyFormulations.g_Earth
 
@@ -196,6 +197,17 @@ class HydrostaticFreeSurfaceModel:
             container_advection = momentum_advection
         if owns_eddy_fields(closure):
             raise NotImplementedError("eddy-viscosity closures are not part of this slice")
+        # closure = ScalarDiffusivity(VerticallyImplicitTimeDiscretization(), ...): the reference's launch sequence with QAB2 on one GPU
+        # (hydrostatic_free_surface_ab2_step.jl:39-108: implicit_step! of u, v and every tracer after its ab2 step; w is diagnostic)
+        self._implicit = is_vertically_implicit(closure)
+        if self._implicit:
+            if fused:
+                raise NotImplementedError("a VerticallyImplicitTimeDiscretization closure runs the reference's launch sequence (fused = False)")
+            if self.split_rk3:
+                raise NotImplementedError("a VerticallyImplicitTimeDiscretization closure with SplitRungeKutta3 is not implemented")
+            if self._dist is not None:
+                raise NotImplementedError("a VerticallyImplicitTimeDiscretization closure on a slab-partitioned (Distributed) grid is not implemented")
+            fused = False
         # fields, physics descriptors, tendency storage and the Adams-Bashforth bookkeeping of the nonhydrostatic model are reused;
         # its pressure solver and w tendency are simply not used
         self._nh = NonhydrostaticModel(grid, advection=container_advection, tracers=tracers, timestepper="QuasiAdamsBashforth2",
@@ -284,7 +296,8 @@ class HydrostaticFreeSurfaceModel:
         if not self._tendencies_current:
             self.compute_tendencies()
 
-    def compute_tendencies(self):
+    def compute_tendencies(self, boundary_contributions=True):
+        """boundary_contributions = False: the interior contributions alone (models.compute_tendencies_ takes the same switch)"""
         nh, g, s = self._nh, self.grid, stream_ptr()
         self._tendencies_current = True
         Gn = nh.timestepper._Gn
@@ -299,13 +312,20 @@ class HydrostaticFreeSurfaceModel:
                       Gn[0].ptr, Gn[1].ptr, Gn[2].ptr, None, s)
             if not (self.split or self.implicit):
                 _lib.call("ocn_add_barotropic_pressure_gradient", g.cref, grav, self.eta.data_ptr(), Gn[0].ptr, Gn[1].ptr, s)  # - g ∇η
-        _lib.call("ocn_add_momentum_terms", g.cref, C.byref(nh._terms), self.u.ptr, self.v.ptr, self.w.ptr, Gn[0].ptr, Gn[1].ptr,
+        terms = nh._terms_noclosure if self._implicit else nh._terms
+        _lib.call("ocn_add_momentum_terms", g.cref, C.byref(terms), self.u.ptr, self.v.ptr, self.w.ptr, Gn[0].ptr, Gn[1].ptr,
                   Gn[2].ptr, None, s)                                                               # - f x U - ∇pHY′ - ∂ⱼτᵢⱼ
         for n, c in enumerate(self.tracers):
-            kappa = 0.0 if nh.closure is None else nh.closure.kappa_of(self.tracer_names[n])
-            _lib.call("ocn_compute_tracer_tendency_terms", g.cref, C.byref(nh._terms), kappa, None, self.u.ptr, self.v.ptr, self.w.ptr,
+            kappa = 0.0 if (nh.closure is None or self._implicit) else nh.closure.kappa_of(self.tracer_names[n])
+            _lib.call("ocn_compute_tracer_tendency_terms", g.cref, C.byref(terms), kappa, None, self.u.ptr, self.v.ptr, self.w.ptr,
                       c.ptr, Gn[3 + n].ptr, None, s)
-        compute_boundary_tendency_contributions(nh)
+        if self._implicit:  # the explicit part of the closure term (Gu, Gv and the tracers: w is diagnostic)
+            nt = len(self.tracers)
+            _lib.call("ocn_add_vertically_implicit_explicit_fluxes", g.cref, nh.closure.nu, self.u.ptr, self.v.ptr, self.w.ptr, Gn[0].ptr,
+                      Gn[1].ptr, None, nt, (C.c_double * max(nt, 1))(*[nh.closure.kappa_of(n) for n in self.tracer_names]),
+                      _lib.ptr_array([c.ptr for c in self.tracers] or [None]), _lib.ptr_array([G.ptr for G in Gn[3:]] or [None]), None, s)
+        if boundary_contributions:
+            compute_boundary_tendency_contributions(nh)
 
     # ---- time_step! (quasi_adams_bashforth_2.jl:74-115 with ab2_step!(::HydrostaticFreeSurfaceModel)) -------------------------
     def _time_step_split_rk3(self, dt):
@@ -391,6 +411,10 @@ class HydrostaticFreeSurfaceModel:
         fields = [self.u, self.v] + list(self.tracers)
         _lib.call("ocn_ab2_step", g.cref, len(idx), _lib.ptr_array([f.ptr for f in fields]), _lib.ptr_array([Gn[q].ptr for q in idx]),
                   _lib.ptr_array([Gm[q].ptr for q in idx]), _lib.i32_array([f.loc for f in fields]), float(dt), float(chi), s)
+        if self._implicit:  # implicit_step! of u, v (ν) and every tracer (its own κ) with the full Δt
+            kappa = [nh.closure.nu] * 2 + [nh.closure.kappa_of(n) for n in self.tracer_names]
+            _lib.call("ocn_implicit_vertical_diffusion_step", g.cref, len(fields), _lib.ptr_array([f.ptr for f in fields]),
+                      _lib.i32_array([f.loc for f in fields]), (C.c_double * len(fields))(*kappa), float(dt), s)
         fs = self.free_surface
         if self.split:
             # compute_free_surface_tendency! (slow forcing from Gⁿ, G⁻ BEFORE they are cached), then step_free_surface!

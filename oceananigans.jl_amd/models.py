@@ -12,7 +12,7 @@ Mirrors, call for call:
 Julia's `f!` names are spelled `f` here.  background_fields is `nothing`; forcing is a dict of arrays, Relaxation(...) and Forcing(func)
 (forcings.py); stokes_drift is UniformStokesDrift (stokes.py); particles is LagrangianParticles (particles.py: stepped after every
 update_state! of a stage, as step_lagrangian_particles! in runge_kutta_3.jl:111, 127, 148 and quasi_adams_bashforth_2.jl:108); advection is WENO()
-or Centered(); coriolis = FPlane, closure = ScalarDiffusivity / AnisotropicMinimumDissipation / Smagorinsky(Lilly), buoyancy = BuoyancyTracer / SeawaterBuoyancy and bottom /
+or Centered(); coriolis = FPlane, closure = ScalarDiffusivity (explicit or vertically implicit) / AnisotropicMinimumDissipation / Smagorinsky(Lilly), buoyancy = BuoyancyTracer / SeawaterBuoyancy and bottom /
 top Flux / Value / Gradient boundary conditions are the SURVEY §8(f) rank-1 terms (physics.py); anything else raises.
 """
 import math
@@ -27,7 +27,7 @@ import ctypes as C
 
 from .advection import WENO, UpwindBiased
 from .physics import (AnisotropicMinimumDissipation, BetaPlane, BuoyancyTracer, Centered, FieldBoundaryConditions, FPlane, ScalarDiffusivity,
-                      SeawaterBuoyancy, Smagorinsky, owns_eddy_fields)
+                      SeawaterBuoyancy, Smagorinsky, implicit_diffusion_solver, is_vertically_implicit, owns_eddy_fields)
 from .architectures import stream_ptr
 from .fields import CenterField, Field, XFaceField, YFaceField, ZFaceField, fill_halo_regions
 from .grids import Bounded, Flat, require_regular_xy
@@ -119,6 +119,10 @@ class NonhydrostaticModel:
         if closure is not None and not isinstance(closure, (ScalarDiffusivity, AnisotropicMinimumDissipation, Smagorinsky)):
             raise NotImplementedError("only closure = ScalarDiffusivity(...), AnisotropicMinimumDissipation(...), Smagorinsky(...) or "
                                       "SmagorinskyLilly(...) is implemented")
+        # closure = ScalarDiffusivity(VerticallyImplicitTimeDiscretization(), ...): a z-Bounded grid on one GPU, stepped by the Python host
+        implicit_diffusion_solver(closure, grid)
+        if is_vertically_implicit(closure) and hasattr(grid.architecture, "partition"):
+            raise NotImplementedError("a VerticallyImplicitTimeDiscretization closure on a Distributed architecture is not implemented (see DESIGN.md)")
         if isinstance(closure, Smagorinsky) and hasattr(grid.architecture, "partition"):
             raise NotImplementedError("closure = Smagorinsky / SmagorinskyLilly on a Distributed architecture is not implemented (see DESIGN.md)")
         if isinstance(closure, Smagorinsky) and grid.topology[2] == Flat:
@@ -244,6 +248,14 @@ class NonhydrostaticModel:
                 s is not None and (s.values is not None or s.func is not None) for b in bcs.values() for s in b.sides.values()):
             raise NotImplementedError("array / function boundary conditions on a Distributed architecture are not implemented")
         self._terms = self._make_terms()
+        # vertically implicit closure: every other term comes from the existing entry points, called with a copy of the terms whose closure
+        # is 0; the explicit part of the closure term is added by its own kernel and the implicit part follows every substep (implicit_step)
+        self._implicit = is_vertically_implicit(closure)
+        self._terms_noclosure = None
+        if self._implicit:
+            self._terms_noclosure = _lib.CModelTerms()
+            C.memmove(C.byref(self._terms_noclosure), C.byref(self._terms), C.sizeof(_lib.CModelTerms))
+            self._terms_noclosure.closure, self._terms_noclosure.nu = 0, 0.0
         # fused stage boundaries: tendencies (+ boundary fluxes) + the next substep in as few launches as possible.  Plain
         # WENO momentum uses the tiled kernel's epilogue; tracers and the §8(f) terms use the general fused entry points
         # (WENO advection only: the Centered(order=2) tracer kernel has no epilogue)
@@ -270,6 +282,8 @@ class NonhydrostaticModel:
                          and all(_fusable_conditions(b) for b in bcs.values()))
         self.fuse_stage_boundaries = (xy_periodic or walls_fusable) and ((not self._general_fused) or (
             isinstance(advection, (WENO, UpwindBiased)) and os.environ.get("OCN_FUSE_GENERAL", "1") != "0"))
+        if self._implicit:  # the column solves sit between a substep and the projection: the reference's launch sequence
+            self.fuse_stage_boundaries = False
         if not xy_periodic:
             if hasattr(grid.architecture, "partition") and not (
                     grid.topology[0] in ("Periodic", "FullyConnected", "RightConnected", "LeftConnected", "Bounded")
@@ -344,6 +358,8 @@ class NonhydrostaticModel:
                 t.T = self.field("T").ptr
             if b.constant_salinity is None:
                 t.S = self.field("S").ptr
+        if self._terms_noclosure is not None:
+            self._terms_noclosure.T, self._terms_noclosure.S = t.T, t.S
 
     def prognostic_fields(self):
         return self.velocities + self.tracers
@@ -500,7 +516,8 @@ def compute_tendencies_(model, rng=None, boundary_contributions=True):
     r = None if rng is None else _lib.i32_array(list(rng))
     s = stream_ptr()
     if model.general_terms:
-        t = C.byref(model._terms)
+        implicit = getattr(model, "_implicit", False)
+        t = C.byref(model._terms_noclosure if implicit else model._terms)
         frc = _refresh_forcing(model)
         if model._stokes is not None:
             model._stokes.refresh(model.clock.time)  # profiles that depend on t: sampled at the time of this tendency evaluation
@@ -517,7 +534,7 @@ def compute_tendencies_(model, rng=None, boundary_contributions=True):
             kappa, kappa_e = 0.0, None
             if model.diffusivity_fields is not None:
                 kappa_e = model.diffusivity_fields["kappa_e"][n].ptr
-            elif model.closure is not None:
+            elif model.closure is not None and not implicit:
                 kappa = model.closure.kappa_of(model.tracer_names[n])
             if frc[3 + n] is not None:
                 _lib.call("ocn_compute_tracer_tendency_terms_forced", g.cref, t, kappa, kappa_e, frc[3 + n], model.u.ptr, model.v.ptr, model.w.ptr,
@@ -525,6 +542,8 @@ def compute_tendencies_(model, rng=None, boundary_contributions=True):
                 continue
             _lib.call("ocn_compute_tracer_tendency_terms", g.cref, t, kappa, kappa_e, model.u.ptr, model.v.ptr, model.w.ptr, c.ptr,
                       Gn[3 + n].ptr, r, s)
+        if implicit:
+            add_vertically_implicit_explicit_fluxes(model, r)
         if boundary_contributions:
             compute_boundary_tendency_contributions(model)
         return
@@ -532,6 +551,27 @@ def compute_tendencies_(model, rng=None, boundary_contributions=True):
               Gn[2].ptr, r, s)
     for n, c in enumerate(model.tracers):
         _lib.call("ocn_compute_tracer_tendency", g.cref, model.u.ptr, model.v.ptr, model.w.ptr, c.ptr, Gn[3 + n].ptr, r, s)
+
+
+def add_vertically_implicit_explicit_fluxes(model, rng=None):
+    """The part of a vertically implicit closure's term that stays in the tendencies (abstract_scalar_diffusivity_closure.jl:214-260):
+    horizontal fluxes, the x / y fluxes of w, the bottom / top boundary fluxes and -ν ∂x w / -ν ∂y w in the z fluxes of u / v -- added to
+    Gⁿ, which holds every other term."""
+    Gn, nt = model.timestepper._Gn, len(model.tracers)
+    kappa = (C.c_double * max(nt, 1))(*[model.closure.kappa_of(n) for n in model.tracer_names])
+    _lib.call("ocn_add_vertically_implicit_explicit_fluxes", model.grid.cref, model.closure.nu, model.u.ptr, model.v.ptr, model.w.ptr,
+              Gn[0].ptr, Gn[1].ptr, Gn[2].ptr, nt, kappa, _lib.ptr_array([c.ptr for c in model.tracers] or [None]),
+              _lib.ptr_array([G.ptr for G in Gn[3:]] or [None]), rng, stream_ptr())
+
+
+def implicit_step(model, dt):
+    """implicit_step!(field, solver, closure, ..., Δt) of every prognostic field -- u, v, w, then the tracers with their own κ -- in one
+    launch: (1 - Δt ∂z κ ∂z) φⁿ⁺¹ = φ★ in place (vertically_implicit_diffusion_solver.jl).  Follows rk3_substep! with the stage Δt
+    Δt (γ + ζ) (runge_kutta_3.jl:157-180) and ab2_step! with Δt (quasi_adams_bashforth_2.jl:144)."""
+    prog = model.prognostic_fields()
+    kappa = [model.closure.nu] * 3 + [model.closure.kappa_of(n) for n in model.tracer_names]
+    _lib.call("ocn_implicit_vertical_diffusion_step", model.grid.cref, len(prog), _lib.ptr_array([f.ptr for f in prog]),
+              _lib.i32_array([f.loc for f in prog]), (C.c_double * len(prog))(*kappa), float(dt), stream_ptr())
 
 
 def _refresh_forcing(model):
@@ -796,6 +836,8 @@ def _project_and_advance(model, dt, stage_dt, gamma_next, zeta_next):
         if particles_dt is not None:
             step_lagrangian_particles(model, particles_dt)
         rk3_substep(model, dt, gamma_next, zeta_next)
+        if model._implicit:
+            implicit_step(model, dt * (gamma_next + zeta_next))  # stage_Δt(Δt, γⁿ, ζⁿ)
 
 
 def _time_step_rk3(model, dt):
@@ -812,6 +854,8 @@ def _time_step_rk3(model, dt):
         update_state_and_rk3_substep(model, dt, ts.g1, None, fill_halos=False)
     else:
         rk3_substep(model, dt, ts.g1, None)
+        if model._implicit:
+            implicit_step(model, first_stage_dt)
     clock.time += first_stage_dt
     clock.stage = 2
     clock.last_stage_dt = first_stage_dt
@@ -845,6 +889,8 @@ def _time_step_qab2(model, dt, euler=False):
     euler = euler or (dt != clock.last_dt)
     chi = -0.5 if euler else ts.chi
     ab2_step(model, dt, chi)
+    if model._implicit:
+        implicit_step(model, dt)
     clock.time += dt
     clock.iteration += 1
     clock.last_dt = dt
@@ -890,6 +936,9 @@ class RK3Driver:
 
     def __init__(self, model, own_solver=False, defer_correction=None):
         require_regular_xy(model.grid, "RK3Driver")
+        if getattr(model, "_implicit", False):
+            raise NotImplementedError("RK3Driver: a model with a VerticallyImplicitTimeDiscretization closure needs the Python host "
+                                      "(time_step(model, dt)): the library's time step has no implicit step")
         if getattr(model, "particles", None) is not None:
             raise NotImplementedError("RK3Driver: a model with particles needs the Python host (time_step(model, dt)): the library's time step "
                                       "does not step LagrangianParticles")
@@ -952,6 +1001,9 @@ class ModelRK3Driver:
 
     def __init__(self, model, own_solver=False):
         require_regular_xy(model.grid, "ModelRK3Driver")
+        if getattr(model, "_implicit", False):
+            raise NotImplementedError("ModelRK3Driver: a model with a VerticallyImplicitTimeDiscretization closure needs the Python host "
+                                      "(time_step(model, dt)): the library's time step has no implicit step")
         if getattr(model, "particles", None) is not None:
             raise NotImplementedError("ModelRK3Driver: a model with particles needs the Python host (time_step(model, dt)): the library's time "
                                       "step does not step LagrangianParticles")

@@ -2,7 +2,8 @@
 
   Centered(order=2)                               src/Advection/centered_reconstruction.jl:39-60 (the reference's default advection)
   FPlane(f=...) / FPlane(rotation_rate, latitude) src/Coriolis/f_plane.jl:8-42
-  ScalarDiffusivity(ν=..., κ=...)                 src/TurbulenceClosures/turbulence_closure_implementations/scalar_diffusivity.jl
+  ScalarDiffusivity([VerticallyImplicitTimeDiscretization()], ν=..., κ=...)
+                                                  src/TurbulenceClosures/turbulence_closure_implementations/scalar_diffusivity.jl
   Smagorinsky(coefficient=..., Pr=...), SmagorinskyLilly(C=..., Cb=..., Pr=...), LillyCoefficient(...)
                                                   .../turbulence_closure_implementations/Smagorinskys/{smagorinsky,lilly_coefficient}.jl
   BuoyancyTracer(), SeawaterBuoyancy(...), LinearEquationOfState(...)
@@ -112,17 +113,71 @@ class BetaPlane:
         self.f0, self.beta = float(f0), float(beta)
 
 
+class ExplicitTimeDiscretization:
+    """ExplicitTimeDiscretization() (TurbulenceClosures.jl): the closure's fluxes enter the tendencies"""
+
+    def __repr__(self):
+        return "ExplicitTimeDiscretization()"
+
+
+class VerticallyImplicitTimeDiscretization:
+    """VerticallyImplicitTimeDiscretization(): the vertical diffusion of u, v, w and the tracers is stepped with backward Euler -- a
+    tridiagonal solve per column after every rk3_substep! / ab2_step! (vertically_implicit_diffusion_solver.jl) -- and only the boundary
+    fluxes and the horizontal fluxes stay in the tendencies (abstract_scalar_diffusivity_closure.jl:214-260)."""
+
+    def __repr__(self):
+        return "VerticallyImplicitTimeDiscretization()"
+
+
+def as_time_discretization(td):
+    """an instance, or one of the strings "Explicit" / "VerticallyImplicit" -> an instance"""
+    if isinstance(td, (ExplicitTimeDiscretization, VerticallyImplicitTimeDiscretization)):
+        return td
+    if td in (ExplicitTimeDiscretization, "Explicit", "ExplicitTimeDiscretization"):
+        return ExplicitTimeDiscretization()
+    if td in (VerticallyImplicitTimeDiscretization, "VerticallyImplicit", "VerticallyImplicitTimeDiscretization"):
+        return VerticallyImplicitTimeDiscretization()
+    raise ValueError(f"time_discretization must be ExplicitTimeDiscretization() or VerticallyImplicitTimeDiscretization(), got {td!r}")
+
+
+def is_vertically_implicit(closure):
+    """is_vertically_implicit(closure) (vertically_implicit_diffusion_solver.jl)"""
+    return isinstance(getattr(closure, "time_discretization", None), VerticallyImplicitTimeDiscretization)
+
+
+def implicit_diffusion_solver(closure, grid):
+    """implicit_diffusion_solver(time_discretization, grid) (vertically_implicit_diffusion_solver.jl:193-205) reduced to its check: the
+    solver itself is a kernel that keeps no state (ocn_implicit_vertical_diffusion_step)."""
+    if is_vertically_implicit(closure) and grid.topology[2] != "Bounded":
+        raise ValueError("VerticallyImplicitTimeDiscretization can only be specified on grids that are Bounded in the z-direction.")
+
+
 class ScalarDiffusivity:
-    """ScalarDiffusivity(; ν=0, κ=0): ExplicitTimeDiscretization, ThreeDimensionalFormulation, constant coefficients.
+    """ScalarDiffusivity([time_discretization]; ν=0, κ=0): ExplicitTimeDiscretization() (default) or
+    VerticallyImplicitTimeDiscretization() -- as the first positional argument, as in the reference, or `time_discretization=` (an instance
+    or "Explicit" / "VerticallyImplicit") --, ThreeDimensionalFormulation, constant coefficients.
     κ is a number (every tracer) or a dict {tracer name: κ}."""
 
-    def __init__(self, nu=0.0, kappa=0.0, time_discretization="Explicit", formulation="ThreeDimensional", **kw):
-        nu = kw.pop("ν", nu)
-        kappa = kw.pop("κ", kappa)
+    def __init__(self, *args, **kw):
+        if args and (isinstance(args[0], (ExplicitTimeDiscretization, VerticallyImplicitTimeDiscretization))
+                     or args[0] in (ExplicitTimeDiscretization, VerticallyImplicitTimeDiscretization)):
+            if "time_discretization" in kw:
+                raise TypeError("time_discretization given twice")
+            kw["time_discretization"], args = args[0], args[1:]
+        names = ("nu", "kappa", "time_discretization", "formulation")
+        if len(args) > len(names):
+            raise TypeError(f"ScalarDiffusivity takes at most {len(names)} positional arguments after the time discretization")
+        for name, value in zip(names, args):
+            if name in kw:
+                raise TypeError(f"{name} given twice")
+            kw[name] = value
+        nu = kw.pop("ν", kw.pop("nu", 0.0))
+        kappa = kw.pop("κ", kw.pop("kappa", 0.0))
+        time_discretization = kw.pop("time_discretization", "Explicit")
+        formulation = kw.pop("formulation", "ThreeDimensional")
         if kw:
             raise TypeError(f"unexpected keyword arguments {sorted(kw)}")
-        if time_discretization != "Explicit":
-            raise NotImplementedError("VerticallyImplicitTimeDiscretization is not implemented")
+        self.time_discretization = as_time_discretization(time_discretization)
         if formulation != "ThreeDimensional":
             raise NotImplementedError("only the ThreeDimensionalFormulation (isotropic) is implemented")
         if callable(nu) or callable(kappa) or np.ndim(nu) > 0:  # (numpy scalars are numbers)
@@ -187,7 +242,7 @@ class Smagorinsky:
     ExplicitTimeDiscretization only."""
 
     def __init__(self, coefficient=0.16, Pr=1.0, time_discretization="Explicit"):
-        if time_discretization != "Explicit":
+        if not isinstance(as_time_discretization(time_discretization), ExplicitTimeDiscretization):
             raise NotImplementedError("VerticallyImplicitTimeDiscretization is not implemented")
         if isinstance(coefficient, type) or callable(coefficient):
             raise NotImplementedError("only a number or a LillyCoefficient is implemented as the Smagorinsky coefficient")
