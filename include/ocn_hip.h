@@ -976,6 +976,15 @@ typedef struct ocn_op_program {
  *
  * compute!(Field(operation)): `out` is the parent array of a field at program->loc; its interior is written, its halos are not. */
 int ocn_op_compute(const ocn_grid *grid, const ocn_op_program *program, double *out, void *stream);
+/* A boundary function with field dependencies (ContinuousBoundaryFunction, continuous_boundary_function.jl:124-157), lowered to a program:
+ * evaluated at every point (a1, a2) of one boundary plane -- side 0..5 = west, east, south, north, bottom, top, which must lie on a Bounded
+ * direction; the two tangential directions in the order x, y, z, N points along each whatever the location -- with the boundary-normal
+ * index fixed at I = 1 (west, south, bottom) or N (east, north, top), as domain_boundary_indices gives it for indexing the dependencies.
+ * The result goes to values[(a1 - 1) + n1 (a2 - 1)]: the layout of ocn_bc.values, so a flux condition whose `values` is this array is
+ * applied by ocn_apply_flux_bcs like any array-valued one.  program->loc is the location of the conditioned field (checked, otherwise
+ * unused: the index space is the plane); LOAD / SPACING offsets are validated for every point of the plane, not of the volume.
+ * Nothing but values[0 .. n1 n2 - 1] is written; no atomics, no allocation, no synchronisation. */
+int ocn_op_compute_boundary(const ocn_grid *grid, const ocn_op_program *program, int32_t side, double *values, void *stream);
 /* Number of doubles of workspace ocn_op_reduce needs for a tree at `loc` reduced over `dims` (bit d: direction d; 1..7). */
 int ocn_op_reduce_workspace(const ocn_grid *grid, int32_t loc, int32_t dims, int64_t *n_doubles);
 /* sum! of the program over `dims`, fused with its evaluation.  `out` is the parent array of the reduced field: extent 1 and no halo along

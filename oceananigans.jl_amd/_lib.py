@@ -238,6 +238,7 @@ _SIGS = {
     "ocn_advect_particles": [C.POINTER(CGrid), C.POINTER(CParticleGeometry), C.c_int64, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _dbl, _i32, C.POINTER(_vp),
                              C.POINTER(_i32), C.POINTER(_vp), _vp],
     "ocn_op_compute": [C.POINTER(CGrid), C.POINTER(COpProgram), _vp, _vp],
+    "ocn_op_compute_boundary": [C.POINTER(CGrid), C.POINTER(COpProgram), _i32, _vp, _vp],
     "ocn_op_reduce_workspace": [C.POINTER(CGrid), _i32, _i32, C.POINTER(C.c_int64)],
     "ocn_op_reduce": [C.POINTER(CGrid), C.POINTER(COpProgram), _i32, _dbl, _vp, C.c_int64, _vp, _vp],
     "ocn_halo_plane_x": [C.POINTER(CGrid), _vp, _i32, _i32, _vp, _i32, _vp],

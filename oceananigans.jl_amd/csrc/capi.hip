@@ -798,6 +798,11 @@ int ocn_op_compute(const ocn_grid *grid, const ocn_op_program *program, double *
     return op_compute(grid, program, out, as_stream(stream));
 }
 
+int ocn_op_compute_boundary(const ocn_grid *grid, const ocn_op_program *program, int32_t side, double *values, void *stream)
+{
+    return op_compute_boundary(grid, program, side, values, as_stream(stream));
+}
+
 int ocn_op_reduce_workspace(const ocn_grid *grid, int32_t loc, int32_t dims, int64_t *n_doubles)
 {
     long long n = 0;

@@ -18,6 +18,10 @@
 // Reductions: a wave owns a task = (output element or 64 of them, a contiguous chunk of the reduced rows); a lane adds its cells in index
 // order; where x is reduced the 64 lane sums are folded by shuffles.  The partial sums go to a workspace and a second small launch adds
 // them in a fixed order (across waves through LDS where an element has many partials) and divides: no atomics anywhere.
+//
+// Boundary functions (ContinuousBoundaryFunction with field_dependencies, src/BoundaryConditions/continuous_boundary_function.jl:124-157):
+// the same interpreter on one boundary plane of the grid, the boundary-normal index fixed at domain_boundary_indices' I; the result goes
+// to the array a flux condition's ocn_bc.values points to, which the apply_flux_bcs* kernels read as they read any array-valued condition.
 #include <algorithm>
 #include <cmath>
 
@@ -141,6 +145,30 @@ __global__ __launch_bounds__(OP_BLOCK) void op_compute_kernel(GridDev g, OpProgr
     if (two) out[O.o + i + O.s2 * jj[1] + O.s3 * k] = v[1];
 }
 
+// One boundary plane: the point (a1, a2) of the two tangential directions (first one fastest, as ocn_bc.values is indexed), the normal index
+// fixed at I0.  A block covers 64 x 8 points; a lane takes the points a2 and a2 + 4, as op_compute_kernel does with its rows.
+// axis 2 (bottom / top) and axis 1 (south / north) have x as a1, so consecutive lanes load consecutive doubles; on axis 0 (west / east)
+// a1 is y and the loads are a row apart.  Those planes are Ny x Nz points of a run whose cost is Nx x Ny x Nz per launch: not tuned.
+struct OpPlane {
+    int axis, I0, n1, n2;
+};
+__global__ __launch_bounds__(OP_BLOCK) void op_boundary_kernel(GridDev g, OpProgramDev P, OpPlane B, double *__restrict__ values)
+{
+    extern __shared__ double regs[];  // n_registers x OP_CELLS x OP_BLOCK
+    const int a1 = blockIdx.x * 64 + threadIdx.x, b0 = blockIdx.y * 8 + threadIdx.y;
+    if (a1 >= B.n1 || b0 >= B.n2) return;
+    const bool two = b0 + 4 < B.n2;  // (a missing second point repeats the first: always in bounds, never stored)
+    const int b1 = two ? b0 + 4 : b0;
+    // (i, j, k) = (I0, a1, a2) on west / east, (a1, I0, a2) on south / north, (a1, a2, I0) on bottom / top
+    const int ii[OP_CELLS] = {B.axis == 0 ? B.I0 : a1, B.axis == 0 ? B.I0 : a1};
+    const int jj[OP_CELLS] = {B.axis == 0 ? a1 : (B.axis == 1 ? B.I0 : b0), B.axis == 0 ? a1 : (B.axis == 1 ? B.I0 : b1)};
+    const int kk[OP_CELLS] = {B.axis == 2 ? B.I0 : b0, B.axis == 2 ? B.I0 : b1};
+    double v[OP_CELLS];
+    op_eval(P, g, regs + threadIdx.y * 64 + threadIdx.x, ii, jj, kk, v);
+    values[a1 + (long long)B.n1 * b0] = v[0];
+    if (two) values[a1 + (long long)B.n1 * b1] = v[1];
+}
+
 template <bool XRED>
 __global__ __launch_bounds__(OP_BLOCK) void op_reduce_kernel(GridDev g, OpProgramDev P, OpReduceGeom G, double *__restrict__ ws)
 {
@@ -214,6 +242,7 @@ __global__ __launch_bounds__(OP_BLOCK) void op_finish_kernel(const double *__res
 // ---- host -------------------------------------------------------------------------------------------------------------------------
 struct OpSpace {
     int N[3], H[3], topo[3], n[3];  // n: interior extents of the tree's location
+    int lo[3], hi[3];               // the 0-based indices the program runs over: 0 .. n - 1, or one index along the normal of a boundary plane
 };
 static int op_space(const ocn_grid *grid, int loc, const char *who, OpSpace &S)
 {
@@ -225,7 +254,22 @@ static int op_space(const ocn_grid *grid, int loc, const char *who, OpSpace &S)
     for (int d = 0; d < 3; ++d) {
         S.N[d] = N[d]; S.H[d] = H[d]; S.topo[d] = T[d];
         S.n[d] = T[d] == OCN_FLAT ? 1 : N[d] + ((((loc >> d) & 1) && T[d] == OCN_BOUNDED) ? 1 : 0);
+        S.lo[d] = 0; S.hi[d] = S.n[d] - 1;
     }
+    return OCN_SUCCESS;
+}
+// The index space of a boundary plane (side 0..5 = west, east, south, north, bottom, top): N points along the two tangential directions
+// -- the extents of ocn_bc.values, whatever the location -- and the one index I - 1 of domain_boundary_indices along the normal
+static int op_plane(OpSpace &S, int side, const char *who)
+{
+    OCN_REQUIRE(side >= 0 && side <= 5, "%s: side %d outside 0..5 (west, east, south, north, bottom, top)", who, side);
+    const int dn = side >> 1;
+    OCN_REQUIRE(S.topo[dn] == OCN_BOUNDED, "%s: side %d lies on direction %d, which is not Bounded", who, side, dn);
+    for (int d = 0; d < 3; ++d) {
+        S.n[d] = d == dn ? 1 : S.N[d];
+        S.lo[d] = 0; S.hi[d] = S.n[d] - 1;
+    }
+    S.lo[dn] = S.hi[dn] = (side & 1) ? S.N[dn] - 1 : 0;
     return OCN_SUCCESS;
 }
 // parent layout of a field at `loc` reduced along the directions of `reduced`
@@ -237,11 +281,16 @@ static void op_layout(const OpSpace &S, int loc, int reduced, long long ext[3], 
     for (int d = 0; d < 3; ++d) o += ((reduced >> d) & 1) ? 0 : S.H[d] * stride[d];
 }
 
-static int op_validate(const ocn_grid *grid, const ocn_op_program *p, const char *who, OpSpace &S, OpProgramDev &D)
+// side == nullptr: the program runs over the interior of its location; otherwise over the boundary plane *side
+static int op_validate(const ocn_grid *grid, const ocn_op_program *p, const char *who, OpSpace &S, OpProgramDev &D, const int *side = nullptr)
 {
     OCN_REQUIRE(grid && p, "%s: null grid or program", who);
     int st = op_space(grid, p->loc, who, S);
     if (st != OCN_SUCCESS) return st;
+    if (side) {
+        st = op_plane(S, *side, who);
+        if (st != OCN_SUCCESS) return st;
+    }
     OCN_REQUIRE(p->n_instructions >= 1 && p->n_instructions <= OCN_OP_MAX_INSTRUCTIONS, "%s: %d instructions outside 1..%d", who,
                 p->n_instructions, OCN_OP_MAX_INSTRUCTIONS);
     OCN_REQUIRE(p->n_registers >= 1 && p->n_registers <= OCN_OP_MAX_REGISTERS, "%s: %d registers outside 1..%d", who, p->n_registers,
@@ -281,8 +330,8 @@ static int op_validate(const ocn_grid *grid, const ocn_op_program *p, const char
                     OCN_REQUIRE(off[d] == 0, "%s: instruction %d: offset %d along direction %d, in which field %d is reduced", who, q, off[d], d, f);
                     continue;
                 }
-                // the cells 0 .. n - 1 of the index space, shifted, must lie in the field's parent array along d
-                const long long lo = (long long)S.H[d] + off[d], hi = (long long)S.H[d] + (S.n[d] - 1) + off[d];
+                // the cells lo .. hi of the index space, shifted, must lie in the field's parent array along d
+                const long long lo = (long long)S.H[d] + S.lo[d] + off[d], hi = (long long)S.H[d] + S.hi[d] + off[d];
                 OCN_REQUIRE(lo >= 0 && hi <= ext[f][d] - 1, "%s: instruction %d: offset %d along direction %d reaches beyond the halo (%d) of field %d",
                             who, q, off[d], d, S.H[d], f);
                 imm += off[d] * stride[f][d];
@@ -297,7 +346,7 @@ static int op_validate(const ocn_grid *grid, const ocn_op_program *p, const char
             J.a = (unsigned char)I.field;
             if (I.field >= 2 && grid->dzc) {
                 OCN_REQUIRE(grid->dzf, "%s: dzc without dzf", who);
-                const long long lo = (long long)S.H[2] + I.dk, hi = (long long)S.H[2] + (S.n[2] - 1) + I.dk;
+                const long long lo = (long long)S.H[2] + S.lo[2] + I.dk, hi = (long long)S.H[2] + S.hi[2] + I.dk;
                 OCN_REQUIRE(lo >= 0 && hi <= S.N[2] + 2LL * S.H[2] - 1, "%s: instruction %d: z spacing offset %d reaches beyond the halo (%d)", who, q,
                             I.dk, S.H[2]);
                 J.imm = S.H[2] + I.dk;
@@ -362,6 +411,25 @@ int op_compute(const ocn_grid *grid, const ocn_op_program *p, double *out, hipSt
     const dim3 block(64, 4, 1), nb((S.n[0] + 63) / 64, (S.n[1] + 7) / 8, S.n[2]);
     OCN_REQUIRE(nb.y <= 65535u && nb.z <= 65535u, "ocn_op_compute: grid too large for one launch");
     hipLaunchKernelGGL(op_compute_kernel, nb, block, op_lds_bytes(p), stream, to_dev(*grid), D, S.n[0], S.n[1], out, O);
+    OCN_CHECK_HIP(hipGetLastError());
+    return OCN_SUCCESS;
+}
+
+int op_compute_boundary(const ocn_grid *grid, const ocn_op_program *p, int side, double *values, hipStream_t stream)
+{
+    OpSpace S;
+    OpProgramDev D;
+    int st = op_validate(grid, p, "ocn_op_compute_boundary", S, D, &side);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(values, "ocn_op_compute_boundary: null values pointer");
+    OpPlane B;
+    B.axis = side >> 1;
+    B.I0 = S.lo[B.axis];
+    B.n1 = S.n[B.axis == 0 ? 1 : 0];
+    B.n2 = S.n[B.axis == 2 ? 1 : 2];
+    const dim3 block(64, 4, 1), nb((B.n1 + 63) / 64, (B.n2 + 7) / 8, 1);
+    OCN_REQUIRE(nb.y <= 65535u, "ocn_op_compute_boundary: plane too large for one launch");
+    hipLaunchKernelGGL(op_boundary_kernel, nb, block, op_lds_bytes(p), stream, to_dev(*grid), D, B, values);
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
 }

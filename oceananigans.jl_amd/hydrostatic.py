@@ -163,6 +163,10 @@ class HydrostaticFreeSurfaceModel:
             raise NotImplementedError("stokes_drift on HydrostaticFreeSurfaceModel is not implemented (NonhydrostaticModel takes UniformStokesDrift)")
         if forcing is not None:
             raise NotImplementedError("forcing on HydrostaticFreeSurfaceModel is not implemented (NonhydrostaticModel takes forcing=; see DESIGN.md §10)")
+        for b in (boundary_conditions or {}).values():
+            if hasattr(b, "field_dependent") and b.field_dependent():
+                raise NotImplementedError("HydrostaticFreeSurfaceModel: boundary conditions with field_dependencies are not implemented "
+                                          "(NonhydrostaticModel takes them; see DESIGN.md §5.2i)")
         require_regular_xy(grid, "HydrostaticFreeSurfaceModel")
         timestepper = str(timestepper).lstrip(":")
         if timestepper not in ("QuasiAdamsBashforth2", "SplitRungeKutta3"):

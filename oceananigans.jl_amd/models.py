@@ -13,7 +13,9 @@ Julia's `f!` names are spelled `f` here.  background_fields is `nothing`; forcin
 (forcings.py); stokes_drift is UniformStokesDrift (stokes.py); particles is LagrangianParticles (particles.py: stepped after every
 update_state! of a stage, as step_lagrangian_particles! in runge_kutta_3.jl:111, 127, 148 and quasi_adams_bashforth_2.jl:108); advection is WENO()
 or Centered(); coriolis = FPlane, closure = ScalarDiffusivity (explicit or vertically implicit) / AnisotropicMinimumDissipation / Smagorinsky(Lilly), buoyancy = BuoyancyTracer / SeawaterBuoyancy and bottom /
-top Flux / Value / Gradient boundary conditions are the SURVEY §8(f) rank-1 terms (physics.py); anything else raises.
+top Flux / Value / Gradient boundary conditions are the SURVEY §8(f) rank-1 terms (physics.py); flux conditions that are functions of the
+model's fields (field_dependencies) are traced at construction and evaluated on the device in update_state (boundary_functions.py);
+anything else raises.
 """
 import math
 
@@ -35,6 +37,7 @@ from .solvers import nonhydrostatic_pressure_solver
 from .stokes import DeviceStokesDrift, UniformStokesDrift
 from .forcings import DeviceForcing, field_location, validate_forcing
 from .particles import LagrangianParticles, step_lagrangian_particles
+from .boundary_functions import BoundaryFunction, validate_dependencies
 
 
 class Clock:
@@ -177,6 +180,18 @@ class NonhydrostaticModel:
                 raise ValueError(f"boundary conditions given for unknown field {name!r}")
             if not isinstance(bcs[name], FieldBoundaryConditions):
                 raise TypeError("boundary_conditions values must be FieldBoundaryConditions")
+        # flux conditions that are functions of the model's fields (field_dependencies): refused here, before anything is allocated, where
+        # they cannot be evaluated
+        for b in ([nu_bcs] if nu_bcs is not None else []) + list(kappa_bcs.values()):
+            if isinstance(b, FieldBoundaryConditions) and b.field_dependent():
+                raise NotImplementedError("a boundary condition with field_dependencies on a νₑ / κₑ field is not implemented: the dependencies "
+                                          "are velocities and tracers, evaluated for the prognostic fields only (see DESIGN.md §5.2i)")
+        for name, b in bcs.items():
+            for side, condition in b.field_dependent():
+                if hasattr(grid.architecture, "partition"):
+                    raise NotImplementedError("boundary conditions with field_dependencies on a Distributed architecture are not implemented "
+                                              "(see DESIGN.md §5.2i)")
+                validate_dependencies(condition.field_dependencies, ("u", "v", "w") + tracers)
         # validate_boundary_condition_topology (boundary_condition.jl:128-136) + the impenetrable wall-normal component
         normal = {"u": ("west", "east"), "v": ("south", "north"), "w": ("bottom", "top")}
         # (a rank-local grid answers with the topology of the GLOBAL grid: the slabs of a Bounded x are RightConnected / FullyConnected /
@@ -247,6 +262,10 @@ class NonhydrostaticModel:
         if self._has_user_bcs and hasattr(grid.architecture, "partition") and any(
                 s is not None and (s.values is not None or s.func is not None) for b in bcs.values() for s in b.sides.values()):
             raise NotImplementedError("array / function boundary conditions on a Distributed architecture are not implemented")
+        # field-dependent flux conditions: traced once, here (boundary_functions.py); evaluated on the device by update_state
+        model_fields = dict(zip(("u", "v", "w") + tracers, self.prognostic_fields()))
+        self._boundary_functions = [BoundaryFunction(condition, grid, f.loc, side, model_fields, self.clock.time)
+                                    for name, f in model_fields.items() if name in bcs for side, condition in bcs[name].field_dependent()]
         self._terms = self._make_terms()
         # vertically implicit closure: every other term comes from the existing entry points, called with a copy of the terms whose closure
         # is 0; the explicit part of the closure term is added by its own kernel and the implicit part follows every substep (implicit_step)
@@ -283,6 +302,8 @@ class NonhydrostaticModel:
         self.fuse_stage_boundaries = (xy_periodic or walls_fusable) and ((not self._general_fused) or (
             isinstance(advection, (WENO, UpwindBiased)) and os.environ.get("OCN_FUSE_GENERAL", "1") != "0"))
         if self._implicit:  # the column solves sit between a substep and the projection: the reference's launch sequence
+            self.fuse_stage_boundaries = False
+        if self._boundary_functions:  # evaluated between the halo fill and the tendencies of every update_state!: the reference's sequence
             self.fuse_stage_boundaries = False
         if not xy_periodic:
             if hasattr(grid.architecture, "partition") and not (
@@ -433,9 +454,19 @@ def update_state(model, compute_tendencies=True, defer_exchange=False):
     if arch_hook is not None:  # Distributed: async exchange overlapped with interior tendencies
         return arch_hook(model, compute_tendencies, defer_exchange) if defer_exchange else arch_hook(model, compute_tendencies)
     fill_halo_regions(model.prognostic_fields(), fill_boundary_normal_velocities=False)
+    compute_boundary_functions(model)
     compute_auxiliaries(model)
     if compute_tendencies:
         compute_tendencies_(model)
+
+
+def compute_boundary_functions(model):
+    """getbc of the flux conditions with field_dependencies (continuous_boundary_function.jl:124-157), which the reference calls inside
+    apply_x/y/z_bcs!: one small launch per condition writes its values, at the clock time of this moment, into the array the flux
+    kernels read.  Needs the halos of the prognostic fields (the tangential interpolations read them) and precedes
+    compute_boundary_tendency_contributions."""
+    for f in getattr(model, "_boundary_functions", ()):
+        f.compute(model.clock.time)
 
 
 def compute_auxiliaries(model):
@@ -936,6 +967,9 @@ class RK3Driver:
 
     def __init__(self, model, own_solver=False, defer_correction=None):
         require_regular_xy(model.grid, "RK3Driver")
+        if getattr(model, "_boundary_functions", None):
+            raise NotImplementedError("RK3Driver: a model with boundary conditions that have field_dependencies needs the Python host "
+                                      "(time_step(model, dt)): the library's time step does not evaluate them")
         if getattr(model, "_implicit", False):
             raise NotImplementedError("RK3Driver: a model with a VerticallyImplicitTimeDiscretization closure needs the Python host "
                                       "(time_step(model, dt)): the library's time step has no implicit step")
@@ -1001,6 +1035,9 @@ class ModelRK3Driver:
 
     def __init__(self, model, own_solver=False):
         require_regular_xy(model.grid, "ModelRK3Driver")
+        if getattr(model, "_boundary_functions", None):
+            raise NotImplementedError("ModelRK3Driver: a model with boundary conditions that have field_dependencies needs the Python host "
+                                      "(time_step(model, dt)): the library's time step does not evaluate them")
         if getattr(model, "_implicit", False):
             raise NotImplementedError("ModelRK3Driver: a model with a VerticallyImplicitTimeDiscretization closure needs the Python host "
                                       "(time_step(model, dt)): the library's time step has no implicit step")

@@ -66,6 +66,12 @@ class AbstractOperation:
     def __neg__(self): return unary_operation("neg", self)
     def __pow__(self, n): return power(self, n)
 
+    def _no_branch(self, *other):
+        raise TypeError("an operation has no truth value and no order: it is a tree that is evaluated on the device, cell by cell.  A function "
+                        "that is traced with symbolic operands (a boundary function with field_dependencies) cannot branch on them")
+
+    __bool__ = __lt__ = __le__ = __gt__ = __ge__ = _no_branch
+
 
 def _validate_grid(*operands):
     """validate_grid (grid_validation.jl): the one grid of all field-like operands"""
@@ -146,10 +152,16 @@ def power(a, n):
 
 
 def sqrt(a):
+    """sqrt of a number, of a field / an operation (a tree node) or of a NumPy array (np.sqrt: one function body then serves the device
+    and a NumPy check of it)"""
+    if isinstance(a, np.ndarray):
+        return np.sqrt(a)
     return float(np.sqrt(a)) if _is_number(a) else unary_operation("sqrt", a)
 
 
 def abs(a):  # noqa: A001 (mirrors the reference's Base.abs on fields)
+    if isinstance(a, np.ndarray):
+        return np.abs(a)
     return float(np.abs(a)) if _is_number(a) else unary_operation("abs", a)
 
 

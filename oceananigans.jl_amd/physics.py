@@ -346,12 +346,30 @@ class BoundaryCondition:
     ContinuousBoundaryFunction  f(x, y, t, c, p) = p * c  with field_dependencies = the field itself as
     condition + coeff * c[i, j, boundary-adjacent cell] (include/ocn_hip.h: struct ocn_bc)."""
 
-    def __init__(self, kind, condition=0.0, coeff=0.0, parameters=None):
-        """condition: a number, an (Nx, Ny) array, or a function f(x, y, t) [f(x, y, t, parameters) with `parameters`] of the two
+    def __init__(self, kind, condition=0.0, coeff=0.0, parameters=None, field_dependencies=(), discrete_form=False):
+        """field_dependencies (flux conditions only): a name or a tuple of names of velocities and tracers of the model; `condition` is then a
+        function f(ξ, η, t, *dependencies[, parameters]) that is traced once and evaluated on the device (boundary_functions.py).
+        condition: a number, an (Nx, Ny) array, or a function f(x, y, t) [f(x, y, t, parameters) with `parameters`] of the two
         coordinates tangential to a bottom / top boundary (without those of Flat directions: f(x, t) on an x-z slice) and time -- the reference's ContinuousBoundaryFunction without field
         dependencies (continuous_boundary_function.jl:17-115).  The function is evaluated on the host at the field's own nodes (called
         once with broadcastable arrays) every time the model state is updated, with the clock time of that moment, and uploaded into
         the (Nx, Ny) device array the kernels read."""
+        if discrete_form:
+            raise NotImplementedError("discrete_form=True: boundary functions f(i, j, grid, clock, model_fields) are not implemented -- the library is "
+                                      "compiled ahead of time and takes no kernel functions (see DESIGN.md §5.2i)")
+        field_dependencies = (field_dependencies,) if isinstance(field_dependencies, str) else tuple(field_dependencies)
+        if field_dependencies:
+            if kind != _lib.BC_FLUX:
+                raise NotImplementedError("field_dependencies on a Value, Gradient or Open boundary condition are not implemented: those conditions "
+                                          "are evaluated inside the halo fills, where the tangential halos of the other fields are not defined "
+                                          "yet; FluxBoundaryCondition takes them (see DESIGN.md §5.2i)")
+            if any(not isinstance(n, str) for n in field_dependencies):
+                raise TypeError("field_dependencies must be a name or a tuple of names of model fields")
+            if not callable(condition):
+                raise TypeError("field_dependencies need a function f(ξ, η, t, *dependencies[, parameters]) as the condition")
+            if coeff != 0.0:
+                raise ValueError("coeff together with field_dependencies: name the field itself among the dependencies instead")
+        self.field_dependencies = field_dependencies
         self.kind = kind
         self.coeff = float(coeff)
         self.values = None
@@ -378,7 +396,7 @@ class BoundaryCondition:
         """Re-evaluate a function-valued condition at `time` (no-op otherwise): f(ξ, η, t[, p]) of the two coordinates tangential to the
         boundary -- (x, y) on bottom / top, (y, z) on west / east, (x, z) on south / north -- at the field's own nodes there
         (continuous_boundary_function.jl:17-115: the reference's ContinuousBoundaryFunction without field dependencies)."""
-        if self.func is None:
+        if self.func is None or self.field_dependencies:  # (a function of the model's fields is evaluated on the device: models.py)
             return
         d1, d2 = self._TANGENTIAL[side]
         n1, n2 = self._extents(grid, side)
@@ -408,26 +426,32 @@ class BoundaryCondition:
             if self._device_values is None:
                 self._device_values = on_architecture(grid.architecture, self.values)
             ptr = self._device_values.data_ptr()
+        elif self.field_dependencies:  # the array ocn_op_compute_boundary writes (boundary_functions.BoundaryFunction)
+            ptr = self._device_values.data_ptr()
         return _lib.CBc(self.kind, 0, self.value, self.coeff, ptr)
 
 
-def FluxBoundaryCondition(condition=0.0, coeff=0.0, parameters=None):
-    return BoundaryCondition(_lib.BC_FLUX, condition, coeff, parameters)
+def FluxBoundaryCondition(condition=0.0, coeff=0.0, parameters=None, field_dependencies=(), discrete_form=False):
+    """FluxBoundaryCondition(condition; parameters, field_dependencies): with field_dependencies = a name or a tuple of names of velocities
+    and tracers, `condition` is the reference's f(ξ, η, t, *dependencies[, parameters]) -- quadratic drag is
+    lambda x, y, t, u, v, p: -p["cd"] * ocn.sqrt(u ** 2 + v ** 2) * u -- traced once and evaluated on the device at every tendency evaluation"""
+    return BoundaryCondition(_lib.BC_FLUX, condition, coeff, parameters, field_dependencies, discrete_form)
 
 
-def ValueBoundaryCondition(condition=0.0, parameters=None):
-    return BoundaryCondition(_lib.BC_VALUE, condition, parameters=parameters)
+def ValueBoundaryCondition(condition=0.0, parameters=None, field_dependencies=(), discrete_form=False):
+    return BoundaryCondition(_lib.BC_VALUE, condition, parameters=parameters, field_dependencies=field_dependencies, discrete_form=discrete_form)
 
 
-def GradientBoundaryCondition(condition=0.0, parameters=None):
-    return BoundaryCondition(_lib.BC_GRADIENT, condition, parameters=parameters)
+def GradientBoundaryCondition(condition=0.0, parameters=None, field_dependencies=(), discrete_form=False):
+    return BoundaryCondition(_lib.BC_GRADIENT, condition, parameters=parameters, field_dependencies=field_dependencies,
+                             discrete_form=discrete_form)
 
 
-def OpenBoundaryCondition(condition=0.0, parameters=None):
+def OpenBoundaryCondition(condition=0.0, parameters=None, field_dependencies=(), discrete_form=False):
     """OpenBoundaryCondition(value) on the side a velocity component is normal to: that component ON the boundary face is set to the
     value (a number, an array over the tangential directions or a function of the tangential coordinates and time) by every halo fill
     that fills boundary-normal velocities (fill_halo_regions_open.jl:9-70); the default Impenetrable condition is Open(nothing) = 0."""
-    return BoundaryCondition(_lib.BC_OPEN, condition, parameters=parameters)
+    return BoundaryCondition(_lib.BC_OPEN, condition, parameters=parameters, field_dependencies=field_dependencies, discrete_form=discrete_form)
 
 
 class FieldBoundaryConditions:
@@ -456,6 +480,10 @@ class FieldBoundaryConditions:
 
     def has_flux(self):
         return any(v is not None and v.kind == _lib.BC_FLUX for v in self.sides.values())
+
+    def field_dependent(self):
+        """(side, condition) of the conditions that are functions of the model's fields"""
+        return [(k, v) for k, v in self.sides.items() if v is not None and v.field_dependencies]
 
     def c_struct(self, grid):
         if self._c is None:
