@@ -214,7 +214,9 @@ __global__ __launch_bounds__(256, 3) void amd_fused_kernel(GridDev g, double Cnu
 #define AMD_Q(num, den) ((num) / (den))
 #else
     const double d2 = 3 * fast_rcp((rFx * rFx + rFy * rFy) + rFz[0] * rFz[0]);
-#define AMD_Q(num, den) ((num) * fast_rcp(den))
+    // q and σ are sums of squares of gradients: nonzero but below 2^-1024 for fields of ~1e-154 and less, where v_rcp_f64 overflows and
+    // the Newton steps of fast_rcp turn the inf into NaN (strict: 0 / q = 0).  Such a denominator takes the IEEE division.
+#define AMD_Q(num, den) ((den) >= 0x1p-1000 ? (num) * fast_rcp(den) : (num) / (den))
 #endif
 
     if (nu_e) {

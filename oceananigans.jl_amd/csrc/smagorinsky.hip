@@ -189,7 +189,8 @@ __global__ __launch_bounds__(256, 4) void smagorinsky_kernel(GridDev g, SmagArgs
 #if OCN_STRICT
             const double ratio = p.Cb * N2p / S2;
 #else
-            const double ratio = p.Cb * N2p * fast_rcp(S2);
+            // (fast_rcp of a nonzero Σ² below 2^-1024 is NaN -- the ratio then compared as >= 1 and νₑ came out 0: IEEE division there)
+            const double ratio = S2 >= 0x1p-1000 ? p.Cb * N2p * fast_rcp(S2) : p.Cb * N2p / S2;
 #endif
             const double sig = S2 == 0 ? 0.0 : sqrt(1.0 - (ratio < 1.0 ? ratio : 1.0));
             cs2 = sig * p.C2;

@@ -9,7 +9,10 @@
 
 Nested-halves 2x2 averages (ℑy(ℑx), ℑz(ℑx), ℑz(ℑy)), left-associated sums, x^2 as x * x.  Along a Flat direction the reference's
 differences are 0 and its interpolations return the value itself; here the shifted view along such a direction is the unshifted one, which
-gives the same bits ((x - x) / Δ = 0, 0.5 (x + x) = x).  Also the seeded random inputs shared by the host and the GPU tests."""
+gives the same bits ((x - x) / Δ = 0, 0.5 (x + x) = x).  Also the seeded random inputs shared by the host and the GPU tests.
+
+The arithmetic type is that of the velocity arrays: with np.longdouble parents (oracle/extended.py: widen) the metrics are widened too and
+every operation, cbrt and sqrt included, is carried out in extended precision -- the same real function of the same Float64 inputs."""
 import numpy as np
 
 from oracle import oracle as O
@@ -49,18 +52,19 @@ def _sh(og, a, di, dj, dk):
     return a[tuple(sl)]
 
 
-def _dz(og, face, dk):
+def _dz(og, face, dk, dtype=np.float64):
     """Δzᵃᵃᶜ (face = False) or Δzᵃᵃᶠ (True) at levels k + dk, k = 1..Nz, broadcastable over the interior"""
     if og.dzc is None:
-        return og.dz
+        return dtype(og.dz)
     a = og.dzf if face else og.dzc  # element 0 <-> k = 1 - Hz
-    return a[og.Hz + dk:og.Hz + dk + og.Nz].reshape(1, 1, -1)
+    return a[og.Hz + dk:og.Hz + dk + og.Nz].reshape(1, 1, -1).astype(dtype)
 
 
 def strain_dot(og, u, v, w):
     """ΣᵢⱼΣᵢⱼᶜᶜᶜ over the interior"""
-    dx, dy = og.dx, og.dy
-    dzc, dzf = _dz(og, False, 0), (_dz(og, True, 0), _dz(og, True, 1))
+    ft = u.dtype.type
+    dx, dy = ft(og.dx), ft(og.dy)
+    dzc, dzf = _dz(og, False, 0, ft), (_dz(og, True, 0, ft), _dz(og, True, 1, ft))
     U = lambda a, b, d: _sh(og, u, a, b, d)
     V = lambda a, b, d: _sh(og, v, a, b, d)
     W = lambda a, b, d: _sh(og, w, a, b, d)
@@ -90,8 +94,10 @@ def buoyancy_frequency(og, buoyancy, T, S):
     if buoyancy is None:
         return np.zeros((og.Nx, og.Ny, og.Nz))
 
+    ft = (T if T is not None else S).dtype.type
+
     def dzb(d):
-        dzf = _dz(og, True, d)
+        dzf = _dz(og, True, d, ft)
         dT = 0.0 if T is None else (_sh(og, T, 0, 0, d) - _sh(og, T, 0, 0, d - 1)) / dzf
         dS = 0.0 if S is None else (_sh(og, S, 0, 0, d) - _sh(og, S, 0, 0, d - 1)) / dzf
         if buoyancy == "BuoyancyTracer":
@@ -105,7 +111,8 @@ def buoyancy_frequency(og, buoyancy, T, S):
 def smagorinsky_viscosity(og, u, v, w, C, lilly=False, Cb=0.0, buoyancy=None, T=None, S=None, parts=False):
     """νₑ over the interior (Nx, Ny, Nz); parts: also Σ², N², ς"""
     S2 = strain_dot(og, u, v, w)
-    Df = np.cbrt((og.dx * og.dy) * _dz(og, False, 0))
+    ft = u.dtype.type
+    Df = np.cbrt((ft(og.dx) * ft(og.dy)) * _dz(og, False, 0, ft))
     N2 = sig = None
     if lilly:
         N2 = buoyancy_frequency(og, buoyancy, T, S)
