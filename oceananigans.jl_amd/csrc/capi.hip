@@ -20,6 +20,15 @@ static inline bool strict_math(const ocn_grid *grid)
     return g_math_mode.load(std::memory_order_relaxed) == OCN_MATH_STRICT;
 }
 
+// THE place that picks the variant of a launcher.  OCN_LAUNCH(grid, launcher, args...): the arithmetic variant by the grid's math mode
+// (the launchers of ocn_launchers_math.inc and, for WENO, of ocn_launchers_scheme.inc).  OCN_LAUNCH_SCHEME(grid, advection, launcher,
+// args...): the launchers of ocn_launchers_scheme.inc, whose UpwindBiased(order=5) builds live in the _up namespaces.
+#define OCN_LAUNCH(grid, f, ...) (strict_math(grid) ? ocn_strict::f(__VA_ARGS__) : ocn_fast::f(__VA_ARGS__))
+#define OCN_LAUNCH_SCHEME(grid, advection, f, ...)                                  \
+    ((advection) != OCN_ADVECTION_UPWIND5 ? OCN_LAUNCH(grid, f, __VA_ARGS__)        \
+     : strict_math(grid)                 ? ocn_strict_up::f(__VA_ARGS__)            \
+                                          : ocn_fast_up::f(__VA_ARGS__))
+
 void set_error(const char *fmt, ...)
 {
     char buf[1024];
@@ -227,11 +236,19 @@ int ocn_compute_momentum_tendencies(const ocn_grid *grid, const double *u, const
     int st = validate_weno(grid);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(u && v && w && Gu && Gv && Gw, "ocn_compute_momentum_tendencies: null field pointer");
-    if (!xy_periodic(grid))
-        return strict_math(grid) ? ocn_strict::launch_momentum_tendencies_general(grid, 0, u, v, w, Gu, Gv, Gw, range, as_stream(stream))
-                                              : ocn_fast::launch_momentum_tendencies_general(grid, 0, u, v, w, Gu, Gv, Gw, range, as_stream(stream));
-    if (strict_math(grid)) return ocn_strict::launch_momentum_tendencies(grid, u, v, w, Gu, Gv, Gw, range, nullptr, as_stream(stream));
-    return ocn_fast::launch_momentum_tendencies(grid, u, v, w, Gu, Gv, Gw, range, nullptr, as_stream(stream));
+    if (!xy_periodic(grid)) return OCN_LAUNCH(grid, launch_momentum_tendencies_general, grid, 0, u, v, w, Gu, Gv, Gw, range, as_stream(stream));
+    return OCN_LAUNCH(grid, launch_momentum_tendencies, grid, u, v, w, Gu, Gv, Gw, range, nullptr, as_stream(stream));
+}
+
+// the next substep as the epilogue of the tiled momentum kernel
+static FuseArgs substep_fuse(const double *Gmu, const double *Gmv, const double *Gmw, double *u_out, double *v_out, double *w_out, double dt,
+                             double gamma, double zeta, int32_t has_zeta)
+{
+    FuseArgs fz{};
+    fz.Gm[0] = Gmu; fz.Gm[1] = Gmv; fz.Gm[2] = Gmw;
+    fz.Uo[0] = u_out; fz.Uo[1] = v_out; fz.Uo[2] = w_out;
+    fz.dt = dt; fz.gamma = gamma; fz.zeta = zeta; fz.on = 1; fz.has_zeta = has_zeta ? 1 : 0;
+    return fz;
 }
 
 static int momentum_tendencies_rk3(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu, double *Gv,
@@ -254,19 +271,14 @@ static int momentum_tendencies_rk3(const ocn_grid *grid, const double *u, const 
         mf.sub[1] = SubstepDev{Gmv, v_out};
         mf.sub[2] = SubstepDev{Gmw, w_out};
         mf.sc = SubstepCoef{dt, gamma, zeta, 1, has_zeta ? 1 : 0};
-        return strict_math(grid) ? ocn_strict::launch_momentum_tendencies_general(grid, 0, u, v, w, Gu, Gv, Gw, nullptr, as_stream(stream), &mf)
-                                 : ocn_fast::launch_momentum_tendencies_general(grid, 0, u, v, w, Gu, Gv, Gw, nullptr, as_stream(stream), &mf);
+        return OCN_LAUNCH(grid, launch_momentum_tendencies_general, grid, 0, u, v, w, Gu, Gv, Gw, nullptr, as_stream(stream), &mf);
     }
-    FuseArgs fz{};
-    fz.Gm[0] = Gmu; fz.Gm[1] = Gmv; fz.Gm[2] = Gmw;
-    fz.Uo[0] = u_out; fz.Uo[1] = v_out; fz.Uo[2] = w_out;
-    fz.dt = dt; fz.gamma = gamma; fz.zeta = zeta; fz.on = 1; fz.has_zeta = has_zeta ? 1 : 0;
+    FuseArgs fz = substep_fuse(Gmu, Gmv, Gmw, u_out, v_out, w_out, dt, gamma, zeta, has_zeta);
     fz.pc_p = p_correct; fz.pc_dt = dt_correct; fz.pc_on = p_correct ? 1 : 0;
     fz.skip_g = (flags & OCN_RK3_SKIP_G_STORE) ? 1 : 0;
     fz.wrap_uvw = (flags & OCN_RK3_WRAPPED_LOADS) ? 1 : 0;
     fz.no_step = (flags & OCN_RK3_CORRECT_ONLY) ? 1 : 0;
-    if (strict_math(grid)) return ocn_strict::launch_momentum_tendencies(grid, u, v, w, Gu, Gv, Gw, range, &fz, as_stream(stream));
-    return ocn_fast::launch_momentum_tendencies(grid, u, v, w, Gu, Gv, Gw, range, &fz, as_stream(stream));
+    return OCN_LAUNCH(grid, launch_momentum_tendencies, grid, u, v, w, Gu, Gv, Gw, range, &fz, as_stream(stream));
 }
 
 int ocn_compute_momentum_tendencies_rk3(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
@@ -306,14 +318,10 @@ int ocn_compute_momentum_tendencies_rk3_strips(const ocn_grid *grid, const doubl
                 "ocn_compute_momentum_tendencies_rk3_strips: the correction-on-load stage of a slab (p_correct) and both strip buffers");
     OCN_REQUIRE(grid->tx == OCN_FULLY_CONNECTED && grid->ty == OCN_PERIODIC && grid->tz == OCN_PERIODIC,
                 "ocn_compute_momentum_tendencies_rk3_strips: a (FullyConnected, Periodic, Periodic) local grid");
-    FuseArgs fz{};
-    fz.Gm[0] = Gmu; fz.Gm[1] = Gmv; fz.Gm[2] = Gmw;
-    fz.Uo[0] = u_out; fz.Uo[1] = v_out; fz.Uo[2] = w_out;
-    fz.dt = dt; fz.gamma = gamma; fz.zeta = zeta; fz.on = 1; fz.has_zeta = has_zeta ? 1 : 0;
+    FuseArgs fz = substep_fuse(Gmu, Gmv, Gmw, u_out, v_out, w_out, dt, gamma, zeta, has_zeta);
     fz.pc_p = p_correct; fz.pc_dt = dt_correct; fz.pc_on = 1;
     fz.strip_w = strip_west; fz.strip_e = strip_east; fz.strip_field = field_doubles;
-    if (strict_math(grid)) return ocn_strict::launch_momentum_tendencies(grid, u, v, w, Gu, Gv, Gw, nullptr, &fz, as_stream(stream));
-    return ocn_fast::launch_momentum_tendencies(grid, u, v, w, Gu, Gv, Gw, nullptr, &fz, as_stream(stream));
+    return OCN_LAUNCH(grid, launch_momentum_tendencies, grid, u, v, w, Gu, Gv, Gw, nullptr, &fz, as_stream(stream));
 }
 
 int ocn_momentum_tendencies_addr32(const ocn_grid *grid, int32_t *selected)
@@ -364,51 +372,24 @@ static int validate_terms(const ocn_grid *grid, const ocn_model_terms *t)
     return OCN_SUCCESS;
 }
 
-// advective part by scheme and math mode
+// advective part: the topology picks the launcher (direction-generic / Centered(order=2) / tiled), OCN_LAUNCH* its variant
 static int launch_advective_momentum(int advection, const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
                                      double *Gv, double *Gw, const int32_t *range, hipStream_t s)
 {
-    const bool strict = strict_math(grid);
-    if (!xy_periodic(grid)) {  // direction-generic kernels (csrc/general.hip)
-        const int c2 = advection == OCN_ADVECTION_CENTERED2;
-        if (advection == OCN_ADVECTION_UPWIND5)
-            return strict ? ocn_strict_up::launch_momentum_tendencies_general(grid, 0, u, v, w, Gu, Gv, Gw, range, s)
-                          : ocn_fast_up::launch_momentum_tendencies_general(grid, 0, u, v, w, Gu, Gv, Gw, range, s);
-        return strict ? ocn_strict::launch_momentum_tendencies_general(grid, c2, u, v, w, Gu, Gv, Gw, range, s)
-                      : ocn_fast::launch_momentum_tendencies_general(grid, c2, u, v, w, Gu, Gv, Gw, range, s);
-    }
-    switch (advection) {
-        case OCN_ADVECTION_WENO5:
-            return strict ? ocn_strict::launch_momentum_tendencies(grid, u, v, w, Gu, Gv, Gw, range, nullptr, s)
-                          : ocn_fast::launch_momentum_tendencies(grid, u, v, w, Gu, Gv, Gw, range, nullptr, s);
-        case OCN_ADVECTION_UPWIND5:
-            return strict ? ocn_strict_up::launch_momentum_tendencies(grid, u, v, w, Gu, Gv, Gw, range, nullptr, s)
-                          : ocn_fast_up::launch_momentum_tendencies(grid, u, v, w, Gu, Gv, Gw, range, nullptr, s);
-        default:
-            return strict ? ocn_strict::launch_momentum_centered2(grid, u, v, w, Gu, Gv, Gw, range, s)
-                          : ocn_fast::launch_momentum_centered2(grid, u, v, w, Gu, Gv, Gw, range, s);
-    }
+    const int c2 = advection == OCN_ADVECTION_CENTERED2;
+    if (!xy_periodic(grid))  // direction-generic kernels (csrc/general.hip)
+        return OCN_LAUNCH_SCHEME(grid, advection, launch_momentum_tendencies_general, grid, c2, u, v, w, Gu, Gv, Gw, range, s);
+    if (c2) return OCN_LAUNCH(grid, launch_momentum_centered2, grid, u, v, w, Gu, Gv, Gw, range, s);
+    return OCN_LAUNCH_SCHEME(grid, advection, launch_momentum_tendencies, grid, u, v, w, Gu, Gv, Gw, range, nullptr, s);
 }
 static int launch_advective_tracer(int advection, const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c,
                                    double *Gc, const int32_t *range, hipStream_t s, const TracerFuse *tf, const ocn::ForcingDev *frc = nullptr)
 {
-    const bool strict = strict_math(grid);
-    if (!xy_periodic(grid)) {  // (tf: diffusion / bottom and top fluxes / the next substep ride along, general.hip)
-        const int c2 = advection == OCN_ADVECTION_CENTERED2;
-        if (advection == OCN_ADVECTION_UPWIND5)
-            return strict ? ocn_strict_up::launch_tracer_tendency_general(grid, 0, u, v, w, c, Gc, range, s, tf, frc)
-                          : ocn_fast_up::launch_tracer_tendency_general(grid, 0, u, v, w, c, Gc, range, s, tf, frc);
-        return strict ? ocn_strict::launch_tracer_tendency_general(grid, c2, u, v, w, c, Gc, range, s, tf, frc)
-                      : ocn_fast::launch_tracer_tendency_general(grid, c2, u, v, w, c, Gc, range, s, tf, frc);
-    }
-    switch (advection) {
-        case OCN_ADVECTION_WENO5:
-            return strict ? ocn_strict::launch_tracer_tendency(grid, u, v, w, c, Gc, range, s, tf, frc) : ocn_fast::launch_tracer_tendency(grid, u, v, w, c, Gc, range, s, tf, frc);
-        case OCN_ADVECTION_UPWIND5:
-            return strict ? ocn_strict_up::launch_tracer_tendency(grid, u, v, w, c, Gc, range, s, tf, frc) : ocn_fast_up::launch_tracer_tendency(grid, u, v, w, c, Gc, range, s, tf, frc);
-        default:
-            return strict ? ocn_strict::launch_tracer_centered2(grid, u, v, w, c, Gc, range, s) : ocn_fast::launch_tracer_centered2(grid, u, v, w, c, Gc, range, s);
-    }
+    const int c2 = advection == OCN_ADVECTION_CENTERED2;
+    if (!xy_periodic(grid))  // (tf: diffusion / bottom and top fluxes / the next substep ride along, general.hip)
+        return OCN_LAUNCH_SCHEME(grid, advection, launch_tracer_tendency_general, grid, c2, u, v, w, c, Gc, range, s, tf, frc);
+    if (c2) return OCN_LAUNCH(grid, launch_tracer_centered2, grid, u, v, w, c, Gc, range, s);
+    return OCN_LAUNCH_SCHEME(grid, advection, launch_tracer_tendency, grid, u, v, w, c, Gc, range, s, tf, frc);
 }
 
 // stokes_drift = UniformStokesDrift: the device vectors of the profiles (NULL = zero); a vertical shear needs a z direction
@@ -447,80 +428,73 @@ int ocn::validate_forcing(const ocn_grid *grid, const ocn_forcing *f, const char
     return OCN_SUCCESS;
 }
 extern "C" {
-// u, v, w: *md is filled and *any says whether a term is present
-static int momentum_forcing(const ocn_grid *grid, const ocn_forcing *const *forcing, const char *who, ocn::MomentumForcingDev *md, bool *any)
+// The optional parts of the two momentum families, checked and converted.  stokes / forcing stay NULL where the caller gave none (forcing:
+// a NULL array, or no term on any of u, v, w): the launchers pick their kernels by these pointers.
+struct MomentumOptions {
+    ocn::StokesDev sd{};
+    ocn::MomentumForcingDev md{};
+    const ocn::StokesDev *stokes = nullptr;
+    const ocn::MomentumForcingDev *forcing = nullptr;
+};
+static int momentum_options(const char *who, const ocn_grid *grid, const ocn_stokes_drift *stokes, const ocn_forcing *const *forcing,
+                            MomentumOptions &o)
 {
     static const char *names[3] = {"u", "v", "w"};
-    *any = false;
-    *md = ocn::MomentumForcingDev{};
-    if (!forcing) return OCN_SUCCESS;
-    OCN_REQUIRE(grid != nullptr, "grid is NULL");
-    for (int f = 0; f < 3; ++f) {
+    OCN_REQUIRE(grid != nullptr || (!stokes && !forcing), "grid is NULL");
+    for (int f = 0; forcing && f < 3; ++f) {
         int st = validate_forcing(grid, forcing[f], who, names[f]);
         if (st != OCN_SUCCESS) return st;
-        md->f[f] = ocn::to_dev(forcing[f]);
-        *any = *any || md->f[f].n > 0;
+        o.md.f[f] = ocn::to_dev(forcing[f]);
+        if (o.md.f[f].n > 0) o.forcing = &o.md;
     }
+    if (!stokes) return OCN_SUCCESS;
+    int st = validate_stokes(grid, stokes, who);
+    if (st != OCN_SUCCESS) return st;
+    o.sd = ocn::to_dev(*stokes);
+    o.stokes = &o.sd;
     return OCN_SUCCESS;
 }
 
+// THE body of ocn_compute_momentum_tendencies_terms[_stokes | _forced]: stokes and forcing (the array, or every entry of it) may be NULL
 static int momentum_tendencies_terms(const char *who, const ocn_grid *grid, const ocn_model_terms *terms, const ocn_stokes_drift *stokes,
-                                     const double *u, const double *v, const double *w, double *Gu, double *Gv, double *Gw,
-                                     const int32_t *range, void *stream, const ocn::MomentumForcingDev *pfd = nullptr)
+                                     const ocn_forcing *const *forcing, const double *u, const double *v, const double *w, double *Gu,
+                                     double *Gv, double *Gw, const int32_t *range, void *stream)
 {
-    int st = validate_terms(grid, terms);
+    MomentumOptions o;
+    int st = momentum_options(who, grid, stokes, forcing, o);
+    if (st != OCN_SUCCESS) return st;
+    st = validate_terms(grid, terms);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(u && v && w && Gu && Gv && Gw, "%s: null field pointer", who);
     OCN_REQUIRE((grid->tx == OCN_FLAT || grid->Hx >= 1) && (grid->ty == OCN_FLAT || grid->Hy >= 1) && (grid->tz == OCN_FLAT || grid->Hz >= 1), "halo >= 1 required");
-    const bool strict = strict_math(grid);
     hipStream_t s = as_stream(stream);
     st = launch_advective_momentum(terms->advection, grid, u, v, w, Gu, Gv, Gw, range, s);
     if (st != OCN_SUCCESS) return st;
-    if (!(terms->coriolis || terms->closure || terms->buoyancy || stokes || pfd)) return OCN_SUCCESS;
+    if (!(terms->coriolis || terms->closure || terms->buoyancy || o.stokes || o.forcing)) return OCN_SUCCESS;
     TermsDev t = to_dev(*terms);
-    ocn::StokesDev sd{};
-    if (stokes) sd = ocn::to_dev(*stokes);
-    const ocn::StokesDev *psd = stokes ? &sd : nullptr;
-    if (!xy_periodic(grid))
-        return strict ? ocn_strict::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, psd, pfd)
-                      : ocn_fast::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, psd, pfd);
-    return strict ? ocn_strict::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, psd, pfd)
-                  : ocn_fast::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, psd, pfd);
+    if (!xy_periodic(grid)) return OCN_LAUNCH(grid, launch_momentum_extra_general, grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, o.stokes, o.forcing);
+    return OCN_LAUNCH(grid, launch_momentum_extra, grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, o.stokes, o.forcing);
 }
 
 int ocn_compute_momentum_tendencies_terms(const ocn_grid *grid, const ocn_model_terms *terms, const double *u, const double *v,
                                           const double *w, double *Gu, double *Gv, double *Gw, const int32_t *range,
                                           void *stream)
 {
-    return momentum_tendencies_terms("ocn_compute_momentum_tendencies_terms", grid, terms, nullptr, u, v, w, Gu, Gv, Gw, range, stream);
+    return momentum_tendencies_terms(__func__, grid, terms, nullptr, nullptr, u, v, w, Gu, Gv, Gw, range, stream);
 }
 
 int ocn_compute_momentum_tendencies_terms_stokes(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_stokes_drift *stokes,
                                                  const double *u, const double *v, const double *w, double *Gu, double *Gv, double *Gw,
                                                  const int32_t *range, void *stream)
 {
-    if (!stokes) return momentum_tendencies_terms("ocn_compute_momentum_tendencies_terms_stokes", grid, terms, nullptr, u, v, w, Gu, Gv, Gw, range, stream);
-    OCN_REQUIRE(grid != nullptr, "grid is NULL");
-    int st = validate_stokes(grid, stokes, "ocn_compute_momentum_tendencies_terms_stokes");
-    if (st != OCN_SUCCESS) return st;
-    return momentum_tendencies_terms("ocn_compute_momentum_tendencies_terms_stokes", grid, terms, stokes, u, v, w, Gu, Gv, Gw, range, stream);
+    return momentum_tendencies_terms(__func__, grid, terms, stokes, nullptr, u, v, w, Gu, Gv, Gw, range, stream);
 }
 
 int ocn_compute_momentum_tendencies_terms_forced(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_stokes_drift *stokes,
                                                  const ocn_forcing *const *forcing, const double *u, const double *v, const double *w,
                                                  double *Gu, double *Gv, double *Gw, const int32_t *range, void *stream)
 {
-    const char *who = "ocn_compute_momentum_tendencies_terms_forced";
-    ocn::MomentumForcingDev md;
-    bool any;
-    int st = momentum_forcing(grid, forcing, who, &md, &any);
-    if (st != OCN_SUCCESS) return st;
-    if (!any) return ocn_compute_momentum_tendencies_terms_stokes(grid, terms, stokes, u, v, w, Gu, Gv, Gw, range, stream);
-    if (stokes) {
-        st = validate_stokes(grid, stokes, who);
-        if (st != OCN_SUCCESS) return st;
-    }
-    return momentum_tendencies_terms(who, grid, terms, stokes, u, v, w, Gu, Gv, Gw, range, stream, &md);
+    return momentum_tendencies_terms(__func__, grid, terms, stokes, forcing, u, v, w, Gu, Gv, Gw, range, stream);
 }
 
 // the extra terms alone, added to a G that already holds what precedes them in the reference's sum (used by the hydrostatic
@@ -534,8 +508,7 @@ int ocn_add_momentum_terms(const ocn_grid *grid, const ocn_model_terms *terms, c
     OCN_REQUIRE(grid->Hx >= 1 && grid->Hy >= 1 && (grid->tz == OCN_FLAT || grid->Hz >= 1), "halo >= 1 required");
     if (!(terms->coriolis || terms->closure || terms->buoyancy)) return OCN_SUCCESS;
     TermsDev t = to_dev(*terms);
-    return strict_math(grid) ? ocn_strict::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, as_stream(stream))
-                                          : ocn_fast::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, as_stream(stream));
+    return OCN_LAUNCH(grid, launch_momentum_extra, grid, t, u, v, w, Gu, Gv, Gw, range, as_stream(stream));
 }
 
 static int validate_hydrostatic(const ocn_grid *grid, const char *who)
@@ -624,29 +597,6 @@ int ocn_explicit_free_surface_ab2_step(const ocn_grid *grid, const double *w, do
     return launch_free_surface_ab2(grid, w, eta, G_eta, G_eta_previous, dt, chi, as_stream(stream));
 }
 
-int ocn_compute_tracer_tendency_terms(const ocn_grid *grid, const ocn_model_terms *terms, double kappa, const double *kappa_e,
-                                      const double *u, const double *v, const double *w, const double *c, double *Gc,
-                                      const int32_t *range, void *stream)
-{
-    int st = validate_terms(grid, terms);
-    if (st != OCN_SUCCESS) return st;
-    OCN_REQUIRE(u && v && w && c && Gc, "ocn_compute_tracer_tendency_terms: null field pointer");
-    const bool strict = strict_math(grid);
-    hipStream_t s = as_stream(stream);
-    OCN_REQUIRE(!kappa_e || terms->closure == 2, "kappa_e is only meaningful with closure == 2");
-    if (!xy_periodic(grid) && terms->closure) {  // advection and diffusion in one call: the interior box adds both before its store
-        TracerFuse tf{};
-        tf.diffusion = 1;
-        tf.kappa = kappa;
-        tf.kappa_e = kappa_e;
-        return launch_advective_tracer(terms->advection, grid, u, v, w, c, Gc, range, s, &tf);
-    }
-    st = launch_advective_tracer(terms->advection, grid, u, v, w, c, Gc, range, s, nullptr);
-    if (st != OCN_SUCCESS || !terms->closure) return st;
-    return strict ? ocn_strict::launch_tracer_diffusion(grid, kappa, kappa_e, c, Gc, range, s)
-                  : ocn_fast::launch_tracer_diffusion(grid, kappa, kappa_e, c, Gc, range, s);
-}
-
 static int validate_amd(const ocn_grid *grid)
 {
     int st = validate_grid_any(grid);  // Bounded x / y: the kernel takes per-field parent layouts
@@ -663,8 +613,7 @@ int ocn_compute_amd_viscosity(const ocn_grid *grid, double C_nu, const double *u
     int st = validate_amd(grid);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(u && v && w && nu_e, "ocn_compute_amd_viscosity: null field pointer");
-    return strict_math(grid) ? ocn_strict::launch_amd_viscosity(grid, C_nu, u, v, w, nu_e, as_stream(stream))
-                                          : ocn_fast::launch_amd_viscosity(grid, C_nu, u, v, w, nu_e, as_stream(stream));
+    return OCN_LAUNCH(grid, launch_amd_viscosity, grid, C_nu, u, v, w, nu_e, as_stream(stream));
 }
 
 int ocn_compute_amd_diffusivities(const ocn_grid *grid, double C_nu, const double *u, const double *v, const double *w,
@@ -677,9 +626,7 @@ int ocn_compute_amd_diffusivities(const ocn_grid *grid, double C_nu, const doubl
     OCN_REQUIRE(n_tracers >= 0 && n_tracers <= 4, "ocn_compute_amd_diffusivities: n_tracers = %d outside 0..4", n_tracers);
     OCN_REQUIRE(n_tracers == 0 || (C_kappa && tracers && kappa_e), "ocn_compute_amd_diffusivities: null tracer arrays");
     for (int n = 0; n < n_tracers; ++n) OCN_REQUIRE(tracers[n] && kappa_e[n], "ocn_compute_amd_diffusivities: tracer %d is NULL", n);
-    return strict_math(grid)
-               ? ocn_strict::launch_amd_fused(grid, C_nu, u, v, w, nu_e, n_tracers, C_kappa, tracers, kappa_e, as_stream(stream))
-               : ocn_fast::launch_amd_fused(grid, C_nu, u, v, w, nu_e, n_tracers, C_kappa, tracers, kappa_e, as_stream(stream));
+    return OCN_LAUNCH(grid, launch_amd_fused, grid, C_nu, u, v, w, nu_e, n_tracers, C_kappa, tracers, kappa_e, as_stream(stream));
 }
 
 int ocn_compute_amd_diffusivities_range(const ocn_grid *grid, double C_nu, const double *u, const double *v, const double *w,
@@ -695,9 +642,7 @@ int ocn_compute_amd_diffusivities_range(const ocn_grid *grid, double C_nu, const
     OCN_REQUIRE(i_first >= 0 && i_last <= grid->Nx + 1, "ocn_compute_amd_diffusivities_range: i range %d:%d outside 0:%d", i_first, i_last, grid->Nx + 1);
     OCN_REQUIRE((i_first >= 1 && i_last <= grid->Nx) || grid->Hx >= 2, "the halo columns 0 and Nx+1 need Hx >= 2");
     const int32_t ir[2] = {i_first, i_last};
-    return strict_math(grid)
-               ? ocn_strict::launch_amd_fused(grid, C_nu, u, v, w, nu_e, n_tracers, C_kappa, tracers, kappa_e, as_stream(stream), ir)
-               : ocn_fast::launch_amd_fused(grid, C_nu, u, v, w, nu_e, n_tracers, C_kappa, tracers, kappa_e, as_stream(stream), ir);
+    return OCN_LAUNCH(grid, launch_amd_fused, grid, C_nu, u, v, w, nu_e, n_tracers, C_kappa, tracers, kappa_e, as_stream(stream), ir);
 }
 
 int ocn_compute_amd_diffusivity(const ocn_grid *grid, double C_kappa, const double *u, const double *v, const double *w,
@@ -706,8 +651,7 @@ int ocn_compute_amd_diffusivity(const ocn_grid *grid, double C_kappa, const doub
     int st = validate_amd(grid);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(u && v && w && c && kappa_e, "ocn_compute_amd_diffusivity: null field pointer");
-    return strict_math(grid) ? ocn_strict::launch_amd_diffusivity(grid, C_kappa, u, v, w, c, kappa_e, as_stream(stream))
-                                          : ocn_fast::launch_amd_diffusivity(grid, C_kappa, u, v, w, c, kappa_e, as_stream(stream));
+    return OCN_LAUNCH(grid, launch_amd_diffusivity, grid, C_kappa, u, v, w, c, kappa_e, as_stream(stream));
 }
 
 int ocn_compute_smagorinsky_diffusivities(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_smagorinsky *closure,
@@ -739,8 +683,7 @@ int ocn_compute_smagorinsky_diffusivities(const ocn_grid *grid, const ocn_model_
                     "ocn_compute_smagorinsky_diffusivities: Pr[%d] == 1: kappa_e must be NULL or the nu_e array (the tracer reads nu_e)", n);
     }
     const TermsDev t = to_dev(*terms);
-    return strict_math(grid) ? ocn_strict::launch_smagorinsky(grid, t, *closure, u, v, w, nu_e, kappa_e, as_stream(stream))
-                             : ocn_fast::launch_smagorinsky(grid, t, *closure, u, v, w, nu_e, kappa_e, as_stream(stream));
+    return OCN_LAUNCH(grid, launch_smagorinsky, grid, t, *closure, u, v, w, nu_e, kappa_e, as_stream(stream));
 }
 
 // ---- Lagrangian particles (csrc/particles.hip) --------------------------------------------------------
@@ -897,14 +840,18 @@ static int flux_side(const ocn_grid *grid, const ocn_field_bcs *b, const char *n
     return OCN_SUCCESS;
 }
 
+// THE body of ocn_compute_momentum_tendencies_terms_rk3[_stokes | _forced]: stokes, forcing (the array, or every entry of it) and the flux
+// conditions may be NULL
 static int momentum_tendencies_terms_rk3(const char *who, const ocn_grid *grid, const ocn_model_terms *terms, const ocn_stokes_drift *stokes,
-                                         const ocn_field_bcs *bcs_u, const ocn_field_bcs *bcs_v, const double *u, const double *v,
-                                         const double *w, double *Gu, double *Gv, double *Gw, const double *Gmu, const double *Gmv,
-                                         const double *Gmw, double *u_out, double *v_out, double *w_out, double dt, double gamma,
-                                         double zeta, int32_t has_zeta, const int32_t *range, void *stream,
-                                         const ocn::MomentumForcingDev *pfd = nullptr)
+                                         const ocn_forcing *const *forcing, const ocn_field_bcs *bcs_u, const ocn_field_bcs *bcs_v,
+                                         const double *u, const double *v, const double *w, double *Gu, double *Gv, double *Gw,
+                                         const double *Gmu, const double *Gmv, const double *Gmw, double *u_out, double *v_out, double *w_out,
+                                         double dt, double gamma, double zeta, int32_t has_zeta, const int32_t *range, void *stream)
 {
-    int st = validate_terms(grid, terms);
+    MomentumOptions o;
+    int st = momentum_options(who, grid, stokes, forcing, o);
+    if (st != OCN_SUCCESS) return st;
+    st = validate_terms(grid, terms);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(xy_periodic(grid) || !range, "%s: ranges need Periodic x and y", who);
     OCN_REQUIRE(u && v && w && Gu && Gv && Gw && u_out && v_out && w_out, "%s: null field pointer", who);
@@ -919,22 +866,17 @@ static int momentum_tendencies_terms_rk3(const char *who, const ocn_grid *grid, 
     mf.sub[1] = SubstepDev{Gmv, v_out};
     mf.sub[2] = SubstepDev{Gmw, w_out};
     mf.sc = SubstepCoef{dt, gamma, zeta, 1, has_zeta ? 1 : 0};
-    const bool strict = strict_math(grid);
     hipStream_t s = as_stream(stream);
     TermsDev t = to_dev(*terms);
-    ocn::StokesDev sd{};
-    if (stokes) sd = ocn::to_dev(*stokes);
-    const ocn::StokesDev *psd = stokes ? &sd : nullptr;
     if (!xy_periodic(grid)) {
         // walls in x / y: advection (box + frames), then the finishing pass in the reference's order with the boundary fluxes and the substep --
         // inside the tiled kernel on the interior box, as per-cell kernels on the frames (general.hip)
         st = launch_advective_momentum(terms->advection, grid, u, v, w, Gu, Gv, Gw, nullptr, s);
         if (st != OCN_SUCCESS) return st;
-        return strict ? ocn_strict::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, nullptr, s, &mf, psd, pfd)
-                      : ocn_fast::launch_momentum_extra_general(grid, t, u, v, w, Gu, Gv, Gw, nullptr, s, &mf, psd, pfd);
+        return OCN_LAUNCH(grid, launch_momentum_extra_general, grid, t, u, v, w, Gu, Gv, Gw, nullptr, s, &mf, o.stokes, o.forcing);
     }
     static const bool extra_first = !(std::getenv("OCN_EXTRA_FIRST") && std::getenv("OCN_EXTRA_FIRST")[0] == '0');
-    if (!strict && extra_first && terms->advection != OCN_ADVECTION_CENTERED2) {
+    if (!strict_math(grid) && extra_first && terms->advection != OCN_ADVECTION_CENTERED2) {
         // Fast math: the finishing pass runs FIRST and leaves the non-advective terms (and the u / v boundary fluxes) in G; the WENO
         // launch -- VALU-bound, with HBM bandwidth to spare -- adds its advective part, stores G and does the substep.  The HBM-bound
         // finishing pass then moves 64 instead of 136 B / cell (no G read-modify-write, no G^-, no second storage); the sum is the
@@ -943,20 +885,15 @@ static int momentum_tendencies_terms_rk3(const char *who, const ocn_grid *grid, 
         MomentumFinal pre = mf;
         pre.pre = 1;
         pre.sc.on = 0;
-        st = ocn_fast::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, &pre, psd, pfd);
+        st = OCN_LAUNCH(grid, launch_momentum_extra, grid, t, u, v, w, Gu, Gv, Gw, range, s, &pre, o.stokes, o.forcing);
         if (st != OCN_SUCCESS) return st;
-        FuseArgs fz{};
-        fz.Gm[0] = Gmu; fz.Gm[1] = Gmv; fz.Gm[2] = Gmw;
-        fz.Uo[0] = u_out; fz.Uo[1] = v_out; fz.Uo[2] = w_out;
-        fz.dt = dt; fz.gamma = gamma; fz.zeta = zeta; fz.on = 1; fz.has_zeta = has_zeta ? 1 : 0;
+        FuseArgs fz = substep_fuse(Gmu, Gmv, Gmw, u_out, v_out, w_out, dt, gamma, zeta, has_zeta);
         fz.acc = 1;
-        return terms->advection == OCN_ADVECTION_WENO5 ? ocn_fast::launch_momentum_tendencies(grid, u, v, w, Gu, Gv, Gw, range, &fz, s)
-                                                       : ocn_fast_up::launch_momentum_tendencies(grid, u, v, w, Gu, Gv, Gw, range, &fz, s);
+        return OCN_LAUNCH_SCHEME(grid, terms->advection, launch_momentum_tendencies, grid, u, v, w, Gu, Gv, Gw, range, &fz, s);
     }
     st = launch_advective_momentum(terms->advection, grid, u, v, w, Gu, Gv, Gw, range, s);
     if (st != OCN_SUCCESS) return st;
-    return strict ? ocn_strict::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, &mf, psd, pfd)
-                  : ocn_fast::launch_momentum_extra(grid, t, u, v, w, Gu, Gv, Gw, range, s, &mf, psd, pfd);
+    return OCN_LAUNCH(grid, launch_momentum_extra, grid, t, u, v, w, Gu, Gv, Gw, range, s, &mf, o.stokes, o.forcing);
 }
 
 int ocn_compute_momentum_tendencies_terms_rk3(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_field_bcs *bcs_u,
@@ -965,8 +902,8 @@ int ocn_compute_momentum_tendencies_terms_rk3(const ocn_grid *grid, const ocn_mo
                                               const double *Gmw, double *u_out, double *v_out, double *w_out, double dt,
                                               double gamma, double zeta, int32_t has_zeta, const int32_t *range, void *stream)
 {
-    return momentum_tendencies_terms_rk3("ocn_compute_momentum_tendencies_terms_rk3", grid, terms, nullptr, bcs_u, bcs_v, u, v, w, Gu, Gv, Gw, Gmu,
-                                         Gmv, Gmw, u_out, v_out, w_out, dt, gamma, zeta, has_zeta, range, stream);
+    return momentum_tendencies_terms_rk3(__func__, grid, terms, nullptr, nullptr, bcs_u, bcs_v, u, v, w, Gu, Gv, Gw, Gmu, Gmv, Gmw, u_out, v_out, w_out,
+                                         dt, gamma, zeta, has_zeta, range, stream);
 }
 
 int ocn_compute_momentum_tendencies_terms_rk3_stokes(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_stokes_drift *stokes,
@@ -976,14 +913,8 @@ int ocn_compute_momentum_tendencies_terms_rk3_stokes(const ocn_grid *grid, const
                                                      double dt, double gamma, double zeta, int32_t has_zeta, const int32_t *range,
                                                      void *stream)
 {
-    const char *who = "ocn_compute_momentum_tendencies_terms_rk3_stokes";
-    if (stokes) {
-        OCN_REQUIRE(grid != nullptr, "grid is NULL");
-        int st = validate_stokes(grid, stokes, who);
-        if (st != OCN_SUCCESS) return st;
-    }
-    return momentum_tendencies_terms_rk3(who, grid, terms, stokes, bcs_u, bcs_v, u, v, w, Gu, Gv, Gw, Gmu, Gmv, Gmw, u_out, v_out, w_out, dt,
-                                         gamma, zeta, has_zeta, range, stream);
+    return momentum_tendencies_terms_rk3(__func__, grid, terms, stokes, nullptr, bcs_u, bcs_v, u, v, w, Gu, Gv, Gw, Gmu, Gmv, Gmw, u_out, v_out, w_out,
+                                         dt, gamma, zeta, has_zeta, range, stream);
 }
 
 int ocn_compute_momentum_tendencies_terms_rk3_forced(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_stokes_drift *stokes,
@@ -993,20 +924,80 @@ int ocn_compute_momentum_tendencies_terms_rk3_forced(const ocn_grid *grid, const
                                                      double *w_out, double dt, double gamma, double zeta, int32_t has_zeta,
                                                      const int32_t *range, void *stream)
 {
-    const char *who = "ocn_compute_momentum_tendencies_terms_rk3_forced";
-    ocn::MomentumForcingDev md;
-    bool any;
-    int st = momentum_forcing(grid, forcing, who, &md, &any);
+    return momentum_tendencies_terms_rk3(__func__, grid, terms, stokes, forcing, bcs_u, bcs_v, u, v, w, Gu, Gv, Gw, Gmu, Gmv, Gmw, u_out, v_out, w_out,
+                                         dt, gamma, zeta, has_zeta, range, stream);
+}
+
+// What rides inside a tracer's advective kernel: the diffusion and -- with a substep (sub != NULL) -- the bottom / top fluxes and the substep
+static int make_tracer_fuse(const ocn_grid *grid, const ocn_model_terms *terms, double kappa, const double *kappa_e, const ocn_field_bcs *bcs_c,
+                            const SubstepDev *sub, const SubstepCoef &sc, TracerFuse &tf)
+{
+    tf = TracerFuse{};
+    tf.diffusion = terms->closure != 0;
+    tf.kappa = kappa;
+    tf.kappa_e = kappa_e;
+    if (!sub) return OCN_SUCCESS;  // (the tendency alone: ocn_apply_flux_bcs adds the boundary fluxes)
+    int st = flux_side(grid, bcs_c, "tracer", tf.bottom, tf.top);
     if (st != OCN_SUCCESS) return st;
-    if (!any)
-        return ocn_compute_momentum_tendencies_terms_rk3_stokes(grid, terms, stokes, bcs_u, bcs_v, u, v, w, Gu, Gv, Gw, Gmu, Gmv, Gmw, u_out, v_out,
-                                                                w_out, dt, gamma, zeta, has_zeta, range, stream);
-    if (stokes) {
-        st = validate_stokes(grid, stokes, who);
+    tf.sub = *sub;
+    tf.sc = sc;
+    return OCN_SUCCESS;
+}
+
+// THE body of ocn_compute_tracer_tendency_terms[_forced | _rk3 | _rk3_forced]: forcing (or its terms), the flux conditions and the substep
+// (sub, with its coefficients sc) may be absent.
+// A forced tracer: F rides inside the tracer kernels (tracer_finish / tracer_finish_general compiled with ocn::TracerFuseForced), between the
+// diffusion and the boundary fluxes.  Only Centered(order=2) advection on a (Periodic, Periodic, *) grid, whose kernel has no epilogue, takes
+// the small tracer_forcing_kernel after the diffusion kernel.
+static int tracer_tendency_terms(const char *who, const ocn_grid *grid, const ocn_model_terms *terms, double kappa, const double *kappa_e,
+                                 const ocn_forcing *forcing, const ocn_field_bcs *bcs_c, const double *u, const double *v, const double *w,
+                                 const double *c, double *Gc, const SubstepDev *sub, const SubstepCoef &sc, const int32_t *range, void *stream)
+{
+    if (forcing) {
+        OCN_REQUIRE(grid != nullptr, "grid is NULL");
+        int st = validate_forcing(grid, forcing, who, "the tracer");
         if (st != OCN_SUCCESS) return st;
     }
-    return momentum_tendencies_terms_rk3(who, grid, terms, stokes, bcs_u, bcs_v, u, v, w, Gu, Gv, Gw, Gmu, Gmv, Gmw, u_out, v_out, w_out, dt,
-                                         gamma, zeta, has_zeta, range, stream, &md);
+    int st = validate_terms(grid, terms);
+    if (st != OCN_SUCCESS) return st;
+    if (sub) {
+        OCN_REQUIRE(xy_periodic(grid) || !range, "%s: ranges need Periodic x and y", who);
+        OCN_REQUIRE(terms->advection != OCN_ADVECTION_CENTERED2, "%s: advection must be WENO5 or UpwindBiased5", who);
+    }
+    OCN_REQUIRE(u && v && w && c && Gc && (!sub || sub->out), "%s: null field pointer", who);
+    if (sub) {
+        OCN_REQUIRE(!sc.has_zeta || sub->Gm, "%s: G⁻ is required when has_zeta != 0", who);
+        OCN_REQUIRE(sub->out != c, "%s: the output must not alias the input", who);
+    }
+    OCN_REQUIRE(!kappa_e || terms->closure == 2, "kappa_e is only meaningful with closure == 2");
+    TracerFuse tf;
+    st = make_tracer_fuse(grid, terms, kappa, kappa_e, bcs_c, sub, sc, tf);
+    if (st != OCN_SUCCESS) return st;
+    const ocn::ForcingDev fd = ocn::to_dev(forcing);
+    const bool forced = fd.n > 0, periodic = xy_periodic(grid);
+    hipStream_t s = as_stream(stream);
+    // ONE call: the substep, F (unless the kernel is the Periodic grids' Centered(order=2) one, which has no epilogue) or -- walls in x / y,
+    // where the interior box adds advection and diffusion before its store -- the diffusion alone ride along
+    if (sub || (forced ? !(periodic && terms->advection == OCN_ADVECTION_CENTERED2) : (!periodic && terms->closure)))
+        return launch_advective_tracer(terms->advection, grid, u, v, w, c, Gc, range, s, &tf, forced ? &fd : nullptr);
+    st = launch_advective_tracer(terms->advection, grid, u, v, w, c, Gc, range, s, nullptr);
+    if (st == OCN_SUCCESS && terms->closure) st = OCN_LAUNCH(grid, launch_tracer_diffusion, grid, kappa, kappa_e, c, Gc, range, s);
+    if (st == OCN_SUCCESS && forced) st = OCN_LAUNCH(grid, launch_tracer_forcing, grid, fd, c, Gc, range, nullptr, s);
+    return st;
+}
+
+int ocn_compute_tracer_tendency_terms(const ocn_grid *grid, const ocn_model_terms *terms, double kappa, const double *kappa_e,
+                                      const double *u, const double *v, const double *w, const double *c, double *Gc,
+                                      const int32_t *range, void *stream)
+{
+    return tracer_tendency_terms(__func__, grid, terms, kappa, kappa_e, nullptr, nullptr, u, v, w, c, Gc, nullptr, SubstepCoef{}, range, stream);
+}
+
+int ocn_compute_tracer_tendency_terms_forced(const ocn_grid *grid, const ocn_model_terms *terms, double kappa, const double *kappa_e,
+                                             const ocn_forcing *forcing, const double *u, const double *v, const double *w, const double *c,
+                                             double *Gc, const int32_t *range, void *stream)
+{
+    return tracer_tendency_terms(__func__, grid, terms, kappa, kappa_e, forcing, nullptr, u, v, w, c, Gc, nullptr, SubstepCoef{}, range, stream);
 }
 
 int ocn_compute_tracer_tendency_terms_rk3(const ocn_grid *grid, const ocn_model_terms *terms, double kappa, const double *kappa_e,
@@ -1014,23 +1005,19 @@ int ocn_compute_tracer_tendency_terms_rk3(const ocn_grid *grid, const ocn_model_
                                           const double *c, double *Gc, const double *Gmc, double *c_out, double dt, double gamma,
                                           double zeta, int32_t has_zeta, const int32_t *range, void *stream)
 {
-    int st = validate_terms(grid, terms);
-    if (st != OCN_SUCCESS) return st;
-    OCN_REQUIRE(xy_periodic(grid) || !range, "ocn_compute_tracer_tendency_terms_rk3: ranges need Periodic x and y");
-    OCN_REQUIRE(terms->advection != OCN_ADVECTION_CENTERED2, "ocn_compute_tracer_tendency_terms_rk3: advection must be WENO5 or UpwindBiased5");
-    OCN_REQUIRE(u && v && w && c && Gc && c_out, "ocn_compute_tracer_tendency_terms_rk3: null field pointer");
-    OCN_REQUIRE(!has_zeta || Gmc, "ocn_compute_tracer_tendency_terms_rk3: G⁻ is required when has_zeta != 0");
-    OCN_REQUIRE(c_out != c, "ocn_compute_tracer_tendency_terms_rk3: the output must not alias the input");
-    OCN_REQUIRE(!kappa_e || terms->closure == 2, "kappa_e is only meaningful with closure == 2");
-    TracerFuse tf{};
-    tf.diffusion = terms->closure != 0;
-    tf.kappa = kappa;
-    tf.kappa_e = kappa_e;
-    st = flux_side(grid, bcs_c, "tracer", tf.bottom, tf.top);
-    if (st != OCN_SUCCESS) return st;
-    tf.sub = SubstepDev{Gmc, c_out};
-    tf.sc = SubstepCoef{dt, gamma, zeta, 1, has_zeta ? 1 : 0};
-    return launch_advective_tracer(terms->advection, grid, u, v, w, c, Gc, range, as_stream(stream), &tf);
+    const SubstepDev sub{Gmc, c_out};
+    return tracer_tendency_terms(__func__, grid, terms, kappa, kappa_e, nullptr, bcs_c, u, v, w, c, Gc, &sub,
+                                 SubstepCoef{dt, gamma, zeta, 1, has_zeta ? 1 : 0}, range, stream);
+}
+
+int ocn_compute_tracer_tendency_terms_rk3_forced(const ocn_grid *grid, const ocn_model_terms *terms, double kappa, const double *kappa_e,
+                                                 const ocn_forcing *forcing, const ocn_field_bcs *bcs_c, const double *u, const double *v,
+                                                 const double *w, const double *c, double *Gc, const double *Gmc, double *c_out, double dt,
+                                                 double gamma, double zeta, int32_t has_zeta, const int32_t *range, void *stream)
+{
+    const SubstepDev sub{Gmc, c_out};
+    return tracer_tendency_terms(__func__, grid, terms, kappa, kappa_e, forcing, bcs_c, u, v, w, c, Gc, &sub,
+                                 SubstepCoef{dt, gamma, zeta, 1, has_zeta ? 1 : 0}, range, stream);  // ONE launch, as without forcing
 }
 
 int ocn_compute_tracer_pair_tendency_terms_rk3(const ocn_grid *grid, const ocn_model_terms *terms, const double *kappa, const double *const *kappa_e,
@@ -1051,91 +1038,15 @@ int ocn_compute_tracer_pair_tendency_terms_rk3(const ocn_grid *grid, const ocn_m
         OCN_REQUIRE(c[t] && Gc[t] && c_out[t] && c_out[t] != c[t], "ocn_compute_tracer_pair_tendency_terms_rk3: null or aliased field pointer");
         OCN_REQUIRE(!has_zeta || (Gc_previous && Gc_previous[t]), "ocn_compute_tracer_pair_tendency_terms_rk3: G⁻ is required when has_zeta != 0");
         OCN_REQUIRE(!(kappa_e && kappa_e[t]) || terms->closure == 2, "kappa_e is only meaningful with closure == 2");
-        tf[t] = TracerFuse{};
-        tf[t].diffusion = terms->closure != 0;
-        tf[t].kappa = kappa[t];
-        tf[t].kappa_e = kappa_e ? kappa_e[t] : nullptr;
-        st = flux_side(grid, bcs_c ? bcs_c[t] : nullptr, "tracer", tf[t].bottom, tf[t].top);
+        const SubstepDev sub{Gc_previous ? Gc_previous[t] : nullptr, c_out[t]};
+        st = make_tracer_fuse(grid, terms, kappa[t], kappa_e ? kappa_e[t] : nullptr, bcs_c ? bcs_c[t] : nullptr, &sub,
+                              SubstepCoef{dt, gamma, zeta, 1, has_zeta ? 1 : 0}, tf[t]);
         if (st != OCN_SUCCESS) return st;
-        tf[t].sub = SubstepDev{Gc_previous ? Gc_previous[t] : nullptr, c_out[t]};
-        tf[t].sc = SubstepCoef{dt, gamma, zeta, 1, has_zeta ? 1 : 0};
     }
     int did = 0;
-    hipStream_t s = as_stream(stream);
-    const bool strict = strict_math(grid);
-    if (terms->advection == OCN_ADVECTION_WENO5)
-        st = strict ? ocn_strict::launch_tracer_pair_tendency(grid, u, v, w, c, Gc, range, s, tf, &did)
-                    : ocn_fast::launch_tracer_pair_tendency(grid, u, v, w, c, Gc, range, s, tf, &did);
-    else
-        st = strict ? ocn_strict_up::launch_tracer_pair_tendency(grid, u, v, w, c, Gc, range, s, tf, &did)
-                    : ocn_fast_up::launch_tracer_pair_tendency(grid, u, v, w, c, Gc, range, s, tf, &did);
+    st = OCN_LAUNCH_SCHEME(grid, terms->advection, launch_tracer_pair_tendency, grid, u, v, w, c, Gc, range, as_stream(stream), tf, &did);
     *launched = did;
     return st;
-}
-
-// A forced tracer: F rides inside the tracer kernels (tracer_finish / tracer_finish_general compiled with ocn::TracerFuseForced), between the
-// diffusion and the boundary fluxes.  Only Centered(order=2) advection on a (Periodic, Periodic, *) grid, whose kernel has no epilogue, takes
-// the small tracer_forcing_kernel after the diffusion kernel.
-int ocn_compute_tracer_tendency_terms_forced(const ocn_grid *grid, const ocn_model_terms *terms, double kappa, const double *kappa_e,
-                                             const ocn_forcing *forcing, const double *u, const double *v, const double *w, const double *c,
-                                             double *Gc, const int32_t *range, void *stream)
-{
-    if (forcing) {
-        OCN_REQUIRE(grid != nullptr, "grid is NULL");
-        int st = validate_forcing(grid, forcing, "ocn_compute_tracer_tendency_terms_forced", "the tracer");
-        if (st != OCN_SUCCESS) return st;
-    }
-    if (!forcing || forcing->n_terms == 0) return ocn_compute_tracer_tendency_terms(grid, terms, kappa, kappa_e, u, v, w, c, Gc, range, stream);
-    int st = validate_terms(grid, terms);
-    if (st != OCN_SUCCESS) return st;
-    OCN_REQUIRE(u && v && w && c && Gc, "ocn_compute_tracer_tendency_terms_forced: null field pointer");
-    OCN_REQUIRE(!kappa_e || terms->closure == 2, "kappa_e is only meaningful with closure == 2");
-    const ocn::ForcingDev fd = ocn::to_dev(forcing);
-    if (terms->advection == OCN_ADVECTION_CENTERED2 && xy_periodic(grid)) {
-        st = ocn_compute_tracer_tendency_terms(grid, terms, kappa, kappa_e, u, v, w, c, Gc, range, stream);
-        if (st != OCN_SUCCESS) return st;
-        return strict_math(grid) ? ocn_strict::launch_tracer_forcing(grid, fd, c, Gc, range, nullptr, as_stream(stream))
-                                 : ocn_fast::launch_tracer_forcing(grid, fd, c, Gc, range, nullptr, as_stream(stream));
-    }
-    TracerFuse tf{};  // advection, diffusion and F in one pass
-    tf.diffusion = terms->closure != 0;
-    tf.kappa = kappa;
-    tf.kappa_e = kappa_e;
-    return launch_advective_tracer(terms->advection, grid, u, v, w, c, Gc, range, as_stream(stream), &tf, &fd);
-}
-
-int ocn_compute_tracer_tendency_terms_rk3_forced(const ocn_grid *grid, const ocn_model_terms *terms, double kappa, const double *kappa_e,
-                                                 const ocn_forcing *forcing, const ocn_field_bcs *bcs_c, const double *u, const double *v,
-                                                 const double *w, const double *c, double *Gc, const double *Gmc, double *c_out, double dt,
-                                                 double gamma, double zeta, int32_t has_zeta, const int32_t *range, void *stream)
-{
-    const char *who = "ocn_compute_tracer_tendency_terms_rk3_forced";
-    if (forcing) {
-        OCN_REQUIRE(grid != nullptr, "grid is NULL");
-        int st = validate_forcing(grid, forcing, who, "the tracer");
-        if (st != OCN_SUCCESS) return st;
-    }
-    if (!forcing || forcing->n_terms == 0)
-        return ocn_compute_tracer_tendency_terms_rk3(grid, terms, kappa, kappa_e, bcs_c, u, v, w, c, Gc, Gmc, c_out, dt, gamma, zeta, has_zeta, range,
-                                                     stream);
-    int st = validate_terms(grid, terms);
-    if (st != OCN_SUCCESS) return st;
-    OCN_REQUIRE(xy_periodic(grid) || !range, "%s: ranges need Periodic x and y", who);
-    OCN_REQUIRE(terms->advection != OCN_ADVECTION_CENTERED2, "%s: advection must be WENO5 or UpwindBiased5", who);
-    OCN_REQUIRE(u && v && w && c && Gc && c_out, "%s: null field pointer", who);
-    OCN_REQUIRE(!has_zeta || Gmc, "%s: G⁻ is required when has_zeta != 0", who);
-    OCN_REQUIRE(c_out != c, "%s: the output must not alias the input", who);
-    OCN_REQUIRE(!kappa_e || terms->closure == 2, "kappa_e is only meaningful with closure == 2");
-    TracerFuse tf{};
-    tf.diffusion = terms->closure != 0;
-    tf.kappa = kappa;
-    tf.kappa_e = kappa_e;
-    st = flux_side(grid, bcs_c, "tracer", tf.bottom, tf.top);
-    if (st != OCN_SUCCESS) return st;
-    tf.sub = SubstepDev{Gmc, c_out};
-    tf.sc = SubstepCoef{dt, gamma, zeta, 1, has_zeta ? 1 : 0};
-    const ocn::ForcingDev fd = ocn::to_dev(forcing);
-    return launch_advective_tracer(terms->advection, grid, u, v, w, c, Gc, range, as_stream(stream), &tf, &fd);  // ONE launch, as without forcing
 }
 
 int ocn_split_explicit_substeps_blocked(const ocn_grid *grid, int32_t n, const double *weights, double dtau, double gravitational_acceleration,
@@ -1241,8 +1152,7 @@ int ocn_hydrostatic_momentum_ab2_step(const ocn_grid *grid, const ocn_model_term
     mf.sc = SubstepCoef{dt, 1.5 + chi, -(0.5 + chi), 1, euler ? 0 : 1};
     ocn::HydroFuse hf{eta, gravitational_acceleration, GU, GV, U_star, V_star};
     TermsDev t = to_dev(*terms);
-    return strict_math(grid) ? ocn_strict::launch_hydrostatic_momentum(grid, t, u, v, w, Gu, Gv, mf, hf, as_stream(stream))
-                                          : ocn_fast::launch_hydrostatic_momentum(grid, t, u, v, w, Gu, Gv, mf, hf, as_stream(stream));
+    return OCN_LAUNCH(grid, launch_hydrostatic_momentum, grid, t, u, v, w, Gu, Gv, mf, hf, as_stream(stream));
 }
 
 int ocn_barotropic_corrector_and_w(const ocn_grid *grid, const double *u_star, const double *v_star, double *u, double *v, double *w,
@@ -1348,11 +1258,8 @@ int ocn_compute_tracer_tendency(const ocn_grid *grid, const double *u, const dou
     int st = validate_weno(grid);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(u && v && w && c && Gc, "ocn_compute_tracer_tendency: null field pointer");
-    if (!xy_periodic(grid))
-        return strict_math(grid) ? ocn_strict::launch_tracer_tendency_general(grid, 0, u, v, w, c, Gc, range, as_stream(stream))
-                                              : ocn_fast::launch_tracer_tendency_general(grid, 0, u, v, w, c, Gc, range, as_stream(stream));
-    if (strict_math(grid)) return ocn_strict::launch_tracer_tendency(grid, u, v, w, c, Gc, range, as_stream(stream));
-    return ocn_fast::launch_tracer_tendency(grid, u, v, w, c, Gc, range, as_stream(stream));
+    if (!xy_periodic(grid)) return OCN_LAUNCH(grid, launch_tracer_tendency_general, grid, 0, u, v, w, c, Gc, range, as_stream(stream));
+    return OCN_LAUNCH(grid, launch_tracer_tendency, grid, u, v, w, c, Gc, range, as_stream(stream));
 }
 
 static int make_step_tuple(int32_t n, double *const *U, const double *const *Gn, double *const *Gm, const int32_t *locs,
@@ -1552,9 +1459,8 @@ int ocn_halo_pack_pressure(const ocn_grid *grid, const double *p, const double *
     int st = validate_pressure_planes(grid, "ocn_halo_pack_pressure");
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(p && u && send_west && send_east, "ocn_halo_pack_pressure: null pointer");
-    if (strict_math(grid))
-        return ocn_strict::launch_pressure_planes(grid, const_cast<double *>(p), const_cast<double *>(u), dt_correct, send_west, send_east, 0, as_stream(stream));
-    return ocn_fast::launch_pressure_planes(grid, const_cast<double *>(p), const_cast<double *>(u), dt_correct, send_west, send_east, 0, as_stream(stream));
+    return OCN_LAUNCH(grid, launch_pressure_planes, grid, const_cast<double *>(p), const_cast<double *>(u), dt_correct, send_west, send_east, 0,
+                      as_stream(stream));
 }
 int ocn_halo_unpack_pressure(const ocn_grid *grid, double *p, double *u, const double *recv_west, const double *recv_east, void *stream)
 {

@@ -539,17 +539,11 @@ static gen::Fields make_fields(const ocn_grid *grid, const double *u, const doub
     return F;
 }
 
-// tendencies.hip (same namespace): the LDS-tiled kernels over the interior box of a grid with walls in x / y
-int launch_momentum_tendencies_box(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu, double *Gv, double *Gw,
-                                   const int32_t box[4], int *launched, hipStream_t stream, const ocn::FuseArgs *fuse = nullptr, int ranged = 0);
-int launch_tracer_tendency_box(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c, double *Gc,
-                               const int32_t box[4], int *launched, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr, int ranged = 0,
-                               const ocn::ForcingDev *forcing = nullptr);
+// the launchers of this namespace, this file's own and the box launchers of tendencies.hip / physics.hip (the extra terms do not depend on
+// the advection scheme: the WENO namespaces only)
+#include "ocn_launchers_scheme.inc"
 #if !OCN_UPWIND
-// physics.hip (compiled for the WENO namespaces only; the extra terms do not depend on the advection scheme): the tiled finishing pass
-int launch_momentum_extra_box(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w, double *Gu, double *Gv,
-                              double *Gw, const int32_t box[4], int *launched, hipStream_t stream, const ocn::MomentumFinal *fin, int ranged = 0,
-                              const ocn::StokesDev *stokes = nullptr, const ocn::MomentumForcingDev *forcing = nullptr);
+#include "ocn_launchers_math.inc"
 #endif
 
 // Interior box + wall frames.  The topology-conditional reconstructions of a Bounded direction differ from the Periodic ones only within
@@ -683,6 +677,7 @@ int launch_tracer_tendency_general(const ocn_grid *grid, int centered2, const do
     return OCN_SUCCESS;
 }
 
+#if !OCN_UPWIND  // (no caller in the UpwindBiased namespaces: the extra terms do not depend on the advection scheme)
 // fin != NULL: the u / v bottom / top flux contributions and the next substep of u, v, w ride on this last pass over G (the finishing pass of
 // the Periodic grids): inside the tiled kernel on the box, as one more per-cell kernel on the frames
 int launch_momentum_extra_general(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w, double *Gu,
@@ -695,7 +690,6 @@ int launch_momentum_extra_general(const ocn_grid *grid, const ocn::TermsDev &t, 
     if (st != OCN_SUCCESS) return st;
     const gen::Fields F = make_fields(grid, u, v, w, 0);
     gen::GFrames cells = whole_range(r);
-#if !OCN_UPWIND
     // interior box (the tiled finishing pass with per-field layouts: every stress once per face, velocities through LDS) + wall frames
     int32_t box[4];
     if (interior_box(grid, 0, range, box)) {
@@ -704,7 +698,6 @@ int launch_momentum_extra_general(const ocn_grid *grid, const ocn::TermsDev &t, 
         if (st != OCN_SUCCESS) return st;
         if (launched) cells = frames_around(grid, box, r);
     }
-#endif
     ocn::with_extra_descriptors(stokes, forcing, [&](auto... x) {
         OCN_GEN_LAUNCH(momentum_extra_general<decltype(x)...>, cells, F, t, Gu, Gv, Gw, x...);
         return OCN_SUCCESS;
@@ -713,17 +706,6 @@ int launch_momentum_extra_general(const ocn_grid *grid, const ocn::TermsDev &t, 
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
 }
-
-int launch_tracer_diffusion_general(const ocn_grid *grid, double kappa, const double *kappa_e, const double *c, double *Gc,
-                                    const int32_t *range, hipStream_t stream)
-{
-    gen::GRange r;
-    int st = make_grange(grid, range, r);
-    if (st != OCN_SUCCESS) return st;
-    const gen::GFrames cells = whole_range(r);
-    OCN_GEN_LAUNCH(tracer_diffusion_general, cells, ocn::to_dev(*grid), kappa, kappa_e, c, Gc);
-    OCN_CHECK_HIP(hipGetLastError());
-    return OCN_SUCCESS;
-}
+#endif
 
 }  // namespace OCN_NS

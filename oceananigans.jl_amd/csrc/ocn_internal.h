@@ -161,127 +161,20 @@ namespace ocn {
 int validate_forcing(const ocn_grid *grid, const ocn_forcing *f, const char *who, const char *field);
 }
 
+// The launchers of the kernels that are compiled once per arithmetic variant (and per advection scheme): every signature is written once,
+// in the two fragments, and declared from there in each namespace that defines it (ocn_weno.h: OCN_NS).
 namespace ocn_strict {
-int launch_momentum_tendencies_general(const ocn_grid *grid, int centered2, const double *u, const double *v, const double *w, double *Gu,
-                                       double *Gv, double *Gw, const int32_t *range, hipStream_t stream, const ocn::MomentumFinal *fin = nullptr);
-int launch_tracer_tendency_general(const ocn_grid *grid, int centered2, const double *u, const double *v, const double *w, const double *c,
-                                   double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr,
-                                   const ocn::ForcingDev *forcing = nullptr);
-int launch_momentum_extra_general(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w, double *Gu,
-                                  double *Gv, double *Gw, const int32_t *range, hipStream_t stream, const ocn::MomentumFinal *fin = nullptr,
-                                  const ocn::StokesDev *stokes = nullptr, const ocn::MomentumForcingDev *forcing = nullptr);
-int launch_tracer_diffusion_general(const ocn_grid *grid, double kappa, const double *kappa_e, const double *c, double *Gc,
-                                    const int32_t *range, hipStream_t stream);
-int launch_pressure_planes(const ocn_grid *grid, double *p, double *u, double dt, double *west, double *east, int unpack, hipStream_t stream);
-int launch_momentum_tendencies(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
-                               double *Gv, double *Gw, const int32_t *range, const ocn::FuseArgs *fuse, hipStream_t stream);
-int launch_tracer_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c,
-                           double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr,
-                           const ocn::ForcingDev *forcing = nullptr);
-int launch_tracer_pair_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *const c[2],
-                                double *const Gc[2], const int32_t *range, hipStream_t stream, const ocn::TracerFuse fuse[2], int *launched);
-int launch_momentum_centered2(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu, double *Gv,
-                              double *Gw, const int32_t *range, hipStream_t stream);
-int launch_tracer_centered2(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c,
-                            double *Gc, const int32_t *range, hipStream_t stream);
-int launch_momentum_extra(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w,
-                          double *Gu, double *Gv, double *Gw, const int32_t *range, hipStream_t stream,
-                          const ocn::MomentumFinal *fin = nullptr, const ocn::StokesDev *stokes = nullptr,
-                          const ocn::MomentumForcingDev *forcing = nullptr);
-int launch_tracer_forcing(const ocn_grid *grid, const ocn::ForcingDev &forcing, const double *c, double *Gc, const int32_t *range,
-                          const ocn::TracerFuse *fuse, hipStream_t stream);
-int launch_hydrostatic_momentum(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w, double *Gu,
-                                double *Gv, const ocn::MomentumFinal &mf, const ocn::HydroFuse &hf, hipStream_t stream);
-int launch_tracer_diffusion(const ocn_grid *grid, double kappa, const double *kappa_e, const double *c, double *Gc,
-                            const int32_t *range, hipStream_t stream);
-int launch_amd_fused(const ocn_grid *grid, double Cnu, const double *u, const double *v, const double *w, double *nu_e, int ntr,
-                     const double *Ck, const double *const *c, double *const *kappa_e, hipStream_t stream, const int32_t *irange = nullptr);
-int launch_amd_viscosity(const ocn_grid *grid, double Cnu, const double *u, const double *v, const double *w, double *nu_e,
-                         hipStream_t stream);
-int launch_amd_diffusivity(const ocn_grid *grid, double Ck, const double *u, const double *v, const double *w, const double *c,
-                           double *kappa_e, hipStream_t stream);
-int launch_smagorinsky(const ocn_grid *grid, const ocn::TermsDev &t, const ocn_smagorinsky &closure, const double *u, const double *v,
-                       const double *w, double *nu_e, double *const *kappa_e, hipStream_t stream);
+#include "ocn_launchers_scheme.inc"
+#include "ocn_launchers_math.inc"
 }
 namespace ocn_fast {
-int launch_momentum_tendencies_general(const ocn_grid *grid, int centered2, const double *u, const double *v, const double *w, double *Gu,
-                                       double *Gv, double *Gw, const int32_t *range, hipStream_t stream, const ocn::MomentumFinal *fin = nullptr);
-int launch_tracer_tendency_general(const ocn_grid *grid, int centered2, const double *u, const double *v, const double *w, const double *c,
-                                   double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr,
-                                   const ocn::ForcingDev *forcing = nullptr);
-int launch_momentum_extra_general(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w, double *Gu,
-                                  double *Gv, double *Gw, const int32_t *range, hipStream_t stream, const ocn::MomentumFinal *fin = nullptr,
-                                  const ocn::StokesDev *stokes = nullptr, const ocn::MomentumForcingDev *forcing = nullptr);
-int launch_tracer_diffusion_general(const ocn_grid *grid, double kappa, const double *kappa_e, const double *c, double *Gc,
-                                    const int32_t *range, hipStream_t stream);
-int launch_pressure_planes(const ocn_grid *grid, double *p, double *u, double dt, double *west, double *east, int unpack, hipStream_t stream);
-int launch_momentum_tendencies(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
-                               double *Gv, double *Gw, const int32_t *range, const ocn::FuseArgs *fuse, hipStream_t stream);
-int launch_tracer_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c,
-                           double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr,
-                           const ocn::ForcingDev *forcing = nullptr);
-int launch_tracer_pair_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *const c[2],
-                                double *const Gc[2], const int32_t *range, hipStream_t stream, const ocn::TracerFuse fuse[2], int *launched);
-int launch_momentum_centered2(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu, double *Gv,
-                              double *Gw, const int32_t *range, hipStream_t stream);
-int launch_tracer_centered2(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c,
-                            double *Gc, const int32_t *range, hipStream_t stream);
-int launch_momentum_extra(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w,
-                          double *Gu, double *Gv, double *Gw, const int32_t *range, hipStream_t stream,
-                          const ocn::MomentumFinal *fin = nullptr, const ocn::StokesDev *stokes = nullptr,
-                          const ocn::MomentumForcingDev *forcing = nullptr);
-int launch_tracer_forcing(const ocn_grid *grid, const ocn::ForcingDev &forcing, const double *c, double *Gc, const int32_t *range,
-                          const ocn::TracerFuse *fuse, hipStream_t stream);
-int launch_hydrostatic_momentum(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w, double *Gu,
-                                double *Gv, const ocn::MomentumFinal &mf, const ocn::HydroFuse &hf, hipStream_t stream);
-int launch_tracer_diffusion(const ocn_grid *grid, double kappa, const double *kappa_e, const double *c, double *Gc,
-                            const int32_t *range, hipStream_t stream);
-int launch_amd_fused(const ocn_grid *grid, double Cnu, const double *u, const double *v, const double *w, double *nu_e, int ntr,
-                     const double *Ck, const double *const *c, double *const *kappa_e, hipStream_t stream, const int32_t *irange = nullptr);
-int launch_amd_viscosity(const ocn_grid *grid, double Cnu, const double *u, const double *v, const double *w, double *nu_e,
-                         hipStream_t stream);
-int launch_amd_diffusivity(const ocn_grid *grid, double Ck, const double *u, const double *v, const double *w, const double *c,
-                           double *kappa_e, hipStream_t stream);
-int launch_smagorinsky(const ocn_grid *grid, const ocn::TermsDev &t, const ocn_smagorinsky &closure, const double *u, const double *v,
-                       const double *w, double *nu_e, double *const *kappa_e, hipStream_t stream);
+#include "ocn_launchers_scheme.inc"
+#include "ocn_launchers_math.inc"
 }
-
-// advection = UpwindBiased(order=5): tendencies.hip compiled with OCN_UPWIND=1
+// advection = UpwindBiased(order=5): tendencies.hip and general.hip compiled with OCN_UPWIND=1
 namespace ocn_strict_up {
-int launch_momentum_tendencies_general(const ocn_grid *grid, int centered2, const double *u, const double *v, const double *w, double *Gu,
-                                       double *Gv, double *Gw, const int32_t *range, hipStream_t stream, const ocn::MomentumFinal *fin = nullptr);
-int launch_tracer_tendency_general(const ocn_grid *grid, int centered2, const double *u, const double *v, const double *w, const double *c,
-                                   double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr,
-                                   const ocn::ForcingDev *forcing = nullptr);
-int launch_momentum_extra_general(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w, double *Gu,
-                                  double *Gv, double *Gw, const int32_t *range, hipStream_t stream, const ocn::MomentumFinal *fin = nullptr,
-                                  const ocn::StokesDev *stokes = nullptr, const ocn::MomentumForcingDev *forcing = nullptr);
-int launch_tracer_diffusion_general(const ocn_grid *grid, double kappa, const double *kappa_e, const double *c, double *Gc,
-                                    const int32_t *range, hipStream_t stream);
-int launch_momentum_tendencies(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
-                               double *Gv, double *Gw, const int32_t *range, const ocn::FuseArgs *fuse, hipStream_t stream);
-int launch_tracer_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c,
-                           double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr,
-                           const ocn::ForcingDev *forcing = nullptr);
-int launch_tracer_pair_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *const c[2],
-                                double *const Gc[2], const int32_t *range, hipStream_t stream, const ocn::TracerFuse fuse[2], int *launched);
+#include "ocn_launchers_scheme.inc"
 }
 namespace ocn_fast_up {
-int launch_momentum_tendencies_general(const ocn_grid *grid, int centered2, const double *u, const double *v, const double *w, double *Gu,
-                                       double *Gv, double *Gw, const int32_t *range, hipStream_t stream, const ocn::MomentumFinal *fin = nullptr);
-int launch_tracer_tendency_general(const ocn_grid *grid, int centered2, const double *u, const double *v, const double *w, const double *c,
-                                   double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr,
-                                   const ocn::ForcingDev *forcing = nullptr);
-int launch_momentum_extra_general(const ocn_grid *grid, const ocn::TermsDev &t, const double *u, const double *v, const double *w, double *Gu,
-                                  double *Gv, double *Gw, const int32_t *range, hipStream_t stream, const ocn::MomentumFinal *fin = nullptr,
-                                  const ocn::StokesDev *stokes = nullptr, const ocn::MomentumForcingDev *forcing = nullptr);
-int launch_tracer_diffusion_general(const ocn_grid *grid, double kappa, const double *kappa_e, const double *c, double *Gc,
-                                    const int32_t *range, hipStream_t stream);
-int launch_momentum_tendencies(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
-                               double *Gv, double *Gw, const int32_t *range, const ocn::FuseArgs *fuse, hipStream_t stream);
-int launch_tracer_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c,
-                           double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr,
-                           const ocn::ForcingDev *forcing = nullptr);
-int launch_tracer_pair_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *const c[2],
-                                double *const Gc[2], const int32_t *range, hipStream_t stream, const ocn::TracerFuse fuse[2], int *launched);
+#include "ocn_launchers_scheme.inc"
 }

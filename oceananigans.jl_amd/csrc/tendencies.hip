@@ -1445,6 +1445,7 @@ __global__ __launch_bounds__(TX *TY) void tracer_pair_tendency_tiled(GridDev g, 
 // an interior row, so its corrected value is that row's.
 //   buffers: (Hx + 1) values per row;  pack:  west[h] = p[1 + h],  east[h] = p[nx - Hx + 1 + h]  (h < Hx),  east[Hx] = corrected u
 //   unpack:  p[1 - Hx + h] = west[h], u[1 - Hx] = west[Hx]  (from the west neighbour's `east`);  p[nx + 1 + h] = east[h]
+#if !OCN_UPWIND  // (independent of the advection scheme: launched through the WENO namespaces only)
 __global__ void pressure_planes_kernel(GridDev g, double *__restrict__ p, double *__restrict__ u, double pcdt, double *__restrict__ west,
                                        double *__restrict__ east, int unpack)
 {
@@ -1492,6 +1493,7 @@ int launch_pressure_planes(const ocn_grid *grid, double *p, double *u, double dt
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
 }
+#endif
 
 // z-chunking target: the launch should have at least this many workgroups (768 run concurrently: 256 CUs x 3)
 static int min_blocks()

@@ -257,7 +257,9 @@ class NonhydrostaticModel:
         self.forcing = forcing_terms
         self._forcing = [DeviceForcing(forcing_terms[n], grid, field_location(n)) if n in forcing_terms else None
                          for n in ("u", "v", "w") + tracers]
-        self._momentum_forced = any(f is not None for f in self._forcing[:3])
+        # (the structs never change: the references are taken once; entries of fields without forcing are NULL, u / v / w as one array)
+        self._forcing_refs = [None if f is None else f.ref for f in self._forcing]
+        self._momentum_forcing = _lib.forcing_array(self._forcing_refs[:3])
         self.forcing_steady = all(f is None or f.steady for f in self._forcing)
         if self._has_user_bcs and hasattr(grid.architecture, "partition") and any(
                 s is not None and (s.values is not None or s.func is not None) for b in bcs.values() for s in b.sides.values()):
@@ -549,30 +551,14 @@ def compute_tendencies_(model, rng=None, boundary_contributions=True):
     if model.general_terms:
         implicit = getattr(model, "_implicit", False)
         t = C.byref(model._terms_noclosure if implicit else model._terms)
-        frc = _refresh_forcing(model)
-        if model._stokes is not None:
-            model._stokes.refresh(model.clock.time)  # profiles that depend on t: sampled at the time of this tendency evaluation
-        if model._momentum_forced:
-            _lib.call("ocn_compute_momentum_tendencies_terms_forced", g.cref, t, None if model._stokes is None else C.byref(model._stokes.c),
-                      _lib.forcing_array(frc[:3]), model.u.ptr, model.v.ptr, model.w.ptr, Gn[0].ptr, Gn[1].ptr, Gn[2].ptr, r, s)
-        elif model._stokes is not None:
-            _lib.call("ocn_compute_momentum_tendencies_terms_stokes", g.cref, t, C.byref(model._stokes.c), model.u.ptr, model.v.ptr, model.w.ptr,
-                      Gn[0].ptr, Gn[1].ptr, Gn[2].ptr, r, s)
-        else:
-            _lib.call("ocn_compute_momentum_tendencies_terms", g.cref, t, model.u.ptr, model.v.ptr, model.w.ptr, Gn[0].ptr,
-                      Gn[1].ptr, Gn[2].ptr, r, s)
+        # the widest entry point of each family: an absent stokes drift / forcing is NULL (as csrc/model_driver.hip calls them)
+        stokes, frc = _refresh_stokes_and_forcing(model)
+        _lib.call("ocn_compute_momentum_tendencies_terms_forced", g.cref, t, stokes, model._momentum_forcing, model.u.ptr, model.v.ptr, model.w.ptr,
+                  Gn[0].ptr, Gn[1].ptr, Gn[2].ptr, r, s)
         for n, c in enumerate(model.tracers):
-            kappa, kappa_e = 0.0, None
-            if model.diffusivity_fields is not None:
-                kappa_e = model.diffusivity_fields["kappa_e"][n].ptr
-            elif model.closure is not None and not implicit:
-                kappa = model.closure.kappa_of(model.tracer_names[n])
-            if frc[3 + n] is not None:
-                _lib.call("ocn_compute_tracer_tendency_terms_forced", g.cref, t, kappa, kappa_e, frc[3 + n], model.u.ptr, model.v.ptr, model.w.ptr,
-                          c.ptr, Gn[3 + n].ptr, r, s)
-                continue
-            _lib.call("ocn_compute_tracer_tendency_terms", g.cref, t, kappa, kappa_e, model.u.ptr, model.v.ptr, model.w.ptr, c.ptr,
-                      Gn[3 + n].ptr, r, s)
+            kappa, kappa_e = _tracer_diffusivity(model, n)
+            _lib.call("ocn_compute_tracer_tendency_terms_forced", g.cref, t, kappa, kappa_e, frc[3 + n], model.u.ptr, model.v.ptr, model.w.ptr,
+                      c.ptr, Gn[3 + n].ptr, r, s)
         if implicit:
             add_vertically_implicit_explicit_fluxes(model, r)
         if boundary_contributions:
@@ -605,14 +591,25 @@ def implicit_step(model, dt):
               _lib.i32_array([f.loc for f in prog]), (C.c_double * len(prog))(*kappa), float(dt), stream_ptr())
 
 
-def _refresh_forcing(model):
-    """struct ocn_forcing references of the prognostic fields (None: not forced), the terms that depend on t sampled at clock.time"""
-    refs = []
+def _refresh_stokes_and_forcing(model):
+    """(struct ocn_stokes_drift reference, struct ocn_forcing references of the prognostic fields), None where the model has none; the
+    profiles and terms that depend on t are sampled at clock.time, the time of this tendency evaluation"""
+    if model._stokes is not None:
+        model._stokes.refresh(model.clock.time)
     for f in model._forcing:
         if f is not None:
             f.refresh(model.clock.time)
-        refs.append(None if f is None else f.ref)
-    return refs
+    return (None if model._stokes is None else C.byref(model._stokes.c)), model._forcing_refs
+
+
+def _tracer_diffusivity(model, n):
+    """(κ, pointer to κₑ) of tracer n as the tracer entry points take them: the κₑ field of an eddy-viscosity closure, else the closure's
+    number -- 0 without a closure, and with a vertically implicit one, whose term has kernels of its own"""
+    if model.diffusivity_fields is not None:
+        return 0.0, model.diffusivity_fields["kappa_e"][n].ptr
+    if model.closure is not None and not model._implicit:
+        return model.closure.kappa_of(model.tracer_names[n]), None
+    return 0.0, None
 
 
 def compute_boundary_tendency_contributions(model):
@@ -620,9 +617,7 @@ def compute_boundary_tendency_contributions(model):
     if not (model.general_terms and model._has_flux_bcs):
         return
     g, Gn, prog = model.grid, model.timestepper._Gn, model.prognostic_fields()
-    arr = (C.POINTER(_lib.CFieldBcs) * len(prog))(*[
-        (C.pointer(f.boundary_conditions.c_struct(g)) if f.boundary_conditions is not None and f.boundary_conditions.has_flux()
-         else C.POINTER(_lib.CFieldBcs)()) for f in prog])
+    arr = (C.POINTER(_lib.CFieldBcs) * len(prog))(*[_bcs_ref(f, g) for f in prog])
     _lib.call("ocn_apply_flux_bcs", g.cref, _lib.ptr_array([G.ptr for G in Gn]), _lib.ptr_array([f.ptr for f in prog]),
               _lib.i32_array([f.loc for f in prog]), arr, len(prog), stream_ptr())
 
@@ -737,15 +732,15 @@ def update_state_and_rk3_substep(model, dt, gamma, zeta, fill_halos=True, p_corr
 
 
 def _bcs_ref(field, grid):
+    """pointer to the field's struct ocn_field_bcs where one of its conditions is a flux, else NULL (false): an argument or an array element"""
     b = getattr(field, "boundary_conditions", None)
-    return C.byref(b.c_struct(grid)) if b is not None and b.has_flux() else None
+    return C.pointer(b.c_struct(grid)) if b is not None and b.has_flux() else C.POINTER(_lib.CFieldBcs)()
 
 
 def fused_tracer_launches(grid, terms_ref, u, v, w, tracers, kappas, kappa_es, Gn, Gm, outs, dt, gamma, zeta, has_zeta, rng, s, forcing=None):
-    """tendency + boundary flux + the next substep of every tracer: pairs of tracers share ONE launch
-    (ocn_compute_tracer_pair_tendency_terms_rk3: u, v, w and the tile staging are read once for both), a remaining single tracer -- and
-    ranges too small for the tiled kernel -- take ocn_compute_tracer_tendency_terms_rk3.  forcing: one struct ocn_forcing reference (or None)
-    per tracer; a forced tracer takes ocn_compute_tracer_tendency_terms_rk3_forced, and a pair with a forced tracer runs as two single launches."""
+    """tendency + boundary flux + the next substep of every tracer: pairs of unforced tracers may share ONE launch
+    (ocn_compute_tracer_pair_tendency_terms_rk3: u, v, w and the tile staging are read once for both; it says whether it launched), every
+    other tracer takes ocn_compute_tracer_tendency_terms_rk3_forced.  forcing: one struct ocn_forcing reference (or None) per tracer."""
     n, q = len(tracers), 0
     forcing = forcing or [None] * n
     r = None if rng is None else _lib.i32_array(list(rng))
@@ -753,9 +748,7 @@ def fused_tracer_launches(grid, terms_ref, u, v, w, tracers, kappas, kappa_es, G
         if q + 1 < n and forcing[q] is None and forcing[q + 1] is None:
             pair = (q, q + 1)
             did = C.c_int32(0)
-            bcs = (C.POINTER(_lib.CFieldBcs) * 2)(*[(C.pointer(tracers[t].boundary_conditions.c_struct(grid))
-                                                      if tracers[t].boundary_conditions is not None and tracers[t].boundary_conditions.has_flux()
-                                                      else C.POINTER(_lib.CFieldBcs)()) for t in pair])
+            bcs = (C.POINTER(_lib.CFieldBcs) * 2)(*[_bcs_ref(tracers[t], grid) for t in pair])
             _lib.call("ocn_compute_tracer_pair_tendency_terms_rk3", grid.cref, terms_ref, (C.c_double * 2)(*[float(kappas[t]) for t in pair]),
                       _lib.ptr_array([kappa_es[t] for t in pair]), bcs, u.ptr, v.ptr, w.ptr, _lib.ptr_array([tracers[t].ptr for t in pair]),
                       _lib.ptr_array([Gn[t].ptr for t in pair]), _lib.ptr_array([Gm[t].ptr for t in pair]),
@@ -765,13 +758,8 @@ def fused_tracer_launches(grid, terms_ref, u, v, w, tracers, kappas, kappa_es, G
                 q += 2
                 continue
         c = tracers[q]
-        if forcing[q] is not None:
-            _lib.call("ocn_compute_tracer_tendency_terms_rk3_forced", grid.cref, terms_ref, float(kappas[q]), kappa_es[q], forcing[q], _bcs_ref(c, grid),
-                      u.ptr, v.ptr, w.ptr, c.ptr, Gn[q].ptr, Gm[q].ptr, outs[q].data_ptr(), float(dt), float(gamma), float(zeta), int(has_zeta), r, s)
-            q += 1
-            continue
-        _lib.call("ocn_compute_tracer_tendency_terms_rk3", grid.cref, terms_ref, float(kappas[q]), kappa_es[q], _bcs_ref(c, grid), u.ptr, v.ptr,
-                  w.ptr, c.ptr, Gn[q].ptr, Gm[q].ptr, outs[q].data_ptr(), float(dt), float(gamma), float(zeta), int(has_zeta), r, s)
+        _lib.call("ocn_compute_tracer_tendency_terms_rk3_forced", grid.cref, terms_ref, float(kappas[q]), kappa_es[q], forcing[q], _bcs_ref(c, grid),
+                  u.ptr, v.ptr, w.ptr, c.ptr, Gn[q].ptr, Gm[q].ptr, outs[q].data_ptr(), float(dt), float(gamma), float(zeta), int(has_zeta), r, s)
         q += 1
 
 
@@ -791,40 +779,24 @@ def _update_state_and_rk3_substep_general(model, dt, gamma, zeta, fill_halos=Tru
     z, hz = (0.0, 0) if zeta is None else (float(zeta), 1)
     t = C.byref(model._terms)
     momentum_extra = (model.coriolis is not None or model.closure is not None or model.buoyancy is not None
-                      or isinstance(model.advection, (Centered, UpwindBiased)) or _bcs_ref(model.u, g) is not None or _bcs_ref(model.v, g) is not None
-                      or model._stokes is not None)
-    if model._stokes is not None:
-        model._stokes.refresh(model.clock.time)
-    frc = _refresh_forcing(model)
+                      or isinstance(model.advection, (Centered, UpwindBiased)) or bool(_bcs_ref(model.u, g)) or bool(_bcs_ref(model.v, g))
+                      or model._stokes is not None or any(f is not None for f in model._forcing[:3]))
+    stokes, frc = _refresh_stokes_and_forcing(model)
 
     def launch(rng=None):
         s = stream_ptr()  # read HERE: the Distributed hook runs the east buffer strip under torch.cuda.stream(side stream)
         r = None if rng is None else _lib.i32_array(list(rng))
-        if model._momentum_forced:
-            _lib.call("ocn_compute_momentum_tendencies_terms_rk3_forced", g.cref, t, None if model._stokes is None else C.byref(model._stokes.c),
-                      _lib.forcing_array(frc[:3]), _bcs_ref(model.u, g), _bcs_ref(model.v, g), model.u.ptr, model.v.ptr, model.w.ptr, Gn[0].ptr,
-                      Gn[1].ptr, Gn[2].ptr, Gm[0].ptr, Gm[1].ptr, Gm[2].ptr, alt[0].data_ptr(), alt[1].data_ptr(), alt[2].data_ptr(), float(dt),
-                      float(gamma), z, hz, r, s)
-        elif model._stokes is not None:
-            _lib.call("ocn_compute_momentum_tendencies_terms_rk3_stokes", g.cref, t, C.byref(model._stokes.c), _bcs_ref(model.u, g),
+        if momentum_extra:  # the widest entry point of the family: an absent stokes drift / forcing is NULL
+            _lib.call("ocn_compute_momentum_tendencies_terms_rk3_forced", g.cref, t, stokes, model._momentum_forcing, _bcs_ref(model.u, g),
                       _bcs_ref(model.v, g), model.u.ptr, model.v.ptr, model.w.ptr, Gn[0].ptr, Gn[1].ptr, Gn[2].ptr, Gm[0].ptr, Gm[1].ptr,
                       Gm[2].ptr, alt[0].data_ptr(), alt[1].data_ptr(), alt[2].data_ptr(), float(dt), float(gamma), z, hz, r, s)
-        elif momentum_extra:
-            _lib.call("ocn_compute_momentum_tendencies_terms_rk3", g.cref, t, _bcs_ref(model.u, g), _bcs_ref(model.v, g),
-                      model.u.ptr, model.v.ptr, model.w.ptr, Gn[0].ptr, Gn[1].ptr, Gn[2].ptr, Gm[0].ptr, Gm[1].ptr, Gm[2].ptr,
-                      alt[0].data_ptr(), alt[1].data_ptr(), alt[2].data_ptr(), float(dt), float(gamma), z, hz, r, s)
-        else:
+        else:  # nothing but WENO advection: the entry point of the correction-on-load kernel
             _lib.call("ocn_compute_momentum_tendencies_rk3", g.cref, model.u.ptr, model.v.ptr, model.w.ptr, Gn[0].ptr, Gn[1].ptr,
                       Gn[2].ptr, Gm[0].ptr, Gm[1].ptr, Gm[2].ptr, alt[0].data_ptr(), alt[1].data_ptr(), alt[2].data_ptr(),
                       float(dt), float(gamma), z, hz, None, 0.0, r, s)
         nt = len(model.tracers)
         if nt:
-            kappas, kappa_es = [0.0] * nt, [None] * nt
-            for n in range(nt):
-                if model.diffusivity_fields is not None:
-                    kappa_es[n] = model.diffusivity_fields["kappa_e"][n].ptr
-                elif model.closure is not None:
-                    kappas[n] = model.closure.kappa_of(model.tracer_names[n])
+            kappas, kappa_es = zip(*[_tracer_diffusivity(model, n) for n in range(nt)])
             fused_tracer_launches(g, t, model.u, model.v, model.w, model.tracers, kappas, kappa_es, Gn[3:], Gm[3:], alt[3:], dt, gamma, z, hz, rng, s,
                                   forcing=frc[3:])
 
@@ -1101,11 +1073,9 @@ class ModelRK3Driver:
             desc.nu_e = d["nu_e"].ptr
         for n, name in enumerate(names):
             desc.tracers[n] = model.tracers[n].ptr
+            desc.kappa[n], desc.kappa_e[n] = _tracer_diffusivity(model, n)
             if eddy:
                 desc.C_kappa[n] = model.closure.Ckappa_of(name) if amd else 0.0
-                desc.kappa_e[n] = d["kappa_e"][n].ptr
-            elif model.closure is not None:
-                desc.kappa[n] = model.closure.kappa_of(name)
         desc.pHY = None if model.pHY is None else model.pHY.ptr
         self._bcs = []  # keep the structs alive until the library has copied them
         for n, f in enumerate(prog):
@@ -1131,7 +1101,7 @@ class ModelRK3Driver:
         if model._stokes is not None:  # steady profiles: the device vectors stay the model's
             _lib.call("ocn_model_driver_set_stokes_drift", self._h, C.byref(model._stokes.c), 0)
         if any(f is not None for f in model._forcing):  # steady terms: the device vectors / arrays stay the model's
-            _lib.call("ocn_model_driver_set_forcing", self._h, _lib.forcing_array([None if f is None else f.ref for f in model._forcing]), 0)
+            _lib.call("ocn_model_driver_set_forcing", self._h, _lib.forcing_array(model._forcing_refs), 0)
 
     def time_step(self, dt):
         _lib.call("ocn_model_driver_time_step", self._h, float(dt), stream_ptr())
