@@ -1391,7 +1391,7 @@ int ocn_divergence(const ocn_grid *grid, const double *u, const double *v, const
     int st = validate_grid_any(grid);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(u && v && w && div, "ocn_divergence: null pointer");
-    return launch_source_term(grid, u, v, w, 1.0, 0, div, grid->Nx, (long long)grid->Nx * grid->Ny, as_stream(stream));
+    return launch_source_term(grid, u, v, w, 1.0, SourceOut::Divergence, div, grid->Nx, (long long)grid->Nx * grid->Ny, as_stream(stream));
 }
 
 int ocn_batched_tridiagonal_solve_z(int32_t Nx, int32_t Ny, int32_t Nz, const double *a, const double *b, const double *c,

@@ -329,7 +329,7 @@ __device__ __forceinline__ int stage_wavenumber(int p);
 
 // MODE 0: forward (natural -> stage order), 1: inverse (stage order -> natural), 2: forward, spectral solve, inverse;
 // MODE 3 / 4: the cosine transforms of the general Poisson solver (REDFT10 / REDFT01 / 2N of the real and of the imaginary part of every
-// column, Makhoul 1980: poisson.hip dct_shuffle_kernel) with their permutation and twiddle passes INSIDE the column transform -- 3: gather on
+// column, Makhoul 1980: poisson_general.hip dct_shuffle_kernel) with their permutation and twiddle passes INSIDE the column transform -- 3: gather on
 // load (v[n] = x[2n], v[N-1-n] = x[2n+1]), FFT, then X[k] = Re(w_k (V[k] + conj V[N-k])) + i Im(w_k (V[k] - conj V[N-k])) through one more
 // LDS exchange, stored in NATURAL wavenumber order; 4: V[k] = conj(w_k) (X[k] - i X[N-k]) / 2 from the natural-order column in LDS, inverse
 // FFT scaled by a.scale, scatter on store.  a.lc = w_k = e^{-i pi k / 2N}, k < N (complex, natural order).  One pass each instead of three.
@@ -538,13 +538,13 @@ static int launch_n(int mode, const ColFFTArgs &a, hipStream_t stream)
 
 static int launch_colfft_args(int N, int mode, const ColFFTArgs &a, hipStream_t stream);
 
-int launch_colfft(int N, int mode, double *data, long long col_stride, long long batch_stride, int ncols, int nbatch,
+int launch_colfft(int N, ColFFT mode, double *data, long long col_stride, long long batch_stride, int ncols, int nbatch,
                   const double *tw, const double *lx, const double *ly, const double *lc, double scale, int inner,
                   hipStream_t stream, int zero_mode)
 {
     ColFFTArgs a{data, col_stride, batch_stride, ncols, nbatch, tw, lx, ly, lc, scale, inner > 0 ? inner : 1, zero_mode, fft_xcd_remap(),
                  nullptr, 0, 0, 0, 0, nullptr};
-    return launch_colfft_args(N, mode, a, stream);
+    return launch_colfft_args(N, (int)mode, a, stream);
 }
 
 // MODE 5: REDFT10 along the column, -b / ((λx + λy) + λz) with the zero mode := 0, REDFT01 / 2N back -- the whole z part of a solve on a
@@ -554,7 +554,7 @@ int launch_colfft_dct_solve(int N, double *data, long long col_stride, int ncols
                             const double *ly, const double *lz, double scale, int inner, hipStream_t stream)
 {
     ColFFTArgs a{data, col_stride, 0, ncols, 1, tw, lx, ly, wd, scale, inner > 0 ? inner : 1, 1, fft_xcd_remap(), nullptr, 0, 0, 0, 0, lz};
-    return launch_colfft_args(N, 5, a, stream);
+    return launch_colfft_args(N, (int)ColFFT::DctSolve, a, stream);
 }
 
 // the inverse cosine transform (MODE 4) of real pairs as the last pass of a solve: written into the pressure field `p` (ColFFTArgs::preal)
@@ -564,7 +564,7 @@ int launch_colfft_dct_to_field(int N, double *data, long long col_stride, long l
 {
     ColFFTArgs a{data, col_stride, batch_stride, ncols, nbatch, tw, nullptr, nullptr, wd, scale, inner > 0 ? inner : 1, 1, fft_xcd_remap(),
                  p, p0, ps2, ps3, pdim, nullptr};
-    return launch_colfft_args(N, 4, a, stream);
+    return launch_colfft_args(N, (int)ColFFT::DctInverse, a, stream);
 }
 
 static int launch_colfft_args(int N, int mode, const ColFFTArgs &a, hipStream_t stream)
@@ -597,8 +597,8 @@ static int launch_colfft_args(int N, int mode, const ColFFTArgs &a, hipStream_t 
 
 // ---------------------------------------------------------------------------------------------------
 // Cosine transforms along x of a REAL array (Nx, Ny, Nz), Ny even, in place: the closed boxes of the general solver (poisson.hip,
-// `gallreal`).  The complex line (jp, kz) is the pair of real rows j = 2 jp (real part) and 2 jp + 1 (imaginary part) -- a cosine transform
-// maps reals to reals, so two rows ride on one complex FFT (poisson.hip dct_rowpair_kernel states the four passes this replaces).
+// the all-real variant).  The complex line (jp, kz) is the pair of real rows j = 2 jp (real part) and 2 jp + 1 (imaginary part) -- a cosine transform
+// maps reals to reals, so two rows ride on one complex FFT (poisson_general.hip dct_rowpair_kernel states the four passes this replaces).
 // MODE 5: REDFT10 (gather on load, FFT, twiddle through LDS, natural wavenumbers);  6: REDFT01 / 2N (pre-twiddle from LDS, inverse FFT, scatter
 // on store);  7: forward, -b / (λx + λy + λz [- m]) with the mode (1, 1, 1) := 0 iff m === 0, inverse -- the whole x part of a solve in ONE pass
 // over the array (16 B per cell instead of seven passes and 112).  Thread (c, t): line c of the workgroup's CB, elements t + (N / 8) r.
@@ -759,11 +759,11 @@ static int launch_rowdct_n(int mode, const RowDCTArgs &a, hipStream_t stream)
     return OCN_SUCCESS;
 }
 
-// mode 5 forward, 6 inverse, 7 forward + division by the eigenvalues + inverse (cosine transforms), 8 the same around the FFT of a Periodic x,
-// of the x lines of the real array `data` (Nx, Ny, Nz), Ny even
-int launch_rowdct(int Nx, int Ny, int Nz, int mode, double *data, const double *tw, const double *wd, const double *lx, const double *ly,
+// the x lines of the real array `data` (Nx, Ny, Nz), Ny even
+int launch_rowdct(int Nx, int Ny, int Nz, RowDCT rmode, double *data, const double *tw, const double *wd, const double *lx, const double *ly,
                   const double *lz, double shift, int shifted, hipStream_t stream)
 {
+    const int mode = (int)rmode;
     if (Ny % 2 != 0 || mode < 5 || mode > 8) {
         set_error("row transform: Ny = %d must be even and the mode (%d) 5 ... 8", Ny, mode);
         return OCN_ERR_INVALID_ARGUMENT;
@@ -779,7 +779,7 @@ int launch_rowdct(int Nx, int Ny, int Nz, int mode, double *data, const double *
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Slab pipeline of the distributed solver (poisson.hip, ocn_dist_poisson "fast" mode): x is partitioned, so the local
+// Slab pipeline of the distributed solver (poisson_dist.hip, ocn_dist_poisson "fast" mode): x is partitioned, so the local
 // directions y and z are transformed first -- y as a REAL transform of strided columns, z as a column FFT that writes straight
 // into the all-to-all send layout -- and x after the exchange with the fused FFT -> divide -> IFFT column kernel above.
 //

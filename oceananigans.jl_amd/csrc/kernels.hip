@@ -1370,13 +1370,13 @@ __global__ __launch_bounds__(256) void source_term_kernel(GridDev g, const doubl
     }
 }
 
-int launch_source_term(const ocn_grid *grid, const double *u, const double *v, const double *w, double dt, int out_mode,
+int launch_source_term(const ocn_grid *grid, const double *u, const double *v, const double *w, double dt, SourceOut out_mode,
                        double *out, long long ld1, long long ld2, hipStream_t stream, int perm_dim, int wrap)
 {
     GridDev g = to_dev(*grid);
     dim3 block(64, 4, 1);
     dim3 nb((g.Nx + 63) / 64, (g.Ny + 3) / 4, g.Nz);
-    switch (out_mode) {
+    switch ((int)out_mode) {
         case 0: hipLaunchKernelGGL(source_term_kernel<0>, nb, block, 0, stream, g, u, v, w, dt, out, ld1, ld2, perm_dim, wrap); break;
         case 1: hipLaunchKernelGGL(source_term_kernel<1>, nb, block, 0, stream, g, u, v, w, dt, out, ld1, ld2, perm_dim, wrap); break;
         case 2: hipLaunchKernelGGL(source_term_kernel<2>, nb, block, 0, stream, g, u, v, w, dt, out, ld1, ld2, perm_dim, wrap); break;
@@ -1451,11 +1451,11 @@ __global__ __launch_bounds__(256) void copy_real_kernel(GridDev g, const double 
     if (perm_dim >= 0) c[perm_dim] = dct_perm(c[perm_dim], perm_dim == 0 ? g.Nx : perm_dim == 1 ? g.Ny : g.Nz);
     p[at(L, i, j, k)] = phi[STRIDE * (c[0] + (long long)g.Nx * (c[1] + (long long)g.Ny * c[2]))];
 }
-int launch_copy_real(const ocn_grid *grid, const double *phi, double *p, hipStream_t stream, int real_source, int perm_dim)
+int launch_copy_real(const ocn_grid *grid, const double *phi, double *p, hipStream_t stream, CopySource source, int perm_dim)
 {
     GridDev g = to_dev(*grid);
     dim3 nb((g.Nx + 63) / 64, (g.Ny + 3) / 4, g.Nz), block(64, 4);
-    if (real_source)
+    if (source == CopySource::Real)
         hipLaunchKernelGGL(copy_real_kernel<1>, nb, block, 0, stream, g, phi, p, perm_dim);
     else
         hipLaunchKernelGGL(copy_real_kernel<2>, nb, block, 0, stream, g, phi, p, perm_dim);

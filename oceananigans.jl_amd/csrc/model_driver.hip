@@ -99,7 +99,7 @@ int fill(ocn_model_driver *d, double *const *fields, const int32_t *locs, const 
     return ocn_halo_exchange_end(d->comm, &d->grid, fields, locs, n, stream);
 }
 
-// solve_for_pressure! on one GPU or on a slab (the slab pipelines of the handle, csrc/poisson.hip)
+// solve_for_pressure! on one GPU or on a slab (the slab pipelines of the handle, csrc/poisson_dist.hip)
 int solve(ocn_model_driver *d, double stage_dt, void *stream)
 {
     if (!d->dsolver) return ocn_solve_for_pressure(d->solver, d->p, d->U[0], d->U[1], d->U[2], stage_dt, stream);

@@ -8,6 +8,37 @@ namespace ocn {
 
 constexpr int MAX_TUPLE = 8;
 
+// The modes of the pressure solver's launchers and kernels.  The values are the integers the kernels are instantiated on or receive as
+// arguments: a launcher casts, device code never sees the names.
+enum class SourceOut : int {  // launch_source_term: what the divergence is stored as
+    Divergence = 0,  // real div(U)
+    Complex = 1,     // complex div(U) / Δt (K8)
+    ComplexDz = 2,   // complex Δzᶜ div(U) / Δt (K9: the right-hand side of the Fourier-tridiagonal solver)
+    Real = 3,        // real div(U) / Δt (the source of a real-to-complex or cosine transform)
+    RealDz = 4,      // real Δzᶜ div(U) / Δt
+};
+enum class CopySource : int { Complex = 0, Real = 1 };  // launch_copy_real: real part of a complex array, or a real array
+enum class ColFFT : int {  // launch_colfft (colfft.hip MODE)
+    Forward = 0,       // natural -> stage order
+    Inverse = 1,       // stage order -> natural
+    Solve = 2,         // forward, division by the eigenvalues, inverse
+    DctForward = 3,    // REDFT10, natural order on both sides
+    DctInverse = 4,    // REDFT01 / 2N (launch_colfft_dct_to_field: stored into the pressure field)
+    DctSolve = 5,      // REDFT10, division, REDFT01 / 2N (launch_colfft_dct_solve)
+};
+enum class RowDCT : int {  // launch_rowdct (colfft.hip rowdct_kernel MODE): the x lines of a real array, two rows per complex line
+    Forward = 5,         // REDFT10
+    Inverse = 6,         // REDFT01 / 2N
+    Solve = 7,           // forward, division by the eigenvalues, inverse
+    PeriodicSolve = 8,   // the same around the FFT of a Periodic x
+};
+enum class DctShuffle : int {  // dct_shuffle_kernel, dct_rowpair_kernel and both halves of dct_twiddle_permute_kernel (poisson_general.hip)
+    Gather = 0,       // x -> v: even points, then odd points backwards
+    PostTwiddle = 1,  // forward: V -> X
+    PreTwiddle = 2,   // inverse: X -> V
+    Scatter = 3,      // v -> x
+};
+
 struct FieldTuple {
     double *f[MAX_TUPLE];
     int loc[MAX_TUPLE];
@@ -55,7 +86,7 @@ int launch_profile_marker(hipStream_t stream);
 int wait_stream(hipStream_t stream, double seconds, const char *who);
 int launch_hydrostatic_pressure(const ocn_grid *grid, const TermsDev &t, double *pHY, hipStream_t stream, const int32_t *irange = nullptr);
 int launch_stepper(const ocn_grid *grid, const StepTuple &st, int mode, double dt, double c1, double c2, hipStream_t stream);
-int launch_source_term(const ocn_grid *grid, const double *u, const double *v, const double *w, double dt, int out_mode,
+int launch_source_term(const ocn_grid *grid, const double *u, const double *v, const double *w, double dt, SourceOut out_mode,
                        double *out, long long ld1, long long ld2, hipStream_t stream, int perm_dim = -1, int wrap = 0);
 int launch_set_source(int Nx, int Ny, int Nz, const double *R, const double *dzc, int Hz, double *out, int complex_out,
                       long long ld1, long long ld2, hipStream_t stream);
@@ -65,7 +96,7 @@ int launch_implicit_free_surface_rhs(const ocn_grid *grid, const double *u, cons
                                      double *Qu, double *Qv, double *rhs, hipStream_t stream);
 int launch_barotropic_pressure_correction(const ocn_grid *grid, double *u, double *v, const double *eta, double grav, double dt,
                                           hipStream_t stream);
-int launch_copy_real(const ocn_grid *grid, const double *phi, double *p, hipStream_t stream, int real_source, int perm_dim = -1);
+int launch_copy_real(const ocn_grid *grid, const double *phi, double *p, hipStream_t stream, CopySource source, int perm_dim = -1);
 int launch_pressure_correct(const ocn_grid *grid, double *u, double *v, double *w, const double *p, double dt, hipStream_t stream);
 int launch_main_diagonal(const ocn_grid *grid, int nxh, const double *lx, const double *ly, double *D, hipStream_t stream);
 int launch_tridiag_z(int Nx, int Ny, int Nz, const double *a, const double *b, const double *c, const double *f, double *t,
@@ -88,12 +119,11 @@ int launch_main_diagonal_xy(int dim, int Nx, int Ny, int Nz, int H, const double
 int launch_source_term_stretched(const ocn_grid *grid, int dim, const double *dc, const double *u, const double *v, const double *w, double dt,
                                  double *out, int perm_dim, hipStream_t stream);
 int launch_set_source_stretched(int Nx, int Ny, int Nz, const double *R, int dim, const double *dc, int H, double *out, hipStream_t stream);
-// column FFTs (colfft.hip): mode 0 forward (natural -> stage order), 1 inverse (stage order -> natural),
-// 2 forward + spectral solve + inverse.  N in {64, 128, 256, 512}.
+// column FFTs (colfft.hip).  N in {64, 128, 256, 512}.
 bool colfft_supported(int N);
 int colfft_wavenumber(int N, int p);
 std::vector<double> colfft_twiddles(int N);
-int launch_colfft(int N, int mode, double *data, long long col_stride, long long batch_stride, int ncols, int nbatch,
+int launch_colfft(int N, ColFFT mode, double *data, long long col_stride, long long batch_stride, int ncols, int nbatch,
                   const double *tw, const double *lx, const double *ly, const double *lc, double scale, int inner,
                   hipStream_t stream, int zero_mode = 1);
 int launch_colfft_dct_solve(int N, double *data, long long col_stride, int ncols, const double *tw, const double *wd, const double *lx,
@@ -142,7 +172,7 @@ int launch_free_surface_ab2(const ocn_grid *grid, const double *w, double *eta, 
                             hipStream_t stream);
 int launch_halo_plane_x(const ocn_grid *grid, double *field, int loc, int which, double *buf, int unpack, hipStream_t stream);
 int launch_halo_pack_x_fields(const ocn_grid *grid, const FieldTuple &ft, double *west, double *east, int unpack, hipStream_t stream);
-int launch_rowdct(int Nx, int Ny, int Nz, int mode, double *data, const double *tw, const double *wd, const double *lx, const double *ly,
+int launch_rowdct(int Nx, int Ny, int Nz, RowDCT mode, double *data, const double *tw, const double *wd, const double *lx, const double *ly,
                   const double *lz, double shift, int shifted, hipStream_t stream);
 int launch_colfft_slab_z(int Nz, int inverse, const double *in, double *out, int nx, int NyH, int R, const double *tw, hipStream_t stream);
 // row FFTs (rowfft.hip): inverse = 0: [div(u,v,w)/dt | real_in] -> half spectrum;  1: half spectrum -> rows of haloed p
