@@ -430,6 +430,40 @@ int ocn_add_vertically_implicit_explicit_fluxes(const ocn_grid *grid, double nu,
  * pointers / location masks / numbers (ν for velocities).  Nz <= 2048 (the multipliers of one column live in LDS). */
 int ocn_implicit_vertical_diffusion_step(const ocn_grid *grid, int32_t n, double *const *fields, const int32_t *locs, const double *kappa,
                                          double dt, void *stream);
+/* ---- Closures of the VerticalFormulation with ν, κ FIELDS at (Center, Center, Face); ConvectiveAdjustmentVerticalDiffusivity ----
+ * (csrc/vertical_diffusivity.hip; z Bounded, x and y not Flat, halos >= 1 in x, y and z for all three entry points; one GPU; strict math
+ * whatever the math mode) */
+typedef struct ocn_convective_adjustment {
+    double convective_kappa_z, convective_nu_z;  /* where ∂z_b < 0 */
+    double background_kappa_z, background_nu_z;  /* where ∂z_b >= 0 (a gradient of exactly 0 is stable) */
+} ocn_convective_adjustment;
+/* compute_convective_adjustment_diffusivities! (convective_adjustment_vertical_diffusivity.jl:91-123) over i = 1..Nx, j = 1..Ny,
+ * k = 1..Nz -- the launch of the HydrostaticFreeSurfaceModel: face Nz+1 of kappa_c / kappa_u ((Center, Center, Face) fields with halos) is
+ * NOT written, nor any halo; the caller fills the x / y halos afterwards.  terms: buoyancy kind, g, alpha, beta, T, S are read (nothing
+ * else); OCN_BUOYANCY_NONE: every face is stable.  T / S are read at k = 0 (the bottom halo).  The four coefficients must be finite.
+ * OCN_ERR_INVALID_ARGUMENT: a z that is not Bounded, a buoyancy kind whose tracer pointer is NULL, kappa_c == kappa_u. */
+int ocn_compute_convective_adjustment_diffusivities(const ocn_grid *grid, const ocn_model_terms *terms,
+                                                    const ocn_convective_adjustment *closure, double *kappa_c, double *kappa_u, void *stream);
+/* The closure term of a VerticalFormulation closure (abstract_scalar_diffusivity_closure.jl:198-211) ADDED to tendencies that hold every
+ * other term:  viscous_flux_uz = -ℑxᶠᵃᵃ(kappa_u) ∂z u,  viscous_flux_vz = -ℑyᵃᶠᵃ(kappa_u) ∂z v,  diffusive_flux_z = -kappa_c[n] ∂z c[n],  no
+ * horizontal flux.  boundary_only != 0: the VerticallyImplicitTimeDiscretization variant (:221-260: the flux at k == 1 | k == Nz+1, zero on
+ * interior faces); 0: ExplicitTimeDiscretization.  kappa_u and kappa_c[n]: (Center, Center, Face) fields whose x / y halos are filled and
+ * whose face Nz+1 holds a finite value.  u == NULL: no momentum part (then kappa_u, v, Gu, Gv are NULL too).  kappa_c / c / Gc: HOST arrays
+ * of n_tracers device pointers.  range and the excluded peripheries as for ocn_add_vertically_implicit_explicit_fluxes. */
+int ocn_add_vertical_diffusivity_fluxes(const ocn_grid *grid, const double *kappa_u, const double *u, const double *v, double *Gu, double *Gv,
+                                        int32_t n_tracers, const double *const *kappa_c, const double *const *c, double *const *Gc,
+                                        int32_t boundary_only, const int32_t *range, void *stream);
+/* implicit_step! with a diffusivity FIELD per field, n fields in place:  (1 - dt ∂z κ ∂z) φ = φ  over columns i = 1..Nx, j = 1..Ny, rows
+ * k = 1..Nz: the Center-in-z rows (vertically_implicit_diffusion_solver.jl:55-78), κz located as abstract_scalar_diffusivity_closure.jl:307-315
+ * locates a (Center, Center, Face) array (κ itself for OCN_LOC_CCC, ℑxᶠᵃᵃ(κ) for OCN_LOC_FCC, ℑyᵃᶠᵃ(κ) for OCN_LOC_CFC), eliminated as
+ * solve_batched_tridiagonal_system_z! does.  fields / locs / kappa / scratch: HOST arrays of n device pointers / location masks / device
+ * pointers / device pointers.  kappa[f]: faces 2..Nz+1 are read (x / y halos filled for the Face-in-x / y locations); finite and >= 0 is
+ * the caller's business.  Fields with the same kappa[f] and locs[f] share a matrix and are swept together; scratch[f] of the FIRST field
+ * of such a group receives its Nx Ny Nz multipliers (the entries of the group's other fields are ignored); groups need distinct arrays.
+ * No limit on Nz.  OCN_ERR_INVALID_ARGUMENT: a Face-in-z location (w has no implicit step in the hydrostatic model), a NULL or shared
+ * scratch array, the same field twice. */
+int ocn_implicit_vertical_diffusion_step_fields(const ocn_grid *grid, int32_t n, double *const *fields, const int32_t *locs,
+                                                const double *const *kappa, double *const *scratch, double dt, void *stream);
 /* cache_previous_tendencies! (src/TimeSteppers/store_tendencies.jl:6-22) */
 int ocn_cache_previous_tendencies(const ocn_grid *grid, int32_t n, double *const *Gm, const double *const *Gn,
                                   const int32_t *locs, void *stream);

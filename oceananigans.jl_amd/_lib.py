@@ -80,6 +80,12 @@ class CModelDriverDesc(C.Structure):
                 ("pHY", C.c_void_p), ("bcs", C.POINTER(CFieldBcs) * (3 + MODEL_MAX_TRACERS))]
 
 
+class CConvectiveAdjustment(C.Structure):
+    """struct ocn_convective_adjustment"""
+    _fields_ = [("convective_kappa_z", C.c_double), ("convective_nu_z", C.c_double), ("background_kappa_z", C.c_double),
+                ("background_nu_z", C.c_double)]
+
+
 class CSmagorinsky(C.Structure):
     """struct ocn_smagorinsky"""
     _fields_ = [("C", C.c_double), ("Cb", C.c_double), ("lilly", C.c_int32), ("n_tracers", C.c_int32), ("Pr", C.c_double * MODEL_MAX_TRACERS)]
@@ -181,6 +187,10 @@ _SIGS = {
     "ocn_add_vertically_implicit_explicit_fluxes": [C.POINTER(CGrid), _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _i32, C.POINTER(_dbl), C.POINTER(_vp),
                                                     C.POINTER(_vp), C.POINTER(_i32), _vp],
     "ocn_implicit_vertical_diffusion_step": [C.POINTER(CGrid), _i32, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_dbl), _dbl, _vp],
+    "ocn_compute_convective_adjustment_diffusivities": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CConvectiveAdjustment), _vp, _vp, _vp],
+    "ocn_add_vertical_diffusivity_fluxes": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _vp, _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                                            _i32, C.POINTER(_i32), _vp],
+    "ocn_implicit_vertical_diffusion_step_fields": [C.POINTER(CGrid), _i32, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_vp), C.POINTER(_vp), _dbl, _vp],
     "ocn_cache_previous_tendencies": [C.POINTER(CGrid), _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), _vp],
     "ocn_pressure_correct_velocities": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _dbl, _vp],
     "ocn_divergence": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _vp],

@@ -1365,6 +1365,75 @@ int ocn_implicit_vertical_diffusion_step(const ocn_grid *grid, int32_t n, double
     return launch_ivd_implicit_step(grid, n, fields, locs, kappa, dt, as_stream(stream));
 }
 
+// the three entry points of vertical_diffusivity.hip: a Bounded z, and the x / y neighbours of a κ field are read
+static int validate_vertical_diffusivity(const ocn_grid *grid, const char *who)
+{
+    int st = validate_grid_any(grid);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(grid->tz == OCN_BOUNDED, "%s: needs a grid that is Bounded in the z-direction", who);
+    OCN_REQUIRE(grid->tx != OCN_FLAT && grid->ty != OCN_FLAT, "%s: a Flat x or y is not implemented", who);
+    OCN_REQUIRE(grid->Hx >= 1 && grid->Hy >= 1 && grid->Hz >= 1, "%s: halo >= 1 required", who);
+    return OCN_SUCCESS;
+}
+
+int ocn_compute_convective_adjustment_diffusivities(const ocn_grid *grid, const ocn_model_terms *terms,
+                                                    const ocn_convective_adjustment *closure, double *kappa_c, double *kappa_u, void *stream)
+{
+    const char *who = "ocn_compute_convective_adjustment_diffusivities";
+    int st = validate_vertical_diffusivity(grid, who);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(terms && closure, "%s: null terms / closure", who);
+    OCN_REQUIRE(kappa_c && kappa_u, "%s: null field pointer", who);
+    OCN_REQUIRE(kappa_c != kappa_u, "%s: kappa_c and kappa_u are the same array", who);
+    const int b = terms->buoyancy;
+    OCN_REQUIRE(b >= OCN_BUOYANCY_NONE && b <= OCN_BUOYANCY_SEAWATER_S, "%s: unknown buoyancy %d", who, b);
+    if (b == OCN_BUOYANCY_TRACER || b == OCN_BUOYANCY_SEAWATER_TS || b == OCN_BUOYANCY_SEAWATER_T)
+        OCN_REQUIRE(terms->T != nullptr, "%s: the T (or b) tracer is NULL", who);
+    if (b == OCN_BUOYANCY_SEAWATER_TS || b == OCN_BUOYANCY_SEAWATER_S) OCN_REQUIRE(terms->S != nullptr, "%s: the S tracer is NULL", who);
+    OCN_REQUIRE(std::isfinite(closure->convective_kappa_z) && std::isfinite(closure->convective_nu_z) &&
+                    std::isfinite(closure->background_kappa_z) && std::isfinite(closure->background_nu_z),
+                "%s: the four coefficients must be finite", who);
+    return launch_convective_adjustment_diffusivities(grid, terms, closure, kappa_c, kappa_u, as_stream(stream));
+}
+
+int ocn_add_vertical_diffusivity_fluxes(const ocn_grid *grid, const double *kappa_u, const double *u, const double *v, double *Gu, double *Gv,
+                                        int32_t n_tracers, const double *const *kappa_c, const double *const *c, double *const *Gc,
+                                        int32_t boundary_only, const int32_t *range, void *stream)
+{
+    const char *who = "ocn_add_vertical_diffusivity_fluxes";
+    int st = validate_vertical_diffusivity(grid, who);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(n_tracers >= 0 && n_tracers <= MAX_TUPLE, "%s: number of tracers %d outside 0..%d", who, n_tracers, MAX_TUPLE);
+    if (u) {
+        OCN_REQUIRE(kappa_u && v && Gu && Gv, "%s: null field pointer (u is given: kappa_u, v, Gu, Gv are needed)", who);
+    } else {
+        OCN_REQUIRE(!kappa_u && !v && !Gu && !Gv, "%s: u is NULL (no momentum part) but another momentum pointer is not", who);
+        OCN_REQUIRE(n_tracers >= 1, "%s: nothing to do (u is NULL and n_tracers is 0)", who);
+    }
+    if (n_tracers) OCN_REQUIRE(kappa_c && c && Gc, "%s: null tracer array", who);
+    for (int n = 0; n < n_tracers; ++n) OCN_REQUIRE(kappa_c[n] && c[n] && Gc[n], "%s: tracer %d: null pointer", who, n);
+    return launch_vertical_diffusivity_fluxes(grid, kappa_u, u, v, Gu, Gv, n_tracers, kappa_c, c, Gc, boundary_only != 0, range,
+                                              as_stream(stream));
+}
+
+int ocn_implicit_vertical_diffusion_step_fields(const ocn_grid *grid, int32_t n, double *const *fields, const int32_t *locs,
+                                                const double *const *kappa, double *const *scratch, double dt, void *stream)
+{
+    const char *who = "ocn_implicit_vertical_diffusion_step_fields";
+    int st = validate_vertical_diffusivity(grid, who);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(n >= 1 && n <= MAX_TUPLE, "%s: number of fields %d outside 1..%d", who, n, MAX_TUPLE);
+    OCN_REQUIRE(fields && locs && kappa && scratch, "%s: null tuple pointer", who);
+    OCN_REQUIRE(std::isfinite(dt) && dt >= 0, "%s: dt = %g must be finite and >= 0", who, dt);
+    for (int f = 0; f < n; ++f) {
+        OCN_REQUIRE(fields[f] != nullptr && kappa[f] != nullptr, "%s: field %d: null pointer", who, f);
+        OCN_REQUIRE(locs[f] == OCN_LOC_CCC || locs[f] == OCN_LOC_FCC || locs[f] == OCN_LOC_CFC,
+                    "%s: field %d: location %d is none of ccc, fcc, cfc (Face-in-z fields have no implicit step here)", who, f, locs[f]);
+        for (int q = 0; q < f; ++q) OCN_REQUIRE(fields[q] != fields[f], "%s: fields %d and %d are the same array", who, q, f);
+    }
+    return launch_ivd_implicit_step_fields(grid, n, fields, locs, kappa, scratch, dt, as_stream(stream));
+}
+
 int ocn_cache_previous_tendencies(const ocn_grid *grid, int32_t n, double *const *Gm, const double *const *Gn,
                                   const int32_t *locs, void *stream)
 {

@@ -23,33 +23,11 @@
 //     arithmetic so that a column has several independent loads in flight.
 //
 // Bandwidth-bound: one strict build (no FMA contraction) whatever the math mode, bit-identical to tests/implicit_diffusion_numpy.py.
-#include "ocn_internal.h"
+#include "ocn_ivd.h"
 
 namespace ocn {
 
 namespace ivd {
-
-struct Spacings {
-    double dz;
-    const double *dzc, *dzf;
-    int Hz;
-    __device__ __forceinline__ double dzC(int k) const { return dzc ? uniform_load(dzc, k + Hz - 1) : dz; }
-    __device__ __forceinline__ double dzF(int k) const { return dzf ? uniform_load(dzf, k + Hz - 1) : dz; }
-};
-__device__ __forceinline__ Spacings spacings_of(const GridDev &g) { return Spacings{g.dz, g.dzc, g.dzf, g.Hz}; }
-
-struct Range {
-    int i0, i1, j0, j1, k0, k1;
-    int ou, ov, ow;  // first index written for Gu (in i), Gv (in j), Gw (in k)
-};
-
-__device__ __forceinline__ bool cell_of(const Range &r, int &i, int &j, int &k)
-{
-    i = r.i0 + blockIdx.x * 64 + threadIdx.x;
-    j = r.j0 + blockIdx.y * 4 + threadIdx.y;
-    k = r.k0 + blockIdx.z;
-    return i <= r.i1 && j <= r.j1;
-}
 
 // G <- G - ∂ⱼτᵢⱼ with the vertically implicit part of τᵢ₃ left out
 __global__ __launch_bounds__(256) void momentum_explicit_part(GridDev g, double nu, const double *__restrict__ u, const double *__restrict__ v,
@@ -249,7 +227,7 @@ __global__ __launch_bounds__(256) void implicit_step(GridDev g, Columns cols, do
 
 }  // namespace ivd
 
-static int make_range(const ocn_grid *grid, const int32_t *range, ivd::Range &r)
+int make_ivd_range(const ocn_grid *grid, const int32_t *range, ivd::Range &r)
 {
     if (range) {
         r.i0 = range[0]; r.i1 = range[1]; r.j0 = range[2]; r.j1 = range[3]; r.k0 = range[4]; r.k1 = range[5];
@@ -272,7 +250,7 @@ int launch_ivd_explicit_part(const ocn_grid *grid, double nu, const double *u, c
                              hipStream_t stream)
 {
     ivd::Range r;
-    int st = make_range(grid, range, r);
+    int st = make_ivd_range(grid, range, r);
     if (st != OCN_SUCCESS) return st;
     const int wx = r.i1 - r.i0 + 1, wy = r.j1 - r.j0 + 1, wz = r.k1 - r.k0 + 1;
     if (wx < 1 || wy < 1 || wz < 1) return OCN_SUCCESS;

@@ -82,6 +82,15 @@ int launch_ivd_explicit_part(const ocn_grid *grid, double nu, const double *u, c
                              hipStream_t stream);
 int launch_ivd_implicit_step(const ocn_grid *grid, int n, double *const *fields, const int32_t *locs, const double *kappa, double dt,
                              hipStream_t stream);
+// vertical_diffusivity.hip: ConvectiveAdjustmentVerticalDiffusivity's κ fields, the term of a closure with (Center, Center, Face) ν / κ fields
+// added to G, and the implicit step of n fields with a κ field each
+int launch_convective_adjustment_diffusivities(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_convective_adjustment *closure,
+                                               double *kappa_c, double *kappa_u, hipStream_t stream);
+int launch_vertical_diffusivity_fluxes(const ocn_grid *grid, const double *kappa_u, const double *u, const double *v, double *Gu, double *Gv,
+                                       int n_tracers, const double *const *kappa_c, const double *const *c, double *const *Gc,
+                                       int boundary_only, const int32_t *range, hipStream_t stream);
+int launch_ivd_implicit_step_fields(const ocn_grid *grid, int n, double *const *fields, const int32_t *locs, const double *const *kappa,
+                                    double *const *scratch, double dt, hipStream_t stream);
 int launch_profile_marker(hipStream_t stream);
 int wait_stream(hipStream_t stream, double seconds, const char *who);
 int launch_hydrostatic_pressure(const ocn_grid *grid, const TermsDev &t, double *pHY, hipStream_t stream, const int32_t *irange = nullptr);

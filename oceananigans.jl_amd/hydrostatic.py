@@ -9,8 +9,11 @@ The horizontal momentum and tracer tendencies are the terms of the Nonhydrostati
 ∂x pHY′, ScalarDiffusivity, flux boundary conditions) plus the barotropic pressure gradient g ∇η; w is diagnosed from continuity;
 there is no pressure solve.  momentum_advection = VectorInvariant() (the reference's default: enstrophy-conserving vorticity flux,
 energy-conserving vertical advection and kinetic-energy gradient) or a flux-form scheme.  closure = ScalarDiffusivity(...), explicit or
-with VerticallyImplicitTimeDiscretization() (QAB2, fused = False: implicit_step! of u, v and the tracers after their ab2 step).  NOT in this slice (each raises):
+with VerticallyImplicitTimeDiscretization() (QAB2, fused = False: implicit_step! of u, v and the tracers after their ab2 step), or
+ConvectiveAdjustmentVerticalDiffusivity(...) (QAB2, fused = False, one GPU: κᶜ, κᵘ fields computed in update_state!, their term and the
+field-valued implicit step in csrc/vertical_diffusivity.hip).  NOT in this slice (each raises):
 SplitExplicitFreeSurface / ImplicitFreeSurface, upwinding / WENO vector-invariant variants, z-star coordinates, eddy-viscosity closures,
+closure tuples,
 a tracer advection scheme different from the momentum one, Distributed architectures.
 """
 import ctypes as C
@@ -19,10 +22,10 @@ import torch
 
 from . import _lib
 from .architectures import stream_ptr
-from .fields import fill_halo_regions
+from .fields import ZFaceField, fill_halo_regions
 from .grids import Bounded, Periodic
 from .models import NonhydrostaticModel, compute_boundary_tendency_contributions, update_hydrostatic_pressure
-from .physics import Centered, is_vertically_implicit, owns_eddy_fields
+from .physics import Centered, ConvectiveAdjustmentVerticalDiffusivity, is_vertically_implicit, owns_eddy_fields
 
 g_Earth = 9.80665  # Oceananigans.BuoyancyFormulations.g_Earth
 
@@ -201,6 +204,18 @@ class HydrostaticFreeSurfaceModel:
             container_advection = momentum_advection
         if owns_eddy_fields(closure):
             raise NotImplementedError("eddy-viscosity closures are not part of this slice")
+        if isinstance(closure, (tuple, list)):
+            raise NotImplementedError("closure tuples are not implemented: give one closure")
+        # closure = ConvectiveAdjustmentVerticalDiffusivity(...): the reference's launch sequence with QAB2 on one GPU, in both discretizations
+        self._cavd = isinstance(closure, ConvectiveAdjustmentVerticalDiffusivity)
+        if self._cavd:
+            if fused:
+                raise NotImplementedError("ConvectiveAdjustmentVerticalDiffusivity runs the reference's launch sequence (fused = False)")
+            if self.split_rk3:
+                raise NotImplementedError("ConvectiveAdjustmentVerticalDiffusivity with SplitRungeKutta3 is not implemented")
+            if self._dist is not None or hasattr(arch, "partition"):
+                raise NotImplementedError("ConvectiveAdjustmentVerticalDiffusivity on a slab-partitioned (Distributed) grid is not implemented")
+            fused = False
         # closure = ScalarDiffusivity(VerticallyImplicitTimeDiscretization(), ...): the reference's launch sequence with QAB2 on one GPU
         # (hydrostatic_free_surface_ab2_step.jl:39-108: implicit_step! of u, v and every tracer after its ab2 step; w is diagnostic)
         self._implicit = is_vertically_implicit(closure)
@@ -216,9 +231,17 @@ class HydrostaticFreeSurfaceModel:
         # its pressure solver and w tendency are simply not used
         self._nh = NonhydrostaticModel(grid, advection=container_advection, tracers=tracers, timestepper="QuasiAdamsBashforth2",
                                        closure=closure, buoyancy=buoyancy, coriolis=coriolis, boundary_conditions=boundary_conditions,
-                                       pressure_solver=None, math_mode=math_mode)
+                                       pressure_solver=None, math_mode=math_mode, _hydrostatic_container=True)
         nh = self._nh
         grid = nh.grid  # (halo-inflated / math-mode-pinned by the container model)
+        # build_diffusivity_fields (convective_adjustment_vertical_diffusivity.jl:85): κᶜ and κᵘ, ZFaceFields with default conditions, and
+        # the multipliers of the three distinct matrices of the implicit step (u, v, every tracer)
+        self.diffusivity_fields = None
+        if self._cavd:
+            self.diffusivity_fields = {"kappa_c": ZFaceField(grid), "kappa_u": ZFaceField(grid)}
+            self._closure_struct = closure.c_struct()
+            if self._implicit:
+                self._ivd_scratch = torch.zeros((3, grid.Nz, grid.Ny, grid.Nx), dtype=torch.float64, device=nh.u.data.device)
         self.grid, self.architecture, self.clock = grid, grid.architecture, nh.clock
         self.free_surface = free_surface
         self.u, self.v, self.w = nh.u, nh.v, nh.w
@@ -289,6 +312,12 @@ class HydrostaticFreeSurfaceModel:
         self._fill_eta_halos()
         _lib.call("ocn_compute_w_from_continuity", g.cref, self.u.ptr, self.v.ptr, self.w.ptr, stream_ptr())
         update_hydrostatic_pressure(nh)
+        if self._cavd:  # compute_diffusivities!, then fill_halo_regions!(diffusivity_fields; only_local_halos = true)
+            d = self.diffusivity_fields
+            nh._refresh_term_pointers()
+            _lib.call("ocn_compute_convective_adjustment_diffusivities", g.cref, C.byref(nh._terms), C.byref(self._closure_struct),
+                      d["kappa_c"].ptr, d["kappa_u"].ptr, stream_ptr())
+            fill_halo_regions((d["kappa_c"], d["kappa_u"]), fill_boundary_normal_velocities=False)  # (a ZFaceField that is no velocity)
         self._tendencies_current = False
         if compute_tendencies:
             self.compute_tendencies()
@@ -316,14 +345,19 @@ class HydrostaticFreeSurfaceModel:
                       Gn[0].ptr, Gn[1].ptr, Gn[2].ptr, None, s)
             if not (self.split or self.implicit):
                 _lib.call("ocn_add_barotropic_pressure_gradient", g.cref, grav, self.eta.data_ptr(), Gn[0].ptr, Gn[1].ptr, s)  # - g ∇η
-        terms = nh._terms_noclosure if self._implicit else nh._terms
+        terms = nh._terms_noclosure if (self._implicit or self._cavd) else nh._terms
         _lib.call("ocn_add_momentum_terms", g.cref, C.byref(terms), self.u.ptr, self.v.ptr, self.w.ptr, Gn[0].ptr, Gn[1].ptr,
                   Gn[2].ptr, None, s)                                                               # - f x U - ∇pHY′ - ∂ⱼτᵢⱼ
         for n, c in enumerate(self.tracers):
-            kappa = 0.0 if (nh.closure is None or self._implicit) else nh.closure.kappa_of(self.tracer_names[n])
+            kappa = 0.0 if (nh.closure is None or self._implicit or self._cavd) else nh.closure.kappa_of(self.tracer_names[n])
             _lib.call("ocn_compute_tracer_tendency_terms", g.cref, C.byref(terms), kappa, None, self.u.ptr, self.v.ptr, self.w.ptr,
                       c.ptr, Gn[3 + n].ptr, None, s)
-        if self._implicit:  # the explicit part of the closure term (Gu, Gv and the tracers: w is diagnostic)
+        if self._cavd:  # the closure term: every vertical flux (explicit), or the fluxes through the two boundaries (vertically implicit)
+            nt, d = len(self.tracers), self.diffusivity_fields
+            _lib.call("ocn_add_vertical_diffusivity_fluxes", g.cref, d["kappa_u"].ptr, self.u.ptr, self.v.ptr, Gn[0].ptr, Gn[1].ptr, nt,
+                      _lib.ptr_array([d["kappa_c"].ptr] * max(nt, 1)), _lib.ptr_array([c.ptr for c in self.tracers] or [None]),
+                      _lib.ptr_array([G.ptr for G in Gn[3:]] or [None]), int(self._implicit), None, s)
+        elif self._implicit:  # the explicit part of the closure term (Gu, Gv and the tracers: w is diagnostic)
             nt = len(self.tracers)
             _lib.call("ocn_add_vertically_implicit_explicit_fluxes", g.cref, nh.closure.nu, self.u.ptr, self.v.ptr, self.w.ptr, Gn[0].ptr,
                       Gn[1].ptr, None, nt, (C.c_double * max(nt, 1))(*[nh.closure.kappa_of(n) for n in self.tracer_names]),
@@ -415,7 +449,13 @@ class HydrostaticFreeSurfaceModel:
         fields = [self.u, self.v] + list(self.tracers)
         _lib.call("ocn_ab2_step", g.cref, len(idx), _lib.ptr_array([f.ptr for f in fields]), _lib.ptr_array([Gn[q].ptr for q in idx]),
                   _lib.ptr_array([Gm[q].ptr for q in idx]), _lib.i32_array([f.loc for f in fields]), float(dt), float(chi), s)
-        if self._implicit:  # implicit_step! of u, v (ν) and every tracer (its own κ) with the full Δt
+        if self._cavd and self._implicit:  # implicit_step! with the κ fields of the last update_state! (the reference does not recompute them)
+            d, w = self.diffusivity_fields, self._ivd_scratch
+            kappas = [d["kappa_u"].ptr] * 2 + [d["kappa_c"].ptr] * len(self.tracers)
+            scratch = [w[0].data_ptr(), w[1].data_ptr()] + [w[2].data_ptr()] * len(self.tracers)
+            _lib.call("ocn_implicit_vertical_diffusion_step_fields", g.cref, len(fields), _lib.ptr_array([f.ptr for f in fields]),
+                      _lib.i32_array([f.loc for f in fields]), _lib.ptr_array(kappas), _lib.ptr_array(scratch), float(dt), s)
+        elif self._implicit:  # implicit_step! of u, v (ν) and every tracer (its own κ) with the full Δt
             kappa = [nh.closure.nu] * 2 + [nh.closure.kappa_of(n) for n in self.tracer_names]
             _lib.call("ocn_implicit_vertical_diffusion_step", g.cref, len(fields), _lib.ptr_array([f.ptr for f in fields]),
                       _lib.i32_array([f.loc for f in fields]), (C.c_double * len(fields))(*kappa), float(dt), s)

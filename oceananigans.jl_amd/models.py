@@ -28,7 +28,8 @@ from . import _lib
 import ctypes as C
 
 from .advection import WENO, UpwindBiased
-from .physics import (AnisotropicMinimumDissipation, BetaPlane, BuoyancyTracer, Centered, FieldBoundaryConditions, FPlane, ScalarDiffusivity,
+from .physics import (AnisotropicMinimumDissipation, BetaPlane, BuoyancyTracer, Centered, ConvectiveAdjustmentVerticalDiffusivity,
+                      FieldBoundaryConditions, FPlane, ScalarDiffusivity,
                       SeawaterBuoyancy, Smagorinsky, implicit_diffusion_solver, is_vertically_implicit, owns_eddy_fields)
 from .architectures import stream_ptr
 from .fields import CenterField, Field, XFaceField, YFaceField, ZFaceField, fill_halo_regions
@@ -90,7 +91,8 @@ class QuasiAdamsBashforth2TimeStepper(_TendencyStore):
 class NonhydrostaticModel:
     def __init__(self, grid, advection=None, tracers=(), timestepper="RungeKutta3", closure=None, buoyancy=None,
                  coriolis=None, forcing=None, stokes_drift=None, boundary_conditions=None,
-                 hydrostatic_pressure_anomaly="default", pressure_solver="default", math_mode=None, particles=None):
+                 hydrostatic_pressure_anomaly="default", pressure_solver="default", math_mode=None, particles=None,
+                 _hydrostatic_container=False):
         """math_mode: None keeps the grid's (default: the process default, ocn.set_math_mode); MATH_STRICT / MATH_FAST pin this
         model's arithmetic variant whatever other models of the process use (ocn_grid.math).
         particles: None or LagrangianParticles(...): moved to the architecture here and stepped with the pressure-corrected, halo-filled
@@ -119,7 +121,13 @@ class NonhydrostaticModel:
             raise NotImplementedError("only coriolis = FPlane(...) or BetaPlane(...) is implemented")
         if isinstance(coriolis, BetaPlane) and grid.topology[1] == Flat:
             raise NotImplementedError("BetaPlane needs a non-Flat y")
-        if closure is not None and not isinstance(closure, (ScalarDiffusivity, AnisotropicMinimumDissipation, Smagorinsky)):
+        # (_hydrostatic_container: the HydrostaticFreeSurfaceModel builds this class as the container of its fields; it owns the κ fields of
+        # a ConvectiveAdjustmentVerticalDiffusivity and every launch of that closure, the container only carries the object)
+        if isinstance(closure, ConvectiveAdjustmentVerticalDiffusivity):
+            if not _hydrostatic_container:
+                raise NotImplementedError("closure = ConvectiveAdjustmentVerticalDiffusivity on NonhydrostaticModel is not implemented (w would need "
+                                          "the Face-in-z rows of the field-valued implicit step); HydrostaticFreeSurfaceModel takes it (see DESIGN.md §5.2j)")
+        elif closure is not None and not isinstance(closure, (ScalarDiffusivity, AnisotropicMinimumDissipation, Smagorinsky)):
             raise NotImplementedError("only closure = ScalarDiffusivity(...), AnisotropicMinimumDissipation(...), Smagorinsky(...) or "
                                       "SmagorinskyLilly(...) is implemented")
         # closure = ScalarDiffusivity(VerticallyImplicitTimeDiscretization(), ...): a z-Bounded grid on one GPU, stepped by the Python host
@@ -273,7 +281,7 @@ class NonhydrostaticModel:
         # is 0; the explicit part of the closure term is added by its own kernel and the implicit part follows every substep (implicit_step)
         self._implicit = is_vertically_implicit(closure)
         self._terms_noclosure = None
-        if self._implicit:
+        if self._implicit or isinstance(closure, ConvectiveAdjustmentVerticalDiffusivity):  # (whose term has kernels of its own in both discretizations)
             self._terms_noclosure = _lib.CModelTerms()
             C.memmove(C.byref(self._terms_noclosure), C.byref(self._terms), C.sizeof(_lib.CModelTerms))
             self._terms_noclosure.closure, self._terms_noclosure.nu = 0, 0.0
@@ -352,7 +360,7 @@ class NonhydrostaticModel:
                 t.coriolis, t.f = 1, self.coriolis.f
         if owns_eddy_fields(self.closure):
             t.closure, t.nu_e = 2, self.diffusivity_fields["nu_e"].ptr
-        elif self.closure is not None:
+        elif isinstance(self.closure, ScalarDiffusivity):
             t.closure, t.nu = 1, self.closure.nu
         b = self.buoyancy
         if isinstance(b, BuoyancyTracer):

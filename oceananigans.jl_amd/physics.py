@@ -4,6 +4,8 @@
   FPlane(f=...) / FPlane(rotation_rate, latitude) src/Coriolis/f_plane.jl:8-42
   ScalarDiffusivity([VerticallyImplicitTimeDiscretization()], ν=..., κ=...)
                                                   src/TurbulenceClosures/turbulence_closure_implementations/scalar_diffusivity.jl
+  ConvectiveAdjustmentVerticalDiffusivity([time_discretization], convective_κz=..., background_κz=..., convective_νz=..., background_νz=...)
+                                                  .../turbulence_closure_implementations/convective_adjustment_vertical_diffusivity.jl
   Smagorinsky(coefficient=..., Pr=...), SmagorinskyLilly(C=..., Cb=..., Pr=...), LillyCoefficient(...)
                                                   .../turbulence_closure_implementations/Smagorinskys/{smagorinsky,lilly_coefficient}.jl
   BuoyancyTracer(), SeawaterBuoyancy(...), LinearEquationOfState(...)
@@ -191,6 +193,53 @@ class ScalarDiffusivity:
                 raise ValueError(f"no diffusivity κ given for tracer {name}")
             return float(self.kappa[name])
         return float(self.kappa)
+
+
+class ConvectiveAdjustmentVerticalDiffusivity:
+    """ConvectiveAdjustmentVerticalDiffusivity([time_discretization = VerticallyImplicitTimeDiscretization()];
+    convective_κz = 0, convective_νz = 0, background_κz = 0, background_νz = 0)
+    (convective_adjustment_vertical_diffusivity.jl:62-70): a VerticalFormulation closure whose tracer diffusivity κᶜ and viscosity κᵘ, fields
+    at (Center, Center, Face), take the convective value where ∂z b < 0 and the background value where ∂z b >= 0.  The time discretization
+    is the first positional argument or `time_discretization=` (an instance or "Explicit" / "VerticallyImplicit").  ASCII aliases:
+    convective_kappa_z, convective_nu_z, background_kappa_z, background_nu_z.  The coefficients are numbers (the reference's kernel puts
+    them straight into an ifelse); HydrostaticFreeSurfaceModel only."""
+    _NAMES = {"convective_κz": "convective_kappa_z", "convective_νz": "convective_nu_z", "background_κz": "background_kappa_z",
+              "background_νz": "background_nu_z"}
+
+    def __init__(self, *args, **kw):
+        if len(args) > 1:
+            raise TypeError("ConvectiveAdjustmentVerticalDiffusivity takes one positional argument, the time discretization")
+        if args:
+            if "time_discretization" in kw:
+                raise TypeError("time_discretization given twice")
+            kw["time_discretization"] = args[0]
+        self.time_discretization = as_time_discretization(kw.pop("time_discretization", VerticallyImplicitTimeDiscretization()))
+        self._given = {}  # the numbers as they were given: the reference's summary prints convective_κz=1 for an integer
+        for greek, ascii_name in self._NAMES.items():
+            if greek in kw and ascii_name in kw:
+                raise TypeError(f"{greek} given twice")
+            value = kw.pop(greek, kw.pop(ascii_name, 0.0))
+            if isinstance(value, (bool, str)) or callable(value) or not np.isscalar(value) or not np.isreal(value):
+                raise NotImplementedError(f"ConvectiveAdjustmentVerticalDiffusivity: {greek} must be a number (functions, arrays, fields and "
+                                          "per-tracer tuples are not implemented)")
+            setattr(self, ascii_name, float(value))
+            self._given[ascii_name] = value
+        if kw:
+            raise TypeError(f"unexpected keyword arguments {sorted(kw)}")
+
+    convective_κz = property(lambda self: self.convective_kappa_z)
+    convective_νz = property(lambda self: self.convective_nu_z)
+    background_κz = property(lambda self: self.background_kappa_z)
+    background_νz = property(lambda self: self.background_nu_z)
+
+    def c_struct(self):
+        """struct ocn_convective_adjustment"""
+        return _lib.CConvectiveAdjustment(self.convective_kappa_z, self.convective_nu_z, self.background_kappa_z, self.background_nu_z)
+
+    def __repr__(self):  # Base.summary (convective_adjustment_vertical_diffusivity.jl:129-133)
+        v = self._given
+        return (f"ConvectiveAdjustmentVerticalDiffusivity{{{type(self.time_discretization).__name__}}}(background_κz={v['background_kappa_z']} "
+                f"convective_κz={v['convective_kappa_z']} background_νz={v['background_nu_z']} convective_νz={v['convective_nu_z']})")
 
 
 class AnisotropicMinimumDissipation:
