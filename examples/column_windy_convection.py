@@ -1,0 +1,77 @@
+#!/usr/bin/env python3
+"""A wind- and cooling-forced column, after the reference's validation/vertical_mixing_closures/column_windy_convection.jl: linearly
+stratified buoyancy b = N² z under a destabilising surface buoyancy flux Jᵇ and a wind stress τˣ on an f-plane, mixed by
+RiBasedVerticalDiffusivity (vertically implicit: Δt is far above Δz² / 2κ).  The reference's column is (Flat, Flat, Bounded); here it is a
+small horizontally periodic box of identical columns, since this package's closure needs a non-Flat x and y.  The mixed layer deepens by
+convective adjustment (κᶜᵃ where N² < 0), by entrainment at its base (Cᵉⁿ Jᵇ / N² under a convecting face) and by shear mixing where
+Ri = N² / S² is small (κ₀, ν₀ times the taper); the script prints its depth -- the shallowest face whose N² is still at least half the
+initial one -- next to the non-penetrative estimate √(2 Jᵇ t / N²).
+
+    python examples/column_windy_convection.py [--closure ri|cavd] [--nz 128] [--hours 24] [--dt 60] [--taper tanh|exp|linear] [--filter]"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+import oceananigans_jl_amd as ocn
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--closure", choices=("ri", "cavd"), default="ri")
+ap.add_argument("--nz", type=int, default=128)
+ap.add_argument("--hours", type=float, default=24.0)
+ap.add_argument("--dt", type=float, default=60.0)
+ap.add_argument("--taper", choices=("tanh", "exp", "linear"), default="tanh")
+ap.add_argument("--filter", action="store_true", help="horizontal_Ri_filter = FivePointHorizontalFilter()")
+a = ap.parse_args()
+
+Lz = 256.0        # extent of the vertical domain [m] (Δz = 2 m at the default Nz)
+f0 = 1e-4         # Coriolis parameter [s⁻¹]
+N2 = 1e-5         # buoyancy gradient [s⁻²]
+Jb = 1e-7         # surface buoyancy flux [m² s⁻³], positive: destabilising
+tau_x = -1e-4     # surface kinematic momentum flux [m² s⁻²]
+n = 4             # columns per side
+grid = ocn.RectilinearGrid(ocn.GPU(), size=(n, n, a.nz), x=(0, 100.0), y=(0, 100.0), z=(-Lz, 0), topology=("Periodic", "Periodic", "Bounded"))
+if a.closure == "ri":
+    taper = {"tanh": ocn.HyperbolicTangentRiDependentTapering, "exp": ocn.ExponentialRiDependentTapering,
+             "linear": ocn.PiecewiseLinearRiDependentTapering}[a.taper]()
+    closure = ocn.RiBasedVerticalDiffusivity(Ri_dependent_tapering=taper, horizontal_Ri_filter=ocn.FivePointHorizontalFilter() if a.filter else None)
+else:
+    closure = ocn.ConvectiveAdjustmentVerticalDiffusivity(convective_κz=1.0, background_κz=1e-5, convective_νz=0.1, background_νz=1e-4)
+bcs = {"b": ocn.FieldBoundaryConditions(top=ocn.FluxBoundaryCondition(Jb)), "u": ocn.FieldBoundaryConditions(top=ocn.FluxBoundaryCondition(tau_x))}
+model = ocn.HydrostaticFreeSurfaceModel(grid, tracers=("b",), buoyancy=ocn.BuoyancyTracer(), coriolis=ocn.FPlane(f=f0), closure=closure,
+                                        boundary_conditions=bcs)
+model.set(b=lambda x, y, z: N2 * z + 0 * x + 0 * y)
+print(closure)
+dz = Lz / a.nz
+print(f"Δz = {dz:g} m, Δt = {a.dt:g} s, Jᵇ = {Jb:g} m² s⁻³, τˣ = {tau_x:g} m² s⁻², N² = {N2:g} s⁻²")
+z_faces = np.asarray(grid.nodes_1d(2, True))[:a.nz + 1]
+
+
+def mixed_layer_depth():
+    """the depth of the shallowest interior face whose N² is at least half the initial stratification (column 1, 1)"""
+    b = model.field("b").interior()[0, 0, :]
+    stratified = (b[1:] - b[:-1]) / dz >= 0.5 * N2          # faces 2..Nz
+    k = np.nonzero(stratified)[0]
+    return float(-z_faces[1 + k.max()]) if k.size else Lz
+
+
+t0, every = time.perf_counter(), max(1, int(round(2 * 3600 / a.dt)))
+depths = []
+while model.clock.time < a.hours * 3600:
+    if model.clock.iteration % every == 0:
+        h = mixed_layer_depth()
+        depths.append(h)
+        kc = model.diffusivity_fields["kappa_c"].interior()[0, 0, :a.nz]
+        print("Iter: %5d, t = %5.1f h, wall %5.1f s | mixed-layer depth %6.1f m, non-penetrative estimate %6.1f m, max(κc) %.3g, max(u) %.3g" % (
+            model.clock.iteration, model.clock.time / 3600, time.perf_counter() - t0, h, np.sqrt(2 * Jb * model.clock.time / N2), kc.max(),
+            float(np.abs(model.u.interior()).max())), flush=True)
+    model.time_step(a.dt)
+ocn.sync_device()
+h, estimate = mixed_layer_depth(), np.sqrt(2 * Jb * model.clock.time / N2)
+print(f"after {model.clock.time / 3600:.1f} h: mixed-layer depth {h:.1f} m, non-penetrative estimate {estimate:.1f} m")
+b = model.field("b").interior()
+print(f"largest difference between the columns: {np.abs(b - b[:1, :1]).max():.3g}")
+assert np.isfinite(b).all() and h > depths[0]

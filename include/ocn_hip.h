@@ -464,6 +464,43 @@ int ocn_add_vertical_diffusivity_fluxes(const ocn_grid *grid, const double *kapp
  * scratch array, the same field twice. */
 int ocn_implicit_vertical_diffusion_step_fields(const ocn_grid *grid, int32_t n, double *const *fields, const int32_t *locs,
                                                 const double *const *kappa, double *const *scratch, double dt, void *stream);
+/* ---- RiBasedVerticalDiffusivity (csrc/ri_based_diffusivity.hip, csrc/ocn_taper.h; turbulence_closure_implementations/
+ * ri_based_vertical_diffusivity.jl): κᶜ, κᵘ and Ri fields at (Center, Center, Face); their term and implicit step are the two entry points
+ * above.  z Bounded, x and y Periodic or Bounded (not Flat), halos >= 1, one GPU; strict math whatever the math mode. */
+#define OCN_RI_TAPER_LINEAR 0 /* PiecewiseLinearRiDependentTapering: 1 - min(1, max(0, (Ri - Ri₀) / Riᵟ)) */
+#define OCN_RI_TAPER_EXP 1    /* ExponentialRiDependentTapering:     exp(-max(0, (Ri - Ri₀) / Riᵟ)) */
+#define OCN_RI_TAPER_TANH 2   /* HyperbolicTangentRiDependentTapering: (1 - tanh((Ri - Ri₀) / Riᵟ)) / 2 */
+#define OCN_RI_FILTER_NONE 0
+#define OCN_RI_FILTER_FIVE_POINT 1 /* FivePointHorizontalFilter: ℑxyᶜᶜᵃ(ℑxyᶠᶠᵃ Ri), a 3 x 3 stencil */
+typedef struct ocn_ri_based {
+    double nu0, kappa0, kappa_ca, C_en, C_av, Ri0, Ri_delta, minimum_entrainment_buoyancy_gradient; /* finite */
+    double maximum_diffusivity, maximum_viscosity;                                                /* may be +inf, no NaN */
+    int32_t tapering;          /* OCN_RI_TAPER_* */
+    int32_t horizontal_filter; /* OCN_RI_FILTER_* */
+} ocn_ri_based;
+/* compute_ri_number! (:245-267) over i = 1..Nx, j = 1..Ny, k = 1..Nz: Ri = N² <= 0 ? 0 : N² / S² with
+ * S² = ℑxᶜᵃᵃ((∂zᶠᶜᶠ u)²) + ℑyᵃᶜᵃ((∂zᶜᶠᶠ v)²) and N² = ∂z_b (+inf where the water is at rest and stable).  Face Nz+1 and the halos of Ri are NOT
+ * written.  terms: buoyancy kind, g, alpha, beta, T, S are read.  u, v, T, S are read at k = 0 (the bottom halo), u at i + 1, v at j + 1.
+ * OCN_ERR_INVALID_ARGUMENT: a z that is not Bounded, a Flat x or y, a buoyancy kind whose tracer pointer is NULL. */
+int ocn_compute_ri_number(const ocn_grid *grid, const ocn_model_terms *terms, const double *u, const double *v, double *Ri, void *stream);
+/* compute_ri_based_diffusivities! (:277-341) over the same cells, from an Ri whose x / y halos the caller has filled (read only with
+ * OCN_RI_FILTER_FIVE_POINT): κ <- (C_av κ + κ⁺) / (1 + C_av) IN PLACE on kappa_c and kappa_u, with κᶜ⁺ = min((κᶜᵃ where N² < 0) + (C_en Jᵇ / N²
+ * where (N² > minimum_entrainment_buoyancy_gradient) & (N²(k+1) < 0) & (Jᵇ > 0)) + kappa0 τ(Ri), maximum_diffusivity), κᵘ⁺ = min(nu0 τ(Ri),
+ * maximum_viscosity), both 0 at face 1 (the periphery).  Jᵇ, the top buoyancy flux, is g (alpha J_T - beta J_S) or J_b: top_T / top_S are the
+ * top conditions of the T (or b) and S tracers; NULL or OCN_BC_DEFAULT: no flux, 0; OCN_BC_FLUX: evaluated as ocn_apply_flux_bcs does (a
+ * `values` array must be current); Value / Gradient: OCN_ERR_INVALID_ARGUMENT.  T / S are read at k = 0 and k = Nz+1.  Face Nz+1 and the
+ * halos of kappa_c / kappa_u are not written.  Also OCN_ERR_INVALID_ARGUMENT: aliased Ri / kappa_c / kappa_u, an unknown tapering or
+ * filter code, a coefficient that is not finite, a maximum that is a NaN. */
+int ocn_compute_ri_based_diffusivities(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_ri_based *closure, const ocn_bc *top_T,
+                                       const ocn_bc *top_S, const double *Ri, double *kappa_c, double *kappa_u, void *stream);
+/* Both of the above in ONE launch for closure->horizontal_filter == OCN_RI_FILTER_NONE (anything else: OCN_ERR_INVALID_ARGUMENT): Ri is
+ * computed, stored and used where it is.  Bit-identical to the two calls. */
+int ocn_compute_ri_based_diffusivities_fused(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_ri_based *closure,
+                                             const ocn_bc *top_T, const ocn_bc *top_S, const double *u, const double *v, double *Ri,
+                                             double *kappa_c, double *kappa_u, void *stream);
+/* The tapering functions on the HOST (no device is touched): out[q] = τ(x[q]; x0, delta), q = 0..n-1, kind = OCN_RI_TAPER_*, by the inline
+ * functions the kernels call (csrc/ocn_taper.h: IEEE +, -, *, / and powers of two only, no math library) -- the same bits as on the device. */
+int ocn_ri_taper_host(int32_t kind, int64_t n, const double *x, double x0, double delta, double *out);
 /* cache_previous_tendencies! (src/TimeSteppers/store_tendencies.jl:6-22) */
 int ocn_cache_previous_tendencies(const ocn_grid *grid, int32_t n, double *const *Gm, const double *const *Gn,
                                   const int32_t *locs, void *stream);

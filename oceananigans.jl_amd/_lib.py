@@ -86,6 +86,12 @@ class CConvectiveAdjustment(C.Structure):
                 ("background_nu_z", C.c_double)]
 
 
+class CRiBased(C.Structure):
+    """struct ocn_ri_based"""
+    _fields_ = [(n, C.c_double) for n in ("nu0", "kappa0", "kappa_ca", "C_en", "C_av", "Ri0", "Ri_delta", "minimum_entrainment_buoyancy_gradient",
+                                           "maximum_diffusivity", "maximum_viscosity")] + [("tapering", C.c_int32), ("horizontal_filter", C.c_int32)]
+
+
 class CSmagorinsky(C.Structure):
     """struct ocn_smagorinsky"""
     _fields_ = [("C", C.c_double), ("Cb", C.c_double), ("lilly", C.c_int32), ("n_tracers", C.c_int32), ("Pr", C.c_double * MODEL_MAX_TRACERS)]
@@ -126,6 +132,8 @@ SCHED_STRIPS, SCHED_PLANE_EAST, SCHED_PLANE_WEST, SCHED_ALL_TO_ALL, SCHED_ALL_GA
 ADVECTION_WENO5, ADVECTION_CENTERED2, ADVECTION_UPWIND5 = 0, 1, 2
 BUOYANCY_NONE, BUOYANCY_TRACER, BUOYANCY_SEAWATER_TS, BUOYANCY_SEAWATER_T, BUOYANCY_SEAWATER_S = 0, 1, 2, 3, 4
 BC_DEFAULT, BC_FLUX, BC_VALUE, BC_GRADIENT, BC_OPEN = 0, 1, 2, 3, 4
+RI_TAPER_LINEAR, RI_TAPER_EXP, RI_TAPER_TANH = 0, 1, 2
+RI_FILTER_NONE, RI_FILTER_FIVE_POINT = 0, 1
 
 _lib = None
 
@@ -191,6 +199,12 @@ _SIGS = {
     "ocn_add_vertical_diffusivity_fluxes": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _vp, _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                             _i32, C.POINTER(_i32), _vp],
     "ocn_implicit_vertical_diffusion_step_fields": [C.POINTER(CGrid), _i32, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_vp), C.POINTER(_vp), _dbl, _vp],
+    "ocn_compute_ri_number": [C.POINTER(CGrid), C.POINTER(CModelTerms), _vp, _vp, _vp, _vp],
+    "ocn_compute_ri_based_diffusivities": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CRiBased), C.POINTER(CBc), C.POINTER(CBc), _vp, _vp,
+                                           _vp, _vp],
+    "ocn_compute_ri_based_diffusivities_fused": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CRiBased), C.POINTER(CBc), C.POINTER(CBc), _vp,
+                                                 _vp, _vp, _vp, _vp, _vp],
+    "ocn_ri_taper_host": [_i32, C.c_int64, _vp, _dbl, _dbl, _vp],
     "ocn_cache_previous_tendencies": [C.POINTER(CGrid), _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), _vp],
     "ocn_pressure_correct_velocities": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _dbl, _vp],
     "ocn_divergence": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _vp],

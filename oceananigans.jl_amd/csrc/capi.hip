@@ -1434,6 +1434,93 @@ int ocn_implicit_vertical_diffusion_step_fields(const ocn_grid *grid, int32_t n,
     return launch_ivd_implicit_step_fields(grid, n, fields, locs, kappa, scratch, dt, as_stream(stream));
 }
 
+// the three entry points of ri_based_diffusivity.hip
+static int validate_ri_buoyancy(const ocn_model_terms *terms, const char *who)
+{
+    OCN_REQUIRE(terms, "%s: null terms", who);
+    const int b = terms->buoyancy;
+    OCN_REQUIRE(b >= OCN_BUOYANCY_NONE && b <= OCN_BUOYANCY_SEAWATER_S, "%s: unknown buoyancy %d", who, b);
+    if (b == OCN_BUOYANCY_TRACER || b == OCN_BUOYANCY_SEAWATER_TS || b == OCN_BUOYANCY_SEAWATER_T)
+        OCN_REQUIRE(terms->T != nullptr, "%s: the T (or b) tracer is NULL", who);
+    if (b == OCN_BUOYANCY_SEAWATER_TS || b == OCN_BUOYANCY_SEAWATER_S) OCN_REQUIRE(terms->S != nullptr, "%s: the S tracer is NULL", who);
+    return OCN_SUCCESS;
+}
+
+static int validate_ri_closure(const ocn_grid *grid, const ocn_ri_based *c, const ocn_bc *top_T, const ocn_bc *top_S, const char *who)
+{
+    OCN_REQUIRE(c, "%s: null closure", who);
+    OCN_REQUIRE(c->tapering >= OCN_RI_TAPER_LINEAR && c->tapering <= OCN_RI_TAPER_TANH, "%s: unknown tapering code %d", who, c->tapering);
+    OCN_REQUIRE(c->horizontal_filter == OCN_RI_FILTER_NONE || c->horizontal_filter == OCN_RI_FILTER_FIVE_POINT,
+                "%s: unknown horizontal filter code %d", who, c->horizontal_filter);
+    OCN_REQUIRE(std::isfinite(c->nu0) && std::isfinite(c->kappa0) && std::isfinite(c->kappa_ca) && std::isfinite(c->C_en) &&
+                    std::isfinite(c->C_av) && std::isfinite(c->Ri0) && std::isfinite(c->Ri_delta) &&
+                    std::isfinite(c->minimum_entrainment_buoyancy_gradient),
+                "%s: the coefficients must be finite (only the two maxima may be +inf)", who);
+    OCN_REQUIRE(!std::isnan(c->maximum_diffusivity) && !std::isnan(c->maximum_viscosity), "%s: a maximum is a NaN", who);
+    const ocn_bc *tops[2] = {top_T, top_S};
+    for (int q = 0; q < 2; ++q) {
+        if (!tops[q]) continue;
+        OCN_REQUIRE(tops[q]->kind == OCN_BC_DEFAULT || tops[q]->kind == OCN_BC_FLUX,
+                    "%s: the top condition of the %s tracer has kind %d: only a Flux (or the default, no flux) is a buoyancy flux", who,
+                    q ? "S" : "T (or b)", tops[q]->kind);
+        OCN_REQUIRE(!tops[q]->values || grid->tx == OCN_PERIODIC || grid->tx == OCN_BOUNDED,
+                    "%s: array boundary conditions are not supported on a partitioned grid", who);
+    }
+    return OCN_SUCCESS;
+}
+
+int ocn_compute_ri_number(const ocn_grid *grid, const ocn_model_terms *terms, const double *u, const double *v, double *Ri, void *stream)
+{
+    const char *who = "ocn_compute_ri_number";
+    int st = validate_vertical_diffusivity(grid, who);
+    if (st != OCN_SUCCESS) return st;
+    st = validate_ri_buoyancy(terms, who);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(u && v && Ri, "%s: null field pointer", who);
+    return launch_ri_based(0, grid, terms, nullptr, nullptr, nullptr, u, v, nullptr, Ri, nullptr, nullptr, as_stream(stream));
+}
+
+int ocn_compute_ri_based_diffusivities(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_ri_based *closure, const ocn_bc *top_T,
+                                       const ocn_bc *top_S, const double *Ri, double *kappa_c, double *kappa_u, void *stream)
+{
+    const char *who = "ocn_compute_ri_based_diffusivities";
+    int st = validate_vertical_diffusivity(grid, who);
+    if (st != OCN_SUCCESS) return st;
+    st = validate_ri_buoyancy(terms, who);
+    if (st != OCN_SUCCESS) return st;
+    st = validate_ri_closure(grid, closure, top_T, top_S, who);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(Ri && kappa_c && kappa_u, "%s: null field pointer", who);
+    OCN_REQUIRE(kappa_c != kappa_u && Ri != kappa_c && Ri != kappa_u, "%s: Ri, kappa_c and kappa_u must be three different arrays", who);
+    return launch_ri_based(1, grid, terms, closure, top_T, top_S, nullptr, nullptr, Ri, nullptr, kappa_c, kappa_u, as_stream(stream));
+}
+
+int ocn_compute_ri_based_diffusivities_fused(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_ri_based *closure,
+                                             const ocn_bc *top_T, const ocn_bc *top_S, const double *u, const double *v, double *Ri,
+                                             double *kappa_c, double *kappa_u, void *stream)
+{
+    const char *who = "ocn_compute_ri_based_diffusivities_fused";
+    int st = validate_vertical_diffusivity(grid, who);
+    if (st != OCN_SUCCESS) return st;
+    st = validate_ri_buoyancy(terms, who);
+    if (st != OCN_SUCCESS) return st;
+    st = validate_ri_closure(grid, closure, top_T, top_S, who);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(closure->horizontal_filter == OCN_RI_FILTER_NONE,
+                "%s: the horizontal filter reads the neighbours' Ri: ocn_compute_ri_number, a halo fill, ocn_compute_ri_based_diffusivities", who);
+    OCN_REQUIRE(u && v && Ri && kappa_c && kappa_u, "%s: null field pointer", who);
+    OCN_REQUIRE(kappa_c != kappa_u && Ri != kappa_c && Ri != kappa_u, "%s: Ri, kappa_c and kappa_u must be three different arrays", who);
+    return launch_ri_based(2, grid, terms, closure, top_T, top_S, u, v, nullptr, Ri, kappa_c, kappa_u, as_stream(stream));
+}
+
+int ocn_ri_taper_host(int32_t kind, int64_t n, const double *x, double x0, double delta, double *out)
+{
+    OCN_REQUIRE(kind >= OCN_RI_TAPER_LINEAR && kind <= OCN_RI_TAPER_TANH, "ocn_ri_taper_host: unknown tapering code %d", kind);
+    OCN_REQUIRE(n >= 0 && (n == 0 || (x && out)), "ocn_ri_taper_host: null array or negative length");
+    ri_taper_host(kind, n, x, x0, delta, out);
+    return OCN_SUCCESS;
+}
+
 int ocn_cache_previous_tendencies(const ocn_grid *grid, int32_t n, double *const *Gm, const double *const *Gn,
                                   const int32_t *locs, void *stream)
 {

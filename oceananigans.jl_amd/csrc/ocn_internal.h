@@ -91,6 +91,11 @@ int launch_vertical_diffusivity_fluxes(const ocn_grid *grid, const double *kappa
                                        int boundary_only, const int32_t *range, hipStream_t stream);
 int launch_ivd_implicit_step_fields(const ocn_grid *grid, int n, double *const *fields, const int32_t *locs, const double *const *kappa,
                                     double *const *scratch, double dt, hipStream_t stream);
+// ri_based_diffusivity.hip: RiBasedVerticalDiffusivity.  mode 0: Ri alone; 1: the diffusivities from a stored Ri; 2: both in one launch
+int launch_ri_based(int mode, const ocn_grid *grid, const ocn_model_terms *terms, const ocn_ri_based *closure, const ocn_bc *top_T,
+                    const ocn_bc *top_S, const double *u, const double *v, const double *ri_in, double *ri_out, double *kappa_c,
+                    double *kappa_u, hipStream_t stream);
+void ri_taper_host(int kind, long long n, const double *x, double x0, double delta, double *out);
 int launch_profile_marker(hipStream_t stream);
 int wait_stream(hipStream_t stream, double seconds, const char *who);
 int launch_hydrostatic_pressure(const ocn_grid *grid, const TermsDev &t, double *pHY, hipStream_t stream, const int32_t *irange = nullptr);

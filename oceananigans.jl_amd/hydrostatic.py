@@ -10,8 +10,9 @@ The horizontal momentum and tracer tendencies are the terms of the Nonhydrostati
 there is no pressure solve.  momentum_advection = VectorInvariant() (the reference's default: enstrophy-conserving vorticity flux,
 energy-conserving vertical advection and kinetic-energy gradient) or a flux-form scheme.  closure = ScalarDiffusivity(...), explicit or
 with VerticallyImplicitTimeDiscretization() (QAB2, fused = False: implicit_step! of u, v and the tracers after their ab2 step), or
-ConvectiveAdjustmentVerticalDiffusivity(...) (QAB2, fused = False, one GPU: κᶜ, κᵘ fields computed in update_state!, their term and the
-field-valued implicit step in csrc/vertical_diffusivity.hip).  NOT in this slice (each raises):
+ConvectiveAdjustmentVerticalDiffusivity(...) / RiBasedVerticalDiffusivity(...) (QAB2, fused = False, one GPU: κᶜ, κᵘ fields computed in
+update_state! -- csrc/vertical_diffusivity.hip, csrc/ri_based_diffusivity.hip --, their term and the field-valued implicit step in
+csrc/vertical_diffusivity.hip).  NOT in this slice (each raises):
 SplitExplicitFreeSurface / ImplicitFreeSurface, upwinding / WENO vector-invariant variants, z-star coordinates, eddy-viscosity closures,
 closure tuples,
 a tracer advection scheme different from the momentum one, Distributed architectures.
@@ -25,7 +26,8 @@ from .architectures import stream_ptr
 from .fields import ZFaceField, fill_halo_regions
 from .grids import Bounded, Periodic
 from .models import NonhydrostaticModel, compute_boundary_tendency_contributions, update_hydrostatic_pressure
-from .physics import Centered, ConvectiveAdjustmentVerticalDiffusivity, is_vertically_implicit, owns_eddy_fields
+from .physics import (BuoyancyTracer, Centered, RiBasedVerticalDiffusivity, SeawaterBuoyancy, has_diffusivity_fields, is_vertically_implicit,
+                      owns_eddy_fields)
 
 g_Earth = 9.80665  # Oceananigans.BuoyancyFormulations.g_Earth
 
@@ -206,16 +208,29 @@ class HydrostaticFreeSurfaceModel:
             raise NotImplementedError("eddy-viscosity closures are not part of this slice")
         if isinstance(closure, (tuple, list)):
             raise NotImplementedError("closure tuples are not implemented: give one closure")
-        # closure = ConvectiveAdjustmentVerticalDiffusivity(...): the reference's launch sequence with QAB2 on one GPU, in both discretizations
-        self._cavd = isinstance(closure, ConvectiveAdjustmentVerticalDiffusivity)
-        if self._cavd:
+        # closure = ConvectiveAdjustmentVerticalDiffusivity(...) or RiBasedVerticalDiffusivity(...), the closures with κᶜ, κᵘ fields: the
+        # reference's launch sequence with QAB2 on one GPU, in both discretizations
+        self._kfields = has_diffusivity_fields(closure)
+        self._ri = isinstance(closure, RiBasedVerticalDiffusivity)
+        if self._kfields:
+            name = type(closure).__name__
             if fused:
-                raise NotImplementedError("ConvectiveAdjustmentVerticalDiffusivity runs the reference's launch sequence (fused = False)")
+                raise NotImplementedError(f"{name} runs the reference's launch sequence (fused = False)")
             if self.split_rk3:
-                raise NotImplementedError("ConvectiveAdjustmentVerticalDiffusivity with SplitRungeKutta3 is not implemented")
+                raise NotImplementedError(f"{name} with SplitRungeKutta3 is not implemented")
             if self._dist is not None or hasattr(arch, "partition"):
-                raise NotImplementedError("ConvectiveAdjustmentVerticalDiffusivity on a slab-partitioned (Distributed) grid is not implemented")
+                raise NotImplementedError(f"{name} on a slab-partitioned (Distributed) grid is not implemented")
             fused = False
+        if self._ri:
+            # top_buoyancy_flux reads the top condition of the buoyancy tracers as a flux; the reference would read the number of a Value or
+            # Gradient condition as one too, which is not reproduced
+            carriers = ("b", None) if isinstance(buoyancy, BuoyancyTracer) else (("T", "S") if isinstance(buoyancy, SeawaterBuoyancy) else (None, None))
+            self._ri_carriers = carriers  # the tracers whose top conditions make up the buoyancy flux: (T or b, S)
+            for tracer in filter(None, carriers):
+                top = getattr((boundary_conditions or {}).get(tracer), "sides", {}).get("top")
+                if top is not None and top.kind != _lib.BC_FLUX:
+                    raise NotImplementedError(f"RiBasedVerticalDiffusivity: the top boundary condition of {tracer} must be a "
+                                              "FluxBoundaryCondition (or the default): it is the surface buoyancy flux of the entrainment term")
         # closure = ScalarDiffusivity(VerticallyImplicitTimeDiscretization(), ...): the reference's launch sequence with QAB2 on one GPU
         # (hydrostatic_free_surface_ab2_step.jl:39-108: implicit_step! of u, v and every tracer after its ab2 step; w is diagnostic)
         self._implicit = is_vertically_implicit(closure)
@@ -234,11 +249,14 @@ class HydrostaticFreeSurfaceModel:
                                        pressure_solver=None, math_mode=math_mode, _hydrostatic_container=True)
         nh = self._nh
         grid = nh.grid  # (halo-inflated / math-mode-pinned by the container model)
-        # build_diffusivity_fields (convective_adjustment_vertical_diffusivity.jl:85): κᶜ and κᵘ, ZFaceFields with default conditions, and
-        # the multipliers of the three distinct matrices of the implicit step (u, v, every tracer)
+        # build_diffusivity_fields (convective_adjustment_vertical_diffusivity.jl:85, ri_based_vertical_diffusivity.jl:186-191): κᶜ and κᵘ
+        # (and Ri), ZFaceFields with default conditions, and the multipliers of the three distinct matrices of the implicit step (u, v,
+        # every tracer)
         self.diffusivity_fields = None
-        if self._cavd:
+        if self._kfields:
             self.diffusivity_fields = {"kappa_c": ZFaceField(grid), "kappa_u": ZFaceField(grid)}
+            if self._ri:
+                self.diffusivity_fields["Ri"] = ZFaceField(grid)
             self._closure_struct = closure.c_struct()
             if self._implicit:
                 self._ivd_scratch = torch.zeros((3, grid.Nz, grid.Ny, grid.Nx), dtype=torch.float64, device=nh.u.data.device)
@@ -312,15 +330,42 @@ class HydrostaticFreeSurfaceModel:
         self._fill_eta_halos()
         _lib.call("ocn_compute_w_from_continuity", g.cref, self.u.ptr, self.v.ptr, self.w.ptr, stream_ptr())
         update_hydrostatic_pressure(nh)
-        if self._cavd:  # compute_diffusivities!, then fill_halo_regions!(diffusivity_fields; only_local_halos = true)
+        if self._kfields:  # compute_diffusivities!, then fill_halo_regions!(diffusivity_fields; only_local_halos = true)
             d = self.diffusivity_fields
             nh._refresh_term_pointers()
-            _lib.call("ocn_compute_convective_adjustment_diffusivities", g.cref, C.byref(nh._terms), C.byref(self._closure_struct),
-                      d["kappa_c"].ptr, d["kappa_u"].ptr, stream_ptr())
-            fill_halo_regions((d["kappa_c"], d["kappa_u"]), fill_boundary_normal_velocities=False)  # (a ZFaceField that is no velocity)
+            if self._ri:
+                self._compute_ri_based_diffusivities()
+            else:
+                _lib.call("ocn_compute_convective_adjustment_diffusivities", g.cref, C.byref(nh._terms), C.byref(self._closure_struct),
+                          d["kappa_c"].ptr, d["kappa_u"].ptr, stream_ptr())
+            fill_halo_regions(tuple(d.values()), fill_boundary_normal_velocities=False)  # (ZFaceFields that are no velocities)
         self._tendencies_current = False
         if compute_tendencies:
             self.compute_tendencies()
+
+    def _top_condition(self, name):
+        """reference to the struct ocn_bc of the top condition of a tracer, or NULL (no such tracer, default conditions: no flux)"""
+        if name is not None and name in self.tracer_names:
+            b = getattr(self.field(name), "boundary_conditions", None)
+            if b is not None and b.sides["top"] is not None:
+                return C.pointer(b.c_struct(self.grid).top)
+        return C.POINTER(_lib.CBc)()
+
+    def _compute_ri_based_diffusivities(self):
+        """compute_diffusivities!(diffusivities, ::RiBasedVerticalDiffusivity, model) (ri_based_vertical_diffusivity.jl:193-229) after
+        update_boundary_conditions, so the `values` arrays of function-valued flux conditions are current: compute_ri_number!, the halo
+        fill of Ri, compute_ri_based_diffusivities! -- or, without a horizontal filter, where Ri is only read at its own cell, all of it
+        in one launch (bit-identical).  Every call advances the time average of κᶜ and κᵘ."""
+        nh, g, d, s = self._nh, self.grid, self.diffusivity_fields, stream_ptr()
+        terms, cl = C.byref(nh._terms), C.byref(self._closure_struct)
+        tops = tuple(self._top_condition(name) for name in self._ri_carriers)
+        if nh.closure.horizontal_Ri_filter is None:
+            _lib.call("ocn_compute_ri_based_diffusivities_fused", g.cref, terms, cl, *tops, self.u.ptr, self.v.ptr, d["Ri"].ptr,
+                      d["kappa_c"].ptr, d["kappa_u"].ptr, s)
+        else:
+            _lib.call("ocn_compute_ri_number", g.cref, terms, self.u.ptr, self.v.ptr, d["Ri"].ptr, s)
+            fill_halo_regions((d["Ri"],), fill_boundary_normal_velocities=False)
+            _lib.call("ocn_compute_ri_based_diffusivities", g.cref, terms, cl, *tops, d["Ri"].ptr, d["kappa_c"].ptr, d["kappa_u"].ptr, s)
 
     # ---- compute_tendencies! (hydrostatic_free_surface_tendency_kernel_functions.jl:45-52, 86-93, 125-131) -----------------------
     def flush_tendencies(self):
@@ -345,14 +390,14 @@ class HydrostaticFreeSurfaceModel:
                       Gn[0].ptr, Gn[1].ptr, Gn[2].ptr, None, s)
             if not (self.split or self.implicit):
                 _lib.call("ocn_add_barotropic_pressure_gradient", g.cref, grav, self.eta.data_ptr(), Gn[0].ptr, Gn[1].ptr, s)  # - g ∇η
-        terms = nh._terms_noclosure if (self._implicit or self._cavd) else nh._terms
+        terms = nh._terms_noclosure if (self._implicit or self._kfields) else nh._terms
         _lib.call("ocn_add_momentum_terms", g.cref, C.byref(terms), self.u.ptr, self.v.ptr, self.w.ptr, Gn[0].ptr, Gn[1].ptr,
                   Gn[2].ptr, None, s)                                                               # - f x U - ∇pHY′ - ∂ⱼτᵢⱼ
         for n, c in enumerate(self.tracers):
-            kappa = 0.0 if (nh.closure is None or self._implicit or self._cavd) else nh.closure.kappa_of(self.tracer_names[n])
+            kappa = 0.0 if (nh.closure is None or self._implicit or self._kfields) else nh.closure.kappa_of(self.tracer_names[n])
             _lib.call("ocn_compute_tracer_tendency_terms", g.cref, C.byref(terms), kappa, None, self.u.ptr, self.v.ptr, self.w.ptr,
                       c.ptr, Gn[3 + n].ptr, None, s)
-        if self._cavd:  # the closure term: every vertical flux (explicit), or the fluxes through the two boundaries (vertically implicit)
+        if self._kfields:  # the closure term: every vertical flux (explicit), or the fluxes through the two boundaries (vertically implicit)
             nt, d = len(self.tracers), self.diffusivity_fields
             _lib.call("ocn_add_vertical_diffusivity_fluxes", g.cref, d["kappa_u"].ptr, self.u.ptr, self.v.ptr, Gn[0].ptr, Gn[1].ptr, nt,
                       _lib.ptr_array([d["kappa_c"].ptr] * max(nt, 1)), _lib.ptr_array([c.ptr for c in self.tracers] or [None]),
@@ -449,7 +494,7 @@ class HydrostaticFreeSurfaceModel:
         fields = [self.u, self.v] + list(self.tracers)
         _lib.call("ocn_ab2_step", g.cref, len(idx), _lib.ptr_array([f.ptr for f in fields]), _lib.ptr_array([Gn[q].ptr for q in idx]),
                   _lib.ptr_array([Gm[q].ptr for q in idx]), _lib.i32_array([f.loc for f in fields]), float(dt), float(chi), s)
-        if self._cavd and self._implicit:  # implicit_step! with the κ fields of the last update_state! (the reference does not recompute them)
+        if self._kfields and self._implicit:  # implicit_step! with the κ fields of the last update_state! (the reference does not recompute them)
             d, w = self.diffusivity_fields, self._ivd_scratch
             kappas = [d["kappa_u"].ptr] * 2 + [d["kappa_c"].ptr] * len(self.tracers)
             scratch = [w[0].data_ptr(), w[1].data_ptr()] + [w[2].data_ptr()] * len(self.tracers)

@@ -28,9 +28,9 @@ from . import _lib
 import ctypes as C
 
 from .advection import WENO, UpwindBiased
-from .physics import (AnisotropicMinimumDissipation, BetaPlane, BuoyancyTracer, Centered, ConvectiveAdjustmentVerticalDiffusivity,
+from .physics import (AnisotropicMinimumDissipation, BetaPlane, BuoyancyTracer, Centered,
                       FieldBoundaryConditions, FPlane, ScalarDiffusivity,
-                      SeawaterBuoyancy, Smagorinsky, implicit_diffusion_solver, is_vertically_implicit, owns_eddy_fields)
+                      SeawaterBuoyancy, Smagorinsky, has_diffusivity_fields, implicit_diffusion_solver, is_vertically_implicit, owns_eddy_fields)
 from .architectures import stream_ptr
 from .fields import CenterField, Field, XFaceField, YFaceField, ZFaceField, fill_halo_regions
 from .grids import Bounded, Flat, require_regular_xy
@@ -122,10 +122,11 @@ class NonhydrostaticModel:
         if isinstance(coriolis, BetaPlane) and grid.topology[1] == Flat:
             raise NotImplementedError("BetaPlane needs a non-Flat y")
         # (_hydrostatic_container: the HydrostaticFreeSurfaceModel builds this class as the container of its fields; it owns the κ fields of
-        # a ConvectiveAdjustmentVerticalDiffusivity and every launch of that closure, the container only carries the object)
-        if isinstance(closure, ConvectiveAdjustmentVerticalDiffusivity):
+        # a ConvectiveAdjustmentVerticalDiffusivity or RiBasedVerticalDiffusivity and every launch of that closure, the container only carries
+        # the object)
+        if has_diffusivity_fields(closure):
             if not _hydrostatic_container:
-                raise NotImplementedError("closure = ConvectiveAdjustmentVerticalDiffusivity on NonhydrostaticModel is not implemented (w would need "
+                raise NotImplementedError(f"closure = {type(closure).__name__} on NonhydrostaticModel is not implemented (w would need "
                                           "the Face-in-z rows of the field-valued implicit step); HydrostaticFreeSurfaceModel takes it (see DESIGN.md §5.2j)")
         elif closure is not None and not isinstance(closure, (ScalarDiffusivity, AnisotropicMinimumDissipation, Smagorinsky)):
             raise NotImplementedError("only closure = ScalarDiffusivity(...), AnisotropicMinimumDissipation(...), Smagorinsky(...) or "
@@ -281,7 +282,7 @@ class NonhydrostaticModel:
         # is 0; the explicit part of the closure term is added by its own kernel and the implicit part follows every substep (implicit_step)
         self._implicit = is_vertically_implicit(closure)
         self._terms_noclosure = None
-        if self._implicit or isinstance(closure, ConvectiveAdjustmentVerticalDiffusivity):  # (whose term has kernels of its own in both discretizations)
+        if self._implicit or has_diffusivity_fields(closure):  # (whose term has kernels of its own in both discretizations)
             self._terms_noclosure = _lib.CModelTerms()
             C.memmove(C.byref(self._terms_noclosure), C.byref(self._terms), C.sizeof(_lib.CModelTerms))
             self._terms_noclosure.closure, self._terms_noclosure.nu = 0, 0.0

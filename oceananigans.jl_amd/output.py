@@ -170,6 +170,9 @@ def write_checkpoint(model, filepath):
         out[f"{ADDR}/η/data"] = model.eta.cpu().numpy().T
         out[f"{ADDR}/timestepper/Gⁿ/η/data"] = model._Geta.cpu().numpy().T
         out[f"{ADDR}/timestepper/G⁻/η/data"] = model._Geta_m.cpu().numpy().T
+        if getattr(model, "_ri", False):  # the time-averaged κᶜ, κᵘ of RiBasedVerticalDiffusivity are state (the reference does not checkpoint them)
+            for name in ("kappa_c", "kappa_u"):
+                out[f"{ADDR}/diffusivity_fields/{name}/data"] = model.diffusivity_fields[name].parent()
         if model.split:
             out[f"{ADDR}/U/data"] = model.U.cpu().numpy().T
             out[f"{ADDR}/V/data"] = model.V.cpu().numpy().T
@@ -253,6 +256,15 @@ def set_from_checkpoint(model, filepath):
         model.clock.last_dt = float(z[f"{ADDR}/clock/last_Δt"])
     if hyd:
         model.update_state(compute_tendencies=False)
+        if getattr(model, "_ri", False):
+            # update_state! has just advanced the time average from whatever the model held: put back the averaged κᶜ, κᵘ that the
+            # checkpointed tendencies were computed with, so that the restart continues bit-identically
+            with np.load(filepath if str(filepath).endswith(".npz") else str(filepath) + ".npz") as z:
+                for name in ("kappa_c", "kappa_u"):
+                    key = f"{ADDR}/diffusivity_fields/{name}/data"
+                    if key not in z.files:
+                        raise KeyError(f"Field {name} of RiBasedVerticalDiffusivity does not exist in checkpoint and could not be restored.")
+                    model.diffusivity_fields[name].data.copy_(torch.from_numpy(np.ascontiguousarray(z[key].T)))
     else:
         update_state(model, compute_tendencies=False)
     return model

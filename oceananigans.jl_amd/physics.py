@@ -6,6 +6,8 @@
                                                   src/TurbulenceClosures/turbulence_closure_implementations/scalar_diffusivity.jl
   ConvectiveAdjustmentVerticalDiffusivity([time_discretization], convective_κz=..., background_κz=..., convective_νz=..., background_νz=...)
                                                   .../turbulence_closure_implementations/convective_adjustment_vertical_diffusivity.jl
+  RiBasedVerticalDiffusivity([time_discretization], Ri_dependent_tapering=..., horizontal_Ri_filter=..., nu_0=..., kappa_0=..., kappa_ca=..., ...)
+                                                  .../turbulence_closure_implementations/ri_based_vertical_diffusivity.jl
   Smagorinsky(coefficient=..., Pr=...), SmagorinskyLilly(C=..., Cb=..., Pr=...), LillyCoefficient(...)
                                                   .../turbulence_closure_implementations/Smagorinskys/{smagorinsky,lilly_coefficient}.jl
   BuoyancyTracer(), SeawaterBuoyancy(...), LinearEquationOfState(...)
@@ -240,6 +242,152 @@ class ConvectiveAdjustmentVerticalDiffusivity:
         v = self._given
         return (f"ConvectiveAdjustmentVerticalDiffusivity{{{type(self.time_discretization).__name__}}}(background_κz={v['background_kappa_z']} "
                 f"convective_κz={v['convective_kappa_z']} background_νz={v['background_nu_z']} convective_νz={v['convective_nu_z']})")
+
+
+class PiecewiseLinearRiDependentTapering:
+    """1 - min(1, max(0, (Ri - Ri₀) / Riᵟ)) (ri_based_vertical_diffusivity.jl:45, 239)"""
+    code = _lib.RI_TAPER_LINEAR
+
+    def __repr__(self):
+        return type(self).__name__
+
+
+class ExponentialRiDependentTapering(PiecewiseLinearRiDependentTapering):
+    """exp(-max(0, (Ri - Ri₀) / Riᵟ)) (:46, 240)"""
+    code = _lib.RI_TAPER_EXP
+
+
+class HyperbolicTangentRiDependentTapering(PiecewiseLinearRiDependentTapering):
+    """(1 - tanh((Ri - Ri₀) / Riᵟ)) / 2 (:47, 241)"""
+    code = _lib.RI_TAPER_TANH
+
+
+class FivePointHorizontalFilter:
+    """filter_horizontally(::FivePointHorizontalFilter) = ℑxyᶜᶜᵃ(ℑxyᶠᶠᵃ Ri) (:54-56)"""
+
+    def __repr__(self):
+        return "FivePointHorizontalFilter"
+
+
+def _prettysummary(x):
+    """prettysummary(::AbstractFloat) (Grids/grid_utils.jl:278): Julia's shortest representation, compact (at most six significant digits)"""
+    from decimal import Decimal
+    x = float(x)
+    if x != x:
+        return "NaN"
+    if math.isinf(x):
+        return "Inf" if x > 0 else "-Inf"
+    if x == 0:
+        return "-0.0" if math.copysign(1.0, x) < 0 else "0.0"
+    d = Decimal(repr(x))
+    if len(d.as_tuple().digits) > 6:
+        d = Decimal(f"{x:.5e}")
+    sign, digits, exp = d.normalize().as_tuple()
+    digits = "".join(map(str, digits))
+    point = len(digits) + exp  # the value is 0.digits x 10^point
+    if -4 < point <= 6:
+        if point <= 0:
+            body = "0." + "0" * (-point) + digits
+        elif point >= len(digits):
+            body = digits + "0" * (point - len(digits)) + ".0"
+        else:
+            body = digits[:point] + "." + digits[point:]
+    else:
+        body = digits[0] + "." + (digits[1:] or "0") + "e" + str(point - 1)
+    return ("-" if sign else "") + body
+
+
+class RiBasedVerticalDiffusivity:
+    """RiBasedVerticalDiffusivity([time_discretization = VerticallyImplicitTimeDiscretization()]; Ri_dependent_tapering =
+    HyperbolicTangentRiDependentTapering(), horizontal_Ri_filter = nothing, minimum_entrainment_buoyancy_gradient = 1e-10,
+    maximum_diffusivity = Inf, maximum_viscosity = Inf, ν₀ = 0.7, κ₀ = 0.5, κᶜᵃ = 1.7, Cᵉⁿ = 0.1, Cᵃᵛ = 0.6, Ri₀ = 0.1, Riᵟ = 0.4, warning = true)
+    (ri_based_vertical_diffusivity.jl:125-162): a VerticalFormulation closure whose κᶜ and κᵘ, fields at (Center, Center, Face), are
+    convective-adjustment, entrainment and shear-mixing coefficients, the last tapered by the Richardson number, averaged in time.
+
+    The canonical keyword names are ASCII: nu_0, kappa_0, kappa_ca, C_en, C_av, Ri_0, Ri_delta.  Keyword names are NFKC-normalised before
+    lookup (Python does the same to identifiers in source), so κᶜᵃ=, Cᵉⁿ=, Cᵃᵛ=, Riᵟ= work as written and ν₀, κ₀, Ri₀, which Python does not
+    accept in source, through **{"ν₀": ...}.  The parameters are numbers; HydrostaticFreeSurfaceModel only."""
+    DEFAULTS = {"nu_0": 0.7, "kappa_0": 0.5, "kappa_ca": 1.7, "C_en": 0.1, "C_av": 0.6, "Ri_0": 0.1, "Ri_delta": 0.4,
+                "minimum_entrainment_buoyancy_gradient": 1e-10, "maximum_diffusivity": math.inf, "maximum_viscosity": math.inf}
+    # NFKC("ν₀") = "ν0", NFKC("κᶜᵃ") = "κca", NFKC("Riᵟ") = "Riδ", ...
+    _NAMES = {"ν0": "nu_0", "κ0": "kappa_0", "κca": "kappa_ca", "Cen": "C_en", "Cav": "C_av", "Ri0": "Ri_0", "Riδ": "Ri_delta"}
+    _SHOWN = {"nu_0": "ν₀", "kappa_0": "κ₀", "kappa_ca": "κᶜᵃ", "C_en": "Cᵉⁿ", "C_av": "Cᵃᵛ", "Ri_0": "Ri₀", "Ri_delta": "Riᵟ"}
+    WARNING = ("RiBasedVerticalDiffusivity is an experimental turbulence closure that \nis unvalidated and whose default parameters are not "
+               "calibrated for \nrealistic ocean conditions or for use in a three-dimensional \nsimulation. Use with caution and report bugs "
+               "and problems with physics \nto https://github.com/CliMA/Oceananigans.jl/issues.")
+
+    @classmethod
+    def canonical(cls, name):
+        """the ASCII name of a keyword or attribute in any spelling, or None"""
+        import unicodedata
+        n = unicodedata.normalize("NFKC", name)
+        return n if n in cls.DEFAULTS else cls._NAMES.get(n)
+
+    def __init__(self, *args, **kw):
+        import warnings
+        if len(args) > 1:
+            raise TypeError("RiBasedVerticalDiffusivity takes one positional argument, the time discretization")
+        if args:
+            if "time_discretization" in kw:
+                raise TypeError("time_discretization given twice")
+            kw["time_discretization"] = args[0]
+        self.time_discretization = as_time_discretization(kw.pop("time_discretization", VerticallyImplicitTimeDiscretization()))
+        tapering = kw.pop("Ri_dependent_tapering", None)
+        tapering = HyperbolicTangentRiDependentTapering() if tapering is None else (tapering() if isinstance(tapering, type) else tapering)
+        if not isinstance(tapering, PiecewiseLinearRiDependentTapering):
+            raise TypeError("Ri_dependent_tapering must be PiecewiseLinearRiDependentTapering(), ExponentialRiDependentTapering() or "
+                            "HyperbolicTangentRiDependentTapering()")
+        self.Ri_dependent_tapering = tapering
+        ri_filter = kw.pop("horizontal_Ri_filter", None)
+        ri_filter = ri_filter() if isinstance(ri_filter, type) else ri_filter
+        if ri_filter is not None and not isinstance(ri_filter, FivePointHorizontalFilter):
+            raise TypeError("horizontal_Ri_filter must be None or FivePointHorizontalFilter()")
+        self.horizontal_Ri_filter = ri_filter
+        warning = kw.pop("warning", True)
+        values = dict(self.DEFAULTS)
+        seen = set()
+        for name, value in kw.items():
+            key = self.canonical(name)
+            if key is None:
+                raise TypeError(f"unexpected keyword arguments {[name]}")
+            if key in seen:
+                raise TypeError(f"{key} given twice")
+            seen.add(key)
+            if isinstance(value, (bool, str)) or callable(value) or not np.isscalar(value) or not np.isreal(value):
+                raise NotImplementedError(f"RiBasedVerticalDiffusivity: {self._SHOWN.get(key, key)} must be a number (functions, arrays, fields "
+                                          "and per-tracer tuples are not implemented)")
+            values[key] = float(value)
+        for key, value in values.items():
+            setattr(self, key, value)
+        if warning:
+            warnings.warn(self.WARNING, stacklevel=2)
+
+    def __getattr__(self, name):  # the reference's field names in any spelling: closure.κᶜᵃ, getattr(closure, "ν₀")
+        key = type(self).canonical(name) if not name.startswith("_") else None
+        if key is None or key == name:
+            raise AttributeError(name)
+        return getattr(self, key)
+
+    def c_struct(self):
+        """struct ocn_ri_based"""
+        return _lib.CRiBased(self.nu_0, self.kappa_0, self.kappa_ca, self.C_en, self.C_av, self.Ri_0, self.Ri_delta,
+                             self.minimum_entrainment_buoyancy_gradient, self.maximum_diffusivity, self.maximum_viscosity,
+                             self.Ri_dependent_tapering.code,
+                             _lib.RI_FILTER_NONE if self.horizontal_Ri_filter is None else _lib.RI_FILTER_FIVE_POINT)
+
+    def __repr__(self):  # Base.show (ri_based_vertical_diffusivity.jl:347-361)
+        rows = [("Ri_dependent_tapering", repr(self.Ri_dependent_tapering))]
+        rows += [(self._SHOWN[k], _prettysummary(getattr(self, k))) for k in ("kappa_0", "nu_0", "kappa_ca", "C_en", "C_av", "Ri_0", "Ri_delta")]
+        rows += [(k, _prettysummary(getattr(self, k))) for k in ("maximum_diffusivity", "maximum_viscosity")]
+        lines = [f"RiBasedVerticalDiffusivity{{{type(self.time_discretization).__name__}}}"]
+        lines += [("└── " if n == len(rows) - 1 else "├── ") + f"{name}: {value}" for n, (name, value) in enumerate(rows)]
+        return "\n".join(lines)
+
+
+def has_diffusivity_fields(closure):
+    """closures of the VerticalFormulation whose κᶜ, κᵘ are (Center, Center, Face) fields that the HydrostaticFreeSurfaceModel computes in
+    update_state! (their term and implicit step: csrc/vertical_diffusivity.hip)"""
+    return isinstance(closure, (ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity))
 
 
 class AnisotropicMinimumDissipation:
