@@ -501,6 +501,26 @@ int ocn_compute_ri_based_diffusivities_fused(const ocn_grid *grid, const ocn_mod
 /* The tapering functions on the HOST (no device is touched): out[q] = τ(x[q]; x0, delta), q = 0..n-1, kind = OCN_RI_TAPER_*, by the inline
  * functions the kernels call (csrc/ocn_taper.h: IEEE +, -, *, / and powers of two only, no math library) -- the same bits as on the device. */
 int ocn_ri_taper_host(int32_t kind, int64_t n, const double *x, double x0, double delta, double *out);
+/* ---- HorizontalScalarBiharmonicDiffusivity: ScalarBiharmonicDiffusivity{HorizontalFormulation} with constant ν and κ
+ * (csrc/biharmonic.hip; abstract_scalar_biharmonic_diffusivity_closure.jl:46-51, 66-67, 75-102; strict math whatever the math mode) ----
+ * The closure term SUBTRACTED from tendencies that hold every other term, over i = 1..Nx, j = 1..Ny, k = 1..Nz:
+ *   Gu -= ∂ⱼτ₁ⱼ, Gv -= ∂ⱼτ₂ⱼ with viscous_flux_ux = viscous_flux_vy = nu δ★ᶜᶜᶜ, viscous_flux_vx = nu ζ★ᶠᶠᶜ, viscous_flux_uy = -nu ζ★ᶠᶠᶜ;
+ *   Gc[n] -= ∇·q with diffusive_flux_x = kappa[n] ∂x_∇²h_cᶠᶜᶜ, diffusive_flux_y = kappa[n] ∂y_∇²h_cᶜᶠᶜ;  no z flux.
+ * The grid: x and y Periodic and regular, Hx >= 2 and Hy >= 2, any z (the term is horizontal; Δz of the cell's own plane enters through the
+ * areas and the volume).  u, v, c[n] are read up to two cells from the interior in x and y (their halos must be filled that far) and at
+ * k = 1..Nz only; nothing but interior cells of G is written.  u == NULL: no momentum part (then v, Gu, Gv, neg_other_u, neg_other_v are NULL
+ * too).  kappa / c / Gc: HOST arrays of n_tracers (0 .. OCN_MODEL_MAX_TRACERS) numbers / device pointers.  A zero nu or kappa[n] skips its
+ * launch (the term is ±0) unless a neg_other array goes with it.
+ * neg_other_u, neg_other_v, neg_other_c (a HOST array of n_tracers device pointers, entries may be NULL), each NULL or an array S in the
+ * field's layout that holds MINUS the term b of the other closure of a two-closure tuple (what ocn_add_vertical_diffusivity_fluxes leaves
+ * in a zeroed array: 0 - b): then G -= (a + (0 - S)), the reference's G - (∂ⱼτ(c₁) + ∂ⱼτ(c₂)) (closure_tuples.jl:41-43), where a alone
+ * gives G -= a.  (0 - S restores b up to the sign of a zero b.)
+ * OCN_ERR_INVALID_ARGUMENT, before any device work: another x / y topology, a stretched x or y (their spacing is not positive here),
+ * Hx < 2 or Hy < 2, n_tracers outside its range, a NULL pointer where one is needed, a momentum pointer without u, nothing to do, nu or
+ * kappa[n] negative or not finite, two of the arrays being the same. */
+int ocn_add_biharmonic_fluxes(const ocn_grid *grid, double nu, const double *u, const double *v, double *Gu, double *Gv, int32_t n_tracers,
+                              const double *kappa, const double *const *c, double *const *Gc, const double *neg_other_u,
+                              const double *neg_other_v, const double *const *neg_other_c, void *stream);
 /* cache_previous_tendencies! (src/TimeSteppers/store_tendencies.jl:6-22) */
 int ocn_cache_previous_tendencies(const ocn_grid *grid, int32_t n, double *const *Gm, const double *const *Gn,
                                   const int32_t *locs, void *stream);

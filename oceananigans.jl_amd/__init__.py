@@ -21,6 +21,8 @@ from .models import (NonhydrostaticModel, QuasiAdamsBashforth2TimeStepper, Runge
                      update_state, compute_boundary_functions, compute_boundary_tendency_contributions)
 from .output import (AdvectiveCFL, DiffusiveCFL, NaNChecker, TimeStepWizard, cell_advection_timescale, cell_diffusion_timescale, hasnan, set_from_checkpoint,
                      write_checkpoint)
+from .physics import (HorizontalDivergenceFormulation, HorizontalFormulation, HorizontalScalarBiharmonicDiffusivity, ScalarBiharmonicDiffusivity,
+                      ThreeDimensionalFormulation, VerticalFormulation)
 from .physics import (ExponentialRiDependentTapering, FivePointHorizontalFilter, HyperbolicTangentRiDependentTapering,
                       PiecewiseLinearRiDependentTapering, RiBasedVerticalDiffusivity)
 from .physics import (AnisotropicMinimumDissipation, ConvectiveAdjustmentVerticalDiffusivity, DynamicCoefficient, DynamicSmagorinsky, LillyCoefficient, Smagorinsky, SmagorinskyLilly, BetaPlane, BoundaryCondition, BuoyancyTracer, Centered, FieldBoundaryConditions, FluxBoundaryCondition, FPlane,

@@ -199,6 +199,8 @@ _SIGS = {
     "ocn_add_vertical_diffusivity_fluxes": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _vp, _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                             _i32, C.POINTER(_i32), _vp],
     "ocn_implicit_vertical_diffusion_step_fields": [C.POINTER(CGrid), _i32, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_vp), C.POINTER(_vp), _dbl, _vp],
+    "ocn_add_biharmonic_fluxes": [C.POINTER(CGrid), _dbl, _vp, _vp, _vp, _vp, _i32, C.POINTER(_dbl), C.POINTER(_vp), C.POINTER(_vp), _vp, _vp,
+                                  C.POINTER(_vp), _vp],
     "ocn_compute_ri_number": [C.POINTER(CGrid), C.POINTER(CModelTerms), _vp, _vp, _vp, _vp],
     "ocn_compute_ri_based_diffusivities": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CRiBased), C.POINTER(CBc), C.POINTER(CBc), _vp, _vp,
                                            _vp, _vp],

@@ -1434,6 +1434,50 @@ int ocn_implicit_vertical_diffusion_step_fields(const ocn_grid *grid, int32_t n,
     return launch_ivd_implicit_step_fields(grid, n, fields, locs, kappa, scratch, dt, as_stream(stream));
 }
 
+// biharmonic.hip: everything is checked on the host before the first HIP call
+int ocn_add_biharmonic_fluxes(const ocn_grid *grid, double nu, const double *u, const double *v, double *Gu, double *Gv, int32_t n_tracers,
+                              const double *kappa, const double *const *c, double *const *Gc, const double *neg_other_u,
+                              const double *neg_other_v, const double *const *neg_other_c, void *stream)
+{
+    const char *who = "ocn_add_biharmonic_fluxes";
+    int st = validate_grid_any(grid);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(grid->tx == OCN_PERIODIC && grid->ty == OCN_PERIODIC,
+                "%s: x and y must be Periodic, got topology (%d, %d, %d) (the biharmonic masks of a wall are not implemented)", who, grid->tx,
+                grid->ty, grid->tz);
+    OCN_REQUIRE(grid->Hx >= 2 && grid->Hy >= 2, "%s: halo >= 2 required in x and y, got (%d, %d)", who, grid->Hx, grid->Hy);
+    OCN_REQUIRE(n_tracers >= 0 && n_tracers <= OCN_MODEL_MAX_TRACERS, "%s: number of tracers %d outside 0..%d", who, n_tracers,
+                OCN_MODEL_MAX_TRACERS);
+    const void *seen[4 + 3 * OCN_MODEL_MAX_TRACERS];  // every array of the call, to refuse aliases
+    int n_seen = 0;
+    if (u) {
+        OCN_REQUIRE(v && Gu && Gv, "%s: null field pointer (u is given: v, Gu, Gv are needed)", who);
+        OCN_REQUIRE(std::isfinite(nu) && nu >= 0, "%s: nu = %g must be finite and >= 0", who, nu);
+        OCN_REQUIRE(u != v, "%s: u and v are the same array", who);
+        seen[n_seen++] = Gu;
+        seen[n_seen++] = Gv;
+        if (neg_other_u) seen[n_seen++] = neg_other_u;
+        if (neg_other_v) seen[n_seen++] = neg_other_v;
+    } else {
+        OCN_REQUIRE(!v && !Gu && !Gv && !neg_other_u && !neg_other_v, "%s: u is NULL (no momentum part) but another momentum pointer is not", who);
+        OCN_REQUIRE(n_tracers >= 1, "%s: nothing to do (u is NULL and n_tracers is 0)", who);
+    }
+    if (n_tracers) OCN_REQUIRE(kappa && c && Gc, "%s: null tracer array", who);
+    for (int n = 0; n < n_tracers; ++n) {
+        OCN_REQUIRE(c[n] && Gc[n], "%s: tracer %d: null pointer", who, n);
+        OCN_REQUIRE(std::isfinite(kappa[n]) && kappa[n] >= 0, "%s: tracer %d: kappa = %g must be finite and >= 0", who, n, kappa[n]);
+        seen[n_seen++] = Gc[n];
+        if (neg_other_c && neg_other_c[n]) seen[n_seen++] = neg_other_c[n];
+    }
+    for (int q = 0; q < n_seen; ++q) {
+        OCN_REQUIRE(!u || (seen[q] != u && seen[q] != v), "%s: a tendency or neg_other array is u or v", who);
+        for (int n = 0; n < n_tracers; ++n) OCN_REQUIRE(seen[q] != c[n], "%s: a tendency or neg_other array is tracer %d", who, n);
+    }
+    for (int q = 0; q < n_seen; ++q)
+        for (int p = 0; p < q; ++p) OCN_REQUIRE(seen[p] != seen[q], "%s: two of the tendency / neg_other arrays are the same array", who);
+    return launch_biharmonic_fluxes(grid, nu, u, v, Gu, Gv, n_tracers, kappa, c, Gc, neg_other_u, neg_other_v, neg_other_c, as_stream(stream));
+}
+
 // the three entry points of ri_based_diffusivity.hip
 static int validate_ri_buoyancy(const ocn_model_terms *terms, const char *who)
 {

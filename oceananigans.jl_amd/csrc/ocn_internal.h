@@ -96,6 +96,11 @@ int launch_ri_based(int mode, const ocn_grid *grid, const ocn_model_terms *terms
                     const ocn_bc *top_S, const double *u, const double *v, const double *ri_in, double *ri_out, double *kappa_c,
                     double *kappa_u, hipStream_t stream);
 void ri_taper_host(int kind, long long n, const double *x, double x0, double delta, double *out);
+// biharmonic.hip: the term of HorizontalScalarBiharmonicDiffusivity (constant ν, κ; Periodic regular x and y) subtracted from G; neg_other_*:
+// minus the term of a tuple's other closure, or NULL
+int launch_biharmonic_fluxes(const ocn_grid *grid, double nu, const double *u, const double *v, double *Gu, double *Gv, int n_tracers,
+                             const double *kappa, const double *const *c, double *const *Gc, const double *neg_other_u,
+                             const double *neg_other_v, const double *const *neg_other_c, hipStream_t stream);
 int launch_profile_marker(hipStream_t stream);
 int wait_stream(hipStream_t stream, double seconds, const char *who);
 int launch_hydrostatic_pressure(const ocn_grid *grid, const TermsDev &t, double *pHY, hipStream_t stream, const int32_t *irange = nullptr);

@@ -12,9 +12,10 @@ energy-conserving vertical advection and kinetic-energy gradient) or a flux-form
 with VerticallyImplicitTimeDiscretization() (QAB2, fused = False: implicit_step! of u, v and the tracers after their ab2 step), or
 ConvectiveAdjustmentVerticalDiffusivity(...) / RiBasedVerticalDiffusivity(...) (QAB2, fused = False, one GPU: κᶜ, κᵘ fields computed in
 update_state! -- csrc/vertical_diffusivity.hip, csrc/ri_based_diffusivity.hip --, their term and the field-valued implicit step in
-csrc/vertical_diffusivity.hip).  NOT in this slice (each raises):
+csrc/vertical_diffusivity.hip), or HorizontalScalarBiharmonicDiffusivity(ν, κ) (fused = False, one GPU: csrc/biharmonic.hip), alone or in a
+two-closure tuple with one of the two closures with κ fields.  NOT in this slice (each raises):
 SplitExplicitFreeSurface / ImplicitFreeSurface, upwinding / WENO vector-invariant variants, z-star coordinates, eddy-viscosity closures,
-closure tuples,
+every other closure tuple,
 a tracer advection scheme different from the momentum one, Distributed architectures.
 """
 import ctypes as C
@@ -27,7 +28,7 @@ from .fields import ZFaceField, fill_halo_regions
 from .grids import Bounded, Periodic
 from .models import NonhydrostaticModel, compute_boundary_tendency_contributions, update_hydrostatic_pressure
 from .physics import (BuoyancyTracer, Centered, RiBasedVerticalDiffusivity, SeawaterBuoyancy, has_diffusivity_fields, is_vertically_implicit,
-                      owns_eddy_fields)
+                      owns_eddy_fields, split_closure_tuple)
 
 g_Earth = 9.80665  # Oceananigans.BuoyancyFormulations.g_Earth
 
@@ -204,10 +205,18 @@ class HydrostaticFreeSurfaceModel:
             if tracer_advection is not None and type(tracer_advection) is not type(momentum_advection):
                 raise NotImplementedError("with a flux-form momentum scheme, tracer_advection must be the same scheme in this slice")
             container_advection = momentum_advection
+        # closure = HorizontalScalarBiharmonicDiffusivity(...), alone or in a tuple with a closure that has κ fields (every other tuple
+        # raises): its term has a kernel of its own and no state, so from here on `closure` is the rest -- the other closure, or None
+        self.closure = tuple(closure) if isinstance(closure, (tuple, list)) else closure
+        self._biharmonic, closure = split_closure_tuple(closure)
+        if self._biharmonic is not None:
+            if fused:
+                raise NotImplementedError("ScalarBiharmonicDiffusivity runs the reference's launch sequence (fused = False)")
+            if self._dist is not None or hasattr(arch, "partition"):
+                raise NotImplementedError("ScalarBiharmonicDiffusivity on a slab-partitioned (Distributed) grid is not implemented")
+            fused = False
         if owns_eddy_fields(closure):
             raise NotImplementedError("eddy-viscosity closures are not part of this slice")
-        if isinstance(closure, (tuple, list)):
-            raise NotImplementedError("closure tuples are not implemented: give one closure")
         # closure = ConvectiveAdjustmentVerticalDiffusivity(...) or RiBasedVerticalDiffusivity(...), the closures with κᶜ, κᵘ fields: the
         # reference's launch sequence with QAB2 on one GPU, in both discretizations
         self._kfields = has_diffusivity_fields(closure)
@@ -246,7 +255,8 @@ class HydrostaticFreeSurfaceModel:
         # its pressure solver and w tendency are simply not used
         self._nh = NonhydrostaticModel(grid, advection=container_advection, tracers=tracers, timestepper="QuasiAdamsBashforth2",
                                        closure=closure, buoyancy=buoyancy, coriolis=coriolis, boundary_conditions=boundary_conditions,
-                                       pressure_solver=None, math_mode=math_mode, _hydrostatic_container=True)
+                                       pressure_solver=None, math_mode=math_mode, _hydrostatic_container=True,
+                                       _closure_halo=0 if self._biharmonic is None else self._biharmonic.required_halo_size)
         nh = self._nh
         grid = nh.grid  # (halo-inflated / math-mode-pinned by the container model)
         # build_diffusivity_fields (convective_adjustment_vertical_diffusivity.jl:85, ri_based_vertical_diffusivity.jl:186-191): κᶜ and κᵘ
@@ -260,6 +270,8 @@ class HydrostaticFreeSurfaceModel:
             self._closure_struct = closure.c_struct()
             if self._implicit:
                 self._ivd_scratch = torch.zeros((3, grid.Nz, grid.Ny, grid.Nx), dtype=torch.float64, device=nh.u.data.device)
+            if self._biharmonic is not None:  # the tuple: minus the other closure's term, for u and v and then tracer by tracer
+                self._tuple_scratch = torch.zeros((2,) + tuple(nh.u.data.shape), dtype=torch.float64, device=nh.u.data.device)
         self.grid, self.architecture, self.clock = grid, grid.architecture, nh.clock
         self.free_surface = free_surface
         self.u, self.v, self.w = nh.u, nh.v, nh.w
@@ -397,7 +409,9 @@ class HydrostaticFreeSurfaceModel:
             kappa = 0.0 if (nh.closure is None or self._implicit or self._kfields) else nh.closure.kappa_of(self.tracer_names[n])
             _lib.call("ocn_compute_tracer_tendency_terms", g.cref, C.byref(terms), kappa, None, self.u.ptr, self.v.ptr, self.w.ptr,
                       c.ptr, Gn[3 + n].ptr, None, s)
-        if self._kfields:  # the closure term: every vertical flux (explicit), or the fluxes through the two boundaries (vertically implicit)
+        if self._biharmonic is not None:
+            self._add_biharmonic_fluxes(Gn, s)
+        elif self._kfields:  # the closure term: every vertical flux (explicit), or the fluxes through the two boundaries (vertically implicit)
             nt, d = len(self.tracers), self.diffusivity_fields
             _lib.call("ocn_add_vertical_diffusivity_fluxes", g.cref, d["kappa_u"].ptr, self.u.ptr, self.v.ptr, Gn[0].ptr, Gn[1].ptr, nt,
                       _lib.ptr_array([d["kappa_c"].ptr] * max(nt, 1)), _lib.ptr_array([c.ptr for c in self.tracers] or [None]),
@@ -409,6 +423,30 @@ class HydrostaticFreeSurfaceModel:
                       _lib.ptr_array([c.ptr for c in self.tracers] or [None]), _lib.ptr_array([G.ptr for G in Gn[3:]] or [None]), None, s)
         if boundary_contributions:
             compute_boundary_tendency_contributions(nh)
+
+    def _add_biharmonic_fluxes(self, Gn, s):
+        """G -= ∂ⱼτ of HorizontalScalarBiharmonicDiffusivity -- or, in a tuple with a closure V that has κ fields, G -= (∂ⱼτ + ∂ⱼτ(V)), the
+        sum formed before it is subtracted (closure_tuples.jl:41-43): V's kernel leaves 0 - ∂ⱼτ(V) in a zeroed array, which the biharmonic
+        kernel adds to its own term.  Two such arrays: u and v first, then tracer by tracer."""
+        g, bih, pa = self.grid, self._biharmonic, _lib.ptr_array
+        nt = len(self.tracers)
+        kappa = [bih.kappa_of(n) for n in self.tracer_names]
+        if not self._kfields:
+            _lib.call("ocn_add_biharmonic_fluxes", g.cref, bih.nu, self.u.ptr, self.v.ptr, Gn[0].ptr, Gn[1].ptr, nt, (C.c_double * max(nt, 1))(*kappa),
+                      pa([c.ptr for c in self.tracers] or [None]), pa([G.ptr for G in Gn[3:]] or [None]), None, None, None, s)
+            return
+        d, S, implicit = self.diffusivity_fields, self._tuple_scratch, int(self._implicit)
+        Su, Sv = S[0].data_ptr(), S[1].data_ptr()
+        S.zero_()
+        _lib.call("ocn_add_vertical_diffusivity_fluxes", g.cref, d["kappa_u"].ptr, self.u.ptr, self.v.ptr, Su, Sv, 0, None, None, None, implicit,
+                  None, s)
+        _lib.call("ocn_add_biharmonic_fluxes", g.cref, bih.nu, self.u.ptr, self.v.ptr, Gn[0].ptr, Gn[1].ptr, 0, None, None, None, Su, Sv, None, s)
+        for n, c in enumerate(self.tracers):
+            S[0].zero_()
+            _lib.call("ocn_add_vertical_diffusivity_fluxes", g.cref, None, None, None, None, None, 1, pa([d["kappa_c"].ptr]), pa([c.ptr]), pa([Su]),
+                      implicit, None, s)
+            _lib.call("ocn_add_biharmonic_fluxes", g.cref, 0.0, None, None, None, None, 1, (C.c_double * 1)(kappa[n]), pa([c.ptr]),
+                      pa([Gn[3 + n].ptr]), None, None, pa([Su]), s)
 
     # ---- time_step! (quasi_adams_bashforth_2.jl:74-115 with ab2_step!(::HydrostaticFreeSurfaceModel)) -------------------------
     def _time_step_split_rk3(self, dt):

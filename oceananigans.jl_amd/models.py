@@ -29,7 +29,7 @@ import ctypes as C
 
 from .advection import WENO, UpwindBiased
 from .physics import (AnisotropicMinimumDissipation, BetaPlane, BuoyancyTracer, Centered,
-                      FieldBoundaryConditions, FPlane, ScalarDiffusivity,
+                      FieldBoundaryConditions, FPlane, ScalarBiharmonicDiffusivity, ScalarDiffusivity,
                       SeawaterBuoyancy, Smagorinsky, has_diffusivity_fields, implicit_diffusion_solver, is_vertically_implicit, owns_eddy_fields)
 from .architectures import stream_ptr
 from .fields import CenterField, Field, XFaceField, YFaceField, ZFaceField, fill_halo_regions
@@ -92,7 +92,7 @@ class NonhydrostaticModel:
     def __init__(self, grid, advection=None, tracers=(), timestepper="RungeKutta3", closure=None, buoyancy=None,
                  coriolis=None, forcing=None, stokes_drift=None, boundary_conditions=None,
                  hydrostatic_pressure_anomaly="default", pressure_solver="default", math_mode=None, particles=None,
-                 _hydrostatic_container=False):
+                 _hydrostatic_container=False, _closure_halo=0):
         """math_mode: None keeps the grid's (default: the process default, ocn.set_math_mode); MATH_STRICT / MATH_FAST pin this
         model's arithmetic variant whatever other models of the process use (ocn_grid.math).
         particles: None or LagrangianParticles(...): moved to the architecture here and stepped with the pressure-corrected, halo-filled
@@ -123,7 +123,11 @@ class NonhydrostaticModel:
             raise NotImplementedError("BetaPlane needs a non-Flat y")
         # (_hydrostatic_container: the HydrostaticFreeSurfaceModel builds this class as the container of its fields; it owns the κ fields of
         # a ConvectiveAdjustmentVerticalDiffusivity or RiBasedVerticalDiffusivity and every launch of that closure, the container only carries
-        # the object)
+        # the object; a ScalarBiharmonicDiffusivity never reaches the container, only the halo it needs: _closure_halo)
+        if isinstance(closure, ScalarBiharmonicDiffusivity):
+            raise NotImplementedError("ScalarBiharmonicDiffusivity on NonhydrostaticModel is not implemented (its w fluxes need the "
+                                      "three-dimensional ∇²ᶜᶜᶠ and the wall masks); HydrostaticFreeSurfaceModel takes "
+                                      "HorizontalScalarBiharmonicDiffusivity (see DESIGN.md §5.2l)")
         if has_diffusivity_fields(closure):
             if not _hydrostatic_container:
                 raise NotImplementedError(f"closure = {type(closure).__name__} on NonhydrostaticModel is not implemented (w would need "
@@ -154,7 +158,8 @@ class NonhydrostaticModel:
         # inflate_grid_halo_size (nonhydrostatic_model.jl:183, 243-257; test_nonhydrostatic_models.jl:34-66): the model rebuilds the
         # grid with the halo its advection scheme and closure need, never with a smaller one than the user gave.
         # adapt_advection_order (a lower-order scheme in a direction with too few cells) is not supported: that raises.
-        required = max(advection.buffer, 1 if closure is not None else 0, 1)
+        # (required_halo_size_x/y/z of a ScalarBiharmonicDiffusivity: 2 in every direction)
+        required = max(advection.buffer, 1 if closure is not None else 0, _closure_halo, 1)
         H = (grid.Hx, grid.Hy, grid.Hz)
         for d, (N, t) in enumerate(zip(grid.size, grid.topology)):
             if t != Flat and N < advection.buffer:

@@ -390,6 +390,130 @@ def has_diffusivity_fields(closure):
     return isinstance(closure, (ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity))
 
 
+class ThreeDimensionalFormulation:
+    """ThreeDimensionalFormulation() (TurbulenceClosures.jl): the closure acts isotropically"""
+
+    def __repr__(self):
+        return type(self).__name__ + "()"
+
+
+class HorizontalFormulation(ThreeDimensionalFormulation):
+    """HorizontalFormulation(): the closure acts in x and y"""
+
+
+class VerticalFormulation(ThreeDimensionalFormulation):
+    """VerticalFormulation(): the closure acts in z"""
+
+
+class HorizontalDivergenceFormulation(ThreeDimensionalFormulation):
+    """HorizontalDivergenceFormulation(): the closure acts on the horizontal divergence alone"""
+
+
+_FORMULATIONS = (ThreeDimensionalFormulation, HorizontalFormulation, VerticalFormulation, HorizontalDivergenceFormulation)
+
+
+def as_formulation(formulation):
+    """an instance, a class, or one of the strings "ThreeDimensional" / "Horizontal" / "Vertical" / "HorizontalDivergence" (with or
+    without "Formulation") -> an instance"""
+    if isinstance(formulation, _FORMULATIONS):
+        return formulation
+    for F in _FORMULATIONS:
+        if formulation is F or formulation in (F.__name__, F.__name__[:-len("Formulation")]):
+            return F()
+    raise ValueError(f"formulation must be one of {', '.join(F.__name__ + '()' for F in _FORMULATIONS)}, got {formulation!r}")
+
+
+class ScalarBiharmonicDiffusivity:
+    """ScalarBiharmonicDiffusivity(formulation = ThreeDimensionalFormulation(); ν = 0, κ = 0) (scalar_biharmonic_diffusivity.jl:75-95):
+    a hyperviscosity ν ∇⁴ and hyperdiffusivity κ ∇⁴, always explicit in time (abstract_scalar_biharmonic_diffusivity_closure.jl:8).
+    Only the HorizontalFormulation with constant coefficients is implemented (HorizontalScalarBiharmonicDiffusivity: csrc/biharmonic.hip;
+    HydrostaticFreeSurfaceModel on a grid Periodic in x and y); every other formulation, and function / array / field coefficients,
+    discrete_form, loc, parameters and a required_halo_size other than 2 raise NotImplementedError.
+    κ is a number (every tracer) or a dict {tracer name: κ}.  ASCII aliases: nu, kappa.  `formulation` is an instance or a string
+    ("Horizontal", ...)."""
+    required_halo_size = 2
+
+    def __init__(self, formulation="ThreeDimensional", **kw):
+        self.formulation = as_formulation(formulation)
+        name = type(self.formulation).__name__
+        if type(self.formulation) is not HorizontalFormulation:
+            raise NotImplementedError(f"ScalarBiharmonicDiffusivity: the {name} is not implemented, only the HorizontalFormulation "
+                                      "(HorizontalScalarBiharmonicDiffusivity; see DESIGN.md §5.2l)")
+        for greek, ascii_name in (("ν", "nu"), ("κ", "kappa")):
+            if greek in kw and ascii_name in kw:
+                raise TypeError(f"{greek} given twice")
+        nu = kw.pop("ν", kw.pop("nu", 0.0))
+        kappa = kw.pop("κ", kw.pop("kappa", 0.0))
+        if kw.pop("discrete_form", False):
+            raise NotImplementedError("ScalarBiharmonicDiffusivity: discrete_form = true is not implemented (constant ν, κ only)")
+        if kw.pop("loc", None) not in (None, (None, None, None)):
+            raise NotImplementedError("ScalarBiharmonicDiffusivity: loc is not implemented (constant ν, κ only)")
+        if kw.pop("parameters", None) is not None:
+            raise NotImplementedError("ScalarBiharmonicDiffusivity: parameters is not implemented (constant ν, κ only)")
+        if kw.pop("required_halo_size", 2) != 2:
+            raise NotImplementedError("ScalarBiharmonicDiffusivity: a required_halo_size other than 2 is not implemented (it serves "
+                                      "coefficient functions; constant ν, κ need 2)")
+        if kw:
+            raise TypeError(f"unexpected keyword arguments {sorted(kw)}")
+
+        def number(x, what):
+            if isinstance(x, (bool, str)) or callable(x) or not np.isscalar(x) or not np.isreal(x):
+                raise NotImplementedError(f"ScalarBiharmonicDiffusivity: {what} must be a number (functions, arrays and fields are not "
+                                          "implemented)")
+            return x
+        self._given_nu = number(nu, "ν")
+        self.nu = float(nu)
+        if isinstance(kappa, dict):
+            self.kappa = {str(k): number(v, f"κ of {k}") for k, v in kappa.items()}
+        else:
+            self.kappa = number(kappa, "κ")
+        self.time_discretization = ExplicitTimeDiscretization()
+
+    ν = property(lambda self: self.nu)
+    κ = property(lambda self: self.kappa)
+
+    def kappa_of(self, name):
+        if isinstance(self.kappa, dict):
+            if name not in self.kappa:
+                raise ValueError(f"no diffusivity κ given for tracer {name}")
+            return float(self.kappa[name])
+        return float(self.kappa)
+
+    def __eq__(self, other):
+        return (isinstance(other, ScalarBiharmonicDiffusivity) and type(other.formulation) is type(self.formulation)
+                and other.nu == self.nu and other.kappa == self.kappa)
+
+    __hash__ = None
+
+    def __repr__(self):  # Base.summary (scalar_biharmonic_diffusivity.jl:105-115)
+        if isinstance(self.kappa, dict):
+            kappa = "(" + ", ".join(f"{k}={_prettysummary(v)}" for k, v in self.kappa.items()) + ("," if len(self.kappa) == 1 else "") + ")"
+        else:
+            kappa = _prettysummary(self.kappa)
+        return f"ScalarBiharmonicDiffusivity{{{type(self.formulation).__name__}}}(ν={_prettysummary(self.nu)}, κ={kappa})"
+
+
+def HorizontalScalarBiharmonicDiffusivity(**kw):
+    """HorizontalScalarBiharmonicDiffusivity(; ν = 0, κ = 0) = ScalarBiharmonicDiffusivity(HorizontalFormulation(); ν, κ)
+    (scalar_biharmonic_diffusivity.jl:18)"""
+    return ScalarBiharmonicDiffusivity(HorizontalFormulation(), **kw)
+
+
+def split_closure_tuple(closure):
+    """A closure, or one of the two-closure tuples that are implemented -- a ScalarBiharmonicDiffusivity with a closure that has κ fields,
+    in either order (closure_tuples.jl) -- -> (biharmonic or None, the other closure or None).  Every other tuple raises."""
+    if isinstance(closure, (tuple, list)):
+        bih = [c for c in closure if isinstance(c, ScalarBiharmonicDiffusivity)]
+        vertical = [c for c in closure if has_diffusivity_fields(c)]
+        if len(closure) != 2 or len(bih) != 1 or len(vertical) != 1:
+            raise NotImplementedError("closure tuples are not implemented, except (HorizontalScalarBiharmonicDiffusivity, "
+                                      "ConvectiveAdjustmentVerticalDiffusivity or RiBasedVerticalDiffusivity) in either order: give one closure")
+        return bih[0], vertical[0]
+    if isinstance(closure, ScalarBiharmonicDiffusivity):
+        return closure, None
+    return None, closure
+
+
 class AnisotropicMinimumDissipation:
     """AnisotropicMinimumDissipation(; C = 1/12, Cν = nothing, Cκ = nothing, Cb = nothing)
     (anisotropic_minimum_dissipation.jl:106-115): ExplicitTimeDiscretization, number (or per-tracer dict) Poincaré constants."""
