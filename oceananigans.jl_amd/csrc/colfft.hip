@@ -278,6 +278,54 @@ __device__ __forceinline__ void fft_inv_stages(cplx *x, cplx *A, const cplx *W, 
     radix8<true>(x);
 }
 
+// ---- the order of a workgroup's first memory requests ---------------------------------------------------------------------------------
+// A column workgroup lives 14 - 17 us at 512^3 and a CU holds two of them, so HBM is busy only while one of the two has requests
+// outstanding: every round trip a workgroup spends waiting for a TABLE (8 KB of L2-resident twiddles, the eigenvalues of the fused z
+// pass) before or between its data accesses is bandwidth not used.  With OCN_FFT_EARLY_LOADS no wait stands in front of the data loads:
+//   eigenvalues (fused z pass only) -> the 8 data loads -> the twiddle entry, into a register -> [the eigenvalues have arrived, vmcnt
+//   retires in order: the eight divisions of the spectral solve, under the data loads] -> one wait -> twiddles to LDS -> barrier.
+// Only the order changes: every value is computed by the expression it had, results are bit for bit the same
+// (tests/test_gpu_poisson_bitwise.py).  -DOCN_FFT_EARLY_LOADS=0 restores the former order (twiddles, wait, data; eigenvalues and
+// divisions between the two transforms) for same-box comparisons of two libraries (tools/ab_bench.sh); profiles/r06a_fft_prologue.md
+// has the listings' figures and the times of both.
+#ifndef OCN_FFT_EARLY_LOADS
+#define OCN_FFT_EARLY_LOADS 1
+#endif
+// a table of NE complex numbers on its way from global memory to LDS, NT threads: table_load() requests, table_store() writes what arrived
+constexpr int table_slots(int NE, int NT) { return (NE + NT - 1) / NT; }  // per thread
+template <int NE, int NT>
+__device__ __forceinline__ void table_load(cplx *v, const double *table, int tid)
+{
+#pragma unroll
+    for (int q = 0; q < table_slots(NE, NT); ++q) {
+        const int j = tid + q * NT;
+        const cplx *e = reinterpret_cast<const cplx *>(table) + (j < NE ? j : 0);  // (unconditional: a load under a branch is waited for on its own)
+        v[q] = cplx{e->x, e->y};
+    }
+}
+template <int NE, int NT>
+__device__ __forceinline__ void table_store(const cplx *v, cplx *lds, int tid)
+{
+#pragma unroll
+    for (int q = 0; q < table_slots(NE, NT); ++q) {
+        const int j = tid + q * NT;
+        if (j < NE) lds[j] = cplx{v[q].x, v[q].y};
+    }
+}
+// Element of a column.  The lanes past the last column of a launch address the block's first column (in bounds) and store nothing; the
+// former order gave them zeros, under a branch per load (a load followed by a select becomes that branch again in code generation), and
+// behind a branch the compiler no longer knows how many loads are in flight: it waits for ALL of them at the next use of a table.  So the
+// early order loads unconditionally: those lanes transform a copy of the first column, in their own slots of the exchange buffer.
+__device__ __forceinline__ cplx load_or_zero(bool active, const cplx *p)
+{
+#if OCN_FFT_EARLY_LOADS
+    (void)active;
+    return cplx{p->x, p->y};
+#else
+    return active ? *p : cplx{0, 0};
+#endif
+}
+
 // MI355X dispatches consecutive workgroup ids round-robin over its 8 XCDs, each with its own L2.  Column blocks that are neighbours
 // in memory share the cache lines their runs straddle (rows of Nx/2 + 1 = 257 complex numbers or of haloed reals are never line-
 // aligned: a 128-byte run touches two lines, both shared with a neighbour), so with the plain mapping every such line is fetched into two
@@ -348,18 +396,58 @@ __global__ __launch_bounds__(CB *(N / 8), (colfft_split<N, CB, MODE> ? 6 : 1)) v
     xcd_block(a.xcd, lbx, lby);
     const int col0 = lbx * CB;
     const int batch = lby;
-    for (int j = tid; j < N; j += CB * T) W[j] = reinterpret_cast<const cplx *>(a.tw)[j];
+    constexpr bool EARLY = OCN_FFT_EARLY_LOADS != 0;
+    constexpr bool SOLVE = MODE == 2;  // the fused z pass divides by the eigenvalues (MODE 5, its cosine twin, keeps its order: below)
+    if constexpr (!EARLY)
+        for (int j = tid; j < N; j += CB * T) W[j] = reinterpret_cast<const cplx *>(a.tw)[j];
     const bool active = (col0 + c) < a.ncols;
     cplx *base = reinterpret_cast<cplx *>(a.data) + (long long)batch * a.batch_stride + (col0 + (active ? c : 0));
     cplx x[8];
     constexpr int HALF = (N + 1) / 2;
+    // EARLY, MODE 2: the eigenvalues are requested in front of the data (an inactive lane reads those of the block's first column and
+    // takes lxy = 1.0 as before), the eight factors -scale / λ are formed in tables_in() and wait in registers for the forward transform.
+    // (MODE 5 loads and divides between its transforms as before: its factors, kept across the forward transform and the cosine
+    //  twiddles, made colfft_kernel<512, 8, 5> 134 VGPRs instead of 112, one workgroup per CU instead of two.)
+    [[maybe_unused]] double lxv = 0.0, lyv = 0.0, lzv[8], sfac[8];
+    if constexpr (EARLY && SOLVE) {
+        const int cl = active ? col0 + c : col0;
+        lxv = a.lx[cl % a.inner];
+        lyv = a.ly[cl / a.inner];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) lzv[m] = a.lc[8 * t + m];
+    }
+    if constexpr (EARLY) OCN_ISSUE_LOADS_HERE();
+    // called once the data loads have been issued: the twiddles are requested behind them (requested in front, with the eigenvalues, the
+    // fused z pass took 0.483 ms instead of 0.465 and the inverse y pass lost what it gains) and go to LDS once everything has arrived;
+    // the barrier in front of their first use follows in every MODE
+    auto tables_in = [&]() __attribute__((always_inline)) {
+        if constexpr (EARLY) {
+            OCN_ISSUE_LOADS_HERE();
+            cplx twv[table_slots(N, CB * T)];
+            table_load<N, CB * T>(twv, a.tw, tid);
+            if constexpr (SOLVE) {
+                const double lxy = active ? lxv + lyv : 1.0;
+                const bool zero_col = a.zero_mode && (col0 + c == 0) && (batch == 0);
+#pragma unroll
+                for (int m = 0; m < 8; ++m) {
+                    const double lam = lxy + lzv[m];
+                    double s = -a.scale / lam;
+                    if (zero_col && 8 * t + m == 0) s = 0.0;  // position 0 is wavenumber 0
+                    asm volatile("" : "+v"(s));  // formed here, under the data loads, not where it is used
+                    sfac[m] = s;
+                }
+            }
+            table_store<N, CB * T>(twv, W, tid);
+        }
+    };
 
     if (MODE == 3 || MODE == 5) {
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             const int e = t + T * r, src = e < HALF ? 2 * e : 2 * (N - 1 - e) + 1;
-            x[r] = active ? base[(long long)src * a.col_stride] : cplx{0, 0};
+            x[r] = load_or_zero(active, base + (long long)src * a.col_stride);
         }
+        tables_in();
         fft_fwd_stages<N, CB>(x, A, W, c, t);
         __syncthreads();  // the exchange buffer is free: the spectrum by natural wavenumber
 #pragma unroll
@@ -402,10 +490,10 @@ __global__ __launch_bounds__(CB *(N / 8), (colfft_split<N, CB, MODE> ? 6 : 1)) v
     if (MODE == 4 || MODE == 5) {
         if (MODE == 4) {
 #pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const int k = t + T * r;
-                A[k * CB + c] = active ? base[(long long)k * a.col_stride] : cplx{0, 0};
-            }
+            for (int r = 0; r < 8; ++r) x[r] = load_or_zero(active, base + (long long)(t + T * r) * a.col_stride);
+            tables_in();
+#pragma unroll
+            for (int r = 0; r < 8; ++r) A[(t + T * r) * CB + c] = x[r];
             __syncthreads();
         }
         const cplx *wd = reinterpret_cast<const cplx *>(a.lc);
@@ -440,16 +528,24 @@ __global__ __launch_bounds__(CB *(N / 8), (colfft_split<N, CB, MODE> ? 6 : 1)) v
 
     if (MODE == 0 || MODE == 2) {
 #pragma unroll
-        for (int r = 0; r < 8; ++r) x[r] = active ? base[(long long)(t + T * r) * a.col_stride] : cplx{0, 0};
+        for (int r = 0; r < 8; ++r) x[r] = load_or_zero(active, base + (long long)(t + T * r) * a.col_stride);
+        tables_in();
         fft_fwd_stages<N, CB, SPLIT>(x, A, W, c, t);
         // x[m] is the spectrum at stored position p = 8 t + m
     } else {
 #pragma unroll
-        for (int m = 0; m < 8; ++m) x[m] = active ? base[(long long)(8 * t + m) * a.col_stride] : cplx{0, 0};
+        for (int m = 0; m < 8; ++m) x[m] = load_or_zero(active, base + (long long)(8 * t + m) * a.col_stride);
+        tables_in();
         __syncthreads();
     }
 
-    if (MODE == 2) {
+    if (MODE == 2 && EARLY) {
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            x[m].x *= sfac[m];
+            x[m].y *= sfac[m];
+        }
+    } else if (MODE == 2) {
         const int col = col0 + c;
         const double lxy = active ? a.lx[col % a.inner] + a.ly[col / a.inner] : 1.0;
         const bool zero_col = a.zero_mode && (col == 0) && (batch == 0);

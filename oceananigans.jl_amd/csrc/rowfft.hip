@@ -124,6 +124,35 @@ __device__ __forceinline__ void dif_fft(cplx *x, cplx *A, const cplx *W, int t)
         radix_last<T2, CONJ>(x);
     }
 }
+// The order of a workgroup's first memory requests (colfft.hip, OCN_FFT_EARLY_LOADS) in rowfft_c2r_kernel: the two tables are requested
+// back to back into registers, the rows' data right behind them, and the LDS stores of the tables follow while the data are on their way;
+// 0 restores the former order (each table load waited for on its own, the data requested after the tables' barrier).  Same values either
+// way.  rowfft_source_r2c_kernel keeps its order: with the tables requested early and stored behind its first group of velocity loads it
+// held 146 VGPRs instead of 133 and was no faster (0.812 against 0.805 ms at 512^3).
+#ifndef OCN_FFT_EARLY_LOADS
+#define OCN_FFT_EARLY_LOADS 1
+#endif
+// a table of NE complex numbers on its way from global memory to LDS, NT threads: table_load() requests, table_store() writes what arrived
+constexpr int table_slots(int NE, int NT) { return (NE + NT - 1) / NT; }  // per thread
+template <int NE, int NT>
+__device__ __forceinline__ void table_load(cplx *v, const double *table, int tid)
+{
+#pragma unroll
+    for (int q = 0; q < table_slots(NE, NT); ++q) {
+        const int j = tid + q * NT;
+        const cplx *e = reinterpret_cast<const cplx *>(table) + (j < NE ? j : 0);  // (unconditional: a load under a branch is waited for on its own)
+        v[q] = cplx{e->x, e->y};
+    }
+}
+template <int NE, int NT>
+__device__ __forceinline__ void table_store(const cplx *v, cplx *lds, int tid)
+{
+#pragma unroll
+    for (int q = 0; q < table_slots(NE, NT); ++q) {
+        const int j = tid + q * NT;
+        if (j < NE) lds[j] = cplx{v[q].x, v[q].y};
+    }
+}
 }  // namespace
 
 struct RowFFTArgs {
@@ -239,20 +268,40 @@ __global__ __launch_bounds__(RB *(M / 8)) void rowfft_c2r_kernel(RowFFTArgs a)
     __shared__ cplx W[M];
     __shared__ cplx WN[M + 1];
     const int tid = threadIdx.x, t = tid % T, rl = tid / T;
-    for (int j = tid; j < M; j += RB * T) W[j] = reinterpret_cast<const cplx *>(a.twM)[j];
-    for (int j = tid; j <= M; j += RB * T) WN[j] = reinterpret_cast<const cplx *>(a.twN)[j];
+    constexpr bool EARLY = OCN_FFT_EARLY_LOADS != 0;
+    cplx twv[table_slots(M, RB * T)], twnv[table_slots(M + 1, RB * T)];
+    if constexpr (EARLY) {
+        table_load<M, RB * T>(twv, a.twM, tid);
+        table_load<M + 1, RB * T>(twnv, a.twN, tid);
+        OCN_ISSUE_LOADS_HERE();
+    } else {
+        for (int j = tid; j < M; j += RB * T) W[j] = reinterpret_cast<const cplx *>(a.twM)[j];
+        for (int j = tid; j <= M; j += RB * T) WN[j] = reinterpret_cast<const cplx *>(a.twN)[j];
+    }
     const long long row = (long long)blockIdx.x * RB + rl;
     const bool active = row < a.nrows;
     const GridDev &g = a.g;
-    const int j = active ? (int)(row % g.Ny) + 1 : 1, k = active ? (int)(row / g.Ny) + 1 : 1;
     const cplx *in = reinterpret_cast<const cplx *>(a.spec) + (active ? row : 0) * (M + 1);
+    // EARLY: the 16 elements of the merge step are requested before the tables go to LDS (and (j, k) of the row, which only the stores
+    // need, are worked out behind the transform)
+    [[maybe_unused]] cplx xin[8], xmi[8];
+    if constexpr (EARLY) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            xin[r] = in[t + T * r];
+            xmi[r] = in[M - (t + T * r)];
+        }
+        OCN_ISSUE_LOADS_HERE();
+        table_store<M, RB * T>(twv, W, tid);
+        table_store<M + 1, RB * T>(twnv, WN, tid);
+    }
     __syncthreads();
     // merge step: Z[k] = (X[k] + conj X[M-k])/2 + i/2 e^{+2 pi i k/N} (X[k] - conj X[M-k]),  k = t + T r
     cplx x[8];
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         const int kk = t + T * r;
-        const cplx xk = in[kk], xm = cconj(in[M - kk]);
+        const cplx xk = EARLY ? xin[r] : in[kk], xm = cconj(EARLY ? xmi[r] : in[M - kk]);
         const cplx s = cadd(xk, xm), d = csub(xk, xm);
         const cplx wd = cmul(cconj(WN[kk]), d);
         x[r] = cplx{0.5 * (s.x - wd.y), 0.5 * (s.y + wd.x)};  // s/2 + (i/2) wd
@@ -263,6 +312,7 @@ __global__ __launch_bounds__(RB *(M / 8)) void rowfft_c2r_kernel(RowFFTArgs a)
     for (int m = 0; m < 8; ++m) A[rl][stage_index<M>(8 * t + m)] = x[m];
     __syncthreads();
     if (active) {
+        const int j = (int)(row % g.Ny) + 1, k = (int)(row / g.Ny) + 1;
         const Lay L = make_lay(g, OCN_LOC_CCC);
         double *prow = a.p + at(L, 1, j, k);
         const int Nx = 2 * M;
