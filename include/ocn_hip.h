@@ -1044,6 +1044,8 @@ int ocn_model_driver_create_distributed(ocn_model_driver_t *driver, const ocn_gr
 #define OCN_OP_SUB 7
 #define OCN_OP_MUL 8
 #define OCN_OP_DIV 9
+#define OCN_OP_MIN 10     /* Julia's min(a, b): a NaN in either operand propagates; min(-0.0, +0.0) = -0.0 in either operand order */
+#define OCN_OP_MAX 11     /* Julia's max(a, b): a NaN in either operand propagates; max(-0.0, +0.0) = +0.0 in either operand order */
 typedef struct ocn_op_instruction {
     int32_t opcode;
     int32_t a, b;        /* operands of the unary (a) and binary (a, b) opcodes: indices of EARLIER instructions */
@@ -1067,6 +1069,14 @@ typedef struct ocn_op_program {
  *
  * compute!(Field(operation)): `out` is the parent array of a field at program->loc; its interior is written, its halos are not. */
 int ocn_op_compute(const ocn_grid *grid, const ocn_op_program *program, double *out, void *stream);
+/* A forcing that is a function of the model's fields (ContinuousForcing with field_dependencies, continuous_forcing.jl:109-142), lowered
+ * to a program: G[i, j, k] += value of the program.  `G` is the parent array of the tendency of a field at program->loc.  The index space
+ * is that of a tendency: the interior of the location as ocn_op_compute defines it WITHOUT the faces that lie on a wall -- along a
+ * Face & Bounded direction the faces 2 .. N of the N + 1 (the one face where N = 1), the cells at which the *_forced tendency entry
+ * points add a struct ocn_forcing.  LOAD / SPACING offsets are validated for those cells.  Halos and wall faces of G are untouched; a
+ * cell's G is read once and written once.  OCN_ERR_INVALID_ARGUMENT also if G is NULL or one of program->fields[].
+ * No atomics, no allocation, no synchronisation. */
+int ocn_op_accumulate(const ocn_grid *grid, const ocn_op_program *program, double *G, void *stream);
 /* A boundary function with field dependencies (ContinuousBoundaryFunction, continuous_boundary_function.jl:124-157), lowered to a program:
  * evaluated at every point (a1, a2) of one boundary plane -- side 0..5 = west, east, south, north, bottom, top, which must lie on a Bounded
  * direction; the two tangential directions in the order x, y, z, N points along each whatever the location -- with the boundary-normal

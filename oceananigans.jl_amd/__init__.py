@@ -18,7 +18,7 @@ from .models import (NonhydrostaticModel, QuasiAdamsBashforth2TimeStepper, Runge
                      cache_previous_tendencies, calculate_pressure_correction, compute_auxiliaries, compute_diffusivities,
                      compute_tendencies, flush_tendencies, RK3Driver, ModelRK3Driver, implicit_step, add_vertically_implicit_explicit_fluxes,
                      pressure_correct_velocities, rk3_substep, set, solve_for_pressure, time_step, update_hydrostatic_pressure,
-                     update_state, compute_boundary_functions, compute_boundary_tendency_contributions)
+                     update_state, compute_boundary_functions, compute_boundary_tendency_contributions, add_forcing_programs)
 from .output import (AdvectiveCFL, DiffusiveCFL, NaNChecker, TimeStepWizard, cell_advection_timescale, cell_diffusion_timescale, hasnan, set_from_checkpoint,
                      write_checkpoint)
 from .physics import (HorizontalDivergenceFormulation, HorizontalFormulation, HorizontalScalarBiharmonicDiffusivity, ScalarBiharmonicDiffusivity,
@@ -31,11 +31,13 @@ from .physics import (AnisotropicMinimumDissipation, ConvectiveAdjustmentVertica
 from .stokes import StokesDrift, UniformStokesDrift
 from .particles import (LagrangianParticles, advect_lagrangian_particles, step_lagrangian_particles,
                         update_lagrangian_particle_properties)
-from .forcings import AdvectiveForcing, Forcing, GaussianMask, LinearTarget, Relaxation
-from . import boundary_functions
+from .forcings import AdvectiveForcing, ContinuousForcing, Forcing, GaussianMask, LinearTarget, Relaxation
+from . import boundary_functions, forcing_programs
+from .forcing_programs import ForcingProgram, ProgramForcing
 from .boundary_functions import BoundaryFunction, BoundaryProgram
 from .operations import (AbstractOperation, Average, BinaryOperation, ComputedField, CumulativeIntegral, Derivative, Integral,
-                         KernelFunctionOperation, UnaryOperation, abs, at, compute, ddx, ddy, ddz, exp, log, lower, sqrt, tanh)
+                         KernelFunctionOperation, UnaryOperation, abs, at, compute, cos, ddx, ddy, ddz, exp, log, lower, maximum, minimum, sin, sqrt,
+                         tanh)
 from .solvers import (BatchedTridiagonalSolver, FFTBasedPoissonSolver, FourierTridiagonalPoissonSolver, XDirection, YDirection, ZDirection,
                       nonhydrostatic_pressure_solver, solve, stretched_direction)
 

@@ -106,7 +106,7 @@ class CParticleGeometry(C.Structure):
 
 
 OP_MAX_INSTRUCTIONS, OP_MAX_REGISTERS, OP_MAX_FIELDS = 128, 16, 8
-OP_LOAD, OP_CONST, OP_SPACING, OP_NEG, OP_ABS, OP_SQRT, OP_ADD, OP_SUB, OP_MUL, OP_DIV = range(10)
+OP_LOAD, OP_CONST, OP_SPACING, OP_NEG, OP_ABS, OP_SQRT, OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_MIN, OP_MAX = range(12)
 SPACING_DX, SPACING_DY, SPACING_DZC, SPACING_DZF = range(4)
 
 
@@ -264,6 +264,7 @@ _SIGS = {
     "ocn_advect_particles": [C.POINTER(CGrid), C.POINTER(CParticleGeometry), C.c_int64, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _dbl, _i32, C.POINTER(_vp),
                              C.POINTER(_i32), C.POINTER(_vp), _vp],
     "ocn_op_compute": [C.POINTER(CGrid), C.POINTER(COpProgram), _vp, _vp],
+    "ocn_op_accumulate": [C.POINTER(CGrid), C.POINTER(COpProgram), _vp, _vp],
     "ocn_op_compute_boundary": [C.POINTER(CGrid), C.POINTER(COpProgram), _i32, _vp, _vp],
     "ocn_op_reduce_workspace": [C.POINTER(CGrid), _i32, _i32, C.POINTER(C.c_int64)],
     "ocn_op_reduce": [C.POINTER(CGrid), C.POINTER(COpProgram), _i32, _dbl, _vp, C.c_int64, _vp, _vp],

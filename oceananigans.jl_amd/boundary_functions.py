@@ -52,6 +52,9 @@ class Coordinate(AbstractOperation):
         self.location = tuple((Face if self.face else Center) if e == d else None for e in range(3))  # (.loc: the mask of it)
         self._data = None
 
+    def reads(self):
+        return False, frozenset((self.d,)), False
+
     def nodes(self):
         return np.ascontiguousarray(self.grid.nodes_1d(self.d, self.face, with_halos=True), dtype=np.float64)
 
@@ -69,6 +72,9 @@ class Time(AbstractOperation):
     def __init__(self, grid):
         self.grid = grid
 
+    def reads(self):
+        return False, frozenset(), True
+
 
 class Dependency(AbstractOperation):
     """ℑ(i, j, I, grid, field): a model field interpolated to the boundary location -- along the tangential directions only, the normal
@@ -81,7 +87,8 @@ class Dependency(AbstractOperation):
 
 class BoundaryProgram(Program):
     """The program of a boundary function: its index space is the boundary plane -- N points along each tangential direction (the extents
-    of ocn_bc.values) and the one index I along the normal.  `time_index`: the instruction that holds the time, or None."""
+    of ocn_bc.values) and the one index I along the normal.  `time_index`: the instruction that holds the time, or None.
+    (forcing_programs.ForcingProgram is this class over another index_range: the cells of a tendency.)"""
 
     def __init__(self, grid, loc, side, time=0.0):
         super().__init__(grid, loc)
@@ -117,7 +124,7 @@ class BoundaryProgram(Program):
         return tuple(hi - lo + 1 for lo, hi in self.index_range())
 
     def _check_halos(self):
-        """every point of the PLANE, shifted, lies in the parent array of the field it reads (the check the library repeats)"""
+        """every point of the index range (the PLANE), shifted, lies in the parent array of the field it reads (the check the library repeats)"""
         g = self.grid
         H, rng = (g.Hx, g.Hy, g.Hz), self.index_range()
         for i in self.loads:
@@ -128,12 +135,12 @@ class BoundaryProgram(Program):
                 if (reduced >> d) & 1:
                     continue
                 if H[d] + rng[d][0] + i["off"][d] < 0 or H[d] + rng[d][1] + i["off"][d] > ext[d] - 1:
-                    raise ValueError(f"the boundary function reads {i['off'][d]:+d} cells along {'xyz'[d]}: further than the grid's halo ({H[d]}) holds")
+                    raise ValueError(f"the traced function reads {i['off'][d]:+d} cells along {'xyz'[d]}: further than the grid's halo ({H[d]}) holds")
         for i in self.instructions:
             if i["op"] == _lib.OP_SPACING and i["field"] >= _lib.SPACING_DZC and g._dzc_host is not None:
                 dk = i["off"][2]
                 if H[2] + rng[2][0] + dk < 0 or H[2] + rng[2][1] + dk > g.Nz + 2 * H[2] - 1:
-                    raise ValueError(f"the boundary function reads the z spacing {dk:+d} cells away: further than the grid's halo ({H[2]})")
+                    raise ValueError(f"the traced function reads the z spacing {dk:+d} cells away: further than the grid's halo ({H[2]})")
 
 
 def validate_dependencies(field_dependencies, model_field_names):

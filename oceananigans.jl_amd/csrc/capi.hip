@@ -741,6 +741,11 @@ int ocn_op_compute(const ocn_grid *grid, const ocn_op_program *program, double *
     return op_compute(grid, program, out, as_stream(stream));
 }
 
+int ocn_op_accumulate(const ocn_grid *grid, const ocn_op_program *program, double *G, void *stream)
+{
+    return op_accumulate(grid, program, G, as_stream(stream));
+}
+
 int ocn_op_compute_boundary(const ocn_grid *grid, const ocn_op_program *program, int32_t side, double *values, void *stream)
 {
     return op_compute_boundary(grid, program, side, values, as_stream(stream));

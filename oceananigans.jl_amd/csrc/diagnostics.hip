@@ -22,6 +22,11 @@
 // Boundary functions (ContinuousBoundaryFunction with field_dependencies, src/BoundaryConditions/continuous_boundary_function.jl:124-157):
 // the same interpreter on one boundary plane of the grid, the boundary-normal index fixed at domain_boundary_indices' I; the result goes
 // to the array a flux condition's ocn_bc.values points to, which the apply_flux_bcs* kernels read as they read any array-valued condition.
+//
+// Forcing functions of the model's fields (ContinuousForcing with field_dependencies, src/Forcings/continuous_forcing.jl:109-142): the same
+// interpreter over the cells a tendency is computed at (the interior without the faces on a wall), its value ADDED to the tendency array,
+// which is read once and written once per cell.  MIN / MAX carry Julia's NaN and signed-zero rules; the instruction set stays IEEE-only
+// (what is transcendental is folded by the host into constants and vectors: forcing_programs.py).
 #include <algorithm>
 #include <cmath>
 
@@ -63,6 +68,22 @@ struct OpReduceGeom {
     long long Ek;      // njk * nkk
     long long E;       // output elements: Ek, times nx where x is kept
 };
+
+// Julia's min / max (Base.min, Base.max of two Float64), as comparisons and selects: a NaN in either operand propagates (NaN compares
+// false, so the first select yields b, and a NaN in a is put back by the last one) and of the two zeros, which compare equal, max takes
+// +0.0 and min -0.0 in either operand order.  Not fmin / fmax: they drop a NaN.
+__device__ __forceinline__ double julia_max(double a, double b)
+{
+    double r = a > b ? a : b;
+    r = a == b ? (__builtin_signbit(a) ? b : a) : r;
+    return a != a ? a : r;
+}
+__device__ __forceinline__ double julia_min(double a, double b)
+{
+    double r = a < b ? a : b;
+    r = a == b ? (__builtin_signbit(a) ? a : b) : r;
+    return a != a ? a : r;
+}
 
 // The program at OP_CELLS 0-based interior cells (i[c], j[c], k[c]) of the tree's location at once: one fetch and decode per instruction
 // serves both cells, and their two dependency chains (load or LDS read -> operation -> LDS write) overlap.  R = this lane's column of the
@@ -120,9 +141,19 @@ __device__ __forceinline__ void op_eval(const OpProgramDev &P, const GridDev &g,
 #pragma unroll
             for (int c = 0; c < OP_CELLS; ++c) v[c] = A[c * OP_BLOCK] * B[c * OP_BLOCK];
             break;
-        default:  // OCN_OP_DIV (the host admits no other opcode)
+        case OCN_OP_DIV:
 #pragma unroll
             for (int c = 0; c < OP_CELLS; ++c) v[c] = A[c * OP_BLOCK] / B[c * OP_BLOCK];
+            break;
+        case OCN_OP_MIN:
+#pragma unroll
+            for (int c = 0; c < OP_CELLS; ++c) v[c] = julia_min(A[c * OP_BLOCK], B[c * OP_BLOCK]);
+            break;
+        case OCN_OP_MAX:
+#pragma unroll
+            for (int c = 0; c < OP_CELLS; ++c) v[c] = julia_max(A[c * OP_BLOCK], B[c * OP_BLOCK]);
+            break;
+        default:  // (the host admits no other opcode)
             break;
         }
         double *D = R + I.dst * (OP_CELLS * OP_BLOCK);
@@ -143,6 +174,26 @@ __global__ __launch_bounds__(OP_BLOCK) void op_compute_kernel(GridDev g, OpProgr
     op_eval(P, g, regs + threadIdx.y * 64 + threadIdx.x, ii, jj, kk, v);
     out[O.o + i + O.s2 * jj[0] + O.s3 * k] = v[0];
     if (two) out[O.o + i + O.s2 * jj[1] + O.s3 * k] = v[1];
+}
+
+// G += the program, over the cells a tendency is computed at: the box of 0-based indices (i0.., j0.., k0..) of extents nx, ny and the
+// launch's z blocks.  The same tile as op_compute_kernel; a cell's G is read once, before the evaluation (the load is in flight under it),
+// and written once.  G is none of the program's fields (the host checks), so no cell reads what another one writes.
+__global__ __launch_bounds__(OP_BLOCK) void op_accumulate_kernel(GridDev g, OpProgramDev P, int i0, int j0, int k0, int nx, int ny,
+                                                                 double *__restrict__ G, OpOut O)
+{
+    extern __shared__ double regs[];  // n_registers x OP_CELLS x OP_BLOCK
+    const int a = blockIdx.x * 64 + threadIdx.x, b = blockIdx.y * 8 + threadIdx.y, k = k0 + blockIdx.z;
+    if (a >= nx || b >= ny) return;
+    const bool two = b + 4 < ny;  // (a missing second cell repeats the first: always in bounds, never stored)
+    const int i = i0 + a;
+    const int ii[OP_CELLS] = {i, i}, jj[OP_CELLS] = {j0 + b, two ? j0 + b + 4 : j0 + b}, kk[OP_CELLS] = {k, k};
+    const long long o0 = O.o + i + O.s2 * jj[0] + O.s3 * k, o1 = O.o + i + O.s2 * jj[1] + O.s3 * k;
+    const double G0 = G[o0], G1 = G[o1];
+    double v[OP_CELLS];
+    op_eval(P, g, regs + threadIdx.y * 64 + threadIdx.x, ii, jj, kk, v);
+    G[o0] = G0 + v[0];
+    if (two) G[o1] = G1 + v[1];
 }
 
 // One boundary plane: the point (a1, a2) of the two tangential directions (first one fastest, as ocn_bc.values is indexed), the normal index
@@ -272,6 +323,17 @@ static int op_plane(OpSpace &S, int side, const char *who)
     S.lo[dn] = S.hi[dn] = (side & 1) ? S.N[dn] - 1 : 0;
     return OCN_SUCCESS;
 }
+// The index space of a tendency: the interior without the faces on a wall -- along a Face & Bounded direction the faces 2 .. N of the
+// N + 1 (periphery_offset, kernel_launching.jl:113-114; the one face of N = 1 stays), as the tendency entry points run (r.ou, r.ov, r.ow)
+static void op_tendency_cells(OpSpace &S, int loc)
+{
+    for (int d = 0; d < 3; ++d) {
+        if (!(((loc >> d) & 1) && S.topo[d] == OCN_BOUNDED)) continue;
+        S.lo[d] = S.N[d] > 1 ? 1 : 0;
+        S.hi[d] = S.N[d] - 1;
+        S.n[d] = S.hi[d] - S.lo[d] + 1;
+    }
+}
 // parent layout of a field at `loc` reduced along the directions of `reduced`
 static void op_layout(const OpSpace &S, int loc, int reduced, long long ext[3], long long stride[3], long long &o)
 {
@@ -281,8 +343,10 @@ static void op_layout(const OpSpace &S, int loc, int reduced, long long ext[3], 
     for (int d = 0; d < 3; ++d) o += ((reduced >> d) & 1) ? 0 : S.H[d] * stride[d];
 }
 
-// side == nullptr: the program runs over the interior of its location; otherwise over the boundary plane *side
-static int op_validate(const ocn_grid *grid, const ocn_op_program *p, const char *who, OpSpace &S, OpProgramDev &D, const int *side = nullptr)
+// side == nullptr: the program runs over the interior of its location (tendency_cells: without the faces on a wall); otherwise over the
+// boundary plane *side
+static int op_validate(const ocn_grid *grid, const ocn_op_program *p, const char *who, OpSpace &S, OpProgramDev &D, const int *side = nullptr,
+                       bool tendency_cells = false)
 {
     OCN_REQUIRE(grid && p, "%s: null grid or program", who);
     int st = op_space(grid, p->loc, who, S);
@@ -291,6 +355,7 @@ static int op_validate(const ocn_grid *grid, const ocn_op_program *p, const char
         st = op_plane(S, *side, who);
         if (st != OCN_SUCCESS) return st;
     }
+    if (tendency_cells) op_tendency_cells(S, p->loc);
     OCN_REQUIRE(p->n_instructions >= 1 && p->n_instructions <= OCN_OP_MAX_INSTRUCTIONS, "%s: %d instructions outside 1..%d", who,
                 p->n_instructions, OCN_OP_MAX_INSTRUCTIONS);
     OCN_REQUIRE(p->n_registers >= 1 && p->n_registers <= OCN_OP_MAX_REGISTERS, "%s: %d registers outside 1..%d", who, p->n_registers,
@@ -317,7 +382,7 @@ static int op_validate(const ocn_grid *grid, const ocn_op_program *p, const char
     for (int q = 0; q < p->n_instructions; ++q) {
         const ocn_op_instruction &I = p->ins[q];
         OpInsDev &J = D.ins[q];
-        OCN_REQUIRE(I.opcode >= OCN_OP_LOAD && I.opcode <= OCN_OP_DIV, "%s: instruction %d: unknown opcode %d", who, q, I.opcode);
+        OCN_REQUIRE(I.opcode >= OCN_OP_LOAD && I.opcode <= OCN_OP_MAX, "%s: instruction %d: unknown opcode %d", who, q, I.opcode);
         OCN_REQUIRE(I.reg >= 0 && I.reg < p->n_registers, "%s: instruction %d: register %d outside 0..%d", who, q, I.reg, p->n_registers - 1);
         J.op = (unsigned char)I.opcode;
         J.dst = (unsigned char)I.reg;
@@ -411,6 +476,23 @@ int op_compute(const ocn_grid *grid, const ocn_op_program *p, double *out, hipSt
     const dim3 block(64, 4, 1), nb((S.n[0] + 63) / 64, (S.n[1] + 7) / 8, S.n[2]);
     OCN_REQUIRE(nb.y <= 65535u && nb.z <= 65535u, "ocn_op_compute: grid too large for one launch");
     hipLaunchKernelGGL(op_compute_kernel, nb, block, op_lds_bytes(p), stream, to_dev(*grid), D, S.n[0], S.n[1], out, O);
+    OCN_CHECK_HIP(hipGetLastError());
+    return OCN_SUCCESS;
+}
+
+int op_accumulate(const ocn_grid *grid, const ocn_op_program *p, double *G, hipStream_t stream)
+{
+    OpSpace S;
+    OpProgramDev D;
+    int st = op_validate(grid, p, "ocn_op_accumulate", S, D, nullptr, true);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(G, "ocn_op_accumulate: null tendency pointer");
+    for (int f = 0; f < p->n_fields; ++f)
+        OCN_REQUIRE(G != p->fields[f], "ocn_op_accumulate: the tendency array is field %d of the program (cells would read what others write)", f);
+    const OpOut O = op_out(S, p->loc, 0);
+    const dim3 block(64, 4, 1), nb((S.n[0] + 63) / 64, (S.n[1] + 7) / 8, S.n[2]);
+    OCN_REQUIRE(nb.y <= 65535u && nb.z <= 65535u, "ocn_op_accumulate: grid too large for one launch");
+    hipLaunchKernelGGL(op_accumulate_kernel, nb, block, op_lds_bytes(p), stream, to_dev(*grid), D, S.lo[0], S.lo[1], S.lo[2], S.n[0], S.n[1], G, O);
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
 }

@@ -72,6 +72,7 @@ int launch_particles(const ocn_grid *grid, const ocn_particle_geometry *geom, lo
                      const double *const *tracked_fields, const int32_t *tracked_locs, double *const *tracked_out, hipStream_t stream);
 // diagnostics.hip: an operation tree lowered to a straight-line program, evaluated per cell; both validate the whole program first
 int op_compute(const ocn_grid *grid, const ocn_op_program *program, double *out, hipStream_t stream);
+int op_accumulate(const ocn_grid *grid, const ocn_op_program *program, double *G, hipStream_t stream);
 int op_compute_boundary(const ocn_grid *grid, const ocn_op_program *program, int side, double *values, hipStream_t stream);
 int op_reduce_workspace(const ocn_grid *grid, int loc, int dims, long long *n_doubles);
 int op_reduce(const ocn_grid *grid, const ocn_op_program *program, int dims, double divisor, double *workspace, long long workspace_doubles,

@@ -4,6 +4,8 @@
         -> Relaxation(rate, mask=None, target=None), GaussianMask("z", center=, width=), LinearTarget("z", intercept=, gradient=)
     Forcing(func; parameters)                                                                                    forcing.jl, continuous_forcing.jl
         -> Forcing(func, parameters=None, steady=None)
+    ContinuousForcing(func; parameters, field_dependencies)                                                      continuous_forcing.jl:109-142
+        -> ContinuousForcing(func, parameters=None, field_dependencies=()): traced once, evaluated on the device (forcing_programs.py)
     an array on the field's grid (regularize_forcing(array::AbstractArray, ...)), a tuple / list of up to four of these (MultipleForcings)
 
 Python has no type parameters, so the direction of a mask / target is its first argument.  A bare Python function is NOT a forcing value
@@ -152,7 +154,8 @@ class Forcing:
     def __init__(self, func, parameters=None, steady=None, field_dependencies=(), discrete_form=False):
         if field_dependencies not in ((), None, []):
             raise NotImplementedError("forcing: Forcing(func, field_dependencies=...) is not implemented: the host samples the function, "
-                                      "it cannot read the fields cell by cell (see DESIGN.md §10)")
+                                      "it cannot read the fields cell by cell; ContinuousForcing(func, field_dependencies=...) traces the "
+                                      "function and evaluates it on the device (see DESIGN.md §5.2d')")
         if discrete_form:
             raise NotImplementedError("forcing: Forcing(func, discrete_form=True) is not implemented (see DESIGN.md §10)")
         if not callable(func):
@@ -165,6 +168,39 @@ class Forcing:
 
     def __repr__(self):
         return f"{self.summary()}\n├── func: {getattr(self.func, '__name__', type(self.func).__name__)}\n└── parameters: {self.parameters!r}"
+
+
+class ContinuousForcing:
+    """ContinuousForcing(func, parameters=None, field_dependencies=()): func(X..., t, deps..., [parameters]) -- the coordinates of the forced
+    field's own location (Flat directions omitted), the time, the dependencies in the order given, interpolated to that location -- is
+    called ONCE, when the model is built, with symbolic operands; the tree it returns is evaluated on the device (forcing_programs.py).
+    field_dependencies: a name or a tuple of names of velocities and tracers; () gives the traced, device-evaluated form of Forcing(func)."""
+
+    def __init__(self, func, parameters=None, field_dependencies=(), discrete_form=False):
+        if discrete_form:
+            raise NotImplementedError("forcing: ContinuousForcing(func, discrete_form=True) is not implemented: a function of (i, j, k, grid, "
+                                      "clock, fields) cannot be traced (see DESIGN.md §10)")
+        if not callable(func):
+            raise TypeError("ContinuousForcing(func, ...): func must be callable; an array is a forcing value by itself")
+        if field_dependencies is None:
+            field_dependencies = ()
+        if isinstance(field_dependencies, str):
+            field_dependencies = (field_dependencies,)
+        field_dependencies = tuple(field_dependencies)
+        if not all(isinstance(n, str) for n in field_dependencies):
+            raise TypeError("ContinuousForcing: field_dependencies is a field name or a tuple of field names")
+        self.func, self.parameters, self.field_dependencies = func, parameters, field_dependencies
+
+    def summary(self):
+        return f"ContinuousForcing{{{'Nothing' if self.parameters is None else type(self.parameters).__name__}}}"
+
+    def __repr__(self):
+        return (f"{self.summary()}\n├── func: {getattr(self.func, '__name__', type(self.func).__name__)}\n├── parameters: {self.parameters!r}\n"
+                f"└── field dependencies: {self.field_dependencies!r}")
+
+
+# names a forcing function may not depend on: the model computes them, they are no prognostic fields
+_AUXILIARY_FIELDS = ("νₑ", "nu_e", "κₑ", "kappa_e", "pNHS", "pHY′", "pHY")
 
 
 class AdvectiveForcing:
@@ -205,7 +241,15 @@ def validate_forcing(forcing, grid, field_names):
         shape = interior_shape(grid, field_location(name))
         checked = []
         for term in terms:
-            if isinstance(term, (Relaxation, Forcing)):
+            if isinstance(term, ContinuousForcing):
+                for dep in term.field_dependencies:
+                    if dep in _AUXILIARY_FIELDS and dep not in field_names:
+                        raise NotImplementedError(f"forcing of {name}: a dependency on the diffusivity / auxiliary field {dep!r} is not "
+                                                  "implemented: the dependencies are velocities and tracers (see DESIGN.md §10)")
+                from .boundary_functions import validate_dependencies
+                validate_dependencies(term.field_dependencies, tuple(field_names))
+                checked.append(term)
+            elif isinstance(term, (Relaxation, Forcing)):
                 if isinstance(term, Relaxation):
                     for what, a in (("mask", term.mask), ("target", term.target)):
                         if isinstance(a, np.ndarray) and a.shape != shape:
@@ -223,7 +267,7 @@ def validate_forcing(forcing, grid, field_names):
                     a = np.asarray(term, dtype=np.float64)
                 except (TypeError, ValueError):
                     raise NotImplementedError(f"forcing of {name}: unsupported forcing {type(term).__name__}; use an array, Relaxation(...), "
-                                              "Forcing(func) or a tuple of them") from None
+                                              "Forcing(func), ContinuousForcing(func, ...) or a tuple of them") from None
                 if a.shape != shape:
                     raise ValueError(f"forcing of {name}: array shape {a.shape} != interior shape {shape}")
                 checked.append(a)
@@ -289,6 +333,11 @@ def sample_term(term, grid, loc, t=0.0):
     elif g is not None:
         out["target_dim"], out["target"] = 3, _evaluate(g, _node_args(grid, loc) + [t], shape)
     return out
+
+
+def has_program(terms):
+    """a ContinuousForcing among the terms: all of them are then lowered into one program (forcing_programs.py)"""
+    return any(isinstance(t, ContinuousForcing) for t in terms)
 
 
 def is_steady(term):

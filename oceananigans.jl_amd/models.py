@@ -10,7 +10,7 @@ Mirrors, call for call:
   time_step!(model::QuasiAdamsBashforth2, Δt)                     src/TimeSteppers/quasi_adams_bashforth_2.jl:74-115
   cache_previous_tendencies!                                      src/TimeSteppers/store_tendencies.jl:12-22
 Julia's `f!` names are spelled `f` here.  background_fields is `nothing`; forcing is a dict of arrays, Relaxation(...) and Forcing(func)
-(forcings.py); stokes_drift is UniformStokesDrift (stokes.py); particles is LagrangianParticles (particles.py: stepped after every
+(forcings.py) and of ContinuousForcing(func, field_dependencies=...), traced at construction and added on the device (forcing_programs.py); stokes_drift is UniformStokesDrift (stokes.py); particles is LagrangianParticles (particles.py: stepped after every
 update_state! of a stage, as step_lagrangian_particles! in runge_kutta_3.jl:111, 127, 148 and quasi_adams_bashforth_2.jl:108); advection is WENO()
 or Centered(); coriolis = FPlane, closure = ScalarDiffusivity (explicit or vertically implicit) / AnisotropicMinimumDissipation / Smagorinsky(Lilly), buoyancy = BuoyancyTracer / SeawaterBuoyancy and bottom /
 top Flux / Value / Gradient boundary conditions are the SURVEY §8(f) rank-1 terms (physics.py); flux conditions that are functions of the
@@ -36,7 +36,8 @@ from .fields import CenterField, Field, XFaceField, YFaceField, ZFaceField, fill
 from .grids import Bounded, Flat, require_regular_xy
 from .solvers import nonhydrostatic_pressure_solver
 from .stokes import DeviceStokesDrift, UniformStokesDrift
-from .forcings import DeviceForcing, field_location, validate_forcing
+from .forcings import DeviceForcing, field_location, has_program, validate_forcing
+from .forcing_programs import ProgramForcing
 from .particles import LagrangianParticles, step_lagrangian_particles
 from .boundary_functions import BoundaryFunction, validate_dependencies
 
@@ -269,8 +270,9 @@ class NonhydrostaticModel:
         self._stokes = DeviceStokesDrift(stokes_drift, grid) if stokes_drift is not None else None
         # the sampled forcing of every forced field (struct ocn_forcing + its device vectors / arrays), in the order of prognostic_fields()
         self.forcing = forcing_terms
-        self._forcing = [DeviceForcing(forcing_terms[n], grid, field_location(n)) if n in forcing_terms else None
-                         for n in ("u", "v", "w") + tracers]
+        # (a field with a ContinuousForcing among its terms has a program instead, below: its entry here is NULL)
+        self._forcing = [DeviceForcing(forcing_terms[n], grid, field_location(n)) if n in forcing_terms and not has_program(forcing_terms[n])
+                         else None for n in ("u", "v", "w") + tracers]
         # (the structs never change: the references are taken once; entries of fields without forcing are NULL, u / v / w as one array)
         self._forcing_refs = [None if f is None else f.ref for f in self._forcing]
         self._momentum_forcing = _lib.forcing_array(self._forcing_refs[:3])
@@ -282,6 +284,10 @@ class NonhydrostaticModel:
         model_fields = dict(zip(("u", "v", "w") + tracers, self.prognostic_fields()))
         self._boundary_functions = [BoundaryFunction(condition, grid, f.loc, side, model_fields, self.clock.time)
                                     for name, f in model_fields.items() if name in bcs for side, condition in bcs[name].field_dependent()]
+        # forcings with a ContinuousForcing: all terms of the field traced and lowered once, here, into one program (forcing_programs.py);
+        # compute_tendencies adds its value as the last interior addend, one ocn_op_accumulate per field
+        self._forcing_programs = [ProgramForcing(forcing_terms[n], grid, n, model_fields, self.clock.time)
+                                  if n in forcing_terms and has_program(forcing_terms[n]) else None for n in model_fields]
         self._terms = self._make_terms()
         # vertically implicit closure: every other term comes from the existing entry points, called with a copy of the terms whose closure
         # is 0; the explicit part of the closure term is added by its own kernel and the implicit part follows every substep (implicit_step)
@@ -320,6 +326,8 @@ class NonhydrostaticModel:
         if self._implicit:  # the column solves sit between a substep and the projection: the reference's launch sequence
             self.fuse_stage_boundaries = False
         if self._boundary_functions:  # evaluated between the halo fill and the tendencies of every update_state!: the reference's sequence
+            self.fuse_stage_boundaries = False
+        if any(p is not None for p in self._forcing_programs):  # read filled halos between update_state! and the tendencies, as those do
             self.fuse_stage_boundaries = False
         if not xy_periodic:
             if hasattr(grid.architecture, "partition") and not (
@@ -575,6 +583,7 @@ def compute_tendencies_(model, rng=None, boundary_contributions=True):
                       c.ptr, Gn[3 + n].ptr, r, s)
         if implicit:
             add_vertically_implicit_explicit_fluxes(model, r)
+        add_forcing_programs(model)
         if boundary_contributions:
             compute_boundary_tendency_contributions(model)
         return
@@ -582,6 +591,15 @@ def compute_tendencies_(model, rng=None, boundary_contributions=True):
               Gn[2].ptr, r, s)
     for n, c in enumerate(model.tracers):
         _lib.call("ocn_compute_tracer_tendency", g.cref, model.u.ptr, model.v.ptr, model.w.ptr, c.ptr, Gn[3 + n].ptr, r, s)
+
+
+def add_forcing_programs(model):
+    """The forcings that are programs (ContinuousForcing, forcing_programs.py), at clock.time: the last interior addend of the tendency
+    (nonhydrostatic_tendency_kernel_functions.jl:77, 137, 199, 258), before the boundary fluxes.  One launch per forced field; every RK3
+    stage and QAB2 come through here."""
+    for G, p in zip(model.timestepper._Gn, getattr(model, "_forcing_programs", ())):
+        if p is not None:
+            p.accumulate(G, model.clock.time)
 
 
 def add_vertically_implicit_explicit_fluxes(model, rng=None):
@@ -953,6 +971,9 @@ class RK3Driver:
 
     def __init__(self, model, own_solver=False, defer_correction=None):
         require_regular_xy(model.grid, "RK3Driver")
+        if any(p is not None for p in getattr(model, "_forcing_programs", ())):
+            raise NotImplementedError("RK3Driver: a model with a ContinuousForcing needs the Python host (time_step(model, dt)): the library's "
+                                      "time step does not evaluate forcing programs")
         if getattr(model, "_boundary_functions", None):
             raise NotImplementedError("RK3Driver: a model with boundary conditions that have field_dependencies needs the Python host "
                                       "(time_step(model, dt)): the library's time step does not evaluate them")
@@ -1021,6 +1042,9 @@ class ModelRK3Driver:
 
     def __init__(self, model, own_solver=False):
         require_regular_xy(model.grid, "ModelRK3Driver")
+        if any(p is not None for p in getattr(model, "_forcing_programs", ())):
+            raise NotImplementedError("ModelRK3Driver: a model with a ContinuousForcing needs the Python host (time_step(model, dt)): the library's "
+                                      "time step does not evaluate forcing programs")
         if getattr(model, "_boundary_functions", None):
             raise NotImplementedError("ModelRK3Driver: a model with boundary conditions that have field_dependencies needs the Python host "
                                       "(time_step(model, dt)): the library's time step does not evaluate them")

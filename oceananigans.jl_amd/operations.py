@@ -22,8 +22,11 @@ from .fields import Field, fill_halo_regions
 from .grids import Bounded, Center, Face, Flat, require_regular_xy
 
 _MODEL_LOCATIONS = (_lib.LOC_CCC, _lib.LOC_FCC, _lib.LOC_CFC, _lib.LOC_CCF)
-_OPCODE = {"+": _lib.OP_ADD, "-": _lib.OP_SUB, "*": _lib.OP_MUL, "/": _lib.OP_DIV, "neg": _lib.OP_NEG, "abs": _lib.OP_ABS, "sqrt": _lib.OP_SQRT}
-_REFUSED_UNARY = ("exp", "log", "log10", "sin", "cos", "tan", "sinh", "cosh", "tanh", "asin", "acos", "atan")
+_OPCODE = {"+": _lib.OP_ADD, "-": _lib.OP_SUB, "*": _lib.OP_MUL, "/": _lib.OP_DIV, "neg": _lib.OP_NEG, "abs": _lib.OP_ABS, "sqrt": _lib.OP_SQRT,
+           "min": _lib.OP_MIN, "max": _lib.OP_MAX}
+_REFUSED_UNARY = ("log10", "tan", "sinh", "cosh", "asin", "acos", "atan")
+# transcendentals the device never evaluates: accepted where the host can fold them (forcing_programs.py), each with its NumPy function
+HOST_FOLDED_UNARY = {"exp": np.exp, "log": np.log, "tanh": np.tanh, "sin": np.sin, "cos": np.cos}
 
 
 def location_of(mask, reduced=0):
@@ -49,7 +52,19 @@ def _location(x):
 
 class AbstractOperation:
     """A node of an operation tree: `grid`, `location`, and arithmetic that builds larger trees."""
-    __array_ufunc__ = None  # np.float64(2) * operation reaches __rmul__
+
+    def __array_ufunc__(self, ufunc, method, *inputs, **kwargs):
+        """np.exp(z), np.maximum(P, 0), np.float64(2) * operation: the NumPy ufuncs that have a node build that node, so a function body
+        written with `np.` traces unchanged; anything else is refused by NumPy (TypeError)"""
+        build = _UFUNC_NODES.get(ufunc.__name__)
+        if method != "__call__" or kwargs or build is None or not all(_is_fieldlike(x) or _is_number(x) for x in inputs):
+            return NotImplemented
+        return build(*inputs)
+
+    def reads(self):
+        """(reads a field, the coordinate directions read, reads the time): what decides whether the host can fold a sub-tree.  A node
+        that does not say is taken to read a field."""
+        return True, frozenset(), False
 
     @property
     def loc(self):
@@ -68,7 +83,8 @@ class AbstractOperation:
 
     def _no_branch(self, *other):
         raise TypeError("an operation has no truth value and no order: it is a tree that is evaluated on the device, cell by cell.  A function "
-                        "that is traced with symbolic operands (a boundary function with field_dependencies) cannot branch on them")
+                        "that is traced with symbolic operands (a boundary function with field_dependencies, a ContinuousForcing) cannot "
+                        "branch on them: write the branch with ocn.minimum / ocn.maximum")
 
     __bool__ = __lt__ = __le__ = __gt__ = __ge__ = _no_branch
 
@@ -101,12 +117,19 @@ class BinaryOperation(AbstractOperation):
     def __init__(self, op, a, b, location, grid):
         self.op, self.a, self.b, self.location, self.grid = op, a, b, tuple(location), grid
 
+    def reads(self):
+        (fa, da, ta), (fb, db, tb) = reads(self.a), reads(self.b)
+        return fa or fb, da | db, ta or tb
+
 
 class UnaryOperation(AbstractOperation):
     """▶(op(arg)): op at the argument's location, interpolated to `location`; `sq` and `cube` are x*x and (x*x)*x"""
 
     def __init__(self, op, arg, location, grid):
         self.op, self.arg, self.location, self.grid = op, arg, tuple(location), grid
+
+    def reads(self):
+        return reads(self.arg)
 
 
 class Derivative(AbstractOperation):
@@ -124,7 +147,7 @@ class Derivative(AbstractOperation):
 
 def binary_operation(op, a, b, location=None):
     """`op(Lc, a, b)` of binary_operations.jl:104-130; Lc defaults to the location of the first field-like operand"""
-    if op not in ("+", "-", "*", "/"):
+    if op not in ("+", "-", "*", "/", "min", "max"):
         raise NotImplementedError(f"binary operator {op!r}")
     for x in (a, b):
         if not (_is_fieldlike(x) or _is_number(x)):
@@ -165,14 +188,88 @@ def abs(a):  # noqa: A001 (mirrors the reference's Base.abs on fields)
     return float(np.abs(a)) if _is_number(a) else unary_operation("abs", a)
 
 
+def reads(x):
+    """(reads a field, the coordinate directions read, reads the time) of a number, a field or an operation"""
+    if _is_number(x):
+        return False, frozenset(), False
+    return x.reads() if isinstance(x, AbstractOperation) else (True, frozenset(), False)
+
+
 def _refused_unary(name):
     def f(a):
-        raise NotImplementedError(f"{name} of a field: only sqrt and abs (and unary minus, ** 2, ** 3) are implemented on the device")
+        raise NotImplementedError(f"{name} of a field: only sqrt and abs (and unary minus, ** 2, ** 3, minimum, maximum) are implemented "
+                                  "on the device")
     f.__name__ = name
     return f
 
 
-exp, log, log10, sin, cos, tan, sinh, cosh, tanh, asin, acos, atan = (_refused_unary(n) for n in _REFUSED_UNARY)
+log10, tan, sinh, cosh, asin, acos, atan = (_refused_unary(n) for n in _REFUSED_UNARY)
+
+
+def _host_folded_unary(name):
+    fn = HOST_FOLDED_UNARY[name]
+
+    def f(a):
+        if isinstance(a, np.ndarray):
+            return fn(a)
+        if _is_number(a):
+            return float(fn(a))
+        if not _is_fieldlike(a):
+            raise TypeError(f"{name} of {type(a).__name__}: not a number, an array, a field or an operation")
+        field, dirs, _ = reads(a)
+        if field or len(dirs) > 1:
+            raise NotImplementedError(f"{name} of an operand that varies cell by cell (it reads {'a field' if field else 'two coordinate directions'}"
+                                      "): only sqrt and abs (and unary minus, ** 2, ** 3, minimum, maximum) are implemented on the device.  "
+                                      f"{name} is accepted where the host can evaluate it once per time: of the time, of numbers and of ONE "
+                                      "coordinate direction, in a ContinuousForcing")
+        return unary_operation(name, a)
+    f.__name__ = name
+    f.__doc__ = f"{name} of a number or a NumPy array (np.{name}), or of a sub-tree the host folds (no field, at most one coordinate direction)"
+    return f
+
+
+exp, log, tanh, sin, cos = (_host_folded_unary(n) for n in HOST_FOLDED_UNARY)
+
+
+def julia_max(a, b):
+    """Julia's max on NumPy operands, with the selects of the device (csrc/diagnostics.hip): a NaN in either operand propagates and
+    max(-0.0, +0.0) = +0.0 in either operand order (np.maximum gives the first of two equal operands)"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    r = np.where(a > b, a, b)
+    r = np.where(a == b, np.where(np.signbit(a), b, a), r)
+    return np.where(a != a, a, r)
+
+
+def julia_min(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    r = np.where(a < b, a, b)
+    r = np.where(a == b, np.where(np.signbit(a), a, b), r)
+    return np.where(a != a, a, r)
+
+
+def _min_max(op, fn, a, b):
+    if _is_fieldlike(a) or _is_fieldlike(b):
+        return binary_operation(op, a, b)
+    with np.errstate(invalid="ignore"):
+        r = fn(a, b)
+    return float(r) if r.ndim == 0 else r
+
+
+def minimum(a, b):
+    """min(a, b) with Julia's semantics (OCN_OP_MIN) of fields / operations, numbers or NumPy arrays"""
+    return _min_max("min", julia_min, a, b)
+
+
+def maximum(a, b):
+    """max(a, b) with Julia's semantics (OCN_OP_MAX) of fields / operations, numbers or NumPy arrays"""
+    return _min_max("max", julia_max, a, b)
+
+
+_UFUNC_NODES = {"add": lambda a, b: binary_operation("+", a, b), "subtract": lambda a, b: binary_operation("-", a, b),
+                "multiply": lambda a, b: binary_operation("*", a, b), "divide": lambda a, b: binary_operation("/", a, b),
+                "negative": lambda a: unary_operation("neg", a), "square": lambda a: power(a, 2), "power": lambda a, n: power(a, n),
+                "exp": exp, "log": log, "tanh": tanh, "sin": sin, "cos": cos, "sqrt": sqrt, "absolute": abs, "minimum": minimum,
+                "maximum": maximum}
 
 
 def _derivative(dim, a, location=None):
@@ -354,6 +451,9 @@ class Program:
         if q is not None:
             return q
         if kind == "unary":
+            if node.op in HOST_FOLDED_UNARY:
+                raise NotImplementedError(f"{node.op} of the time or of a coordinate is folded by the host in a ContinuousForcing only: the "
+                                          "device has no transcendental functions")
             x = self.value(node.arg, off)
             if node.op == "sq":
                 q = self._emit(_lib.OP_MUL, x, x)
