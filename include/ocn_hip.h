@@ -555,6 +555,11 @@ int ocn_poisson_create_stretched(ocn_poisson_t *solver, const ocn_grid *grid, in
  * column-kernel length -- the Thomas sweep replaced by its exact spectral twin, cosine transform / division / inverse cosine transform in
  * one column pass (what the reference's FFTBasedPoissonSolver does on such a grid; OCN_POISSON_DCT_Z=0 keeps the sweep) */
 int ocn_poisson_info(ocn_poisson_t solver, int32_t *kind, int32_t *r2c, int32_t *direct_out);
+/* read-only: the three pass lists the handle walks as NUL-terminated UTF-8 text in buf, three lines "source: ...",
+ * "set_source: ...", "solve: ...", each followed by one item per pass in execution order, `PassName(d=D,mode=M,n=A×B×C)`: the direction,
+ * the launcher's mode and the extents of the array as the pass sees it.  OCN_ERR_INVALID_ARGUMENT (buf untouched) when len is too small;
+ * 4096 bytes hold every handle. */
+int ocn_poisson_describe(ocn_poisson_t solver, char *buf, size_t len);
 /* *wraps = 1 when the source-term pass of this handle reads u[i + 1], v[j + 1], w[k + 1] by periodically wrapped indices, i.e. reads no
  * halo cell of u, v, w: every (Periodic, Periodic, Periodic) handle created without OCN_POISSON_SOURCE_WRAP=0 in the environment.  Same
  * values as the filled halos hold, bit for bit. */

@@ -214,6 +214,7 @@ _SIGS = {
     "ocn_poisson_destroy": [_vp],
     "ocn_poisson_create_stretched": [C.POINTER(_vp), C.POINTER(CGrid), _i32, _vp, _vp],
     "ocn_poisson_info": [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)],
+    "ocn_poisson_describe": [_vp, C.c_char_p, C.c_size_t],
     "ocn_poisson_source_wraps": [_vp, C.POINTER(_i32)],
     "ocn_poisson_compute_source_term": [_vp, _vp, _vp, _vp, _dbl, _vp],
     "ocn_poisson_set_source_term": [_vp, _vp, _vp],

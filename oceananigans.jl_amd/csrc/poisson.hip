@@ -14,6 +14,10 @@
 // and records the ordered passes of the three entry points in the handle.  ocn_poisson_compute_source_term,
 // ocn_poisson_set_source_term, ocn_poisson_solve and ocn_poisson_solve_shifted walk those lists (run_passes); none of them looks at
 // the topology, the grid size or the environment again.
+#include <cstring>
+#include <string>
+#include <utility>
+
 #include "poisson_internal.h"
 
 using namespace ocn::poisson;
@@ -523,6 +527,28 @@ extern "C" int ocn_poisson_info(ocn_poisson_t s, int32_t *kind, int32_t *r2c, in
     if (kind) *kind = s->info[0];
     if (r2c) *r2c = s->info[1];
     if (direct_out) *direct_out = s->info[2];
+    return OCN_SUCCESS;
+}
+
+// The three pass lists as text, read-only: one line per list ("source:", "set_source:", "solve:"), one item per pass in the order
+// run_passes walks them, `pass_name(d=…,mode=…,n=a×b×c)` separated by single spaces.
+extern "C" int ocn_poisson_describe(ocn_poisson_t s, char *buf, size_t len)
+{
+    OCN_REQUIRE(s && buf, "ocn_poisson_describe: null argument");
+    std::string out;
+    const std::pair<const char *, const std::vector<PassRec> *> lists[] = {
+        {"source:", &s->passes.source}, {"set_source:", &s->passes.set_source}, {"solve:", &s->passes.solve}};
+    for (const auto &l : lists) {
+        out += l.first;
+        for (const PassRec &r : *l.second) {
+            char item[160];
+            snprintf(item, sizeof(item), " %s(d=%d,mode=%d,n=%d×%d×%d)", pass_name(r.pass), r.d, r.mode, r.n[0], r.n[1], r.n[2]);
+            out += item;
+        }
+        out += "\n";
+    }
+    OCN_REQUIRE(out.size() + 1 <= len, "ocn_poisson_describe: the description needs %zu bytes, the buffer has %zu", out.size() + 1, len);
+    memcpy(buf, out.c_str(), out.size() + 1);
     return OCN_SUCCESS;
 }
 

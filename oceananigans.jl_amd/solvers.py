@@ -65,6 +65,17 @@ class _PoissonHandle:
         _lib.call("ocn_poisson_info", self._h, C.byref(k), C.byref(r), C.byref(d))
         return {"kind": k.value, "r2c": bool(r.value), "direct_out": d.value, "fused_z": bool(d.value & 2), "dct_z": bool(d.value & 8)}
 
+    def passes(self):
+        """The handle's three pass lists (ocn_poisson_describe): (source, set_source, solve), each a list of strings
+        `PassName(d=…,mode=…,n=a×b×c)` in the order the executor walks them."""
+        buf = C.create_string_buffer(4096)
+        _lib.call("ocn_poisson_describe", self._h, buf, len(buf))
+        lists = {}
+        for line in buf.value.decode("utf-8").splitlines():
+            name, _, items = line.partition(":")
+            lists[name] = items.split()
+        return lists["source"], lists["set_source"], lists["solve"]
+
     def compute_source_term(self, u, v, w, dt):
         """compute_source_term!(pressure, solver, Δt, Ũ) (solve_for_pressure.jl:57-76)"""
         _lib.call("ocn_poisson_compute_source_term", self._h, u.ptr, v.ptr, w.ptr, float(dt), stream_ptr())
