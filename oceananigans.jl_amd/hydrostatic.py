@@ -6,29 +6,26 @@ flux-form momentum advection, QuasiAdamsBashforth2, static (Periodic, Periodic, 
     hydrostatic_free_surface_ab2_step.jl:9-111, update_hydrostatic_free_surface_model_state.jl:35-96
 
 The horizontal momentum and tracer tendencies are the terms of the NonhydrostaticModel path (flux-form advection, FPlane,
-∂x pHY′, ScalarDiffusivity, flux boundary conditions) plus the barotropic pressure gradient g ∇η; w is diagnosed from continuity;
-there is no pressure solve.  momentum_advection = VectorInvariant() (the reference's default: enstrophy-conserving vorticity flux,
-energy-conserving vertical advection and kinetic-energy gradient) or a flux-form scheme.  closure = ScalarDiffusivity(...), explicit or
-with VerticallyImplicitTimeDiscretization() (QAB2, fused = False: implicit_step! of u, v and the tracers after their ab2 step), or
-ConvectiveAdjustmentVerticalDiffusivity(...) / RiBasedVerticalDiffusivity(...) (QAB2, fused = False, one GPU: κᶜ, κᵘ fields computed in
-update_state! -- csrc/vertical_diffusivity.hip, csrc/ri_based_diffusivity.hip --, their term and the field-valued implicit step in
-csrc/vertical_diffusivity.hip), or HorizontalScalarBiharmonicDiffusivity(ν, κ) (fused = False, one GPU: csrc/biharmonic.hip), alone or in a
-two-closure tuple with one of the two closures with κ fields.  NOT in this slice (each raises):
-SplitExplicitFreeSurface / ImplicitFreeSurface, upwinding / WENO vector-invariant variants, z-star coordinates, eddy-viscosity closures,
-every other closure tuple,
+∂x pHY′, the closure term of ocn_model_terms, flux boundary conditions) plus the barotropic pressure gradient g ∇η; w is diagnosed from
+continuity; there is no pressure solve.  momentum_advection = VectorInvariant() (the reference's default: enstrophy-conserving vorticity flux,
+energy-conserving vertical advection and kinetic-energy gradient) or a flux-form scheme.  The closures, what each of them launches and
+what each refuses: hydrostatic_closures.py.  NOT in this slice (each raises):
+SplitExplicitFreeSurface / ImplicitFreeSurface, upwinding / WENO vector-invariant variants, z-star coordinates,
 a tracer advection scheme different from the momentum one, Distributed architectures.
 """
 import ctypes as C
+import math
 
 import torch
 
 from . import _lib
 from .architectures import stream_ptr
-from .fields import ZFaceField, fill_halo_regions
-from .grids import Bounded, Periodic
-from .models import NonhydrostaticModel, compute_boundary_tendency_contributions, update_hydrostatic_pressure
-from .physics import (BuoyancyTracer, Centered, RiBasedVerticalDiffusivity, SeawaterBuoyancy, has_diffusivity_fields, is_vertically_implicit,
-                      owns_eddy_fields, split_closure_tuple)
+from .fields import fill_halo_regions
+from .grids import Bounded, Flat, FullyConnected, Periodic, RectilinearGrid, require_regular_xy
+from .hydrostatic_closures import resolve_closure
+from .models import (NonhydrostaticModel, _bcs_ref, compute_boundary_tendency_contributions, fused_tracer_launches, update_boundary_conditions,
+                     update_hydrostatic_pressure)
+from .physics import Centered
 
 g_Earth = 9.80665  # Oceananigans.BuoyancyFormulations.g_Earth
 
@@ -123,7 +120,6 @@ class SplitExplicitFreeSurface:
 
     def __init__(self, grid=None, substeps=None, cfl=None, fixed_Δt=None, gravitational_acceleration=g_Earth,
                  averaging_kernel=averaging_shape_function, timestepper=None):
-        import math
         self.gravitational_acceleration = float(gravitational_acceleration)
         self.averaging_kernel = averaging_kernel
         self.timestepper = ForwardBackwardScheme() if timestepper is None else timestepper
@@ -150,7 +146,6 @@ class SplitExplicitFreeSurface:
         """calculate_substeps / calculate_adaptive_settings (step_split_explicit_free_surface.jl:54-58): (fractional Δτ, weights)"""
         if self.Δt_barotropic is None:
             return self.fractional_step_size, self.averaging_weights
-        import math
         n = max(MINIMUM_SUBSTEPS, math.ceil(2 * float(dt) / self.Δt_barotropic))
         return weights_from_substeps(n, self.averaging_kernel)
 
@@ -164,7 +159,6 @@ class HydrostaticFreeSurfaceModel:
         substep loop, one pass for the barotropic corrector + w, one halo launch, the hydrostatic pressure; the tendency evaluation
         that closes the reference's time_step! is deferred into the next step's fused launches (`flush_tendencies` completes it).
         fused = False keeps the reference's launch sequence.  Both are bit-identical in strict math."""
-        from .grids import FullyConnected, require_regular_xy
         if stokes_drift is not None:
             raise NotImplementedError("stokes_drift on HydrostaticFreeSurfaceModel is not implemented (NonhydrostaticModel takes UniformStokesDrift)")
         if forcing is not None:
@@ -205,73 +199,21 @@ class HydrostaticFreeSurfaceModel:
             if tracer_advection is not None and type(tracer_advection) is not type(momentum_advection):
                 raise NotImplementedError("with a flux-form momentum scheme, tracer_advection must be the same scheme in this slice")
             container_advection = momentum_advection
-        # closure = HorizontalScalarBiharmonicDiffusivity(...), alone or in a tuple with a closure that has κ fields (every other tuple
-        # raises): its term has a kernel of its own and no state, so from here on `closure` is the rest -- the other closure, or None
+        # every launch of the closure but the term in ocn_model_terms, and every refusal, is the business of this one object
         self.closure = tuple(closure) if isinstance(closure, (tuple, list)) else closure
-        self._biharmonic, closure = split_closure_tuple(closure)
-        if self._biharmonic is not None:
-            if fused:
-                raise NotImplementedError("ScalarBiharmonicDiffusivity runs the reference's launch sequence (fused = False)")
-            if self._dist is not None or hasattr(arch, "partition"):
-                raise NotImplementedError("ScalarBiharmonicDiffusivity on a slab-partitioned (Distributed) grid is not implemented")
-            fused = False
-        if owns_eddy_fields(closure):
-            raise NotImplementedError("eddy-viscosity closures are not part of this slice")
-        # closure = ConvectiveAdjustmentVerticalDiffusivity(...) or RiBasedVerticalDiffusivity(...), the closures with κᶜ, κᵘ fields: the
-        # reference's launch sequence with QAB2 on one GPU, in both discretizations
-        self._kfields = has_diffusivity_fields(closure)
-        self._ri = isinstance(closure, RiBasedVerticalDiffusivity)
-        if self._kfields:
-            name = type(closure).__name__
-            if fused:
-                raise NotImplementedError(f"{name} runs the reference's launch sequence (fused = False)")
-            if self.split_rk3:
-                raise NotImplementedError(f"{name} with SplitRungeKutta3 is not implemented")
-            if self._dist is not None or hasattr(arch, "partition"):
-                raise NotImplementedError(f"{name} on a slab-partitioned (Distributed) grid is not implemented")
-            fused = False
-        if self._ri:
-            # top_buoyancy_flux reads the top condition of the buoyancy tracers as a flux; the reference would read the number of a Value or
-            # Gradient condition as one too, which is not reproduced
-            carriers = ("b", None) if isinstance(buoyancy, BuoyancyTracer) else (("T", "S") if isinstance(buoyancy, SeawaterBuoyancy) else (None, None))
-            self._ri_carriers = carriers  # the tracers whose top conditions make up the buoyancy flux: (T or b, S)
-            for tracer in filter(None, carriers):
-                top = getattr((boundary_conditions or {}).get(tracer), "sides", {}).get("top")
-                if top is not None and top.kind != _lib.BC_FLUX:
-                    raise NotImplementedError(f"RiBasedVerticalDiffusivity: the top boundary condition of {tracer} must be a "
-                                              "FluxBoundaryCondition (or the default): it is the surface buoyancy flux of the entrainment term")
-        # closure = ScalarDiffusivity(VerticallyImplicitTimeDiscretization(), ...): the reference's launch sequence with QAB2 on one GPU
-        # (hydrostatic_free_surface_ab2_step.jl:39-108: implicit_step! of u, v and every tracer after its ab2 step; w is diagnostic)
-        self._implicit = is_vertically_implicit(closure)
-        if self._implicit:
-            if fused:
-                raise NotImplementedError("a VerticallyImplicitTimeDiscretization closure runs the reference's launch sequence (fused = False)")
-            if self.split_rk3:
-                raise NotImplementedError("a VerticallyImplicitTimeDiscretization closure with SplitRungeKutta3 is not implemented")
-            if self._dist is not None:
-                raise NotImplementedError("a VerticallyImplicitTimeDiscretization closure on a slab-partitioned (Distributed) grid is not implemented")
+        self._closure = resolve_closure(closure, fused, self.split_rk3, hasattr(arch, "partition"), self._dist is not None, buoyancy,
+                                        boundary_conditions)
+        if self._closure.unfused:
             fused = False
         # fields, physics descriptors, tendency storage and the Adams-Bashforth bookkeeping of the nonhydrostatic model are reused;
         # its pressure solver and w tendency are simply not used
         self._nh = NonhydrostaticModel(grid, advection=container_advection, tracers=tracers, timestepper="QuasiAdamsBashforth2",
-                                       closure=closure, buoyancy=buoyancy, coriolis=coriolis, boundary_conditions=boundary_conditions,
-                                       pressure_solver=None, math_mode=math_mode, _hydrostatic_container=True,
-                                       _closure_halo=0 if self._biharmonic is None else self._biharmonic.required_halo_size)
+                                       closure=self._closure.container_closure, buoyancy=buoyancy, coriolis=coriolis,
+                                       boundary_conditions=boundary_conditions, pressure_solver=None, math_mode=math_mode,
+                                       _closure_halo=self._closure.halo)
         nh = self._nh
         grid = nh.grid  # (halo-inflated / math-mode-pinned by the container model)
-        # build_diffusivity_fields (convective_adjustment_vertical_diffusivity.jl:85, ri_based_vertical_diffusivity.jl:186-191): κᶜ and κᵘ
-        # (and Ri), ZFaceFields with default conditions, and the multipliers of the three distinct matrices of the implicit step (u, v,
-        # every tracer)
-        self.diffusivity_fields = None
-        if self._kfields:
-            self.diffusivity_fields = {"kappa_c": ZFaceField(grid), "kappa_u": ZFaceField(grid)}
-            if self._ri:
-                self.diffusivity_fields["Ri"] = ZFaceField(grid)
-            self._closure_struct = closure.c_struct()
-            if self._implicit:
-                self._ivd_scratch = torch.zeros((3, grid.Nz, grid.Ny, grid.Nx), dtype=torch.float64, device=nh.u.data.device)
-            if self._biharmonic is not None:  # the tuple: minus the other closure's term, for u and v and then tracer by tracer
-                self._tuple_scratch = torch.zeros((2,) + tuple(nh.u.data.shape), dtype=torch.float64, device=nh.u.data.device)
+        self.diffusivity_fields = self._closure.allocate(nh)
         self.grid, self.architecture, self.clock = grid, grid.architecture, nh.clock
         self.free_surface = free_surface
         self.u, self.v, self.w = nh.u, nh.v, nh.w
@@ -291,7 +233,6 @@ class HydrostaticFreeSurfaceModel:
         if self.implicit:
             if self.fused or self._dist is not None:
                 raise NotImplementedError("ImplicitFreeSurface: the reference's launch sequence on one GPU (fused = False)")
-            from .grids import Flat, RectilinearGrid
             from .solvers import FFTBasedPoissonSolver
             # FFTImplicitFreeSurfaceSolver (fft_based_implicit_free_surface_solver.jl:39-70): a Poisson solver on the horizontal grid
             hgrid = RectilinearGrid(grid.architecture, size=(grid.Nx, grid.Ny), x=grid._interval[0],
@@ -336,48 +277,15 @@ class HydrostaticFreeSurfaceModel:
     # ---- update_state! (update_hydrostatic_free_surface_model_state.jl:35-53, 74-96) -------------------------------------
     def update_state(self, compute_tendencies=True):
         nh, g = self._nh, self.grid
-        from .models import update_boundary_conditions
         update_boundary_conditions(nh)
         fill_halo_regions((self.u, self.v) + tuple(self.tracers), fill_boundary_normal_velocities=False)
         self._fill_eta_halos()
         _lib.call("ocn_compute_w_from_continuity", g.cref, self.u.ptr, self.v.ptr, self.w.ptr, stream_ptr())
         update_hydrostatic_pressure(nh)
-        if self._kfields:  # compute_diffusivities!, then fill_halo_regions!(diffusivity_fields; only_local_halos = true)
-            d = self.diffusivity_fields
-            nh._refresh_term_pointers()
-            if self._ri:
-                self._compute_ri_based_diffusivities()
-            else:
-                _lib.call("ocn_compute_convective_adjustment_diffusivities", g.cref, C.byref(nh._terms), C.byref(self._closure_struct),
-                          d["kappa_c"].ptr, d["kappa_u"].ptr, stream_ptr())
-            fill_halo_regions(tuple(d.values()), fill_boundary_normal_velocities=False)  # (ZFaceFields that are no velocities)
+        self._closure.compute_diffusivities(nh)
         self._tendencies_current = False
         if compute_tendencies:
             self.compute_tendencies()
-
-    def _top_condition(self, name):
-        """reference to the struct ocn_bc of the top condition of a tracer, or NULL (no such tracer, default conditions: no flux)"""
-        if name is not None and name in self.tracer_names:
-            b = getattr(self.field(name), "boundary_conditions", None)
-            if b is not None and b.sides["top"] is not None:
-                return C.pointer(b.c_struct(self.grid).top)
-        return C.POINTER(_lib.CBc)()
-
-    def _compute_ri_based_diffusivities(self):
-        """compute_diffusivities!(diffusivities, ::RiBasedVerticalDiffusivity, model) (ri_based_vertical_diffusivity.jl:193-229) after
-        update_boundary_conditions, so the `values` arrays of function-valued flux conditions are current: compute_ri_number!, the halo
-        fill of Ri, compute_ri_based_diffusivities! -- or, without a horizontal filter, where Ri is only read at its own cell, all of it
-        in one launch (bit-identical).  Every call advances the time average of κᶜ and κᵘ."""
-        nh, g, d, s = self._nh, self.grid, self.diffusivity_fields, stream_ptr()
-        terms, cl = C.byref(nh._terms), C.byref(self._closure_struct)
-        tops = tuple(self._top_condition(name) for name in self._ri_carriers)
-        if nh.closure.horizontal_Ri_filter is None:
-            _lib.call("ocn_compute_ri_based_diffusivities_fused", g.cref, terms, cl, *tops, self.u.ptr, self.v.ptr, d["Ri"].ptr,
-                      d["kappa_c"].ptr, d["kappa_u"].ptr, s)
-        else:
-            _lib.call("ocn_compute_ri_number", g.cref, terms, self.u.ptr, self.v.ptr, d["Ri"].ptr, s)
-            fill_halo_regions((d["Ri"],), fill_boundary_normal_velocities=False)
-            _lib.call("ocn_compute_ri_based_diffusivities", g.cref, terms, cl, *tops, d["Ri"].ptr, d["kappa_c"].ptr, d["kappa_u"].ptr, s)
 
     # ---- compute_tendencies! (hydrostatic_free_surface_tendency_kernel_functions.jl:45-52, 86-93, 125-131) -----------------------
     def flush_tendencies(self):
@@ -402,51 +310,15 @@ class HydrostaticFreeSurfaceModel:
                       Gn[0].ptr, Gn[1].ptr, Gn[2].ptr, None, s)
             if not (self.split or self.implicit):
                 _lib.call("ocn_add_barotropic_pressure_gradient", g.cref, grav, self.eta.data_ptr(), Gn[0].ptr, Gn[1].ptr, s)  # - g ∇η
-        terms = nh._terms_noclosure if (self._implicit or self._kfields) else nh._terms
-        _lib.call("ocn_add_momentum_terms", g.cref, C.byref(terms), self.u.ptr, self.v.ptr, self.w.ptr, Gn[0].ptr, Gn[1].ptr,
+        terms = C.byref(nh._terms)  # (of the closure they hold what the container was given: hydrostatic_closures.py)
+        _lib.call("ocn_add_momentum_terms", g.cref, terms, self.u.ptr, self.v.ptr, self.w.ptr, Gn[0].ptr, Gn[1].ptr,
                   Gn[2].ptr, None, s)                                                               # - f x U - ∇pHY′ - ∂ⱼτᵢⱼ
-        for n, c in enumerate(self.tracers):
-            kappa = 0.0 if (nh.closure is None or self._implicit or self._kfields) else nh.closure.kappa_of(self.tracer_names[n])
-            _lib.call("ocn_compute_tracer_tendency_terms", g.cref, C.byref(terms), kappa, None, self.u.ptr, self.v.ptr, self.w.ptr,
-                      c.ptr, Gn[3 + n].ptr, None, s)
-        if self._biharmonic is not None:
-            self._add_biharmonic_fluxes(Gn, s)
-        elif self._kfields:  # the closure term: every vertical flux (explicit), or the fluxes through the two boundaries (vertically implicit)
-            nt, d = len(self.tracers), self.diffusivity_fields
-            _lib.call("ocn_add_vertical_diffusivity_fluxes", g.cref, d["kappa_u"].ptr, self.u.ptr, self.v.ptr, Gn[0].ptr, Gn[1].ptr, nt,
-                      _lib.ptr_array([d["kappa_c"].ptr] * max(nt, 1)), _lib.ptr_array([c.ptr for c in self.tracers] or [None]),
-                      _lib.ptr_array([G.ptr for G in Gn[3:]] or [None]), int(self._implicit), None, s)
-        elif self._implicit:  # the explicit part of the closure term (Gu, Gv and the tracers: w is diagnostic)
-            nt = len(self.tracers)
-            _lib.call("ocn_add_vertically_implicit_explicit_fluxes", g.cref, nh.closure.nu, self.u.ptr, self.v.ptr, self.w.ptr, Gn[0].ptr,
-                      Gn[1].ptr, None, nt, (C.c_double * max(nt, 1))(*[nh.closure.kappa_of(n) for n in self.tracer_names]),
-                      _lib.ptr_array([c.ptr for c in self.tracers] or [None]), _lib.ptr_array([G.ptr for G in Gn[3:]] or [None]), None, s)
+        for name, c, G in zip(self.tracer_names, self.tracers, Gn[3:]):
+            _lib.call("ocn_compute_tracer_tendency_terms", g.cref, terms, self._closure.tracer_kappa(name), None, self.u.ptr, self.v.ptr,
+                      self.w.ptr, c.ptr, G.ptr, None, s)
+        self._closure.add_fluxes(nh, Gn, s)  # the term of every other closure
         if boundary_contributions:
             compute_boundary_tendency_contributions(nh)
-
-    def _add_biharmonic_fluxes(self, Gn, s):
-        """G -= ∂ⱼτ of HorizontalScalarBiharmonicDiffusivity -- or, in a tuple with a closure V that has κ fields, G -= (∂ⱼτ + ∂ⱼτ(V)), the
-        sum formed before it is subtracted (closure_tuples.jl:41-43): V's kernel leaves 0 - ∂ⱼτ(V) in a zeroed array, which the biharmonic
-        kernel adds to its own term.  Two such arrays: u and v first, then tracer by tracer."""
-        g, bih, pa = self.grid, self._biharmonic, _lib.ptr_array
-        nt = len(self.tracers)
-        kappa = [bih.kappa_of(n) for n in self.tracer_names]
-        if not self._kfields:
-            _lib.call("ocn_add_biharmonic_fluxes", g.cref, bih.nu, self.u.ptr, self.v.ptr, Gn[0].ptr, Gn[1].ptr, nt, (C.c_double * max(nt, 1))(*kappa),
-                      pa([c.ptr for c in self.tracers] or [None]), pa([G.ptr for G in Gn[3:]] or [None]), None, None, None, s)
-            return
-        d, S, implicit = self.diffusivity_fields, self._tuple_scratch, int(self._implicit)
-        Su, Sv = S[0].data_ptr(), S[1].data_ptr()
-        S.zero_()
-        _lib.call("ocn_add_vertical_diffusivity_fluxes", g.cref, d["kappa_u"].ptr, self.u.ptr, self.v.ptr, Su, Sv, 0, None, None, None, implicit,
-                  None, s)
-        _lib.call("ocn_add_biharmonic_fluxes", g.cref, bih.nu, self.u.ptr, self.v.ptr, Gn[0].ptr, Gn[1].ptr, 0, None, None, None, Su, Sv, None, s)
-        for n, c in enumerate(self.tracers):
-            S[0].zero_()
-            _lib.call("ocn_add_vertical_diffusivity_fluxes", g.cref, None, None, None, None, None, 1, pa([d["kappa_c"].ptr]), pa([c.ptr]), pa([Su]),
-                      implicit, None, s)
-            _lib.call("ocn_add_biharmonic_fluxes", g.cref, 0.0, None, None, None, None, 1, (C.c_double * 1)(kappa[n]), pa([c.ptr]),
-                      pa([Gn[3 + n].ptr]), None, None, pa([Su]), s)
 
     # ---- time_step! (quasi_adams_bashforth_2.jl:74-115 with ab2_step!(::HydrostaticFreeSurfaceModel)) -------------------------
     def _time_step_split_rk3(self, dt):
@@ -505,6 +377,10 @@ class HydrostaticFreeSurfaceModel:
                       self._Ub.data_ptr(), self._Vb.data_ptr(), float(g.Lz), s)
             self.update_state(compute_tendencies=True)
         clock.stage = 1
+        self._tick(dt)
+
+    def _tick(self, dt):
+        clock = self.clock
         clock.time += dt
         clock.iteration += 1
         clock.last_dt = dt
@@ -532,16 +408,7 @@ class HydrostaticFreeSurfaceModel:
         fields = [self.u, self.v] + list(self.tracers)
         _lib.call("ocn_ab2_step", g.cref, len(idx), _lib.ptr_array([f.ptr for f in fields]), _lib.ptr_array([Gn[q].ptr for q in idx]),
                   _lib.ptr_array([Gm[q].ptr for q in idx]), _lib.i32_array([f.loc for f in fields]), float(dt), float(chi), s)
-        if self._kfields and self._implicit:  # implicit_step! with the κ fields of the last update_state! (the reference does not recompute them)
-            d, w = self.diffusivity_fields, self._ivd_scratch
-            kappas = [d["kappa_u"].ptr] * 2 + [d["kappa_c"].ptr] * len(self.tracers)
-            scratch = [w[0].data_ptr(), w[1].data_ptr()] + [w[2].data_ptr()] * len(self.tracers)
-            _lib.call("ocn_implicit_vertical_diffusion_step_fields", g.cref, len(fields), _lib.ptr_array([f.ptr for f in fields]),
-                      _lib.i32_array([f.loc for f in fields]), _lib.ptr_array(kappas), _lib.ptr_array(scratch), float(dt), s)
-        elif self._implicit:  # implicit_step! of u, v (ν) and every tracer (its own κ) with the full Δt
-            kappa = [nh.closure.nu] * 2 + [nh.closure.kappa_of(n) for n in self.tracer_names]
-            _lib.call("ocn_implicit_vertical_diffusion_step", g.cref, len(fields), _lib.ptr_array([f.ptr for f in fields]),
-                      _lib.i32_array([f.loc for f in fields]), (C.c_double * len(fields))(*kappa), float(dt), s)
+        self._closure.implicit_step(nh, fields, dt, s)  # implicit_step! of a vertically implicit closure
         fs = self.free_surface
         if self.split:
             # compute_free_surface_tendency! (slow forcing from Gⁿ, G⁻ BEFORE they are cached), then step_free_surface!
@@ -567,10 +434,7 @@ class HydrostaticFreeSurfaceModel:
             # compute_free_surface_tendency! + step_free_surface!
             _lib.call("ocn_explicit_free_surface_ab2_step", g.cref, self.w.ptr, self.eta.data_ptr(), self._Geta.data_ptr(),
                       self._Geta_m.data_ptr(), float(dt), float(chi), s)
-        clock.time += dt
-        clock.iteration += 1
-        clock.last_dt = dt
-        clock.last_stage_dt = dt
+        self._tick(dt)
         # (no pressure correction with an explicit free surface) cache_previous_tendencies!: role swap
         nh.timestepper._Gn, nh.timestepper._Gm = Gm, Gn
         self._Geta, self._Geta_m = self._Geta_m, self._Geta
@@ -622,14 +486,12 @@ class HydrostaticFreeSurfaceModel:
         euler = bool(euler or (dt != clock.last_dt))
         chi = -0.5 if euler else nh.timestepper.chi
         Gn, Gm = nh.timestepper._Gn, nh.timestepper._Gm
-        from .models import update_boundary_conditions
         update_boundary_conditions(nh)   # (the deferred tendencies belong to update_state! at the current clock time)
         prog = [self.u, self.v] + list(self.tracers)
         if self._alt is None:
             self._alt = [torch.zeros_like(f.data) for f in prog]
         alt = self._alt
         t = C.byref(nh._terms)
-        from .models import _bcs_ref
         fs = self.free_surface
         grav = fs.gravitational_acceleration
         # compute_tendencies! (of the state the previous step left) + ab2_step_velocities! + compute_free_surface_tendency!
@@ -639,9 +501,8 @@ class HydrostaticFreeSurfaceModel:
                   None if self.split else self.eta.data_ptr(), grav, *sp, s)
         # tracer tendencies + ab2_step_tracers!
         gamma, zeta = 1.5 + chi, -(0.5 + chi)
-        kappas = [0.0 if nh.closure is None else nh.closure.kappa_of(name) for name in self.tracer_names]
+        kappas = [self._closure.tracer_kappa(name) for name in self.tracer_names]
         if self._tracer_fusable and self.tracers:
-            from .models import fused_tracer_launches
             fused_tracer_launches(g, t, self.u, self.v, self.w, self.tracers, kappas, [None] * len(self.tracers), Gn[3:], Gm[3:], alt[2:], dt,
                                   gamma, zeta, 0 if euler else 1, None, s)
         else:
@@ -668,10 +529,7 @@ class HydrostaticFreeSurfaceModel:
             for n, c in enumerate(self.tracers):
                 c.data, alt[2 + n] = alt[2 + n], c.data
             nh._refresh_term_pointers()
-        clock.time += dt
-        clock.iteration += 1
-        clock.last_dt = dt
-        clock.last_stage_dt = dt
+        self._tick(dt)
         nh.timestepper._Gn, nh.timestepper._Gm = Gm, Gn                     # cache_previous_tendencies!: role swap
         # update_state!(model; compute_tendencies = false): halos (w's halo columns are periodic images of the interior ones computed
         # above), η halos, hydrostatic pressure; the tendencies follow in the next step's fused launches

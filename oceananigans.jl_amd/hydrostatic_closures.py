@@ -1,0 +1,227 @@
+"""Everything HydrostaticFreeSurfaceModel knows about its closure (src/TurbulenceClosures/closure_tuples.jl: a closure answers
+compute_diffusivities!, the flux divergences, implicit_step! and required_halo_size, and a tuple is the sum of its members).
+
+`resolve_closure` turns the user's closure into ONE object, or refuses; it allocates nothing and touches no device.  The model asks that
+object: at construction `container_closure` (what ocn_model_terms carries: an explicit ScalarDiffusivity or None), `halo`, `unfused` and
+`allocate(nh)` (the diffusivity_fields dict, or None); in update_state `compute_diffusivities(nh)`; in compute_tendencies `tracer_kappa(name)`
+for the built-in tracer entry point and `add_fluxes(nh, Gn, s)` after those entry points; in time_step `implicit_step(nh, fields, dt, s)` after
+ocn_ab2_step; checkpoints read `state_fields`.  Every kind but InModelTerms keeps the closure out of ocn_model_terms and runs the
+reference's launch sequence (fused = False) with QAB2 on one GPU."""
+import ctypes as C
+
+import torch
+
+from . import _lib
+from .architectures import stream_ptr
+from .fields import ZFaceField, fill_halo_regions
+from .models import implicit_diffusion_step
+from .physics import (BuoyancyTracer, RiBasedVerticalDiffusivity, ScalarBiharmonicDiffusivity, SeawaterBuoyancy, has_diffusivity_fields,
+                      is_vertically_implicit, owns_eddy_fields)
+
+
+def _refuse(what, fused, split_rk3, slabs):
+    if fused:
+        raise NotImplementedError(f"{what} runs the reference's launch sequence (fused = False)")
+    if split_rk3:
+        raise NotImplementedError(f"{what} with SplitRungeKutta3 is not implemented")
+    if slabs:
+        raise NotImplementedError(f"{what} on a slab-partitioned (Distributed) grid is not implemented")
+
+
+def resolve_closure(closure, fused, split_rk3, partitioned, distributed, buoyancy, boundary_conditions):
+    """closure: a closure, a two-element tuple or list, or None; partitioned: the architecture has a `partition`; distributed: it also
+    communicates (a slab-x rank)."""
+    biharmonic = None
+    if isinstance(closure, (tuple, list)):  # (closure_tuples.jl) the biharmonic with a closure that has κ fields, in either order
+        biharmonic = [c for c in closure if isinstance(c, ScalarBiharmonicDiffusivity)]
+        vertical = [c for c in closure if has_diffusivity_fields(c)]
+        if len(closure) != 2 or len(biharmonic) != 1 or len(vertical) != 1:
+            raise NotImplementedError("closure tuples are not implemented, except (HorizontalScalarBiharmonicDiffusivity, "
+                                      "ConvectiveAdjustmentVerticalDiffusivity or RiBasedVerticalDiffusivity) in either order: give one closure")
+        biharmonic, closure = biharmonic[0], vertical[0]
+    elif isinstance(closure, ScalarBiharmonicDiffusivity):
+        biharmonic, closure = closure, None
+    if biharmonic is not None:  # (SplitRungeKutta3 is fine: the term has no state)
+        _refuse("ScalarBiharmonicDiffusivity", fused, False, partitioned)
+        fused = False
+    if owns_eddy_fields(closure):
+        raise NotImplementedError("eddy-viscosity closures are not part of this slice")
+    other = None
+    if has_diffusivity_fields(closure):
+        _refuse(type(closure).__name__, fused, split_rk3, partitioned)
+        carriers = None
+        if isinstance(closure, RiBasedVerticalDiffusivity):
+            # top_buoyancy_flux reads the top condition of the buoyancy tracers as a flux; the reference would read the number of a Value or
+            # Gradient condition as one too, which is not reproduced
+            carriers = ("b", None) if isinstance(buoyancy, BuoyancyTracer) else (("T", "S") if isinstance(buoyancy, SeawaterBuoyancy) else (None, None))
+            for tracer in filter(None, carriers):
+                top = getattr((boundary_conditions or {}).get(tracer), "sides", {}).get("top")
+                if top is not None and top.kind != _lib.BC_FLUX:
+                    raise NotImplementedError(f"RiBasedVerticalDiffusivity: the top boundary condition of {tracer} must be a "
+                                              "FluxBoundaryCondition (or the default): it is the surface buoyancy flux of the entrainment term")
+        other = KappaFields(closure, carriers)
+    elif is_vertically_implicit(closure):
+        _refuse("a VerticallyImplicitTimeDiscretization closure", fused, split_rk3, distributed)
+        if partitioned:
+            raise NotImplementedError("a VerticallyImplicitTimeDiscretization closure on a Distributed architecture is not implemented (see DESIGN.md)")
+        return ImplicitScalar(closure)
+    if biharmonic is not None:
+        return Biharmonic(biharmonic, other)
+    return other or InModelTerms(closure)
+
+
+class InModelTerms:
+    """no closure, or an explicit ScalarDiffusivity: its term lives in ocn_model_terms, everything else is a no-op"""
+    halo, unfused, implicit, state_fields = 0, False, False, ()
+
+    def __init__(self, closure):
+        self.container_closure = closure
+
+    def allocate(self, nh):
+        return None
+
+    def compute_diffusivities(self, nh):
+        pass
+
+    def tracer_kappa(self, name):
+        return 0.0 if self.container_closure is None else self.container_closure.kappa_of(name)
+
+    def add_fluxes(self, nh, Gn, s):
+        pass
+
+    def implicit_step(self, nh, fields, dt, s):
+        pass
+
+
+class ImplicitScalar(InModelTerms):
+    """hydrostatic_free_surface_ab2_step.jl:39-108: implicit_step! of u, v and every tracer after its ab2 step; w is diagnostic"""
+    container_closure, unfused, implicit = None, True, True
+
+    def __init__(self, closure):
+        self.closure = closure
+
+    def add_fluxes(self, nh, Gn, s):
+        """the explicit part of the closure term (Gu, Gv and the tracers)"""
+        nt, cl = len(nh.tracers), self.closure
+        _lib.call("ocn_add_vertically_implicit_explicit_fluxes", nh.grid.cref, cl.nu, nh.u.ptr, nh.v.ptr, nh.w.ptr, Gn[0].ptr, Gn[1].ptr, None,
+                  nt, (C.c_double * max(nt, 1))(*[cl.kappa_of(n) for n in nh.tracer_names]),
+                  _lib.ptr_array([c.ptr for c in nh.tracers] or [None]), _lib.ptr_array([G.ptr for G in Gn[3:]] or [None]), None, s)
+
+    def implicit_step(self, nh, fields, dt, s):
+        """u, v (ν) and every tracer (its own κ) with the full Δt"""
+        implicit_diffusion_step(nh.grid, fields, [self.closure.nu] * 2 + [self.closure.kappa_of(n) for n in nh.tracer_names], dt, s)
+
+
+class KappaFields(InModelTerms):
+    """ConvectiveAdjustmentVerticalDiffusivity or RiBasedVerticalDiffusivity, in both discretizations: κᶜ, κᵘ fields computed in update_state!
+    (csrc/vertical_diffusivity.hip, csrc/ri_based_diffusivity.hip).  carriers: None, or for the Ri-based one -- which differs in how the
+    fields are computed and in their being state -- the tracers whose top conditions make up the surface buoyancy flux: (T or b, S)"""
+    container_closure, unfused = None, True
+
+    def __init__(self, closure, carriers):
+        self.closure, self.carriers, self.implicit = closure, carriers, is_vertically_implicit(closure)
+        self.state_fields = () if carriers is None else ("kappa_c", "kappa_u")  # time averages (the reference does not checkpoint them)
+
+    def allocate(self, nh):
+        """build_diffusivity_fields (convective_adjustment_vertical_diffusivity.jl:85, ri_based_vertical_diffusivity.jl:186-191): κᶜ and κᵘ
+        (and Ri), ZFaceFields with default conditions, and the multipliers of the three distinct matrices of the implicit step (u, v,
+        every tracer)"""
+        g = nh.grid
+        self.fields = {"kappa_c": ZFaceField(g), "kappa_u": ZFaceField(g)}
+        if self.carriers is not None:
+            self.fields["Ri"] = ZFaceField(g)
+        self.struct = self.closure.c_struct()
+        if self.implicit:
+            self.ivd_scratch = torch.zeros((3, g.Nz, g.Ny, g.Nx), dtype=torch.float64, device=nh.u.data.device)
+        return self.fields
+
+    def top_conditions(self, nh):
+        """references to the struct ocn_bc of the top conditions of the carriers, NULL where there is none (no such tracer, default
+        conditions: no flux)"""
+        bcs = [getattr(nh.field(name), "boundary_conditions", None) if name in nh.tracer_names else None for name in self.carriers or ()]
+        return tuple(C.pointer(b.c_struct(nh.grid).top) if b is not None and b.sides["top"] is not None else C.POINTER(_lib.CBc)() for b in bcs)
+
+    def compute_diffusivities(self, nh):
+        """compute_diffusivities!, then fill_halo_regions!(diffusivity_fields; only_local_halos = true).  RiBasedVerticalDiffusivity
+        (ri_based_vertical_diffusivity.jl:193-229), after update_boundary_conditions, so the `values` arrays of function-valued flux
+        conditions are current: compute_ri_number!, the halo fill of Ri, compute_ri_based_diffusivities! -- or, without a horizontal
+        filter, where Ri is only read at its own cell, all of it in one launch (bit-identical).  Every call advances the time average."""
+        g, d, s = nh.grid, self.fields, stream_ptr()
+        nh._refresh_term_pointers()
+        terms, cl = C.byref(nh._terms), C.byref(self.struct)
+        tops = self.top_conditions(nh)
+        if self.carriers is None:
+            _lib.call("ocn_compute_convective_adjustment_diffusivities", g.cref, terms, cl, d["kappa_c"].ptr, d["kappa_u"].ptr, s)
+        elif self.closure.horizontal_Ri_filter is None:
+            _lib.call("ocn_compute_ri_based_diffusivities_fused", g.cref, terms, cl, *tops, nh.u.ptr, nh.v.ptr, d["Ri"].ptr,
+                      d["kappa_c"].ptr, d["kappa_u"].ptr, s)
+        else:
+            _lib.call("ocn_compute_ri_number", g.cref, terms, nh.u.ptr, nh.v.ptr, d["Ri"].ptr, s)
+            fill_halo_regions((d["Ri"],), fill_boundary_normal_velocities=False)
+            _lib.call("ocn_compute_ri_based_diffusivities", g.cref, terms, cl, *tops, d["Ri"].ptr, d["kappa_c"].ptr, d["kappa_u"].ptr, s)
+        fill_halo_regions(tuple(d.values()), fill_boundary_normal_velocities=False)  # (ZFaceFields that are no velocities)
+
+    def add_to(self, g, u, v, Gu, Gv, nt, c, G, s):
+        """G -= ∂ⱼτ: every vertical flux (explicit), or the fluxes through the two boundaries (vertically implicit).  Pointers; u = None:
+        no momentum; c, G: lists, or None for a launch without tracer arrays"""
+        d, pa = self.fields, _lib.ptr_array
+        _lib.call("ocn_add_vertical_diffusivity_fluxes", g.cref, u and d["kappa_u"].ptr, u, v, Gu, Gv, nt, c and pa([d["kappa_c"].ptr] * len(c)),
+                  c and pa(c), G and pa(G), int(self.implicit), None, s)
+
+    def add_fluxes(self, nh, Gn, s):
+        self.add_to(nh.grid, nh.u.ptr, nh.v.ptr, Gn[0].ptr, Gn[1].ptr, len(nh.tracers), [c.ptr for c in nh.tracers] or [None],
+                    [G.ptr for G in Gn[3:]] or [None], s)
+
+    def implicit_step(self, nh, fields, dt, s):
+        """implicit_step! with the κ fields of the last update_state! (the reference does not recompute them)"""
+        if not self.implicit:
+            return
+        d, w, nt = self.fields, self.ivd_scratch, len(fields) - 2
+        kappas = [d["kappa_u"].ptr] * 2 + [d["kappa_c"].ptr] * nt
+        scratch = [w[0].data_ptr(), w[1].data_ptr()] + [w[2].data_ptr()] * nt
+        _lib.call("ocn_implicit_vertical_diffusion_step_fields", nh.grid.cref, len(fields), _lib.ptr_array([f.ptr for f in fields]),
+                  _lib.i32_array([f.loc for f in fields]), _lib.ptr_array(kappas), _lib.ptr_array(scratch), float(dt), s)
+
+
+class Biharmonic(InModelTerms):
+    """G -= ∂ⱼτ of HorizontalScalarBiharmonicDiffusivity -- or, in a pair with a closure V that has κ fields, G -= (∂ⱼτ + ∂ⱼτ(V)), the sum
+    formed before it is subtracted (closure_tuples.jl:41-43): V's kernel leaves 0 - ∂ⱼτ(V) in a zeroed array, which the biharmonic kernel
+    adds to its own term.  Two such arrays: u and v first, then tracer by tracer.  Everything else of a pair is V's."""
+    container_closure, unfused = None, True
+
+    def __init__(self, closure, other):
+        self.closure, self.other, self.halo = closure, other, closure.required_halo_size
+        if other is not None:
+            self.implicit, self.state_fields = other.implicit, other.state_fields
+            self.compute_diffusivities, self.implicit_step = other.compute_diffusivities, other.implicit_step
+
+    def allocate(self, nh):
+        if self.other is None:
+            return None
+        fields = self.other.allocate(nh)
+        self.scratch = torch.zeros((2,) + tuple(nh.u.data.shape), dtype=torch.float64, device=nh.u.data.device)
+        return fields
+
+    @staticmethod
+    def add_to(g, nu, u, v, Gu, Gv, nt, kappa, c, G, neg_u, neg_v, neg_c, s):
+        """pointers; u = None: no momentum; kappa, c, G: lists, or None for a launch without tracer arrays; neg_*: minus the other closure's
+        term, or None"""
+        pa = _lib.ptr_array
+        _lib.call("ocn_add_biharmonic_fluxes", g.cref, nu, u, v, Gu, Gv, nt, kappa and (C.c_double * len(kappa))(*kappa), c and pa(c), G and pa(G),
+                  neg_u, neg_v, neg_c and pa(neg_c), s)
+
+    def add_fluxes(self, nh, Gn, s):
+        g, bih, V = nh.grid, self.closure, self.other
+        u, v, Gu, Gv = nh.u.ptr, nh.v.ptr, Gn[0].ptr, Gn[1].ptr
+        kappa, cs, Gs = [bih.kappa_of(n) for n in nh.tracer_names], [c.ptr for c in nh.tracers], [G.ptr for G in Gn[3:]]
+        if V is None:
+            return self.add_to(g, bih.nu, u, v, Gu, Gv, len(cs), kappa or [0.0], cs or [None], Gs or [None], None, None, None, s)
+        S = self.scratch
+        Su, Sv = S[0].data_ptr(), S[1].data_ptr()
+        S.zero_()
+        V.add_to(g, u, v, Su, Sv, 0, None, None, s)
+        self.add_to(g, bih.nu, u, v, Gu, Gv, 0, None, None, None, Su, Sv, None, s)
+        for k, c, G in zip(kappa, cs, Gs):
+            S[0].zero_()
+            V.add_to(g, None, None, None, None, 1, [c], [Su], s)
+            self.add_to(g, 0.0, None, None, None, None, 1, [k], [c], [G], None, None, [Su], s)

@@ -92,8 +92,7 @@ class QuasiAdamsBashforth2TimeStepper(_TendencyStore):
 class NonhydrostaticModel:
     def __init__(self, grid, advection=None, tracers=(), timestepper="RungeKutta3", closure=None, buoyancy=None,
                  coriolis=None, forcing=None, stokes_drift=None, boundary_conditions=None,
-                 hydrostatic_pressure_anomaly="default", pressure_solver="default", math_mode=None, particles=None,
-                 _hydrostatic_container=False, _closure_halo=0):
+                 hydrostatic_pressure_anomaly="default", pressure_solver="default", math_mode=None, particles=None, _closure_halo=0):
         """math_mode: None keeps the grid's (default: the process default, ocn.set_math_mode); MATH_STRICT / MATH_FAST pin this
         model's arithmetic variant whatever other models of the process use (ocn_grid.math).
         particles: None or LagrangianParticles(...): moved to the architecture here and stepped with the pressure-corrected, halo-filled
@@ -122,18 +121,16 @@ class NonhydrostaticModel:
             raise NotImplementedError("only coriolis = FPlane(...) or BetaPlane(...) is implemented")
         if isinstance(coriolis, BetaPlane) and grid.topology[1] == Flat:
             raise NotImplementedError("BetaPlane needs a non-Flat y")
-        # (_hydrostatic_container: the HydrostaticFreeSurfaceModel builds this class as the container of its fields; it owns the κ fields of
-        # a ConvectiveAdjustmentVerticalDiffusivity or RiBasedVerticalDiffusivity and every launch of that closure, the container only carries
-        # the object; a ScalarBiharmonicDiffusivity never reaches the container, only the halo it needs: _closure_halo)
+        # (the HydrostaticFreeSurfaceModel builds this class as the container of its fields and gives it the closure that ocn_model_terms
+        # carries, an explicit ScalarDiffusivity or None, plus the halo that its own closure needs: _closure_halo; hydrostatic_closures.py)
         if isinstance(closure, ScalarBiharmonicDiffusivity):
             raise NotImplementedError("ScalarBiharmonicDiffusivity on NonhydrostaticModel is not implemented (its w fluxes need the "
                                       "three-dimensional ∇²ᶜᶜᶠ and the wall masks); HydrostaticFreeSurfaceModel takes "
                                       "HorizontalScalarBiharmonicDiffusivity (see DESIGN.md §5.2l)")
         if has_diffusivity_fields(closure):
-            if not _hydrostatic_container:
-                raise NotImplementedError(f"closure = {type(closure).__name__} on NonhydrostaticModel is not implemented (w would need "
-                                          "the Face-in-z rows of the field-valued implicit step); HydrostaticFreeSurfaceModel takes it (see DESIGN.md §5.2j)")
-        elif closure is not None and not isinstance(closure, (ScalarDiffusivity, AnisotropicMinimumDissipation, Smagorinsky)):
+            raise NotImplementedError(f"closure = {type(closure).__name__} on NonhydrostaticModel is not implemented (w would need "
+                                      "the Face-in-z rows of the field-valued implicit step); HydrostaticFreeSurfaceModel takes it (see DESIGN.md §5.2j)")
+        if closure is not None and not isinstance(closure, (ScalarDiffusivity, AnisotropicMinimumDissipation, Smagorinsky)):
             raise NotImplementedError("only closure = ScalarDiffusivity(...), AnisotropicMinimumDissipation(...), Smagorinsky(...) or "
                                       "SmagorinskyLilly(...) is implemented")
         # closure = ScalarDiffusivity(VerticallyImplicitTimeDiscretization(), ...): a z-Bounded grid on one GPU, stepped by the Python host
@@ -293,7 +290,7 @@ class NonhydrostaticModel:
         # is 0; the explicit part of the closure term is added by its own kernel and the implicit part follows every substep (implicit_step)
         self._implicit = is_vertically_implicit(closure)
         self._terms_noclosure = None
-        if self._implicit or has_diffusivity_fields(closure):  # (whose term has kernels of its own in both discretizations)
+        if self._implicit:
             self._terms_noclosure = _lib.CModelTerms()
             C.memmove(C.byref(self._terms_noclosure), C.byref(self._terms), C.sizeof(_lib.CModelTerms))
             self._terms_noclosure.closure, self._terms_noclosure.nu = 0, 0.0
@@ -617,10 +614,14 @@ def implicit_step(model, dt):
     """implicit_step!(field, solver, closure, ..., Δt) of every prognostic field -- u, v, w, then the tracers with their own κ -- in one
     launch: (1 - Δt ∂z κ ∂z) φⁿ⁺¹ = φ★ in place (vertically_implicit_diffusion_solver.jl).  Follows rk3_substep! with the stage Δt
     Δt (γ + ζ) (runge_kutta_3.jl:157-180) and ab2_step! with Δt (quasi_adams_bashforth_2.jl:144)."""
-    prog = model.prognostic_fields()
-    kappa = [model.closure.nu] * 3 + [model.closure.kappa_of(n) for n in model.tracer_names]
-    _lib.call("ocn_implicit_vertical_diffusion_step", model.grid.cref, len(prog), _lib.ptr_array([f.ptr for f in prog]),
-              _lib.i32_array([f.loc for f in prog]), (C.c_double * len(prog))(*kappa), float(dt), stream_ptr())
+    implicit_diffusion_step(model.grid, model.prognostic_fields(),
+                            [model.closure.nu] * 3 + [model.closure.kappa_of(n) for n in model.tracer_names], dt, stream_ptr())
+
+
+def implicit_diffusion_step(grid, fields, kappa, dt, s):
+    """the column solves of `fields`, each with its own number κ, in one launch"""
+    _lib.call("ocn_implicit_vertical_diffusion_step", grid.cref, len(fields), _lib.ptr_array([f.ptr for f in fields]),
+              _lib.i32_array([f.loc for f in fields]), (C.c_double * len(fields))(*kappa), float(dt), s)
 
 
 def _refresh_stokes_and_forcing(model):

@@ -170,9 +170,8 @@ def write_checkpoint(model, filepath):
         out[f"{ADDR}/η/data"] = model.eta.cpu().numpy().T
         out[f"{ADDR}/timestepper/Gⁿ/η/data"] = model._Geta.cpu().numpy().T
         out[f"{ADDR}/timestepper/G⁻/η/data"] = model._Geta_m.cpu().numpy().T
-        if getattr(model, "_ri", False):  # the time-averaged κᶜ, κᵘ of RiBasedVerticalDiffusivity are state (the reference does not checkpoint them)
-            for name in ("kappa_c", "kappa_u"):
-                out[f"{ADDR}/diffusivity_fields/{name}/data"] = model.diffusivity_fields[name].parent()
+        for name in model._closure.state_fields:  # the time-averaged κᶜ, κᵘ of RiBasedVerticalDiffusivity (the reference does not checkpoint them)
+            out[f"{ADDR}/diffusivity_fields/{name}/data"] = model.diffusivity_fields[name].parent()
         if model.split:
             out[f"{ADDR}/U/data"] = model.U.cpu().numpy().T
             out[f"{ADDR}/V/data"] = model.V.cpu().numpy().T
@@ -256,11 +255,11 @@ def set_from_checkpoint(model, filepath):
         model.clock.last_dt = float(z[f"{ADDR}/clock/last_Δt"])
     if hyd:
         model.update_state(compute_tendencies=False)
-        if getattr(model, "_ri", False):
+        if model._closure.state_fields:
             # update_state! has just advanced the time average from whatever the model held: put back the averaged κᶜ, κᵘ that the
             # checkpointed tendencies were computed with, so that the restart continues bit-identically
             with np.load(filepath if str(filepath).endswith(".npz") else str(filepath) + ".npz") as z:
-                for name in ("kappa_c", "kappa_u"):
+                for name in model._closure.state_fields:
                     key = f"{ADDR}/diffusivity_fields/{name}/data"
                     if key not in z.files:
                         raise KeyError(f"Field {name} of RiBasedVerticalDiffusivity does not exist in checkpoint and could not be restored.")

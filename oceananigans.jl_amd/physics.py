@@ -499,21 +499,6 @@ def HorizontalScalarBiharmonicDiffusivity(**kw):
     return ScalarBiharmonicDiffusivity(HorizontalFormulation(), **kw)
 
 
-def split_closure_tuple(closure):
-    """A closure, or one of the two-closure tuples that are implemented -- a ScalarBiharmonicDiffusivity with a closure that has κ fields,
-    in either order (closure_tuples.jl) -- -> (biharmonic or None, the other closure or None).  Every other tuple raises."""
-    if isinstance(closure, (tuple, list)):
-        bih = [c for c in closure if isinstance(c, ScalarBiharmonicDiffusivity)]
-        vertical = [c for c in closure if has_diffusivity_fields(c)]
-        if len(closure) != 2 or len(bih) != 1 or len(vertical) != 1:
-            raise NotImplementedError("closure tuples are not implemented, except (HorizontalScalarBiharmonicDiffusivity, "
-                                      "ConvectiveAdjustmentVerticalDiffusivity or RiBasedVerticalDiffusivity) in either order: give one closure")
-        return bih[0], vertical[0]
-    if isinstance(closure, ScalarBiharmonicDiffusivity):
-        return closure, None
-    return None, closure
-
-
 class AnisotropicMinimumDissipation:
     """AnisotropicMinimumDissipation(; C = 1/12, Cν = nothing, Cκ = nothing, Cb = nothing)
     (anisotropic_minimum_dissipation.jl:106-115): ExplicitTimeDiscretization, number (or per-tracer dict) Poincaré constants."""

@@ -218,7 +218,7 @@ def _restate_closure_term(ocn, r, bih, vertical):
         bs = [None] * (2 + len(tracers))
         if vertical:
             d = r.diffusivity_fields
-            b_u, b_v, b_c = CAN.vertical_fluxes(g, d["kappa_u"].parent(), u, v, [d["kappa_c"].parent()] * len(tracers), tracers, int(r._implicit))
+            b_u, b_v, b_c = CAN.vertical_fluxes(g, d["kappa_u"].parent(), u, v, [d["kappa_c"].parent()] * len(tracers), tracers, int(r._closure.implicit))
             bs = [b_u, b_v] + b_c
             seen["b"] = max(seen["b"], max(np.abs(x).max() for x in bs))
         for q, a, b in zip([0, 1] + [3 + n for n in range(len(tracers))], [a_u, a_v] + a_c, bs):
@@ -258,7 +258,7 @@ def _run_against_twin(ocn, kind, vertical=None, timestepper="QuasiAdamsBashforth
         r.time_step(DT)
     ocn.sync_device()
     # (a vertically implicit V keeps only the fluxes through the bottom and the top in the tendencies, which the default conditions make 0)
-    assert seen["calls"] >= 3 and seen["a"] > 1e-3 and (vertical is None or r._implicit or seen["b"] > 1e-3)
+    assert seen["calls"] >= 3 and seen["a"] > 1e-3 and (vertical is None or r._closure.implicit or seen["b"] > 1e-3)
     for name in ("u", "v", "w", "T", "S"):
         a, b = m.field(name).parent(), r.field(name).parent()
         assert np.isfinite(a).all(), name
@@ -307,7 +307,7 @@ def test_closure_tuple_steps_equal_the_twin_with_the_restated_sum(ocn, which, or
               "ri_based": lambda: ocn.RiBasedVerticalDiffusivity()}[which]()
         m = _run_against_twin(ocn, "split", vertical=V_, order=order)
     assert m.closure[order] is not V_ and m.closure[1 - order] is V_
-    assert m._implicit == (which != "cavd_explicit")
+    assert m._closure.implicit == (which != "cavd_explicit")
 
 
 # ---- 9. a property of the device result ------------------------------------------------------------------------------------------------------

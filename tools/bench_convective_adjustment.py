@@ -82,12 +82,12 @@ unstable = float((kc.interior_view()[:Nz] == 1.0).double().mean())
 print(f"grid {Nx}x{Nx}x{Nz}, dt = {dt:.4g} s (diffusion number dt convective_κz / Δz² = {dt * 1.0 / g.dz ** 2:.3g}), {100 * unstable:.1f} % of the faces unstable", flush=True)
 # ---- kernels
 nh = m._nh
-cl = m._closure_struct
+cl = m._closure.struct
 ms = device_ms(lambda: L.call("ocn_compute_convective_adjustment_diffusivities", g.cref, C.byref(nh._terms), C.byref(cl), kc.ptr, ku.ptr, 0))
 print(f"diffusivities: {ms:.3f} ms per launch, {32 * cells / ms / 1e9:.3f} TB/s of its 32 B/cell", flush=True)
 fields = [m.u, m.v] + list(m.tracers)
 work = [torch.clone(f.data) for f in fields]  # the solves run on copies: repeated in-place solves drive the fields to their column means
-tscr = m._ivd_scratch
+tscr = m._closure.ivd_scratch
 locs = [f.loc for f in fields]
 
 

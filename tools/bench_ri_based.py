@@ -84,7 +84,7 @@ nh = m._nh
 terms = C.byref(nh._terms)
 plain, filtered = ri_based().c_struct(), ri_based(horizontal_Ri_filter=ocn.FivePointHorizontalFilter()).c_struct()
 cacl = cavd().c_struct()
-tops = tuple(m._top_condition(name) for name in m._ri_carriers)
+tops = m._closure.top_conditions(nh)
 fused_call = lambda: L.call("ocn_compute_ri_based_diffusivities_fused", g.cref, terms, C.byref(plain), *tops, m.u.ptr, m.v.ptr, ri.ptr, kc.ptr, ku.ptr, 0)
 ri_call = lambda: L.call("ocn_compute_ri_number", g.cref, terms, m.u.ptr, m.v.ptr, ri.ptr, 0)
 dif_call = lambda cl: (lambda: L.call("ocn_compute_ri_based_diffusivities", g.cref, terms, C.byref(cl), *tops, ri.ptr, kc.ptr, ku.ptr, 0))
