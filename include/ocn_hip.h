@@ -590,6 +590,23 @@ int ocn_add_momentum_terms(const ocn_grid *grid, const ocn_model_terms *terms, c
 int ocn_compute_vector_invariant_momentum_tendencies(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
                                                      double *Gv, const double *eta /* or NULL: without - g grad(eta) */,
                                                      double gravitational_acceleration, void *stream);
+/* The same tendencies with an upwinding vector-invariant scheme (VectorInvariant with WENO(order=5) sub-schemes, WENOVectorInvariant(order=5),
+ * OnlySelfUpwinding; vector_invariant_advection.jl:325-339, 367-385, vector_invariant_self_upwinding.jl).  scheme_flags: which sub-schemes
+ * are WENO(order=5) instead of their conserving defaults -- OCN_VI_WENO_VORTICITY (vorticity_scheme), OCN_VI_WENO_VERTICAL (vertical_scheme
+ * and divergence_scheme, which the reference dispatches on together), OCN_VI_WENO_KINETIC_ENERGY (kinetic_energy_gradient_scheme; needs
+ * OCN_VI_WENO_VERTICAL, whose Centered(order=4) is the cross scheme) -- and OCN_VI_DEFAULT_STENCIL: the vorticity weights from the
+ * vorticity itself (DefaultStencil()) instead of from the velocities (VelocityStencil()).  No WENO bit set is the entry point above and is
+ * refused here.  Periodic x (not a partitioned one).  Reads u and v up to 3 cells, w up to 2 cells beyond the interior in x and y (Hx, Hy >= 3)
+ * and one plane beyond it in z (Hz >= 1: the order reduction next to the bottom and the surface keeps the z stencils inside).  One arithmetic
+ * variant (the reference's evaluation order) whatever the math mode. */
+#define OCN_VI_WENO_VORTICITY 1
+#define OCN_VI_WENO_VERTICAL 2
+#define OCN_VI_WENO_KINETIC_ENERGY 4
+#define OCN_VI_DEFAULT_STENCIL 8
+int ocn_compute_vector_invariant_weno_momentum_tendencies(const ocn_grid *grid, int32_t scheme_flags, const double *u, const double *v,
+                                                          const double *w, double *Gu, double *Gv,
+                                                          const double *eta /* or NULL: without - g grad(eta) */,
+                                                          double gravitational_acceleration, void *stream);
 /* SplitExplicitFreeSurface with the ForwardBackwardScheme (the SplitExplicitFreeSurfaces directory), (Periodic, Periodic) static grid of column
  * depth H; every 2-D quantity is an (Nx+2Hx) x (Ny+2Hy) plane like eta, of which only the interior is used.
  *   forcing:   compute_split_explicit_forcing! (compute_slow_tendencies.jl:12-32)

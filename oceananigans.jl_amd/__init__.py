@@ -43,7 +43,8 @@ from .solvers import (BatchedTridiagonalSolver, FFTBasedPoissonSolver, FourierTr
 
 
 from .hydrostatic import (AdamsBashforth3Scheme, ExplicitFreeSurface, ForwardBackwardScheme, HydrostaticFreeSurfaceModel, ImplicitFreeSurface, SplitExplicitFreeSurface,  # noqa: E402
-                          VectorInvariant)
+                          VectorInvariant, WENOVectorInvariant, EnergyConserving, EnstrophyConserving, VelocityStencil, DefaultStencil,
+                          FunctionStencil, OnlySelfUpwinding, CrossAndSelfUpwinding)
 
 
 def set_math_mode(mode):

@@ -531,6 +531,24 @@ int ocn_compute_vector_invariant_momentum_tendencies(const ocn_grid *grid, const
     OCN_REQUIRE(grid->Hz >= 1, "ocn_compute_vector_invariant_momentum_tendencies: needs a z halo");
     return launch_vector_invariant(grid, u, v, w, Gu, Gv, as_stream(stream), eta, gravitational_acceleration);
 }
+int ocn_compute_vector_invariant_weno_momentum_tendencies(const ocn_grid *grid, int32_t scheme_flags, const double *u, const double *v,
+                                                          const double *w, double *Gu, double *Gv, const double *eta,
+                                                          double gravitational_acceleration, void *stream)
+{
+    const char *who = "ocn_compute_vector_invariant_weno_momentum_tendencies";
+    int st = validate_hydrostatic(grid, who);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE_PERIODIC_X(who);
+    OCN_REQUIRE(u && v && w && Gu && Gv, "%s: null field pointer", who);
+    const int32_t weno = OCN_VI_WENO_VORTICITY | OCN_VI_WENO_VERTICAL | OCN_VI_WENO_KINETIC_ENERGY;
+    OCN_REQUIRE(!(scheme_flags & ~(weno | OCN_VI_DEFAULT_STENCIL)), "%s: unknown scheme flag bits in %d", who, (int)scheme_flags);
+    OCN_REQUIRE(scheme_flags & weno, "%s: no sub-scheme is WENO: that is ocn_compute_vector_invariant_momentum_tendencies", who);
+    OCN_REQUIRE(!(scheme_flags & OCN_VI_WENO_KINETIC_ENERGY) || (scheme_flags & OCN_VI_WENO_VERTICAL),
+                "%s: an upwinding kinetic-energy gradient needs an upwinding divergence scheme (its Centered(order=4) is the cross scheme)", who);
+    OCN_REQUIRE(grid->Hx >= 3 && grid->Hy >= 3 && grid->Hz >= 1, "%s: reads 3 cells beyond the interior in x and y and 1 plane in z; halo is (%d, %d, %d)",
+                who, grid->Hx, grid->Hy, grid->Hz);
+    return launch_vector_invariant_weno(grid, scheme_flags, u, v, w, Gu, Gv, eta, gravitational_acceleration, as_stream(stream));
+}
 int ocn_split_explicit_forcing(const ocn_grid *grid, const double *Gu, const double *Gu_previous, const double *Gv, const double *Gv_previous,
                                double chi, double *GU, double *GV, void *stream)
 {

@@ -165,6 +165,8 @@ int launch_xtri_finish(double *a1, const double *ly, const double *lz, int NyH, 
                        int R, hipStream_t stream);
 int launch_vector_invariant(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu, double *Gv,
                             hipStream_t stream, const double *eta = nullptr, double grav = 0.0);
+int launch_vector_invariant_weno(const ocn_grid *grid, int scheme_flags, const double *u, const double *v, const double *w, double *Gu,
+                                 double *Gv, const double *eta, double grav, hipStream_t stream);  // vector_invariant_weno.hip
 int launch_split_explicit_forcing(const ocn_grid *grid, const double *Gun, const double *Gum, const double *Gvn, const double *Gvm, double chi,
                                   double *GU, double *GV, hipStream_t stream);
 int launch_split_explicit_substeps(const ocn_grid *grid, int n, const double *weights, double dtau, double grav, double H, double *eta,

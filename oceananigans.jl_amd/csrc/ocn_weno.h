@@ -173,6 +173,49 @@ __device__ __forceinline__ double weno5(double S0, double S1, double S2, double 
 #endif
 }
 
+#if OCN_STRICT && !OCN_UPWIND
+// The same reconstruction of S with the weights taken from OTHER values on the same stencil points (the smoothness stencils of the
+// vector-invariant schemes, weno_interpolants.jl:350-363, 546-554): A alone (FunctionStencil), or A and B with
+// beta_r = (beta_r(A) + beta_r(B)) / 2 (VelocityStencil, beta_sum :278-286).  weno5() above is weno5_smooth(S, S).
+__device__ __forceinline__ void weno5_betas(const double *A, bool left, double &be0, double &be1, double &be2)
+{
+    const double a0 = left ? A[2] : A[3], a1 = left ? A[3] : A[2], a2 = left ? A[4] : A[1];
+    const double b0 = left ? A[1] : A[4], b1 = left ? A[2] : A[3], b2 = left ? A[3] : A[2];
+    const double c0 = left ? A[0] : A[5], c1 = left ? A[1] : A[4], c2 = left ? A[2] : A[3];
+    be0 = beta3(a0, a1, a2, 10., -31., 11., 25., -19., 4.);
+    be1 = beta3(b0, b1, b2, 4., -13., 5., 13., -13., 4.);
+    be2 = beta3(c0, c1, c2, 4., -19., 11., 25., -31., 10.);
+}
+__device__ __forceinline__ double weno5_weighted(const double *S, bool left, double be0, double be1, double be2)
+{
+    const double a0 = left ? S[2] : S[3], a1 = left ? S[3] : S[2], a2 = left ? S[4] : S[1];
+    const double b0 = left ? S[1] : S[4], b1 = left ? S[2] : S[3], b2 = left ? S[3] : S[2];
+    const double c0 = left ? S[0] : S[5], c1 = left ? S[1] : S[4], c2 = left ? S[2] : S[3];
+    const double tau = fabs(be0 - be2);
+    const double p0 = (OCN_W5P_00 * a0 + OCN_W5P_01 * a1) + OCN_W5P_02 * a2;
+    const double p1 = (OCN_W5P_10 * b0 + OCN_W5P_11 * b1) + OCN_W5P_12 * b2;
+    const double p2 = (OCN_W5P_20 * c0 + OCN_W5P_21 * c1) + OCN_W5P_22 * c2;
+    const double q0 = tau / (be0 + OCN_WENO_EPS), q1 = tau / (be1 + OCN_WENO_EPS), q2 = tau / (be2 + OCN_WENO_EPS);
+    const double al0 = OCN_C5_0 * (1 + q0 * q0), al1 = OCN_C5_1 * (1 + q1 * q1), al2 = OCN_C5_2 * (1 + q2 * q2);
+    const double sa = (al0 + al1) + al2;
+    const double w0 = al0 / sa, w1 = al1 / sa, w2 = al2 / sa;
+    return (w0 * p0 + w1 * p1) + w2 * p2;
+}
+__device__ __forceinline__ double weno5_smooth(const double *S, const double *A, bool left)
+{
+    double be0, be1, be2;
+    weno5_betas(A, left, be0, be1, be2);
+    return weno5_weighted(S, left, be0, be1, be2);
+}
+__device__ __forceinline__ double weno5_smooth2(const double *S, const double *A, const double *B, bool left)
+{
+    double a0, a1, a2, b0, b1, b2;
+    weno5_betas(A, left, a0, a1, a2);
+    weno5_betas(B, left, b0, b1, b2);
+    return weno5_weighted(S, left, (a0 + b0) / 2, (a1 + b1) / 2, (a2 + b2) / 2);
+}
+#endif
+
 // WENO3 (buffer scheme) from S = psi[n-2..n+1]
 __device__ __forceinline__ double weno3(double S0, double S1, double S2, double S3, bool left)
 {

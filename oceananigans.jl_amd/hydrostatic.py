@@ -8,9 +8,10 @@ flux-form momentum advection, QuasiAdamsBashforth2, static (Periodic, Periodic, 
 The horizontal momentum and tracer tendencies are the terms of the NonhydrostaticModel path (flux-form advection, FPlane,
 ∂x pHY′, the closure term of ocn_model_terms, flux boundary conditions) plus the barotropic pressure gradient g ∇η; w is diagnosed from
 continuity; there is no pressure solve.  momentum_advection = VectorInvariant() (the reference's default: enstrophy-conserving vorticity flux,
-energy-conserving vertical advection and kinetic-energy gradient) or a flux-form scheme.  The closures, what each of them launches and
+energy-conserving vertical advection and kinetic-energy gradient), VectorInvariant(...) / WENOVectorInvariant(order=5) with WENO(order=5)
+sub-schemes (csrc/vector_invariant_weno.hip, unfused) or a flux-form scheme.  The closures, what each of them launches and
 what each refuses: hydrostatic_closures.py.  NOT in this slice (each raises):
-SplitExplicitFreeSurface / ImplicitFreeSurface, upwinding / WENO vector-invariant variants, z-star coordinates,
+vector-invariant sub-schemes of another order or kind, cross upwinding, multi-dimensional stencils, z-star coordinates,
 a tracer advection scheme different from the momentum one, Distributed architectures.
 """
 import ctypes as C
@@ -19,6 +20,7 @@ import math
 import torch
 
 from . import _lib
+from .advection import WENO, UpwindBiased
 from .architectures import stream_ptr
 from .fields import fill_halo_regions
 from .grids import Bounded, Flat, FullyConnected, Periodic, RectilinearGrid, require_regular_xy
@@ -30,13 +32,198 @@ from .physics import Centered
 g_Earth = 9.80665  # Oceananigans.BuoyancyFormulations.g_Earth
 
 
-class VectorInvariant:
-    """VectorInvariant() with its defaults (Advection/vector_invariant_advection.jl:104-130): EnstrophyConserving vorticity scheme,
-    EnergyConserving vertical scheme and kinetic-energy gradient, second order."""
+class EnergyConserving:
+    """EnergyConserving() (vector_invariant_advection.jl:2-5)"""
     buffer = 1
 
     def __repr__(self):
-        return "VectorInvariant()"
+        return "EnergyConserving()"
+
+
+class EnstrophyConserving:
+    """EnstrophyConserving() (vector_invariant_advection.jl:3-6)"""
+    buffer = 1
+
+    def __repr__(self):
+        return "EnstrophyConserving()"
+
+
+class VelocityStencil:
+    """VelocityStencil() (weno_interpolants.jl:60-61): the smoothness of the vorticity reconstruction is measured on the velocities"""
+
+    def __repr__(self):
+        return "VelocityStencil()"
+
+
+class DefaultStencil:
+    """DefaultStencil() (weno_interpolants.jl:57-58): the smoothness is measured on the reconstructed variable"""
+
+    def __repr__(self):
+        return "DefaultStencil()"
+
+
+# the smoothness functions of the reference's default FunctionStencils (vector_invariant_self_upwinding.jl:18, 56-57), as names: the
+# kernel evaluates them; a FunctionStencil of anything else is a custom stencil, which is not implemented
+divergence_smoothness, u_smoothness, v_smoothness = "divergence_smoothness", "u_smoothness", "v_smoothness"
+
+
+class FunctionStencil:
+    """FunctionStencil(func) (weno_interpolants.jl:63-66)"""
+
+    def __init__(self, func):
+        self.func = func
+
+    def __repr__(self):
+        return f"FunctionStencil f = {getattr(self.func, '__name__', self.func)}"
+
+
+def _extract_centered_scheme(scheme):
+    """extract_centered_scheme (vector_invariant_upwinding.jl:26-27): an upwind scheme's advecting_velocity_scheme, of one order less
+    (weno_reconstruction.jl:119, upwind_biased_reconstruction.jl); anything else unchanged"""
+    if isinstance(scheme, (WENO, UpwindBiased)):
+        return f"Centered(order={scheme.order - 1})"
+    return scheme
+
+
+class OnlySelfUpwinding:
+    """OnlySelfUpwinding(; cross_scheme = Centered(), δU_stencil = FunctionStencil(divergence_smoothness), δV_stencil = the same,
+    δu²_stencil = FunctionStencil(u_smoothness), δv²_stencil = FunctionStencil(v_smoothness)) (vector_invariant_upwinding.jl:55-60)"""
+
+    def __init__(self, cross_scheme=None, δU_stencil=None, δV_stencil=None, δu2_stencil=None, δv2_stencil=None, **kw):
+        δu2_stencil, δv2_stencil = kw.pop("δu²_stencil", δu2_stencil), kw.pop("δv²_stencil", δv2_stencil)
+        if kw:
+            raise TypeError(f"OnlySelfUpwinding: unexpected keyword arguments {sorted(kw)}")
+        self.cross_scheme = _extract_centered_scheme(Centered() if cross_scheme is None else cross_scheme)
+        self.δU_stencil = FunctionStencil(divergence_smoothness) if δU_stencil is None else δU_stencil
+        self.δV_stencil = FunctionStencil(divergence_smoothness) if δV_stencil is None else δV_stencil
+        self.δu2_stencil = FunctionStencil(u_smoothness) if δu2_stencil is None else δu2_stencil
+        self.δv2_stencil = FunctionStencil(v_smoothness) if δv2_stencil is None else δv2_stencil
+
+    def has_default_stencils(self):
+        want = ((self.δU_stencil, divergence_smoothness), (self.δV_stencil, divergence_smoothness), (self.δu2_stencil, u_smoothness),
+                (self.δv2_stencil, v_smoothness))
+        return all(isinstance(s, FunctionStencil) and s.func is f for s, f in want)
+
+    def __repr__(self):
+        return "OnlySelfUpwinding"
+
+
+class CrossAndSelfUpwinding:
+    """CrossAndSelfUpwinding(; cross_scheme = Centered(), divergence_stencil = DefaultStencil(), δu²_stencil, δv²_stencil)
+    (vector_invariant_upwinding.jl:85-89).  Constructible; a VectorInvariant with it is not implemented."""
+
+    def __init__(self, cross_scheme=None, divergence_stencil=None, **kw):
+        self.cross_scheme = _extract_centered_scheme(Centered() if cross_scheme is None else cross_scheme)
+        self.divergence_stencil = DefaultStencil() if divergence_stencil is None else divergence_stencil
+        self.stencils = kw
+
+    def __repr__(self):
+        return "CrossAndSelfUpwinding"
+
+
+# scheme_flags of ocn_compute_vector_invariant_weno_momentum_tendencies (include/ocn_hip.h)
+VI_WENO_VORTICITY, VI_WENO_VERTICAL, VI_WENO_KINETIC_ENERGY, VI_DEFAULT_STENCIL = 1, 2, 4, 8
+
+
+class VectorInvariant:
+    """VectorInvariant(; vorticity_scheme = EnstrophyConserving(), vorticity_stencil = VelocityStencil(), vertical_scheme = EnergyConserving(),
+    divergence_scheme = vertical_scheme, kinetic_energy_gradient_scheme = divergence_scheme,
+    upwinding = OnlySelfUpwinding(; cross_scheme = divergence_scheme), multi_dimensional_stencil = false)
+    (Advection/vector_invariant_advection.jl:104-128).  VectorInvariant() is the model's default: second order, conserving, fusable.
+
+    Implemented: every sub-scheme either its conserving default or WENO(order=5), with
+      * vorticity_scheme  EnstrophyConserving() or WENO(), vorticity_stencil VelocityStencil() or DefaultStencil();
+      * vertical_scheme   EnergyConserving() or WENO(), divergence_scheme of the same kind (the reference dispatches the term
+                          "vertical advection + divergence flux" on both together);
+      * kinetic_energy_gradient_scheme  EnergyConserving() or WENO(); WENO() needs a WENO() divergence_scheme: the cross terms are
+                          interpolated with extract_centered_scheme(divergence_scheme), and the reference has no symmetric interpolation
+                          for EnergyConserving();
+      * upwinding         the default OnlySelfUpwinding with its default FunctionStencils.
+    Everything else raises NotImplementedError here, before anything is allocated."""
+
+    def __init__(self, vorticity_scheme=None, vorticity_stencil=None, vertical_scheme=None, divergence_scheme=None,
+                 kinetic_energy_gradient_scheme=None, upwinding=None, multi_dimensional_stencil=False):
+        self.vorticity_scheme = EnstrophyConserving() if vorticity_scheme is None else vorticity_scheme
+        self.vorticity_stencil = VelocityStencil() if vorticity_stencil is None else vorticity_stencil
+        self.vertical_scheme = EnergyConserving() if vertical_scheme is None else vertical_scheme
+        self.divergence_scheme = self.vertical_scheme if divergence_scheme is None else divergence_scheme
+        self.kinetic_energy_gradient_scheme = self.divergence_scheme if kinetic_energy_gradient_scheme is None else kinetic_energy_gradient_scheme
+        self.upwinding = OnlySelfUpwinding(cross_scheme=self.divergence_scheme) if upwinding is None else upwinding
+        self.multi_dimensional_stencil = bool(multi_dimensional_stencil)
+        self._validate()
+        weno = lambda s: isinstance(s, WENO)
+        self.scheme_flags = ((VI_WENO_VORTICITY if weno(self.vorticity_scheme) else 0) | (VI_WENO_VERTICAL if weno(self.vertical_scheme) else 0)
+                             | (VI_WENO_KINETIC_ENERGY if weno(self.kinetic_energy_gradient_scheme) else 0))
+        if weno(self.vorticity_scheme) and isinstance(self.vorticity_stencil, DefaultStencil):
+            self.scheme_flags |= VI_DEFAULT_STENCIL
+        self.upwinds = bool(self.scheme_flags & (VI_WENO_VORTICITY | VI_WENO_VERTICAL | VI_WENO_KINETIC_ENERGY))
+        schemes = (self.vorticity_scheme, self.divergence_scheme, self.kinetic_energy_gradient_scheme)
+        # required_halo_size_x/y/z (:241-251): one more than the widest horizontal sub-scheme unless that is 1; z is the vertical scheme's
+        hx = max(s.buffer for s in schemes)
+        hx = hx if hx == 1 else hx + 1
+        self.required_halo = (hx, hx, self.vertical_scheme.buffer)
+        self.buffer = max(s.buffer for s in schemes + (self.vertical_scheme,))  # N of VectorInvariant{N} (:112-118)
+
+    def _validate(self):
+        name = "VectorInvariant"
+        if self.multi_dimensional_stencil:
+            raise NotImplementedError(f"{name}: multi_dimensional_stencil = true is not implemented (use the dimension-by-dimension reconstruction)")
+        for label, s, conserving in (("vorticity_scheme", self.vorticity_scheme, EnstrophyConserving),
+                                     ("vertical_scheme", self.vertical_scheme, EnergyConserving),
+                                     ("divergence_scheme", self.divergence_scheme, EnergyConserving),
+                                     ("kinetic_energy_gradient_scheme", self.kinetic_energy_gradient_scheme, EnergyConserving)):
+            if isinstance(s, UpwindBiased):
+                raise NotImplementedError(f"{name}: {label} = {s!r} is not implemented; use WENO(order=5) or {conserving.__name__}()")
+            if label == "vorticity_scheme" and isinstance(s, EnergyConserving):
+                raise NotImplementedError(f"{name}: vorticity_scheme = EnergyConserving() is not implemented; use EnstrophyConserving() or WENO(order=5)")
+            if not isinstance(s, (WENO, conserving)):
+                raise NotImplementedError(f"{name}: {label} = {s!r} is not implemented; use WENO(order=5) or {conserving.__name__}()")
+        if isinstance(self.divergence_scheme, WENO) != isinstance(self.vertical_scheme, WENO):
+            raise NotImplementedError(f"{name}: divergence_scheme must be of the kind of vertical_scheme (both WENO(order=5) or both "
+                                      "EnergyConserving()): the reference computes their term together")
+        if isinstance(self.kinetic_energy_gradient_scheme, WENO) and not isinstance(self.divergence_scheme, WENO):
+            raise NotImplementedError(f"{name}: kinetic_energy_gradient_scheme = WENO() needs vertical_scheme = WENO(): its cross terms are "
+                                      "interpolated with the divergence scheme's Centered(order=4)")
+        if not isinstance(self.vorticity_stencil, (VelocityStencil, DefaultStencil)):
+            raise NotImplementedError(f"{name}: vorticity_stencil must be VelocityStencil() or DefaultStencil()")
+        if isinstance(self.upwinding, CrossAndSelfUpwinding):
+            raise NotImplementedError(f"{name}: CrossAndSelfUpwinding is not implemented; use the default OnlySelfUpwinding")
+        if not isinstance(self.upwinding, OnlySelfUpwinding):
+            raise NotImplementedError(f"{name}: upwinding must be OnlySelfUpwinding(...)")
+        if not self.upwinding.has_default_stencils():
+            raise NotImplementedError(f"{name}: a custom FunctionStencil is not implemented; leave the stencils of OnlySelfUpwinding at "
+                                      "their defaults (divergence_smoothness, u_smoothness, v_smoothness)")
+        if isinstance(self.divergence_scheme, WENO) and self.upwinding.cross_scheme != _extract_centered_scheme(self.divergence_scheme):
+            raise NotImplementedError(f"{name}: OnlySelfUpwinding with a cross_scheme other than the default (the divergence scheme's) is not implemented")
+
+    def __repr__(self):
+        if not self.upwinds:
+            return "VectorInvariant()"
+        return (f"VectorInvariant(vorticity_scheme={self.vorticity_scheme!r}, vorticity_stencil={self.vorticity_stencil!r}, "
+                f"vertical_scheme={self.vertical_scheme!r}, kinetic_energy_gradient_scheme={self.kinetic_energy_gradient_scheme!r})")
+
+
+def WENOVectorInvariant(order=None, vorticity_order=None, vertical_order=None, divergence_order=None, kinetic_energy_gradient_order=None,
+                        upwinding=None, vorticity_stencil=None, multi_dimensional_stencil=False):
+    """WENOVectorInvariant(; upwinding, vorticity_stencil = VelocityStencil(), order, vorticity_order, vertical_order, divergence_order,
+    kinetic_energy_gradient_order, multi_dimensional_stencil = false) (vector_invariant_advection.jl:190-237): without `order` the
+    vorticity scheme is of order 9 and the others of order 5; with it, every order not given is `order`.  Only order 5 is implemented."""
+    if order is None:
+        defaults = dict(vorticity=9, vertical=5, divergence=5, kinetic_energy_gradient=5)
+    else:
+        defaults = dict.fromkeys(("vorticity", "vertical", "divergence", "kinetic_energy_gradient"), order)
+    given = dict(vorticity=vorticity_order, vertical=vertical_order, divergence=divergence_order, kinetic_energy_gradient=kinetic_energy_gradient_order)
+    orders = {k: defaults[k] if v is None else v for k, v in given.items()}
+    if order is None and vorticity_order is None:
+        raise NotImplementedError("WENOVectorInvariant(): the default vorticity scheme is WENO(order=9), which is not implemented; "
+                                  "pass `order=5` or `vorticity_order=5`")
+    for k, o in orders.items():
+        if o != 5:
+            raise NotImplementedError(f"WENOVectorInvariant: {k}_order = {o} is not implemented; every order must be 5 "
+                                      "(pass `order=5` or `vorticity_order=5`)")
+    return VectorInvariant(vorticity_scheme=WENO(order=5), vorticity_stencil=vorticity_stencil, vertical_scheme=WENO(order=5),
+                           divergence_scheme=WENO(order=5), kinetic_energy_gradient_scheme=WENO(order=5), upwinding=upwinding,
+                           multi_dimensional_stencil=multi_dimensional_stencil)
 
 
 class ExplicitFreeSurface:
@@ -192,6 +379,17 @@ class HydrostaticFreeSurfaceModel:
         if momentum_advection is None:
             momentum_advection = VectorInvariant()  # the reference's default (hydrostatic_free_surface_model.jl)
         self.vector_invariant = isinstance(momentum_advection, VectorInvariant)
+        self.momentum_advection = momentum_advection
+        # an upwinding vector-invariant scheme takes the reference's launch sequence (its kernel has no fused epilogue)
+        self._vi_weno = self.vector_invariant and momentum_advection.upwinds
+        if self._vi_weno:
+            if fused:
+                raise NotImplementedError("fused = True with an upwinding VectorInvariant / WENOVectorInvariant is not implemented: "
+                                          "leave fused at its default (False with these schemes)")
+            if hasattr(arch, "partition"):
+                raise NotImplementedError("an upwinding VectorInvariant / WENOVectorInvariant on a Distributed grid is not implemented: a "
+                                          "slab-partitioned model needs the fused step; use momentum_advection = VectorInvariant()")
+            fused = False
         if self.vector_invariant:
             # the container model below carries the tracer scheme (reference default: Centered()); momentum goes its own way
             container_advection = tracer_advection if tracer_advection is not None else Centered()
@@ -210,7 +408,7 @@ class HydrostaticFreeSurfaceModel:
         self._nh = NonhydrostaticModel(grid, advection=container_advection, tracers=tracers, timestepper="QuasiAdamsBashforth2",
                                        closure=self._closure.container_closure, buoyancy=buoyancy, coriolis=coriolis,
                                        boundary_conditions=boundary_conditions, pressure_solver=None, math_mode=math_mode,
-                                       _closure_halo=self._closure.halo)
+                                       _closure_halo=self._required_halo())
         nh = self._nh
         grid = nh.grid  # (halo-inflated / math-mode-pinned by the container model)
         self.diffusivity_fields = self._closure.allocate(nh)
@@ -264,6 +462,13 @@ class HydrostaticFreeSurfaceModel:
         self.update_state(compute_tendencies=False)
 
     # ---- helpers -------------------------------------------------------------------------------------------------------
+    def _required_halo(self):
+        """what the closure needs (one number for all directions) and, per direction, what the momentum scheme needs
+        (required_halo_size_x/y/z(::VectorInvariant), vector_invariant_advection.jl:241-251); the container adds the tracer scheme's"""
+        if not self._vi_weno:
+            return self._closure.halo
+        return tuple(max(self._closure.halo, h) for h in self.momentum_advection.required_halo)
+
     def field(self, name):
         return self._nh.field(name)
 
@@ -302,7 +507,10 @@ class HydrostaticFreeSurfaceModel:
         grav = self.free_surface.gravitational_acceleration
         # explicit_barotropic_pressure_x/y_gradient: g ∇η for the ExplicitFreeSurface, zero for the split-explicit one
         eta_ptr = None if (self.split or self.implicit) else self.eta.data_ptr()
-        if self.vector_invariant:                                                         # - U_dot_∇u - g ∂x η, - U_dot_∇v - g ∂y η
+        if self._vi_weno:                                                                 # the same with upwinding reconstructions
+            _lib.call("ocn_compute_vector_invariant_weno_momentum_tendencies", g.cref, self.momentum_advection.scheme_flags, self.u.ptr,
+                      self.v.ptr, self.w.ptr, Gn[0].ptr, Gn[1].ptr, eta_ptr, grav, s)
+        elif self.vector_invariant:                                                       # - U_dot_∇u - g ∂x η, - U_dot_∇v - g ∂y η
             _lib.call("ocn_compute_vector_invariant_momentum_tendencies", g.cref, self.u.ptr, self.v.ptr, self.w.ptr, Gn[0].ptr,
                       Gn[1].ptr, eta_ptr, grav, s)
         else:

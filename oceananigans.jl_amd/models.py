@@ -157,14 +157,16 @@ class NonhydrostaticModel:
         # grid with the halo its advection scheme and closure need, never with a smaller one than the user gave.
         # adapt_advection_order (a lower-order scheme in a direction with too few cells) is not supported: that raises.
         # (required_halo_size_x/y/z of a ScalarBiharmonicDiffusivity: 2 in every direction)
-        required = max(advection.buffer, 1 if closure is not None else 0, _closure_halo, 1)
+        # (_closure_halo: what the hydrostatic model's own closure and momentum scheme need, one number or one per direction)
+        extra = tuple(_closure_halo) if isinstance(_closure_halo, (tuple, list)) else (_closure_halo,) * 3
+        required = tuple(max(advection.buffer, 1 if closure is not None else 0, e, 1) for e in extra)
         H = (grid.Hx, grid.Hy, grid.Hz)
         for d, (N, t) in enumerate(zip(grid.size, grid.topology)):
             if t != Flat and N < advection.buffer:
                 raise NotImplementedError(f"{advection!r} needs size >= {advection.buffer} in dimension {d + 1} (got N={N}); "
                                           "adapt_advection_order is not implemented")
-        if any(t != Flat and h < required for h, t in zip(H, grid.topology)):
-            grid = grid.with_halo(tuple(max(h, required) for h in H))
+        if any(t != Flat and h < r for h, r, t in zip(H, required, grid.topology)):
+            grid = grid.with_halo(tuple(max(h, r) for h, r in zip(H, required)))
         if math_mode is not None:
             grid = grid.with_math_mode(math_mode)
         self.grid = grid
