@@ -687,7 +687,15 @@ int ocn_hydrostatic_momentum_ab2_step(const ocn_grid *grid, const ocn_model_term
 int ocn_barotropic_corrector_and_w(const ocn_grid *grid, const double *u_star, const double *v_star, double *u, double *v, double *w,
                                    const double *U, const double *V, const double *U_star, const double *V_star, double column_depth,
                                    void *stream);
-/* fill_halo_regions!(eta): periodic x, y halos of the free-surface plane */
+/* The entry points of the hydrostatic model below take (Periodic, Periodic, Bounded) grids.  These also take (Periodic, Bounded, Bounded)
+ * channels and (Bounded, Bounded, Bounded) basins (one GPU, regular x and y), where u, v, w / c each have their own parent layout and the
+ * planes follow (eta: Center, Center; U, GU, Qu like u; V, GV, Qv like v): ocn_compute_w_from_continuity, ocn_fill_free_surface_halos,
+ * ocn_add_barotropic_pressure_gradient, ocn_compute_vector_invariant_momentum_tendencies, ocn_compute_barotropic_mode,
+ * ocn_split_explicit_forcing, ocn_split_explicit_substeps, ocn_barotropic_split_explicit_corrector, ocn_explicit_free_surface_ab2_step,
+ * ocn_implicit_free_surface_rhs, ocn_barotropic_pressure_correction.  They run over 1:Nx, 1:Ny (the west / south wall face included, as
+ * the reference's launches do); the wall-normal velocity on the wall faces is reset by the halo fill with fill_boundary_normal_velocities. */
+/* fill_halo_regions!(eta): periodic x, y halos of the free-surface plane; along a Bounded direction the default no-flux condition (the
+ * first halo cell) */
 int ocn_fill_free_surface_halos(const ocn_grid *grid, double *eta, void *stream);
 /* _compute_w_from_continuity! (compute_w_from_continuity.jl:31-40) for every parent column with east / north neighbours */
 int ocn_compute_w_from_continuity(const ocn_grid *grid, const double *u, const double *v, double *w, void *stream);

@@ -508,16 +508,34 @@ int ocn_add_momentum_terms(const ocn_grid *grid, const ocn_model_terms *terms, c
     OCN_REQUIRE(grid->Hx >= 1 && grid->Hy >= 1 && (grid->tz == OCN_FLAT || grid->Hz >= 1), "halo >= 1 required");
     if (!(terms->coriolis || terms->closure || terms->buoyancy)) return OCN_SUCCESS;
     TermsDev t = to_dev(*terms);
+    if (!xy_periodic(grid))  // walls in x / y: per-field parent layouts (general.hip), as ocn_compute_momentum_tendencies_terms dispatches
+        return OCN_LAUNCH(grid, launch_momentum_extra_general, grid, t, u, v, w, Gu, Gv, Gw, range, as_stream(stream), nullptr, nullptr, nullptr);
     return OCN_LAUNCH(grid, launch_momentum_extra, grid, t, u, v, w, Gu, Gv, Gw, range, as_stream(stream));
 }
 
-static int validate_hydrostatic(const ocn_grid *grid, const char *who)
+// the grids of hydrostatic_walls.hip: walls in y (a channel) or in x and y (a closed basin), regular and not partitioned
+static bool hydrostatic_walls(const ocn_grid *grid)
 {
+    return (grid->tx == OCN_PERIODIC || grid->tx == OCN_BOUNDED) && grid->ty == OCN_BOUNDED && grid->tz == OCN_BOUNDED;
+}
+// walls_ok: the entry point has kernels for (Periodic, Bounded, Bounded) and (Bounded, Bounded, Bounded) grids as well; the others say
+// which topology they need
+static int validate_hydrostatic(const ocn_grid *grid, const char *who, bool walls_ok = false)
+{
+    OCN_REQUIRE(grid, "%s: null grid", who);
+    if (hydrostatic_walls(grid)) {
+        OCN_REQUIRE(walls_ok, "%s: this entry point of the hydrostatic slice needs a (Periodic, Periodic, Bounded) grid", who);
+        int st = validate_grid_any(grid);
+        if (st != OCN_SUCCESS) return st;
+        OCN_REQUIRE(grid->Hx >= 1 && grid->Hy >= 1, "%s: needs x, y halos", who);
+        return OCN_SUCCESS;
+    }
     int st = validate_grid(grid);
     if (st != OCN_SUCCESS) return st;
     // x may be the partitioned direction of a slab-x rank (FullyConnected: halos come from the neighbours, interior arithmetic as Periodic)
     OCN_REQUIRE((grid->tx == OCN_PERIODIC || grid->tx == OCN_FULLY_CONNECTED) && grid->ty == OCN_PERIODIC && grid->tz == OCN_BOUNDED,
-                "%s: the hydrostatic slice supports (Periodic, Periodic, Bounded) grids", who);
+                walls_ok ? "%s: the hydrostatic slice supports (Periodic, Periodic | Bounded, Bounded) and (Bounded, Bounded, Bounded) grids"
+                         : "%s: the hydrostatic slice supports (Periodic, Periodic, Bounded) grids", who);
     OCN_REQUIRE(grid->Hx >= 1 && grid->Hy >= 1, "%s: needs x, y halos", who);
     return OCN_SUCCESS;
 }
@@ -525,10 +543,11 @@ static int validate_hydrostatic(const ocn_grid *grid, const char *who)
 int ocn_compute_vector_invariant_momentum_tendencies(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
                                                      double *Gv, const double *eta, double gravitational_acceleration, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_compute_vector_invariant_momentum_tendencies");
+    int st = validate_hydrostatic(grid, "ocn_compute_vector_invariant_momentum_tendencies", true);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(u && v && w && Gu && Gv, "ocn_compute_vector_invariant_momentum_tendencies: null field pointer");
     OCN_REQUIRE(grid->Hz >= 1, "ocn_compute_vector_invariant_momentum_tendencies: needs a z halo");
+    if (hydrostatic_walls(grid)) return launch_vector_invariant_walls(grid, u, v, w, Gu, Gv, eta, gravitational_acceleration, as_stream(stream));
     return launch_vector_invariant(grid, u, v, w, Gu, Gv, as_stream(stream), eta, gravitational_acceleration);
 }
 int ocn_compute_vector_invariant_weno_momentum_tendencies(const ocn_grid *grid, int32_t scheme_flags, const double *u, const double *v,
@@ -552,64 +571,74 @@ int ocn_compute_vector_invariant_weno_momentum_tendencies(const ocn_grid *grid, 
 int ocn_split_explicit_forcing(const ocn_grid *grid, const double *Gu, const double *Gu_previous, const double *Gv, const double *Gv_previous,
                                double chi, double *GU, double *GV, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_split_explicit_forcing");
+    int st = validate_hydrostatic(grid, "ocn_split_explicit_forcing", true);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(Gu && Gu_previous && Gv && Gv_previous && GU && GV, "ocn_split_explicit_forcing: null pointer");
+    if (hydrostatic_walls(grid)) return launch_split_explicit_forcing_walls(grid, Gu, Gu_previous, Gv, Gv_previous, chi, GU, GV, as_stream(stream));
     return launch_split_explicit_forcing(grid, Gu, Gu_previous, Gv, Gv_previous, chi, GU, GV, as_stream(stream));
 }
 int ocn_split_explicit_substeps(const ocn_grid *grid, int32_t n, const double *weights, double dtau, double gravitational_acceleration,
                                 double column_depth, double *eta, double *U, double *V, double *eta_filtered, double *U_filtered,
                                 double *V_filtered, const double *GU, const double *GV, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_split_explicit_substeps");
+    int st = validate_hydrostatic(grid, "ocn_split_explicit_substeps", true);
     if (st != OCN_SUCCESS) return st;
-    OCN_REQUIRE_PERIODIC_X("ocn_split_explicit_substeps");
+    OCN_REQUIRE(grid->tx != OCN_FULLY_CONNECTED, "ocn_split_explicit_substeps wraps x periodically: not for a partitioned (FullyConnected) x");
     OCN_REQUIRE(n >= 1 && weights, "ocn_split_explicit_substeps: needs n >= 1 averaging weights (host array)");
     OCN_REQUIRE(eta && U && V && eta_filtered && U_filtered && V_filtered && GU && GV, "ocn_split_explicit_substeps: null pointer");
+    if (hydrostatic_walls(grid))
+        return launch_split_explicit_substeps_walls(grid, n, weights, dtau, gravitational_acceleration, column_depth, eta, U, V, eta_filtered,
+                                                    U_filtered, V_filtered, GU, GV, as_stream(stream));
     return launch_split_explicit_substeps(grid, n, weights, dtau, gravitational_acceleration, column_depth, eta, U, V, eta_filtered, U_filtered,
                                           V_filtered, GU, GV, as_stream(stream));
 }
 int ocn_compute_barotropic_mode(const ocn_grid *grid, const double *u, const double *v, double *U, double *V, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_compute_barotropic_mode");
+    int st = validate_hydrostatic(grid, "ocn_compute_barotropic_mode", true);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(u && v && U && V, "ocn_compute_barotropic_mode: null pointer");
+    if (hydrostatic_walls(grid)) return launch_barotropic_mode_walls(grid, u, v, U, V, as_stream(stream));
     return launch_barotropic_mode(grid, u, v, U, V, as_stream(stream));
 }
 int ocn_barotropic_split_explicit_corrector(const ocn_grid *grid, double *u, double *v, const double *U, const double *V, double *U_filtered,
                                             double *V_filtered, double column_depth, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_barotropic_split_explicit_corrector");
+    int st = validate_hydrostatic(grid, "ocn_barotropic_split_explicit_corrector", true);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(u && v && U && V && U_filtered && V_filtered, "ocn_barotropic_split_explicit_corrector: null pointer");
+    if (hydrostatic_walls(grid))
+        return launch_barotropic_corrector_walls(grid, u, v, U, V, U_filtered, V_filtered, column_depth, as_stream(stream));
     return launch_barotropic_corrector(grid, u, v, U, V, U_filtered, V_filtered, column_depth, as_stream(stream));
 }
 int ocn_fill_free_surface_halos(const ocn_grid *grid, double *eta, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_fill_free_surface_halos");
+    int st = validate_hydrostatic(grid, "ocn_fill_free_surface_halos", true);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(eta, "ocn_fill_free_surface_halos: null pointer");
+    if (hydrostatic_walls(grid)) return launch_plane_halo_walls(grid, eta, as_stream(stream));
     return launch_plane_halo(grid, eta, as_stream(stream));
 }
 int ocn_compute_w_from_continuity(const ocn_grid *grid, const double *u, const double *v, double *w, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_compute_w_from_continuity");
+    int st = validate_hydrostatic(grid, "ocn_compute_w_from_continuity", true);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(u && v && w, "ocn_compute_w_from_continuity: null field pointer");
+    if (hydrostatic_walls(grid)) return launch_w_from_continuity_walls(grid, u, v, w, as_stream(stream));
     return launch_w_from_continuity(grid, u, v, w, as_stream(stream));
 }
 int ocn_add_barotropic_pressure_gradient(const ocn_grid *grid, double gravitational_acceleration, const double *eta, double *Gu, double *Gv,
                                          void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_add_barotropic_pressure_gradient");
+    int st = validate_hydrostatic(grid, "ocn_add_barotropic_pressure_gradient", true);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(eta && Gu && Gv, "ocn_add_barotropic_pressure_gradient: null pointer");
+    if (hydrostatic_walls(grid)) return launch_barotropic_gradient_walls(grid, gravitational_acceleration, eta, Gu, Gv, as_stream(stream));
     return launch_barotropic_gradient(grid, gravitational_acceleration, eta, Gu, Gv, as_stream(stream));
 }
 int ocn_explicit_free_surface_ab2_step(const ocn_grid *grid, const double *w, double *eta, double *G_eta, const double *G_eta_previous,
                                        double dt, double chi, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_explicit_free_surface_ab2_step");
+    int st = validate_hydrostatic(grid, "ocn_explicit_free_surface_ab2_step", true);  // (w and η share x / y extents: one kernel)
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(w && eta && G_eta && G_eta_previous, "ocn_explicit_free_surface_ab2_step: null pointer");
     return launch_free_surface_ab2(grid, w, eta, G_eta, G_eta_previous, dt, chi, as_stream(stream));
@@ -1088,19 +1117,23 @@ int ocn_split_explicit_substeps_blocked(const ocn_grid *grid, int32_t n, const d
 int ocn_implicit_free_surface_rhs(const ocn_grid *grid, const double *u, const double *v, const double *eta, double gravitational_acceleration,
                                   double dt, double *Qu, double *Qv, double *rhs, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_implicit_free_surface_rhs");
+    int st = validate_hydrostatic(grid, "ocn_implicit_free_surface_rhs", true);
     if (st != OCN_SUCCESS) return st;
-    OCN_REQUIRE_PERIODIC_X("ocn_implicit_free_surface_rhs");
+    OCN_REQUIRE(grid->tx != OCN_FULLY_CONNECTED, "ocn_implicit_free_surface_rhs wraps x periodically: not for a partitioned (FullyConnected) x");
     OCN_REQUIRE(u && v && eta && Qu && Qv && rhs, "ocn_implicit_free_surface_rhs: null pointer");
     OCN_REQUIRE(dt > 0, "ocn_implicit_free_surface_rhs: dt must be positive");
+    if (hydrostatic_walls(grid))
+        return launch_implicit_free_surface_rhs_walls(grid, u, v, eta, gravitational_acceleration, dt, Qu, Qv, rhs, as_stream(stream));
     return launch_implicit_free_surface_rhs(grid, u, v, eta, gravitational_acceleration, dt, Qu, Qv, rhs, as_stream(stream));
 }
 int ocn_barotropic_pressure_correction(const ocn_grid *grid, double *u, double *v, const double *eta, double gravitational_acceleration,
                                        double dt, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_barotropic_pressure_correction");
+    int st = validate_hydrostatic(grid, "ocn_barotropic_pressure_correction", true);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(u && v && eta, "ocn_barotropic_pressure_correction: null pointer");
+    if (hydrostatic_walls(grid))
+        return launch_barotropic_pressure_correction_walls(grid, u, v, eta, gravitational_acceleration, dt, as_stream(stream));
     return launch_barotropic_pressure_correction(grid, u, v, eta, gravitational_acceleration, dt, as_stream(stream));
 }
 

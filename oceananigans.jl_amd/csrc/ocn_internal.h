@@ -192,6 +192,24 @@ int launch_w_from_continuity(const ocn_grid *grid, const double *u, const double
 int launch_barotropic_gradient(const ocn_grid *grid, double grav, const double *eta, double *Gu, double *Gv, hipStream_t stream);
 int launch_free_surface_ab2(const ocn_grid *grid, const double *w, double *eta, double *Gn, const double *Gm, double dt, double chi,
                             hipStream_t stream);
+// the hydrostatic kernels on grids with walls in y or in x and y (hydrostatic_walls.hip): per-location parent layouts and planes
+int launch_w_from_continuity_walls(const ocn_grid *grid, const double *u, const double *v, double *w, hipStream_t stream);
+int launch_vector_invariant_walls(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu, double *Gv,
+                                  const double *eta, double grav, hipStream_t stream);
+int launch_barotropic_gradient_walls(const ocn_grid *grid, double grav, const double *eta, double *Gu, double *Gv, hipStream_t stream);
+int launch_barotropic_pressure_correction_walls(const ocn_grid *grid, double *u, double *v, const double *eta, double grav, double dt,
+                                                hipStream_t stream);
+int launch_plane_halo_walls(const ocn_grid *grid, double *plane, hipStream_t stream);
+int launch_split_explicit_forcing_walls(const ocn_grid *grid, const double *Gun, const double *Gum, const double *Gvn, const double *Gvm,
+                                        double chi, double *GU, double *GV, hipStream_t stream);
+int launch_barotropic_mode_walls(const ocn_grid *grid, const double *u, const double *v, double *U, double *V, hipStream_t stream);
+int launch_barotropic_corrector_walls(const ocn_grid *grid, double *u, double *v, const double *U, const double *V, double *Ub, double *Vb,
+                                      double H, hipStream_t stream);
+int launch_split_explicit_substeps_walls(const ocn_grid *grid, int n, const double *weights, double dtau, double grav, double H, double *eta,
+                                         double *U, double *V, double *etab, double *Ub, double *Vb, const double *GU, const double *GV,
+                                         hipStream_t stream);
+int launch_implicit_free_surface_rhs_walls(const ocn_grid *grid, const double *u, const double *v, const double *eta, double grav, double dt,
+                                           double *Qu, double *Qv, double *rhs, hipStream_t stream);
 int launch_halo_plane_x(const ocn_grid *grid, double *field, int loc, int which, double *buf, int unpack, hipStream_t stream);
 int launch_halo_pack_x_fields(const ocn_grid *grid, const FieldTuple &ft, double *west, double *east, int unpack, hipStream_t stream);
 int launch_rowdct(int Nx, int Ny, int Nz, RowDCT mode, double *data, const double *tw, const double *wd, const double *lx, const double *ly,

@@ -1,5 +1,7 @@
 """First slice of the reference's HydrostaticFreeSurfaceModel on the HIP backend: ExplicitFreeSurface,
-flux-form momentum advection, QuasiAdamsBashforth2, static (Periodic, Periodic, Bounded) RectilinearGrid, one GPU.
+flux-form momentum advection, QuasiAdamsBashforth2, static (Periodic, Periodic, Bounded) RectilinearGrid, one GPU.  (Periodic, Bounded, Bounded)
+channels and (Bounded, Bounded, Bounded) basins run the reference's launch sequence on the kernels of csrc/hydrostatic_walls.hip (what they
+take and refuse: `_refuse_on_walls`).
 
     src/Models/HydrostaticFreeSurfaceModels/hydrostatic_free_surface_model.jl (constructor), explicit_free_surface.jl,
     compute_w_from_continuity.jl, hydrostatic_free_surface_tendency_kernel_functions.jl:29-97,
@@ -368,8 +370,15 @@ class HydrostaticFreeSurfaceModel:
             fused = False
         arch = grid.architecture
         self._dist = arch if (hasattr(arch, "partition") and arch.communicates) else None   # a slab-x rank (distributed.py)
-        if tuple(grid.topology) != (FullyConnected if self._dist is not None else Periodic, Periodic, Bounded):
-            raise NotImplementedError("HydrostaticFreeSurfaceModel: (Periodic, Periodic, Bounded) grids (x may be slab-partitioned)")
+        topology = tuple(grid.topology)
+        # a channel or a closed basin: per-location layouts and planes, csrc/hydrostatic_walls.hip
+        self._walls = self._dist is None and topology in ((Periodic, Bounded, Bounded), (Bounded, Bounded, Bounded))
+        if not self._walls and topology != (FullyConnected if self._dist is not None else Periodic, Periodic, Bounded):
+            raise NotImplementedError("HydrostaticFreeSurfaceModel: (Periodic, Periodic, Bounded), (Periodic, Bounded, Bounded) and (Bounded, Bounded, "
+                                      "Bounded) grids (Flat directions are not implemented; only a (Periodic, Periodic, Bounded) grid may be "
+                                      "slab-partitioned in x)")
+        if self._walls:
+            fused = self._refuse_on_walls(grid, momentum_advection, free_surface, closure, fused)
         if free_surface is None:
             free_surface = ImplicitFreeSurface()  # default_free_surface(grid::XYRegularRG) (hydrostatic_free_surface_model.jl:51-52)
         if not isinstance(free_surface, (ExplicitFreeSurface, SplitExplicitFreeSurface, ImplicitFreeSurface)):
@@ -416,13 +425,14 @@ class HydrostaticFreeSurfaceModel:
         self.free_surface = free_surface
         self.u, self.v, self.w = nh.u, nh.v, nh.w
         self.velocities, self.tracers, self.tracer_names = nh.velocities, nh.tracers, nh.tracer_names
-        sx, sy = grid.Nx + 2 * grid.Hx, grid.Ny + 2 * grid.Hy
         dev = self.u.data.device
-        self.eta = torch.zeros((sy, sx), dtype=torch.float64, device=dev)       # η[i, j, Nz+1], halos included, x fastest
+        self.eta = self._plane()                                                # η[i, j, Nz+1], halos included, x fastest
         self._Geta = torch.zeros_like(self.eta)
         self._Geta_m = torch.zeros_like(self.eta)
-        if self.split:  # barotropic velocities, filtered state, slow forcing: planes like η (interiors used)
-            self.U, self.V, self._Ub, self._Vb, self._etab, self._GU, self._GV = (torch.zeros_like(self.eta) for _ in range(7))
+        if self.split:  # barotropic velocities, filtered state, slow forcing: planes like η, or (walls) U like u and V like v
+            self.U, self._Ub, self._GU = (self._plane(self.u) for _ in range(3))
+            self.V, self._Vb, self._GV = (self._plane(self.v) for _ in range(3))
+            self._etab = torch.zeros_like(self.eta)
             self._weights_key, self._weights, self._frac = None, None, None
             self._initialized = False
         self._adv_only = _lib.CModelTerms()                                     # the advective part alone, by scheme
@@ -434,9 +444,9 @@ class HydrostaticFreeSurfaceModel:
             from .solvers import FFTBasedPoissonSolver
             # FFTImplicitFreeSurfaceSolver (fft_based_implicit_free_surface_solver.jl:39-70): a Poisson solver on the horizontal grid
             hgrid = RectilinearGrid(grid.architecture, size=(grid.Nx, grid.Ny), x=grid._interval[0],
-                                    y=grid._interval[1], topology=(Periodic, Periodic, Flat), halo=(grid.Hx, grid.Hy))
+                                    y=grid._interval[1], topology=(grid.topology[0], grid.topology[1], Flat), halo=(grid.Hx, grid.Hy))
             self._fs_solver = FFTBasedPoissonSolver(hgrid)
-            self._Qu, self._Qv = torch.zeros_like(self.eta), torch.zeros_like(self.eta)
+            self._Qu, self._Qv = self._plane(self.u), self._plane(self.v)
             self._fs_rhs = torch.zeros((grid.Ny, grid.Nx), dtype=torch.float64, device=dev)
         if self.fused and not self.vector_invariant:
             raise NotImplementedError("fused = True needs momentum_advection = VectorInvariant()")
@@ -462,6 +472,32 @@ class HydrostaticFreeSurfaceModel:
         self.update_state(compute_tendencies=False)
 
     # ---- helpers -------------------------------------------------------------------------------------------------------
+    def _refuse_on_walls(self, grid, momentum_advection, free_surface, closure, fused):
+        """what a (Periodic, Bounded, Bounded) or (Bounded, Bounded, Bounded) grid does not take: raised before anything
+        is allocated.  Returns `fused` (False: the reference's launch sequence is the one implemented there)."""
+        from .physics import ScalarDiffusivity, is_vertically_implicit
+        who = "HydrostaticFreeSurfaceModel on a grid with walls in x or y"
+        if fused:
+            raise NotImplementedError(f"{who}: fused = True is not implemented; the fused kernels wrap x and y (leave fused at its default, False)")
+        if self.split_rk3:
+            raise NotImplementedError(f"{who}: SplitRungeKutta3 is not implemented; use QuasiAdamsBashforth2")
+        if hasattr(grid.architecture, "partition"):
+            raise NotImplementedError(f"{who}: slab-partitioned (Distributed) grids are not implemented")
+        if isinstance(free_surface, SplitExplicitFreeSurface) and isinstance(free_surface.timestepper, AdamsBashforth3Scheme):
+            raise NotImplementedError(f"{who}: the AdamsBashforth3Scheme substepping is not implemented; use the ForwardBackwardScheme")
+        if isinstance(momentum_advection, VectorInvariant) and momentum_advection.upwinds:
+            raise NotImplementedError(f"{who}: an upwinding VectorInvariant / WENOVectorInvariant is not implemented; use VectorInvariant() "
+                                      "or a flux-form scheme (WENO(), UpwindBiased(order=5), Centered())")
+        if closure is not None and not (isinstance(closure, ScalarDiffusivity) and not is_vertically_implicit(closure)):
+            raise NotImplementedError(f"{who}: closure must be None or an explicit ScalarDiffusivity; the kernels and column solvers of "
+                                      "the other closures (vertically implicit, convective adjustment, Ri-based, biharmonic) wrap x and y")
+        return False
+
+    def _plane(self, like=None):
+        """a zeroed 2-D plane [y, x] with halos, with the x / y extents of the field `like` (U like u, V like v) or of a centre field (η)"""
+        sz, sy, sx = (self.w if like is None else like).data.shape
+        return torch.zeros((sy, sx), dtype=torch.float64, device=self.u.data.device)
+
     def _required_halo(self):
         """what the closure needs (one number for all directions) and, per direction, what the momentum scheme needs
         (required_halo_size_x/y/z(::VectorInvariant), vector_invariant_advection.jl:241-251); the container adds the tracer scheme's"""
@@ -483,7 +519,10 @@ class HydrostaticFreeSurfaceModel:
     def update_state(self, compute_tendencies=True):
         nh, g = self._nh, self.grid
         update_boundary_conditions(nh)
-        fill_halo_regions((self.u, self.v) + tuple(self.tracers), fill_boundary_normal_velocities=False)
+        # tupled_fill_halo_regions!(prognostic_fields(model), ...) keeps the default fill_boundary_normal_velocities = true
+        # (update_hydrostatic_free_surface_model_state.jl:42, fill_halo_regions.jl:50-56): on a grid with walls the wall faces of the
+        # wall-normal velocity are reset to 0 here.  Without walls in x or y no face of u, v is one, and the switch changes nothing.
+        fill_halo_regions((self.u, self.v) + tuple(self.tracers), fill_boundary_normal_velocities=self._walls)
         self._fill_eta_halos()
         _lib.call("ocn_compute_w_from_continuity", g.cref, self.u.ptr, self.v.ptr, self.w.ptr, stream_ptr())
         update_hydrostatic_pressure(nh)
@@ -628,7 +667,9 @@ class HydrostaticFreeSurfaceModel:
                       self._Ub.data_ptr(), self._Vb.data_ptr(), float(g.Lz), s)
         elif self.implicit:
             # step_free_surface!(::ImplicitFreeSurface) (implicit_free_surface.jl:112-145); the halo fills of the velocities and of the
-            # volume fluxes are not needed: the kernels wrap their x / y neighbour indices
+            # volume fluxes are not needed: the kernels wrap their x / y neighbour indices along Periodic directions
+            if self._walls:  # fill_halo_regions!(model.velocities, ...) (implicit_free_surface.jl:133): u★, v★ are 0 on the wall faces
+                fill_halo_regions((self.u, self.v), fill_boundary_normal_velocities=True)
             _lib.call("ocn_implicit_free_surface_rhs", g.cref, self.u.ptr, self.v.ptr, self.eta.data_ptr(), fs.gravitational_acceleration,
                       float(dt), self._Qu.data_ptr(), self._Qv.data_ptr(), self._fs_rhs.data_ptr(), s)
             h = self._fs_solver._h
