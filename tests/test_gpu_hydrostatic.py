@@ -32,11 +32,8 @@ def test_w_from_continuity_bitwise(oracle, ocn, stretched):
     np.testing.assert_array_equal(got[:-1, :-1, og.Hz:og.Hz + og.Nz + 1], w[:-1, :-1, og.Hz:og.Hz + og.Nz + 1])
 
 
-@pytest.mark.parametrize("advection", ["Centered2", "WENO5", "VectorInvariant", "VectorInvariant-unfused"])
-@pytest.mark.parametrize("physics", [False, True])
-def test_hydrostatic_model_steps_match_oracle(oracle, ocn, advection, physics):
-    """3 QAB2 steps (the first one Euler) of the explicit-free-surface model: u, v, w, η and the tracers equal the oracle's bit
-    for bit in strict math."""
+def _explicit_pair(oracle, ocn, advection, physics):
+    """the explicit-free-surface model on both sides at (16, 12, 7) stretched; "VectorInvariant-unfused": the reference's launch sequence"""
     from oracle import hydrostatic as Hy
     O = oracle
     size = (16, 12, 7)
@@ -64,10 +61,10 @@ def test_hydrostatic_model_steps_match_oracle(oracle, ocn, advection, physics):
     pm = ocn.HydrostaticFreeSurfaceModel(pg, momentum_advection=scheme, tracers=tracers, free_surface=ocn.ExplicitFreeSurface(), fused=fused, **kw_p)
     assert pm.fused == (advection == "VectorInvariant" and fused is None)
     pm.set(**init)
-    for dt in (2.0, 2.0, 2.0):
-        om.time_step(dt)
-        pm.time_step(dt)
-    ocn.sync_device()
+    return og, om, pm
+
+
+def _compare_explicit(og, om, pm):
     for name, a, d in zip(("u", "v", "w"), (om.u, om.v, om.w), pm.velocities):
         np.testing.assert_array_equal(og.interior(from_dev(d)), og.interior(a), err_msg=name)
     eta = pm.eta_interior().cpu().numpy().T
@@ -75,6 +72,35 @@ def test_hydrostatic_model_steps_match_oracle(oracle, ocn, advection, physics):
     for a, d in zip(om.tracers, pm.tracers):
         np.testing.assert_array_equal(og.interior(from_dev(d)), og.interior(a))
     assert np.abs(eta).max() > 0 and np.isfinite(eta).all()
+
+
+@pytest.mark.parametrize("advection", ["Centered2", "WENO5", "VectorInvariant", "VectorInvariant-unfused"])
+@pytest.mark.parametrize("physics", [False, True])
+def test_hydrostatic_model_steps_match_oracle(oracle, ocn, advection, physics):
+    """3 QAB2 steps (the first one Euler) of the explicit-free-surface model: u, v, w, η and the tracers equal the oracle's bit
+    for bit in strict math."""
+    og, om, pm = _explicit_pair(oracle, ocn, advection, physics)
+    for dt in (2.0, 2.0, 2.0):
+        om.time_step(dt)
+        pm.time_step(dt)
+    ocn.sync_device()
+    _compare_explicit(og, om, pm)
+
+
+def test_explicit_free_surface_model_with_a_changing_time_step_matches_oracle(oracle, ocn):
+    """dt = 2, 2, 3, 3 with the fused step: step 3 is an Euler step in the middle of the run (χ = -1/2, G⁻ not read), step 4 an AB2 step
+    with the new dt -- the `euler` argument of ocn_hydrostatic_momentum_ab2_step and of the free-surface step without the split path"""
+    og, om, pm = _explicit_pair(oracle, ocn, "VectorInvariant", True)
+    assert pm.fused
+    euler = []
+    for dt in (2.0, 2.0, 3.0, 3.0):
+        euler.append(dt != pm.clock.last_dt)
+        om.time_step(dt)
+        pm.time_step(dt)
+    ocn.sync_device()
+    assert euler == [True, False, True, False]
+    _compare_explicit(og, om, pm)
+    assert np.abs(og.interior(om.u)).max() < 1.0
 
 
 @pytest.mark.parametrize("fused", [True, False])
@@ -118,7 +144,9 @@ def test_split_explicit_free_surface_model_steps_match_oracle(oracle, ocn, fused
 
 
 # ---- BASELINE.json configs[4]: VectorInvariant momentum + WENO tracer advection + SplitExplicitFreeSurface -----------------------------
-def _config5_pair(oracle, ocn, size, substeps, stretched, seed=31, fused=None, timestepper="QuasiAdamsBashforth2", beta=None):
+def _config5_pair(oracle, ocn, size, substeps, stretched, seed=31, fused=None, timestepper="QuasiAdamsBashforth2", beta=None,
+                  free_surface=None):
+    """free_surface(pg): the product's free surface when it is not SplitExplicitFreeSurface(substeps = substeps), which the oracle always gets"""
     from oracle import hydrostatic as Hy
     O = oracle
     og, pg = _pair(O, ocn, size, stretched=stretched)
@@ -131,7 +159,7 @@ def _config5_pair(oracle, ocn, size, substeps, stretched, seed=31, fused=None, t
                                         boundary_conditions={"u": {"top": O.FluxBoundaryCondition(-1e-4)}, "T": {"top": O.FluxBoundaryCondition(5e-5)}})
     om.set(**init)
     pm = ocn.HydrostaticFreeSurfaceModel(pg, momentum_advection=ocn.VectorInvariant(), tracer_advection=ocn.WENO(), tracers=("T", "S"),
-                                         free_surface=ocn.SplitExplicitFreeSurface(substeps=substeps),
+                                         free_surface=ocn.SplitExplicitFreeSurface(substeps=substeps) if free_surface is None else free_surface(pg),
                                          coriolis=ocn.FPlane(f=1e-4) if beta is None else ocn.BetaPlane(f0=1e-4, beta=beta),
                                          closure=ocn.ScalarDiffusivity(ν=1e-2, κ=2e-3),
                                          buoyancy=ocn.SeawaterBuoyancy(equation_of_state=ocn.LinearEquationOfState(2e-4, 8e-4)),
@@ -201,6 +229,54 @@ def test_config5_combination_on_a_beta_plane_matches_oracle(oracle, ocn, fused):
     for _ in range(3):
         om2.time_step(20.0)
     assert np.abs(og.interior(om.u) - og2.interior(om2.u)).max() > 0  # β matters
+
+
+@pytest.mark.parametrize("fused", [True, False])
+def test_default_split_explicit_free_surface_matches_oracle(oracle, ocn, fused):
+    """SplitExplicitFreeSurface() as the package builds it by default: MINIMUM_SUBSTEPS = 5 substeps, of which the averaging kernel keeps
+    3 weights -- one launch of the blocked kernel that is both the first and the last.  3 steps, bit for bit.  dt = 8: Δτ = 2 dt / 5 = 3.2
+    keeps the gravity-wave CFL sqrt(g H) Δτ / Δx at 0.51 on this grid (Δx = Δy = 125, H = 40)."""
+    ocn.set_math_mode(ocn.MATH_STRICT)
+    og, om, pm = _config5_pair(oracle, ocn, (16, 12, 7), 5, True, fused=fused, free_surface=lambda pg: ocn.SplitExplicitFreeSurface())
+    assert pm.fused == fused
+    assert len(pm.free_surface.averaging_weights) == 3 and len(om.weights) == 3
+    for _ in range(3):
+        om.time_step(8.0)
+        pm.time_step(8.0)
+    ocn.sync_device()
+    _compare_hydrostatic(og, om, pm, 0)
+    assert np.abs(om.U).max() > 0 and np.abs(og.interior(om.u)).max() < 1.0 and np.abs(om.eta).max() < 1.0
+
+
+@pytest.mark.parametrize("fused", [True, False])
+def test_variable_time_steps_with_a_cfl_free_surface_match_oracle(oracle, ocn, fused):
+    """SplitExplicitFreeSurface(grid, cfl = 0.7) (FixedTimeStepSize): the number of substeps max(5, ceil(2 Δt / Δt_barotropic)) and the
+    averaging weights are recomputed from every baroclinic Δt (step_split_explicit_free_surface.jl:54-58), and a changed Δt makes the
+    step an Euler step (quasi_adams_bashforth_2.jl:86-90): the `euler` flag of the fused momentum launch, the has-G⁻ flag of the tracer
+    launches and the tendencies deferred across the switch.  Δt = 20, 20, 30, 30, 5 gives 13, 13, 20, 20, 5 substeps and 9, 9, 14, 14, 3
+    weights; steps 1, 3 and 5 are Euler steps.  The oracle is handed the weights of each step; bit for bit."""
+    from oracle import hydrostatic as Hy
+    ocn.set_math_mode(ocn.MATH_STRICT)
+    og, om, pm = _config5_pair(oracle, ocn, (16, 12, 7), 5, True, fused=fused, free_surface=lambda pg: ocn.SplitExplicitFreeSurface(pg, cfl=0.7))
+    assert pm.fused == fused
+    dts = (20.0, 20.0, 30.0, 30.0, 5.0)
+    # barotropic_time_step (split_explicit_free_surface.jl:217-235) restated: Δs = 1 / sqrt(1 / Δx² + 1 / Δy²), Δt_barotropic = cfl Δs / sqrt(g H)
+    dt_barotropic = 0.7 * np.sqrt(1 / (1 / og.dx ** 2 + 1 / og.dy ** 2)) / np.sqrt(9.80665 * 40.0)
+    substeps = [max(5, int(np.ceil(2 * dt / dt_barotropic))) for dt in dts]
+    assert substeps == [13, 13, 20, 20, 5]
+    counts, euler = [], []
+    for dt, N in zip(dts, substeps):
+        om.frac_dt, om.weights = Hy.weights_from_substeps(N)
+        assert len(pm.free_surface.settings(dt)[1]) == len(om.weights)
+        counts.append(len(om.weights))
+        euler.append(dt != pm.clock.last_dt)
+        om.time_step(dt)
+        pm.time_step(dt)
+    ocn.sync_device()
+    assert counts == [9, 9, 14, 14, 3] and len(set(counts)) >= 3 and euler == [True, False, True, False, True]
+    _compare_hydrostatic(og, om, pm, 0)
+    assert pm.clock.iteration == 5 and pm.clock.time == sum(dts)
+    assert np.abs(om.U).max() > 0 and np.abs(og.interior(om.u)).max() < 1.0 and np.abs(om.eta).max() < 1.0
 
 
 @pytest.mark.parametrize("size,substeps,stretched,dt", [((16, 12, 7), 12, True, 20.0), ((67, 9, 12), 8, True, 3.0)])
