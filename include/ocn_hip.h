@@ -501,6 +501,56 @@ int ocn_compute_ri_based_diffusivities_fused(const ocn_grid *grid, const ocn_mod
 /* The tapering functions on the HOST (no device is touched): out[q] = τ(x[q]; x0, delta), q = 0..n-1, kind = OCN_RI_TAPER_*, by the inline
  * functions the kernels call (csrc/ocn_taper.h: IEEE +, -, *, / and powers of two only, no math library) -- the same bits as on the device. */
 int ocn_ri_taper_host(int32_t kind, int64_t n, const double *x, double x0, double delta, double *out);
+/* ---- CATKEVerticalDiffusivity (csrc/catke.hip, csrc/ocn_catke.h; turbulence_closure_implementations/TKEBasedVerticalDiffusivities/):
+ * κᵘ, κᶜ, κᵉ at (Center, Center, Face), the linear coefficient Le at (Center, Center, Center), the averaged surface buoyancy flux Jᵇ as a plane
+ * of Nx Ny doubles without halos (x fastest, like the `values` of an ocn_bc), and the substep of the turbulent kinetic energy e.  The
+ * grid: (Periodic, Periodic, Bounded), halos >= 1, Nz >= 2 (with one layer ℑbzᵃᵃᶜ evaluates the peripheral faces), one GPU; strict math
+ * whatever the math mode.  znodes_f / znodes_c: DEVICE vectors of the Nz + 1 interior z faces / the Nz z centres (element 0 <-> k = 1).
+ * Reach of every entry point: u at i, i + 1 and v at j, j + 1, k = 1..Nz; T, S at k = 1..Nz + 1 (the first top halo plane: N² of face
+ * Nz + 1); e at k = 1..Nz; κᵘ (the substep) at i - 1..i + 1, j - 1..j + 1, faces 2..Nz; κᶜ (the substep) at faces 2..Nz of the column. */
+typedef struct ocn_catke {
+    /* CATKEMixingLength (catke_mixing_length.jl:15-36) */
+    double C_s, C_b, C_sp, CRi_delta, CRi_0;
+    double C_hi_u, C_lo_u, C_un_u, C_c_u, C_e_u;
+    double C_hi_c, C_lo_c, C_un_c, C_c_c, C_e_c;
+    double C_hi_e, C_lo_e, C_un_e, C_c_e, C_e_e;
+    /* CATKEEquation (catke_equation.jl:7-16) */
+    double C_hi_D, C_lo_D, C_un_D, C_c_D, C_e_D, C_W_ustar, C_W_wdelta, C_W_eps;
+    /* CATKEVerticalDiffusivity (catke_vertical_diffusivity.jl:96-120); the three maxima may be +inf */
+    double maximum_tracer_diffusivity, maximum_tke_diffusivity, maximum_viscosity;
+    double minimum_tke, minimum_convective_buoyancy_flux, negative_tke_damping_time_scale;
+} ocn_catke;
+/* out[q] = cbrt(x[q]), q = 0..n-1, on the HOST (no device is touched) by the inline function the kernels call (csrc/ocn_catke.h: IEEE +, -, *,
+ * / and exponent manipulation, six Newton steps): the same bits as on the device and in tests/catke_numpy.py. */
+int ocn_catke_host_cbrt(int64_t n, const double *x, double *out);
+/* compute_average_surface_buoyancy_flux! (catke_vertical_diffusivity.jl:253-271) over the columns: Jᵇ <- (Jᵇ + ϵ Jᵇ★) / (1 + ϵ), ϵ = dt / t★,
+ * t★ = cbrt(ℓᴰ² / max(Jᵇᵋ, Jᵇ, Jᵇ★)), Jᵇ★ the top buoyancy flux of top_T / top_S (as for ocn_compute_ri_based_diffusivities) and ℓᴰ
+ * dissipation_length_scaleᶜᶜᶜ at k = Nz.  dt >= 0. */
+int ocn_compute_catke_surface_buoyancy_flux(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_catke *closure, const ocn_bc *top_T,
+                                            const ocn_bc *top_S, const double *znodes_f, const double *znodes_c, const double *u,
+                                            const double *v, const double *e, double *Jb, double dt, void *stream);
+/* top_tke_flux (catke_equation.jl:98-120, tke_top_boundary_condition.jl:64-77) over the columns into the plane Qe (Nx Ny doubles, the
+ * `values` of e's top flux condition): - Cᵂu★ u★³ - CᵂwΔ wΔ³ with u★ = sqrt(sqrt(τx² + τy²)) from the top conditions of u and v (evaluated at
+ * the same i, j) and wΔ³ = max(0, Jᵇ★) Δzᶜ(Nz).  NULL or OCN_BC_DEFAULT: no flux. */
+int ocn_compute_catke_top_tke_flux(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_catke *closure, const ocn_bc *top_u,
+                                   const ocn_bc *top_v, const ocn_bc *top_T, const ocn_bc *top_S, const double *u, const double *v, double *Qe,
+                                   void *stream);
+/* compute_CATKE_diffusivities! (catke_vertical_diffusivity.jl:273-325, catke_mixing_length.jl) over i = 1..Nx, j = 1..Ny, faces k = 1..Nz in
+ * one launch, a thread per column marching upwards: κ = min(ℓ w★, maximum), face 1 exactly 0 (mask_diffusivity); face Nz + 1 and the halos
+ * are NOT written.  OCN_ERR_INVALID_ARGUMENT: aliased outputs, a coefficient that is not finite, a NaN maximum, a grid outside the scope. */
+int ocn_compute_catke_diffusivities(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_catke *closure, const double *znodes_f,
+                                    const double *znodes_c, const double *u, const double *v, const double *e, const double *Jb,
+                                    double *kappa_u, double *kappa_c, double *kappa_e, void *stream);
+/* substep_turbulent_kinetic_energy! (time_step_catke_equation.jl:78-173) and, with solve != 0, the implicit_step! of e that follows it
+ * (vertically_implicit_diffusion_solver.jl: (1 - dtau ∂z κᵉ ∂z - dtau Le) e = e), one launch, a thread per column: κᵉ (faces 1..Nz) and Le
+ * (cells 1..Nz) are written, e <- e + dtau ((1.5 + chi) (Gn_e + P + wb⁺) - (0.5 + chi) Gm_e), Gm_e <- Gn_e + P + wb⁺, then the tridiagonal
+ * solve in the column.  Every e read by the substep is the e of before the call.  u_next, v_next: the current velocities; u_prev,
+ * v_prev: the previous ones; kappa_u, kappa_c: as ocn_compute_catke_diffusivities left them, x / y halos of kappa_u filled.
+ * scratch: Nx Ny Nz doubles (the multipliers of the elimination; not read with solve == 0). */
+int ocn_catke_substep_tke(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_catke *closure, const double *znodes_f,
+                          const double *znodes_c, const double *u_next, const double *v_next, const double *u_prev, const double *v_prev,
+                          double *e, const double *Jb, const double *kappa_u, const double *kappa_c, double *kappa_e, double *Le,
+                          const double *Gn_e, double *Gm_e, double *scratch, double dtau, double chi, int32_t solve, void *stream);
 /* ---- HorizontalScalarBiharmonicDiffusivity: ScalarBiharmonicDiffusivity{HorizontalFormulation} with constant ν and κ
  * (csrc/biharmonic.hip; abstract_scalar_biharmonic_diffusivity_closure.jl:46-51, 66-67, 75-102; strict math whatever the math mode) ----
  * The closure term SUBTRACTED from tendencies that hold every other term, over i = 1..Nx, j = 1..Ny, k = 1..Nz:

@@ -25,6 +25,7 @@ from .physics import (HorizontalDivergenceFormulation, HorizontalFormulation, Ho
                       ThreeDimensionalFormulation, VerticalFormulation)
 from .physics import (ExponentialRiDependentTapering, FivePointHorizontalFilter, HyperbolicTangentRiDependentTapering,
                       PiecewiseLinearRiDependentTapering, RiBasedVerticalDiffusivity)
+from .physics import CATKEEquation, CATKEMixingLength, CATKEVerticalDiffusivity
 from .physics import (AnisotropicMinimumDissipation, ConvectiveAdjustmentVerticalDiffusivity, DynamicCoefficient, DynamicSmagorinsky, LillyCoefficient, Smagorinsky, SmagorinskyLilly, BetaPlane, BoundaryCondition, BuoyancyTracer, Centered, FieldBoundaryConditions, FluxBoundaryCondition, FPlane,
                       GradientBoundaryCondition, LinearEquationOfState, OpenBoundaryCondition, ScalarDiffusivity, SeawaterBuoyancy,
                       ValueBoundaryCondition, ExplicitTimeDiscretization, VerticallyImplicitTimeDiscretization)

@@ -92,6 +92,17 @@ class CRiBased(C.Structure):
                                            "maximum_diffusivity", "maximum_viscosity")] + [("tapering", C.c_int32), ("horizontal_filter", C.c_int32)]
 
 
+CATKE_FIELDS = ("C_s", "C_b", "C_sp", "CRi_delta", "CRi_0", "C_hi_u", "C_lo_u", "C_un_u", "C_c_u", "C_e_u", "C_hi_c", "C_lo_c", "C_un_c", "C_c_c",
+                "C_e_c", "C_hi_e", "C_lo_e", "C_un_e", "C_c_e", "C_e_e", "C_hi_D", "C_lo_D", "C_un_D", "C_c_D", "C_e_D", "C_W_ustar", "C_W_wdelta",
+                "C_W_eps", "maximum_tracer_diffusivity", "maximum_tke_diffusivity", "maximum_viscosity", "minimum_tke",
+                "minimum_convective_buoyancy_flux", "negative_tke_damping_time_scale")
+
+
+class CCatke(C.Structure):
+    """struct ocn_catke"""
+    _fields_ = [(n, C.c_double) for n in CATKE_FIELDS]
+
+
 class CSmagorinsky(C.Structure):
     """struct ocn_smagorinsky"""
     _fields_ = [("C", C.c_double), ("Cb", C.c_double), ("lilly", C.c_int32), ("n_tracers", C.c_int32), ("Pr", C.c_double * MODEL_MAX_TRACERS)]
@@ -207,6 +218,13 @@ _SIGS = {
     "ocn_compute_ri_based_diffusivities_fused": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CRiBased), C.POINTER(CBc), C.POINTER(CBc), _vp,
                                                  _vp, _vp, _vp, _vp, _vp],
     "ocn_ri_taper_host": [_i32, C.c_int64, _vp, _dbl, _dbl, _vp],
+    "ocn_catke_host_cbrt": [C.c_int64, _vp, _vp],
+    "ocn_compute_catke_surface_buoyancy_flux": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CCatke), C.POINTER(CBc), C.POINTER(CBc), _vp, _vp,
+                                                _vp, _vp, _vp, _vp, _dbl, _vp],
+    "ocn_compute_catke_top_tke_flux": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CCatke), C.POINTER(CBc), C.POINTER(CBc), C.POINTER(CBc),
+                                       C.POINTER(CBc), _vp, _vp, _vp, _vp],
+    "ocn_compute_catke_diffusivities": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CCatke)] + [_vp] * 10,
+    "ocn_catke_substep_tke": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CCatke)] + [_vp] * 15 + [_dbl, _dbl, _i32, _vp],
     "ocn_cache_previous_tendencies": [C.POINTER(CGrid), _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), _vp],
     "ocn_pressure_correct_velocities": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _dbl, _vp],
     "ocn_divergence": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _vp],

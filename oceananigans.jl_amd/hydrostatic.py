@@ -409,9 +409,10 @@ class HydrostaticFreeSurfaceModel:
         # every launch of the closure but the term in ocn_model_terms, and every refusal, is the business of this one object
         self.closure = tuple(closure) if isinstance(closure, (tuple, list)) else closure
         self._closure = resolve_closure(closure, fused, self.split_rk3, hasattr(arch, "partition"), self._dist is not None, buoyancy,
-                                        boundary_conditions)
+                                        boundary_conditions, (tracers,) if isinstance(tracers, str) else tuple(tracers))
         if self._closure.unfused:
             fused = False
+        boundary_conditions = self._closure.boundary_conditions(boundary_conditions, grid)  # add_closure_specific_boundary_conditions
         # fields, physics descriptors, tendency storage and the Adams-Bashforth bookkeeping of the nonhydrostatic model are reused;
         # its pressure solver and w tendency are simply not used
         self._nh = NonhydrostaticModel(grid, advection=container_advection, tracers=tracers, timestepper="QuasiAdamsBashforth2",
@@ -651,8 +652,10 @@ class HydrostaticFreeSurfaceModel:
         Gn, Gm = nh.timestepper._Gn, nh.timestepper._Gm
         # local_ab2_step!: u, v by ab2_step_field!; tracers by _ab2_step_tracer_field!, which with σ = 1 (static grid) is the same
         # arithmetic for finite values
-        idx = [0, 1] + [3 + n for n in range(len(self.tracers))]
-        fields = [self.u, self.v] + list(self.tracers)
+        # (a tracer that the closure steps itself -- e of CATKEVerticalDiffusivity -- is skipped here and in cache_previous_tendencies!)
+        own = [n for n, name in enumerate(self.tracer_names) if name in self._closure.self_stepped]
+        idx = [0, 1] + [3 + n for n in range(len(self.tracers)) if n not in own]
+        fields = [self.u, self.v] + [c for n, c in enumerate(self.tracers) if n not in own]
         _lib.call("ocn_ab2_step", g.cref, len(idx), _lib.ptr_array([f.ptr for f in fields]), _lib.ptr_array([Gn[q].ptr for q in idx]),
                   _lib.ptr_array([Gm[q].ptr for q in idx]), _lib.i32_array([f.loc for f in fields]), float(dt), float(chi), s)
         self._closure.implicit_step(nh, fields, dt, s)  # implicit_step! of a vertically implicit closure
@@ -686,8 +689,16 @@ class HydrostaticFreeSurfaceModel:
         self._tick(dt)
         # (no pressure correction with an explicit free surface) cache_previous_tendencies!: role swap
         nh.timestepper._Gn, nh.timestepper._Gm = Gm, Gn
+        for n in own:  # (not cached: Gⁿ and G⁻ of such a tracer keep their roles)
+            Gn[3 + n], Gm[3 + n] = Gm[3 + n], Gn[3 + n]
         self._Geta, self._Geta_m = self._Geta_m, self._Geta
-        self.update_state(compute_tendencies=True)
+        # the reference keeps χ = -1/2 in the time stepper for the whole of an Euler step, the closing update_state! included, and restores it
+        # afterwards (quasi_adams_bashforth_2.jl:91-112): a closure that steps a tracer there (time_step_catke_equation.jl:52) reads it
+        chi0, nh.timestepper.chi = nh.timestepper.chi, chi
+        try:
+            self.update_state(compute_tendencies=True)
+        finally:
+            nh.timestepper.chi = chi0
 
     # ---- the same step with fused launches -----------------------------------------------------------------------------------
     def _substep_free_surface(self, dt, s):

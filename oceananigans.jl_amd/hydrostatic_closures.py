@@ -3,20 +3,24 @@ compute_diffusivities!, the flux divergences, implicit_step! and required_halo_s
 
 `resolve_closure` turns the user's closure into ONE object, or refuses; it allocates nothing and touches no device.  The model asks that
 object: at construction `container_closure` (what ocn_model_terms carries: an explicit ScalarDiffusivity or None), `halo`, `unfused` and
-`allocate(nh)` (the diffusivity_fields dict, or None); in update_state `compute_diffusivities(nh)`; in compute_tendencies `tracer_kappa(name)`
-for the built-in tracer entry point and `add_fluxes(nh, Gn, s)` after those entry points; in time_step `implicit_step(nh, fields, dt, s)` after
-ocn_ab2_step; checkpoints read `state_fields`.  Every kind but InModelTerms keeps the closure out of ocn_model_terms and runs the
+`allocate(nh)` (the diffusivity_fields dict, or None) and `boundary_conditions(user_bcs, grid)` (the conditions the fields are built with); in
+update_state `compute_diffusivities(nh)`; in compute_tendencies `tracer_kappa(name)` for the built-in tracer entry point and
+`add_fluxes(nh, Gn, s)` after those entry points; in time_step `self_stepped` (the tracers that ab2_step, implicit_step and
+cache_previous_tendencies leave to the closure) and `implicit_step(nh, fields, dt, s)` after ocn_ab2_step; checkpoints read `state_fields`,
+`checkpoint_state(nh)` and call `restore_state(nh, get)`.  Every kind but InModelTerms keeps the closure out of ocn_model_terms and runs the
 reference's launch sequence (fused = False) with QAB2 on one GPU."""
 import ctypes as C
+import math
 
+import numpy as np
 import torch
 
 from . import _lib
 from .architectures import stream_ptr
-from .fields import ZFaceField, fill_halo_regions
+from .fields import CenterField, XFaceField, YFaceField, ZFaceField, fill_halo_regions
 from .models import implicit_diffusion_step
-from .physics import (BuoyancyTracer, RiBasedVerticalDiffusivity, ScalarBiharmonicDiffusivity, SeawaterBuoyancy, has_diffusivity_fields,
-                      is_vertically_implicit, owns_eddy_fields)
+from .physics import (BuoyancyTracer, CATKEVerticalDiffusivity, FieldBoundaryConditions, FluxBoundaryCondition, RiBasedVerticalDiffusivity,
+                      ScalarBiharmonicDiffusivity, SeawaterBuoyancy, has_diffusivity_fields, is_vertically_implicit, owns_eddy_fields)
 
 
 def _refuse(what, fused, split_rk3, slabs):
@@ -28,16 +32,19 @@ def _refuse(what, fused, split_rk3, slabs):
         raise NotImplementedError(f"{what} on a slab-partitioned (Distributed) grid is not implemented")
 
 
-def resolve_closure(closure, fused, split_rk3, partitioned, distributed, buoyancy, boundary_conditions):
+def resolve_closure(closure, fused, split_rk3, partitioned, distributed, buoyancy, boundary_conditions, tracers=()):
     """closure: a closure, a two-element tuple or list, or None; partitioned: the architecture has a `partition`; distributed: it also
     communicates (a slab-x rank)."""
     biharmonic = None
+    if isinstance(closure, np.ndarray):
+        raise NotImplementedError("arrays of closures (ensembles) are not implemented: give one closure")
     if isinstance(closure, (tuple, list)):  # (closure_tuples.jl) the biharmonic with a closure that has κ fields, in either order
         biharmonic = [c for c in closure if isinstance(c, ScalarBiharmonicDiffusivity)]
         vertical = [c for c in closure if has_diffusivity_fields(c)]
         if len(closure) != 2 or len(biharmonic) != 1 or len(vertical) != 1:
             raise NotImplementedError("closure tuples are not implemented, except (HorizontalScalarBiharmonicDiffusivity, "
-                                      "ConvectiveAdjustmentVerticalDiffusivity or RiBasedVerticalDiffusivity) in either order: give one closure")
+                                      "ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity or CATKEVerticalDiffusivity) in either order: "
+                                      "give one closure")
         biharmonic, closure = biharmonic[0], vertical[0]
     elif isinstance(closure, ScalarBiharmonicDiffusivity):
         biharmonic, closure = closure, None
@@ -50,16 +57,25 @@ def resolve_closure(closure, fused, split_rk3, partitioned, distributed, buoyanc
     if has_diffusivity_fields(closure):
         _refuse(type(closure).__name__, fused, split_rk3, partitioned)
         carriers = None
-        if isinstance(closure, RiBasedVerticalDiffusivity):
+        if isinstance(closure, CATKEVerticalDiffusivity):
+            if "e" not in tuple(tracers):  # with_tracers (catke_vertical_diffusivity.jl:122-128)
+                raise ValueError(closure.MISSING_TRACER)
+        if isinstance(closure, (RiBasedVerticalDiffusivity, CATKEVerticalDiffusivity)):
             # top_buoyancy_flux reads the top condition of the buoyancy tracers as a flux; the reference would read the number of a Value or
             # Gradient condition as one too, which is not reproduced
             carriers = ("b", None) if isinstance(buoyancy, BuoyancyTracer) else (("T", "S") if isinstance(buoyancy, SeawaterBuoyancy) else (None, None))
+            name = type(closure).__name__
             for tracer in filter(None, carriers):
                 top = getattr((boundary_conditions or {}).get(tracer), "sides", {}).get("top")
                 if top is not None and top.kind != _lib.BC_FLUX:
-                    raise NotImplementedError(f"RiBasedVerticalDiffusivity: the top boundary condition of {tracer} must be a "
+                    raise NotImplementedError(f"{name}: the top boundary condition of {tracer} must be a "
                                               "FluxBoundaryCondition (or the default): it is the surface buoyancy flux of the entrainment term")
-        other = KappaFields(closure, carriers)
+            for velocity in ("u", "v") if isinstance(closure, CATKEVerticalDiffusivity) else ():
+                top = getattr((boundary_conditions or {}).get(velocity), "sides", {}).get("top")
+                if top is not None and top.kind != _lib.BC_FLUX:
+                    raise NotImplementedError(f"{name}: the top boundary condition of {velocity} must be a "
+                                              "FluxBoundaryCondition (or the default): it is the wind stress of the friction velocity")
+        other = CATKEFields(closure, carriers) if isinstance(closure, CATKEVerticalDiffusivity) else KappaFields(closure, carriers)
     elif is_vertically_implicit(closure):
         _refuse("a VerticallyImplicitTimeDiscretization closure", fused, split_rk3, distributed)
         if partitioned:
@@ -72,13 +88,24 @@ def resolve_closure(closure, fused, split_rk3, partitioned, distributed, buoyanc
 
 class InModelTerms:
     """no closure, or an explicit ScalarDiffusivity: its term lives in ocn_model_terms, everything else is a no-op"""
-    halo, unfused, implicit, state_fields = 0, False, False, ()
+    halo, unfused, implicit, state_fields, self_stepped = 0, False, False, (), ()
 
     def __init__(self, closure):
         self.container_closure = closure
 
+    def boundary_conditions(self, user_bcs, grid):
+        """add_closure_specific_boundary_conditions: what the fields are built with"""
+        return user_bcs
+
     def allocate(self, nh):
         return None
+
+    def checkpoint_state(self, nh):
+        """what a restart needs beyond the prognostic fields, the tendencies and `state_fields`: {name: host array}"""
+        return {}
+
+    def restore_state(self, nh, get):
+        """after the update_state! of set!(model, filepath); get(name): the array of checkpoint_state, or None"""
 
     def compute_diffusivities(self, nh):
         pass
@@ -161,16 +188,20 @@ class KappaFields(InModelTerms):
             _lib.call("ocn_compute_ri_based_diffusivities", g.cref, terms, cl, *tops, d["Ri"].ptr, d["kappa_c"].ptr, d["kappa_u"].ptr, s)
         fill_halo_regions(tuple(d.values()), fill_boundary_normal_velocities=False)  # (ZFaceFields that are no velocities)
 
-    def add_to(self, g, u, v, Gu, Gv, nt, c, G, s):
+    def kappa_of_tracer(self, name):
+        """diffusivity(closure, diffusivity_fields, Val(id)): the κ array of a tracer"""
+        return self.fields["kappa_c"].ptr
+
+    def add_to(self, g, u, v, Gu, Gv, nt, c, G, s, kappas=None):
         """G -= ∂ⱼτ: every vertical flux (explicit), or the fluxes through the two boundaries (vertically implicit).  Pointers; u = None:
-        no momentum; c, G: lists, or None for a launch without tracer arrays"""
+        no momentum; c, G: lists, or None for a launch without tracer arrays; kappas: the κ arrays of the tracers (default: κᶜ for all)"""
         d, pa = self.fields, _lib.ptr_array
-        _lib.call("ocn_add_vertical_diffusivity_fluxes", g.cref, u and d["kappa_u"].ptr, u, v, Gu, Gv, nt, c and pa([d["kappa_c"].ptr] * len(c)),
-                  c and pa(c), G and pa(G), int(self.implicit), None, s)
+        _lib.call("ocn_add_vertical_diffusivity_fluxes", g.cref, u and d["kappa_u"].ptr, u, v, Gu, Gv, nt,
+                  c and pa(kappas or [d["kappa_c"].ptr] * len(c)), c and pa(c), G and pa(G), int(self.implicit), None, s)
 
     def add_fluxes(self, nh, Gn, s):
         self.add_to(nh.grid, nh.u.ptr, nh.v.ptr, Gn[0].ptr, Gn[1].ptr, len(nh.tracers), [c.ptr for c in nh.tracers] or [None],
-                    [G.ptr for G in Gn[3:]] or [None], s)
+                    [G.ptr for G in Gn[3:]] or [None], s, kappas=[self.kappa_of_tracer(n) for n in nh.tracer_names] or None)
 
     def implicit_step(self, nh, fields, dt, s):
         """implicit_step! with the κ fields of the last update_state! (the reference does not recompute them)"""
@@ -183,6 +214,116 @@ class KappaFields(InModelTerms):
                   _lib.i32_array([f.loc for f in fields]), _lib.ptr_array(kappas), _lib.ptr_array(scratch), float(dt), s)
 
 
+class CATKEFields(KappaFields):
+    """CATKEVerticalDiffusivity (csrc/catke.hip): κᵘ, κᶜ, κᵉ, the linear coefficient Le, the averaged surface buoyancy flux Jᵇ and the previous
+    velocities (build_diffusivity_fields, catke_vertical_diffusivity.jl:180-208).  The closure steps the tracer e itself, inside
+    compute_diffusivities! (:219-251): M substeps of substep_turbulent_kinetic_energy! + implicit_step! in one launch each.  e's tendency is
+    the ordinary tracer tendency; ab2_step, the implicit step of the other fields and cache_previous_tendencies leave e alone
+    (hydrostatic_free_surface_ab2_step.jl:72-108, cache_hydrostatic_free_surface_tendencies.jl:30-57).  e's top condition is the closure's own
+    (add_closure_specific_boundary_conditions, catke_equation.jl:126-155): an array-valued flux that ocn_compute_catke_top_tke_flux writes."""
+    self_stepped = ("e",)
+
+    def __init__(self, closure, carriers):
+        super().__init__(closure, carriers)
+        self.state_fields = ()  # (everything goes through checkpoint_state / restore_state)
+
+    def boundary_conditions(self, user_bcs, grid):
+        bcs = dict(user_bcs or {})
+        sides = dict(bcs["e"].sides) if bcs.get("e") is not None else {}
+        self.top_e = FluxBoundaryCondition(np.zeros((grid.Nx, grid.Ny)))  # (a user's top condition on e is replaced, as in the reference)
+        sides["top"] = self.top_e
+        bcs["e"] = FieldBoundaryConditions(**{k: v for k, v in sides.items() if v is not None})
+        return bcs
+
+    def allocate(self, nh):
+        g, dev = nh.grid, nh.u.data.device
+        self.fields = {"kappa_u": ZFaceField(g), "kappa_c": ZFaceField(g), "kappa_e": ZFaceField(g), "Le": CenterField(g),
+                       "Jb": torch.zeros((g.Ny, g.Nx), dtype=torch.float64, device=dev)}
+        self.u_prev, self.v_prev = XFaceField(g), YFaceField(g)
+        self.previous_compute_time = nh.clock.time
+        self.struct = self.closure.c_struct()
+        self.znodes = [torch.from_numpy(np.ascontiguousarray(g.nodes_1d(2, face), dtype=np.float64)).to(dev) for face in (True, False)]
+        self.ivd_scratch = torch.zeros((4, g.Nz, g.Ny, g.Nx), dtype=torch.float64, device=dev)  # u, v, the tracers, e
+        self.top_e.c_struct(g, "top")  # (allocates the device array of the condition)
+        return self.fields
+
+    def kappa_of_tracer(self, name):
+        return self.fields["kappa_e" if name == "e" else "kappa_c"].ptr
+
+    @staticmethod
+    def _top(nh, field):
+        b = getattr(field, "boundary_conditions", None)
+        return C.pointer(b.c_struct(nh.grid).top) if b is not None and b.sides["top"] is not None else C.POINTER(_lib.CBc)()
+
+    def _e_tendencies(self, nh):
+        q = 3 + nh.tracer_names.index("e")
+        return nh.timestepper._Gn[q], nh.timestepper._Gm[q]
+
+    def time_step_tke(self, nh, s):
+        """time_step_catke_equation! (time_step_catke_equation.jl:12-76)"""
+        g, d, zf, zc = nh.grid, self.fields, *self.znodes
+        Dt, tau = nh.clock.last_dt, self.closure.tke_time_step
+        M = 1 if tau is None else math.ceil(Dt / tau)
+        dtau = Dt if tau is None else Dt / M
+        Gn, Gm = self._e_tendencies(nh)
+        for m in range(1, M + 1):
+            # an Euler step opens several substeps; otherwise the time stepper's χ, which is -1/2 during an Euler step of the model
+            chi = -0.5 if (m == 1 and M != 1) else nh.timestepper.chi
+            _lib.call("ocn_catke_substep_tke", g.cref, C.byref(nh._terms), C.byref(self.struct), zf.data_ptr(), zc.data_ptr(), nh.u.ptr, nh.v.ptr,
+                      self.u_prev.ptr, self.v_prev.ptr, nh.field("e").ptr, d["Jb"].data_ptr(), d["kappa_u"].ptr, d["kappa_c"].ptr,
+                      d["kappa_e"].ptr, d["Le"].ptr, Gn.ptr, Gm.ptr, self.ivd_scratch[3].data_ptr(), float(dtau), float(chi), 1, s)
+
+    def compute_diffusivities(self, nh):
+        g, d, s, zf, zc = nh.grid, self.fields, stream_ptr(), *self.znodes
+        nh._refresh_term_pointers()
+        terms, cl = C.byref(nh._terms), C.byref(self.struct)
+        dt = nh.clock.time - self.previous_compute_time  # update_previous_compute_time!
+        self.previous_compute_time = nh.clock.time
+        if math.isfinite(nh.clock.last_dt):  # the model has taken a step
+            self.time_step_tke(nh, s)
+        self.u_prev.data.copy_(nh.u.data)
+        self.v_prev.data.copy_(nh.v.data)
+        tops, e = self.top_conditions(nh), nh.field("e")
+        _lib.call("ocn_compute_catke_surface_buoyancy_flux", g.cref, terms, cl, *tops, zf.data_ptr(), zc.data_ptr(), nh.u.ptr, nh.v.ptr, e.ptr,
+                  d["Jb"].data_ptr(), float(dt), s)
+        _lib.call("ocn_compute_catke_diffusivities", g.cref, terms, cl, zf.data_ptr(), zc.data_ptr(), nh.u.ptr, nh.v.ptr, e.ptr,
+                  d["Jb"].data_ptr(), d["kappa_u"].ptr, d["kappa_c"].ptr, d["kappa_e"].ptr, s)
+        fill_halo_regions((d["kappa_u"], d["kappa_c"], d["kappa_e"]), fill_boundary_normal_velocities=False)
+        # the top flux of e, for the compute_boundary_tendency_contributions! of this state
+        _lib.call("ocn_compute_catke_top_tke_flux", g.cref, terms, cl, self._top(nh, nh.u), self._top(nh, nh.v), *tops, nh.u.ptr, nh.v.ptr,
+                  self.top_e._device_values.data_ptr(), s)
+
+    def implicit_step(self, nh, fields, dt, s):
+        """implicit_step! of u, v (κᵘ) and the tracers but e (κᶜ); e is stepped in compute_diffusivities"""
+        d, w, nt = self.fields, self.ivd_scratch, len(fields) - 2
+        kappas = [d["kappa_u"].ptr] * 2 + [d["kappa_c"].ptr] * nt
+        scratch = [w[0].data_ptr(), w[1].data_ptr()] + [w[2].data_ptr()] * nt
+        _lib.call("ocn_implicit_vertical_diffusion_step_fields", nh.grid.cref, len(fields), _lib.ptr_array([f.ptr for f in fields]),
+                  _lib.i32_array([f.loc for f in fields]), _lib.ptr_array(kappas), _lib.ptr_array(scratch), float(dt), s)
+
+    def checkpoint_state(self, nh):
+        d = self.fields
+        out = {name: d[name].parent() for name in ("kappa_u", "kappa_c", "kappa_e", "Le")}
+        out.update(Jb=d["Jb"].cpu().numpy().T, u_prev=self.u_prev.parent(), v_prev=self.v_prev.parent(),
+                   top_e=self.top_e._device_values.cpu().numpy().T, previous_compute_time=np.float64(self.previous_compute_time),
+                   e=nh.field("e").parent(), Gm_e=self._e_tendencies(nh)[1].parent())
+        return out
+
+    def restore_state(self, nh, get):
+        """the update_state! of set!(model, filepath) has stepped e and averaged Jᵇ once more: put back what the checkpointed tendencies
+        were computed with, so that the restart continues bit for bit"""
+        d = self.fields
+        targets = {name: d[name].data for name in ("kappa_u", "kappa_c", "kappa_e", "Le")}
+        targets.update(Jb=d["Jb"], u_prev=self.u_prev.data, v_prev=self.v_prev.data, top_e=self.top_e._device_values, e=nh.field("e").data,
+                       Gm_e=self._e_tendencies(nh)[1].data)
+        for name, t in targets.items():
+            a = get(name)
+            if a is None:
+                raise KeyError(f"Field {name} of CATKEVerticalDiffusivity does not exist in checkpoint and could not be restored.")
+            t.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(a).T)))
+        self.previous_compute_time = float(get("previous_compute_time"))
+
+
 class Biharmonic(InModelTerms):
     """G -= ∂ⱼτ of HorizontalScalarBiharmonicDiffusivity -- or, in a pair with a closure V that has κ fields, G -= (∂ⱼτ + ∂ⱼτ(V)), the sum
     formed before it is subtracted (closure_tuples.jl:41-43): V's kernel leaves 0 - ∂ⱼτ(V) in a zeroed array, which the biharmonic kernel
@@ -192,8 +333,9 @@ class Biharmonic(InModelTerms):
     def __init__(self, closure, other):
         self.closure, self.other, self.halo = closure, other, closure.required_halo_size
         if other is not None:
-            self.implicit, self.state_fields = other.implicit, other.state_fields
+            self.implicit, self.state_fields, self.self_stepped = other.implicit, other.state_fields, other.self_stepped
             self.compute_diffusivities, self.implicit_step = other.compute_diffusivities, other.implicit_step
+            self.boundary_conditions, self.checkpoint_state, self.restore_state = other.boundary_conditions, other.checkpoint_state, other.restore_state
 
     def allocate(self, nh):
         if self.other is None:
@@ -221,7 +363,7 @@ class Biharmonic(InModelTerms):
         S.zero_()
         V.add_to(g, u, v, Su, Sv, 0, None, None, s)
         self.add_to(g, bih.nu, u, v, Gu, Gv, 0, None, None, None, Su, Sv, None, s)
-        for k, c, G in zip(kappa, cs, Gs):
+        for name, k, c, G in zip(nh.tracer_names, kappa, cs, Gs):
             S[0].zero_()
-            V.add_to(g, None, None, None, None, 1, [c], [Su], s)
+            V.add_to(g, None, None, None, None, 1, [c], [Su], s, kappas=[V.kappa_of_tracer(name)])
             self.add_to(g, 0.0, None, None, None, None, 1, [k], [c], [G], None, None, [Su], s)

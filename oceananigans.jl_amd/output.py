@@ -172,6 +172,12 @@ def write_checkpoint(model, filepath):
         out[f"{ADDR}/timestepper/G⁻/η/data"] = model._Geta_m.cpu().numpy().T
         for name in model._closure.state_fields:  # the time-averaged κᶜ, κᵘ of RiBasedVerticalDiffusivity (the reference does not checkpoint them)
             out[f"{ADDR}/diffusivity_fields/{name}/data"] = model.diffusivity_fields[name].parent()
+        # What else the closure needs to continue bit for bit (CATKEVerticalDiffusivity).  e and G⁻e are in there a SECOND time, next to the
+        # copies among the prognostic fields and tendencies: set_from_checkpoint ends with update_state!, as the reference's set! does, and
+        # with this closure that takes one more substep of e and one more average of Jᵇ; restore_state then puts everything the closure
+        # owns or steps back from closure_state/, without having to know how the fields above are keyed.
+        for name, a in model._closure.checkpoint_state(nh).items():
+            out[f"{ADDR}/closure_state/{name}"] = a
         if model.split:
             out[f"{ADDR}/U/data"] = model.U.cpu().numpy().T
             out[f"{ADDR}/V/data"] = model.V.cpu().numpy().T
@@ -255,15 +261,17 @@ def set_from_checkpoint(model, filepath):
         model.clock.last_dt = float(z[f"{ADDR}/clock/last_Δt"])
     if hyd:
         model.update_state(compute_tendencies=False)
-        if model._closure.state_fields:
-            # update_state! has just advanced the time average from whatever the model held: put back the averaged κᶜ, κᵘ that the
-            # checkpointed tendencies were computed with, so that the restart continues bit-identically
-            with np.load(filepath if str(filepath).endswith(".npz") else str(filepath) + ".npz") as z:
-                for name in model._closure.state_fields:
-                    key = f"{ADDR}/diffusivity_fields/{name}/data"
-                    if key not in z.files:
-                        raise KeyError(f"Field {name} of RiBasedVerticalDiffusivity does not exist in checkpoint and could not be restored.")
-                    model.diffusivity_fields[name].data.copy_(torch.from_numpy(np.ascontiguousarray(z[key].T)))
+        # update_state! has just advanced the closure's own state from whatever the model held (the time average of κᶜ, κᵘ; with CATKE a
+        # substep of e and an average of Jᵇ): put back what the checkpointed tendencies were computed with, so that the restart continues
+        # bit-identically
+        with np.load(filepath if str(filepath).endswith(".npz") else str(filepath) + ".npz") as z:
+            for name in model._closure.state_fields:
+                key = f"{ADDR}/diffusivity_fields/{name}/data"
+                if key not in z.files:
+                    raise KeyError(f"Field {name} of RiBasedVerticalDiffusivity does not exist in checkpoint and could not be restored.")
+                model.diffusivity_fields[name].data.copy_(torch.from_numpy(np.ascontiguousarray(z[key].T)))
+            key = lambda name: f"{ADDR}/closure_state/{name}"
+            model._closure.restore_state(model._nh, lambda name: z[key(name)] if key(name) in z.files else None)
     else:
         update_state(model, compute_tendencies=False)
     return model

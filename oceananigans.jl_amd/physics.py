@@ -8,6 +8,8 @@
                                                   .../turbulence_closure_implementations/convective_adjustment_vertical_diffusivity.jl
   RiBasedVerticalDiffusivity([time_discretization], Ri_dependent_tapering=..., horizontal_Ri_filter=..., nu_0=..., kappa_0=..., kappa_ca=..., ...)
                                                   .../turbulence_closure_implementations/ri_based_vertical_diffusivity.jl
+  CATKEVerticalDiffusivity([time_discretization], mixing_length=CATKEMixingLength(...), turbulent_kinetic_energy_equation=CATKEEquation(...), ...)
+                                                  .../turbulence_closure_implementations/TKEBasedVerticalDiffusivities/
   Smagorinsky(coefficient=..., Pr=...), SmagorinskyLilly(C=..., Cb=..., Pr=...), LillyCoefficient(...)
                                                   .../turbulence_closure_implementations/Smagorinskys/{smagorinsky,lilly_coefficient}.jl
   BuoyancyTracer(), SeawaterBuoyancy(...), LinearEquationOfState(...)
@@ -384,10 +386,124 @@ class RiBasedVerticalDiffusivity:
         return "\n".join(lines)
 
 
+class _Coefficients:
+    """a Base.@kwdef struct of numbers: ASCII keyword names are canonical, the reference's spellings are accepted after NFKC normalisation
+    (which Python applies to identifiers in source: Cʰⁱu= arrives as Chiu) and through **{...} where Python takes no such identifier"""
+    DEFAULTS, SPELLINGS = {}, {}
+
+    @classmethod
+    def canonical(cls, name):
+        import unicodedata
+        if name in cls.DEFAULTS:
+            return name
+        n = unicodedata.normalize("NFKC", name)
+        for ascii_name, spelling in cls.SPELLINGS.items():
+            if n == unicodedata.normalize("NFKC", spelling):
+                return ascii_name
+        return None
+
+    def __init__(self, **kw):
+        values, seen = dict(self.DEFAULTS), set()
+        for name, value in kw.items():
+            key = self.canonical(name)
+            if key is None:
+                raise TypeError(f"{type(self).__name__}: unexpected keyword arguments {[name]}")
+            if key in seen:
+                raise TypeError(f"{type(self).__name__}: {key} given twice")
+            seen.add(key)
+            if isinstance(value, (bool, str)) or callable(value) or not np.isscalar(value) or not np.isreal(value):
+                raise NotImplementedError(f"{type(self).__name__}: {self.SPELLINGS[key]} must be a number (arrays, fields and functions are "
+                                          "not implemented)")
+            values[key] = float(value)
+        for key, value in values.items():
+            setattr(self, key, value)
+
+    def __getattr__(self, name):  # the reference's field names: mixing_length.Cˢ, getattr(equation, "Cᵂu★")
+        key = type(self).canonical(name) if not name.startswith("_") else None
+        if key is None or key == name:
+            raise AttributeError(name)
+        return getattr(self, key)
+
+
+class CATKEMixingLength(_Coefficients):
+    """CATKEMixingLength(; Cˢ = 1.131, Cᵇ = 0.28, Cˢᵖ = 0.505, CRiᵟ = 1.02, CRi⁰ = 0.254, Cʰⁱu = 0.242, Cˡᵒu = 0.361, Cᵘⁿu = 0.370, Cᶜu = 3.705,
+    Cᵉu = 0, Cʰⁱc = 0.098, Cˡᵒc = 0.369, Cᵘⁿc = 0.572, Cᶜc = 4.793, Cᵉc = 0.112, Cʰⁱe = 0.548, Cˡᵒe = 7.863, Cᵘⁿe = 1.447, Cᶜe = 3.642, Cᵉe = 0)
+    (catke_mixing_length.jl:15-36).  ASCII: C_s, C_b, C_sp, CRi_delta, CRi_0, C_hi_u, C_lo_u, C_un_u, C_c_u, C_e_u, ... _c, ... _e."""
+    DEFAULTS = {"C_s": 1.131, "C_b": 0.28, "C_sp": 0.505, "CRi_delta": 1.02, "CRi_0": 0.254,
+                "C_hi_u": 0.242, "C_lo_u": 0.361, "C_un_u": 0.370, "C_c_u": 3.705, "C_e_u": 0.0,
+                "C_hi_c": 0.098, "C_lo_c": 0.369, "C_un_c": 0.572, "C_c_c": 4.793, "C_e_c": 0.112,
+                "C_hi_e": 0.548, "C_lo_e": 7.863, "C_un_e": 1.447, "C_c_e": 3.642, "C_e_e": 0.0}
+    SPELLINGS = {"C_s": "Cˢ", "C_b": "Cᵇ", "C_sp": "Cˢᵖ", "CRi_delta": "CRiᵟ", "CRi_0": "CRi⁰",
+                 **{f"C_{a}_{x}": f"C{s}{x}" for x in "uce" for a, s in (("hi", "ʰⁱ"), ("lo", "ˡᵒ"), ("un", "ᵘⁿ"), ("c", "ᶜ"), ("e", "ᵉ"))}}
+
+
+class CATKEEquation(_Coefficients):
+    """CATKEEquation(; CʰⁱD = 0.579, CˡᵒD = 1.604, CᵘⁿD = 0.923, CᶜD = 3.254, CᵉD = 0, Cᵂu★ = 3.179, CᵂwΔ = 0.383, Cᵂϵ = 1)
+    (catke_equation.jl:7-16).  ASCII: C_hi_D, C_lo_D, C_un_D, C_c_D, C_e_D, C_W_ustar, C_W_wdelta, C_W_eps."""
+    DEFAULTS = {"C_hi_D": 0.579, "C_lo_D": 1.604, "C_un_D": 0.923, "C_c_D": 3.254, "C_e_D": 0.0, "C_W_ustar": 3.179, "C_W_wdelta": 0.383,
+                "C_W_eps": 1.0}
+    SPELLINGS = {"C_hi_D": "CʰⁱD", "C_lo_D": "CˡᵒD", "C_un_D": "CᵘⁿD", "C_c_D": "CᶜD", "C_e_D": "CᵉD", "C_W_ustar": "Cᵂu★", "C_W_wdelta": "CᵂwΔ",
+                 "C_W_eps": "Cᵂϵ"}
+
+
+class CATKEVerticalDiffusivity:
+    """CATKEVerticalDiffusivity([time_discretization = VerticallyImplicitTimeDiscretization()]; mixing_length = CATKEMixingLength(),
+    turbulent_kinetic_energy_equation = CATKEEquation(), maximum_tracer_diffusivity = Inf, maximum_tke_diffusivity = Inf,
+    maximum_viscosity = Inf, minimum_tke = 1e-9, minimum_convective_buoyancy_flux = 1e-11, negative_tke_damping_time_scale = 1minute,
+    tke_time_step = nothing) (catke_vertical_diffusivity.jl:96-120): κᵘ, κᶜ, κᵉ from a prognostic turbulent kinetic energy, the tracer "e",
+    which the closure steps itself.  HydrostaticFreeSurfaceModel only; the explicit discretization, arrays of closures (ensembles) and
+    coefficients that are no numbers are not implemented."""
+    NUMBERS = {"maximum_tracer_diffusivity": math.inf, "maximum_tke_diffusivity": math.inf, "maximum_viscosity": math.inf, "minimum_tke": 1e-9,
+               "minimum_convective_buoyancy_flux": 1e-11, "negative_tke_damping_time_scale": 60.0}
+    MISSING_TRACER = "Tracers must contain :e to represent turbulent kinetic energy for `CATKEVerticalDiffusivity`."
+
+    def __init__(self, *args, **kw):
+        if len(args) > 1:
+            raise TypeError("CATKEVerticalDiffusivity takes one positional argument, the time discretization")
+        if args:
+            if "time_discretization" in kw:
+                raise TypeError("time_discretization given twice")
+            kw["time_discretization"] = args[0]
+        self.time_discretization = as_time_discretization(kw.pop("time_discretization", VerticallyImplicitTimeDiscretization()))
+        if not isinstance(self.time_discretization, VerticallyImplicitTimeDiscretization):
+            raise NotImplementedError("CATKEVerticalDiffusivity with ExplicitTimeDiscretization is not implemented: use the default "
+                                      "VerticallyImplicitTimeDiscretization()")
+        mixing_length = kw.pop("mixing_length", None)
+        equation = kw.pop("turbulent_kinetic_energy_equation", None)
+        self.mixing_length = CATKEMixingLength() if mixing_length is None else mixing_length
+        self.turbulent_kinetic_energy_equation = CATKEEquation() if equation is None else equation
+        if not isinstance(self.mixing_length, CATKEMixingLength):
+            raise TypeError("mixing_length must be CATKEMixingLength(...)")
+        if not isinstance(self.turbulent_kinetic_energy_equation, CATKEEquation):
+            raise TypeError("turbulent_kinetic_energy_equation must be CATKEEquation(...)")
+        for key, default in self.NUMBERS.items():
+            value = kw.pop(key, default)
+            if isinstance(value, (bool, str)) or callable(value) or not np.isscalar(value) or not np.isreal(value):
+                raise NotImplementedError(f"CATKEVerticalDiffusivity: {key} must be a number (arrays, fields and functions are not implemented)")
+            setattr(self, key, float(value))
+        tke_time_step = kw.pop("tke_time_step", None)
+        if tke_time_step is not None:
+            if isinstance(tke_time_step, (bool, str)) or not np.isscalar(tke_time_step) or not np.isreal(tke_time_step) or not tke_time_step > 0:
+                raise ValueError("tke_time_step must be None or a positive number")
+            tke_time_step = float(tke_time_step)
+        self.tke_time_step = tke_time_step
+        if kw:
+            raise TypeError(f"unexpected keyword arguments {sorted(kw)}")
+
+    def c_struct(self):
+        """struct ocn_catke"""
+        ml, eq = self.mixing_length, self.turbulent_kinetic_energy_equation
+        source = {**{k: getattr(ml, k) for k in ml.DEFAULTS}, **{k: getattr(eq, k) for k in eq.DEFAULTS}, **{k: getattr(self, k) for k in self.NUMBERS}}
+        return _lib.CCatke(*[source[name] for name in _lib.CATKE_FIELDS])
+
+    def __repr__(self):  # Base.summary (catke_vertical_diffusivity.jl:334-337)
+        return f"CATKEVerticalDiffusivity{{{type(self.time_discretization).__name__}}}"
+
+
 def has_diffusivity_fields(closure):
     """closures of the VerticalFormulation whose κᶜ, κᵘ are (Center, Center, Face) fields that the HydrostaticFreeSurfaceModel computes in
     update_state! (their term and implicit step: csrc/vertical_diffusivity.hip)"""
-    return isinstance(closure, (ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity))
+    return isinstance(closure, (ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity, CATKEVerticalDiffusivity))
 
 
 class ThreeDimensionalFormulation:
