@@ -571,6 +571,41 @@ int ocn_catke_substep_tke(const ocn_grid *grid, const ocn_model_terms *terms, co
 int ocn_add_biharmonic_fluxes(const ocn_grid *grid, double nu, const double *u, const double *v, double *Gu, double *Gv, int32_t n_tracers,
                               const double *kappa, const double *const *c, double *const *Gc, const double *neg_other_u,
                               const double *neg_other_v, const double *const *neg_other_c, void *stream);
+/* ---- IsopycnalSkewSymmetricDiffusivity (csrc/isopycnal.hip; turbulence_closure_implementations/isopycnal_skew_symmetric_diffusivity.jl,
+ * advective_skew_diffusion.jl, isopycnal_rotation_tensor_components.jl): SmallSlopeIsopycnalTensor, FluxTapering, vertically implicit, number
+ * coefficients.  The grid: (Periodic, Periodic, Bounded), x and y regular, halos >= 1, one GPU; strict math whatever the math mode.
+ * terms: buoyancy kind, g, alpha, beta, T, S are read; ∂x b, ∂y b, ∂z b are formed from T and S (or b) as the reference forms them. */
+typedef struct ocn_isopycnal {
+    double max_slope;  /* FluxTapering(max_slope): finite, > 0 */
+    double minimum_bz; /* SmallSlopeIsopycnalTensor(minimum_bz): no NaN */
+} ocn_isopycnal;
+/* compute_diffusivities! (:118-143, advective_skew_diffusion.jl:9-76) over i = 1..Nx, j = 1..Ny, faces k = 1..Nz in ONE launch:
+ *   eps_R33 = tapering_factorᶜᶜᶠ · isopycnal_rotation_tensor_zz_ccf at (Center, Center, Face); face Nz + 1 and the halos are not written;
+ *   kz[q] = eps_R33 · kappa_symmetric[q], q = 0..n_kz-1 (0 .. OCN_MODEL_MAX_TRACERS; HOST arrays of numbers / device pointers to
+ *   (Center, Center, Face) arrays): the κz of the implicit step, one array per distinct coefficient;
+ *   ue != NULL (then ve, we too): the eddy velocities uₑ = -∂z(kappa_skew Sxᶠᶜᶠ), vₑ = -∂z(kappa_skew Syᶜᶠᶠ) at cells k = 1..Nz and
+ *   wₑ = ∂x(kappa_skew Sxᶠᶜᶠ) + ∂y(kappa_skew Syᶜᶠᶠ) at faces 2..Nz, with faces 1 and Nz + 1 of wₑ set to 0 (what the Impenetrable condition of
+ *   the reference's halo fill leaves there).  Halos: the caller fills them (ocn_fill_halo_regions without the open fill).
+ * T, S (or b) are read at i - 1..i + 1, j - 1..j + 1 (no corners), k = 0..Nz + 1.
+ * OCN_ERR_INVALID_ARGUMENT: a grid outside the scope, an unknown buoyancy kind or one whose tracer pointer is NULL, a max_slope that is
+ * not finite and positive, a coefficient that is not finite, aliased outputs, ue without ve and we. */
+int ocn_compute_isopycnal_diffusivities(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_isopycnal *closure, double kappa_skew,
+                                        double *eps_R33, double *ue, double *ve, double *we, int32_t n_kz, const double *kappa_symmetric,
+                                        double *const *kz, void *stream);
+/* SumOfArrays{2}(u, uₑ) (Utils/sum_of_arrays.jl:23) materialized: out[f][q] = a[f][q] + b[f][q] over the WHOLE parent arrays (halos included)
+ * of the three velocity locations (Face, Center, Center), (Center, Face, Center), (Center, Center, Face).  a, b, out: HOST arrays of three
+ * device pointers.  One launch. */
+int ocn_sum_velocities(const ocn_grid *grid, const double *const *a, const double *const *b, double *const *out, void *stream);
+/* Gc[n] -= ∇·q over i = 1..Nx, j = 1..Ny, k = 1..Nz with diffusive_flux_x / y / z of :229-314 (the vertically implicit z flux: no
+ * κ_symmetric R₃₃ ∂z c; that is the implicit step with kz) and kappa_symmetric[n], kappa_skew[n] of tracer n (kappa_skew[n] = 0 with the
+ * AdvectiveFormulation, :225-226).  c / Gc: HOST arrays of n_tracers (1 .. OCN_MODEL_MAX_TRACERS) device pointers; c[n] may be T or S.
+ * ϵ and R₁₃, R₂₃, R₃₁, R₃₂ are computed once per face and launch; two tracers share a launch.  The fluxes through faces 1 and Nz + 1 come
+ * from the formula.  c and T, S (or b) are read at i - 1..i + 1, j - 1..j + 1, k = 0..Nz + 1 (their halos must be filled); nothing but
+ * interior cells of Gc is written.  Into a zeroed array the call leaves 0 - ∇·q: the neg_other_c of ocn_add_biharmonic_fluxes.
+ * OCN_ERR_INVALID_ARGUMENT as above, and: n_tracers outside its range, a NULL pointer, a Gc that is another array of the call. */
+int ocn_add_isopycnal_fluxes(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_isopycnal *closure, int32_t n_tracers,
+                             const double *kappa_symmetric, const double *kappa_skew, const double *const *c, double *const *Gc,
+                             void *stream);
 /* cache_previous_tendencies! (src/TimeSteppers/store_tendencies.jl:6-22) */
 int ocn_cache_previous_tendencies(const ocn_grid *grid, int32_t n, double *const *Gm, const double *const *Gn,
                                   const int32_t *locs, void *stream);

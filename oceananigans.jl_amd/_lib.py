@@ -92,6 +92,11 @@ class CRiBased(C.Structure):
                                            "maximum_diffusivity", "maximum_viscosity")] + [("tapering", C.c_int32), ("horizontal_filter", C.c_int32)]
 
 
+class CIsopycnal(C.Structure):
+    """struct ocn_isopycnal"""
+    _fields_ = [("max_slope", C.c_double), ("minimum_bz", C.c_double)]
+
+
 CATKE_FIELDS = ("C_s", "C_b", "C_sp", "CRi_delta", "CRi_0", "C_hi_u", "C_lo_u", "C_un_u", "C_c_u", "C_e_u", "C_hi_c", "C_lo_c", "C_un_c", "C_c_c",
                 "C_e_c", "C_hi_e", "C_lo_e", "C_un_e", "C_c_e", "C_e_e", "C_hi_D", "C_lo_D", "C_un_D", "C_c_D", "C_e_D", "C_W_ustar", "C_W_wdelta",
                 "C_W_eps", "maximum_tracer_diffusivity", "maximum_tke_diffusivity", "maximum_viscosity", "minimum_tke",
@@ -212,6 +217,11 @@ _SIGS = {
     "ocn_implicit_vertical_diffusion_step_fields": [C.POINTER(CGrid), _i32, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_vp), C.POINTER(_vp), _dbl, _vp],
     "ocn_add_biharmonic_fluxes": [C.POINTER(CGrid), _dbl, _vp, _vp, _vp, _vp, _i32, C.POINTER(_dbl), C.POINTER(_vp), C.POINTER(_vp), _vp, _vp,
                                   C.POINTER(_vp), _vp],
+    "ocn_compute_isopycnal_diffusivities": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CIsopycnal), _dbl, _vp, _vp, _vp, _vp, _i32,
+                                            C.POINTER(_dbl), C.POINTER(_vp), _vp],
+    "ocn_sum_velocities": [C.POINTER(CGrid), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp],
+    "ocn_add_isopycnal_fluxes": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CIsopycnal), _i32, C.POINTER(_dbl), C.POINTER(_dbl),
+                                 C.POINTER(_vp), C.POINTER(_vp), _vp],
     "ocn_compute_ri_number": [C.POINTER(CGrid), C.POINTER(CModelTerms), _vp, _vp, _vp, _vp],
     "ocn_compute_ri_based_diffusivities": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CRiBased), C.POINTER(CBc), C.POINTER(CBc), _vp, _vp,
                                            _vp, _vp],

@@ -1535,6 +1535,87 @@ int ocn_add_biharmonic_fluxes(const ocn_grid *grid, double nu, const double *u, 
 }
 
 // the three entry points of ri_based_diffusivity.hip
+static int validate_ri_buoyancy(const ocn_model_terms *terms, const char *who);
+
+// isopycnal.hip: everything is checked on the host before the first HIP call
+static int validate_isopycnal(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_isopycnal *closure, const char *who)
+{
+    int st = validate_grid_any(grid);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(grid->tx == OCN_PERIODIC && grid->ty == OCN_PERIODIC && grid->tz == OCN_BOUNDED,
+                "%s: the grid must be (Periodic, Periodic, Bounded), got topology (%d, %d, %d)", who, grid->tx, grid->ty, grid->tz);
+    OCN_REQUIRE(grid->Hx >= 1 && grid->Hy >= 1 && grid->Hz >= 1, "%s: halo >= 1 required", who);
+    st = validate_ri_buoyancy(terms, who);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(closure, "%s: null closure", who);
+    OCN_REQUIRE(std::isfinite(closure->max_slope) && closure->max_slope > 0, "%s: max_slope = %g must be finite and > 0", who, closure->max_slope);
+    OCN_REQUIRE(!std::isnan(closure->minimum_bz), "%s: minimum_bz is a NaN", who);
+    return OCN_SUCCESS;
+}
+
+int ocn_compute_isopycnal_diffusivities(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_isopycnal *closure, double kappa_skew,
+                                        double *eps_R33, double *ue, double *ve, double *we, int32_t n_kz, const double *kappa_symmetric,
+                                        double *const *kz, void *stream)
+{
+    const char *who = "ocn_compute_isopycnal_diffusivities";
+    int st = validate_isopycnal(grid, terms, closure, who);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(eps_R33, "%s: eps_R33 is NULL", who);
+    OCN_REQUIRE(n_kz >= 0 && n_kz <= OCN_MODEL_MAX_TRACERS, "%s: n_kz = %d outside 0..%d", who, n_kz, OCN_MODEL_MAX_TRACERS);
+    if (n_kz) OCN_REQUIRE(kappa_symmetric && kz, "%s: null kappa_symmetric / kz array", who);
+    const void *out[4 + OCN_MODEL_MAX_TRACERS];
+    int n_out = 0;
+    out[n_out++] = eps_R33;
+    if (ue) {
+        OCN_REQUIRE(ve && we, "%s: ue is given: ve and we are needed", who);
+        OCN_REQUIRE(std::isfinite(kappa_skew), "%s: kappa_skew = %g must be finite", who, kappa_skew);
+        out[n_out++] = ue;
+        out[n_out++] = ve;
+        out[n_out++] = we;
+    } else {
+        OCN_REQUIRE(!ve && !we, "%s: ue is NULL (no eddy velocities) but ve or we is not", who);
+    }
+    for (int q = 0; q < n_kz; ++q) {
+        OCN_REQUIRE(kz[q], "%s: kz[%d] is NULL", who, q);
+        OCN_REQUIRE(std::isfinite(kappa_symmetric[q]), "%s: kappa_symmetric[%d] = %g must be finite", who, q, kappa_symmetric[q]);
+        out[n_out++] = kz[q];
+    }
+    for (int q = 0; q < n_out; ++q) {
+        OCN_REQUIRE(out[q] != terms->T && out[q] != terms->S, "%s: an output array is T or S", who);
+        for (int p = 0; p < q; ++p) OCN_REQUIRE(out[p] != out[q], "%s: two of the output arrays are the same array", who);
+    }
+    return launch_isopycnal_diffusivities(grid, terms, closure, kappa_skew, eps_R33, ue, ve, we, n_kz, kappa_symmetric, kz, as_stream(stream));
+}
+
+int ocn_sum_velocities(const ocn_grid *grid, const double *const *a, const double *const *b, double *const *out, void *stream)
+{
+    const char *who = "ocn_sum_velocities";
+    int st = validate_grid_any(grid);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(a && b && out, "%s: null tuple pointer", who);
+    for (int f = 0; f < 3; ++f) OCN_REQUIRE(a[f] && b[f] && out[f], "%s: field %d: null pointer", who, f);
+    return launch_sum_velocities(grid, a, b, out, as_stream(stream));
+}
+
+int ocn_add_isopycnal_fluxes(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_isopycnal *closure, int32_t n_tracers,
+                             const double *kappa_symmetric, const double *kappa_skew, const double *const *c, double *const *Gc, void *stream)
+{
+    const char *who = "ocn_add_isopycnal_fluxes";
+    int st = validate_isopycnal(grid, terms, closure, who);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(n_tracers >= 1 && n_tracers <= OCN_MODEL_MAX_TRACERS, "%s: number of tracers %d outside 1..%d", who, n_tracers,
+                OCN_MODEL_MAX_TRACERS);
+    OCN_REQUIRE(kappa_symmetric && kappa_skew && c && Gc, "%s: null tracer array", who);
+    for (int n = 0; n < n_tracers; ++n) {
+        OCN_REQUIRE(c[n] && Gc[n], "%s: tracer %d: null pointer", who, n);
+        OCN_REQUIRE(std::isfinite(kappa_symmetric[n]) && std::isfinite(kappa_skew[n]), "%s: tracer %d: the coefficients must be finite", who, n);
+        OCN_REQUIRE(Gc[n] != terms->T && Gc[n] != terms->S, "%s: tendency %d is T or S", who, n);
+        for (int m = 0; m < n_tracers; ++m) OCN_REQUIRE(Gc[n] != c[m], "%s: tendency %d is tracer %d", who, n, m);
+        for (int m = 0; m < n; ++m) OCN_REQUIRE(Gc[n] != Gc[m], "%s: tendencies %d and %d are the same array", who, m, n);
+    }
+    return launch_isopycnal_fluxes(grid, terms, closure, n_tracers, kappa_symmetric, kappa_skew, c, Gc, as_stream(stream));
+}
+
 static int validate_ri_buoyancy(const ocn_model_terms *terms, const char *who)
 {
     OCN_REQUIRE(terms, "%s: null terms", who);

@@ -102,6 +102,14 @@ void ri_taper_host(int kind, long long n, const double *x, double x0, double del
 int launch_biharmonic_fluxes(const ocn_grid *grid, double nu, const double *u, const double *v, double *Gu, double *Gv, int n_tracers,
                              const double *kappa, const double *const *c, double *const *Gc, const double *neg_other_u,
                              const double *neg_other_v, const double *const *neg_other_c, hipStream_t stream);
+// isopycnal.hip: IsopycnalSkewSymmetricDiffusivity: ϵ_R₃₃, the κz fields and the eddy velocities; the total velocities; the flux divergence
+int launch_isopycnal_diffusivities(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_isopycnal *closure, double kappa_skew,
+                                   double *eps_R33, double *ue, double *ve, double *we, int n_kz, const double *kappa_symmetric,
+                                   double *const *kz, hipStream_t stream);
+int launch_sum_velocities(const ocn_grid *grid, const double *const *a, const double *const *b, double *const *out, hipStream_t stream);
+int launch_isopycnal_fluxes(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_isopycnal *closure, int n_tracers,
+                            const double *kappa_symmetric, const double *kappa_skew, const double *const *c, double *const *Gc,
+                            hipStream_t stream);
 int launch_profile_marker(hipStream_t stream);
 int wait_stream(hipStream_t stream, double seconds, const char *who);
 int launch_hydrostatic_pressure(const ocn_grid *grid, const TermsDev &t, double *pHY, hipStream_t stream, const int32_t *irange = nullptr);

@@ -561,9 +561,9 @@ class HydrostaticFreeSurfaceModel:
         terms = C.byref(nh._terms)  # (of the closure they hold what the container was given: hydrostatic_closures.py)
         _lib.call("ocn_add_momentum_terms", g.cref, terms, self.u.ptr, self.v.ptr, self.w.ptr, Gn[0].ptr, Gn[1].ptr,
                   Gn[2].ptr, None, s)                                                               # - f x U - ∇pHY′ - ∂ⱼτᵢⱼ
+        ua, va, wa = self._closure.advecting_velocities(nh)  # (u, v, w but for a closure with eddy velocities)
         for name, c, G in zip(self.tracer_names, self.tracers, Gn[3:]):
-            _lib.call("ocn_compute_tracer_tendency_terms", g.cref, terms, self._closure.tracer_kappa(name), None, self.u.ptr, self.v.ptr,
-                      self.w.ptr, c.ptr, G.ptr, None, s)
+            _lib.call("ocn_compute_tracer_tendency_terms", g.cref, terms, self._closure.tracer_kappa(name), None, ua, va, wa, c.ptr, G.ptr, None, s)
         self._closure.add_fluxes(nh, Gn, s)  # the term of every other closure
         if boundary_contributions:
             compute_boundary_tendency_contributions(nh)

@@ -4,8 +4,8 @@ compute_diffusivities!, the flux divergences, implicit_step! and required_halo_s
 `resolve_closure` turns the user's closure into ONE object, or refuses; it allocates nothing and touches no device.  The model asks that
 object: at construction `container_closure` (what ocn_model_terms carries: an explicit ScalarDiffusivity or None), `halo`, `unfused` and
 `allocate(nh)` (the diffusivity_fields dict, or None) and `boundary_conditions(user_bcs, grid)` (the conditions the fields are built with); in
-update_state `compute_diffusivities(nh)`; in compute_tendencies `tracer_kappa(name)` for the built-in tracer entry point and
-`add_fluxes(nh, Gn, s)` after those entry points; in time_step `self_stepped` (the tracers that ab2_step, implicit_step and
+update_state `compute_diffusivities(nh)`; in compute_tendencies `tracer_kappa(name)` and `advecting_velocities(nh)` (u, v, w, plus the eddy
+velocities of IsopycnalSkewSymmetricDiffusivity) for the built-in tracer entry point and `add_fluxes(nh, Gn, s)` after those entry points; in time_step `self_stepped` (the tracers that ab2_step, implicit_step and
 cache_previous_tendencies leave to the closure) and `implicit_step(nh, fields, dt, s)` after ocn_ab2_step; checkpoints read `state_fields`,
 `checkpoint_state(nh)` and call `restore_state(nh, get)`.  Every kind but InModelTerms keeps the closure out of ocn_model_terms and runs the
 reference's launch sequence (fused = False) with QAB2 on one GPU."""
@@ -19,8 +19,9 @@ from . import _lib
 from .architectures import stream_ptr
 from .fields import CenterField, XFaceField, YFaceField, ZFaceField, fill_halo_regions
 from .models import implicit_diffusion_step
-from .physics import (BuoyancyTracer, CATKEVerticalDiffusivity, FieldBoundaryConditions, FluxBoundaryCondition, RiBasedVerticalDiffusivity,
-                      ScalarBiharmonicDiffusivity, SeawaterBuoyancy, has_diffusivity_fields, is_vertically_implicit, owns_eddy_fields)
+from .physics import (BuoyancyTracer, CATKEVerticalDiffusivity, FieldBoundaryConditions, FluxBoundaryCondition, IsopycnalSkewSymmetricDiffusivity,
+                      RiBasedVerticalDiffusivity, ScalarBiharmonicDiffusivity, SeawaterBuoyancy, has_diffusivity_fields, is_vertically_implicit,
+                      owns_eddy_fields)
 
 
 def _refuse(what, fused, split_rk3, slabs):
@@ -40,7 +41,7 @@ def resolve_closure(closure, fused, split_rk3, partitioned, distributed, buoyanc
         raise NotImplementedError("arrays of closures (ensembles) are not implemented: give one closure")
     if isinstance(closure, (tuple, list)):  # (closure_tuples.jl) the biharmonic with a closure that has κ fields, in either order
         biharmonic = [c for c in closure if isinstance(c, ScalarBiharmonicDiffusivity)]
-        vertical = [c for c in closure if has_diffusivity_fields(c)]
+        vertical = [c for c in closure if has_diffusivity_fields(c) or isinstance(c, IsopycnalSkewSymmetricDiffusivity)]
         if len(closure) != 2 or len(biharmonic) != 1 or len(vertical) != 1:
             raise NotImplementedError("closure tuples are not implemented, except (HorizontalScalarBiharmonicDiffusivity, "
                                       "ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity or CATKEVerticalDiffusivity) in either order: "
@@ -54,7 +55,14 @@ def resolve_closure(closure, fused, split_rk3, partitioned, distributed, buoyanc
     if owns_eddy_fields(closure):
         raise NotImplementedError("eddy-viscosity closures are not part of this slice")
     other = None
-    if has_diffusivity_fields(closure):
+    if isinstance(closure, IsopycnalSkewSymmetricDiffusivity):
+        _refuse("IsopycnalSkewSymmetricDiffusivity", fused, split_rk3, partitioned)
+        for kappa in (closure.kappa_symmetric, closure.kappa_skew):  # tracer_diffusivities (with_tracers, :76-86)
+            for name in tuple(tracers) if isinstance(kappa, dict) else ():
+                if name not in kappa:
+                    raise ValueError(f"no diffusivity κ given for tracer {name}")
+        other = IsopycnalFields(closure)
+    elif has_diffusivity_fields(closure):
         _refuse(type(closure).__name__, fused, split_rk3, partitioned)
         carriers = None
         if isinstance(closure, CATKEVerticalDiffusivity):
@@ -118,6 +126,10 @@ class InModelTerms:
 
     def implicit_step(self, nh, fields, dt, s):
         pass
+
+    def advecting_velocities(self, nh):
+        """pointers to the velocities that advect the tracers (div_Uc): u, v, w, plus the eddy velocities of a closure that has some"""
+        return nh.u.ptr, nh.v.ptr, nh.w.ptr
 
 
 class ImplicitScalar(InModelTerms):
@@ -324,6 +336,86 @@ class CATKEFields(KappaFields):
         self.previous_compute_time = float(get("previous_compute_time"))
 
 
+class IsopycnalFields(InModelTerms):
+    """IsopycnalSkewSymmetricDiffusivity (csrc/isopycnal.hip): the tapered ϵ_R₃₃ at (Center, Center, Face) and, with skew advection, the eddy
+    velocities u, v, w (build_diffusivity_fields, isopycnal_skew_symmetric_diffusivity.jl:102-116), computed in update_state! in one launch with
+    the κz = ϵ_R₃₃ κ_symmetric arrays of the implicit step, one per distinct κ_symmetric.  The tracers are advected by u + uₑ, v + vₑ, w + wₑ
+    (SumOfArrays, hydrostatic_free_surface_tendency_kernel_functions.jl), materialized after the halo fill; momentum keeps u, v, w and has no
+    term (the closure has no viscosity).  Nothing is state: every field is recomputed from the tracers."""
+    container_closure, unfused = None, True
+
+    def __init__(self, closure):
+        self.closure, self.halo = closure, closure.required_halo_size
+        self.eddy = closure.advective and closure.kappa_skew is not None          # (:110-113)
+        self.no_diffusion = closure.advective and closure.kappa_symmetric is None  # NoDiffusionISSD: the three fluxes are zero (:215-217)
+        self.implicit = closure.kappa_symmetric is not None
+
+    def allocate(self, nh):
+        g, cl = nh.grid, self.closure
+        self.fields = {"eps_R33": ZFaceField(g)}
+        if self.eddy:
+            self.fields.update(u=XFaceField(g), v=YFaceField(g), w=ZFaceField(g))
+            self.total = (XFaceField(g), YFaceField(g), ZFaceField(g))
+        self.struct, self._terms = cl.c_struct(), nh._terms
+        # κz of the implicit step: one array and one set of multipliers per distinct κ_symmetric
+        self.kz = {}
+        for name in nh.tracer_names if self.implicit else ():
+            self.kz.setdefault(cl.kappa_symmetric_of(name), ZFaceField(g))
+        if len(self.kz) > _lib.MODEL_MAX_TRACERS:
+            raise NotImplementedError(f"IsopycnalSkewSymmetricDiffusivity: more than {_lib.MODEL_MAX_TRACERS} distinct κ_symmetric")
+        if self.kz:
+            self.ivd_scratch = torch.zeros((len(self.kz), g.Nz, g.Ny, g.Nx), dtype=torch.float64, device=nh.u.data.device)
+        return self.fields
+
+    def compute_diffusivities(self, nh):
+        """compute_diffusivities! (:118-132), then fill_halo_regions!(diffusivity_fields; only_local_halos = true): ϵ_R₃₃ has no condition
+        in z; uₑ, vₑ take the no-flux mirror; wₑ's Impenetrable condition (0 on faces 1 and Nz + 1) is written by the kernel"""
+        g, d, s, pa = nh.grid, self.fields, stream_ptr(), _lib.ptr_array
+        nh._refresh_term_pointers()
+        eddy = [d[n].ptr for n in "uvw"] if self.eddy else [None] * 3
+        ks = list(self.kz)
+        _lib.call("ocn_compute_isopycnal_diffusivities", g.cref, C.byref(nh._terms), C.byref(self.struct),
+                  self.closure.kappa_skew if self.eddy else 0.0, d["eps_R33"].ptr, *eddy, len(ks), (C.c_double * len(ks))(*ks) if ks else None,
+                  pa([self.kz[k].ptr for k in ks]) if ks else None, s)
+        fill_halo_regions(tuple(d.values()), fill_boundary_normal_velocities=False)
+        if self.eddy:
+            _lib.call("ocn_sum_velocities", g.cref, pa([nh.u.ptr, nh.v.ptr, nh.w.ptr]), pa(eddy), pa([f.ptr for f in self.total]), s)
+
+    def advecting_velocities(self, nh):
+        return tuple(f.ptr for f in self.total) if self.eddy else (nh.u.ptr, nh.v.ptr, nh.w.ptr)
+
+    def kappa_of_tracer(self, name):
+        """(κ_symmetric, κ_skew) of a tracer as the diffusive fluxes take them"""
+        return self.closure.kappa_symmetric_of(name), self.closure.kappa_skew_of(name)
+
+    def add_to(self, g, u, v, Gu, Gv, nt, c, G, s, kappas=None):
+        """G -= ∇·q of the tracers (pointers; c, G: lists; kappas: kappa_of_tracer of each); no momentum term.  The arguments of
+        KappaFields.add_to, so that the pair with the biharmonic closure calls both alike"""
+        if not nt or self.no_diffusion:
+            return
+        M = _lib.MODEL_MAX_TRACERS
+        for q in range(0, nt, M):
+            n = min(M, nt - q)
+            ks, kw = zip(*kappas[q:q + n])
+            _lib.call("ocn_add_isopycnal_fluxes", g.cref, C.byref(self._terms), C.byref(self.struct), n, (C.c_double * n)(*ks), (C.c_double * n)(*kw),
+                      _lib.ptr_array(c[q:q + n]), _lib.ptr_array(G[q:q + n]), s)
+
+    def add_fluxes(self, nh, Gn, s):
+        self.add_to(nh.grid, None, None, None, None, len(nh.tracers), [c.ptr for c in nh.tracers], [G.ptr for G in Gn[3:]], s,
+                    kappas=[self.kappa_of_tracer(n) for n in nh.tracer_names])
+
+    def implicit_step(self, nh, fields, dt, s):
+        """implicit_step! of the tracers with κz = ϵ_R₃₃ κ_symmetric (:327-332) of the last update_state!; u and v are not stepped"""
+        tracers = fields[2:]
+        if not self.implicit or not tracers:
+            return
+        ks = list(self.kz)
+        index = [ks.index(self.closure.kappa_symmetric_of(n)) for n in nh.tracer_names]
+        _lib.call("ocn_implicit_vertical_diffusion_step_fields", nh.grid.cref, len(tracers), _lib.ptr_array([f.ptr for f in tracers]),
+                  _lib.i32_array([f.loc for f in tracers]), _lib.ptr_array([self.kz[ks[q]].ptr for q in index]),
+                  _lib.ptr_array([self.ivd_scratch[q].data_ptr() for q in index]), float(dt), s)
+
+
 class Biharmonic(InModelTerms):
     """G -= ∂ⱼτ of HorizontalScalarBiharmonicDiffusivity -- or, in a pair with a closure V that has κ fields, G -= (∂ⱼτ + ∂ⱼτ(V)), the sum
     formed before it is subtracted (closure_tuples.jl:41-43): V's kernel leaves 0 - ∂ⱼτ(V) in a zeroed array, which the biharmonic kernel
@@ -331,11 +423,12 @@ class Biharmonic(InModelTerms):
     container_closure, unfused = None, True
 
     def __init__(self, closure, other):
-        self.closure, self.other, self.halo = closure, other, closure.required_halo_size
+        self.closure, self.other, self.halo = closure, other, max(closure.required_halo_size, getattr(other, "halo", 0))
         if other is not None:
             self.implicit, self.state_fields, self.self_stepped = other.implicit, other.state_fields, other.self_stepped
             self.compute_diffusivities, self.implicit_step = other.compute_diffusivities, other.implicit_step
             self.boundary_conditions, self.checkpoint_state, self.restore_state = other.boundary_conditions, other.checkpoint_state, other.restore_state
+            self.advecting_velocities = other.advecting_velocities
 
     def allocate(self, nh):
         if self.other is None:

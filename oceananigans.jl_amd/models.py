@@ -29,7 +29,7 @@ import ctypes as C
 
 from .advection import WENO, UpwindBiased
 from .physics import (AnisotropicMinimumDissipation, BetaPlane, BuoyancyTracer, Centered,
-                      FieldBoundaryConditions, FPlane, ScalarBiharmonicDiffusivity, ScalarDiffusivity,
+                      FieldBoundaryConditions, FPlane, IsopycnalSkewSymmetricDiffusivity, ScalarBiharmonicDiffusivity, ScalarDiffusivity,
                       SeawaterBuoyancy, Smagorinsky, has_diffusivity_fields, implicit_diffusion_solver, is_vertically_implicit, owns_eddy_fields)
 from .architectures import stream_ptr
 from .fields import CenterField, Field, XFaceField, YFaceField, ZFaceField, fill_halo_regions
@@ -130,6 +130,10 @@ class NonhydrostaticModel:
         if has_diffusivity_fields(closure):
             raise NotImplementedError(f"closure = {type(closure).__name__} on NonhydrostaticModel is not implemented (w would need "
                                       "the Face-in-z rows of the field-valued implicit step); HydrostaticFreeSurfaceModel takes it (see DESIGN.md §5.2j)")
+        if isinstance(closure, IsopycnalSkewSymmetricDiffusivity):
+            raise NotImplementedError("closure = IsopycnalSkewSymmetricDiffusivity on NonhydrostaticModel is not implemented (the reference steps "
+                                      "it on HydrostaticFreeSurfaceModel only, and w would need the Face-in-z rows of the field-valued implicit "
+                                      "step); HydrostaticFreeSurfaceModel takes it (see DESIGN.md §5.2p)")
         if closure is not None and not isinstance(closure, (ScalarDiffusivity, AnisotropicMinimumDissipation, Smagorinsky)):
             raise NotImplementedError("only closure = ScalarDiffusivity(...), AnisotropicMinimumDissipation(...), Smagorinsky(...) or "
                                       "SmagorinskyLilly(...) is implemented")

@@ -271,8 +271,9 @@ class FivePointHorizontalFilter:
         return "FivePointHorizontalFilter"
 
 
-def _prettysummary(x):
-    """prettysummary(::AbstractFloat) (Grids/grid_utils.jl:278): Julia's shortest representation, compact (at most six significant digits)"""
+def _prettysummary(x, compact=True):
+    """prettysummary(::AbstractFloat) (Grids/grid_utils.jl:278): Julia's shortest representation, compact (at most six significant digits);
+    compact = False: string(::Float64), every digit of the shortest representation"""
     from decimal import Decimal
     x = float(x)
     if x != x:
@@ -282,7 +283,7 @@ def _prettysummary(x):
     if x == 0:
         return "-0.0" if math.copysign(1.0, x) < 0 else "0.0"
     d = Decimal(repr(x))
-    if len(d.as_tuple().digits) > 6:
+    if compact and len(d.as_tuple().digits) > 6:
         d = Decimal(f"{x:.5e}")
     sign, digits, exp = d.normalize().as_tuple()
     digits = "".join(map(str, digits))
@@ -504,6 +505,162 @@ def has_diffusivity_fields(closure):
     """closures of the VerticalFormulation whose κᶜ, κᵘ are (Center, Center, Face) fields that the HydrostaticFreeSurfaceModel computes in
     update_state! (their term and implicit step: csrc/vertical_diffusivity.hip)"""
     return isinstance(closure, (ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity, CATKEVerticalDiffusivity))
+
+
+class AdvectiveFormulation:
+    """AdvectiveFormulation() (isopycnal_skew_symmetric_diffusivity.jl:3): the skew flux as advection by the eddy velocities"""
+
+    def __repr__(self):
+        return type(self).__name__ + "()"
+
+
+class DiffusiveFormulation:
+    """DiffusiveFormulation() (:4): the skew flux as the antisymmetric part of the diffusion tensor"""
+
+    def __repr__(self):
+        return type(self).__name__ + "()"
+
+
+class SmallSlopeIsopycnalTensor:
+    """SmallSlopeIsopycnalTensor(; minimum_bz = 0) (isopycnal_rotation_tensor_components.jl:60-64)"""
+
+    def __init__(self, minimum_bz=0.0):
+        if isinstance(minimum_bz, (bool, str)) or not np.isscalar(minimum_bz) or not np.isreal(minimum_bz) or math.isnan(minimum_bz):
+            raise ValueError("minimum_bz must be a number")
+        self.minimum_bz = float(minimum_bz)
+
+    def __repr__(self):
+        return f"{type(self).__name__}{{Float64}}({_prettysummary(self.minimum_bz, compact=False)})"
+
+
+class IsopycnalTensor(SmallSlopeIsopycnalTensor):
+    """IsopycnalTensor(minimum_bz) (:28-30): constructible; IsopycnalSkewSymmetricDiffusivity refuses it, as the reference does"""
+
+    def __init__(self, minimum_bz):
+        super().__init__(minimum_bz)
+
+
+class FluxTapering:
+    """FluxTapering(max_slope) (isopycnal_skew_symmetric_diffusivity.jl:149-151): every flux is scaled by min(1, max_slope² / slope²)"""
+
+    def __init__(self, max_slope):
+        if isinstance(max_slope, (bool, str)) or not np.isscalar(max_slope) or not np.isreal(max_slope):
+            raise NotImplementedError("FluxTapering: max_slope must be a number")
+        if not (math.isfinite(max_slope) and max_slope > 0):
+            raise ValueError("FluxTapering: max_slope must be finite and positive")
+        self.max_slope = float(max_slope)
+
+    def __repr__(self):
+        return f"FluxTapering{{Float64}}({_prettysummary(self.max_slope, compact=False)})"
+
+
+class IsopycnalSkewSymmetricDiffusivity:
+    """IsopycnalSkewSymmetricDiffusivity([time_discretization = VerticallyImplicitTimeDiscretization()]; κ_skew = nothing, κ_symmetric = nothing,
+    skew_flux_formulation = AdvectiveFormulation(), isopycnal_tensor = SmallSlopeIsopycnalTensor(), slope_limiter = FluxTapering(1e-2),
+    required_halo_size = 1) (isopycnal_skew_symmetric_diffusivity.jl:50-71): Gent-McWilliams skew transport with κ_skew and Redi diffusion
+    along isopycnals with κ_symmetric (csrc/isopycnal.hip).  ASCII aliases: kappa_skew, kappa_symmetric.  The coefficients are numbers or None
+    (the reference's nothing); κ_symmetric may be a dict {tracer name: κ}, κ_skew only with the DiffusiveFormulation.  The vertical part
+    of the symmetric flux is stepped implicitly; HydrostaticFreeSurfaceModel only."""
+    PER_TRACER_SKEW = "Only one skew coefficient for all tracers is currently supported with the AdvectiveFormulation."
+    ONLY_SMALL_SLOPE = "Only isopycnal_tensor=SmallSlopeIsopycnalTensor() is currently supported."
+
+    def __init__(self, *args, **kw):
+        if len(args) > 1:
+            raise TypeError("IsopycnalSkewSymmetricDiffusivity takes one positional argument, the time discretization")
+        if args:
+            if "time_discretization" in kw:
+                raise TypeError("time_discretization given twice")
+            kw["time_discretization"] = args[0]
+        self.time_discretization = as_time_discretization(kw.pop("time_discretization", VerticallyImplicitTimeDiscretization()))
+        if not isinstance(self.time_discretization, VerticallyImplicitTimeDiscretization):
+            raise NotImplementedError("IsopycnalSkewSymmetricDiffusivity with the ExplicitTimeDiscretization is not implemented: the reference's own "
+                                      "explicit method cannot be called (the call of explicit_κ_∂z_c in diffusive_flux_z, "
+                                      "isopycnal_skew_symmetric_diffusivity.jl:308, does not match the method at :316); use the default, "
+                                      "VerticallyImplicitTimeDiscretization()")
+        for greek, ascii_name in (("κ_skew", "kappa_skew"), ("κ_symmetric", "kappa_symmetric")):
+            if greek in kw and ascii_name in kw:
+                raise TypeError(f"{greek} given twice")
+        kappa_skew = kw.pop("κ_skew", kw.pop("kappa_skew", None))
+        kappa_symmetric = kw.pop("κ_symmetric", kw.pop("kappa_symmetric", None))
+        formulation = kw.pop("skew_flux_formulation", None)
+        formulation = AdvectiveFormulation() if formulation is None else (formulation() if isinstance(formulation, type) else formulation)
+        if not isinstance(formulation, (AdvectiveFormulation, DiffusiveFormulation)):
+            raise TypeError("skew_flux_formulation must be AdvectiveFormulation() or DiffusiveFormulation()")
+        tensor = kw.pop("isopycnal_tensor", None)
+        tensor = SmallSlopeIsopycnalTensor() if tensor is None else tensor
+        limiter = kw.pop("slope_limiter", None)
+        limiter = FluxTapering(1e-2) if limiter is None else limiter
+        halo = kw.pop("required_halo_size", 1)
+        if kw:
+            raise TypeError(f"unexpected keyword arguments {sorted(kw)}")
+        self.advective = isinstance(formulation, AdvectiveFormulation)
+        if isinstance(kappa_skew, dict) and self.advective:
+            raise ValueError(self.PER_TRACER_SKEW)
+        if type(tensor) is not SmallSlopeIsopycnalTensor:
+            raise NotImplementedError(self.ONLY_SMALL_SLOPE)
+        if not isinstance(limiter, FluxTapering):
+            raise NotImplementedError("IsopycnalSkewSymmetricDiffusivity: slope_limiter must be FluxTapering(max_slope)")
+        if isinstance(halo, bool) or not isinstance(halo, (int, np.integer)) or halo < 1:
+            raise ValueError("required_halo_size must be an integer >= 1")
+
+        def number(x, what):
+            if isinstance(x, (bool, str)) or callable(x) or not np.isscalar(x) or not np.isreal(x):
+                raise NotImplementedError(f"IsopycnalSkewSymmetricDiffusivity: {what} must be a number (functions, arrays and fields are not "
+                                          "implemented)")
+            return float(x)  # convert_diffusivity(FT, κ)
+
+        def coefficient(x, what):
+            if x is None:
+                return None
+            if isinstance(x, dict):
+                return {str(k): number(v, f"{what} of {k}") for k, v in x.items()}
+            return number(x, what)
+        self.kappa_skew = coefficient(kappa_skew, "κ_skew")
+        self.kappa_symmetric = coefficient(kappa_symmetric, "κ_symmetric")
+        self.skew_flux_formulation, self.isopycnal_tensor, self.slope_limiter = formulation, tensor, limiter
+        self.required_halo_size = int(halo)
+
+    κ_skew = property(lambda self: self.kappa_skew)
+    κ_symmetric = property(lambda self: self.kappa_symmetric)
+
+    @staticmethod
+    def _of(kappa, name):
+        """get_tracer_κ (:220-222): nothing is 0"""
+        if kappa is None:
+            return 0.0
+        if isinstance(kappa, dict):
+            if name not in kappa:
+                raise ValueError(f"no diffusivity κ given for tracer {name}")
+            return kappa[name]
+        return kappa
+
+    def kappa_symmetric_of(self, name):
+        return self._of(self.kappa_symmetric, name)
+
+    def kappa_skew_of(self, name):
+        """the skew coefficient inside the diffusive fluxes: 0 with the AdvectiveFormulation (skew_diffusivity, :225-226)"""
+        return 0.0 if self.advective else self._of(self.kappa_skew, name)
+
+    def c_struct(self):
+        """struct ocn_isopycnal"""
+        return _lib.CIsopycnal(self.slope_limiter.max_slope, self.isopycnal_tensor.minimum_bz)
+
+    @staticmethod
+    def _shown(kappa, pretty):
+        if kappa is None:
+            return "Nothing" if pretty else "nothing"
+        if isinstance(kappa, dict):
+            sep = "=" if pretty else " = "
+            items = [f"{k}{sep}{_prettysummary(v, compact=pretty)}" for k, v in kappa.items()]
+            return "(" + ", ".join(items) + ("," if len(items) == 1 else "") + ")" if items else "NamedTuple()"
+        return _prettysummary(kappa, compact=pretty)
+
+    def summary(self):  # Base.summary (:350-353)
+        return f"IsopycnalSkewSymmetricDiffusivity(κ_skew={self._shown(self.kappa_skew, True)}, κ_symmetric={self._shown(self.kappa_symmetric, True)})"
+
+    def __repr__(self):  # Base.show (:355-358)
+        return (f"IsopycnalSkewSymmetricDiffusivity: (κ_symmetric={self._shown(self.kappa_symmetric, False)}, "
+                f"κ_skew={self._shown(self.kappa_skew, False)}, (isopycnal_tensor={self.isopycnal_tensor!r}, slope_limiter={self.slope_limiter!r})")
 
 
 class ThreeDimensionalFormulation:
