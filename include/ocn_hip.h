@@ -1210,6 +1210,50 @@ int ocn_op_reduce_workspace(const ocn_grid *grid, int32_t loc, int32_t dims, int
 int ocn_op_reduce(const ocn_grid *grid, const ocn_op_program *program, int32_t dims, double divisor, double *workspace,
                   int64_t workspace_doubles, double *out, void *stream);
 
+/* ---- ImmersedBoundaryGrid(grid, GridFittedBottom(h)): bathymetry under the HydrostaticFreeSurfaceModel --------------------------------------
+ * (Periodic, Periodic, Bounded) underlying grid, regular x and y, halo >= 1 in every direction, one GPU; strict arithmetic only.  The
+ * bathymetry is ONE int32 plane `kbot`, shaped like eta ((Nx + 2 Hx) x (Ny + 2 Hy), x fastest) with periodically filled halos: the number of
+ * immersed cells of the column; cell k is immersed iff k <= kbot.  Every node predicate of the reference (inactive_node, peripheral_node and
+ * their immersed_ variants, Grids/inactive_node.jl:127-155) is a comparison of k with the minimum or maximum of kbot over the columns the
+ * node touches.  Every entry point runs over 1:Nx, 1:Ny(, 1:Nz) and needs filled halos of what it reads. */
+/* materialize_immersed_boundary (grid_fitted_bottom.jl:99-122): from the bottom height h (a plane like eta, interior read), the z of the Nz
+ * cell centres and of the Nz + 1 faces (device vectors), the materialized bottom height, kbot and the static column depths
+ * Hcc = z_top - bottom, Hfc / Hcf = the minimum over the two columns of the face (:147-150); halos included.
+ * interface_condition 0: CenterImmersedCondition (z_centre <= h), 1: InterfaceImmersedCondition (z_face(k+1) <= h). */
+int ocn_immersed_compute_bottom(const ocn_grid *grid, int32_t interface_condition, const double *h, const double *z_centers,
+                                const double *z_faces, double *bottom_height, int32_t *kbot, double *Hcc, double *Hfc, double *Hcf,
+                                void *stream);
+/* mask_immersed_field! (mask_immersed_field.jl:53-105) in one launch: fields[f] = value on the immersed_peripheral_node of locs[f], for
+ * n <= 8 fields, and on the planes eta (Center, Center, Face at k = Nz + 1), U (Face, Center at k = Nz), V (Center, Face at k = Nz); a
+ * NULL plane is skipped, n may be 0.  Only masked nodes are written. */
+int ocn_immersed_mask_fields(const ocn_grid *grid, const int32_t *kbot, int32_t n, double *const *fields, const int32_t *locs, double value,
+                             double *eta, double *U, double *V, void *stream);
+/* ocn_compute_vector_invariant_momentum_tendencies with the conditional differences (conditional_differences.jl:25-77) in the vorticity,
+ * in dz u / dz v of the vertical advection and in the gradient of the kinetic energy; eta as there (never zeroed: it is taken at k = Nz + 1). */
+int ocn_immersed_vector_invariant_momentum_tendencies(const ocn_grid *grid, const int32_t *kbot, const double *u, const double *v,
+                                                      const double *w, double *Gu, double *Gv, const double *eta,
+                                                      double gravitational_acceleration, void *stream);
+/* Gu -= d_j tau_1j, Gv -= d_j tau_2j of an explicit ScalarDiffusivity(nu), the stresses 0 on the immersed periphery of their locations
+ * (immersed_diffusive_fluxes.jl:27-34) and the differences inside them conditional. */
+int ocn_immersed_add_viscous_terms(const ocn_grid *grid, const int32_t *kbot, double nu, const double *u, const double *v, const double *w,
+                                   double *Gu, double *Gv, void *stream);
+/* Gc = - div(U c) [Centered(order = 2)] - div q [closure = 1: ScalarDiffusivity(kappa)], the advective and diffusive fluxes 0 on the immersed
+ * periphery of their faces (immersed_advective_fluxes.jl:57-59, immersed_diffusive_fluxes.jl:42-44). */
+int ocn_immersed_tracer_tendency(const ocn_grid *grid, const int32_t *kbot, int32_t closure, double kappa, const double *u, const double *v,
+                                 const double *w, const double *c, double *Gc, void *stream);
+/* ocn_split_explicit_forcing with ab2_step_G = 0 on a peripheral node (compute_slow_tendencies.jl:30-42) */
+int ocn_immersed_split_explicit_forcing(const ocn_grid *grid, const int32_t *kbot, const double *Gu, const double *Gu_previous,
+                                        const double *Gv, const double *Gv_previous, double chi, double *GU, double *GV, void *stream);
+/* ocn_split_explicit_substeps with the transports through conditional_U_fcc / V_cfc, the gradients of eta 0 next to a dry column
+ * (conditional_differences.jl:83-92) and the column depths Hfc, Hcf instead of one number */
+int ocn_immersed_split_explicit_substeps(const ocn_grid *grid, const int32_t *kbot, const double *Hfc, const double *Hcf, int32_t n,
+                                         const double *weights, double dtau, double gravitational_acceleration, double *eta, double *U,
+                                         double *V, double *eta_filtered, double *U_filtered, double *V_filtered, const double *GU,
+                                         const double *GV, void *stream);
+/* ocn_barotropic_split_explicit_corrector dividing by Hfc, Hcf; on a dry face that is 0 / 0, as in the reference: the next mask removes it */
+int ocn_immersed_barotropic_corrector(const ocn_grid *grid, const double *Hfc, const double *Hcf, double *u, double *v, const double *U,
+                                      const double *V, double *U_filtered, double *V_filtered, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

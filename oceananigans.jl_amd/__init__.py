@@ -12,8 +12,11 @@ from .advection import WENO, UpwindBiased
 from .architectures import CPU, GPU, on_architecture, sync_device, zeros
 from .distributed import (Distributed, DistributedFFTBasedPoissonSolver, DistributedFourierTridiagonalPoissonSolver, Partition,
                           TorchDistributedFabric)
-from .fields import CenterField, Field, XFaceField, YFaceField, ZFaceField, fill_halo_regions
+from .fields import CenterField, Field, XFaceField, YFaceField, ZFaceField, fill_halo_regions, mask_immersed_field
 from .grids import Bounded, Center, Face, Flat, FullyConnected, LeftConnected, Periodic, RectilinearGrid, RightConnected
+from .grids import (CenterImmersedCondition, GridFittedBottom, GridFittedBoundary, ImmersedBoundaryGrid, InterfaceImmersedCondition,
+                    PartialCellBottom, immersed_cell, immersed_inactive_node, immersed_peripheral_node, inactive_node, peripheral_node,
+                    static_column_depth)
 from .models import (NonhydrostaticModel, QuasiAdamsBashforth2TimeStepper, RungeKutta3TimeStepper, ab2_step,
                      cache_previous_tendencies, calculate_pressure_correction, compute_auxiliaries, compute_diffusivities,
                      compute_tendencies, flush_tendencies, RK3Driver, ModelRK3Driver, implicit_step, add_vertically_implicit_explicit_fluxes,

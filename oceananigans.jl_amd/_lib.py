@@ -344,6 +344,14 @@ _SIGS = {
     "ocn_dist_poisson_exchange": [_vp, _vp, _i32, _vp],
     "ocn_comm_allreduce": [_vp, _vp, C.c_size_t, _i32, _vp],
     "ocn_comm_barrier": [_vp],
+    "ocn_immersed_compute_bottom": [C.POINTER(CGrid), _i32] + [_vp] * 8 + [_vp],
+    "ocn_immersed_mask_fields": [C.POINTER(CGrid), _vp, _i32, C.POINTER(_vp), C.POINTER(_i32), _dbl, _vp, _vp, _vp, _vp],
+    "ocn_immersed_vector_invariant_momentum_tendencies": [C.POINTER(CGrid)] + [_vp] * 7 + [_dbl, _vp],
+    "ocn_immersed_add_viscous_terms": [C.POINTER(CGrid), _vp, _dbl] + [_vp] * 5 + [_vp],
+    "ocn_immersed_tracer_tendency": [C.POINTER(CGrid), _vp, _i32, _dbl] + [_vp] * 5 + [_vp],
+    "ocn_immersed_split_explicit_forcing": [C.POINTER(CGrid)] + [_vp] * 5 + [_dbl, _vp, _vp, _vp],
+    "ocn_immersed_split_explicit_substeps": [C.POINTER(CGrid), _vp, _vp, _vp, _i32, C.POINTER(_dbl), _dbl, _dbl] + [_vp] * 8 + [_vp],
+    "ocn_immersed_barotropic_corrector": [C.POINTER(CGrid)] + [_vp] * 8 + [_vp],
 }
 EXPORTED_SYMBOLS = sorted(list(_SIGS) + ["ocn_last_error", "ocn_version", "ocn_get_math_mode"])
 

@@ -644,6 +644,99 @@ int ocn_explicit_free_surface_ab2_step(const ocn_grid *grid, const double *w, do
     return launch_free_surface_ab2(grid, w, eta, G_eta, G_eta_previous, dt, chi, as_stream(stream));
 }
 
+// ---- ImmersedBoundaryGrid(grid, GridFittedBottom(h)) on a (Periodic, Periodic, Bounded) grid (immersed.hip)
+static int validate_immersed(const ocn_grid *grid, const char *who)
+{
+    int st = validate_hydrostatic(grid, who);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(grid->tx == OCN_PERIODIC, "%s: an immersed grid cannot be partitioned (FullyConnected x)", who);
+    OCN_REQUIRE(grid->Hz >= 1, "%s: needs a z halo", who);
+    return OCN_SUCCESS;
+}
+int ocn_immersed_compute_bottom(const ocn_grid *grid, int32_t interface_condition, const double *h, const double *z_centers,
+                                const double *z_faces, double *bottom_height, int32_t *kbot, double *Hcc, double *Hfc, double *Hcf,
+                                void *stream)
+{
+    int st = validate_immersed(grid, "ocn_immersed_compute_bottom");
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(interface_condition == 0 || interface_condition == 1, "ocn_immersed_compute_bottom: immersed condition %d is neither 0 (Center) nor 1 (Interface)",
+                (int)interface_condition);
+    OCN_REQUIRE(h && z_centers && z_faces && bottom_height && kbot && Hcc && Hfc && Hcf, "ocn_immersed_compute_bottom: null pointer");
+    return launch_immersed_bottom(grid, interface_condition, h, z_centers, z_faces, bottom_height, kbot, Hcc, Hfc, Hcf, as_stream(stream));
+}
+int ocn_immersed_mask_fields(const ocn_grid *grid, const int32_t *kbot, int32_t n, double *const *fields, const int32_t *locs, double value,
+                             double *eta, double *U, double *V, void *stream)
+{
+    int st = validate_immersed(grid, "ocn_immersed_mask_fields");
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(kbot, "ocn_immersed_mask_fields: null kbot");
+    FieldTuple ft;
+    ft.n = 0;
+    if (n != 0) {
+        st = make_field_tuple(grid, fields, locs, n, ft);
+        if (st != OCN_SUCCESS) return st;
+    }
+    OCN_REQUIRE(n != 0 || eta || U || V, "ocn_immersed_mask_fields: nothing to mask");
+    return launch_immersed_mask(grid, kbot, ft, value, eta, U, V, as_stream(stream));
+}
+int ocn_immersed_vector_invariant_momentum_tendencies(const ocn_grid *grid, const int32_t *kbot, const double *u, const double *v,
+                                                      const double *w, double *Gu, double *Gv, const double *eta,
+                                                      double gravitational_acceleration, void *stream)
+{
+    int st = validate_immersed(grid, "ocn_immersed_vector_invariant_momentum_tendencies");
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(kbot && u && v && w && Gu && Gv, "ocn_immersed_vector_invariant_momentum_tendencies: null pointer");
+    return launch_vector_invariant_immersed(grid, kbot, u, v, w, Gu, Gv, eta, gravitational_acceleration, as_stream(stream));
+}
+int ocn_immersed_add_viscous_terms(const ocn_grid *grid, const int32_t *kbot, double nu, const double *u, const double *v, const double *w,
+                                   double *Gu, double *Gv, void *stream)
+{
+    int st = validate_immersed(grid, "ocn_immersed_add_viscous_terms");
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(kbot && u && v && w && Gu && Gv, "ocn_immersed_add_viscous_terms: null pointer");
+    OCN_REQUIRE(std::isfinite(nu) && nu >= 0, "ocn_immersed_add_viscous_terms: nu = %g must be finite and >= 0", nu);
+    return launch_viscosity_immersed(grid, kbot, nu, u, v, w, Gu, Gv, as_stream(stream));
+}
+int ocn_immersed_tracer_tendency(const ocn_grid *grid, const int32_t *kbot, int32_t closure, double kappa, const double *u, const double *v,
+                                 const double *w, const double *c, double *Gc, void *stream)
+{
+    int st = validate_immersed(grid, "ocn_immersed_tracer_tendency");
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(kbot && u && v && w && c && Gc, "ocn_immersed_tracer_tendency: null pointer");
+    OCN_REQUIRE(closure == 0 || closure == 1, "ocn_immersed_tracer_tendency: closure must be 0 (none) or 1 (ScalarDiffusivity), got %d", (int)closure);
+    OCN_REQUIRE(!closure || (std::isfinite(kappa) && kappa >= 0), "ocn_immersed_tracer_tendency: kappa = %g must be finite and >= 0", kappa);
+    return launch_tracer_immersed(grid, kbot, closure, kappa, u, v, w, c, Gc, as_stream(stream));
+}
+int ocn_immersed_split_explicit_forcing(const ocn_grid *grid, const int32_t *kbot, const double *Gu, const double *Gu_previous,
+                                        const double *Gv, const double *Gv_previous, double chi, double *GU, double *GV, void *stream)
+{
+    int st = validate_immersed(grid, "ocn_immersed_split_explicit_forcing");
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(kbot && Gu && Gu_previous && Gv && Gv_previous && GU && GV, "ocn_immersed_split_explicit_forcing: null pointer");
+    return launch_split_explicit_forcing_immersed(grid, kbot, Gu, Gu_previous, Gv, Gv_previous, chi, GU, GV, as_stream(stream));
+}
+int ocn_immersed_split_explicit_substeps(const ocn_grid *grid, const int32_t *kbot, const double *Hfc, const double *Hcf, int32_t n,
+                                         const double *weights, double dtau, double gravitational_acceleration, double *eta, double *U,
+                                         double *V, double *eta_filtered, double *U_filtered, double *V_filtered, const double *GU,
+                                         const double *GV, void *stream)
+{
+    int st = validate_immersed(grid, "ocn_immersed_split_explicit_substeps");
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(n >= 1 && weights, "ocn_immersed_split_explicit_substeps: needs n >= 1 averaging weights (host array)");
+    OCN_REQUIRE(kbot && Hfc && Hcf && eta && U && V && eta_filtered && U_filtered && V_filtered && GU && GV,
+                "ocn_immersed_split_explicit_substeps: null pointer");
+    return launch_split_explicit_substeps_immersed(grid, kbot, Hfc, Hcf, n, weights, dtau, gravitational_acceleration, eta, U, V, eta_filtered,
+                                                   U_filtered, V_filtered, GU, GV, as_stream(stream));
+}
+int ocn_immersed_barotropic_corrector(const ocn_grid *grid, const double *Hfc, const double *Hcf, double *u, double *v, const double *U,
+                                      const double *V, double *U_filtered, double *V_filtered, void *stream)
+{
+    int st = validate_immersed(grid, "ocn_immersed_barotropic_corrector");
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(Hfc && Hcf && u && v && U && V && U_filtered && V_filtered, "ocn_immersed_barotropic_corrector: null pointer");
+    return launch_barotropic_corrector_immersed(grid, Hfc, Hcf, u, v, U, V, U_filtered, V_filtered, as_stream(stream));
+}
+
 static int validate_amd(const ocn_grid *grid)
 {
     int st = validate_grid_any(grid);  // Bounded x / y: the kernel takes per-field parent layouts

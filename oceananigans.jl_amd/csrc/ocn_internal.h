@@ -218,6 +218,24 @@ int launch_split_explicit_substeps_walls(const ocn_grid *grid, int n, const doub
                                          hipStream_t stream);
 int launch_implicit_free_surface_rhs_walls(const ocn_grid *grid, const double *u, const double *v, const double *eta, double grav, double dt,
                                            double *Qu, double *Qv, double *rhs, hipStream_t stream);
+// the hydrostatic kernels on ImmersedBoundaryGrid(grid, GridFittedBottom(h)) (immersed.hip): kbot is the int32 plane of immersed cells per column
+int launch_immersed_bottom(const ocn_grid *grid, int interface_condition, const double *h, const double *zc, const double *zf, double *bottom,
+                           int32_t *kbot, double *Hcc, double *Hfc, double *Hcf, hipStream_t stream);
+int launch_immersed_mask(const ocn_grid *grid, const int32_t *kbot, const FieldTuple &f, double value, double *eta, double *U, double *V,
+                         hipStream_t stream);
+int launch_vector_invariant_immersed(const ocn_grid *grid, const int32_t *kbot, const double *u, const double *v, const double *w, double *Gu,
+                                     double *Gv, const double *eta, double grav, hipStream_t stream);
+int launch_viscosity_immersed(const ocn_grid *grid, const int32_t *kbot, double nu, const double *u, const double *v, const double *w,
+                              double *Gu, double *Gv, hipStream_t stream);
+int launch_tracer_immersed(const ocn_grid *grid, const int32_t *kbot, int diffuse, double kappa, const double *u, const double *v,
+                           const double *w, const double *c, double *Gc, hipStream_t stream);
+int launch_split_explicit_forcing_immersed(const ocn_grid *grid, const int32_t *kbot, const double *Gun, const double *Gum, const double *Gvn,
+                                           const double *Gvm, double chi, double *GU, double *GV, hipStream_t stream);
+int launch_split_explicit_substeps_immersed(const ocn_grid *grid, const int32_t *kbot, const double *Hfc, const double *Hcf, int n,
+                                            const double *weights, double dtau, double grav, double *eta, double *U, double *V, double *etab,
+                                            double *Ub, double *Vb, const double *GU, const double *GV, hipStream_t stream);
+int launch_barotropic_corrector_immersed(const ocn_grid *grid, const double *Hfc, const double *Hcf, double *u, double *v, const double *U,
+                                         const double *V, double *Ub, double *Vb, hipStream_t stream);
 int launch_halo_plane_x(const ocn_grid *grid, double *field, int loc, int which, double *buf, int unpack, hipStream_t stream);
 int launch_halo_pack_x_fields(const ocn_grid *grid, const FieldTuple &ft, double *west, double *east, int unpack, hipStream_t stream);
 int launch_rowdct(int Nx, int Ny, int Nz, RowDCT mode, double *data, const double *tw, const double *wd, const double *lx, const double *ly,

@@ -170,3 +170,14 @@ def fill_halo_regions(fields, fill_boundary_normal_velocities=True, **_):
     if hook is not None:  # Distributed: local fills + x-halo exchange (distributed.py)
         return hook(fields, fill_boundary_normal_velocities)
     local_fill_halo_regions(grid, fields, fill_boundary_normal_velocities)
+
+
+def mask_immersed_field(field, value=0.0):
+    """mask_immersed_field!(field, value = 0) (ImmersedBoundaries/mask_immersed_field.jl:24-64): `value` wherever the field's node is an
+    immersed_peripheral_node (a velocity face next to an immersed cell, a tracer cell inside the bottom); nothing on a plain grid."""
+    grid = field.grid
+    if not hasattr(grid, "immersed_boundary"):
+        return field
+    _lib.call("ocn_immersed_mask_fields", grid.cref, grid.plane_ptr("kbot"), 1, _lib.ptr_array([field.ptr]), _lib.i32_array([field.loc]),
+              float(value), None, None, None, stream_ptr())
+    return field

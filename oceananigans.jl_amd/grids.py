@@ -362,3 +362,229 @@ class RectilinearGrid:
     def __repr__(self):
         return (f"{self.Nx}x{self.Ny}x{self.Nz} RectilinearGrid on {self.architecture} with "
                 f"{self.Hx}x{self.Hy}x{self.Hz} halo, topology {self.topology}")
+
+
+# ---- ImmersedBoundaryGrid(grid, GridFittedBottom(h)) (src/ImmersedBoundaries) -----------------------------------------------------------
+class CenterImmersedCondition:
+    """CenterImmersedCondition() (grid_fitted_bottom.jl:12): a cell is immersed when its centre lies at or below the bottom height"""
+
+    def __repr__(self):
+        return "CenterImmersedCondition()"
+
+
+class InterfaceImmersedCondition:
+    """InterfaceImmersedCondition() (grid_fitted_bottom.jl:13): a cell is immersed when its upper interface lies at or below the bottom height"""
+
+    def __repr__(self):
+        return "InterfaceImmersedCondition()"
+
+
+class GridFittedBottom:
+    """GridFittedBottom(bottom_height, immersed_condition = CenterImmersedCondition()) (grid_fitted_bottom.jl:15-46).  bottom_height: a
+    number, an (Nx, Ny) array or a function f(x, y) of the cell-centre coordinates.  On an ImmersedBoundaryGrid, `bottom_height` is the
+    materialized (Nx, Ny) array: the z of the upper interface of the highest immersed cell of every column (the domain's bottom where
+    there is none)."""
+
+    def __init__(self, bottom_height, immersed_condition=None):
+        immersed_condition = CenterImmersedCondition() if immersed_condition is None else immersed_condition
+        if isinstance(immersed_condition, type):
+            immersed_condition = immersed_condition()
+        if not isinstance(immersed_condition, (CenterImmersedCondition, InterfaceImmersedCondition)):
+            raise TypeError("immersed_condition must be CenterImmersedCondition() or InterfaceImmersedCondition()")
+        self.bottom_height = bottom_height
+        self.immersed_condition = immersed_condition
+
+    def __repr__(self):
+        return f"GridFittedBottom({self.immersed_condition!r})"
+
+
+class PartialCellBottom:
+    """PartialCellBottom(bottom_height; minimum_fractional_cell_height = 0.2) (partial_cell_bottom.jl): constructible; an
+    ImmersedBoundaryGrid with it is not implemented."""
+
+    def __init__(self, bottom_height, minimum_fractional_cell_height=0.2):
+        self.bottom_height, self.minimum_fractional_cell_height = bottom_height, float(minimum_fractional_cell_height)
+
+
+class GridFittedBoundary:
+    """GridFittedBoundary(mask) (grid_fitted_boundary.jl): constructible; an ImmersedBoundaryGrid with it is not implemented."""
+
+    def __init__(self, mask):
+        self.mask = mask
+
+
+def materialize_bottom_height(grid, ib):
+    """materialize_immersed_boundary (grid_fitted_bottom.jl:99-122) on the host: (the materialized (Nx, Ny) bottom height, kbot).  The
+    height starts at face 1 and is raised to face k + 1 for every k whose centre (CenterImmersedCondition) or upper interface
+    (InterfaceImmersedCondition) lies at or below h; kbot counts the cells whose centre lies at or below the result (immersed_cell,
+    :124-130)."""
+    Nx, Ny, Nz = grid.Nx, grid.Ny, grid.Nz
+    h = ib.bottom_height
+    if callable(h):  # set!(bottom_field, f): f(x, y) at the (Center, Center) nodes
+        x, y = grid.nodes_1d(0, False).reshape(-1, 1), grid.nodes_1d(1, False).reshape(1, -1)
+        try:
+            a = np.asarray(h(x, y), dtype=np.float64)
+        except (TypeError, ValueError):
+            a = np.vectorize(h, otypes=[np.float64])(x, y)
+        h = np.broadcast_to(a, (Nx, Ny))
+    elif np.ndim(h) == 0:
+        h = np.full((Nx, Ny), float(h))
+    else:
+        h = np.asarray(h, dtype=np.float64)
+        if h.shape != (Nx, Ny):
+            raise ValueError(f"bottom_height has shape {h.shape}; the grid needs ({Nx}, {Ny})")
+    h = np.array(h, dtype=np.float64)
+    zc, zf = grid.nodes_1d(2, False), grid.nodes_1d(2, True)
+    interface = isinstance(ib.immersed_condition, InterfaceImmersedCondition)
+    bottom = np.full((Nx, Ny), zf[0])
+    for k in range(Nz):
+        bottom_cell = (zf[k + 1] <= h) if interface else (zc[k] <= h)
+        bottom = np.where(bottom_cell, zf[k + 1], bottom)
+    kbot = (zc[None, None, :] <= bottom[:, :, None]).sum(axis=2).astype(np.int32)
+    return h, bottom, kbot
+
+
+class ImmersedBoundaryGrid:
+    """ImmersedBoundaryGrid(grid, GridFittedBottom(h)) (immersed_boundary_grid.jl:17-67): `grid` with the cells below the bottom height
+    taken out of the fluid.  Every property of the underlying grid is a property of this one (Base.getproperty, :80-85).
+
+    Implemented: a (Periodic, Periodic, Bounded) underlying RectilinearGrid on one GPU with GridFittedBottom; HydrostaticFreeSurfaceModel
+    steps on it (hydrostatic.py).  The bathymetry is held as `kbot`, the number of immersed cells per column: cell (i, j, k) is immersed
+    iff k <= kbot[i, j]."""
+
+    def __init__(self, grid, immersed_boundary, active_cells_map=False, active_z_columns=False):
+        who = "ImmersedBoundaryGrid"
+        if isinstance(grid, ImmersedBoundaryGrid):
+            raise TypeError(f"{who}: the underlying grid is itself an ImmersedBoundaryGrid")
+        if isinstance(immersed_boundary, PartialCellBottom):
+            raise NotImplementedError(f"{who}: PartialCellBottom is not implemented; use GridFittedBottom(h)")
+        if isinstance(immersed_boundary, GridFittedBoundary):
+            raise NotImplementedError(f"{who}: GridFittedBoundary is not implemented; use GridFittedBottom(h)")
+        if not isinstance(immersed_boundary, GridFittedBottom):
+            raise TypeError(f"{who}: immersed_boundary must be GridFittedBottom(h)")
+        if active_cells_map or active_z_columns:
+            raise NotImplementedError(f"{who}: active_cells_map = true is not implemented; the kernels keep the whole extent in the launch "
+                                      "(leave it at false)")
+        if hasattr(grid.architecture, "partition"):
+            raise NotImplementedError(f"{who}: Distributed grids are not implemented; build the grid on one GPU")
+        if tuple(grid.topology) != (Periodic, Periodic, Bounded):
+            raise NotImplementedError(f"{who}: the underlying grid must be (Periodic, Periodic, Bounded); walls or a Flat direction in it are "
+                                      f"not implemented (got {tuple(grid.topology)})")
+        require_regular_xy(grid, who)
+        self.underlying_grid = grid
+        h, bottom, kbot = materialize_bottom_height(grid, immersed_boundary)
+        self.immersed_boundary = GridFittedBottom(bottom, immersed_boundary.immersed_condition)
+        self.kbot = kbot
+        self._kbot_halo = np.pad(kbot, ((grid.Hx, grid.Hx), (grid.Hy, grid.Hy)), mode="wrap")
+        top = grid.nodes_1d(2, True)[grid.Nz]
+        Hcc = np.pad(top - bottom, ((1, 0), (1, 0)), mode="wrap")
+        self._depth = {"cc": Hcc[1:, 1:], "fc": np.minimum(Hcc[:-1, 1:], Hcc[1:, 1:]), "cf": np.minimum(Hcc[1:, :-1], Hcc[1:, 1:])}
+        self._planes = None
+        if grid.architecture is not None:
+            self._materialize_on_device(h)
+
+    def _materialize_on_device(self, h):
+        """the planes the kernels read, by ocn_immersed_compute_bottom: bottom height, kbot (int32), Hᶜᶜ, Hᶠᶜ, Hᶜᶠ, shaped like η with halos"""
+        from .architectures import on_architecture, stream_ptr
+        g = self.underlying_grid
+        dev = device(child_architecture(g.architecture))
+        shape = (g.Ny + 2 * g.Hy, g.Nx + 2 * g.Hx)
+        hp = torch.zeros(shape, dtype=torch.float64, device=dev)
+        hp[g.Hy:g.Hy + g.Ny, g.Hx:g.Hx + g.Nx] = on_architecture(g.architecture, np.ascontiguousarray(h.T))
+        zc = on_architecture(g.architecture, np.ascontiguousarray(g.nodes_1d(2, False)))
+        zf = on_architecture(g.architecture, np.ascontiguousarray(g.nodes_1d(2, True)))
+        P = {n: torch.zeros(shape, dtype=torch.float64, device=dev) for n in ("bottom", "Hcc", "Hfc", "Hcf")}
+        P["kbot"] = torch.zeros(shape, dtype=torch.int32, device=dev)
+        interface = int(isinstance(self.immersed_boundary.immersed_condition, InterfaceImmersedCondition))
+        _lib.call("ocn_immersed_compute_bottom", g.cref, interface, hp.data_ptr(), zc.data_ptr(), zf.data_ptr(), P["bottom"].data_ptr(),
+                  P["kbot"].data_ptr(), P["Hcc"].data_ptr(), P["Hfc"].data_ptr(), P["Hcf"].data_ptr(), stream_ptr())
+        self._planes = P
+
+    def __getattr__(self, name):
+        if name in ("underlying_grid", "__setstate__", "__deepcopy__"):
+            raise AttributeError(name)
+        return getattr(self.underlying_grid, name)
+
+    def plane_ptr(self, name):
+        """device pointer of the plane "kbot", "bottom", "Hcc", "Hfc" or "Hcf" """
+        if self._planes is None:
+            raise RuntimeError("this ImmersedBoundaryGrid holds metadata only (architecture = None)")
+        return self._planes[name].data_ptr()
+
+    def with_halo(self, new_halo):
+        """with_halo(halo, ibg) (immersed_boundary_grid.jl:69-76): the underlying grid rebuilt with the new halo, the materialized boundary
+        carried along and materialized again on it"""
+        return ImmersedBoundaryGrid(self.underlying_grid.with_halo(new_halo), self.immersed_boundary)
+
+    def with_math_mode(self, mode):
+        import copy
+        g = copy.copy(self)
+        g.underlying_grid = self.underlying_grid.with_math_mode(mode)
+        return g
+
+    def __repr__(self):
+        return (f"{self.Nx}x{self.Ny}x{self.Nz} ImmersedBoundaryGrid on {self.architecture} with {self.Hx}x{self.Hy}x{self.Hz} halo, "
+                f"{self.immersed_boundary!r}")
+
+
+def _require_immersed(grid, who):
+    if not isinstance(grid, ImmersedBoundaryGrid):
+        raise TypeError(f"{who} needs an ImmersedBoundaryGrid")
+
+
+def immersed_cell(grid):
+    """immersed_cell(i, j, k, ibg) (grid_fitted_bottom.jl:124-130) as a boolean (Nx, Ny, Nz) array"""
+    _require_immersed(grid, "immersed_cell")
+    return np.arange(1, grid.Nz + 1)[None, None, :] <= grid.kbot[:, :, None]
+
+
+def static_column_depth(grid, location="cc"):
+    """static_column_depthᶜᶜᵃ / ᶠᶜᵃ / ᶜᶠᵃ (grid_fitted_bottom.jl:147-150) as an (Nx, Ny) array: z_top - bottom_height at "cc", the minimum
+    over the two columns of the face at "fc" and "cf" """
+    _require_immersed(grid, "static_column_depth")
+    if location not in ("cc", "fc", "cf"):
+        raise ValueError('location must be "cc", "fc" or "cf"')
+    return grid._depth[location].copy()
+
+
+def _node_predicate(grid, loc, kbot_halo, any_cell):
+    """inactive_node (any_cell = False: AND over the cells the node touches) or peripheral_node (True: OR) at location `loc` (bit 0 / 1 /
+    2: Face in x / y / z) for i = 1..Nx, j = 1..Ny, k = 1..Nz (+ 1 at a z Face), on a grid whose columns hold kbot_halo immersed cells.
+    inactive_cell (immersed, or outside 1..Nz) is monotone in kbot, so the AND is the predicate at the minimum of kbot over the columns
+    and the OR the one at the maximum (Grids/inactive_node.jl:127-155)."""
+    Nx, Ny, Nz, Hx, Hy = grid.Nx, grid.Ny, grid.Nz, grid.Hx, grid.Hy
+    pick = np.maximum if any_cell else np.minimum
+    m = kbot_halo[Hx:Hx + Nx, Hy:Hy + Ny]
+    if loc & 1:
+        m = pick(m, kbot_halo[Hx - 1:Hx + Nx - 1, Hy:Hy + Ny])
+    if loc & 2:
+        m = pick(m, kbot_halo[Hx:Hx + Nx, Hy - 1:Hy + Ny - 1])
+        if loc & 1:
+            m = pick(m, pick(kbot_halo[Hx - 1:Hx + Nx - 1, Hy - 1:Hy + Ny - 1], kbot_halo[Hx - 1:Hx + Nx - 1, Hy:Hy + Ny]))
+    k = np.arange(1, Nz + (2 if loc & 4 else 1))[None, None, :]
+    cell = lambda kk: (kk < 1) | (kk > Nz) | (kk <= m[:, :, None])
+    if not loc & 4:
+        return cell(k)
+    return (cell(k - 1) | cell(k)) if any_cell else (cell(k - 1) & cell(k))
+
+
+def inactive_node(grid, loc):
+    """inactive_node(i, j, k, grid, LX, LY, LZ) as a boolean array (see _node_predicate for the index ranges)"""
+    _require_immersed(grid, "inactive_node")
+    return _node_predicate(grid, loc, grid._kbot_halo, False)
+
+
+def peripheral_node(grid, loc):
+    _require_immersed(grid, "peripheral_node")
+    return _node_predicate(grid, loc, grid._kbot_halo, True)
+
+
+def immersed_inactive_node(grid, loc):
+    """inactive_node(ibg) & !inactive_node(underlying grid) (immersed_boundary_interface.jl:53-60)"""
+    _require_immersed(grid, "immersed_inactive_node")
+    return _node_predicate(grid, loc, grid._kbot_halo, False) & ~_node_predicate(grid, loc, np.zeros_like(grid._kbot_halo), False)
+
+
+def immersed_peripheral_node(grid, loc):
+    _require_immersed(grid, "immersed_peripheral_node")
+    return _node_predicate(grid, loc, grid._kbot_halo, True) & ~_node_predicate(grid, loc, np.zeros_like(grid._kbot_halo), True)

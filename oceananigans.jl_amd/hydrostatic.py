@@ -1,7 +1,8 @@
 """First slice of the reference's HydrostaticFreeSurfaceModel on the HIP backend: ExplicitFreeSurface,
 flux-form momentum advection, QuasiAdamsBashforth2, static (Periodic, Periodic, Bounded) RectilinearGrid, one GPU.  (Periodic, Bounded, Bounded)
 channels and (Bounded, Bounded, Bounded) basins run the reference's launch sequence on the kernels of csrc/hydrostatic_walls.hip (what they
-take and refuse: `_refuse_on_walls`).
+take and refuse: `_refuse_on_walls`).  On ImmersedBoundaryGrid(grid, GridFittedBottom(h)) the model steps over a stepped bottom with
+the kernels of csrc/immersed.hip, again in the reference's launch sequence (`_refuse_on_immersed`).
 
     src/Models/HydrostaticFreeSurfaceModels/hydrostatic_free_surface_model.jl (constructor), explicit_free_surface.jl,
     compute_w_from_continuity.jl, hydrostatic_free_surface_tendency_kernel_functions.jl:29-97,
@@ -25,7 +26,7 @@ from . import _lib
 from .advection import WENO, UpwindBiased
 from .architectures import stream_ptr
 from .fields import fill_halo_regions
-from .grids import Bounded, Flat, FullyConnected, Periodic, RectilinearGrid, require_regular_xy
+from .grids import Bounded, Flat, FullyConnected, ImmersedBoundaryGrid, Periodic, RectilinearGrid, require_regular_xy
 from .hydrostatic_closures import resolve_closure
 from .models import (NonhydrostaticModel, _bcs_ref, compute_boundary_tendency_contributions, fused_tracer_launches, update_boundary_conditions,
                      update_hydrostatic_pressure)
@@ -379,6 +380,12 @@ class HydrostaticFreeSurfaceModel:
                                       "slab-partitioned in x)")
         if self._walls:
             fused = self._refuse_on_walls(grid, momentum_advection, free_surface, closure, fused)
+        # a stepped bottom: masks, conditional differences and fluxes, column depths: csrc/immersed.hip
+        self._immersed = isinstance(grid, ImmersedBoundaryGrid)
+        if self._immersed:
+            fused = self._refuse_on_immersed(grid, momentum_advection, tracer_advection, free_surface, closure, fused)
+            if free_surface is None:  # default_free_surface(grid) (hydrostatic_free_surface_model.jl:54-55): not the implicit one
+                free_surface = SplitExplicitFreeSurface(grid, cfl=0.7)
         if free_surface is None:
             free_surface = ImplicitFreeSurface()  # default_free_surface(grid::XYRegularRG) (hydrostatic_free_surface_model.jl:51-52)
         if not isinstance(free_surface, (ExplicitFreeSurface, SplitExplicitFreeSurface, ImplicitFreeSurface)):
@@ -418,7 +425,7 @@ class HydrostaticFreeSurfaceModel:
         self._nh = NonhydrostaticModel(grid, advection=container_advection, tracers=tracers, timestepper="QuasiAdamsBashforth2",
                                        closure=self._closure.container_closure, buoyancy=buoyancy, coriolis=coriolis,
                                        boundary_conditions=boundary_conditions, pressure_solver=None, math_mode=math_mode,
-                                       _closure_halo=self._required_halo())
+                                       _closure_halo=self._required_halo(), _hydrostatic_container=True)
         nh = self._nh
         grid = nh.grid  # (halo-inflated / math-mode-pinned by the container model)
         self.diffusivity_fields = self._closure.allocate(nh)
@@ -494,6 +501,32 @@ class HydrostaticFreeSurfaceModel:
                                       "the other closures (vertically implicit, convective adjustment, Ri-based, biharmonic) wrap x and y")
         return False
 
+    def _refuse_on_immersed(self, grid, momentum_advection, tracer_advection, free_surface, closure, fused):
+        """what an ImmersedBoundaryGrid does not take: raised before anything is allocated.  Returns `fused` (False: the
+        reference's launch sequence is the one implemented there)."""
+        from .physics import ScalarDiffusivity, is_vertically_implicit
+        who = "HydrostaticFreeSurfaceModel on an ImmersedBoundaryGrid"
+        if fused:
+            raise NotImplementedError(f"{who}: fused = True is not implemented; the fused kernels know no bathymetry (leave fused at its default, False)")
+        if self.split_rk3:
+            raise NotImplementedError(f"{who}: SplitRungeKutta3 is not implemented; use QuasiAdamsBashforth2")
+        if isinstance(free_surface, ImplicitFreeSurface):
+            raise NotImplementedError(f"{who}: ImplicitFreeSurface is not implemented (its FFT solver needs a constant depth); use "
+                                      "SplitExplicitFreeSurface(...) or ExplicitFreeSurface()")
+        if isinstance(free_surface, SplitExplicitFreeSurface) and isinstance(free_surface.timestepper, AdamsBashforth3Scheme):
+            raise NotImplementedError(f"{who}: the AdamsBashforth3Scheme substepping is not implemented; use the ForwardBackwardScheme")
+        if momentum_advection is not None and not (isinstance(momentum_advection, VectorInvariant) and not momentum_advection.upwinds):
+            raise NotImplementedError(f"{who}: momentum_advection = {momentum_advection!r} is not implemented: WENO, UpwindBiased and "
+                                      "WENOVectorInvariant reduce their order next to the bottom (immersed_advective_fluxes.jl:154-218); "
+                                      "use VectorInvariant()")
+        if tracer_advection is not None and not (isinstance(tracer_advection, Centered) and tracer_advection.buffer == 1):
+            raise NotImplementedError(f"{who}: tracer_advection = {tracer_advection!r} is not implemented: schemes with a buffer wider than 1 "
+                                      "reduce their order next to the bottom; use Centered()")
+        if closure is not None and not (isinstance(closure, ScalarDiffusivity) and not is_vertically_implicit(closure)):
+            raise NotImplementedError(f"{who}: closure must be None or an explicit constant ScalarDiffusivity; the kernels and column solvers "
+                                      "of the other closures know no bathymetry")
+        return False
+
     def _plane(self, like=None):
         """a zeroed 2-D plane [y, x] with halos, with the x / y extents of the field `like` (U like u, V like v) or of a centre field (η)"""
         sz, sy, sx = (self.w if like is None else like).data.shape
@@ -519,6 +552,8 @@ class HydrostaticFreeSurfaceModel:
     # ---- update_state! (update_hydrostatic_free_surface_model_state.jl:35-53, 74-96) -------------------------------------
     def update_state(self, compute_tendencies=True):
         nh, g = self._nh, self.grid
+        if self._immersed:  # mask_immersed_model_fields! comes first (update_hydrostatic_free_surface_model_state.jl:32-72)
+            self._mask_immersed()
         update_boundary_conditions(nh)
         # tupled_fill_halo_regions!(prognostic_fields(model), ...) keeps the default fill_boundary_normal_velocities = true
         # (update_hydrostatic_free_surface_model_state.jl:42, fill_halo_regions.jl:50-56): on a grid with walls the wall faces of the
@@ -539,10 +574,46 @@ class HydrostaticFreeSurfaceModel:
         if not self._tendencies_current:
             self.compute_tendencies()
 
+    def _mask_immersed(self, velocities_only=False):
+        """mask_immersed_field! of u, v alone (step_free_surface!, step_split_explicit_free_surface.jl:169-170) or of every prognostic field:
+        u, v, the tracers, U, V of the split-explicit surface and η in the plane k = Nz + 1 (mask_immersed_model_fields!); one launch"""
+        g = self.grid
+        fields = [self.u, self.v] + ([] if velocities_only else list(self.tracers))
+        planes = [None, None, None]
+        if not velocities_only:
+            planes = [self.eta.data_ptr()] + ([self.U.data_ptr(), self.V.data_ptr()] if self.split else [None, None])
+        for q in range(0, len(fields), 8):
+            part = fields[q:q + 8]
+            _lib.call("ocn_immersed_mask_fields", g.cref, g.plane_ptr("kbot"), len(part), _lib.ptr_array([f.ptr for f in part]),
+                      _lib.i32_array([f.loc for f in part]), 0.0, *(planes if q == 0 else [None] * 3), stream_ptr())
+
+    def _compute_tendencies_immersed(self, boundary_contributions):
+        """compute_tendencies! on an ImmersedBoundaryGrid.  The Coriolis term (interpolations only) and ∂x pHY′, ∂y pHY′ keep the plain
+        launch: the conditional difference zeroes the pressure gradient only on a peripheral face, whose tendency reaches nothing that
+        survives the next mask.  Everything else is csrc/immersed.hip."""
+        nh, g, s = self._nh, self.grid, stream_ptr()
+        Gn = nh.timestepper._Gn
+        kbot = g.plane_ptr("kbot")
+        eta_ptr = None if self.split else self.eta.data_ptr()
+        _lib.call("ocn_immersed_vector_invariant_momentum_tendencies", g.cref, kbot, self.u.ptr, self.v.ptr, self.w.ptr, Gn[0].ptr, Gn[1].ptr,
+                  eta_ptr, self.free_surface.gravitational_acceleration, s)
+        terms = _lib.CModelTerms.from_buffer_copy(nh._terms)
+        closure, terms.closure = terms.closure, 0
+        _lib.call("ocn_add_momentum_terms", g.cref, C.byref(terms), self.u.ptr, self.v.ptr, self.w.ptr, Gn[0].ptr, Gn[1].ptr, Gn[2].ptr, None, s)
+        if closure:
+            _lib.call("ocn_immersed_add_viscous_terms", g.cref, kbot, float(terms.nu), self.u.ptr, self.v.ptr, self.w.ptr, Gn[0].ptr, Gn[1].ptr, s)
+        for name, c, G in zip(self.tracer_names, self.tracers, Gn[3:]):
+            _lib.call("ocn_immersed_tracer_tendency", g.cref, kbot, int(bool(closure)), float(self._closure.tracer_kappa(name)) if closure else 0.0,
+                      self.u.ptr, self.v.ptr, self.w.ptr, c.ptr, G.ptr, s)
+        if boundary_contributions:
+            compute_boundary_tendency_contributions(nh)
+
     def compute_tendencies(self, boundary_contributions=True):
         """boundary_contributions = False: the interior contributions alone (models.compute_tendencies_ takes the same switch)"""
         nh, g, s = self._nh, self.grid, stream_ptr()
         self._tendencies_current = True
+        if self._immersed:
+            return self._compute_tendencies_immersed(boundary_contributions)
         Gn = nh.timestepper._Gn
         grav = self.free_surface.gravitational_acceleration
         # explicit_barotropic_pressure_x/y_gradient: g ∇η for the ExplicitFreeSurface, zero for the split-explicit one
@@ -662,12 +733,21 @@ class HydrostaticFreeSurfaceModel:
         fs = self.free_surface
         if self.split:
             # compute_free_surface_tendency! (slow forcing from Gⁿ, G⁻ BEFORE they are cached), then step_free_surface!
-            _lib.call("ocn_split_explicit_forcing", g.cref, Gn[0].ptr, Gm[0].ptr, Gn[1].ptr, Gm[1].ptr, float(chi), self._GU.data_ptr(),
-                      self._GV.data_ptr(), s)
-            self._substep_free_surface(dt, s)
-            # pressure_correct_velocities!: the barotropic corrector
-            _lib.call("ocn_barotropic_split_explicit_corrector", g.cref, self.u.ptr, self.v.ptr, self.U.data_ptr(), self.V.data_ptr(),
-                      self._Ub.data_ptr(), self._Vb.data_ptr(), float(g.Lz), s)
+            if self._immersed:
+                _lib.call("ocn_immersed_split_explicit_forcing", g.cref, g.plane_ptr("kbot"), Gn[0].ptr, Gm[0].ptr, Gn[1].ptr, Gm[1].ptr,
+                          float(chi), self._GU.data_ptr(), self._GV.data_ptr(), s)
+                self._substep_free_surface(dt, s)
+                self._mask_immersed(velocities_only=True)   # (step_free_surface! ends with it)
+                # (on a dry face the corrector leaves 0 / 0 in u, as the reference does; nothing reads u before the mask of update_state!)
+                _lib.call("ocn_immersed_barotropic_corrector", g.cref, g.plane_ptr("Hfc"), g.plane_ptr("Hcf"), self.u.ptr, self.v.ptr,
+                          self.U.data_ptr(), self.V.data_ptr(), self._Ub.data_ptr(), self._Vb.data_ptr(), s)
+            else:
+                _lib.call("ocn_split_explicit_forcing", g.cref, Gn[0].ptr, Gm[0].ptr, Gn[1].ptr, Gm[1].ptr, float(chi), self._GU.data_ptr(),
+                          self._GV.data_ptr(), s)
+                self._substep_free_surface(dt, s)
+                # pressure_correct_velocities!: the barotropic corrector
+                _lib.call("ocn_barotropic_split_explicit_corrector", g.cref, self.u.ptr, self.v.ptr, self.U.data_ptr(), self.V.data_ptr(),
+                          self._Ub.data_ptr(), self._Vb.data_ptr(), float(g.Lz), s)
         elif self.implicit:
             # step_free_surface!(::ImplicitFreeSurface) (implicit_free_surface.jl:112-145); the halo fills of the velocities and of the
             # volume fluxes are not needed: the kernels wrap their x / y neighbour indices along Periodic directions
@@ -709,7 +789,10 @@ class HydrostaticFreeSurfaceModel:
         args = (g.cref, len(self._weights), self._weights, frac * float(dt), fs.gravitational_acceleration, float(g.Lz), self.eta.data_ptr(),
                 self.U.data_ptr(), self.V.data_ptr(), self._etab.data_ptr(), self._Ub.data_ptr(), self._Vb.data_ptr(), self._GU.data_ptr(),
                 self._GV.data_ptr())
-        if isinstance(fs.timestepper, AdamsBashforth3Scheme):
+        if self._immersed:
+            _lib.call("ocn_immersed_split_explicit_substeps", g.cref, g.plane_ptr("kbot"), g.plane_ptr("Hfc"), g.plane_ptr("Hcf"), *args[1:5],
+                      *args[6:], s)
+        elif isinstance(fs.timestepper, AdamsBashforth3Scheme):
             if self._dist is not None:
                 raise NotImplementedError("AdamsBashforth3Scheme substepping on a slab-partitioned grid")
             if getattr(self, "_ab3_work", None) is None:

@@ -92,12 +92,17 @@ class QuasiAdamsBashforth2TimeStepper(_TendencyStore):
 class NonhydrostaticModel:
     def __init__(self, grid, advection=None, tracers=(), timestepper="RungeKutta3", closure=None, buoyancy=None,
                  coriolis=None, forcing=None, stokes_drift=None, boundary_conditions=None,
-                 hydrostatic_pressure_anomaly="default", pressure_solver="default", math_mode=None, particles=None, _closure_halo=0):
+                 hydrostatic_pressure_anomaly="default", pressure_solver="default", math_mode=None, particles=None, _closure_halo=0,
+                 _hydrostatic_container=False):
         """math_mode: None keeps the grid's (default: the process default, ocn.set_math_mode); MATH_STRICT / MATH_FAST pin this
         model's arithmetic variant whatever other models of the process use (ocn_grid.math).
         particles: None or LagrangianParticles(...): moved to the architecture here and stepped with the pressure-corrected, halo-filled
         velocities after the update_state! of every RK3 stage / QAB2 step (one GPU; the C drivers refuse such a model)."""
         require_regular_xy(grid, "NonhydrostaticModel")
+        immersed = hasattr(grid, "immersed_boundary")
+        if immersed and not _hydrostatic_container:
+            raise NotImplementedError("NonhydrostaticModel on an ImmersedBoundaryGrid is not implemented (its pressure solver and w tendency "
+                                      "know no bathymetry); HydrostaticFreeSurfaceModel takes ImmersedBoundaryGrid(grid, GridFittedBottom(h))")
         if particles is not None:
             if not isinstance(particles, LagrangianParticles):
                 raise TypeError(f"particles must be LagrangianParticles(...) or None, got {type(particles).__name__}")
@@ -164,6 +169,10 @@ class NonhydrostaticModel:
         # (_closure_halo: what the hydrostatic model's own closure and momentum scheme need, one number or one per direction)
         extra = tuple(_closure_halo) if isinstance(_closure_halo, (tuple, list)) else (_closure_halo,) * 3
         required = tuple(max(advection.buffer, 1 if closure is not None else 0, e, 1) for e in extra)
+        if immersed:
+            # inflate_halo_size_one_dimension(req_H, old_H, _, ::IBG) = max(req_H + 1, old_H) (immersed_boundary_grid.jl:99-102): one more
+            # point, to check the inactivity of a Face node at N + H; with_halo carries the bathymetry along (:69-76)
+            required = tuple(r + 1 for r in required)
         H = (grid.Hx, grid.Hy, grid.Hz)
         for d, (N, t) in enumerate(zip(grid.size, grid.topology)):
             if t != Flat and N < advection.buffer:

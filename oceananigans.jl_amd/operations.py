@@ -607,6 +607,10 @@ def _metric(program, dims, location):
 
 
 def _refuse(grid, who):
+    if hasattr(grid, "immersed_boundary"):
+        # (the reference's reductions there are conditional on the active cells, and its operations mask their result)
+        raise NotImplementedError(f"{who} of a field on an ImmersedBoundaryGrid is not implemented: conditional reductions and masked "
+                                  "operations do not exist here; compute on the host with ocn.immersed_cell(grid)")
     if hasattr(grid.architecture, "partition"):
         raise NotImplementedError(f"{who} on a Distributed architecture is not implemented")
     require_regular_xy(grid, who)

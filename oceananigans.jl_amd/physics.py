@@ -1043,6 +1043,9 @@ class FieldBoundaryConditions:
 
     def __init__(self, **sides):
         for k in sides:
+            if k == "immersed":
+                raise NotImplementedError("immersed = ... boundary conditions are not implemented: an immersed boundary is no-flux for tracers "
+                                          "and free-slip for momentum (leave `immersed` out)")
             if k not in self.SIDES:
                 raise TypeError(f"unknown boundary {k!r}")
         self.sides = {k: sides.get(k) for k in self.SIDES}
