@@ -192,6 +192,25 @@ int ocn_compute_momentum_tendencies_rk3_flags(const ocn_grid *grid, const double
  * (every field's parent array below 2^31 bytes, halos of at least 3, OCN_TEND_ADDR32 not 0), 0 for the one with 64-bit addresses.
  * Host only: no device memory is touched. */
 int ocn_momentum_tendencies_addr32(const ocn_grid *grid, int32_t *selected);
+/* Which kernel, patch, z-chunk and launch grid a momentum-tendency launch for this grid and range (NULL = :xyz) takes, decided by the
+ * code the launch itself runs, into the eight elements of `plan`.  correct_on_load != 0: the launch of ocn_compute_momentum_tendencies_rk3 with p_correct (flags as in
+ * ocn_compute_momentum_tendencies_rk3_flags; strips != 0: ocn_compute_momentum_tendencies_rk3_strips); all three 0: the plain launch
+ * of ocn_compute_momentum_tendencies, whose fused forms (_rk3 without p_correct) take the same kernel.
+ *   plan[0]  OCN_PLAN_DIRECT (one thread per cell), OCN_PLAN_TILED (LDS patches, 64-bit addresses), OCN_PLAN_PC32 (correction on load,
+ *            32-bit addresses) or OCN_PLAN_STRIP_PATCH (the 4 x 64 patches of a halo-wide x-strip); -1 for an empty range
+ *   plan[1], plan[2]  TX, TY: the patch, which owns (TX - 1) x (TY - 1) columns (the direct kernel: its thread block)
+ *   plan[3]  KZ: planes marched per workgroup; workgroup n of a column starts at plane k0 + n KZ (the direct kernel: 1)
+ *   plan[4..6]  gridDim.x, .y, .z
+ *   plan[7]  OCN_PLAN_CORRECT_ON_LOAD | OCN_PLAN_WRITES_STRIPS: the instantiation of the tiled kernel (PC32: correction on load)
+ * Returns what the launch would return, OCN_ERR_UNSUPPORTED for a combination it refuses included.  Host only: no device is touched. */
+#define OCN_PLAN_DIRECT 0
+#define OCN_PLAN_TILED 1
+#define OCN_PLAN_PC32 2
+#define OCN_PLAN_STRIP_PATCH 3
+#define OCN_PLAN_CORRECT_ON_LOAD 1
+#define OCN_PLAN_WRITES_STRIPS 2
+int ocn_momentum_tendencies_plan(const ocn_grid *grid, const int32_t *range, int32_t correct_on_load, int32_t flags, int32_t strips,
+                                 int32_t *plan);
 /* compute_Gc! (compute_nonhydrostatic_tendencies.jl:186-195; tracer_tendency :228-259) */
 int ocn_compute_tracer_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w,
                                 const double *c, double *Gc, const int32_t *range, void *stream);

@@ -172,6 +172,7 @@ _SIGS = {
     "ocn_compute_momentum_tendencies_rk3_strips": [C.POINTER(CGrid)] + [_vp] * 12 + [_dbl, _dbl, _dbl, _i32, _vp, _dbl, _vp, _vp, C.c_int64, _vp],
     "ocn_compute_momentum_tendencies_rk3_flags": [C.POINTER(CGrid)] + [_vp] * 12 + [_dbl, _dbl, _dbl, _i32, _vp, _dbl, _i32, _vp],
     "ocn_momentum_tendencies_addr32": [C.POINTER(CGrid), C.POINTER(_i32)],
+    "ocn_momentum_tendencies_plan": [C.POINTER(CGrid), C.POINTER(_i32), _i32, _i32, _i32, C.POINTER(_i32)],
     "ocn_compute_tracer_tendency": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32), _vp],
     "ocn_compute_momentum_tendencies_terms": [C.POINTER(CGrid), C.POINTER(CModelTerms), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32), _vp],
     "ocn_compute_tracer_tendency_terms": [C.POINTER(CGrid), C.POINTER(CModelTerms), _dbl, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32), _vp],
@@ -395,3 +396,17 @@ def forcing_array(refs):
 
 def i32_array(vals):
     return (C.c_int32 * len(vals))(*vals)
+
+
+PLAN_KINDS = {-1: "none", 0: "direct", 1: "tiled", 2: "pc32", 3: "strip-patch"}  # OCN_PLAN_* (include/ocn_hip.h)
+
+
+def momentum_tendencies_plan(cgrid, range=None, correct_on_load=False, flags=0, strips=False):
+    """ocn_momentum_tendencies_plan: (status, plan) with plan = dict(kind, TX, TY, KZ, blocks, correct_on_load, strips).
+    Host only; the status is the launch's own (-2 = OCN_ERR_UNSUPPORTED is a result here, not an exception)."""
+    out = (C.c_int32 * 8)()
+    rng = i32_array(list(range)) if range is not None else None
+    st = lib().ocn_momentum_tendencies_plan(C.byref(cgrid), rng, int(bool(correct_on_load)), int(flags), int(bool(strips)), out)
+    p = list(out)
+    return st, dict(kind=PLAN_KINDS.get(p[0], p[0]), TX=p[1], TY=p[2], KZ=p[3], blocks=tuple(p[4:7]),
+                    correct_on_load=bool(p[7] & 1), strips=bool(p[7] & 2))

@@ -331,6 +331,32 @@ int ocn_momentum_tendencies_addr32(const ocn_grid *grid, int32_t *selected)
     return OCN_SUCCESS;
 }
 
+// the FuseArgs that the entry point in question builds, as far as the decision reads them (no pointer is dereferenced), through the
+// launcher's own plan function
+int ocn_momentum_tendencies_plan(const ocn_grid *grid, const int32_t *range, int32_t correct_on_load, int32_t flags, int32_t strips,
+                                 int32_t *plan)
+{
+    int st = validate_weno(grid);
+    if (st != OCN_SUCCESS) return st;
+    OCN_REQUIRE(plan, "ocn_momentum_tendencies_plan: plan is NULL");
+    OCN_REQUIRE(xy_periodic(grid), "ocn_momentum_tendencies_plan: grids Periodic (or partitioned) in x and Periodic in y");
+    OCN_REQUIRE(!(flags & ~(OCN_RK3_SKIP_G_STORE | OCN_RK3_WRAPPED_LOADS | OCN_RK3_CORRECT_ONLY)),
+                "ocn_momentum_tendencies_plan: unknown flag in %d", flags);
+    OCN_REQUIRE(correct_on_load || (!flags && !strips), "ocn_momentum_tendencies_plan: flags and strips belong to the correction-on-load launch");
+    OCN_REQUIRE(!strips || !flags, "ocn_momentum_tendencies_plan: the strip-writing launch takes no flags");
+    OCN_REQUIRE(!strips || (grid->tx == OCN_FULLY_CONNECTED && grid->ty == OCN_PERIODIC && grid->tz == OCN_PERIODIC),
+                "ocn_momentum_tendencies_plan: strips need a (FullyConnected, Periodic, Periodic) local grid");
+    if (!correct_on_load) return ocn_strict::plan_momentum_tendencies_query(grid, range, nullptr, plan);
+    static double nowhere;  // (stands for p_correct and the strip buffers: the decision only asks whether they are there)
+    FuseArgs fz = substep_fuse(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, 0.0, 0);
+    fz.pc_p = &nowhere; fz.pc_on = 1;
+    fz.skip_g = (flags & OCN_RK3_SKIP_G_STORE) ? 1 : 0;
+    fz.wrap_uvw = (flags & OCN_RK3_WRAPPED_LOADS) ? 1 : 0;
+    fz.no_step = (flags & OCN_RK3_CORRECT_ONLY) ? 1 : 0;
+    if (strips) { fz.strip_w = fz.strip_e = &nowhere; fz.strip_field = 1; }
+    return ocn_strict::plan_momentum_tendencies_query(grid, range, &fz, plan);
+}
+
 int ocn_cell_advection_timescale(const ocn_grid *grid, const double *u, const double *v, const double *w, double *result_device,
                                  void *stream)
 {

@@ -2,6 +2,8 @@
 // inside each of the four namespaces ocn_strict, ocn_fast, ocn_strict_up, ocn_fast_up (ocn_internal.h, general.hip).  Declarations only.
 int launch_momentum_tendencies(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
                                double *Gv, double *Gw, const int32_t *range, const ocn::FuseArgs *fuse, hipStream_t stream);
+// what launch_momentum_tendencies would launch, and its status, without launching (ocn_momentum_tendencies_plan)
+int plan_momentum_tendencies_query(const ocn_grid *grid, const int32_t *range, const ocn::FuseArgs *fuse, int32_t plan[8]);
 int launch_tracer_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c,
                            double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse = nullptr,
                            const ocn::ForcingDev *forcing = nullptr);

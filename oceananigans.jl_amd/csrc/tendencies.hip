@@ -1549,18 +1549,16 @@ static PatchGrid patch_grid(int TX, int TY, int wx, int wy, int wz, int min_wg, 
 
 template <int TZ, int TX, int TY, bool PC, bool GL = false, bool ST = false>
 static void launch_tiled(const GridDev &g, const double *u, const double *v, const double *w, double *Gu, double *Gv, double *Gw, const Range &r,
-                         const ocn::FuseArgs &fz, int wx, int wy, int wz, hipStream_t stream)
+                         const ocn::FuseArgs &fz, const PatchGrid &pg, hipStream_t stream)
 {
-    const PatchGrid pg = patch_grid(TX, TY, wx, wy, wz, min_blocks(), 16);
     hipLaunchKernelGGL((momentum_tendencies_tiled<TZ, TX, TY, 3, PC, GL, ST>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, Gu, Gv, Gw, r, pg.KZ, fz);
 }
 
 // the same launch (full range, periodic z, correction on load) through momentum_tendencies_pc32 (ocn::tendency_addr32_fits)
 template <int TX, int TY>
 static void launch_pc32(const ocn_grid &grid, const double *u, const double *v, const double *w, double *Gu, double *Gv, double *Gw,
-                        const Range &r, const ocn::FuseArgs &fz, int wx, int wy, int wz, hipStream_t stream)
+                        const Range &r, const ocn::FuseArgs &fz, const PatchGrid &pg, hipStream_t stream)
 {
-    const PatchGrid pg = patch_grid(TX, TY, wx, wy, wz, min_blocks(), 16);
     PcArgs a;
     a.u = u; a.v = v; a.w = w; a.p = fz.pc_p;
     a.G[0] = Gu; a.G[1] = Gv; a.G[2] = Gw;
@@ -1635,10 +1633,11 @@ int launch_momentum_tendencies_box(const ocn_grid *grid, const double *u, const 
     GridDev g = ocn::to_dev(*grid);
     ocn::FuseArgs fz{};
     if (fuse) fz = *fuse;  // (the next substep as the epilogue: per-field offsets like the G stores)
+    const PatchGrid pg = patch_grid(32, 8, wx, wy, wz, min_blocks(), 16);
     if (grid->tz == OCN_PERIODIC)
-        launch_tiled<OCN_PERIODIC, 32, 8, false, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
+        launch_tiled<OCN_PERIODIC, 32, 8, false, true>(g, u, v, w, Gu, Gv, Gw, r, fz, pg, stream);
     else
-        launch_tiled<OCN_BOUNDED, 32, 8, false, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
+        launch_tiled<OCN_BOUNDED, 32, 8, false, true>(g, u, v, w, Gu, Gv, Gw, r, fz, pg, stream);
     OCN_CHECK_HIP(hipGetLastError());
     *launched = 1;
     return OCN_SUCCESS;
@@ -1685,38 +1684,43 @@ int launch_tracer_tendency_box(const ocn_grid *grid, const double *u, const doub
 //  * range at least 16 x 8 x 4, plain: 17 x 15 patches where narrow_tile() says so, else 32 x 8;
 //  * the halo-wide x-strips of a distributed run (wx <= 3, wy >= 64, plain): 4 x 64 patches;
 //  * anything else, or OCN_TENDENCY_KERNEL=direct: momentum_tendencies_direct.
-int launch_momentum_tendencies(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
-                               double *Gv, double *Gw, const int32_t *range, const ocn::FuseArgs *fuse, hipStream_t stream)
+// THE decision, taken once here for the launcher and for the host-only query (ocn_momentum_tendencies_plan): the kernel (kind, with
+// pc = correction on load and st = strip-writing for the tiled one), its patch (the thread block of the direct kernel), the z-chunk and
+// the launch grid.  Sets fz.pc_xhalo.  kind = PLAN_NONE: an empty range, nothing to launch.
+enum { PLAN_NONE = -1, PLAN_DIRECT = OCN_PLAN_DIRECT, PLAN_TILED = OCN_PLAN_TILED, PLAN_PC32 = OCN_PLAN_PC32, PLAN_STRIP_PATCH = OCN_PLAN_STRIP_PATCH };
+struct TendencyPlan {
+    int kind, TX, TY;
+    bool pc, st;
+    PatchGrid pg;
+};
+static int plan_momentum_tendencies(const ocn_grid *grid, const int32_t *range, ocn::FuseArgs &fz, Range &r, TendencyPlan &pl)
 {
-    ocn::FuseArgs fz{};
-    if (fuse) fz = *fuse;
-    Range r;
+    pl = TendencyPlan{PLAN_NONE, 0, 0, false, false, {dim3(0, 0, 0), 0}};
     int st = make_range(grid, range, r);
     if (st != OCN_SUCCESS) return st;
     if (r.i1 < r.i0 || r.j1 < r.j0 || r.k1 < r.k0) return OCN_SUCCESS;
-    GridDev g = ocn::to_dev(*grid);
     const int wx = r.i1 - r.i0 + 1, wy = r.j1 - r.j0 + 1, wz = r.k1 - r.k0 + 1;
     static const int force_direct = (getenv("OCN_TENDENCY_KERNEL") && !strcmp(getenv("OCN_TENDENCY_KERNEL"), "direct"));
-    constexpr int P = OCN_PERIODIC, B = OCN_BOUNDED;
     if (!force_direct && grid->tz != OCN_FLAT && wx >= 16 && wy >= 8 && wz >= 4) {
         // narrow ranges (the 64-wide slab of one rank of eight): 32 x 8 patches own 31 columns each, so 64 columns take 3 patches (69 %
         // of the lanes useful in x); 17 x 15 patches own 16 x 14 and fit 64 = 4 x 16 exactly
-        const bool narrow = narrow_tile(wx, wy);
+        bool narrow = narrow_tile(wx, wy);
+        pl.kind = PLAN_TILED;
         if (fz.pc_on) {  // pressure correction on load: periodic z; x Periodic (wrapped) or FullyConnected (p halos exchanged), full range
             if ((grid->tx != OCN_PERIODIC && grid->tx != OCN_FULLY_CONNECTED) || grid->tz != OCN_PERIODIC || range != nullptr) {
                 ocn::set_error("pressure correction on load needs a (Periodic | FullyConnected, Periodic, Periodic) grid and the full range");
                 return OCN_ERR_UNSUPPORTED;
             }
             fz.pc_xhalo = grid->tx == OCN_FULLY_CONNECTED;
+            pl.pc = true;
             // without strips, 17 x 15 patches (16 x 14 cells owned: 87.8 % of the lanes useful against 84.8 % of 32 x 8) also on full boxes:
             // 24.42 against 24.56 ms per 512^3 step, six same-box pairs (round 4; 16 x 16 patches: 24.9 - 25.4)
             if (fz.strip_w) {  // slab-x rank whose next exchange takes its strips from this launch
-                if (!fz.pc_xhalo || !fz.strip_e || !fz.on || wx < 2 * g.Hx) {
+                if (!fz.pc_xhalo || !fz.strip_e || !fz.on || wx < 2 * grid->Hx) {
                     ocn::set_error("strips are written by the correction-on-load stage of a slab at least 2 Hx wide");
                     return OCN_ERR_INVALID_ARGUMENT;
                 }
-                if (narrow) launch_tiled<P, 17, 15, true, false, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
-                else launch_tiled<P, 32, 8, true, false, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
+                pl.st = true;
             } else if (fz.on && !fz.acc && ocn::tendency_addr32_enabled() && ocn::tendency_addr32_fits(*grid)) {
                 if (fz.wrap_uvw && fz.pc_xhalo) {
                     ocn::set_error("wrapped velocity loads need a Periodic x (the x halos of a slab hold the neighbours' columns)");
@@ -1726,38 +1730,95 @@ int launch_momentum_tendencies(const ocn_grid *grid, const double *u, const doub
                     ocn::set_error("a launch that stores the corrected velocity takes no substep (has_zeta must be 0)");
                     return OCN_ERR_INVALID_ARGUMENT;
                 }
-                launch_pc32<17, 15>(*grid, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
+                pl.kind = PLAN_PC32;
+                narrow = true;
             } else if (fz.wrap_uvw || fz.no_step) {  // (skip_g is a permission: the 64-bit kernel stores G)
                 ocn::set_error("wrapped velocity loads / the corrected-velocity store are the 32-bit kernel's (ocn_momentum_tendencies_addr32)");
                 return OCN_ERR_UNSUPPORTED;
             } else
-                launch_tiled<P, 17, 15, true>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
-        } else if (narrow) {
-            if (grid->tz == OCN_PERIODIC) launch_tiled<P, 17, 15, false>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
-            else launch_tiled<B, 17, 15, false>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
-        } else {  // fastest measured at 512^3 (6.9 ms vs 9.7 ms direct)
-            if (grid->tz == OCN_PERIODIC) launch_tiled<P, 32, 8, false>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
-            else launch_tiled<B, 32, 8, false>(g, u, v, w, Gu, Gv, Gw, r, fz, wx, wy, wz, stream);
+                narrow = true;
         }
+        // plain, 32 x 8: fastest measured at 512^3 (6.9 ms vs 9.7 ms direct)
+        pl.TX = narrow ? 17 : 32;
+        pl.TY = narrow ? 15 : 8;
+        pl.pg = patch_grid(pl.TX, pl.TY, wx, wy, wz, min_blocks(), 16);
     } else if (!force_direct && !fz.pc_on && grid->tz != OCN_FLAT && wx <= 3 && wy >= 64 && wz >= 4) {
         // the halo-wide x-strips of a distributed run (buffer tendencies): the same shared-flux kernel with a 4 x 64 patch of
         // columns (3 x 63 owned), i.e. tiled in y instead of x
-        constexpr int TX = 4, TY = 64;
-        const PatchGrid pg = patch_grid(TX, TY, wx, wy, wz, 2048, strip_min_kz());
-        if (grid->tz == OCN_PERIODIC)
-            hipLaunchKernelGGL((momentum_tendencies_tiled<P, TX, TY, 3, false>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, Gu, Gv, Gw, r, pg.KZ, fz);
-        else
-            hipLaunchKernelGGL((momentum_tendencies_tiled<B, TX, TY, 3, false>), pg.blocks, dim3(TX * TY), 0, stream, g, u, v, w, Gu, Gv, Gw, r, pg.KZ, fz);
+        pl.kind = PLAN_STRIP_PATCH;
+        pl.TX = 4;
+        pl.TY = 64;
+        pl.pg = patch_grid(pl.TX, pl.TY, wx, wy, wz, 2048, strip_min_kz());
     } else if (fz.pc_on) {
         ocn::set_error("pressure correction on load needs the tiled kernel (non-Flat z, range at least 16 x 8 x 4)");
         return OCN_ERR_UNSUPPORTED;
     } else {
-        const dim3 block = ocn::range_block(wx), nb = ocn::range_grid(block, wx, wy, wz);
-        switch (grid->tz) {
-            case OCN_PERIODIC: hipLaunchKernelGGL(momentum_tendencies_direct<OCN_PERIODIC>, nb, block, 0, stream, g, u, v, w, Gu, Gv, Gw, r, fz); break;
-            case OCN_BOUNDED: hipLaunchKernelGGL(momentum_tendencies_direct<OCN_BOUNDED>, nb, block, 0, stream, g, u, v, w, Gu, Gv, Gw, r, fz); break;
-            case OCN_FLAT: hipLaunchKernelGGL(momentum_tendencies_direct<OCN_FLAT>, nb, block, 0, stream, g, u, v, w, Gu, Gv, Gw, r, fz); break;
-            default: ocn::set_error("unsupported z topology %d", grid->tz); return OCN_ERR_UNSUPPORTED;
+        if (grid->tz != OCN_PERIODIC && grid->tz != OCN_BOUNDED && grid->tz != OCN_FLAT) {
+            ocn::set_error("unsupported z topology %d", grid->tz);
+            return OCN_ERR_UNSUPPORTED;
+        }
+        const dim3 block = ocn::range_block(wx);
+        pl.kind = PLAN_DIRECT;
+        pl.TX = block.x;
+        pl.TY = block.y;
+        pl.pg = PatchGrid{ocn::range_grid(block, wx, wy, wz), (int)block.z};
+    }
+    return OCN_SUCCESS;
+}
+
+int plan_momentum_tendencies_query(const ocn_grid *grid, const int32_t *range, const ocn::FuseArgs *fuse, int32_t plan[8])
+{
+    ocn::FuseArgs fz{};
+    if (fuse) fz = *fuse;
+    Range r;
+    TendencyPlan pl;
+    const int st = plan_momentum_tendencies(grid, range, fz, r, pl);
+    plan[0] = pl.kind; plan[1] = pl.TX; plan[2] = pl.TY; plan[3] = pl.pg.KZ;
+    plan[4] = (int32_t)pl.pg.blocks.x; plan[5] = (int32_t)pl.pg.blocks.y; plan[6] = (int32_t)pl.pg.blocks.z;
+    plan[7] = (pl.pc ? OCN_PLAN_CORRECT_ON_LOAD : 0) | (pl.st ? OCN_PLAN_WRITES_STRIPS : 0);
+    return st;
+}
+
+int launch_momentum_tendencies(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
+                               double *Gv, double *Gw, const int32_t *range, const ocn::FuseArgs *fuse, hipStream_t stream)
+{
+    ocn::FuseArgs fz{};
+    if (fuse) fz = *fuse;
+    Range r;
+    TendencyPlan pl;
+    int st = plan_momentum_tendencies(grid, range, fz, r, pl);
+    if (st != OCN_SUCCESS) return st;
+    if (pl.kind == PLAN_NONE) return OCN_SUCCESS;
+    GridDev g = ocn::to_dev(*grid);
+    constexpr int P = OCN_PERIODIC, B = OCN_BOUNDED;
+    const bool narrow = pl.TX == 17, periodic = grid->tz == OCN_PERIODIC;
+    switch (pl.kind) {
+        case PLAN_PC32: launch_pc32<17, 15>(*grid, u, v, w, Gu, Gv, Gw, r, fz, pl.pg, stream); break;
+        case PLAN_TILED:
+            if (pl.st) {
+                if (narrow) launch_tiled<P, 17, 15, true, false, true>(g, u, v, w, Gu, Gv, Gw, r, fz, pl.pg, stream);
+                else launch_tiled<P, 32, 8, true, false, true>(g, u, v, w, Gu, Gv, Gw, r, fz, pl.pg, stream);
+            } else if (pl.pc)
+                launch_tiled<P, 17, 15, true>(g, u, v, w, Gu, Gv, Gw, r, fz, pl.pg, stream);
+            else if (narrow) {
+                if (periodic) launch_tiled<P, 17, 15, false>(g, u, v, w, Gu, Gv, Gw, r, fz, pl.pg, stream);
+                else launch_tiled<B, 17, 15, false>(g, u, v, w, Gu, Gv, Gw, r, fz, pl.pg, stream);
+            } else {
+                if (periodic) launch_tiled<P, 32, 8, false>(g, u, v, w, Gu, Gv, Gw, r, fz, pl.pg, stream);
+                else launch_tiled<B, 32, 8, false>(g, u, v, w, Gu, Gv, Gw, r, fz, pl.pg, stream);
+            }
+            break;
+        case PLAN_STRIP_PATCH:
+            if (periodic) launch_tiled<P, 4, 64, false>(g, u, v, w, Gu, Gv, Gw, r, fz, pl.pg, stream);
+            else launch_tiled<B, 4, 64, false>(g, u, v, w, Gu, Gv, Gw, r, fz, pl.pg, stream);
+            break;
+        default: {
+            const dim3 block(pl.TX, pl.TY, pl.pg.KZ), nb = pl.pg.blocks;
+            switch (grid->tz) {
+                case OCN_PERIODIC: hipLaunchKernelGGL(momentum_tendencies_direct<OCN_PERIODIC>, nb, block, 0, stream, g, u, v, w, Gu, Gv, Gw, r, fz); break;
+                case OCN_BOUNDED: hipLaunchKernelGGL(momentum_tendencies_direct<OCN_BOUNDED>, nb, block, 0, stream, g, u, v, w, Gu, Gv, Gw, r, fz); break;
+                default: hipLaunchKernelGGL(momentum_tendencies_direct<OCN_FLAT>, nb, block, 0, stream, g, u, v, w, Gu, Gv, Gw, r, fz); break;
+            }
         }
     }
     OCN_CHECK_HIP(hipGetLastError());

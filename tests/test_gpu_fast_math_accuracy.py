@@ -24,7 +24,8 @@ Where s = 0 the result must equal G_ext exactly.  Assertions, per family, shape 
     FMA contraction never adds a rounding; the reorderings (factored metrics, difference form) are linear.  Both figures are printed;
   * the strict build equals G_64 bit for bit (signed zeros included) on the same inputs.
 
-Kernel selection (launch_momentum_tendencies / launch_tracer_tendency_t in csrc/tendencies.hip; no info call reports it): momentum takes
+Kernel selection (launch_momentum_tendencies / launch_tracer_tendency_t in csrc/tendencies.hip; ocn_momentum_tendencies_plan reports the
+momentum launch's, and tests/test_gpu_tendency_variants.py asserts it case by case): momentum takes
 17 x 15 patches where narrow_tile() prefers them (ranges at least 16 x 14) and 32 x 8 patches otherwise, for ranges of at least
 16 x 8 x 4 on a non-Flat z, the per-cell kernel below that; the tracer kernel always 32 x 8 patches; the z chunk is halved from Nz while
 longer than 16 (Nz = 40: 10, Nz = 20: 10).  Grids with walls in x / y go through csrc/general.hip.  On a failure the worst cell is
@@ -96,11 +97,13 @@ def _on_device(ocn, pg, f, mode, run):
     return [np.asfortranarray(from_dev(a)) for a in out]
 
 
-def _chunk(Nz):
-    KZ = Nz
-    while KZ > 16:
-        KZ = (KZ + 1) // 2
-    return KZ
+def _chunk(og):
+    """the z chunk of the momentum launch on this grid, from the launcher's own decision (ocn_momentum_tendencies_plan; 1 for the per-cell
+    kernel and where the query does not apply: walls in x / y)"""
+    import oceananigans_jl_amd as ocn
+    g = ocn._lib.CGrid(og.Nx, og.Ny, og.Nz, og.Hx, og.Hy, og.Hz, og.tx, og.ty, og.tz, 0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, None, None)
+    st, plan = ocn._lib.momentum_tendencies_plan(g)
+    return plan["KZ"] if st == 0 and plan["KZ"] > 0 else 1
 
 
 def _check_fast(og, label, names, got, G64, Gext, scales):
@@ -119,7 +122,7 @@ def _check_fast(og, label, names, got, G64, Gext, scales):
             i, j, k = at
             failures.append(f"{n}: E_fast = {Ef:.2f} > {FACTOR:g} max(E_64 = {E64:.2f}, 1) at (i, j, k) = {at}; mod 16 x 14 patches "
                             f"({(i - 1) % 16}, {(j - 1) % 14}), mod 31 x 7 patches ({(i - 1) % 31}, {(j - 1) % 7}), "
-                            f"mod the z chunk {(k - 1) % _chunk(og.Nz)}")
+                            f"mod the z chunk {(k - 1) % _chunk(og)}")
     assert not failures, f"{label}: " + "; ".join(failures)
 
 
