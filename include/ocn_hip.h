@@ -570,6 +570,55 @@ int ocn_catke_substep_tke(const ocn_grid *grid, const ocn_model_terms *terms, co
                           const double *znodes_c, const double *u_next, const double *v_next, const double *u_prev, const double *v_prev,
                           double *e, const double *Jb, const double *kappa_u, const double *kappa_c, double *kappa_e, double *Le,
                           const double *Gn_e, double *Gm_e, double *scratch, double dtau, double chi, int32_t solve, void *stream);
+/* ---- TKEDissipationVerticalDiffusivity, the k-ϵ closure (csrc/tke_dissipation.hip; turbulence_closure_implementations/
+ * TKEBasedVerticalDiffusivities/tke_dissipation_*.jl): κᵘ, κᶜ, κᵉ, κᵋ at (Center, Center, Face), the linear coefficients Le, Lϵ at (Center, Center,
+ * Center), the top fluxes of e and ϵ as planes of Nx Ny doubles (x fastest, the `values` of an ocn_bc) and the substep of e and ϵ.  The grid:
+ * (Periodic, Periodic, Bounded), halos >= 1, Nz >= 2, one GPU; strict math whatever the math mode.
+ * Reach: u at i, i + 1 and v at j, j + 1, k = 1..Nz; e, ϵ at k = 1..Nz; T, S at k = 1..Nz (the diffusivities) or k = 0..Nz + 1 (the substep: the
+ * plain ℑzᵃᵃᶜ(∂z_b) of the choice between Cᵇϵ⁺ and Cᵇϵ⁻ reads faces 1 and Nz + 1 from the first z halo planes); κᵘ (the substep) at
+ * i - 1..i + 1, j - 1..j + 1, faces 2..Nz; κᶜ (the substep) at faces 2..Nz of the column. */
+#define OCN_STABILITY_VARIABLE 0 /* VariableStabilityFunctions: the rational functions of the clamped αᴺ, αᴹ */
+#define OCN_STABILITY_CONSTANT 1 /* ConstantStabilityFunctions: 𝕊u = Cu0, 𝕊c = Cc0 (Cu1.. Cd5 are not read) */
+typedef struct ocn_tke_dissipation {
+    /* TKEDissipationEquations (tke_dissipation_equations.jl:10-20) */
+    double C_eps_eps, C_P_eps, C_b_eps_plus, C_b_eps_minus, C_W_ustar, C_W_wdelta, C_W_alpha, gravitational_acceleration, minimum_roughness_length;
+    /* the stability functions (tke_dissipation_stability_functions.jl:17-23, 40-100) */
+    double C_sigma_e, C_sigma_eps, Cu0, Cu1, Cu2, Cc0, Cc1, Cc2, Cd0, Cd1, Cd2, Cd3, Cd4, Cd5;
+    /* StratifiedDisplacementScale (tke_dissipation_vertical_diffusivity.jl:143-146) */
+    double C_N, minimum_buoyancy_frequency;
+    /* constants of the coefficients alone, computed once by the caller so that every user holds the same bits: 𝕊u₀, 𝕊u₀ 𝕊u₀ 𝕊u₀,
+     * ((𝕊u₀ 𝕊u₀) (𝕊u₀ 𝕊u₀)) / Cσϵ, minimum_stratification_number(closure) (the root times the safety factor; not read with
+     * OCN_STABILITY_CONSTANT) */
+    double Su0, Su0_cubed, Su0_fourth_over_sigma_eps, minimum_stratification_number;
+    /* TKEDissipationVerticalDiffusivity (tke_dissipation_vertical_diffusivity.jl:102-114); the four maxima may be +inf */
+    double maximum_tracer_diffusivity, maximum_tke_diffusivity, maximum_dissipation_diffusivity, maximum_viscosity;
+    double minimum_tke, negative_tke_damping_time_scale;
+    int32_t stability_functions; /* OCN_STABILITY_* */
+    int32_t reserved;
+} ocn_tke_dissipation;
+/* top_tke_flux and top_dissipation_flux (tke_dissipation_equations.jl:196-251) over the columns into the planes Qe and Qeps:
+ * Qe = - Cᵂu★ u★³, Qeps = - 𝕊u₀⁴ / Cσϵ e★(Nz)² / (d + ℓᵣ) with u★ = sqrt(sqrt(τx² + τy²)) from the top conditions of u and v (NULL or
+ * OCN_BC_DEFAULT: no flux), d = - znodes_c[Nz - 1], ℓᵣ = max(minimum_roughness_length, Cᵂα u★² / g).  znodes_c: a DEVICE vector of the Nz z
+ * centres. */
+int ocn_compute_tke_dissipation_top_fluxes(const ocn_grid *grid, const ocn_tke_dissipation *closure, const ocn_bc *top_u, const ocn_bc *top_v,
+                                           const double *znodes_c, const double *u, const double *v, const double *e, double *Qe, double *Qeps,
+                                           void *stream);
+/* compute_TKEDissipation_diffusivities! (tke_dissipation_vertical_diffusivity.jl:258-354) over i = 1..Nx, j = 1..Ny, faces k = 1..Nz in one
+ * launch, a thread per column marching upwards: κ = min(𝕊 e² / ϵ̄, maximum), face 1 exactly 0 (mask_diffusivity); face Nz + 1 and the halos
+ * are NOT written.  OCN_ERR_INVALID_ARGUMENT: aliased arrays, a coefficient that is not finite, a NaN maximum, a grid outside the scope. */
+int ocn_compute_tke_dissipation_diffusivities(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_tke_dissipation *closure,
+                                              const double *u, const double *v, const double *e, const double *eps, double *kappa_u,
+                                              double *kappa_c, double *kappa_e, double *kappa_eps, void *stream);
+/* substep_tke_dissipation! (tke_dissipation_equations.jl:90-185) and, with solve != 0, the implicit_step! of e (κᵉ, Le) and of ϵ (κᵋ, Lϵ) that
+ * follow it, one launch, a thread per column: κᵉ, κᵋ (faces 1..Nz) and Le, Lϵ (cells 1..Nz) are written, e and ϵ take their AB2 update with
+ * α = 1.5 + chi, β = 0.5 + chi, Gm_e and Gm_eps become the total tendencies, then the two tridiagonal solves in the column.  Every e and ϵ
+ * read by the substep is of before the call.  kappa_u, kappa_c: as ocn_compute_tke_dissipation_diffusivities left them, x / y halos of kappa_u
+ * filled.  scratch: 2 Nx Ny Nz doubles (the multipliers of the two eliminations; not read with solve == 0). */
+int ocn_tke_dissipation_substep(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_tke_dissipation *closure, const double *u_next,
+                                const double *v_next, const double *u_prev, const double *v_prev, double *e, double *eps,
+                                const double *kappa_u, const double *kappa_c, double *kappa_e, double *kappa_eps, double *Le, double *Leps,
+                                const double *Gn_e, double *Gm_e, const double *Gn_eps, double *Gm_eps, double *scratch, double dtau, double chi,
+                                int32_t solve, void *stream);
 /* ---- HorizontalScalarBiharmonicDiffusivity: ScalarBiharmonicDiffusivity{HorizontalFormulation} with constant ν and κ
  * (csrc/biharmonic.hip; abstract_scalar_biharmonic_diffusivity_closure.jl:46-51, 66-67, 75-102; strict math whatever the math mode) ----
  * The closure term SUBTRACTED from tendencies that hold every other term, over i = 1..Nx, j = 1..Ny, k = 1..Nz:

@@ -29,6 +29,8 @@ from .physics import (HorizontalDivergenceFormulation, HorizontalFormulation, Ho
 from .physics import (ExponentialRiDependentTapering, FivePointHorizontalFilter, HyperbolicTangentRiDependentTapering,
                       PiecewiseLinearRiDependentTapering, RiBasedVerticalDiffusivity)
 from .physics import CATKEEquation, CATKEMixingLength, CATKEVerticalDiffusivity
+from .physics import (ConstantStabilityFunctions, StratifiedDisplacementScale, TKEDissipationEquations, TKEDissipationVerticalDiffusivity,
+                      VariableStabilityFunctions)
 from .physics import (AdvectiveFormulation, DiffusiveFormulation, FluxTapering, IsopycnalSkewSymmetricDiffusivity, IsopycnalTensor,
                       SmallSlopeIsopycnalTensor)
 from .physics import (AnisotropicMinimumDissipation, ConvectiveAdjustmentVerticalDiffusivity, DynamicCoefficient, DynamicSmagorinsky, LillyCoefficient, Smagorinsky, SmagorinskyLilly, BetaPlane, BoundaryCondition, BuoyancyTracer, Centered, FieldBoundaryConditions, FluxBoundaryCondition, FPlane,

@@ -108,6 +108,19 @@ class CCatke(C.Structure):
     _fields_ = [(n, C.c_double) for n in CATKE_FIELDS]
 
 
+TKE_DISSIPATION_FIELDS = ("C_eps_eps", "C_P_eps", "C_b_eps_plus", "C_b_eps_minus", "C_W_ustar", "C_W_wdelta", "C_W_alpha",
+                          "gravitational_acceleration", "minimum_roughness_length", "C_sigma_e", "C_sigma_eps", "Cu0", "Cu1", "Cu2", "Cc0", "Cc1", "Cc2",
+                          "Cd0", "Cd1", "Cd2", "Cd3", "Cd4", "Cd5", "C_N", "minimum_buoyancy_frequency", "Su0", "Su0_cubed",
+                          "Su0_fourth_over_sigma_eps", "minimum_stratification_number", "maximum_tracer_diffusivity", "maximum_tke_diffusivity",
+                          "maximum_dissipation_diffusivity", "maximum_viscosity", "minimum_tke", "negative_tke_damping_time_scale")
+STABILITY_VARIABLE, STABILITY_CONSTANT = 0, 1
+
+
+class CTKEDissipation(C.Structure):
+    """struct ocn_tke_dissipation"""
+    _fields_ = [(n, C.c_double) for n in TKE_DISSIPATION_FIELDS] + [("stability_functions", C.c_int32), ("reserved", C.c_int32)]
+
+
 class CSmagorinsky(C.Structure):
     """struct ocn_smagorinsky"""
     _fields_ = [("C", C.c_double), ("Cb", C.c_double), ("lilly", C.c_int32), ("n_tracers", C.c_int32), ("Pr", C.c_double * MODEL_MAX_TRACERS)]
@@ -236,6 +249,9 @@ _SIGS = {
                                        C.POINTER(CBc), _vp, _vp, _vp, _vp],
     "ocn_compute_catke_diffusivities": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CCatke)] + [_vp] * 10,
     "ocn_catke_substep_tke": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CCatke)] + [_vp] * 15 + [_dbl, _dbl, _i32, _vp],
+    "ocn_compute_tke_dissipation_top_fluxes": [C.POINTER(CGrid), C.POINTER(CTKEDissipation), C.POINTER(CBc), C.POINTER(CBc)] + [_vp] * 7,
+    "ocn_compute_tke_dissipation_diffusivities": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CTKEDissipation)] + [_vp] * 9,
+    "ocn_tke_dissipation_substep": [C.POINTER(CGrid), C.POINTER(CModelTerms), C.POINTER(CTKEDissipation)] + [_vp] * 17 + [_dbl, _dbl, _i32, _vp],
     "ocn_cache_previous_tendencies": [C.POINTER(CGrid), _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), _vp],
     "ocn_pressure_correct_velocities": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _dbl, _vp],
     "ocn_divergence": [C.POINTER(CGrid), _vp, _vp, _vp, _vp, _vp],

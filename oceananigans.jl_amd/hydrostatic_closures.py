@@ -20,8 +20,8 @@ from .architectures import stream_ptr
 from .fields import CenterField, XFaceField, YFaceField, ZFaceField, fill_halo_regions
 from .models import implicit_diffusion_step
 from .physics import (BuoyancyTracer, CATKEVerticalDiffusivity, FieldBoundaryConditions, FluxBoundaryCondition, IsopycnalSkewSymmetricDiffusivity,
-                      RiBasedVerticalDiffusivity, ScalarBiharmonicDiffusivity, SeawaterBuoyancy, has_diffusivity_fields, is_vertically_implicit,
-                      owns_eddy_fields)
+                      RiBasedVerticalDiffusivity, ScalarBiharmonicDiffusivity, SeawaterBuoyancy, TKEDissipationVerticalDiffusivity,
+                      has_diffusivity_fields, is_vertically_implicit, owns_eddy_fields)
 
 
 def _refuse(what, fused, split_rk3, slabs):
@@ -44,8 +44,8 @@ def resolve_closure(closure, fused, split_rk3, partitioned, distributed, buoyanc
         vertical = [c for c in closure if has_diffusivity_fields(c) or isinstance(c, IsopycnalSkewSymmetricDiffusivity)]
         if len(closure) != 2 or len(biharmonic) != 1 or len(vertical) != 1:
             raise NotImplementedError("closure tuples are not implemented, except (HorizontalScalarBiharmonicDiffusivity, "
-                                      "ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity or CATKEVerticalDiffusivity) in either order: "
-                                      "give one closure")
+                                      "ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity or CATKEVerticalDiffusivity) in either order, "
+                                      "and the same pair with TKEDissipationVerticalDiffusivity: give one closure")
         biharmonic, closure = biharmonic[0], vertical[0]
     elif isinstance(closure, ScalarBiharmonicDiffusivity):
         biharmonic, closure = closure, None
@@ -68,7 +68,11 @@ def resolve_closure(closure, fused, split_rk3, partitioned, distributed, buoyanc
         if isinstance(closure, CATKEVerticalDiffusivity):
             if "e" not in tuple(tracers):  # with_tracers (catke_vertical_diffusivity.jl:122-128)
                 raise ValueError(closure.MISSING_TRACER)
-        if isinstance(closure, (RiBasedVerticalDiffusivity, CATKEVerticalDiffusivity)):
+        if isinstance(closure, TKEDissipationVerticalDiffusivity):  # with_tracers (tke_dissipation_vertical_diffusivity.jl:131-137)
+            if "e" not in tuple(tracers) or closure.dissipation_name(tracers) is None:
+                raise ValueError(closure.MISSING_TRACER)
+        stress_driven = isinstance(closure, (CATKEVerticalDiffusivity, TKEDissipationVerticalDiffusivity))
+        if isinstance(closure, (RiBasedVerticalDiffusivity, CATKEVerticalDiffusivity, TKEDissipationVerticalDiffusivity)):
             # top_buoyancy_flux reads the top condition of the buoyancy tracers as a flux; the reference would read the number of a Value or
             # Gradient condition as one too, which is not reproduced
             carriers = ("b", None) if isinstance(buoyancy, BuoyancyTracer) else (("T", "S") if isinstance(buoyancy, SeawaterBuoyancy) else (None, None))
@@ -78,12 +82,15 @@ def resolve_closure(closure, fused, split_rk3, partitioned, distributed, buoyanc
                 if top is not None and top.kind != _lib.BC_FLUX:
                     raise NotImplementedError(f"{name}: the top boundary condition of {tracer} must be a "
                                               "FluxBoundaryCondition (or the default): it is the surface buoyancy flux of the entrainment term")
-            for velocity in ("u", "v") if isinstance(closure, CATKEVerticalDiffusivity) else ():
+            for velocity in ("u", "v") if stress_driven else ():
                 top = getattr((boundary_conditions or {}).get(velocity), "sides", {}).get("top")
                 if top is not None and top.kind != _lib.BC_FLUX:
                     raise NotImplementedError(f"{name}: the top boundary condition of {velocity} must be a "
                                               "FluxBoundaryCondition (or the default): it is the wind stress of the friction velocity")
-        other = CATKEFields(closure, carriers) if isinstance(closure, CATKEVerticalDiffusivity) else KappaFields(closure, carriers)
+        if isinstance(closure, TKEDissipationVerticalDiffusivity):
+            other = TKEDissipationFields(closure, carriers, closure.dissipation_name(tracers))
+        else:
+            other = CATKEFields(closure, carriers) if isinstance(closure, CATKEVerticalDiffusivity) else KappaFields(closure, carriers)
     elif is_vertically_implicit(closure):
         _refuse("a VerticallyImplicitTimeDiscretization closure", fused, split_rk3, distributed)
         if partitioned:
@@ -334,6 +341,114 @@ class CATKEFields(KappaFields):
                 raise KeyError(f"Field {name} of CATKEVerticalDiffusivity does not exist in checkpoint and could not be restored.")
             t.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(a).T)))
         self.previous_compute_time = float(get("previous_compute_time"))
+
+
+class TKEDissipationFields(KappaFields):
+    """TKEDissipationVerticalDiffusivity (csrc/tke_dissipation.hip): κᵘ, κᶜ, κᵉ, κᵋ, the linear coefficients Le, Lϵ and the previous velocities
+    (build_diffusivity_fields, tke_dissipation_vertical_diffusivity.jl:184-223).  The closure steps the tracers e and ϵ itself, inside
+    compute_diffusivities! (:228-256): M substeps of substep_tke_dissipation! + the implicit_step! of e + that of ϵ, one launch each.  Their
+    slow tendencies are the ordinary tracer tendencies with κᵉ / κᵋ; ab2_step, the implicit step of the other fields and
+    cache_previous_tendencies leave them alone.  Their top conditions are the closure's own (add_closure_specific_boundary_conditions,
+    tke_dissipation_equations.jl:258-303): two array-valued fluxes that ocn_compute_tke_dissipation_top_fluxes writes.  `eps`: the name the user
+    gave the dissipation tracer."""
+
+    def __init__(self, closure, carriers, eps):
+        super().__init__(closure, carriers)
+        self.state_fields = ()  # (everything goes through checkpoint_state / restore_state)
+        self.eps, self.self_stepped = eps, ("e", eps)
+
+    def boundary_conditions(self, user_bcs, grid):
+        """the top conditions of e and ϵ are replaced; the user's other sides are kept (the reference's branch for user conditions on ϵ copies
+        the sides of e's, a slip: here ϵ keeps its own)"""
+        bcs = dict(user_bcs or {})
+        self.tops = {}
+        for name in self.self_stepped:
+            sides = dict(bcs[name].sides) if bcs.get(name) is not None else {}
+            self.tops[name] = sides["top"] = FluxBoundaryCondition(np.zeros((grid.Nx, grid.Ny)))
+            bcs[name] = FieldBoundaryConditions(**{k: v for k, v in sides.items() if v is not None})
+        return bcs
+
+    def allocate(self, nh):
+        g, dev = nh.grid, nh.u.data.device
+        self.fields = {"kappa_u": ZFaceField(g), "kappa_c": ZFaceField(g), "kappa_e": ZFaceField(g), "kappa_eps": ZFaceField(g),
+                       "Le": CenterField(g), "Leps": CenterField(g)}
+        self.u_prev, self.v_prev = XFaceField(g), YFaceField(g)
+        self.struct = self.closure.c_struct()
+        self.zc = torch.from_numpy(np.ascontiguousarray(g.nodes_1d(2, False), dtype=np.float64)).to(dev)
+        self.ivd_scratch = torch.zeros((5, g.Nz, g.Ny, g.Nx), dtype=torch.float64, device=dev)  # u, v, the tracers, e and ϵ
+        for top in self.tops.values():
+            top.c_struct(g, "top")  # (allocates the device array of the condition)
+        return self.fields
+
+    def kappa_of_tracer(self, name):
+        return self.fields["kappa_e" if name == "e" else ("kappa_eps" if name == self.eps else "kappa_c")].ptr
+
+    _top = staticmethod(CATKEFields._top)
+
+    def _tendencies(self, nh, name):
+        q = 3 + nh.tracer_names.index(name)
+        return nh.timestepper._Gn[q], nh.timestepper._Gm[q]
+
+    def time_step_tke_dissipation(self, nh, s):
+        """time_step_tke_dissipation_equations! (tke_dissipation_equations.jl:24-88)"""
+        g, d = nh.grid, self.fields
+        Dt, tau = nh.clock.last_dt, self.closure.tke_dissipation_time_step
+        M = 1 if tau is None else math.ceil(Dt / tau)
+        dtau = Dt if tau is None else Dt / M
+        (Gn_e, Gm_e), (Gn_eps, Gm_eps) = self._tendencies(nh, "e"), self._tendencies(nh, self.eps)
+        for m in range(1, M + 1):
+            # an Euler step opens several substeps; otherwise the time stepper's χ, which is -1/2 during an Euler step of the model
+            chi = -0.5 if (m == 1 and M != 1) else nh.timestepper.chi
+            _lib.call("ocn_tke_dissipation_substep", g.cref, C.byref(nh._terms), C.byref(self.struct), nh.u.ptr, nh.v.ptr, self.u_prev.ptr,
+                      self.v_prev.ptr, nh.field("e").ptr, nh.field(self.eps).ptr, d["kappa_u"].ptr, d["kappa_c"].ptr, d["kappa_e"].ptr,
+                      d["kappa_eps"].ptr, d["Le"].ptr, d["Leps"].ptr, Gn_e.ptr, Gm_e.ptr, Gn_eps.ptr, Gm_eps.ptr, self.ivd_scratch[3].data_ptr(),
+                      float(dtau), float(chi), 1, s)
+
+    def compute_diffusivities(self, nh):
+        g, d, s = nh.grid, self.fields, stream_ptr()
+        nh._refresh_term_pointers()
+        terms, cl = C.byref(nh._terms), C.byref(self.struct)
+        if math.isfinite(nh.clock.last_dt):  # the model has taken a step
+            self.time_step_tke_dissipation(nh, s)
+        self.u_prev.data.copy_(nh.u.data)
+        self.v_prev.data.copy_(nh.v.data)
+        e, eps = nh.field("e"), nh.field(self.eps)
+        kappas = [d[name] for name in ("kappa_u", "kappa_c", "kappa_e", "kappa_eps")]
+        _lib.call("ocn_compute_tke_dissipation_diffusivities", g.cref, terms, cl, nh.u.ptr, nh.v.ptr, e.ptr, eps.ptr, *[k.ptr for k in kappas], s)
+        # (the reference's fill_halo_regions!(::TKEDissipationDiffusivityFields) names an undefined variable: what it evidently means)
+        fill_halo_regions(tuple(kappas), fill_boundary_normal_velocities=False)
+        # the top fluxes of e and ϵ, for the compute_boundary_tendency_contributions! of this state
+        _lib.call("ocn_compute_tke_dissipation_top_fluxes", g.cref, cl, self._top(nh, nh.u), self._top(nh, nh.v), self.zc.data_ptr(), nh.u.ptr,
+                  nh.v.ptr, e.ptr, self.tops["e"]._device_values.data_ptr(), self.tops[self.eps]._device_values.data_ptr(), s)
+
+    def implicit_step(self, nh, fields, dt, s):
+        """implicit_step! of u, v (κᵘ) and the tracers but e and ϵ (κᶜ), which are stepped in compute_diffusivities"""
+        d, w, nt = self.fields, self.ivd_scratch, len(fields) - 2
+        kappas = [d["kappa_u"].ptr] * 2 + [d["kappa_c"].ptr] * nt
+        scratch = [w[0].data_ptr(), w[1].data_ptr()] + [w[2].data_ptr()] * nt
+        _lib.call("ocn_implicit_vertical_diffusion_step_fields", nh.grid.cref, len(fields), _lib.ptr_array([f.ptr for f in fields]),
+                  _lib.i32_array([f.loc for f in fields]), _lib.ptr_array(kappas), _lib.ptr_array(scratch), float(dt), s)
+
+    def _state(self, nh):
+        """{name: (the device tensor, whether it is a plane of Nx Ny values)}: everything a bit-identical restart needs"""
+        d = self.fields
+        out = {name: d[name].data for name in ("kappa_u", "kappa_c", "kappa_e", "kappa_eps", "Le", "Leps")}
+        out.update(u_prev=self.u_prev.data, v_prev=self.v_prev.data, top_e=self.tops["e"]._device_values,
+                   top_eps=self.tops[self.eps]._device_values, e=nh.field("e").data, eps=nh.field(self.eps).data,
+                   Gm_e=self._tendencies(nh, "e")[1].data, Gm_eps=self._tendencies(nh, self.eps)[1].data)
+        return out
+
+    def checkpoint_state(self, nh):
+        return {name: np.ascontiguousarray(t.cpu().numpy().T) for name, t in self._state(nh).items()}
+
+    def restore_state(self, nh, get):
+        """the update_state! of set!(model, filepath) has stepped e and ϵ once more: put back what the checkpointed tendencies were computed
+        with, so that the restart continues bit for bit"""
+        for name, t in self._state(nh).items():
+            a = get(name)
+            if a is None:
+                raise KeyError(f"Field {name} of TKEDissipationVerticalDiffusivity does not exist in checkpoint and could not be restored.")
+            t.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(a).T)))
 
 
 class IsopycnalFields(InModelTerms):

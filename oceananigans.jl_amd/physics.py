@@ -10,6 +10,10 @@
                                                   .../turbulence_closure_implementations/ri_based_vertical_diffusivity.jl
   CATKEVerticalDiffusivity([time_discretization], mixing_length=CATKEMixingLength(...), turbulent_kinetic_energy_equation=CATKEEquation(...), ...)
                                                   .../turbulence_closure_implementations/TKEBasedVerticalDiffusivities/
+  TKEDissipationVerticalDiffusivity([time_discretization], tke_dissipation_equations=TKEDissipationEquations(...),
+                                    stability_functions=VariableStabilityFunctions(...) | ConstantStabilityFunctions(...),
+                                    minimum_length_scale=StratifiedDisplacementScale(...), ...)
+                                                  .../TKEBasedVerticalDiffusivities/tke_dissipation_*.jl
   Smagorinsky(coefficient=..., Pr=...), SmagorinskyLilly(C=..., Cb=..., Pr=...), LillyCoefficient(...)
                                                   .../turbulence_closure_implementations/Smagorinskys/{smagorinsky,lilly_coefficient}.jl
   BuoyancyTracer(), SeawaterBuoyancy(...), LinearEquationOfState(...)
@@ -501,10 +505,148 @@ class CATKEVerticalDiffusivity:
         return f"CATKEVerticalDiffusivity{{{type(self.time_discretization).__name__}}}"
 
 
+class TKEDissipationEquations(_Coefficients):
+    """TKEDissipationEquations(; Cᵋϵ = 1.92, Cᴾϵ = 1.44, Cᵇϵ⁺ = -0.65, Cᵇϵ⁻ = -0.65, Cᵂu★ = 0, CᵂwΔ = 0, Cᵂα = 0.11, gravitational_acceleration =
+    9.8065, minimum_roughness_length = 1e-4) (tke_dissipation_equations.jl:10-20).  ASCII: C_eps_eps, C_P_eps, C_b_eps_plus, C_b_eps_minus,
+    C_W_ustar, C_W_wdelta, C_W_alpha."""
+    DEFAULTS = {"C_eps_eps": 1.92, "C_P_eps": 1.44, "C_b_eps_plus": -0.65, "C_b_eps_minus": -0.65, "C_W_ustar": 0.0, "C_W_wdelta": 0.0,
+                "C_W_alpha": 0.11, "gravitational_acceleration": 9.8065, "minimum_roughness_length": 1e-4}
+    SPELLINGS = {"C_eps_eps": "Cᵋϵ", "C_P_eps": "Cᴾϵ", "C_b_eps_plus": "Cᵇϵ⁺", "C_b_eps_minus": "Cᵇϵ⁻", "C_W_ustar": "Cᵂu★", "C_W_wdelta": "CᵂwΔ",
+                 "C_W_alpha": "Cᵂα", "gravitational_acceleration": "gravitational_acceleration",
+                 "minimum_roughness_length": "minimum_roughness_length"}
+
+
+class ConstantStabilityFunctions(_Coefficients):
+    """ConstantStabilityFunctions(; Cσe = 1.0, Cσϵ = 1.2, Cu₀ = 0.53, Cc₀ = 0.53, 𝕊u₀ = 0.53) (tke_dissipation_stability_functions.jl:17-23): 𝕊u = Cu₀,
+    𝕊c = Cc₀, 𝕊e = 𝕊u / Cσe, 𝕊ϵ = 𝕊u / Cσϵ.  ASCII: C_sigma_e, C_sigma_eps, Cu0, Cc0, Su0."""
+    DEFAULTS = {"C_sigma_e": 1.0, "C_sigma_eps": 1.2, "Cu0": 0.53, "Cc0": 0.53, "Su0": 0.53}
+    SPELLINGS = {"C_sigma_e": "Cσe", "C_sigma_eps": "Cσϵ", "Cu0": "Cu₀", "Cc0": "Cc₀", "Su0": "𝕊u₀"}
+    CODE = _lib.STABILITY_CONSTANT
+
+    def minimum_stratification_number(self, safety_factor):
+        """(not read: the constants take no αᴺ)"""
+        return 0.0
+
+    def __repr__(self):  # Base.summary
+        return "ConstantStabilityFunctions{Float64}"
+
+
+class VariableStabilityFunctions(_Coefficients):
+    """VariableStabilityFunctions(; Cσe = 1.0, Cσϵ = 1.2, Cu₀ = 0.1067, Cu₁ = 0.0173, Cu₂ = -0.0001205, Cc₀ = 0.1120, Cc₁ = 0.003766, Cc₂ = 0.0008871,
+    Cd₀ = 1.0, Cd₁ = 0.2398, Cd₂ = 0.02872, Cd₃ = 0.005154, Cd₄ = 0.006930, Cd₅ = -0.0003372, 𝕊u₀ = nothing)
+    (tke_dissipation_stability_functions.jl:40-100): 𝕊u and 𝕊c are rational functions of the clamped stratification and shear numbers.
+    𝕊u₀ = nothing: the value of the logarithmic boundary layer, (2a / (-b - sqrt(b² - 4ac)))^(1/4) with a = Cd₅ - Cu₂, b = Cd₂ - Cu₀, c = Cd₀.
+    ASCII: C_sigma_e, C_sigma_eps, Cu0 .. Cu2, Cc0 .. Cc2, Cd0 .. Cd5, Su0."""
+    DEFAULTS = {"C_sigma_e": 1.0, "C_sigma_eps": 1.2, "Cu0": 0.1067, "Cu1": 0.0173, "Cu2": -0.0001205, "Cc0": 0.1120, "Cc1": 0.003766,
+                "Cc2": 0.0008871, "Cd0": 1.0, "Cd1": 0.2398, "Cd2": 0.02872, "Cd3": 0.005154, "Cd4": 0.006930, "Cd5": -0.0003372, "Su0": None}
+    SPELLINGS = {"C_sigma_e": "Cσe", "C_sigma_eps": "Cσϵ", "Su0": "𝕊u₀",
+                 **{f"C{x}{n}": f"C{x}{s}" for x, count in (("u", 3), ("c", 3), ("d", 6)) for n, s in list(enumerate("₀₁₂₃₄₅"))[:count]}}
+    CODE = _lib.STABILITY_VARIABLE
+
+    def __init__(self, **kw):
+        given = {name: value for name, value in kw.items() if not (self.canonical(name) == "Su0" and value is None)}
+        super().__init__(**given)
+        if self.Su0 is None:
+            a, b, c = self.Cd5 - self.Cu2, self.Cd2 - self.Cu0, self.Cd0
+            self.Su0 = (2 * a / (-b - math.sqrt(b * b - 4 * a * c))) ** (1 / 4)
+
+    def minimum_stratification_number(self, safety_factor):
+        """minimum_stratification_number(closure) (:150-173, Umlauf & Burchard 2005, eq. A.22), reduced by the safety factor"""
+        a, b, c = self.Cd4 + self.Cc1, self.Cd1 + self.Cc0, self.Cd0
+        return (-b + math.sqrt(b * b - 4 * a * c)) / (2 * a) * safety_factor
+
+    def __repr__(self):  # Base.summary
+        return "VariableStabilityFunctions{Float64}"
+
+
+class StratifiedDisplacementScale(_Coefficients):
+    """StratifiedDisplacementScale(; Cᴺ = 0.75, minimum_buoyancy_frequency = 1e-14) (tke_dissipation_vertical_diffusivity.jl:143-146): the floor
+    of the dissipation, ϵ ≥ 𝕊u₀³ sqrt(e)³ / min(Lz, Cᴺ sqrt(e / N²)).  ASCII: C_N."""
+    DEFAULTS = {"C_N": 0.75, "minimum_buoyancy_frequency": 1e-14}
+    SPELLINGS = {"C_N": "Cᴺ", "minimum_buoyancy_frequency": "minimum_buoyancy_frequency"}
+
+
+class TKEDissipationVerticalDiffusivity:
+    """TKEDissipationVerticalDiffusivity([time_discretization = VerticallyImplicitTimeDiscretization()]; tke_dissipation_equations =
+    TKEDissipationEquations(), stability_functions = VariableStabilityFunctions(), minimum_length_scale = StratifiedDisplacementScale(),
+    maximum_tracer_diffusivity = Inf, maximum_tke_diffusivity = Inf, maximum_dissipation_diffusivity = Inf, maximum_viscosity = Inf,
+    minimum_tke = 1e-6, minimum_stratification_number_safety_factor = 0.73, negative_tke_damping_time_scale = 1minute,
+    tke_dissipation_time_step = nothing) (tke_dissipation_vertical_diffusivity.jl:102-129): the k-ϵ closure (Burchard & Bolding 2001, Umlauf &
+    Burchard 2003, 2005).  κᵘ, κᶜ, κᵉ, κᵋ = 𝕊 e² / ϵ from two prognostic tracers, the turbulent kinetic energy "e" and its dissipation
+    ("epsilon", "ϵ" or "ε"), which the closure steps itself.  HydrostaticFreeSurfaceModel only; the explicit discretization, arrays of closures
+    (ensembles) and coefficients that are no numbers are not implemented."""
+    NUMBERS = {"maximum_tracer_diffusivity": math.inf, "maximum_tke_diffusivity": math.inf, "maximum_dissipation_diffusivity": math.inf,
+               "maximum_viscosity": math.inf, "minimum_tke": 1e-6, "minimum_stratification_number_safety_factor": 0.73,
+               "negative_tke_damping_time_scale": 60.0}
+    MISSING_TRACER = "Tracers must contain :e and :ϵ to represent turbulent kinetic energy for `TKEDissipationVerticalDiffusivity`."
+    DISSIPATION_NAMES = ("epsilon", "ϵ", "ε")  # canonical, the reference's (U+03F5), the Greek letter (U+03B5)
+    PARTS = {"tke_dissipation_equations": (TKEDissipationEquations,), "stability_functions": (VariableStabilityFunctions, ConstantStabilityFunctions),
+             "minimum_length_scale": (StratifiedDisplacementScale,)}
+
+    def __init__(self, *args, **kw):
+        if len(args) > 1:
+            raise TypeError("TKEDissipationVerticalDiffusivity takes one positional argument, the time discretization")
+        if args:
+            if "time_discretization" in kw:
+                raise TypeError("time_discretization given twice")
+            kw["time_discretization"] = args[0]
+        self.time_discretization = as_time_discretization(kw.pop("time_discretization", VerticallyImplicitTimeDiscretization()))
+        if not isinstance(self.time_discretization, VerticallyImplicitTimeDiscretization):
+            raise NotImplementedError("TKEDissipationVerticalDiffusivity with ExplicitTimeDiscretization is not implemented: use the default "
+                                      "VerticallyImplicitTimeDiscretization()")
+        for key, kinds in self.PARTS.items():
+            part = kw.pop(key, None)
+            part = kinds[0]() if part is None else part
+            if not isinstance(part, kinds):
+                raise TypeError(f"{key} must be " + " or ".join(f"{kind.__name__}(...)" for kind in kinds))
+            setattr(self, key, part)
+        for key, default in self.NUMBERS.items():
+            value = kw.pop(key, default)
+            if isinstance(value, (bool, str)) or callable(value) or not np.isscalar(value) or not np.isreal(value):
+                raise NotImplementedError(f"TKEDissipationVerticalDiffusivity: {key} must be a number (arrays, fields and functions are not "
+                                          "implemented)")
+            setattr(self, key, float(value))
+        time_step = kw.pop("tke_dissipation_time_step", None)
+        if time_step is not None:
+            if isinstance(time_step, (bool, str)) or not np.isscalar(time_step) or not np.isreal(time_step) or not time_step > 0:
+                raise ValueError("tke_dissipation_time_step must be None or a positive number")
+            time_step = float(time_step)
+        self.tke_dissipation_time_step = time_step
+        if kw:
+            raise TypeError(f"unexpected keyword arguments {sorted(kw)}")
+
+    @classmethod
+    def dissipation_name(cls, tracers):
+        """the name the user gave the dissipation tracer, or None"""
+        return next((name for name in cls.DISSIPATION_NAMES if name in tuple(tracers)), None)
+
+    def derived_constants(self):
+        """what depends on the coefficients alone, in Python floats: the kernels and the tests' restatement take these bits.  𝕊u₀⁴ is
+        (𝕊u₀ 𝕊u₀) (𝕊u₀ 𝕊u₀)"""
+        sf = self.stability_functions
+        Su0 = sf.Su0
+        return {"Su0": Su0, "Su0_cubed": Su0 * Su0 * Su0, "Su0_fourth_over_sigma_eps": (Su0 * Su0) * (Su0 * Su0) / sf.C_sigma_eps,
+                "minimum_stratification_number": sf.minimum_stratification_number(self.minimum_stratification_number_safety_factor)}
+
+    def c_struct(self):
+        """struct ocn_tke_dissipation"""
+        eq, sf, ls = self.tke_dissipation_equations, self.stability_functions, self.minimum_length_scale
+        source = {name: 0.0 for name in _lib.TKE_DISSIPATION_FIELDS}  # (the coefficients that ConstantStabilityFunctions does not have)
+        for part in (eq, sf, ls):
+            source.update({k: getattr(part, k) for k in part.DEFAULTS})
+        source.update({k: getattr(self, k) for k in self.NUMBERS if k in source})
+        source.update(self.derived_constants())
+        return _lib.CTKEDissipation(*[source[name] for name in _lib.TKE_DISSIPATION_FIELDS], sf.CODE, 0)
+
+    def __repr__(self):  # Base.summary (tke_dissipation_vertical_diffusivity.jl:363-366)
+        return f"TKEDissipationVerticalDiffusivity{{{type(self.time_discretization).__name__}}}"
+
+
 def has_diffusivity_fields(closure):
     """closures of the VerticalFormulation whose κᶜ, κᵘ are (Center, Center, Face) fields that the HydrostaticFreeSurfaceModel computes in
     update_state! (their term and implicit step: csrc/vertical_diffusivity.hip)"""
-    return isinstance(closure, (ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity, CATKEVerticalDiffusivity))
+    return isinstance(closure, (ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity, CATKEVerticalDiffusivity,
+                                TKEDissipationVerticalDiffusivity))
 
 
 class AdvectiveFormulation:
