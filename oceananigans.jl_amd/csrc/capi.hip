@@ -4,6 +4,7 @@
 #include <cstring>
 #include <string>
 
+#include "ocn_buoyancy.h"
 #include "ocn_internal.h"
 
 namespace ocn {
@@ -385,10 +386,8 @@ static int validate_terms(const ocn_grid *grid, const ocn_model_terms *t)
     OCN_REQUIRE((t->closure == 2) == (t->nu_e != nullptr), "nu_e must be given exactly when closure == 2 (AnisotropicMinimumDissipation)");
     OCN_REQUIRE(t->closure != 2 || grid->tz != OCN_FLAT, "AnisotropicMinimumDissipation needs a non-Flat z");
     OCN_REQUIRE(t->buoyancy >= OCN_BUOYANCY_NONE && t->buoyancy <= OCN_BUOYANCY_SEAWATER_S, "unknown buoyancy code %d", t->buoyancy);
-    if (t->buoyancy == OCN_BUOYANCY_TRACER || t->buoyancy == OCN_BUOYANCY_SEAWATER_TS || t->buoyancy == OCN_BUOYANCY_SEAWATER_T)
-        OCN_REQUIRE(t->T != nullptr, "buoyancy formulation %d needs the T (or b) tracer", t->buoyancy);
-    if (t->buoyancy == OCN_BUOYANCY_SEAWATER_TS || t->buoyancy == OCN_BUOYANCY_SEAWATER_S)
-        OCN_REQUIRE(t->S != nullptr, "buoyancy formulation %d needs the S tracer", t->buoyancy);
+    if (buoyancy_reads_T(t->buoyancy)) OCN_REQUIRE(t->T != nullptr, "buoyancy formulation %d needs the T (or b) tracer", t->buoyancy);
+    if (buoyancy_reads_S(t->buoyancy)) OCN_REQUIRE(t->S != nullptr, "buoyancy formulation %d needs the S tracer", t->buoyancy);
     OCN_REQUIRE(!t->pHY || t->buoyancy != OCN_BUOYANCY_NONE, "a hydrostatic pressure anomaly exists only with buoyancy (nonhydrostatic_model.jl:143-158)");
     if (t->advection != OCN_ADVECTION_CENTERED2) return validate_weno(grid);  // UpwindBiased(order=5): same halo / size needs
     int st = validate_grid_any(grid);
@@ -836,9 +835,9 @@ int ocn_compute_smagorinsky_diffusivities(const ocn_grid *grid, const ocn_model_
     if (closure->lilly) {
         const int b = terms->buoyancy;
         OCN_REQUIRE(b >= OCN_BUOYANCY_NONE && b <= OCN_BUOYANCY_SEAWATER_S, "ocn_compute_smagorinsky_diffusivities: unknown buoyancy %d", b);
-        if (b == OCN_BUOYANCY_TRACER || b == OCN_BUOYANCY_SEAWATER_TS || b == OCN_BUOYANCY_SEAWATER_T)
+        if (buoyancy_reads_T(b))
             OCN_REQUIRE(terms->T != nullptr, "ocn_compute_smagorinsky_diffusivities: LillyCoefficient reads N²: T (or b) tracer is NULL");
-        if (b == OCN_BUOYANCY_SEAWATER_TS || b == OCN_BUOYANCY_SEAWATER_S)
+        if (buoyancy_reads_S(b))
             OCN_REQUIRE(terms->S != nullptr, "ocn_compute_smagorinsky_diffusivities: LillyCoefficient reads N²: S tracer is NULL");
     }
     for (int n = 0; n < closure->n_tracers; ++n) {
@@ -938,7 +937,7 @@ int ocn_update_hydrostatic_pressure(const ocn_grid *grid, const ocn_model_terms 
     OCN_REQUIRE(terms != nullptr && pHY != nullptr, "ocn_update_hydrostatic_pressure: null argument");
     OCN_REQUIRE(terms->buoyancy != OCN_BUOYANCY_NONE, "ocn_update_hydrostatic_pressure: buoyancy is nothing");
     if (terms->buoyancy != OCN_BUOYANCY_SEAWATER_S) OCN_REQUIRE(terms->T != nullptr, "T (or b) tracer is NULL");
-    if (terms->buoyancy == OCN_BUOYANCY_SEAWATER_TS || terms->buoyancy == OCN_BUOYANCY_SEAWATER_S) OCN_REQUIRE(terms->S != nullptr, "S tracer is NULL");
+    if (buoyancy_reads_S(terms->buoyancy)) OCN_REQUIRE(terms->S != nullptr, "S tracer is NULL");
     OCN_REQUIRE((grid->tx == OCN_FLAT || grid->Hx >= 1) && (grid->ty == OCN_FLAT || grid->Hy >= 1) && (grid->tz == OCN_FLAT || grid->Hz >= 1),
                 "halo >= 1 required");
     return launch_hydrostatic_pressure(grid, to_dev(*terms), pHY, as_stream(stream));
@@ -952,7 +951,7 @@ int ocn_update_hydrostatic_pressure_range(const ocn_grid *grid, const ocn_model_
     OCN_REQUIRE(terms != nullptr && pHY != nullptr, "ocn_update_hydrostatic_pressure_range: null argument");
     OCN_REQUIRE(terms->buoyancy != OCN_BUOYANCY_NONE, "ocn_update_hydrostatic_pressure_range: buoyancy is nothing");
     if (terms->buoyancy != OCN_BUOYANCY_SEAWATER_S) OCN_REQUIRE(terms->T != nullptr, "T (or b) tracer is NULL");
-    if (terms->buoyancy == OCN_BUOYANCY_SEAWATER_TS || terms->buoyancy == OCN_BUOYANCY_SEAWATER_S) OCN_REQUIRE(terms->S != nullptr, "S tracer is NULL");
+    if (buoyancy_reads_S(terms->buoyancy)) OCN_REQUIRE(terms->S != nullptr, "S tracer is NULL");
     OCN_REQUIRE(grid->Hx >= 1 && grid->Hy >= 1 && (grid->tz == OCN_FLAT || grid->Hz >= 1), "halo >= 1 required");
     OCN_REQUIRE(i_first >= 0 && i_last <= grid->Nx + 1, "ocn_update_hydrostatic_pressure_range: i range %d:%d outside 0:%d", i_first, i_last, grid->Nx + 1);
     const int32_t ir[2] = {i_first, i_last};
@@ -1560,11 +1559,8 @@ int ocn_compute_convective_adjustment_diffusivities(const ocn_grid *grid, const 
     OCN_REQUIRE(terms && closure, "%s: null terms / closure", who);
     OCN_REQUIRE(kappa_c && kappa_u, "%s: null field pointer", who);
     OCN_REQUIRE(kappa_c != kappa_u, "%s: kappa_c and kappa_u are the same array", who);
-    const int b = terms->buoyancy;
-    OCN_REQUIRE(b >= OCN_BUOYANCY_NONE && b <= OCN_BUOYANCY_SEAWATER_S, "%s: unknown buoyancy %d", who, b);
-    if (b == OCN_BUOYANCY_TRACER || b == OCN_BUOYANCY_SEAWATER_TS || b == OCN_BUOYANCY_SEAWATER_T)
-        OCN_REQUIRE(terms->T != nullptr, "%s: the T (or b) tracer is NULL", who);
-    if (b == OCN_BUOYANCY_SEAWATER_TS || b == OCN_BUOYANCY_SEAWATER_S) OCN_REQUIRE(terms->S != nullptr, "%s: the S tracer is NULL", who);
+    st = validate_buoyancy_terms(terms, who);
+    if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(std::isfinite(closure->convective_kappa_z) && std::isfinite(closure->convective_nu_z) &&
                     std::isfinite(closure->background_kappa_z) && std::isfinite(closure->background_nu_z),
                 "%s: the four coefficients must be finite", who);
@@ -1654,8 +1650,6 @@ int ocn_add_biharmonic_fluxes(const ocn_grid *grid, double nu, const double *u, 
 }
 
 // the three entry points of ri_based_diffusivity.hip
-static int validate_ri_buoyancy(const ocn_model_terms *terms, const char *who);
-
 // isopycnal.hip: everything is checked on the host before the first HIP call
 static int validate_isopycnal(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_isopycnal *closure, const char *who)
 {
@@ -1664,7 +1658,7 @@ static int validate_isopycnal(const ocn_grid *grid, const ocn_model_terms *terms
     OCN_REQUIRE(grid->tx == OCN_PERIODIC && grid->ty == OCN_PERIODIC && grid->tz == OCN_BOUNDED,
                 "%s: the grid must be (Periodic, Periodic, Bounded), got topology (%d, %d, %d)", who, grid->tx, grid->ty, grid->tz);
     OCN_REQUIRE(grid->Hx >= 1 && grid->Hy >= 1 && grid->Hz >= 1, "%s: halo >= 1 required", who);
-    st = validate_ri_buoyancy(terms, who);
+    st = validate_buoyancy_terms(terms, who);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(closure, "%s: null closure", who);
     OCN_REQUIRE(std::isfinite(closure->max_slope) && closure->max_slope > 0, "%s: max_slope = %g must be finite and > 0", who, closure->max_slope);
@@ -1735,17 +1729,6 @@ int ocn_add_isopycnal_fluxes(const ocn_grid *grid, const ocn_model_terms *terms,
     return launch_isopycnal_fluxes(grid, terms, closure, n_tracers, kappa_symmetric, kappa_skew, c, Gc, as_stream(stream));
 }
 
-static int validate_ri_buoyancy(const ocn_model_terms *terms, const char *who)
-{
-    OCN_REQUIRE(terms, "%s: null terms", who);
-    const int b = terms->buoyancy;
-    OCN_REQUIRE(b >= OCN_BUOYANCY_NONE && b <= OCN_BUOYANCY_SEAWATER_S, "%s: unknown buoyancy %d", who, b);
-    if (b == OCN_BUOYANCY_TRACER || b == OCN_BUOYANCY_SEAWATER_TS || b == OCN_BUOYANCY_SEAWATER_T)
-        OCN_REQUIRE(terms->T != nullptr, "%s: the T (or b) tracer is NULL", who);
-    if (b == OCN_BUOYANCY_SEAWATER_TS || b == OCN_BUOYANCY_SEAWATER_S) OCN_REQUIRE(terms->S != nullptr, "%s: the S tracer is NULL", who);
-    return OCN_SUCCESS;
-}
-
 static int validate_ri_closure(const ocn_grid *grid, const ocn_ri_based *c, const ocn_bc *top_T, const ocn_bc *top_S, const char *who)
 {
     OCN_REQUIRE(c, "%s: null closure", who);
@@ -1774,7 +1757,7 @@ int ocn_compute_ri_number(const ocn_grid *grid, const ocn_model_terms *terms, co
     const char *who = "ocn_compute_ri_number";
     int st = validate_vertical_diffusivity(grid, who);
     if (st != OCN_SUCCESS) return st;
-    st = validate_ri_buoyancy(terms, who);
+    st = validate_buoyancy_terms(terms, who);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(u && v && Ri, "%s: null field pointer", who);
     return launch_ri_based(0, grid, terms, nullptr, nullptr, nullptr, u, v, nullptr, Ri, nullptr, nullptr, as_stream(stream));
@@ -1786,7 +1769,7 @@ int ocn_compute_ri_based_diffusivities(const ocn_grid *grid, const ocn_model_ter
     const char *who = "ocn_compute_ri_based_diffusivities";
     int st = validate_vertical_diffusivity(grid, who);
     if (st != OCN_SUCCESS) return st;
-    st = validate_ri_buoyancy(terms, who);
+    st = validate_buoyancy_terms(terms, who);
     if (st != OCN_SUCCESS) return st;
     st = validate_ri_closure(grid, closure, top_T, top_S, who);
     if (st != OCN_SUCCESS) return st;
@@ -1802,7 +1785,7 @@ int ocn_compute_ri_based_diffusivities_fused(const ocn_grid *grid, const ocn_mod
     const char *who = "ocn_compute_ri_based_diffusivities_fused";
     int st = validate_vertical_diffusivity(grid, who);
     if (st != OCN_SUCCESS) return st;
-    st = validate_ri_buoyancy(terms, who);
+    st = validate_buoyancy_terms(terms, who);
     if (st != OCN_SUCCESS) return st;
     st = validate_ri_closure(grid, closure, top_T, top_S, who);
     if (st != OCN_SUCCESS) return st;

@@ -20,27 +20,23 @@
 // same march, the multipliers go to a scratch array and the backward sweep follows in the same thread: one launch, the bits of two.
 //
 // Strict build (no FMA contraction, IEEE division and square root), min / max / Bool products / cbrt of ocn_catke.h: bit-identical to
-// tests/catke_numpy.py.
+// tests/catke_numpy.py.  What is shared with the other vertical closures (ocn_buoyancy.h, ocn_tke_columns.h) and what is not: DESIGN.md §5.2s.
 #include <cmath>
 #include <cstddef>
 
+#include "ocn_buoyancy.h"
 #include "ocn_catke.h"
 #include "ocn_ivd.h"
+#include "ocn_tke_columns.h"
 
 namespace ocn {
 
 namespace catke {
 
 using ivd::Spacings;
+using tke::bz;
 
 enum Mode { MODE_DIFFUSIVITIES = 0, MODE_SUBSTEP = 1 };
-
-struct Buoyancy {
-    int kind;
-    double g, alpha, beta;
-    const double *T, *S;  // NULL: a constant, its derivative and its flux are 0
-    ZBc top_T, top_S;     // kind OCN_BC_FLUX, or OCN_BC_DEFAULT: no flux
-};
 
 struct Args {
     const double *zf, *zc;
@@ -58,26 +54,6 @@ struct Args {
     double dtau, chi;
     int solve;
 };
-
-// ∂z_b at a face from the values above and below it (seawater_buoyancy.jl:219-224, buoyancy_tracer.jl:16)
-__device__ __forceinline__ double dz_b(const Buoyancy &b, double T1, double T0, double S1, double S0, double dzf)
-{
-    if (b.kind == OCN_BUOYANCY_NONE) return 0.0;
-    const double dT = b.T ? (T1 - T0) / dzf : 0.0;
-    if (b.kind == OCN_BUOYANCY_TRACER) return dT;
-    const double dS = b.S ? (S1 - S0) / dzf : 0.0;
-    return b.g * (b.alpha * dT - b.beta * dS);
-}
-
-// top_buoyancy_flux (seawater_buoyancy.jl:234-246, buoyancy_tracer.jl:18): T_top, S_top are the tracers in the top cell
-__device__ __forceinline__ double top_buoyancy_flux(const Buoyancy &b, int i, int j, int Nx, double T_top, double S_top)
-{
-    if (b.kind == OCN_BUOYANCY_NONE) return 0.0;
-    const double JT = (b.T && b.top_T.kind == OCN_BC_FLUX) ? bc_condition(b.top_T, i, j, Nx, T_top) : 0.0;
-    if (b.kind == OCN_BUOYANCY_TRACER) return JT;
-    const double JS = (b.S && b.top_S.kind == OCN_BC_FLUX) ? bc_condition(b.top_S, i, j, Nx, S_top) : 0.0;
-    return b.g * (b.alpha * JT - b.beta * JS);
-}
 
 // step and scale (catke_mixing_length.jl:195-202); Ri = ±inf flows through as in Julia
 __device__ __forceinline__ double scale(double Ri, double s_un, double s_lo, double s_hi, double c, double w)
@@ -150,7 +126,7 @@ struct Face {
 };
 
 template <int MODE>
-__global__ __launch_bounds__(256) void catke_columns(GridDev g, Buoyancy b, ocn_catke cl, Args a)
+__global__ __launch_bounds__(256) void catke_columns(GridDev g, SurfaceBuoyancy b, ocn_catke cl, Args a)
 {
     const int i = 1 + blockIdx.x * 64 + threadIdx.x, j = 1 + blockIdx.y * 4 + threadIdx.y;
     if (i > g.Nx || j > g.Ny) return;
@@ -188,7 +164,8 @@ __global__ __launch_bounds__(256) void catke_columns(GridDev g, Buoyancy b, ocn_
         a.kappa_c[of] = 0.0;
     }
     a.kappa_e[of] = 0.0;
-    double beta = 0.0, up_prev = 0.0, prev = 0.0;  // the elimination
+    // the elimination: written out, not tke::eliminate of k-ϵ, which costs this kernel 2 %
+    double beta = 0.0, up_prev = 0.0, prev = 0.0;
     const double tiny = 10 * 2.220446049250313e-16;  // 10 eps(Float64)
     const double ab_alpha = 1.5 + a.chi, ab_beta = 0.5 + a.chi;
 
@@ -247,38 +224,29 @@ __global__ __launch_bounds__(256) void catke_columns(GridDev g, Buoyancy b, ocn_
         if (MODE == MODE_SUBSTEP) {
             // cell k: ℑbzᵃᵃᶜ of its faces k (lo) and k + 1 (hi), a peripheral face replaced by the other
             const bool p_lo = k == 1, p_hi = k == Nz;
-            auto bz = [&](double x_lo, double x_hi) {
-                const double fp = p_hi ? x_lo : x_hi;
-                const double fm = p_lo ? fp : x_lo;
-                return (fp + fm) / 2;
-            };
-            const double N2 = bz(n2_lo, n2_hi);
-            double N2_above;  // ℑbzᵃᵃᶜ at k + 1: faces k + 1 and k + 2
-            {
-                const double fp = (k + 2 >= Nz + 1) ? n2_hi : n2_top;
-                const double fm = (k + 1 >= Nz + 1) ? fp : n2_hi;
-                N2_above = (fp + fm) / 2;
-            }
-            const double Ri = bz(lo.Ri, hi.Ri);
-            const double S2 = 0.5 * (bz(lo.du2[0], hi.du2[0]) + bz(lo.du2[1], hi.du2[1])) +
-                              0.5 * (bz(lo.dv2[0], hi.dv2[0]) + bz(lo.dv2[1], hi.dv2[1]));  // shearᶜᶜᶜ
+            auto bzk = [&](double x_lo, double x_hi) { return bz(x_lo, x_hi, p_lo, p_hi); };
+            const double N2 = bzk(n2_lo, n2_hi);
+            const double N2_above = bz(n2_hi, n2_top, k + 1 >= Nz + 1, k + 2 >= Nz + 1);  // ℑbzᵃᵃᶜ at k + 1: faces k + 1 and k + 2
+            const double Ri = bzk(lo.Ri, hi.Ri);
+            const double S2 = 0.5 * (bzk(lo.du2[0], hi.du2[0]) + bzk(lo.du2[1], hi.du2[1])) +
+                              0.5 * (bzk(lo.dv2[0], hi.dv2[0]) + bzk(lo.dv2[1], hi.dv2[1]));  // shearᶜᶜᶜ
             const double ek = e_lo, w = w_lo, dzc = M.dzC(k);
             const double depth = clip(ztop - zc(k)), height = jmax(dzc / 2, zc(k) - zbot);
             const double lD = dissipation_length(cl, H, w, S2, N2, N2_above, Ri, Jb, depth, height);
             const double omega = ek < 0 ? 1 / cl.negative_tke_damping_time_scale : sqrt(fabs(ek)) / lD;  // dissipation_rate
-            const double wb = bz(lo.wb, hi.wb);  // explicit_buoyancy_flux
+            const double wb = bzk(lo.wb, hi.wb);  // explicit_buoyancy_flux
             const double wb_minus = jmin(0.0, wb), wb_plus = jmax(0.0, wb);
             const double wb_e = bmul(wb_minus / ek, ek > emin);
             const double div_Je = (k == 1 ? -1.0 : 0.0) * cl.C_W_eps * sqrt(clip(ek)) / dzc;  // the bottom cell
             const double L = wb_e - omega + div_Je;
             a.Le[oc + (k - 1) * c3] = L;
-            const double Px0 = (bz(lo.Pn[0], hi.Pn[0]) + bz(lo.Pp[0], hi.Pp[0])) / (2 * dzc);
-            const double Px1 = (bz(lo.Pn[1], hi.Pn[1]) + bz(lo.Pp[1], hi.Pp[1])) / (2 * dzc);
-            const double Py0 = (bz(lo.Qn[0], hi.Qn[0]) + bz(lo.Qp[0], hi.Qp[0])) / (2 * dzc);
-            const double Py1 = (bz(lo.Qn[1], hi.Qn[1]) + bz(lo.Qp[1], hi.Qp[1])) / (2 * dzc);
+            const double Px0 = (bzk(lo.Pn[0], hi.Pn[0]) + bzk(lo.Pp[0], hi.Pp[0])) / (2 * dzc);
+            const double Px1 = (bzk(lo.Pn[1], hi.Pn[1]) + bzk(lo.Pp[1], hi.Pp[1])) / (2 * dzc);
+            const double Py0 = (bzk(lo.Qn[0], hi.Qn[0]) + bzk(lo.Qp[0], hi.Qp[0])) / (2 * dzc);
+            const double Py1 = (bzk(lo.Qn[1], hi.Qn[1]) + bzk(lo.Qp[1], hi.Qp[1])) / (2 * dzc);
             const double P = 0.5 * (Px0 + Px1) + 0.5 * (Py0 + Py1);  // shear_production
-            const double fast = P + wb_plus;                          // (dissipation is implicit: - 0)
             const long long og = oc + (k - 1) * c3;
+            const double fast = P + wb_plus;                          // (dissipation is implicit: - 0)
             const double total = a.Gn[og] + fast;
             const double e_new = ek + a.dtau * (ab_alpha * total - ab_beta * a.Gm[og]);
             a.Gm[og] = total;
@@ -333,7 +301,7 @@ struct PlaneArgs {
     double *Qe;
 };
 
-__global__ __launch_bounds__(256) void surface_buoyancy_flux(GridDev g, Buoyancy b, ocn_catke cl, PlaneArgs a)
+__global__ __launch_bounds__(256) void surface_buoyancy_flux(GridDev g, SurfaceBuoyancy b, ocn_catke cl, PlaneArgs a)
 {
     const int i = 1 + blockIdx.x * 64 + threadIdx.x, j = 1 + blockIdx.y * 4 + threadIdx.y;
     if (i > g.Nx || j > g.Ny) return;
@@ -366,7 +334,7 @@ __global__ __launch_bounds__(256) void surface_buoyancy_flux(GridDev g, Buoyancy
     a.Jb[op] = (Jb + eps * J_star) / (1 + eps);
 }
 
-__global__ __launch_bounds__(256) void top_tke_flux(GridDev g, Buoyancy b, ocn_catke cl, PlaneArgs a)
+__global__ __launch_bounds__(256) void top_tke_flux(GridDev g, SurfaceBuoyancy b, ocn_catke cl, PlaneArgs a)
 {
     const int i = 1 + blockIdx.x * 64 + threadIdx.x, j = 1 + blockIdx.y * 4 + threadIdx.y;
     if (i > g.Nx || j > g.Ny) return;
@@ -382,43 +350,19 @@ __global__ __launch_bounds__(256) void top_tke_flux(GridDev g, Buoyancy b, ocn_c
     a.Qe[(i - 1) + (long long)g.Nx * (j - 1)] = -cl.C_W_ustar * (u_star * u_star * u_star) - cl.C_W_wdelta * w_delta3;
 }
 
-static ZBc flux_or_default(const ocn_bc *bc)
-{
-    if (bc && bc->kind == OCN_BC_FLUX) return ZBc{OCN_BC_FLUX, bc->value, bc->coeff, bc->values};
-    return ZBc{OCN_BC_DEFAULT, 0.0, 0.0, nullptr};
-}
-
-static Buoyancy make_buoyancy(const ocn_model_terms *terms, const ocn_bc *top_T, const ocn_bc *top_S)
-{
-    Buoyancy b{terms->buoyancy, terms->g, terms->alpha, terms->beta, nullptr, nullptr, flux_or_default(top_T), flux_or_default(top_S)};
-    if (b.kind == OCN_BUOYANCY_TRACER || b.kind == OCN_BUOYANCY_SEAWATER_TS || b.kind == OCN_BUOYANCY_SEAWATER_T) b.T = terms->T;
-    if (b.kind == OCN_BUOYANCY_SEAWATER_TS || b.kind == OCN_BUOYANCY_SEAWATER_S) b.S = terms->S;
-    return b;
-}
-
 // ---- argument checks: nothing here touches a device -----------------------------------------------------------------------------------
 static int validate_grid_and_closure(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_catke *c, const char *who)
 {
-    int st = validate_grid_any(grid);
+    int st = tke::validate_tke_grid(grid, who);
     if (st != OCN_SUCCESS) return st;
-    OCN_REQUIRE(grid->tx == OCN_PERIODIC && grid->ty == OCN_PERIODIC && grid->tz == OCN_BOUNDED,
-                "%s: needs a (Periodic, Periodic, Bounded) grid on one GPU, got topology (%d, %d, %d)", who, grid->tx, grid->ty, grid->tz);
-    OCN_REQUIRE(grid->Hx >= 1 && grid->Hy >= 1 && grid->Hz >= 1, "%s: halo >= 1 required", who);
-    OCN_REQUIRE(grid->Nz >= 2, "%s: Nz = %d: at least two layers are needed", who, grid->Nz);
-    OCN_REQUIRE(std::isfinite(grid->Lz) && grid->Lz > 0, "%s: grid.Lz = %g must be finite and > 0", who, grid->Lz);
-    OCN_REQUIRE(terms, "%s: null terms", who);
-    const int b = terms->buoyancy;
-    OCN_REQUIRE(b >= OCN_BUOYANCY_NONE && b <= OCN_BUOYANCY_SEAWATER_S, "%s: unknown buoyancy %d", who, b);
-    if (b == OCN_BUOYANCY_TRACER || b == OCN_BUOYANCY_SEAWATER_TS || b == OCN_BUOYANCY_SEAWATER_T)
-        OCN_REQUIRE(terms->T != nullptr, "%s: the T (or b) tracer is NULL", who);
-    if (b == OCN_BUOYANCY_SEAWATER_TS || b == OCN_BUOYANCY_SEAWATER_S) OCN_REQUIRE(terms->S != nullptr, "%s: the S tracer is NULL", who);
+    st = validate_buoyancy_terms(terms, who);
+    if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(c, "%s: null closure", who);
     // every member in front of the three maxima is a coefficient (the struct holds doubles only)
     constexpr size_t n_coefficients = offsetof(ocn_catke, maximum_tracer_diffusivity) / sizeof(double);
     static_assert(offsetof(ocn_catke, C_s) == 0 && sizeof(ocn_catke) % sizeof(double) == 0, "ocn_catke: doubles only, coefficients first");
-    const double *coefficients = reinterpret_cast<const double *>(c);
-    for (size_t q = 0; q < n_coefficients; ++q)
-        OCN_REQUIRE(std::isfinite(coefficients[q]), "%s: coefficient %d of the closure is not finite", who, (int)q);
+    st = tke::validate_finite_coefficients(reinterpret_cast<const double *>(c), n_coefficients, who);
+    if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(!std::isnan(c->maximum_tracer_diffusivity) && !std::isnan(c->maximum_tke_diffusivity) && !std::isnan(c->maximum_viscosity),
                 "%s: a maximum is a NaN", who);
     OCN_REQUIRE(std::isfinite(c->minimum_tke) && std::isfinite(c->minimum_convective_buoyancy_flux) &&
@@ -426,19 +370,6 @@ static int validate_grid_and_closure(const ocn_grid *grid, const ocn_model_terms
                 "%s: minimum_tke, minimum_convective_buoyancy_flux and negative_tke_damping_time_scale must be finite", who);
     return OCN_SUCCESS;
 }
-
-static int validate_tops(const ocn_bc *const *tops, const char *const *names, int n, const char *who)
-{
-    for (int q = 0; q < n; ++q) {
-        if (!tops[q]) continue;
-        OCN_REQUIRE(tops[q]->kind == OCN_BC_DEFAULT || tops[q]->kind == OCN_BC_FLUX,
-                    "%s: the top condition of %s has kind %d: only a Flux (or the default, no flux) is a surface flux", who, names[q],
-                    tops[q]->kind);
-    }
-    return OCN_SUCCESS;
-}
-
-static dim3 column_blocks(const ocn_grid *grid) { return dim3((grid->Nx + 63) / 64, (grid->Ny + 3) / 4, 1); }
 
 }  // namespace catke
 
@@ -464,14 +395,14 @@ int ocn_compute_catke_surface_buoyancy_flux(const ocn_grid *grid, const ocn_mode
     if (st != OCN_SUCCESS) return st;
     const ocn_bc *tops[2] = {top_T, top_S};
     const char *names[2] = {"the T (or b) tracer", "the S tracer"};
-    st = catke::validate_tops(tops, names, 2, who);
+    st = tke::validate_top_fluxes(tops, names, 2, who);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(znodes_f && znodes_c && u && v && e && Jb, "%s: null pointer", who);
     OCN_REQUIRE(std::isfinite(dt) && dt >= 0, "%s: dt = %g must be finite and >= 0", who, dt);
     catke::PlaneArgs a{};
     a.zf = znodes_f; a.zc = znodes_c; a.Lz = grid->Lz; a.u = u; a.v = v; a.e = e; a.Jb = Jb; a.dt = dt;
-    hipLaunchKernelGGL(catke::surface_buoyancy_flux, catke::column_blocks(grid), dim3(64, 4, 1), 0, as_stream(stream), to_dev(*grid),
-                       catke::make_buoyancy(terms, top_T, top_S), *closure, a);
+    hipLaunchKernelGGL(catke::surface_buoyancy_flux, tke::column_blocks(grid), dim3(64, 4, 1), 0, as_stream(stream), to_dev(*grid),
+                       make_surface_buoyancy(terms, top_T, top_S), *closure, a);
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
 }
@@ -485,15 +416,15 @@ int ocn_compute_catke_top_tke_flux(const ocn_grid *grid, const ocn_model_terms *
     if (st != OCN_SUCCESS) return st;
     const ocn_bc *tops[4] = {top_u, top_v, top_T, top_S};
     const char *names[4] = {"u", "v", "the T (or b) tracer", "the S tracer"};
-    st = catke::validate_tops(tops, names, 4, who);
+    st = tke::validate_top_fluxes(tops, names, 4, who);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(u && v && Qe, "%s: null pointer", who);
     catke::PlaneArgs a{};
     a.u = u; a.v = v; a.Qe = Qe; a.Lz = grid->Lz;
-    a.top_u = catke::flux_or_default(top_u);
-    a.top_v = catke::flux_or_default(top_v);
-    hipLaunchKernelGGL(catke::top_tke_flux, catke::column_blocks(grid), dim3(64, 4, 1), 0, as_stream(stream), to_dev(*grid),
-                       catke::make_buoyancy(terms, top_T, top_S), *closure, a);
+    a.top_u = flux_or_default(top_u);
+    a.top_v = flux_or_default(top_v);
+    hipLaunchKernelGGL(catke::top_tke_flux, tke::column_blocks(grid), dim3(64, 4, 1), 0, as_stream(stream), to_dev(*grid),
+                       make_surface_buoyancy(terms, top_T, top_S), *closure, a);
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
 }
@@ -511,8 +442,8 @@ int ocn_compute_catke_diffusivities(const ocn_grid *grid, const ocn_model_terms 
     catke::Args a{};
     a.zf = znodes_f; a.zc = znodes_c; a.Lz = grid->Lz; a.u = u; a.v = v; a.e_in = e; a.Jb = Jb;
     a.kappa_u = kappa_u; a.kappa_c = kappa_c; a.kappa_e = kappa_e;
-    hipLaunchKernelGGL(catke::catke_columns<catke::MODE_DIFFUSIVITIES>, catke::column_blocks(grid), dim3(64, 4, 1), 0, as_stream(stream),
-                       to_dev(*grid), catke::make_buoyancy(terms, nullptr, nullptr), *closure, a);
+    hipLaunchKernelGGL(catke::catke_columns<catke::MODE_DIFFUSIVITIES>, tke::column_blocks(grid), dim3(64, 4, 1), 0, as_stream(stream),
+                       to_dev(*grid), make_surface_buoyancy(terms, nullptr, nullptr), *closure, a);
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
 }
@@ -538,8 +469,8 @@ int ocn_catke_substep_tke(const ocn_grid *grid, const ocn_model_terms *terms, co
     a.zf = znodes_f; a.zc = znodes_c; a.Lz = grid->Lz; a.u = u_next; a.v = v_next; a.u_prev = u_prev; a.v_prev = v_prev; a.e = e; a.Jb = Jb;
     a.ku_in = kappa_u; a.kc_in = kappa_c; a.kappa_e = kappa_e; a.Le = Le; a.Gn = Gn_e; a.Gm = Gm_e; a.t = scratch;
     a.dtau = dtau; a.chi = chi; a.solve = solve != 0;
-    hipLaunchKernelGGL(catke::catke_columns<catke::MODE_SUBSTEP>, catke::column_blocks(grid), dim3(64, 4, 1), 0, as_stream(stream),
-                       to_dev(*grid), catke::make_buoyancy(terms, nullptr, nullptr), *closure, a);
+    hipLaunchKernelGGL(catke::catke_columns<catke::MODE_SUBSTEP>, tke::column_blocks(grid), dim3(64, 4, 1), 0, as_stream(stream),
+                       to_dev(*grid), make_surface_buoyancy(terms, nullptr, nullptr), *closure, a);
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
 }

@@ -22,7 +22,9 @@
 // Division-bound rather than bandwidth-bound (a strict IEEE division per derivative): keeping the derivatives in LDS instead of the raw
 // planes is what makes every one of them be formed once per point rather than once per face that reads it.
 // One strict build (no FMA contraction, IEEE division): bit-identical to tests/isopycnal_numpy.py.  Julia's min, max and ifelse are
-// comparisons and selects; the 0 / 0 and x / 0 that the reference selects away are computed and selected away here too.
+// comparisons and selects; the 0 / 0 and x / 0 that the reference selects away are computed and selected away here too.  The buoyancy is
+// that of ocn_buoyancy.h.
+#include "ocn_buoyancy.h"
 #include "ocn_ivd.h"
 
 namespace ocn {
@@ -31,24 +33,10 @@ namespace iso {
 
 using ivd::Spacings;
 
-struct Buoyancy {
-    int kind;
-    double g, alpha, beta;
-    const double *T, *S;  // NULL: a constant, its derivatives are 0
-};
-
 struct Slopes {
     double max_slope2;  // slope_limiter.max_slope^2
     double minimum_bz;  // isopycnal_tensor.minimum_bz
 };
-
-// a derivative of the buoyancy from the same derivative of T (or b) and S   (buoyancy_tracer.jl:14-16, seawater_buoyancy.jl:167-224)
-__device__ __forceinline__ double b_of(const Buoyancy &b, double dT, double dS)
-{
-    if (b.kind == OCN_BUOYANCY_NONE) return 0.0;
-    if (b.kind == OCN_BUOYANCY_TRACER) return dT;
-    return b.g * (b.alpha * dT - b.beta * dS);
-}
 
 // Julia's max(a, b) and min(1, x) for Float64: a NaN propagates, max(-0.0, 0.0) is 0.0
 __device__ __forceinline__ double jl_max(double a, double b)
@@ -374,14 +362,6 @@ __global__ __launch_bounds__(NT) void isopycnal_fluxes(GridDev g, Buoyancy b, Sl
     }
 }
 
-static Buoyancy make_buoyancy(const ocn_model_terms *terms)
-{
-    Buoyancy b{terms->buoyancy, terms->g, terms->alpha, terms->beta, nullptr, nullptr};
-    if (b.kind == OCN_BUOYANCY_TRACER || b.kind == OCN_BUOYANCY_SEAWATER_TS || b.kind == OCN_BUOYANCY_SEAWATER_T) b.T = terms->T;
-    if (b.kind == OCN_BUOYANCY_SEAWATER_TS || b.kind == OCN_BUOYANCY_SEAWATER_S) b.S = terms->S;
-    return b;
-}
-
 template <int NTR>
 static void launch_fluxes(const GridDev &gd, const Buoyancy &b, const Slopes &sl, int nt, const double *ks, const double *kw,
                           const double *const *c, double *const *G, dim3 blocks, hipStream_t stream)
@@ -414,7 +394,7 @@ int launch_isopycnal_diffusivities(const ocn_grid *grid, const ocn_model_terms *
                                    double *eps_R33, double *ue, double *ve, double *we, int n_kz, const double *kappa_symmetric,
                                    double *const *kz, hipStream_t stream)
 {
-    const iso::Buoyancy b = iso::make_buoyancy(terms);
+    const Buoyancy b = make_buoyancy(terms);
     const iso::Slopes sl{closure->max_slope * closure->max_slope, closure->minimum_bz};
     iso::DiffArgs a{};
     a.kappa_skew = kappa_skew;
@@ -457,7 +437,7 @@ int launch_isopycnal_fluxes(const ocn_grid *grid, const ocn_model_terms *terms, 
                             const double *kappa_symmetric, const double *kappa_skew, const double *const *c, double *const *Gc,
                             hipStream_t stream)
 {
-    const iso::Buoyancy b = iso::make_buoyancy(terms);
+    const Buoyancy b = make_buoyancy(terms);
     const iso::Slopes sl{closure->max_slope * closure->max_slope, closure->minimum_bz};
     const GridDev gd = to_dev(*grid);
     const dim3 blocks((grid->Nx + iso::TX - 1) / iso::TX, (grid->Ny + iso::TY - 1) / iso::TY, (grid->Nz + iso::PLANES - 1) / iso::PLANES);

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "ocn_buoyancy.h"
 #include "ocn_internal.h"
 
 using ocn::GridDev;
@@ -403,8 +404,7 @@ static int model_driver_create(ocn_model_driver_t *out, const ocn_grid *grid, co
                 "ocn_model_driver_create: unknown closure %d / buoyancy %d", t.closure, t.buoyancy);
     OCN_REQUIRE(desc->tracer_T >= -1 && desc->tracer_T < desc->n_tracers && desc->tracer_S >= -1 && desc->tracer_S < desc->n_tracers,
                 "ocn_model_driver_create: tracer_T / tracer_S outside the tracer list");
-    const bool needT = t.buoyancy == OCN_BUOYANCY_TRACER || t.buoyancy == OCN_BUOYANCY_SEAWATER_TS || t.buoyancy == OCN_BUOYANCY_SEAWATER_T;
-    const bool needS = t.buoyancy == OCN_BUOYANCY_SEAWATER_TS || t.buoyancy == OCN_BUOYANCY_SEAWATER_S;
+    const bool needT = ocn::buoyancy_reads_T(t.buoyancy), needS = ocn::buoyancy_reads_S(t.buoyancy);
     OCN_REQUIRE((!needT || desc->tracer_T >= 0) && (!needS || desc->tracer_S >= 0), "ocn_model_driver_create: buoyancy %d needs its tracer(s)",
                 t.buoyancy);
     OCN_REQUIRE(desc->pHY == t.pHY, "ocn_model_driver_create: desc->pHY must equal desc->terms.pHY");

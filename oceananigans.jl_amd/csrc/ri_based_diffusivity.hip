@@ -16,7 +16,8 @@
 // only needed locally: MODE_FUSED computes it, stores it and goes on to the diffusivities: 72 B per cell (u, v, T, S read, κᶜ, κᵘ read and
 // written, Ri written) in one launch.  All three modes are one template and call the same inline functions: the fused launch equals the two
 // launches bit for bit.  Strict build (no FMA contraction, IEEE division), no math library (ocn_taper.h): bit-identical to
-// tests/ri_based_numpy.py.
+// tests/ri_based_numpy.py.  The buoyancy is that of ocn_buoyancy.h.
+#include "ocn_buoyancy.h"
 #include "ocn_ivd.h"
 #include "ocn_taper.h"
 
@@ -28,13 +29,6 @@ using ivd::Spacings;
 
 enum Mode { MODE_RI = 0, MODE_DIFFUSIVITIES = 1, MODE_FUSED = 2 };
 
-struct Buoyancy {
-    int kind;
-    double g, alpha, beta;
-    const double *T, *S;  // NULL: a constant, its derivative and its flux are 0
-    ZBc top_T, top_S;     // kind OCN_BC_FLUX, or OCN_BC_DEFAULT: no flux
-};
-
 struct Args {
     const double *u, *v;  // MODE_RI, MODE_FUSED
     const double *ri_in;  // MODE_DIFFUSIVITIES
@@ -42,21 +36,11 @@ struct Args {
     double *kappa_c, *kappa_u;
 };
 
-// ∂z_b at face k from the values above and below it (seawater_buoyancy.jl:219-224, buoyancy_tracer.jl:16)
-__device__ __forceinline__ double dz_b(const Buoyancy &b, double T1, double T0, double S1, double S0, double dzf)
-{
-    if (b.kind == OCN_BUOYANCY_NONE) return 0.0;
-    const double dT = b.T ? (T1 - T0) / dzf : 0.0;
-    if (b.kind == OCN_BUOYANCY_TRACER) return dT;
-    const double dS = b.S ? (S1 - S0) / dzf : 0.0;
-    return b.g * (b.alpha * dT - b.beta * dS);
-}
-
 // Julia's min(a, m) for a maximum m that is no NaN: a NaN propagates
 __device__ __forceinline__ double min_with(double a, double m) { return a != a ? a : (a < m ? a : m); }
 
 template <int MODE>
-__global__ __launch_bounds__(256) void ri_based_columns(GridDev g, Buoyancy b, ocn_ri_based cl, Args a)
+__global__ __launch_bounds__(256) void ri_based_columns(GridDev g, SurfaceBuoyancy b, ocn_ri_based cl, Args a)
 {
     const int i = 1 + blockIdx.x * 64 + threadIdx.x, j = 1 + blockIdx.y * 4 + threadIdx.y;
     if (i > g.Nx || j > g.Ny) return;
@@ -78,7 +62,7 @@ __global__ __launch_bounds__(256) void ri_based_columns(GridDev g, Buoyancy b, o
         u0 = up[0]; u1 = up[1]; v0 = vp[0]; v1 = vp[v2];
     }
     double Jb = 0.0;
-    if (MODE != MODE_RI && b.kind != OCN_BUOYANCY_NONE) {  // top_buoyancy_flux: getbc of the top conditions, 0 for no flux
+    if (MODE != MODE_RI && b.kind != OCN_BUOYANCY_NONE) {  // top_buoyancy_flux of ocn_buoyancy.h, the top cell read only under a Flux condition
         const double JT = (Tp && b.top_T.kind == OCN_BC_FLUX) ? bc_condition(b.top_T, i, j, g.Nx, Tp[Nz * c3]) : 0.0;
         if (b.kind == OCN_BUOYANCY_TRACER) {
             Jb = JT;
@@ -133,17 +117,6 @@ __global__ __launch_bounds__(256) void ri_based_columns(GridDev g, Buoyancy b, o
     }
 }
 
-static Buoyancy make_buoyancy(const ocn_model_terms *terms, const ocn_bc *top_T, const ocn_bc *top_S)
-{
-    Buoyancy b{terms->buoyancy, terms->g, terms->alpha, terms->beta, nullptr, nullptr, ZBc{OCN_BC_DEFAULT, 0.0, 0.0, nullptr},
-               ZBc{OCN_BC_DEFAULT, 0.0, 0.0, nullptr}};
-    if (b.kind == OCN_BUOYANCY_TRACER || b.kind == OCN_BUOYANCY_SEAWATER_TS || b.kind == OCN_BUOYANCY_SEAWATER_T) b.T = terms->T;
-    if (b.kind == OCN_BUOYANCY_SEAWATER_TS || b.kind == OCN_BUOYANCY_SEAWATER_S) b.S = terms->S;
-    if (top_T && top_T->kind == OCN_BC_FLUX) b.top_T = ZBc{OCN_BC_FLUX, top_T->value, top_T->coeff, top_T->values};
-    if (top_S && top_S->kind == OCN_BC_FLUX) b.top_S = ZBc{OCN_BC_FLUX, top_S->value, top_S->coeff, top_S->values};
-    return b;
-}
-
 }  // namespace rbd
 
 // the callers have validated the grid (z Bounded, x and y not Flat, halos >= 1), the closure and the pointers.
@@ -152,7 +125,7 @@ int launch_ri_based(int mode, const ocn_grid *grid, const ocn_model_terms *terms
                     const ocn_bc *top_S, const double *u, const double *v, const double *ri_in, double *ri_out, double *kappa_c,
                     double *kappa_u, hipStream_t stream)
 {
-    const rbd::Buoyancy b = rbd::make_buoyancy(terms, top_T, top_S);
+    const SurfaceBuoyancy b = make_surface_buoyancy(terms, top_T, top_S);
     const rbd::Args a{u, v, ri_in, ri_out, kappa_c, kappa_u};
     const ocn_ri_based cl = closure ? *closure : ocn_ri_based{};
     const GridDev gd = to_dev(*grid);

@@ -18,12 +18,15 @@
 // arrays and the two backward sweeps follow in the same thread.
 //
 // Strict build (no FMA contraction, IEEE division and square root), min / max / Bool products of ocn_catke.h: bit-identical to
-// tests/tke_dissipation_numpy.py.
+// tests/tke_dissipation_numpy.py.  What is shared with the other vertical closures (ocn_buoyancy.h, ocn_tke_columns.h) and what is not:
+// DESIGN.md §5.2s.
 #include <cmath>
 #include <cstddef>
 
+#include "ocn_buoyancy.h"
 #include "ocn_catke.h"
 #include "ocn_ivd.h"
+#include "ocn_tke_columns.h"
 
 namespace ocn {
 
@@ -33,14 +36,9 @@ using catke::bmul;
 using catke::jmax;
 using catke::jmin;
 using ivd::Spacings;
+using tke::bz;
 
 enum Mode { MODE_DIFFUSIVITIES = 0, MODE_SUBSTEP = 1 };
-
-struct Buoyancy {
-    int kind;
-    double g, alpha, beta;
-    const double *T, *S;  // NULL: a constant, its derivative is 0
-};
 
 struct Args {
     double Lz;
@@ -57,16 +55,6 @@ struct Args {
     double dtau, chi;
     int solve;
 };
-
-// ∂z_b at a face from the values above and below it (seawater_buoyancy.jl:219-224, buoyancy_tracer.jl:16)
-__device__ __forceinline__ double dz_b(const Buoyancy &b, double T1, double T0, double S1, double S0, double dzf)
-{
-    if (b.kind == OCN_BUOYANCY_NONE) return 0.0;
-    const double dT = b.T ? (T1 - T0) / dzf : 0.0;
-    if (b.kind == OCN_BUOYANCY_TRACER) return dT;
-    const double dS = b.S ? (S1 - S0) / dzf : 0.0;
-    return b.g * (b.alpha * dT - b.beta * dS);
-}
 
 // Julia's clamp(x, lo, hi) = ifelse(x > hi, hi, ifelse(x < lo, lo, x)): a NaN x comes back, a NaN bound never binds
 __device__ __forceinline__ double jclamp(double x, double lo, double hi) { return x > hi ? hi : (x < lo ? lo : x); }
@@ -90,9 +78,7 @@ __device__ __forceinline__ Cell make_cell(const ocn_tke_dissipation &cl, double 
     c.eps = eps;
     c.es = jmax(cl.minimum_tke, e);
     const double a_lo = jmax(cl.minimum_buoyancy_frequency, n2_lo), a_hi = jmax(cl.minimum_buoyancy_frequency, n2_hi);
-    const double fp = p_hi ? a_lo : a_hi;
-    const double fm = p_lo ? fp : a_lo;
-    const double N2p = (fp + fm) / 2;
+    const double N2p = bz(a_lo, a_hi, p_lo, p_hi);
     const double lst = cl.C_N * sqrt(c.es / N2p);
     const double lmin = jmin(Lz, lst);
     const double s = sqrt(c.es);
@@ -153,34 +139,6 @@ struct Face {
     double ke, keps;                    // κᵉ, κᵋ (masked)
 };
 
-// one unknown of the two tridiagonal systems: the state of its elimination
-struct Elimination {
-    double beta, up_prev, prev;
-};
-
-// row k of (1 - Δτ ∂z κ ∂z - Δτ L) c = c (the rows of ocn_ivd.h / catke.hip); returns the value left in cell k, the multiplier goes to *t
-__device__ __forceinline__ double eliminate(Elimination &s, int k, int Nz, double dtau, double k_lo, double k_hi, double L, double rhs, double dzc,
-                                            double dzf_lo, double dzf_hi, double *t)
-{
-    const double tiny = 10 * 2.220446049250313e-16;                          // 10 eps(Float64)
-    const double low = k == 1 ? 0.0 : -dtau * k_lo / (dzc * dzf_lo);         // ivd_lower_diagonal(k - 1)
-    const double du = -dtau * k_hi / (dzc * dzf_hi);                         // ivd_upper_diagonal(k)
-    const double upk = k > Nz - 1 ? 0.0 : du;
-    const double diag = 1.0 - dtau * L - upk - low;
-    if (k == 1) {
-        s.beta = diag;
-        s.prev = rhs / s.beta;
-    } else {
-        const double m = s.up_prev / s.beta;
-        s.beta = diag - low * m;
-        *t = m;
-        const double star = (rhs - low * s.prev) / s.beta;
-        s.prev = fabs(s.beta) > tiny ? star : rhs;
-    }
-    s.up_prev = upk;
-    return s.prev;
-}
-
 template <int MODE, int KIND>
 __global__ __launch_bounds__(256) void tke_dissipation_columns(GridDev g, Buoyancy b, ocn_tke_dissipation cl, Args a)
 {
@@ -220,7 +178,7 @@ __global__ __launch_bounds__(256) void tke_dissipation_columns(GridDev g, Buoyan
     }
     a.kappa_e[of] = 0.0;
     a.kappa_eps[of] = 0.0;
-    Elimination se{}, sp{};
+    tke::Elimination se{}, sp{};
     const double ab_alpha = 1.5 + a.chi, ab_beta = 0.5 + a.chi;
     const long long t2 = (long long)g.Nx * g.Ny, ot = (i - 1) + (long long)g.Nx * (j - 1);
 
@@ -272,16 +230,12 @@ __global__ __launch_bounds__(256) void tke_dissipation_columns(GridDev g, Buoyan
         if (MODE == MODE_SUBSTEP) {
             // cell k: ℑbzᵃᵃᶜ of its faces k (lo) and k + 1 (hi), a peripheral face replaced by the other
             const bool p_lo = k == 1, p_hi = k == Nz;
-            auto bz = [&](double x_lo, double x_hi) {
-                const double fp = p_hi ? x_lo : x_hi;
-                const double fm = p_lo ? fp : x_lo;
-                return (fp + fm) / 2;
-            };
+            auto bzk = [&](double x_lo, double x_hi) { return bz(x_lo, x_hi, p_lo, p_hi); };
             const double ek = c_lo.e, pk = c_lo.eps, es = c_lo.es, dzc = M.dzC(k);
             const double omega_star = c_lo.epss / es;
             const double omega_e = ek < 0 ? cl.negative_tke_damping_time_scale : omega_star;  // (the time scale itself, as in the reference)
             const double omega_eps = pk / es;
-            const double wb = bz(lo.wb, hi.wb);  // explicit_buoyancy_flux
+            const double wb = bzk(lo.wb, hi.wb);  // explicit_buoyancy_flux
             const double wb_minus = jmin(wb, 0.0), wb_plus = jmax(wb, 0.0);
             const double wb_e = bmul(wb_minus / ek, ek > emin);
             const double N2 = 0.5 * (n2_lo + n2_hi);  // the plain ℑzᵃᵃᶜ(∂z_b): faces 1 and Nz + 1 from the z halos of the tracers
@@ -293,10 +247,10 @@ __global__ __launch_bounds__(256) void tke_dissipation_columns(GridDev g, Buoyan
             const long long og = oc + (k - 1) * c3;
             a.Le[og] = L_e;
             a.Leps[og] = L_eps;
-            const double Px0 = (bz(lo.Pn[0], hi.Pn[0]) + bz(lo.Pp[0], hi.Pp[0])) / (2 * dzc);
-            const double Px1 = (bz(lo.Pn[1], hi.Pn[1]) + bz(lo.Pp[1], hi.Pp[1])) / (2 * dzc);
-            const double Py0 = (bz(lo.Qn[0], hi.Qn[0]) + bz(lo.Qp[0], hi.Qp[0])) / (2 * dzc);
-            const double Py1 = (bz(lo.Qn[1], hi.Qn[1]) + bz(lo.Qp[1], hi.Qp[1])) / (2 * dzc);
+            const double Px0 = (bzk(lo.Pn[0], hi.Pn[0]) + bzk(lo.Pp[0], hi.Pp[0])) / (2 * dzc);
+            const double Px1 = (bzk(lo.Pn[1], hi.Pn[1]) + bzk(lo.Pp[1], hi.Pp[1])) / (2 * dzc);
+            const double Py0 = (bzk(lo.Qn[0], hi.Qn[0]) + bzk(lo.Qp[0], hi.Qp[0])) / (2 * dzc);
+            const double Py1 = (bzk(lo.Qn[1], hi.Qn[1]) + bzk(lo.Qp[1], hi.Qp[1])) / (2 * dzc);
             const double P = 0.5 * (Px0 + Px1) + 0.5 * (Py0 + Py1);  // shear_production
             const double total_e = a.Gn_e[og] + (P + wb_plus);
             const double total_eps = a.Gn_eps[og] + omega_eps * (cl.C_P_eps * P + Cb_wb_plus);
@@ -310,8 +264,8 @@ __global__ __launch_bounds__(256) void tke_dissipation_columns(GridDev g, Buoyan
             } else {
                 const double dzf_lo = M.dzF(k), dzf_hi = M.dzF(k + 1);
                 const long long o = ot + t2 * (k - 1);
-                a.e[og] = eliminate(se, k, Nz, a.dtau, lo.ke, hi.ke, L_e, e_new, dzc, dzf_lo, dzf_hi, a.t_e + o);
-                a.eps[og] = eliminate(sp, k, Nz, a.dtau, lo.keps, hi.keps, L_eps, eps_new, dzc, dzf_lo, dzf_hi, a.t_eps + o);
+                a.e[og] = tke::eliminate(se, k, Nz, a.dtau, lo.ke, hi.ke, L_e, e_new, dzc, dzf_lo, dzf_hi, a.t_e + o);
+                a.eps[og] = tke::eliminate(sp, k, Nz, a.dtau, lo.keps, hi.keps, L_eps, eps_new, dzc, dzf_lo, dzf_hi, a.t_eps + o);
             }
         }
         lo = hi;
@@ -357,38 +311,18 @@ __global__ __launch_bounds__(256) void top_fluxes(GridDev g, ocn_tke_dissipation
     a.Qeps[op] = -cl.Su0_fourth_over_sigma_eps * (es * es) / (d + l_r);
 }
 
-static ZBc flux_or_default(const ocn_bc *bc)
-{
-    if (bc && bc->kind == OCN_BC_FLUX) return ZBc{OCN_BC_FLUX, bc->value, bc->coeff, bc->values};
-    return ZBc{OCN_BC_DEFAULT, 0.0, 0.0, nullptr};
-}
-
-static Buoyancy make_buoyancy(const ocn_model_terms *terms)
-{
-    Buoyancy b{terms->buoyancy, terms->g, terms->alpha, terms->beta, nullptr, nullptr};
-    if (b.kind == OCN_BUOYANCY_TRACER || b.kind == OCN_BUOYANCY_SEAWATER_TS || b.kind == OCN_BUOYANCY_SEAWATER_T) b.T = terms->T;
-    if (b.kind == OCN_BUOYANCY_SEAWATER_TS || b.kind == OCN_BUOYANCY_SEAWATER_S) b.S = terms->S;
-    return b;
-}
-
 // ---- argument checks: nothing here touches a device -----------------------------------------------------------------------------------
 static int validate_grid_and_closure(const ocn_grid *grid, const ocn_tke_dissipation *c, const char *who)
 {
-    int st = validate_grid_any(grid);
+    int st = tke::validate_tke_grid(grid, who);
     if (st != OCN_SUCCESS) return st;
-    OCN_REQUIRE(grid->tx == OCN_PERIODIC && grid->ty == OCN_PERIODIC && grid->tz == OCN_BOUNDED,
-                "%s: needs a (Periodic, Periodic, Bounded) grid on one GPU, got topology (%d, %d, %d)", who, grid->tx, grid->ty, grid->tz);
-    OCN_REQUIRE(grid->Hx >= 1 && grid->Hy >= 1 && grid->Hz >= 1, "%s: halo >= 1 required", who);
-    OCN_REQUIRE(grid->Nz >= 2, "%s: Nz = %d: at least two layers are needed", who, grid->Nz);
-    OCN_REQUIRE(std::isfinite(grid->Lz) && grid->Lz > 0, "%s: grid.Lz = %g must be finite and > 0", who, grid->Lz);
     OCN_REQUIRE(c, "%s: null closure", who);
     // every member in front of the four maxima is a coefficient or a constant derived from coefficients (doubles only up to there)
     constexpr size_t n_coefficients = offsetof(ocn_tke_dissipation, maximum_tracer_diffusivity) / sizeof(double);
     static_assert(offsetof(ocn_tke_dissipation, C_eps_eps) == 0 && offsetof(ocn_tke_dissipation, maximum_tracer_diffusivity) % sizeof(double) == 0,
                   "ocn_tke_dissipation: coefficients first, doubles");
-    const double *coefficients = reinterpret_cast<const double *>(c);
-    for (size_t q = 0; q < n_coefficients; ++q)
-        OCN_REQUIRE(std::isfinite(coefficients[q]), "%s: coefficient %d of the closure is not finite", who, (int)q);
+    st = tke::validate_finite_coefficients(reinterpret_cast<const double *>(c), n_coefficients, who);
+    if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(!std::isnan(c->maximum_tracer_diffusivity) && !std::isnan(c->maximum_tke_diffusivity) &&
                     !std::isnan(c->maximum_dissipation_diffusivity) && !std::isnan(c->maximum_viscosity),
                 "%s: a maximum is a NaN", who);
@@ -399,28 +333,15 @@ static int validate_grid_and_closure(const ocn_grid *grid, const ocn_tke_dissipa
     return OCN_SUCCESS;
 }
 
-static int validate_terms(const ocn_model_terms *terms, const char *who)
-{
-    OCN_REQUIRE(terms, "%s: null terms", who);
-    const int b = terms->buoyancy;
-    OCN_REQUIRE(b >= OCN_BUOYANCY_NONE && b <= OCN_BUOYANCY_SEAWATER_S, "%s: unknown buoyancy %d", who, b);
-    if (b == OCN_BUOYANCY_TRACER || b == OCN_BUOYANCY_SEAWATER_TS || b == OCN_BUOYANCY_SEAWATER_T)
-        OCN_REQUIRE(terms->T != nullptr, "%s: the T (or b) tracer is NULL", who);
-    if (b == OCN_BUOYANCY_SEAWATER_TS || b == OCN_BUOYANCY_SEAWATER_S) OCN_REQUIRE(terms->S != nullptr, "%s: the S tracer is NULL", who);
-    return OCN_SUCCESS;
-}
-
-static dim3 column_blocks(const ocn_grid *grid) { return dim3((grid->Nx + 63) / 64, (grid->Ny + 3) / 4, 1); }
-
 template <int MODE>
 static void launch_columns(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_tke_dissipation *closure, const Args &a, void *stream)
 {
     if (closure->stability_functions == OCN_STABILITY_CONSTANT)
-        hipLaunchKernelGGL((tke_dissipation_columns<MODE, OCN_STABILITY_CONSTANT>), column_blocks(grid), dim3(64, 4, 1), 0, as_stream(stream),
-                           to_dev(*grid), make_buoyancy(terms), *closure, a);
+        hipLaunchKernelGGL((tke_dissipation_columns<MODE, OCN_STABILITY_CONSTANT>), tke::column_blocks(grid), dim3(64, 4, 1), 0,
+                           as_stream(stream), to_dev(*grid), make_buoyancy(terms), *closure, a);
     else
-        hipLaunchKernelGGL((tke_dissipation_columns<MODE, OCN_STABILITY_VARIABLE>), column_blocks(grid), dim3(64, 4, 1), 0, as_stream(stream),
-                           to_dev(*grid), make_buoyancy(terms), *closure, a);
+        hipLaunchKernelGGL((tke_dissipation_columns<MODE, OCN_STABILITY_VARIABLE>), tke::column_blocks(grid), dim3(64, 4, 1), 0,
+                           as_stream(stream), to_dev(*grid), make_buoyancy(terms), *closure, a);
 }
 
 }  // namespace tked
@@ -440,19 +361,15 @@ int ocn_compute_tke_dissipation_top_fluxes(const ocn_grid *grid, const ocn_tke_d
     if (st != OCN_SUCCESS) return st;
     const ocn_bc *tops[2] = {top_u, top_v};
     const char *names[2] = {"u", "v"};
-    for (int q = 0; q < 2; ++q) {
-        if (!tops[q]) continue;
-        OCN_REQUIRE(tops[q]->kind == OCN_BC_DEFAULT || tops[q]->kind == OCN_BC_FLUX,
-                    "%s: the top condition of %s has kind %d: only a Flux (or the default, no flux) is a surface flux", who, names[q],
-                    tops[q]->kind);
-    }
+    st = tke::validate_top_fluxes(tops, names, 2, who);
+    if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(znodes_c && u && v && e && Qe && Qeps, "%s: null pointer", who);
     OCN_REQUIRE(Qe != Qeps, "%s: Qe and Qeps must be two different planes", who);
     tked::PlaneArgs a{};
     a.zc = znodes_c; a.u = u; a.v = v; a.e = e; a.Qe = Qe; a.Qeps = Qeps;
-    a.top_u = tked::flux_or_default(top_u);
-    a.top_v = tked::flux_or_default(top_v);
-    hipLaunchKernelGGL(tked::top_fluxes, tked::column_blocks(grid), dim3(64, 4, 1), 0, as_stream(stream), to_dev(*grid), *closure, a);
+    a.top_u = flux_or_default(top_u);
+    a.top_v = flux_or_default(top_v);
+    hipLaunchKernelGGL(tked::top_fluxes, tke::column_blocks(grid), dim3(64, 4, 1), 0, as_stream(stream), to_dev(*grid), *closure, a);
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
 }
@@ -464,7 +381,7 @@ int ocn_compute_tke_dissipation_diffusivities(const ocn_grid *grid, const ocn_mo
     const char *who = "ocn_compute_tke_dissipation_diffusivities";
     int st = tked::validate_grid_and_closure(grid, closure, who);
     if (st != OCN_SUCCESS) return st;
-    st = tked::validate_terms(terms, who);
+    st = validate_buoyancy_terms(terms, who);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(u && v && e && eps && kappa_u && kappa_c && kappa_e && kappa_eps, "%s: null pointer", who);
     OCN_REQUIRE(kappa_u != kappa_c && kappa_u != kappa_e && kappa_u != kappa_eps && kappa_c != kappa_e && kappa_c != kappa_eps &&
@@ -488,7 +405,7 @@ int ocn_tke_dissipation_substep(const ocn_grid *grid, const ocn_model_terms *ter
     const char *who = "ocn_tke_dissipation_substep";
     int st = tked::validate_grid_and_closure(grid, closure, who);
     if (st != OCN_SUCCESS) return st;
-    st = tked::validate_terms(terms, who);
+    st = validate_buoyancy_terms(terms, who);
     if (st != OCN_SUCCESS) return st;
     OCN_REQUIRE(u_next && v_next && u_prev && v_prev && e && eps && kappa_u && kappa_c && kappa_e && kappa_eps && Le && Leps && Gn_e && Gm_e &&
                     Gn_eps && Gm_eps,

@@ -25,7 +25,8 @@
 //     Loads are issued a batch of planes ahead of the sequential arithmetic.
 //
 // Bandwidth-bound: one strict build (no FMA contraction, IEEE division) whatever the math mode, bit-identical to
-// tests/convective_adjustment_numpy.py.
+// tests/convective_adjustment_numpy.py.  The buoyancy is that of ocn_buoyancy.h.
+#include "ocn_buoyancy.h"
 #include "ocn_ivd.h"
 
 namespace ocn {
@@ -35,12 +36,6 @@ namespace vdf {
 using ivd::Range;
 using ivd::Spacings;
 
-struct Buoyancy {
-    int kind;
-    double g, alpha, beta;
-    const double *T, *S;  // NULL: a constant, its derivative is 0
-};
-
 __global__ __launch_bounds__(256) void convective_adjustment_diffusivities(GridDev g, Buoyancy b, ocn_convective_adjustment cl,
                                                                            double *__restrict__ kappa_c, double *__restrict__ kappa_u)
 {
@@ -49,7 +44,7 @@ __global__ __launch_bounds__(256) void convective_adjustment_diffusivities(GridD
     const Spacings M = ivd::spacings_of(g);
     const Lay Lc = make_lay(g, OCN_LOC_CCC), Lf = make_lay(g, OCN_LOC_CCF);
     const long long o = at(Lc, i, j, k);
-    double dzb = 0.0;
+    double dzb = 0.0;  // dz_b of ocn_buoyancy.h, the tracers read only where the kind needs them
     if (b.kind != OCN_BUOYANCY_NONE) {
         const double dzf = M.dzF(k);
         const double dT = b.T ? (b.T[o] - b.T[o - Lc.s3]) / dzf : 0.0;
@@ -249,11 +244,9 @@ static void launch_groups(const GridDev &gd, const Groups &groups, int n, double
 int launch_convective_adjustment_diffusivities(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_convective_adjustment *closure,
                                                double *kappa_c, double *kappa_u, hipStream_t stream)
 {
-    vdf::Buoyancy b{terms->buoyancy, terms->g, terms->alpha, terms->beta, nullptr, nullptr};
-    if (b.kind == OCN_BUOYANCY_TRACER || b.kind == OCN_BUOYANCY_SEAWATER_TS || b.kind == OCN_BUOYANCY_SEAWATER_T) b.T = terms->T;
-    if (b.kind == OCN_BUOYANCY_SEAWATER_TS || b.kind == OCN_BUOYANCY_SEAWATER_S) b.S = terms->S;
     const dim3 block(64, 4, 1), blocks((grid->Nx + 63) / 64, (grid->Ny + 3) / 4, grid->Nz);
-    hipLaunchKernelGGL(vdf::convective_adjustment_diffusivities, blocks, block, 0, stream, to_dev(*grid), b, *closure, kappa_c, kappa_u);
+    hipLaunchKernelGGL(vdf::convective_adjustment_diffusivities, blocks, block, 0, stream, to_dev(*grid), make_buoyancy(terms), *closure, kappa_c,
+                       kappa_u);
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
 }

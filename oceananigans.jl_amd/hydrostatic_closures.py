@@ -158,6 +158,12 @@ class ImplicitScalar(InModelTerms):
         implicit_diffusion_step(nh.grid, fields, [self.closure.nu] * 2 + [self.closure.kappa_of(n) for n in nh.tracer_names], dt, s)
 
 
+def top_condition(nh, field):
+    """a reference to the struct ocn_bc of the top condition of a field, NULL where there is none (no field, default conditions: no flux)"""
+    b = getattr(field, "boundary_conditions", None)
+    return C.pointer(b.c_struct(nh.grid).top) if b is not None and b.sides["top"] is not None else C.POINTER(_lib.CBc)()
+
+
 class KappaFields(InModelTerms):
     """ConvectiveAdjustmentVerticalDiffusivity or RiBasedVerticalDiffusivity, in both discretizations: κᶜ, κᵘ fields computed in update_state!
     (csrc/vertical_diffusivity.hip, csrc/ri_based_diffusivity.hip).  carriers: None, or for the Ri-based one -- which differs in how the
@@ -182,10 +188,8 @@ class KappaFields(InModelTerms):
         return self.fields
 
     def top_conditions(self, nh):
-        """references to the struct ocn_bc of the top conditions of the carriers, NULL where there is none (no such tracer, default
-        conditions: no flux)"""
-        bcs = [getattr(nh.field(name), "boundary_conditions", None) if name in nh.tracer_names else None for name in self.carriers or ()]
-        return tuple(C.pointer(b.c_struct(nh.grid).top) if b is not None and b.sides["top"] is not None else C.POINTER(_lib.CBc)() for b in bcs)
+        """top_condition of the carriers (NULL for a carrier that is no tracer of the model)"""
+        return tuple(top_condition(nh, nh.field(name) if name in nh.tracer_names else None) for name in self.carriers or ())
 
     def compute_diffusivities(self, nh):
         """compute_diffusivities!, then fill_halo_regions!(diffusivity_fields; only_local_halos = true).  RiBasedVerticalDiffusivity
@@ -233,61 +237,110 @@ class KappaFields(InModelTerms):
                   _lib.i32_array([f.loc for f in fields]), _lib.ptr_array(kappas), _lib.ptr_array(scratch), float(dt), s)
 
 
-class CATKEFields(KappaFields):
-    """CATKEVerticalDiffusivity (csrc/catke.hip): κᵘ, κᶜ, κᵉ, the linear coefficient Le, the averaged surface buoyancy flux Jᵇ and the previous
-    velocities (build_diffusivity_fields, catke_vertical_diffusivity.jl:180-208).  The closure steps the tracer e itself, inside
-    compute_diffusivities! (:219-251): M substeps of substep_turbulent_kinetic_energy! + implicit_step! in one launch each.  e's tendency is
-    the ordinary tracer tendency; ab2_step, the implicit step of the other fields and cache_previous_tendencies leave e alone
-    (hydrostatic_free_surface_ab2_step.jl:72-108, cache_hydrostatic_free_surface_tendencies.jl:30-57).  e's top condition is the closure's own
-    (add_closure_specific_boundary_conditions, catke_equation.jl:126-155): an array-valued flux that ocn_compute_catke_top_tke_flux writes."""
-    self_stepped = ("e",)
+class TKEBasedFields(KappaFields):
+    """What CATKEVerticalDiffusivity and TKEDissipationVerticalDiffusivity share (TKEBasedVerticalDiffusivities.jl): the closure steps the
+    tracers `self_stepped` itself, inside compute_diffusivities!, in substeps of one launch each; their tendencies are the ordinary tracer
+    tendencies; ab2_step, the implicit step of the other fields (KappaFields.implicit_step: both closures are always vertically implicit)
+    and cache_previous_tendencies leave them alone.  Their top conditions are the closure's own
+    (add_closure_specific_boundary_conditions): array-valued fluxes, `tops`, that the closure's kernel writes.  A subclass gives `name`,
+    `self_stepped` (and `state_keys`, what its tracers are called in a checkpoint) and `diffusivity_fields`."""
+    name, state_keys = None, {"e": "e"}
 
     def __init__(self, closure, carriers):
         super().__init__(closure, carriers)
         self.state_fields = ()  # (everything goes through checkpoint_state / restore_state)
 
     def boundary_conditions(self, user_bcs, grid):
+        """the top conditions of the self-stepped tracers are replaced, as in the reference; the user's other sides are kept (the
+        reference's branch for user conditions on ϵ copies the sides of e's, a slip: here ϵ keeps its own)"""
         bcs = dict(user_bcs or {})
-        sides = dict(bcs["e"].sides) if bcs.get("e") is not None else {}
-        self.top_e = FluxBoundaryCondition(np.zeros((grid.Nx, grid.Ny)))  # (a user's top condition on e is replaced, as in the reference)
-        sides["top"] = self.top_e
-        bcs["e"] = FieldBoundaryConditions(**{k: v for k, v in sides.items() if v is not None})
+        self.tops = {}
+        for name in self.self_stepped:
+            sides = dict(bcs[name].sides) if bcs.get(name) is not None else {}
+            self.tops[name] = sides["top"] = FluxBoundaryCondition(np.zeros((grid.Nx, grid.Ny)))
+            bcs[name] = FieldBoundaryConditions(**{k: v for k, v in sides.items() if v is not None})
         return bcs
 
     def allocate(self, nh):
         g, dev = nh.grid, nh.u.data.device
-        self.fields = {"kappa_u": ZFaceField(g), "kappa_c": ZFaceField(g), "kappa_e": ZFaceField(g), "Le": CenterField(g),
-                       "Jb": torch.zeros((g.Ny, g.Nx), dtype=torch.float64, device=dev)}
+        self.fields = self.diffusivity_fields(g, dev)
         self.u_prev, self.v_prev = XFaceField(g), YFaceField(g)
-        self.previous_compute_time = nh.clock.time
         self.struct = self.closure.c_struct()
-        self.znodes = [torch.from_numpy(np.ascontiguousarray(g.nodes_1d(2, face), dtype=np.float64)).to(dev) for face in (True, False)]
-        self.ivd_scratch = torch.zeros((4, g.Nz, g.Ny, g.Nx), dtype=torch.float64, device=dev)  # u, v, the tracers, e
-        self.top_e.c_struct(g, "top")  # (allocates the device array of the condition)
+        # the multipliers of u, v, the other tracers, and of every self-stepped tracer (those last, contiguous)
+        self.ivd_scratch = torch.zeros((3 + len(self.self_stepped), g.Nz, g.Ny, g.Nx), dtype=torch.float64, device=dev)
+        for top in self.tops.values():
+            top.c_struct(g, "top")  # (allocates the device array of the condition)
         return self.fields
+
+    def refresh_previous_velocities(self, nh):
+        self.u_prev.data.copy_(nh.u.data)
+        self.v_prev.data.copy_(nh.v.data)
+
+    def _tendencies(self, nh, name):
+        q = 3 + nh.tracer_names.index(name)
+        return nh.timestepper._Gn[q], nh.timestepper._Gm[q]
+
+    @staticmethod
+    def substeps(nh, tau):
+        """(Δτ, χ) of every substep of a model step (time_step_catke_equation.jl:12-76, tke_dissipation_equations.jl:24-88): an Euler step
+        opens several substeps; otherwise the time stepper's χ, which is -1/2 during an Euler step of the model"""
+        Dt = nh.clock.last_dt
+        M = 1 if tau is None else math.ceil(Dt / tau)
+        dtau = Dt if tau is None else Dt / M
+        return [(dtau, -0.5 if (m == 1 and M != 1) else nh.timestepper.chi) for m in range(1, M + 1)]
+
+    def _state(self, nh):
+        """{name in a checkpoint: the device tensor}: everything a bit-identical restart needs"""
+        out = {name: getattr(f, "data", f) for name, f in self.fields.items()}
+        out.update(u_prev=self.u_prev.data, v_prev=self.v_prev.data)
+        for name, key in self.state_keys.items():
+            out["top_" + key], out[key] = self.tops[name]._device_values, nh.field(name).data
+            out["Gm_" + key] = self._tendencies(nh, name)[1].data
+        return out
+
+    def checkpoint_state(self, nh):
+        return {name: np.ascontiguousarray(t.cpu().numpy().T) for name, t in self._state(nh).items()}
+
+    def restore_state(self, nh, get):
+        """the update_state! of set!(model, filepath) has stepped the closure's tracers once more: put back what the checkpointed
+        tendencies were computed with, so that the restart continues bit for bit"""
+        for name, t in self._state(nh).items():
+            a = get(name)
+            if a is None:
+                raise KeyError(f"Field {name} of {self.name} does not exist in checkpoint and could not be restored.")
+            t.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(a).T)))
+
+
+class CATKEFields(TKEBasedFields):
+    """CATKEVerticalDiffusivity (csrc/catke.hip): κᵘ, κᶜ, κᵉ, the linear coefficient Le, the averaged surface buoyancy flux Jᵇ and the previous
+    velocities (build_diffusivity_fields, catke_vertical_diffusivity.jl:180-208).  The closure steps e in M substeps of
+    substep_turbulent_kinetic_energy! + implicit_step! (:219-251, hydrostatic_free_surface_ab2_step.jl:72-108,
+    cache_hydrostatic_free_surface_tendencies.jl:30-57); ocn_compute_catke_top_tke_flux writes e's top flux (catke_equation.jl:126-155)."""
+    name, self_stepped = "CATKEVerticalDiffusivity", ("e",)
+    top_e = property(lambda self: self.tops["e"])
+
+    @staticmethod
+    def diffusivity_fields(g, dev):
+        return {"kappa_u": ZFaceField(g), "kappa_c": ZFaceField(g), "kappa_e": ZFaceField(g), "Le": CenterField(g),
+                "Jb": torch.zeros((g.Ny, g.Nx), dtype=torch.float64, device=dev)}
+
+    def allocate(self, nh):
+        g = nh.grid
+        self.previous_compute_time = nh.clock.time
+        self.znodes = [torch.from_numpy(np.ascontiguousarray(g.nodes_1d(2, face), dtype=np.float64)).to(nh.u.data.device) for face in (True, False)]
+        return super().allocate(nh)
 
     def kappa_of_tracer(self, name):
         return self.fields["kappa_e" if name == "e" else "kappa_c"].ptr
 
-    @staticmethod
-    def _top(nh, field):
-        b = getattr(field, "boundary_conditions", None)
-        return C.pointer(b.c_struct(nh.grid).top) if b is not None and b.sides["top"] is not None else C.POINTER(_lib.CBc)()
-
     def _e_tendencies(self, nh):
-        q = 3 + nh.tracer_names.index("e")
-        return nh.timestepper._Gn[q], nh.timestepper._Gm[q]
+        return self._tendencies(nh, "e")
 
     def time_step_tke(self, nh, s):
         """time_step_catke_equation! (time_step_catke_equation.jl:12-76)"""
         g, d, zf, zc = nh.grid, self.fields, *self.znodes
-        Dt, tau = nh.clock.last_dt, self.closure.tke_time_step
-        M = 1 if tau is None else math.ceil(Dt / tau)
-        dtau = Dt if tau is None else Dt / M
         Gn, Gm = self._e_tendencies(nh)
-        for m in range(1, M + 1):
-            # an Euler step opens several substeps; otherwise the time stepper's χ, which is -1/2 during an Euler step of the model
-            chi = -0.5 if (m == 1 and M != 1) else nh.timestepper.chi
+        for dtau, chi in self.substeps(nh, self.closure.tke_time_step):
             _lib.call("ocn_catke_substep_tke", g.cref, C.byref(nh._terms), C.byref(self.struct), zf.data_ptr(), zc.data_ptr(), nh.u.ptr, nh.v.ptr,
                       self.u_prev.ptr, self.v_prev.ptr, nh.field("e").ptr, d["Jb"].data_ptr(), d["kappa_u"].ptr, d["kappa_c"].ptr,
                       d["kappa_e"].ptr, d["Le"].ptr, Gn.ptr, Gm.ptr, self.ivd_scratch[3].data_ptr(), float(dtau), float(chi), 1, s)
@@ -300,8 +353,7 @@ class CATKEFields(KappaFields):
         self.previous_compute_time = nh.clock.time
         if math.isfinite(nh.clock.last_dt):  # the model has taken a step
             self.time_step_tke(nh, s)
-        self.u_prev.data.copy_(nh.u.data)
-        self.v_prev.data.copy_(nh.v.data)
+        self.refresh_previous_velocities(nh)
         tops, e = self.top_conditions(nh), nh.field("e")
         _lib.call("ocn_compute_catke_surface_buoyancy_flux", g.cref, terms, cl, *tops, zf.data_ptr(), zc.data_ptr(), nh.u.ptr, nh.v.ptr, e.ptr,
                   d["Jb"].data_ptr(), float(dt), s)
@@ -309,96 +361,47 @@ class CATKEFields(KappaFields):
                   d["Jb"].data_ptr(), d["kappa_u"].ptr, d["kappa_c"].ptr, d["kappa_e"].ptr, s)
         fill_halo_regions((d["kappa_u"], d["kappa_c"], d["kappa_e"]), fill_boundary_normal_velocities=False)
         # the top flux of e, for the compute_boundary_tendency_contributions! of this state
-        _lib.call("ocn_compute_catke_top_tke_flux", g.cref, terms, cl, self._top(nh, nh.u), self._top(nh, nh.v), *tops, nh.u.ptr, nh.v.ptr,
-                  self.top_e._device_values.data_ptr(), s)
-
-    def implicit_step(self, nh, fields, dt, s):
-        """implicit_step! of u, v (κᵘ) and the tracers but e (κᶜ); e is stepped in compute_diffusivities"""
-        d, w, nt = self.fields, self.ivd_scratch, len(fields) - 2
-        kappas = [d["kappa_u"].ptr] * 2 + [d["kappa_c"].ptr] * nt
-        scratch = [w[0].data_ptr(), w[1].data_ptr()] + [w[2].data_ptr()] * nt
-        _lib.call("ocn_implicit_vertical_diffusion_step_fields", nh.grid.cref, len(fields), _lib.ptr_array([f.ptr for f in fields]),
-                  _lib.i32_array([f.loc for f in fields]), _lib.ptr_array(kappas), _lib.ptr_array(scratch), float(dt), s)
+        _lib.call("ocn_compute_catke_top_tke_flux", g.cref, terms, cl, top_condition(nh, nh.u), top_condition(nh, nh.v), *tops, nh.u.ptr,
+                  nh.v.ptr, self.top_e._device_values.data_ptr(), s)
 
     def checkpoint_state(self, nh):
-        d = self.fields
-        out = {name: d[name].parent() for name in ("kappa_u", "kappa_c", "kappa_e", "Le")}
-        out.update(Jb=d["Jb"].cpu().numpy().T, u_prev=self.u_prev.parent(), v_prev=self.v_prev.parent(),
-                   top_e=self.top_e._device_values.cpu().numpy().T, previous_compute_time=np.float64(self.previous_compute_time),
-                   e=nh.field("e").parent(), Gm_e=self._e_tendencies(nh)[1].parent())
-        return out
+        return dict(super().checkpoint_state(nh), previous_compute_time=np.float64(self.previous_compute_time))
 
     def restore_state(self, nh, get):
-        """the update_state! of set!(model, filepath) has stepped e and averaged Jᵇ once more: put back what the checkpointed tendencies
-        were computed with, so that the restart continues bit for bit"""
-        d = self.fields
-        targets = {name: d[name].data for name in ("kappa_u", "kappa_c", "kappa_e", "Le")}
-        targets.update(Jb=d["Jb"], u_prev=self.u_prev.data, v_prev=self.v_prev.data, top_e=self.top_e._device_values, e=nh.field("e").data,
-                       Gm_e=self._e_tendencies(nh)[1].data)
-        for name, t in targets.items():
-            a = get(name)
-            if a is None:
-                raise KeyError(f"Field {name} of CATKEVerticalDiffusivity does not exist in checkpoint and could not be restored.")
-            t.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(a).T)))
+        """... and Jᵇ has been averaged once more"""
+        super().restore_state(nh, get)
         self.previous_compute_time = float(get("previous_compute_time"))
 
 
-class TKEDissipationFields(KappaFields):
+class TKEDissipationFields(TKEBasedFields):
     """TKEDissipationVerticalDiffusivity (csrc/tke_dissipation.hip): κᵘ, κᶜ, κᵉ, κᵋ, the linear coefficients Le, Lϵ and the previous velocities
-    (build_diffusivity_fields, tke_dissipation_vertical_diffusivity.jl:184-223).  The closure steps the tracers e and ϵ itself, inside
-    compute_diffusivities! (:228-256): M substeps of substep_tke_dissipation! + the implicit_step! of e + that of ϵ, one launch each.  Their
-    slow tendencies are the ordinary tracer tendencies with κᵉ / κᵋ; ab2_step, the implicit step of the other fields and
-    cache_previous_tendencies leave them alone.  Their top conditions are the closure's own (add_closure_specific_boundary_conditions,
-    tke_dissipation_equations.jl:258-303): two array-valued fluxes that ocn_compute_tke_dissipation_top_fluxes writes.  `eps`: the name the user
-    gave the dissipation tracer."""
+    (build_diffusivity_fields, tke_dissipation_vertical_diffusivity.jl:184-223).  The closure steps e and ϵ in M substeps of
+    substep_tke_dissipation! + the implicit_step! of e + that of ϵ (:228-256); their slow tendencies carry κᵉ / κᵋ;
+    ocn_compute_tke_dissipation_top_fluxes writes their top fluxes (tke_dissipation_equations.jl:258-303).  `eps`: the name the user gave
+    the dissipation tracer."""
+    name = "TKEDissipationVerticalDiffusivity"
 
     def __init__(self, closure, carriers, eps):
         super().__init__(closure, carriers)
-        self.state_fields = ()  # (everything goes through checkpoint_state / restore_state)
-        self.eps, self.self_stepped = eps, ("e", eps)
+        self.eps, self.self_stepped, self.state_keys = eps, ("e", eps), {"e": "e", eps: "eps"}
 
-    def boundary_conditions(self, user_bcs, grid):
-        """the top conditions of e and ϵ are replaced; the user's other sides are kept (the reference's branch for user conditions on ϵ copies
-        the sides of e's, a slip: here ϵ keeps its own)"""
-        bcs = dict(user_bcs or {})
-        self.tops = {}
-        for name in self.self_stepped:
-            sides = dict(bcs[name].sides) if bcs.get(name) is not None else {}
-            self.tops[name] = sides["top"] = FluxBoundaryCondition(np.zeros((grid.Nx, grid.Ny)))
-            bcs[name] = FieldBoundaryConditions(**{k: v for k, v in sides.items() if v is not None})
-        return bcs
+    @staticmethod
+    def diffusivity_fields(g, dev):
+        return {"kappa_u": ZFaceField(g), "kappa_c": ZFaceField(g), "kappa_e": ZFaceField(g), "kappa_eps": ZFaceField(g),
+                "Le": CenterField(g), "Leps": CenterField(g)}
 
     def allocate(self, nh):
-        g, dev = nh.grid, nh.u.data.device
-        self.fields = {"kappa_u": ZFaceField(g), "kappa_c": ZFaceField(g), "kappa_e": ZFaceField(g), "kappa_eps": ZFaceField(g),
-                       "Le": CenterField(g), "Leps": CenterField(g)}
-        self.u_prev, self.v_prev = XFaceField(g), YFaceField(g)
-        self.struct = self.closure.c_struct()
-        self.zc = torch.from_numpy(np.ascontiguousarray(g.nodes_1d(2, False), dtype=np.float64)).to(dev)
-        self.ivd_scratch = torch.zeros((5, g.Nz, g.Ny, g.Nx), dtype=torch.float64, device=dev)  # u, v, the tracers, e and ϵ
-        for top in self.tops.values():
-            top.c_struct(g, "top")  # (allocates the device array of the condition)
-        return self.fields
+        self.zc = torch.from_numpy(np.ascontiguousarray(nh.grid.nodes_1d(2, False), dtype=np.float64)).to(nh.u.data.device)
+        return super().allocate(nh)
 
     def kappa_of_tracer(self, name):
         return self.fields["kappa_e" if name == "e" else ("kappa_eps" if name == self.eps else "kappa_c")].ptr
 
-    _top = staticmethod(CATKEFields._top)
-
-    def _tendencies(self, nh, name):
-        q = 3 + nh.tracer_names.index(name)
-        return nh.timestepper._Gn[q], nh.timestepper._Gm[q]
-
     def time_step_tke_dissipation(self, nh, s):
         """time_step_tke_dissipation_equations! (tke_dissipation_equations.jl:24-88)"""
         g, d = nh.grid, self.fields
-        Dt, tau = nh.clock.last_dt, self.closure.tke_dissipation_time_step
-        M = 1 if tau is None else math.ceil(Dt / tau)
-        dtau = Dt if tau is None else Dt / M
         (Gn_e, Gm_e), (Gn_eps, Gm_eps) = self._tendencies(nh, "e"), self._tendencies(nh, self.eps)
-        for m in range(1, M + 1):
-            # an Euler step opens several substeps; otherwise the time stepper's χ, which is -1/2 during an Euler step of the model
-            chi = -0.5 if (m == 1 and M != 1) else nh.timestepper.chi
+        for dtau, chi in self.substeps(nh, self.closure.tke_dissipation_time_step):
             _lib.call("ocn_tke_dissipation_substep", g.cref, C.byref(nh._terms), C.byref(self.struct), nh.u.ptr, nh.v.ptr, self.u_prev.ptr,
                       self.v_prev.ptr, nh.field("e").ptr, nh.field(self.eps).ptr, d["kappa_u"].ptr, d["kappa_c"].ptr, d["kappa_e"].ptr,
                       d["kappa_eps"].ptr, d["Le"].ptr, d["Leps"].ptr, Gn_e.ptr, Gm_e.ptr, Gn_eps.ptr, Gm_eps.ptr, self.ivd_scratch[3].data_ptr(),
@@ -410,45 +413,15 @@ class TKEDissipationFields(KappaFields):
         terms, cl = C.byref(nh._terms), C.byref(self.struct)
         if math.isfinite(nh.clock.last_dt):  # the model has taken a step
             self.time_step_tke_dissipation(nh, s)
-        self.u_prev.data.copy_(nh.u.data)
-        self.v_prev.data.copy_(nh.v.data)
+        self.refresh_previous_velocities(nh)
         e, eps = nh.field("e"), nh.field(self.eps)
         kappas = [d[name] for name in ("kappa_u", "kappa_c", "kappa_e", "kappa_eps")]
         _lib.call("ocn_compute_tke_dissipation_diffusivities", g.cref, terms, cl, nh.u.ptr, nh.v.ptr, e.ptr, eps.ptr, *[k.ptr for k in kappas], s)
         # (the reference's fill_halo_regions!(::TKEDissipationDiffusivityFields) names an undefined variable: what it evidently means)
         fill_halo_regions(tuple(kappas), fill_boundary_normal_velocities=False)
         # the top fluxes of e and ϵ, for the compute_boundary_tendency_contributions! of this state
-        _lib.call("ocn_compute_tke_dissipation_top_fluxes", g.cref, cl, self._top(nh, nh.u), self._top(nh, nh.v), self.zc.data_ptr(), nh.u.ptr,
-                  nh.v.ptr, e.ptr, self.tops["e"]._device_values.data_ptr(), self.tops[self.eps]._device_values.data_ptr(), s)
-
-    def implicit_step(self, nh, fields, dt, s):
-        """implicit_step! of u, v (κᵘ) and the tracers but e and ϵ (κᶜ), which are stepped in compute_diffusivities"""
-        d, w, nt = self.fields, self.ivd_scratch, len(fields) - 2
-        kappas = [d["kappa_u"].ptr] * 2 + [d["kappa_c"].ptr] * nt
-        scratch = [w[0].data_ptr(), w[1].data_ptr()] + [w[2].data_ptr()] * nt
-        _lib.call("ocn_implicit_vertical_diffusion_step_fields", nh.grid.cref, len(fields), _lib.ptr_array([f.ptr for f in fields]),
-                  _lib.i32_array([f.loc for f in fields]), _lib.ptr_array(kappas), _lib.ptr_array(scratch), float(dt), s)
-
-    def _state(self, nh):
-        """{name: (the device tensor, whether it is a plane of Nx Ny values)}: everything a bit-identical restart needs"""
-        d = self.fields
-        out = {name: d[name].data for name in ("kappa_u", "kappa_c", "kappa_e", "kappa_eps", "Le", "Leps")}
-        out.update(u_prev=self.u_prev.data, v_prev=self.v_prev.data, top_e=self.tops["e"]._device_values,
-                   top_eps=self.tops[self.eps]._device_values, e=nh.field("e").data, eps=nh.field(self.eps).data,
-                   Gm_e=self._tendencies(nh, "e")[1].data, Gm_eps=self._tendencies(nh, self.eps)[1].data)
-        return out
-
-    def checkpoint_state(self, nh):
-        return {name: np.ascontiguousarray(t.cpu().numpy().T) for name, t in self._state(nh).items()}
-
-    def restore_state(self, nh, get):
-        """the update_state! of set!(model, filepath) has stepped e and ϵ once more: put back what the checkpointed tendencies were computed
-        with, so that the restart continues bit for bit"""
-        for name, t in self._state(nh).items():
-            a = get(name)
-            if a is None:
-                raise KeyError(f"Field {name} of TKEDissipationVerticalDiffusivity does not exist in checkpoint and could not be restored.")
-            t.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(a).T)))
+        _lib.call("ocn_compute_tke_dissipation_top_fluxes", g.cref, cl, top_condition(nh, nh.u), top_condition(nh, nh.v), self.zc.data_ptr(),
+                  nh.u.ptr, nh.v.ptr, e.ptr, self.tops["e"]._device_values.data_ptr(), self.tops[self.eps]._device_values.data_ptr(), s)
 
 
 class IsopycnalFields(InModelTerms):

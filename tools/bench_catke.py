@@ -20,6 +20,7 @@ import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import oceananigans_jl_amd as ocn
+from oceananigans_jl_amd.hydrostatic_closures import top_condition
 
 Nx = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 Nz = int(sys.argv[2]) if len(sys.argv) > 2 else 128
@@ -88,7 +89,7 @@ d = cf.fields
 terms, cl, (zf, zc_) = C.byref(nh._terms), C.byref(cf.struct), cf.znodes
 tops = cf.top_conditions(nh)
 e = nh.field("e")
-Gn, Gm = cf._e_tendencies(nh)
+Gn, Gm = cf._tendencies(nh, "e")
 e_work, Gm_work, Jb_work = torch.zeros_like(e.data), torch.zeros_like(Gm.data), torch.zeros_like(d["Jb"])
 ku_w, kc_w, ke_w, Le_w = (torch.zeros_like(d[n].data) for n in ("kappa_u", "kappa_c", "kappa_e", "Le"))
 print(f"grid {Nx}x{Nx}x{Nz}, dt = {dt:.4g} s; max e {float(e.interior_view().max()):.3g}, max κᶜ {float(d['kappa_c'].interior_view().max()):.3g}, "
@@ -107,7 +108,7 @@ def substep_call(solve):
 
 jb_call = lambda: L.call("ocn_compute_catke_surface_buoyancy_flux", g.cref, terms, cl, *tops, zf.data_ptr(), zc_.data_ptr(), m.u.ptr, m.v.ptr, e.ptr,
                          Jb_work.data_ptr(), float(dt), 0)
-top_call = lambda: L.call("ocn_compute_catke_top_tke_flux", g.cref, terms, cl, cf._top(nh, nh.u), cf._top(nh, nh.v), *tops, m.u.ptr, m.v.ptr,
+top_call = lambda: L.call("ocn_compute_catke_top_tke_flux", g.cref, terms, cl, top_condition(nh, nh.u), top_condition(nh, nh.v), *tops, m.u.ptr, m.v.ptr,
                           cf.top_e._device_values.data_ptr(), 0)
 calls = [("diffusivities", dif_call, 64), ("substep + solve", substep_call(1), 152), ("substep alone", substep_call(0), 120),
          ("surface buoyancy flux (plane)", jb_call, 0), ("top flux of e (plane)", top_call, 0)]

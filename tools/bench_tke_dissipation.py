@@ -23,6 +23,7 @@ import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import oceananigans_jl_amd as ocn
+from oceananigans_jl_amd.hydrostatic_closures import top_condition
 
 Nx = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 Nz = int(sys.argv[2]) if len(sys.argv) > 2 else 128
@@ -116,12 +117,12 @@ def k_substep(solve):
     return call
 
 
-k_top = lambda: L.call("ocn_compute_tke_dissipation_top_fluxes", g.cref, k_cl, kf._top(kn, kn.u), kf._top(kn, kn.v), kf.zc.data_ptr(), mk.u.ptr, mk.v.ptr,
+k_top = lambda: L.call("ocn_compute_tke_dissipation_top_fluxes", g.cref, k_cl, top_condition(kn, kn.u), top_condition(kn, kn.v), kf.zc.data_ptr(), mk.u.ptr, mk.v.ptr,
                        e.ptr, Qw[0].data_ptr(), Qw[1].data_ptr(), 0)
 # the yardstick
 c_terms, c_cl, (zf, zc_) = C.byref(cn._terms), C.byref(cf.struct), cf.znodes
 ce = cn.field("e")
-cGn, cGm = cf._e_tendencies(cn)
+cGn, cGm = cf._tendencies(cn, "e")
 c_work = {"e": torch.zeros_like(ce.data), "Gm": torch.zeros_like(cGm.data), "Le": torch.zeros_like(cd["Le"].data)}
 cw = [torch.zeros_like(cd[n].data) for n in ("kappa_u", "kappa_c", "kappa_e")]
 c_dif = lambda: L.call("ocn_compute_catke_diffusivities", g.cref, c_terms, c_cl, zf.data_ptr(), zc_.data_ptr(), mc.u.ptr, mc.v.ptr, ce.ptr,

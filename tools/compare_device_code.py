@@ -9,6 +9,7 @@ bundle where the compiler wrote one, and compared.  One line per object:
 
     identical                       the two code objects are the same bytes
     kernels -N: <names>             B lacks N kernels of A (or has +N more); every kernel both have disassembles to the same text
+    kernels renamed N: <names>      N kernels have another symbol (the types of their arguments were renamed); all disassemble to the same text
     DIFFERENT: ...                  anything else
 
 Whole code objects and the disassembly text of whole kernels are compared; nothing looks for particular instructions.
@@ -101,6 +102,14 @@ def compare(a, b):
     if changed:
         return False, f"DIFFERENT: the disassembly of {len(changed)} kernels differs: " + ", ".join(demangle(changed)[:4])
     gone, new = sorted(ka.keys() - kb.keys()), sorted(kb.keys() - ka.keys())
+    # a kernel whose argument types were renamed (a struct moved to another namespace) has another symbol: pair such kernels by their
+    # demangled name without the parameter list and compare their text with the kernel's own symbol taken out
+    renamed = {n: m for n, dn in zip(gone, demangle(gone)) for m, dm in zip(new, demangle(new)) if dn == dm}
+    if renamed and len(renamed) == len(gone) == len(new):
+        changed = sorted(n for n, m in renamed.items() if ka[n].replace(n, "") != kb[m].replace(m, ""))
+        if changed:
+            return False, f"DIFFERENT: {len(renamed)} kernels renamed, the disassembly of {len(changed)} differs: " + ", ".join(demangle(changed)[:4])
+        return True, f"kernels renamed {len(renamed)}: " + ", ".join(demangle(gone)) + f"; all {len(ka)} kernels disassemble to the same text"
     if not gone and not new:
         return False, "DIFFERENT: same kernels with the same disassembly, other bytes (data, metadata)"
     parts = ([f"kernels -{len(gone)}: " + ", ".join(demangle(gone))] if gone else []) + ([f"kernels +{len(new)}: " + ", ".join(demangle(new))] if new else [])
