@@ -100,8 +100,7 @@ static bool xy_periodic(const ocn_grid *g) { return (g->tx == OCN_PERIODIC || g-
 // WENO5 reads 3 halo cells (nonhydrostatic_model.jl:183, 243-257 inflates the halo to >= 3)
 static int validate_weno(const ocn_grid *g)
 {
-    int st = validate_grid_any(g);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(g));
     OCN_REQUIRE((g->tx == OCN_FLAT || g->Hx >= 3) && (g->ty == OCN_FLAT || g->Hy >= 3) && (g->tz == OCN_FLAT || g->Hz >= 3),
                 "WENO(order=5) needs halo >= 3, got (%d, %d, %d)", g->Hx, g->Hy, g->Hz);
     OCN_REQUIRE((g->tx == OCN_FLAT || g->Nx >= 3) && (g->ty == OCN_FLAT || g->Ny >= 3) && (g->tz == OCN_FLAT || g->Nz >= 3),
@@ -209,33 +208,28 @@ static int make_field_tuple(const ocn_grid *grid, double *const *fields, const i
 int ocn_fill_halo_regions(const ocn_grid *grid, double *const *fields, const int32_t *locs, int32_t n,
                           int32_t fill_boundary_normal_velocities, void *stream)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     FieldTuple ft;
-    st = make_field_tuple(grid, fields, locs, n, ft);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_field_tuple(grid, fields, locs, n, ft));
     if (!xy_periodic(grid)) return launch_fill_halos_general(grid, ft, fill_boundary_normal_velocities, as_stream(stream));
     return launch_fill_halos(grid, ft, fill_boundary_normal_velocities, -1, as_stream(stream));
 }
 
 int ocn_fill_halo_periodic(const ocn_grid *grid, double *const *fields, const int32_t *locs, int32_t n, int32_t dir, void *stream)
 {
-    int st = validate_grid(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid(grid));
     OCN_REQUIRE(dir >= 0 && dir <= 2, "dir must be 0, 1 or 2");
     const int t = dir == 0 ? grid->tx : dir == 1 ? grid->ty : grid->tz;
     OCN_REQUIRE(t == OCN_PERIODIC, "direction %d is not Periodic", dir);
     FieldTuple ft;
-    st = make_field_tuple(grid, fields, locs, n, ft);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_field_tuple(grid, fields, locs, n, ft));
     return launch_fill_halos(grid, ft, 0, dir, as_stream(stream));
 }
 
 int ocn_compute_momentum_tendencies(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
                                     double *Gv, double *Gw, const int32_t *range, void *stream)
 {
-    int st = validate_weno(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_weno(grid));
     OCN_REQUIRE(u && v && w && Gu && Gv && Gw, "ocn_compute_momentum_tendencies: null field pointer");
     if (!xy_periodic(grid)) return OCN_LAUNCH(grid, launch_momentum_tendencies_general, grid, 0, u, v, w, Gu, Gv, Gw, range, as_stream(stream));
     return OCN_LAUNCH(grid, launch_momentum_tendencies, grid, u, v, w, Gu, Gv, Gw, range, nullptr, as_stream(stream));
@@ -257,8 +251,7 @@ static int momentum_tendencies_rk3(const ocn_grid *grid, const double *u, const 
                                    double *w_out, double dt, double gamma, double zeta, int32_t has_zeta, const double *p_correct,
                                    double dt_correct, const int32_t *range, int32_t flags, void *stream)
 {
-    int st = validate_weno(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_weno(grid));
     OCN_REQUIRE(u && v && w && Gu && Gv && Gw && u_out && v_out && w_out, "ocn_compute_momentum_tendencies_rk3: null field pointer");
     OCN_REQUIRE(!has_zeta || (Gmu && Gmv && Gmw), "ocn_compute_momentum_tendencies_rk3: G⁻ pointers are required when has_zeta != 0");
     OCN_REQUIRE(u_out != u && v_out != v && w_out != w, "ocn_compute_momentum_tendencies_rk3: outputs must not alias the inputs");
@@ -310,8 +303,7 @@ int ocn_compute_momentum_tendencies_rk3_strips(const ocn_grid *grid, const doubl
                                                int32_t has_zeta, const double *p_correct, double dt_correct, double *strip_west,
                                                double *strip_east, int64_t field_doubles, void *stream)
 {
-    int st = validate_weno(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_weno(grid));
     OCN_REQUIRE(u && v && w && Gu && Gv && Gw && u_out && v_out && w_out, "ocn_compute_momentum_tendencies_rk3_strips: null field pointer");
     OCN_REQUIRE(!has_zeta || (Gmu && Gmv && Gmw), "ocn_compute_momentum_tendencies_rk3_strips: G⁻ pointers are required when has_zeta != 0");
     OCN_REQUIRE(u_out != u && v_out != v && w_out != w, "ocn_compute_momentum_tendencies_rk3_strips: outputs must not alias the inputs");
@@ -337,8 +329,7 @@ int ocn_momentum_tendencies_addr32(const ocn_grid *grid, int32_t *selected)
 int ocn_momentum_tendencies_plan(const ocn_grid *grid, const int32_t *range, int32_t correct_on_load, int32_t flags, int32_t strips,
                                  int32_t *plan)
 {
-    int st = validate_weno(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_weno(grid));
     OCN_REQUIRE(plan, "ocn_momentum_tendencies_plan: plan is NULL");
     OCN_REQUIRE(xy_periodic(grid), "ocn_momentum_tendencies_plan: grids Periodic (or partitioned) in x and Periodic in y");
     OCN_REQUIRE(!(flags & ~(OCN_RK3_SKIP_G_STORE | OCN_RK3_WRAPPED_LOADS | OCN_RK3_CORRECT_ONLY)),
@@ -361,8 +352,7 @@ int ocn_momentum_tendencies_plan(const ocn_grid *grid, const int32_t *range, int
 int ocn_cell_advection_timescale(const ocn_grid *grid, const double *u, const double *v, const double *w, double *result_device,
                                  void *stream)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     OCN_REQUIRE(u && v && w && result_device, "ocn_cell_advection_timescale: null pointer");
     return launch_advection_timescale(grid, u, v, w, result_device, as_stream(stream));
 }
@@ -390,8 +380,7 @@ static int validate_terms(const ocn_grid *grid, const ocn_model_terms *t)
     if (buoyancy_reads_S(t->buoyancy)) OCN_REQUIRE(t->S != nullptr, "buoyancy formulation %d needs the S tracer", t->buoyancy);
     OCN_REQUIRE(!t->pHY || t->buoyancy != OCN_BUOYANCY_NONE, "a hydrostatic pressure anomaly exists only with buoyancy (nonhydrostatic_model.jl:143-158)");
     if (t->advection != OCN_ADVECTION_CENTERED2) return validate_weno(grid);  // UpwindBiased(order=5): same halo / size needs
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     OCN_REQUIRE((grid->tx == OCN_FLAT || grid->Hx >= 1) && (grid->ty == OCN_FLAT || grid->Hy >= 1) && (grid->tz == OCN_FLAT || grid->Hz >= 1),
                 "Centered(order=2) and the closure stencils need halo >= 1");
     return OCN_SUCCESS;
@@ -467,14 +456,12 @@ static int momentum_options(const char *who, const ocn_grid *grid, const ocn_sto
     static const char *names[3] = {"u", "v", "w"};
     OCN_REQUIRE(grid != nullptr || (!stokes && !forcing), "grid is NULL");
     for (int f = 0; forcing && f < 3; ++f) {
-        int st = validate_forcing(grid, forcing[f], who, names[f]);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(validate_forcing(grid, forcing[f], who, names[f]));
         o.md.f[f] = ocn::to_dev(forcing[f]);
         if (o.md.f[f].n > 0) o.forcing = &o.md;
     }
     if (!stokes) return OCN_SUCCESS;
-    int st = validate_stokes(grid, stokes, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_stokes(grid, stokes, who));
     o.sd = ocn::to_dev(*stokes);
     o.stokes = &o.sd;
     return OCN_SUCCESS;
@@ -486,15 +473,12 @@ static int momentum_tendencies_terms(const char *who, const ocn_grid *grid, cons
                                      double *Gv, double *Gw, const int32_t *range, void *stream)
 {
     MomentumOptions o;
-    int st = momentum_options(who, grid, stokes, forcing, o);
-    if (st != OCN_SUCCESS) return st;
-    st = validate_terms(grid, terms);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(momentum_options(who, grid, stokes, forcing, o));
+    OCN_TRY(validate_terms(grid, terms));
     OCN_REQUIRE(u && v && w && Gu && Gv && Gw, "%s: null field pointer", who);
     OCN_REQUIRE((grid->tx == OCN_FLAT || grid->Hx >= 1) && (grid->ty == OCN_FLAT || grid->Hy >= 1) && (grid->tz == OCN_FLAT || grid->Hz >= 1), "halo >= 1 required");
     hipStream_t s = as_stream(stream);
-    st = launch_advective_momentum(terms->advection, grid, u, v, w, Gu, Gv, Gw, range, s);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(launch_advective_momentum(terms->advection, grid, u, v, w, Gu, Gv, Gw, range, s));
     if (!(terms->coriolis || terms->closure || terms->buoyancy || o.stokes || o.forcing)) return OCN_SUCCESS;
     TermsDev t = to_dev(*terms);
     if (!xy_periodic(grid)) return OCN_LAUNCH(grid, launch_momentum_extra_general, grid, t, u, v, w, Gu, Gv, Gw, range, s, nullptr, o.stokes, o.forcing);
@@ -527,8 +511,7 @@ int ocn_compute_momentum_tendencies_terms_forced(const ocn_grid *grid, const ocn
 int ocn_add_momentum_terms(const ocn_grid *grid, const ocn_model_terms *terms, const double *u, const double *v, const double *w,
                            double *Gu, double *Gv, double *Gw, const int32_t *range, void *stream)
 {
-    int st = validate_terms(grid, terms);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_terms(grid, terms));
     OCN_REQUIRE(u && v && w && Gu && Gv && Gw, "ocn_add_momentum_terms: null field pointer");
     OCN_REQUIRE(grid->Hx >= 1 && grid->Hy >= 1 && (grid->tz == OCN_FLAT || grid->Hz >= 1), "halo >= 1 required");
     if (!(terms->coriolis || terms->closure || terms->buoyancy)) return OCN_SUCCESS;
@@ -550,13 +533,11 @@ static int validate_hydrostatic(const ocn_grid *grid, const char *who, bool wall
     OCN_REQUIRE(grid, "%s: null grid", who);
     if (hydrostatic_walls(grid)) {
         OCN_REQUIRE(walls_ok, "%s: this entry point of the hydrostatic slice needs a (Periodic, Periodic, Bounded) grid", who);
-        int st = validate_grid_any(grid);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(validate_grid_any(grid));
         OCN_REQUIRE(grid->Hx >= 1 && grid->Hy >= 1, "%s: needs x, y halos", who);
         return OCN_SUCCESS;
     }
-    int st = validate_grid(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid(grid));
     // x may be the partitioned direction of a slab-x rank (FullyConnected: halos come from the neighbours, interior arithmetic as Periodic)
     OCN_REQUIRE((grid->tx == OCN_PERIODIC || grid->tx == OCN_FULLY_CONNECTED) && grid->ty == OCN_PERIODIC && grid->tz == OCN_BOUNDED,
                 walls_ok ? "%s: the hydrostatic slice supports (Periodic, Periodic | Bounded, Bounded) and (Bounded, Bounded, Bounded) grids"
@@ -568,8 +549,7 @@ static int validate_hydrostatic(const ocn_grid *grid, const char *who, bool wall
 int ocn_compute_vector_invariant_momentum_tendencies(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu,
                                                      double *Gv, const double *eta, double gravitational_acceleration, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_compute_vector_invariant_momentum_tendencies", true);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic(grid, "ocn_compute_vector_invariant_momentum_tendencies", true));
     OCN_REQUIRE(u && v && w && Gu && Gv, "ocn_compute_vector_invariant_momentum_tendencies: null field pointer");
     OCN_REQUIRE(grid->Hz >= 1, "ocn_compute_vector_invariant_momentum_tendencies: needs a z halo");
     if (hydrostatic_walls(grid)) return launch_vector_invariant_walls(grid, u, v, w, Gu, Gv, eta, gravitational_acceleration, as_stream(stream));
@@ -580,8 +560,7 @@ int ocn_compute_vector_invariant_weno_momentum_tendencies(const ocn_grid *grid, 
                                                           double gravitational_acceleration, void *stream)
 {
     const char *who = "ocn_compute_vector_invariant_weno_momentum_tendencies";
-    int st = validate_hydrostatic(grid, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic(grid, who));
     OCN_REQUIRE_PERIODIC_X(who);
     OCN_REQUIRE(u && v && w && Gu && Gv, "%s: null field pointer", who);
     const int32_t weno = OCN_VI_WENO_VORTICITY | OCN_VI_WENO_VERTICAL | OCN_VI_WENO_KINETIC_ENERGY;
@@ -596,8 +575,7 @@ int ocn_compute_vector_invariant_weno_momentum_tendencies(const ocn_grid *grid, 
 int ocn_split_explicit_forcing(const ocn_grid *grid, const double *Gu, const double *Gu_previous, const double *Gv, const double *Gv_previous,
                                double chi, double *GU, double *GV, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_split_explicit_forcing", true);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic(grid, "ocn_split_explicit_forcing", true));
     OCN_REQUIRE(Gu && Gu_previous && Gv && Gv_previous && GU && GV, "ocn_split_explicit_forcing: null pointer");
     if (hydrostatic_walls(grid)) return launch_split_explicit_forcing_walls(grid, Gu, Gu_previous, Gv, Gv_previous, chi, GU, GV, as_stream(stream));
     return launch_split_explicit_forcing(grid, Gu, Gu_previous, Gv, Gv_previous, chi, GU, GV, as_stream(stream));
@@ -606,8 +584,7 @@ int ocn_split_explicit_substeps(const ocn_grid *grid, int32_t n, const double *w
                                 double column_depth, double *eta, double *U, double *V, double *eta_filtered, double *U_filtered,
                                 double *V_filtered, const double *GU, const double *GV, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_split_explicit_substeps", true);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic(grid, "ocn_split_explicit_substeps", true));
     OCN_REQUIRE(grid->tx != OCN_FULLY_CONNECTED, "ocn_split_explicit_substeps wraps x periodically: not for a partitioned (FullyConnected) x");
     OCN_REQUIRE(n >= 1 && weights, "ocn_split_explicit_substeps: needs n >= 1 averaging weights (host array)");
     OCN_REQUIRE(eta && U && V && eta_filtered && U_filtered && V_filtered && GU && GV, "ocn_split_explicit_substeps: null pointer");
@@ -619,8 +596,7 @@ int ocn_split_explicit_substeps(const ocn_grid *grid, int32_t n, const double *w
 }
 int ocn_compute_barotropic_mode(const ocn_grid *grid, const double *u, const double *v, double *U, double *V, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_compute_barotropic_mode", true);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic(grid, "ocn_compute_barotropic_mode", true));
     OCN_REQUIRE(u && v && U && V, "ocn_compute_barotropic_mode: null pointer");
     if (hydrostatic_walls(grid)) return launch_barotropic_mode_walls(grid, u, v, U, V, as_stream(stream));
     return launch_barotropic_mode(grid, u, v, U, V, as_stream(stream));
@@ -628,8 +604,7 @@ int ocn_compute_barotropic_mode(const ocn_grid *grid, const double *u, const dou
 int ocn_barotropic_split_explicit_corrector(const ocn_grid *grid, double *u, double *v, const double *U, const double *V, double *U_filtered,
                                             double *V_filtered, double column_depth, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_barotropic_split_explicit_corrector", true);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic(grid, "ocn_barotropic_split_explicit_corrector", true));
     OCN_REQUIRE(u && v && U && V && U_filtered && V_filtered, "ocn_barotropic_split_explicit_corrector: null pointer");
     if (hydrostatic_walls(grid))
         return launch_barotropic_corrector_walls(grid, u, v, U, V, U_filtered, V_filtered, column_depth, as_stream(stream));
@@ -637,16 +612,14 @@ int ocn_barotropic_split_explicit_corrector(const ocn_grid *grid, double *u, dou
 }
 int ocn_fill_free_surface_halos(const ocn_grid *grid, double *eta, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_fill_free_surface_halos", true);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic(grid, "ocn_fill_free_surface_halos", true));
     OCN_REQUIRE(eta, "ocn_fill_free_surface_halos: null pointer");
     if (hydrostatic_walls(grid)) return launch_plane_halo_walls(grid, eta, as_stream(stream));
     return launch_plane_halo(grid, eta, as_stream(stream));
 }
 int ocn_compute_w_from_continuity(const ocn_grid *grid, const double *u, const double *v, double *w, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_compute_w_from_continuity", true);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic(grid, "ocn_compute_w_from_continuity", true));
     OCN_REQUIRE(u && v && w, "ocn_compute_w_from_continuity: null field pointer");
     if (hydrostatic_walls(grid)) return launch_w_from_continuity_walls(grid, u, v, w, as_stream(stream));
     return launch_w_from_continuity(grid, u, v, w, as_stream(stream));
@@ -654,8 +627,7 @@ int ocn_compute_w_from_continuity(const ocn_grid *grid, const double *u, const d
 int ocn_add_barotropic_pressure_gradient(const ocn_grid *grid, double gravitational_acceleration, const double *eta, double *Gu, double *Gv,
                                          void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_add_barotropic_pressure_gradient", true);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic(grid, "ocn_add_barotropic_pressure_gradient", true));
     OCN_REQUIRE(eta && Gu && Gv, "ocn_add_barotropic_pressure_gradient: null pointer");
     if (hydrostatic_walls(grid)) return launch_barotropic_gradient_walls(grid, gravitational_acceleration, eta, Gu, Gv, as_stream(stream));
     return launch_barotropic_gradient(grid, gravitational_acceleration, eta, Gu, Gv, as_stream(stream));
@@ -663,8 +635,7 @@ int ocn_add_barotropic_pressure_gradient(const ocn_grid *grid, double gravitatio
 int ocn_explicit_free_surface_ab2_step(const ocn_grid *grid, const double *w, double *eta, double *G_eta, const double *G_eta_previous,
                                        double dt, double chi, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_explicit_free_surface_ab2_step", true);  // (w and η share x / y extents: one kernel)
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic(grid, "ocn_explicit_free_surface_ab2_step", true));  // (w and η share x / y extents: one kernel)
     OCN_REQUIRE(w && eta && G_eta && G_eta_previous, "ocn_explicit_free_surface_ab2_step: null pointer");
     return launch_free_surface_ab2(grid, w, eta, G_eta, G_eta_previous, dt, chi, as_stream(stream));
 }
@@ -672,8 +643,7 @@ int ocn_explicit_free_surface_ab2_step(const ocn_grid *grid, const double *w, do
 // ---- ImmersedBoundaryGrid(grid, GridFittedBottom(h)) on a (Periodic, Periodic, Bounded) grid (immersed.hip)
 static int validate_immersed(const ocn_grid *grid, const char *who)
 {
-    int st = validate_hydrostatic(grid, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic(grid, who));
     OCN_REQUIRE(grid->tx == OCN_PERIODIC, "%s: an immersed grid cannot be partitioned (FullyConnected x)", who);
     OCN_REQUIRE(grid->Hz >= 1, "%s: needs a z halo", who);
     return OCN_SUCCESS;
@@ -682,8 +652,7 @@ int ocn_immersed_compute_bottom(const ocn_grid *grid, int32_t interface_conditio
                                 const double *z_faces, double *bottom_height, int32_t *kbot, double *Hcc, double *Hfc, double *Hcf,
                                 void *stream)
 {
-    int st = validate_immersed(grid, "ocn_immersed_compute_bottom");
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_immersed(grid, "ocn_immersed_compute_bottom"));
     OCN_REQUIRE(interface_condition == 0 || interface_condition == 1, "ocn_immersed_compute_bottom: immersed condition %d is neither 0 (Center) nor 1 (Interface)",
                 (int)interface_condition);
     OCN_REQUIRE(h && z_centers && z_faces && bottom_height && kbot && Hcc && Hfc && Hcf, "ocn_immersed_compute_bottom: null pointer");
@@ -692,14 +661,12 @@ int ocn_immersed_compute_bottom(const ocn_grid *grid, int32_t interface_conditio
 int ocn_immersed_mask_fields(const ocn_grid *grid, const int32_t *kbot, int32_t n, double *const *fields, const int32_t *locs, double value,
                              double *eta, double *U, double *V, void *stream)
 {
-    int st = validate_immersed(grid, "ocn_immersed_mask_fields");
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_immersed(grid, "ocn_immersed_mask_fields"));
     OCN_REQUIRE(kbot, "ocn_immersed_mask_fields: null kbot");
     FieldTuple ft;
     ft.n = 0;
     if (n != 0) {
-        st = make_field_tuple(grid, fields, locs, n, ft);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(make_field_tuple(grid, fields, locs, n, ft));
     }
     OCN_REQUIRE(n != 0 || eta || U || V, "ocn_immersed_mask_fields: nothing to mask");
     return launch_immersed_mask(grid, kbot, ft, value, eta, U, V, as_stream(stream));
@@ -708,16 +675,14 @@ int ocn_immersed_vector_invariant_momentum_tendencies(const ocn_grid *grid, cons
                                                       const double *w, double *Gu, double *Gv, const double *eta,
                                                       double gravitational_acceleration, void *stream)
 {
-    int st = validate_immersed(grid, "ocn_immersed_vector_invariant_momentum_tendencies");
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_immersed(grid, "ocn_immersed_vector_invariant_momentum_tendencies"));
     OCN_REQUIRE(kbot && u && v && w && Gu && Gv, "ocn_immersed_vector_invariant_momentum_tendencies: null pointer");
     return launch_vector_invariant_immersed(grid, kbot, u, v, w, Gu, Gv, eta, gravitational_acceleration, as_stream(stream));
 }
 int ocn_immersed_add_viscous_terms(const ocn_grid *grid, const int32_t *kbot, double nu, const double *u, const double *v, const double *w,
                                    double *Gu, double *Gv, void *stream)
 {
-    int st = validate_immersed(grid, "ocn_immersed_add_viscous_terms");
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_immersed(grid, "ocn_immersed_add_viscous_terms"));
     OCN_REQUIRE(kbot && u && v && w && Gu && Gv, "ocn_immersed_add_viscous_terms: null pointer");
     OCN_REQUIRE(std::isfinite(nu) && nu >= 0, "ocn_immersed_add_viscous_terms: nu = %g must be finite and >= 0", nu);
     return launch_viscosity_immersed(grid, kbot, nu, u, v, w, Gu, Gv, as_stream(stream));
@@ -725,8 +690,7 @@ int ocn_immersed_add_viscous_terms(const ocn_grid *grid, const int32_t *kbot, do
 int ocn_immersed_tracer_tendency(const ocn_grid *grid, const int32_t *kbot, int32_t closure, double kappa, const double *u, const double *v,
                                  const double *w, const double *c, double *Gc, void *stream)
 {
-    int st = validate_immersed(grid, "ocn_immersed_tracer_tendency");
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_immersed(grid, "ocn_immersed_tracer_tendency"));
     OCN_REQUIRE(kbot && u && v && w && c && Gc, "ocn_immersed_tracer_tendency: null pointer");
     OCN_REQUIRE(closure == 0 || closure == 1, "ocn_immersed_tracer_tendency: closure must be 0 (none) or 1 (ScalarDiffusivity), got %d", (int)closure);
     OCN_REQUIRE(!closure || (std::isfinite(kappa) && kappa >= 0), "ocn_immersed_tracer_tendency: kappa = %g must be finite and >= 0", kappa);
@@ -735,8 +699,7 @@ int ocn_immersed_tracer_tendency(const ocn_grid *grid, const int32_t *kbot, int3
 int ocn_immersed_split_explicit_forcing(const ocn_grid *grid, const int32_t *kbot, const double *Gu, const double *Gu_previous,
                                         const double *Gv, const double *Gv_previous, double chi, double *GU, double *GV, void *stream)
 {
-    int st = validate_immersed(grid, "ocn_immersed_split_explicit_forcing");
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_immersed(grid, "ocn_immersed_split_explicit_forcing"));
     OCN_REQUIRE(kbot && Gu && Gu_previous && Gv && Gv_previous && GU && GV, "ocn_immersed_split_explicit_forcing: null pointer");
     return launch_split_explicit_forcing_immersed(grid, kbot, Gu, Gu_previous, Gv, Gv_previous, chi, GU, GV, as_stream(stream));
 }
@@ -745,8 +708,7 @@ int ocn_immersed_split_explicit_substeps(const ocn_grid *grid, const int32_t *kb
                                          double *V, double *eta_filtered, double *U_filtered, double *V_filtered, const double *GU,
                                          const double *GV, void *stream)
 {
-    int st = validate_immersed(grid, "ocn_immersed_split_explicit_substeps");
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_immersed(grid, "ocn_immersed_split_explicit_substeps"));
     OCN_REQUIRE(n >= 1 && weights, "ocn_immersed_split_explicit_substeps: needs n >= 1 averaging weights (host array)");
     OCN_REQUIRE(kbot && Hfc && Hcf && eta && U && V && eta_filtered && U_filtered && V_filtered && GU && GV,
                 "ocn_immersed_split_explicit_substeps: null pointer");
@@ -756,16 +718,14 @@ int ocn_immersed_split_explicit_substeps(const ocn_grid *grid, const int32_t *kb
 int ocn_immersed_barotropic_corrector(const ocn_grid *grid, const double *Hfc, const double *Hcf, double *u, double *v, const double *U,
                                       const double *V, double *U_filtered, double *V_filtered, void *stream)
 {
-    int st = validate_immersed(grid, "ocn_immersed_barotropic_corrector");
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_immersed(grid, "ocn_immersed_barotropic_corrector"));
     OCN_REQUIRE(Hfc && Hcf && u && v && U && V && U_filtered && V_filtered, "ocn_immersed_barotropic_corrector: null pointer");
     return launch_barotropic_corrector_immersed(grid, Hfc, Hcf, u, v, U, V, U_filtered, V_filtered, as_stream(stream));
 }
 
 static int validate_amd(const ocn_grid *grid)
 {
-    int st = validate_grid_any(grid);  // Bounded x / y: the kernel takes per-field parent layouts
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));  // Bounded x / y: the kernel takes per-field parent layouts
     OCN_REQUIRE(grid->tz != OCN_FLAT, "AnisotropicMinimumDissipation needs a non-Flat z");
     OCN_REQUIRE((grid->tx == OCN_FLAT || grid->Hx >= 1) && (grid->ty == OCN_FLAT || grid->Hy >= 1) && grid->Hz >= 1,
                 "AnisotropicMinimumDissipation needs halo >= 1");
@@ -775,8 +735,7 @@ static int validate_amd(const ocn_grid *grid)
 int ocn_compute_amd_viscosity(const ocn_grid *grid, double C_nu, const double *u, const double *v, const double *w, double *nu_e,
                               void *stream)
 {
-    int st = validate_amd(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_amd(grid));
     OCN_REQUIRE(u && v && w && nu_e, "ocn_compute_amd_viscosity: null field pointer");
     return OCN_LAUNCH(grid, launch_amd_viscosity, grid, C_nu, u, v, w, nu_e, as_stream(stream));
 }
@@ -785,8 +744,7 @@ int ocn_compute_amd_diffusivities(const ocn_grid *grid, double C_nu, const doubl
                                   double *nu_e, int32_t n_tracers, const double *C_kappa, const double *const *tracers,
                                   double *const *kappa_e, void *stream)
 {
-    int st = validate_amd(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_amd(grid));
     OCN_REQUIRE(u && v && w && nu_e, "ocn_compute_amd_diffusivities: null field pointer");
     OCN_REQUIRE(n_tracers >= 0 && n_tracers <= 4, "ocn_compute_amd_diffusivities: n_tracers = %d outside 0..4", n_tracers);
     OCN_REQUIRE(n_tracers == 0 || (C_kappa && tracers && kappa_e), "ocn_compute_amd_diffusivities: null tracer arrays");
@@ -798,8 +756,7 @@ int ocn_compute_amd_diffusivities_range(const ocn_grid *grid, double C_nu, const
                                         double *nu_e, int32_t n_tracers, const double *C_kappa, const double *const *tracers,
                                         double *const *kappa_e, int32_t i_first, int32_t i_last, void *stream)
 {
-    int st = validate_amd(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_amd(grid));
     OCN_REQUIRE(u && v && w && nu_e, "ocn_compute_amd_diffusivities_range: null field pointer");
     OCN_REQUIRE(n_tracers >= 0 && n_tracers <= 4, "ocn_compute_amd_diffusivities_range: n_tracers = %d outside 0..4", n_tracers);
     OCN_REQUIRE(n_tracers == 0 || (C_kappa && tracers && kappa_e), "ocn_compute_amd_diffusivities_range: null tracer arrays");
@@ -813,8 +770,7 @@ int ocn_compute_amd_diffusivities_range(const ocn_grid *grid, double C_nu, const
 int ocn_compute_amd_diffusivity(const ocn_grid *grid, double C_kappa, const double *u, const double *v, const double *w,
                                 const double *c, double *kappa_e, void *stream)
 {
-    int st = validate_amd(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_amd(grid));
     OCN_REQUIRE(u && v && w && c && kappa_e, "ocn_compute_amd_diffusivity: null field pointer");
     return OCN_LAUNCH(grid, launch_amd_diffusivity, grid, C_kappa, u, v, w, c, kappa_e, as_stream(stream));
 }
@@ -823,8 +779,7 @@ int ocn_compute_smagorinsky_diffusivities(const ocn_grid *grid, const ocn_model_
                                           const double *u, const double *v, const double *w, double *nu_e, double *const *kappa_e,
                                           void *stream)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     OCN_REQUIRE(grid->tz != OCN_FLAT, "Smagorinsky needs a non-Flat z");
     OCN_REQUIRE((grid->tx == OCN_FLAT || grid->Hx >= 1) && (grid->ty == OCN_FLAT || grid->Hy >= 1) && grid->Hz >= 1, "Smagorinsky needs halo >= 1");
     OCN_REQUIRE(terms && closure, "ocn_compute_smagorinsky_diffusivities: null terms / closure");
@@ -857,8 +812,7 @@ static int validate_particles(const char *who, const ocn_grid *grid, const ocn_p
                               const double *const *tracked_fields, const int32_t *tracked_locs, double *const *tracked_out)
 {
     OCN_REQUIRE(n >= 0, "%s: negative particle count %lld", who, (long long)n);
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     if (partitioned_x(grid)) {
         set_error("%s: particles on a partitioned x (topology code %d) are not supported", who, grid->tx);
         return OCN_ERR_UNSUPPORTED;
@@ -932,8 +886,7 @@ int ocn_op_reduce(const ocn_grid *grid, const ocn_op_program *program, int32_t d
 
 int ocn_update_hydrostatic_pressure(const ocn_grid *grid, const ocn_model_terms *terms, double *pHY, void *stream)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     OCN_REQUIRE(terms != nullptr && pHY != nullptr, "ocn_update_hydrostatic_pressure: null argument");
     OCN_REQUIRE(terms->buoyancy != OCN_BUOYANCY_NONE, "ocn_update_hydrostatic_pressure: buoyancy is nothing");
     if (terms->buoyancy != OCN_BUOYANCY_SEAWATER_S) OCN_REQUIRE(terms->T != nullptr, "T (or b) tracer is NULL");
@@ -946,8 +899,7 @@ int ocn_update_hydrostatic_pressure(const ocn_grid *grid, const ocn_model_terms 
 int ocn_update_hydrostatic_pressure_range(const ocn_grid *grid, const ocn_model_terms *terms, double *pHY, int32_t i_first, int32_t i_last,
                                           void *stream)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     OCN_REQUIRE(terms != nullptr && pHY != nullptr, "ocn_update_hydrostatic_pressure_range: null argument");
     OCN_REQUIRE(terms->buoyancy != OCN_BUOYANCY_NONE, "ocn_update_hydrostatic_pressure_range: buoyancy is nothing");
     if (terms->buoyancy != OCN_BUOYANCY_SEAWATER_S) OCN_REQUIRE(terms->T != nullptr, "T (or b) tracer is NULL");
@@ -1019,19 +971,15 @@ static int momentum_tendencies_terms_rk3(const char *who, const ocn_grid *grid, 
                                          double dt, double gamma, double zeta, int32_t has_zeta, const int32_t *range, void *stream)
 {
     MomentumOptions o;
-    int st = momentum_options(who, grid, stokes, forcing, o);
-    if (st != OCN_SUCCESS) return st;
-    st = validate_terms(grid, terms);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(momentum_options(who, grid, stokes, forcing, o));
+    OCN_TRY(validate_terms(grid, terms));
     OCN_REQUIRE(xy_periodic(grid) || !range, "%s: ranges need Periodic x and y", who);
     OCN_REQUIRE(u && v && w && Gu && Gv && Gw && u_out && v_out && w_out, "%s: null field pointer", who);
     OCN_REQUIRE(!has_zeta || (Gmu && Gmv && Gmw), "%s: G⁻ pointers are required when has_zeta != 0", who);
     OCN_REQUIRE(u_out != u && v_out != v && w_out != w, "%s: outputs must not alias the inputs", who);
     MomentumFinal mf{};
-    st = flux_side(grid, bcs_u, "u", mf.bottom[0], mf.top[0]);
-    if (st != OCN_SUCCESS) return st;
-    st = flux_side(grid, bcs_v, "v", mf.bottom[1], mf.top[1]);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(flux_side(grid, bcs_u, "u", mf.bottom[0], mf.top[0]));
+    OCN_TRY(flux_side(grid, bcs_v, "v", mf.bottom[1], mf.top[1]));
     mf.sub[0] = SubstepDev{Gmu, u_out};
     mf.sub[1] = SubstepDev{Gmv, v_out};
     mf.sub[2] = SubstepDev{Gmw, w_out};
@@ -1041,8 +989,7 @@ static int momentum_tendencies_terms_rk3(const char *who, const ocn_grid *grid, 
     if (!xy_periodic(grid)) {
         // walls in x / y: advection (box + frames), then the finishing pass in the reference's order with the boundary fluxes and the substep --
         // inside the tiled kernel on the interior box, as per-cell kernels on the frames (general.hip)
-        st = launch_advective_momentum(terms->advection, grid, u, v, w, Gu, Gv, Gw, nullptr, s);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(launch_advective_momentum(terms->advection, grid, u, v, w, Gu, Gv, Gw, nullptr, s));
         return OCN_LAUNCH(grid, launch_momentum_extra_general, grid, t, u, v, w, Gu, Gv, Gw, nullptr, s, &mf, o.stokes, o.forcing);
     }
     static const bool extra_first = !(std::getenv("OCN_EXTRA_FIRST") && std::getenv("OCN_EXTRA_FIRST")[0] == '0');
@@ -1055,14 +1002,12 @@ static int momentum_tendencies_terms_rk3(const char *who, const ocn_grid *grid, 
         MomentumFinal pre = mf;
         pre.pre = 1;
         pre.sc.on = 0;
-        st = OCN_LAUNCH(grid, launch_momentum_extra, grid, t, u, v, w, Gu, Gv, Gw, range, s, &pre, o.stokes, o.forcing);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(OCN_LAUNCH(grid, launch_momentum_extra, grid, t, u, v, w, Gu, Gv, Gw, range, s, &pre, o.stokes, o.forcing));
         FuseArgs fz = substep_fuse(Gmu, Gmv, Gmw, u_out, v_out, w_out, dt, gamma, zeta, has_zeta);
         fz.acc = 1;
         return OCN_LAUNCH_SCHEME(grid, terms->advection, launch_momentum_tendencies, grid, u, v, w, Gu, Gv, Gw, range, &fz, s);
     }
-    st = launch_advective_momentum(terms->advection, grid, u, v, w, Gu, Gv, Gw, range, s);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(launch_advective_momentum(terms->advection, grid, u, v, w, Gu, Gv, Gw, range, s));
     return OCN_LAUNCH(grid, launch_momentum_extra, grid, t, u, v, w, Gu, Gv, Gw, range, s, &mf, o.stokes, o.forcing);
 }
 
@@ -1107,8 +1052,7 @@ static int make_tracer_fuse(const ocn_grid *grid, const ocn_model_terms *terms, 
     tf.kappa = kappa;
     tf.kappa_e = kappa_e;
     if (!sub) return OCN_SUCCESS;  // (the tendency alone: ocn_apply_flux_bcs adds the boundary fluxes)
-    int st = flux_side(grid, bcs_c, "tracer", tf.bottom, tf.top);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(flux_side(grid, bcs_c, "tracer", tf.bottom, tf.top));
     tf.sub = *sub;
     tf.sc = sc;
     return OCN_SUCCESS;
@@ -1125,11 +1069,9 @@ static int tracer_tendency_terms(const char *who, const ocn_grid *grid, const oc
 {
     if (forcing) {
         OCN_REQUIRE(grid != nullptr, "grid is NULL");
-        int st = validate_forcing(grid, forcing, who, "the tracer");
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(validate_forcing(grid, forcing, who, "the tracer"));
     }
-    int st = validate_terms(grid, terms);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_terms(grid, terms));
     if (sub) {
         OCN_REQUIRE(xy_periodic(grid) || !range, "%s: ranges need Periodic x and y", who);
         OCN_REQUIRE(terms->advection != OCN_ADVECTION_CENTERED2, "%s: advection must be WENO5 or UpwindBiased5", who);
@@ -1141,8 +1083,7 @@ static int tracer_tendency_terms(const char *who, const ocn_grid *grid, const oc
     }
     OCN_REQUIRE(!kappa_e || terms->closure == 2, "kappa_e is only meaningful with closure == 2");
     TracerFuse tf;
-    st = make_tracer_fuse(grid, terms, kappa, kappa_e, bcs_c, sub, sc, tf);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_tracer_fuse(grid, terms, kappa, kappa_e, bcs_c, sub, sc, tf));
     const ocn::ForcingDev fd = ocn::to_dev(forcing);
     const bool forced = fd.n > 0, periodic = xy_periodic(grid);
     hipStream_t s = as_stream(stream);
@@ -1150,7 +1091,7 @@ static int tracer_tendency_terms(const char *who, const ocn_grid *grid, const oc
     // where the interior box adds advection and diffusion before its store -- the diffusion alone ride along
     if (sub || (forced ? !(periodic && terms->advection == OCN_ADVECTION_CENTERED2) : (!periodic && terms->closure)))
         return launch_advective_tracer(terms->advection, grid, u, v, w, c, Gc, range, s, &tf, forced ? &fd : nullptr);
-    st = launch_advective_tracer(terms->advection, grid, u, v, w, c, Gc, range, s, nullptr);
+    int st = launch_advective_tracer(terms->advection, grid, u, v, w, c, Gc, range, s, nullptr);
     if (st == OCN_SUCCESS && terms->closure) st = OCN_LAUNCH(grid, launch_tracer_diffusion, grid, kappa, kappa_e, c, Gc, range, s);
     if (st == OCN_SUCCESS && forced) st = OCN_LAUNCH(grid, launch_tracer_forcing, grid, fd, c, Gc, range, nullptr, s);
     return st;
@@ -1196,8 +1137,7 @@ int ocn_compute_tracer_pair_tendency_terms_rk3(const ocn_grid *grid, const ocn_m
                                                double dt, double gamma, double zeta, int32_t has_zeta, const int32_t *range,
                                                int32_t *launched, void *stream)
 {
-    int st = validate_terms(grid, terms);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_terms(grid, terms));
     OCN_REQUIRE(launched, "ocn_compute_tracer_pair_tendency_terms_rk3: launched is NULL");
     *launched = 0;
     if (!xy_periodic(grid)) return OCN_SUCCESS;  // walls in x / y: one tracer per launch (ocn_compute_tracer_tendency_terms_rk3)
@@ -1209,12 +1149,11 @@ int ocn_compute_tracer_pair_tendency_terms_rk3(const ocn_grid *grid, const ocn_m
         OCN_REQUIRE(!has_zeta || (Gc_previous && Gc_previous[t]), "ocn_compute_tracer_pair_tendency_terms_rk3: G⁻ is required when has_zeta != 0");
         OCN_REQUIRE(!(kappa_e && kappa_e[t]) || terms->closure == 2, "kappa_e is only meaningful with closure == 2");
         const SubstepDev sub{Gc_previous ? Gc_previous[t] : nullptr, c_out[t]};
-        st = make_tracer_fuse(grid, terms, kappa[t], kappa_e ? kappa_e[t] : nullptr, bcs_c ? bcs_c[t] : nullptr, &sub,
-                              SubstepCoef{dt, gamma, zeta, 1, has_zeta ? 1 : 0}, tf[t]);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(make_tracer_fuse(grid, terms, kappa[t], kappa_e ? kappa_e[t] : nullptr, bcs_c ? bcs_c[t] : nullptr, &sub,
+                                 SubstepCoef{dt, gamma, zeta, 1, has_zeta ? 1 : 0}, tf[t]));
     }
     int did = 0;
-    st = OCN_LAUNCH_SCHEME(grid, terms->advection, launch_tracer_pair_tendency, grid, u, v, w, c, Gc, range, as_stream(stream), tf, &did);
+    const int st = OCN_LAUNCH_SCHEME(grid, terms->advection, launch_tracer_pair_tendency, grid, u, v, w, c, Gc, range, as_stream(stream), tf, &did);
     *launched = did;
     return st;
 }
@@ -1223,8 +1162,7 @@ int ocn_split_explicit_substeps_blocked(const ocn_grid *grid, int32_t n, const d
                                         double column_depth, double *eta, double *U, double *V, double *eta_filtered, double *U_filtered,
                                         double *V_filtered, const double *GU, const double *GV, double *work, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_split_explicit_substeps_blocked");
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic(grid, "ocn_split_explicit_substeps_blocked"));
     OCN_REQUIRE_PERIODIC_X("ocn_split_explicit_substeps_blocked");
     OCN_REQUIRE(n >= 1 && weights, "ocn_split_explicit_substeps_blocked: needs n >= 1 averaging weights (host array)");
     OCN_REQUIRE(eta && U && V && eta_filtered && U_filtered && V_filtered && GU && GV && work, "ocn_split_explicit_substeps_blocked: null pointer");
@@ -1235,8 +1173,7 @@ int ocn_split_explicit_substeps_blocked(const ocn_grid *grid, int32_t n, const d
 int ocn_implicit_free_surface_rhs(const ocn_grid *grid, const double *u, const double *v, const double *eta, double gravitational_acceleration,
                                   double dt, double *Qu, double *Qv, double *rhs, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_implicit_free_surface_rhs", true);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic(grid, "ocn_implicit_free_surface_rhs", true));
     OCN_REQUIRE(grid->tx != OCN_FULLY_CONNECTED, "ocn_implicit_free_surface_rhs wraps x periodically: not for a partitioned (FullyConnected) x");
     OCN_REQUIRE(u && v && eta && Qu && Qv && rhs, "ocn_implicit_free_surface_rhs: null pointer");
     OCN_REQUIRE(dt > 0, "ocn_implicit_free_surface_rhs: dt must be positive");
@@ -1247,8 +1184,7 @@ int ocn_implicit_free_surface_rhs(const ocn_grid *grid, const double *u, const d
 int ocn_barotropic_pressure_correction(const ocn_grid *grid, double *u, double *v, const double *eta, double gravitational_acceleration,
                                        double dt, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_barotropic_pressure_correction", true);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic(grid, "ocn_barotropic_pressure_correction", true));
     OCN_REQUIRE(u && v && eta, "ocn_barotropic_pressure_correction: null pointer");
     if (hydrostatic_walls(grid))
         return launch_barotropic_pressure_correction_walls(grid, u, v, eta, gravitational_acceleration, dt, as_stream(stream));
@@ -1259,8 +1195,7 @@ int ocn_split_explicit_substeps_ab3(const ocn_grid *grid, int32_t n, const doubl
                                     double column_depth, const double *coefficients, double *eta, double *U, double *V, double *eta_filtered,
                                     double *U_filtered, double *V_filtered, const double *GU, const double *GV, double *work, void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_split_explicit_substeps_ab3");
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic(grid, "ocn_split_explicit_substeps_ab3"));
     OCN_REQUIRE_PERIODIC_X("ocn_split_explicit_substeps_ab3");
     OCN_REQUIRE(n >= 1 && weights && coefficients, "ocn_split_explicit_substeps_ab3: needs n >= 1 weights and the 7 AB3 coefficients (host arrays)");
     OCN_REQUIRE(eta && U && V && eta_filtered && U_filtered && V_filtered && GU && GV && work, "ocn_split_explicit_substeps_ab3: null pointer");
@@ -1270,8 +1205,7 @@ int ocn_split_explicit_substeps_ab3(const ocn_grid *grid, int32_t n, const doubl
 
 static int validate_hydrostatic_slab(const ocn_grid *grid, const char *who)
 {
-    int st = validate_grid(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid(grid));
     OCN_REQUIRE((grid->tx == OCN_PERIODIC || grid->tx == OCN_FULLY_CONNECTED) && grid->ty == OCN_PERIODIC && grid->tz == OCN_BOUNDED,
                 "%s: (Periodic | FullyConnected, Periodic, Bounded) grids", who);
     return OCN_SUCCESS;
@@ -1279,8 +1213,7 @@ static int validate_hydrostatic_slab(const ocn_grid *grid, const char *who)
 int ocn_split_explicit_dist_begin(const ocn_grid *grid, int32_t n, const double *eta, const double *U, const double *V, const double *GU,
                                   const double *GV, double *work, double *send_west, double *send_east, void *stream)
 {
-    int st = validate_hydrostatic_slab(grid, "ocn_split_explicit_dist_begin");
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic_slab(grid, "ocn_split_explicit_dist_begin"));
     OCN_REQUIRE(n >= 1 && n <= grid->Nx, "ocn_split_explicit_dist_begin: the number of substeps (%d) must not exceed the slab's Nx (%d): the extended halo "
                 "would reach past the neighbouring rank", n, grid->Nx);
     OCN_REQUIRE(eta && U && V && GU && GV && work && send_west && send_east, "ocn_split_explicit_dist_begin: null pointer");
@@ -1290,8 +1223,7 @@ int ocn_split_explicit_dist_run(const ocn_grid *grid, int32_t n, const double *w
                                 double column_depth, double *eta, double *U, double *V, double *work, const double *recv_west,
                                 const double *recv_east, void *stream)
 {
-    int st = validate_hydrostatic_slab(grid, "ocn_split_explicit_dist_run");
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic_slab(grid, "ocn_split_explicit_dist_run"));
     OCN_REQUIRE(n >= 1 && n <= grid->Nx && weights, "ocn_split_explicit_dist_run: needs 1 <= n <= Nx averaging weights (host array)");
     OCN_REQUIRE(eta && U && V && work && recv_west && recv_east, "ocn_split_explicit_dist_run: null pointer");
     return launch_split_explicit_dist_run(grid, n, n, weights, dtau, gravitational_acceleration, column_depth, eta, U, V, work, recv_west,
@@ -1304,10 +1236,8 @@ int ocn_hydrostatic_momentum_ab2_step(const ocn_grid *grid, const ocn_model_term
                                       double chi, int32_t euler, const double *eta, double gravitational_acceleration, double *GU,
                                       double *GV, double *U_star, double *V_star, void *stream)
 {
-    int st = validate_hydrostatic_slab(grid, "ocn_hydrostatic_momentum_ab2_step");
-    if (st != OCN_SUCCESS) return st;
-    st = validate_terms(grid, terms);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic_slab(grid, "ocn_hydrostatic_momentum_ab2_step"));
+    OCN_TRY(validate_terms(grid, terms));
     OCN_REQUIRE(grid->Hz >= 1, "ocn_hydrostatic_momentum_ab2_step: needs a z halo");
     OCN_REQUIRE(terms->closure != 2, "ocn_hydrostatic_momentum_ab2_step: eddy-viscosity closures are not supported");
     OCN_REQUIRE(u && v && w && Gu && Gv && u_out && v_out, "ocn_hydrostatic_momentum_ab2_step: null field pointer");
@@ -1316,10 +1246,8 @@ int ocn_hydrostatic_momentum_ab2_step(const ocn_grid *grid, const ocn_model_term
     OCN_REQUIRE((GU && GV && U_star && V_star) || (!GU && !GV && !U_star && !V_star),
                 "ocn_hydrostatic_momentum_ab2_step: GU, GV, U_star, V_star go together (all or none)");
     MomentumFinal mf{};
-    st = flux_side(grid, bcs_u, "u", mf.bottom[0], mf.top[0]);
-    if (st != OCN_SUCCESS) return st;
-    st = flux_side(grid, bcs_v, "v", mf.bottom[1], mf.top[1]);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(flux_side(grid, bcs_u, "u", mf.bottom[0], mf.top[0]));
+    OCN_TRY(flux_side(grid, bcs_v, "v", mf.bottom[1], mf.top[1]));
     mf.sub[0] = SubstepDev{Gu_previous, u_out};
     mf.sub[1] = SubstepDev{Gv_previous, v_out};
     if (euler) chi = -0.5;
@@ -1333,8 +1261,7 @@ int ocn_barotropic_corrector_and_w(const ocn_grid *grid, const double *u_star, c
                                    const double *U, const double *V, const double *U_star, const double *V_star, double column_depth,
                                    void *stream)
 {
-    int st = validate_hydrostatic(grid, "ocn_barotropic_corrector_and_w");
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_hydrostatic(grid, "ocn_barotropic_corrector_and_w"));
     OCN_REQUIRE(u_star && v_star && u && v && w, "ocn_barotropic_corrector_and_w: null field pointer");
     OCN_REQUIRE(u != u_star && v != v_star, "ocn_barotropic_corrector_and_w: the outputs must not alias the inputs");
     OCN_REQUIRE((U && V && U_star && V_star) || (!U && !V), "ocn_barotropic_corrector_and_w: U, V, U_star, V_star go together");
@@ -1345,11 +1272,9 @@ int ocn_fill_halo_regions_bcs(const ocn_grid *grid, double *const *fields, const
                               const ocn_field_bcs *const *bcs, int32_t n, int32_t fill_boundary_normal_velocities,
                               void *stream)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     FieldTuple ft;
-    st = make_field_tuple(grid, fields, locs, n, ft);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_field_tuple(grid, fields, locs, n, ft));
     if (!xy_periodic(grid)) {  // every side may carry a condition (fill_halo_regions_value_gradient.jl for west / east / south / north too)
         SideBcTuple sb{};
         bool any = false;
@@ -1373,21 +1298,17 @@ int ocn_fill_halo_regions_bcs(const ocn_grid *grid, double *const *fields, const
     }
     ZBcTuple z;
     bool any;
-    st = make_zbc_tuple(grid, locs, bcs, n, z, false, any);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_zbc_tuple(grid, locs, bcs, n, z, false, any));
     return launch_fill_halos(grid, ft, fill_boundary_normal_velocities, -1, as_stream(stream), any ? &z : nullptr);
 }
 
 int ocn_apply_flux_bcs(const ocn_grid *grid, double *const *G, const double *const *fields, const int32_t *locs,
                        const ocn_field_bcs *const *bcs, int32_t n, void *stream)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     FieldTuple gt, ft;
-    st = make_field_tuple(grid, G, locs, n, gt);
-    if (st != OCN_SUCCESS) return st;
-    st = make_field_tuple(grid, const_cast<double *const *>(fields), locs, n, ft);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_field_tuple(grid, G, locs, n, gt));
+    OCN_TRY(make_field_tuple(grid, const_cast<double *const *>(fields), locs, n, ft));
     if (!xy_periodic(grid)) {  // apply_x_bcs!, apply_y_bcs!, then apply_z_bcs! (compute_nonhydrostatic_tendencies.jl:204-213)
         SideBcTuple sb{};
         ZBcTuple z{};
@@ -1413,15 +1334,13 @@ int ocn_apply_flux_bcs(const ocn_grid *grid, double *const *G, const double *con
             }
         }
         if (any_xy) {
-            st = launch_apply_flux_bcs_lateral(grid, gt, ft, sb, as_stream(stream));
-            if (st != OCN_SUCCESS) return st;
+            OCN_TRY(launch_apply_flux_bcs_lateral(grid, gt, ft, sb, as_stream(stream)));
         }
         return any_z ? launch_apply_flux_bcs(grid, gt, ft, z, as_stream(stream)) : OCN_SUCCESS;
     }
     ZBcTuple z;
     bool any;
-    st = make_zbc_tuple(grid, locs, bcs, n, z, true, any);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_zbc_tuple(grid, locs, bcs, n, z, true, any));
     if (!any) return OCN_SUCCESS;
     return launch_apply_flux_bcs(grid, gt, ft, z, as_stream(stream));
 }
@@ -1429,8 +1348,7 @@ int ocn_apply_flux_bcs(const ocn_grid *grid, double *const *G, const double *con
 int ocn_compute_tracer_tendency(const ocn_grid *grid, const double *u, const double *v, const double *w, const double *c,
                                 double *Gc, const int32_t *range, void *stream)
 {
-    int st = validate_weno(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_weno(grid));
     OCN_REQUIRE(u && v && w && c && Gc, "ocn_compute_tracer_tendency: null field pointer");
     if (!xy_periodic(grid)) return OCN_LAUNCH(grid, launch_tracer_tendency_general, grid, 0, u, v, w, c, Gc, range, as_stream(stream));
     return OCN_LAUNCH(grid, launch_tracer_tendency, grid, u, v, w, c, Gc, range, as_stream(stream));
@@ -1455,22 +1373,18 @@ static int make_step_tuple(int32_t n, double *const *U, const double *const *Gn,
 int ocn_rk3_substep(const ocn_grid *grid, int32_t n, double *const *U, const double *const *Gn, const double *const *Gm,
                     const int32_t *locs, double dt, double gamma, double zeta, int32_t has_zeta, void *stream)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     StepTuple t;
-    st = make_step_tuple(n, U, Gn, const_cast<double *const *>(reinterpret_cast<const double *const *>(Gm)), locs, true, t);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_step_tuple(n, U, Gn, const_cast<double *const *>(reinterpret_cast<const double *const *>(Gm)), locs, true, t));
     return launch_stepper(grid, t, has_zeta ? 1 : 0, dt, gamma, zeta, as_stream(stream));
 }
 
 int ocn_split_rk3_substep(const ocn_grid *grid, int32_t n, double *const *U, const double *const *G, const double *const *Psi,
                           const int32_t *locs, double dt, double gamma, double zeta, void *stream)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     StepTuple t;
-    st = make_step_tuple(n, U, G, const_cast<double *const *>(reinterpret_cast<const double *const *>(Psi)), locs, true, t);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_step_tuple(n, U, G, const_cast<double *const *>(reinterpret_cast<const double *const *>(Psi)), locs, true, t));
     for (int f = 0; f < n; ++f) OCN_REQUIRE(Psi[f] != U[f], "ocn_split_rk3_substep: field %d: Psi must not alias U", f);
     return launch_stepper(grid, t, 4, dt, gamma, zeta, as_stream(stream));
 }
@@ -1478,19 +1392,16 @@ int ocn_split_rk3_substep(const ocn_grid *grid, int32_t n, double *const *U, con
 int ocn_ab2_step(const ocn_grid *grid, int32_t n, double *const *U, const double *const *Gn, const double *const *Gm,
                  const int32_t *locs, double dt, double chi, void *stream)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     StepTuple t;
-    st = make_step_tuple(n, U, Gn, const_cast<double *const *>(reinterpret_cast<const double *const *>(Gm)), locs, true, t);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_step_tuple(n, U, Gn, const_cast<double *const *>(reinterpret_cast<const double *const *>(Gm)), locs, true, t));
     const double not_euler = (chi != -0.5) ? 1.0 : 0.0;
     return launch_stepper(grid, t, 2, dt, chi, not_euler, as_stream(stream));
 }
 
 static int validate_vertically_implicit(const ocn_grid *grid, const char *who)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     OCN_REQUIRE(grid->tz == OCN_BOUNDED, "%s: VerticallyImplicitTimeDiscretization can only be specified on grids that are Bounded in the z-direction.", who);
     OCN_REQUIRE((grid->tx == OCN_FLAT || grid->Hx >= 1) && (grid->ty == OCN_FLAT || grid->Hy >= 1) && grid->Hz >= 1, "%s: halo >= 1 required", who);
     return OCN_SUCCESS;
@@ -1501,8 +1412,7 @@ int ocn_add_vertically_implicit_explicit_fluxes(const ocn_grid *grid, double nu,
                                                 double *const *Gc, const int32_t *range, void *stream)
 {
     const char *who = "ocn_add_vertically_implicit_explicit_fluxes";
-    int st = validate_vertically_implicit(grid, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_vertically_implicit(grid, who));
     OCN_REQUIRE(n_tracers >= 0 && n_tracers <= MAX_TUPLE, "%s: number of tracers %d outside 0..%d", who, n_tracers, MAX_TUPLE);
     if (u) {
         OCN_REQUIRE(v && w && Gu && Gv, "%s: null field pointer (u is given: v, w, Gu, Gv are needed; Gw may be NULL)", who);
@@ -1523,8 +1433,7 @@ int ocn_implicit_vertical_diffusion_step(const ocn_grid *grid, int32_t n, double
                                          double dt, void *stream)
 {
     const char *who = "ocn_implicit_vertical_diffusion_step";
-    int st = validate_vertically_implicit(grid, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_vertically_implicit(grid, who));
     OCN_REQUIRE(n >= 1 && n <= MAX_TUPLE, "%s: number of fields %d outside 1..%d", who, n, MAX_TUPLE);
     OCN_REQUIRE(fields && locs && kappa, "%s: null tuple pointer", who);
     OCN_REQUIRE(grid->Nz <= 2048, "%s: Nz = %d > 2048 (the multipliers of a column are kept in LDS)", who, grid->Nz);
@@ -1542,8 +1451,7 @@ int ocn_implicit_vertical_diffusion_step(const ocn_grid *grid, int32_t n, double
 // the three entry points of vertical_diffusivity.hip: a Bounded z, and the x / y neighbours of a κ field are read
 static int validate_vertical_diffusivity(const ocn_grid *grid, const char *who)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     OCN_REQUIRE(grid->tz == OCN_BOUNDED, "%s: needs a grid that is Bounded in the z-direction", who);
     OCN_REQUIRE(grid->tx != OCN_FLAT && grid->ty != OCN_FLAT, "%s: a Flat x or y is not implemented", who);
     OCN_REQUIRE(grid->Hx >= 1 && grid->Hy >= 1 && grid->Hz >= 1, "%s: halo >= 1 required", who);
@@ -1554,13 +1462,11 @@ int ocn_compute_convective_adjustment_diffusivities(const ocn_grid *grid, const 
                                                     const ocn_convective_adjustment *closure, double *kappa_c, double *kappa_u, void *stream)
 {
     const char *who = "ocn_compute_convective_adjustment_diffusivities";
-    int st = validate_vertical_diffusivity(grid, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_vertical_diffusivity(grid, who));
     OCN_REQUIRE(terms && closure, "%s: null terms / closure", who);
     OCN_REQUIRE(kappa_c && kappa_u, "%s: null field pointer", who);
     OCN_REQUIRE(kappa_c != kappa_u, "%s: kappa_c and kappa_u are the same array", who);
-    st = validate_buoyancy_terms(terms, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_buoyancy_terms(terms, who));
     OCN_REQUIRE(std::isfinite(closure->convective_kappa_z) && std::isfinite(closure->convective_nu_z) &&
                     std::isfinite(closure->background_kappa_z) && std::isfinite(closure->background_nu_z),
                 "%s: the four coefficients must be finite", who);
@@ -1572,8 +1478,7 @@ int ocn_add_vertical_diffusivity_fluxes(const ocn_grid *grid, const double *kapp
                                         int32_t boundary_only, const int32_t *range, void *stream)
 {
     const char *who = "ocn_add_vertical_diffusivity_fluxes";
-    int st = validate_vertical_diffusivity(grid, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_vertical_diffusivity(grid, who));
     OCN_REQUIRE(n_tracers >= 0 && n_tracers <= MAX_TUPLE, "%s: number of tracers %d outside 0..%d", who, n_tracers, MAX_TUPLE);
     if (u) {
         OCN_REQUIRE(kappa_u && v && Gu && Gv, "%s: null field pointer (u is given: kappa_u, v, Gu, Gv are needed)", who);
@@ -1591,8 +1496,7 @@ int ocn_implicit_vertical_diffusion_step_fields(const ocn_grid *grid, int32_t n,
                                                 const double *const *kappa, double *const *scratch, double dt, void *stream)
 {
     const char *who = "ocn_implicit_vertical_diffusion_step_fields";
-    int st = validate_vertical_diffusivity(grid, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_vertical_diffusivity(grid, who));
     OCN_REQUIRE(n >= 1 && n <= MAX_TUPLE, "%s: number of fields %d outside 1..%d", who, n, MAX_TUPLE);
     OCN_REQUIRE(fields && locs && kappa && scratch, "%s: null tuple pointer", who);
     OCN_REQUIRE(std::isfinite(dt) && dt >= 0, "%s: dt = %g must be finite and >= 0", who, dt);
@@ -1611,8 +1515,7 @@ int ocn_add_biharmonic_fluxes(const ocn_grid *grid, double nu, const double *u, 
                               const double *neg_other_v, const double *const *neg_other_c, void *stream)
 {
     const char *who = "ocn_add_biharmonic_fluxes";
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     OCN_REQUIRE(grid->tx == OCN_PERIODIC && grid->ty == OCN_PERIODIC,
                 "%s: x and y must be Periodic, got topology (%d, %d, %d) (the biharmonic masks of a wall are not implemented)", who, grid->tx,
                 grid->ty, grid->tz);
@@ -1653,13 +1556,11 @@ int ocn_add_biharmonic_fluxes(const ocn_grid *grid, double nu, const double *u, 
 // isopycnal.hip: everything is checked on the host before the first HIP call
 static int validate_isopycnal(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_isopycnal *closure, const char *who)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     OCN_REQUIRE(grid->tx == OCN_PERIODIC && grid->ty == OCN_PERIODIC && grid->tz == OCN_BOUNDED,
                 "%s: the grid must be (Periodic, Periodic, Bounded), got topology (%d, %d, %d)", who, grid->tx, grid->ty, grid->tz);
     OCN_REQUIRE(grid->Hx >= 1 && grid->Hy >= 1 && grid->Hz >= 1, "%s: halo >= 1 required", who);
-    st = validate_buoyancy_terms(terms, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_buoyancy_terms(terms, who));
     OCN_REQUIRE(closure, "%s: null closure", who);
     OCN_REQUIRE(std::isfinite(closure->max_slope) && closure->max_slope > 0, "%s: max_slope = %g must be finite and > 0", who, closure->max_slope);
     OCN_REQUIRE(!std::isnan(closure->minimum_bz), "%s: minimum_bz is a NaN", who);
@@ -1671,8 +1572,7 @@ int ocn_compute_isopycnal_diffusivities(const ocn_grid *grid, const ocn_model_te
                                         double *const *kz, void *stream)
 {
     const char *who = "ocn_compute_isopycnal_diffusivities";
-    int st = validate_isopycnal(grid, terms, closure, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_isopycnal(grid, terms, closure, who));
     OCN_REQUIRE(eps_R33, "%s: eps_R33 is NULL", who);
     OCN_REQUIRE(n_kz >= 0 && n_kz <= OCN_MODEL_MAX_TRACERS, "%s: n_kz = %d outside 0..%d", who, n_kz, OCN_MODEL_MAX_TRACERS);
     if (n_kz) OCN_REQUIRE(kappa_symmetric && kz, "%s: null kappa_symmetric / kz array", who);
@@ -1703,8 +1603,7 @@ int ocn_compute_isopycnal_diffusivities(const ocn_grid *grid, const ocn_model_te
 int ocn_sum_velocities(const ocn_grid *grid, const double *const *a, const double *const *b, double *const *out, void *stream)
 {
     const char *who = "ocn_sum_velocities";
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     OCN_REQUIRE(a && b && out, "%s: null tuple pointer", who);
     for (int f = 0; f < 3; ++f) OCN_REQUIRE(a[f] && b[f] && out[f], "%s: field %d: null pointer", who, f);
     return launch_sum_velocities(grid, a, b, out, as_stream(stream));
@@ -1714,8 +1613,7 @@ int ocn_add_isopycnal_fluxes(const ocn_grid *grid, const ocn_model_terms *terms,
                              const double *kappa_symmetric, const double *kappa_skew, const double *const *c, double *const *Gc, void *stream)
 {
     const char *who = "ocn_add_isopycnal_fluxes";
-    int st = validate_isopycnal(grid, terms, closure, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_isopycnal(grid, terms, closure, who));
     OCN_REQUIRE(n_tracers >= 1 && n_tracers <= OCN_MODEL_MAX_TRACERS, "%s: number of tracers %d outside 1..%d", who, n_tracers,
                 OCN_MODEL_MAX_TRACERS);
     OCN_REQUIRE(kappa_symmetric && kappa_skew && c && Gc, "%s: null tracer array", who);
@@ -1755,10 +1653,8 @@ static int validate_ri_closure(const ocn_grid *grid, const ocn_ri_based *c, cons
 int ocn_compute_ri_number(const ocn_grid *grid, const ocn_model_terms *terms, const double *u, const double *v, double *Ri, void *stream)
 {
     const char *who = "ocn_compute_ri_number";
-    int st = validate_vertical_diffusivity(grid, who);
-    if (st != OCN_SUCCESS) return st;
-    st = validate_buoyancy_terms(terms, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_vertical_diffusivity(grid, who));
+    OCN_TRY(validate_buoyancy_terms(terms, who));
     OCN_REQUIRE(u && v && Ri, "%s: null field pointer", who);
     return launch_ri_based(0, grid, terms, nullptr, nullptr, nullptr, u, v, nullptr, Ri, nullptr, nullptr, as_stream(stream));
 }
@@ -1767,12 +1663,9 @@ int ocn_compute_ri_based_diffusivities(const ocn_grid *grid, const ocn_model_ter
                                        const ocn_bc *top_S, const double *Ri, double *kappa_c, double *kappa_u, void *stream)
 {
     const char *who = "ocn_compute_ri_based_diffusivities";
-    int st = validate_vertical_diffusivity(grid, who);
-    if (st != OCN_SUCCESS) return st;
-    st = validate_buoyancy_terms(terms, who);
-    if (st != OCN_SUCCESS) return st;
-    st = validate_ri_closure(grid, closure, top_T, top_S, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_vertical_diffusivity(grid, who));
+    OCN_TRY(validate_buoyancy_terms(terms, who));
+    OCN_TRY(validate_ri_closure(grid, closure, top_T, top_S, who));
     OCN_REQUIRE(Ri && kappa_c && kappa_u, "%s: null field pointer", who);
     OCN_REQUIRE(kappa_c != kappa_u && Ri != kappa_c && Ri != kappa_u, "%s: Ri, kappa_c and kappa_u must be three different arrays", who);
     return launch_ri_based(1, grid, terms, closure, top_T, top_S, nullptr, nullptr, Ri, nullptr, kappa_c, kappa_u, as_stream(stream));
@@ -1783,12 +1676,9 @@ int ocn_compute_ri_based_diffusivities_fused(const ocn_grid *grid, const ocn_mod
                                              double *kappa_c, double *kappa_u, void *stream)
 {
     const char *who = "ocn_compute_ri_based_diffusivities_fused";
-    int st = validate_vertical_diffusivity(grid, who);
-    if (st != OCN_SUCCESS) return st;
-    st = validate_buoyancy_terms(terms, who);
-    if (st != OCN_SUCCESS) return st;
-    st = validate_ri_closure(grid, closure, top_T, top_S, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_vertical_diffusivity(grid, who));
+    OCN_TRY(validate_buoyancy_terms(terms, who));
+    OCN_TRY(validate_ri_closure(grid, closure, top_T, top_S, who));
     OCN_REQUIRE(closure->horizontal_filter == OCN_RI_FILTER_NONE,
                 "%s: the horizontal filter reads the neighbours' Ri: ocn_compute_ri_number, a halo fill, ocn_compute_ri_based_diffusivities", who);
     OCN_REQUIRE(u && v && Ri && kappa_c && kappa_u, "%s: null field pointer", who);
@@ -1807,18 +1697,15 @@ int ocn_ri_taper_host(int32_t kind, int64_t n, const double *x, double x0, doubl
 int ocn_cache_previous_tendencies(const ocn_grid *grid, int32_t n, double *const *Gm, const double *const *Gn,
                                   const int32_t *locs, void *stream)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     StepTuple t;
-    st = make_step_tuple(n, nullptr, Gn, Gm, locs, false, t);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_step_tuple(n, nullptr, Gn, Gm, locs, false, t));
     return launch_stepper(grid, t, 3, 0.0, 0.0, 0.0, as_stream(stream));
 }
 
 int ocn_pressure_correct_velocities(const ocn_grid *grid, double *u, double *v, double *w, const double *p, double dt, void *stream)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     OCN_REQUIRE(u && v && w && p, "ocn_pressure_correct_velocities: null field pointer");
     OCN_REQUIRE((grid->tx == OCN_FLAT || grid->Hx >= 1) && (grid->ty == OCN_FLAT || grid->Hy >= 1) && (grid->tz == OCN_FLAT || grid->Hz >= 1),
                 "pressure correction needs halo >= 1");
@@ -1827,8 +1714,7 @@ int ocn_pressure_correct_velocities(const ocn_grid *grid, double *u, double *v, 
 
 int ocn_divergence(const ocn_grid *grid, const double *u, const double *v, const double *w, double *div, void *stream)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     OCN_REQUIRE(u && v && w && div, "ocn_divergence: null pointer");
     return launch_source_term(grid, u, v, w, 1.0, SourceOut::Divergence, div, grid->Nx, (long long)grid->Nx * grid->Ny, as_stream(stream));
 }
@@ -1862,23 +1748,20 @@ int ocn_batched_tridiagonal_solve_y(int32_t Nx, int32_t Ny, int32_t Nz, const do
 
 int ocn_halo_pack_x(const ocn_grid *grid, const double *field, int32_t loc, double *send_west, double *send_east, void *stream)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     OCN_REQUIRE(field && send_west && send_east, "ocn_halo_pack_x: null pointer");
     return launch_halo_pack_x(grid, field, loc, send_west, send_east, 0, as_stream(stream));
 }
 int ocn_halo_unpack_x(const ocn_grid *grid, double *field, int32_t loc, const double *recv_west, const double *recv_east, void *stream)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     OCN_REQUIRE(field && recv_west && recv_east, "ocn_halo_unpack_x: null pointer");
     return launch_halo_pack_x(grid, field, loc, const_cast<double *>(recv_west), const_cast<double *>(recv_east), 1, as_stream(stream));
 }
 
 int ocn_halo_plane_x(const ocn_grid *grid, double *field, int32_t loc, int32_t which, double *buffer, int32_t unpack, void *stream)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     OCN_REQUIRE(field && buffer, "ocn_halo_plane_x: null pointer");
     OCN_REQUIRE(which == 0 || which == 1, "ocn_halo_plane_x: which must be 0 (west) or 1 (east)");
     OCN_REQUIRE(grid->Hx >= 1, "ocn_halo_plane_x: needs an x halo");
@@ -1886,8 +1769,7 @@ int ocn_halo_plane_x(const ocn_grid *grid, double *field, int32_t loc, int32_t w
 }
 static int validate_pressure_planes(const ocn_grid *grid, const char *who)
 {
-    int st = validate_grid(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid(grid));
     OCN_REQUIRE(grid->ty == OCN_PERIODIC && grid->tz == OCN_PERIODIC, "%s: y and z must be Periodic", who);
     OCN_REQUIRE(grid->Hx >= 1 && grid->Nx >= grid->Hx + 1, "%s: needs nx >= Hx + 1 (got nx = %d, Hx = %d)", who, grid->Nx, grid->Hx);
     return OCN_SUCCESS;
@@ -1895,39 +1777,33 @@ static int validate_pressure_planes(const ocn_grid *grid, const char *who)
 int ocn_halo_pack_pressure(const ocn_grid *grid, const double *p, const double *u, double dt_correct, double *send_west,
                            double *send_east, void *stream)
 {
-    int st = validate_pressure_planes(grid, "ocn_halo_pack_pressure");
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_pressure_planes(grid, "ocn_halo_pack_pressure"));
     OCN_REQUIRE(p && u && send_west && send_east, "ocn_halo_pack_pressure: null pointer");
     return OCN_LAUNCH(grid, launch_pressure_planes, grid, const_cast<double *>(p), const_cast<double *>(u), dt_correct, send_west, send_east, 0,
                       as_stream(stream));
 }
 int ocn_halo_unpack_pressure(const ocn_grid *grid, double *p, double *u, const double *recv_west, const double *recv_east, void *stream)
 {
-    int st = validate_pressure_planes(grid, "ocn_halo_unpack_pressure");
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_pressure_planes(grid, "ocn_halo_unpack_pressure"));
     OCN_REQUIRE(p && u && recv_west && recv_east, "ocn_halo_unpack_pressure: null pointer");
     return ocn_strict::launch_pressure_planes(grid, p, u, 0.0, const_cast<double *>(recv_west), const_cast<double *>(recv_east), 1, as_stream(stream));
 }
 int ocn_halo_pack_x_fields(const ocn_grid *grid, double *const *fields, const int32_t *locs, int32_t n, double *send_west,
                            double *send_east, void *stream)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     OCN_REQUIRE(send_west && send_east, "ocn_halo_pack_x_fields: null buffer");
     FieldTuple ft;
-    st = make_field_tuple(grid, fields, locs, n, ft);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_field_tuple(grid, fields, locs, n, ft));
     return launch_halo_pack_x_fields(grid, ft, send_west, send_east, 0, as_stream(stream));
 }
 int ocn_halo_unpack_x_fields(const ocn_grid *grid, double *const *fields, const int32_t *locs, int32_t n, const double *recv_west,
                              const double *recv_east, void *stream)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     OCN_REQUIRE(recv_west && recv_east, "ocn_halo_unpack_x_fields: null buffer");
     FieldTuple ft;
-    st = make_field_tuple(grid, fields, locs, n, ft);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_field_tuple(grid, fields, locs, n, ft));
     return launch_halo_pack_x_fields(grid, ft, const_cast<double *>(recv_west), const_cast<double *>(recv_east), 1, as_stream(stream));
 }
 
@@ -1940,26 +1816,22 @@ static int check_transpose(int32_t nx, int32_t Ny, int32_t Nz, int32_t R, const 
 }
 int ocn_transpose_pack_y_to_x(int32_t nx, int32_t Ny, int32_t Nz, int32_t R, const double *yfield, double *send, void *stream)
 {
-    int st = check_transpose(nx, Ny, Nz, R, yfield, send);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(check_transpose(nx, Ny, Nz, R, yfield, send));
     return launch_transpose(0, nx, Ny, Nz, R, yfield, send, as_stream(stream));
 }
 int ocn_transpose_unpack_x_from_y(int32_t nx, int32_t Ny, int32_t Nz, int32_t R, const double *recv, double *xfield, void *stream)
 {
-    int st = check_transpose(nx, Ny, Nz, R, recv, xfield);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(check_transpose(nx, Ny, Nz, R, recv, xfield));
     return launch_transpose(1, nx, Ny, Nz, R, recv, xfield, as_stream(stream));
 }
 int ocn_transpose_pack_x_to_y(int32_t nx, int32_t Ny, int32_t Nz, int32_t R, const double *xfield, double *send, void *stream)
 {
-    int st = check_transpose(nx, Ny, Nz, R, xfield, send);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(check_transpose(nx, Ny, Nz, R, xfield, send));
     return launch_transpose(2, nx, Ny, Nz, R, xfield, send, as_stream(stream));
 }
 int ocn_transpose_unpack_y_from_x(int32_t nx, int32_t Ny, int32_t Nz, int32_t R, const double *recv, double *yfield, void *stream)
 {
-    int st = check_transpose(nx, Ny, Nz, R, recv, yfield);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(check_transpose(nx, Ny, Nz, R, recv, yfield));
     return launch_transpose(3, nx, Ny, Nz, R, recv, yfield, as_stream(stream));
 }
 

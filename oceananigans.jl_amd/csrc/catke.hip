@@ -353,16 +353,13 @@ __global__ __launch_bounds__(256) void top_tke_flux(GridDev g, SurfaceBuoyancy b
 // ---- argument checks: nothing here touches a device -----------------------------------------------------------------------------------
 static int validate_grid_and_closure(const ocn_grid *grid, const ocn_model_terms *terms, const ocn_catke *c, const char *who)
 {
-    int st = tke::validate_tke_grid(grid, who);
-    if (st != OCN_SUCCESS) return st;
-    st = validate_buoyancy_terms(terms, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(tke::validate_tke_grid(grid, who));
+    OCN_TRY(validate_buoyancy_terms(terms, who));
     OCN_REQUIRE(c, "%s: null closure", who);
     // every member in front of the three maxima is a coefficient (the struct holds doubles only)
     constexpr size_t n_coefficients = offsetof(ocn_catke, maximum_tracer_diffusivity) / sizeof(double);
     static_assert(offsetof(ocn_catke, C_s) == 0 && sizeof(ocn_catke) % sizeof(double) == 0, "ocn_catke: doubles only, coefficients first");
-    st = tke::validate_finite_coefficients(reinterpret_cast<const double *>(c), n_coefficients, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(tke::validate_finite_coefficients(reinterpret_cast<const double *>(c), n_coefficients, who));
     OCN_REQUIRE(!std::isnan(c->maximum_tracer_diffusivity) && !std::isnan(c->maximum_tke_diffusivity) && !std::isnan(c->maximum_viscosity),
                 "%s: a maximum is a NaN", who);
     OCN_REQUIRE(std::isfinite(c->minimum_tke) && std::isfinite(c->minimum_convective_buoyancy_flux) &&
@@ -391,12 +388,10 @@ int ocn_compute_catke_surface_buoyancy_flux(const ocn_grid *grid, const ocn_mode
                                             const double *v, const double *e, double *Jb, double dt, void *stream)
 {
     const char *who = "ocn_compute_catke_surface_buoyancy_flux";
-    int st = catke::validate_grid_and_closure(grid, terms, closure, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(catke::validate_grid_and_closure(grid, terms, closure, who));
     const ocn_bc *tops[2] = {top_T, top_S};
     const char *names[2] = {"the T (or b) tracer", "the S tracer"};
-    st = tke::validate_top_fluxes(tops, names, 2, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(tke::validate_top_fluxes(tops, names, 2, who));
     OCN_REQUIRE(znodes_f && znodes_c && u && v && e && Jb, "%s: null pointer", who);
     OCN_REQUIRE(std::isfinite(dt) && dt >= 0, "%s: dt = %g must be finite and >= 0", who, dt);
     catke::PlaneArgs a{};
@@ -412,12 +407,10 @@ int ocn_compute_catke_top_tke_flux(const ocn_grid *grid, const ocn_model_terms *
                                    void *stream)
 {
     const char *who = "ocn_compute_catke_top_tke_flux";
-    int st = catke::validate_grid_and_closure(grid, terms, closure, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(catke::validate_grid_and_closure(grid, terms, closure, who));
     const ocn_bc *tops[4] = {top_u, top_v, top_T, top_S};
     const char *names[4] = {"u", "v", "the T (or b) tracer", "the S tracer"};
-    st = tke::validate_top_fluxes(tops, names, 4, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(tke::validate_top_fluxes(tops, names, 4, who));
     OCN_REQUIRE(u && v && Qe, "%s: null pointer", who);
     catke::PlaneArgs a{};
     a.u = u; a.v = v; a.Qe = Qe; a.Lz = grid->Lz;
@@ -434,8 +427,7 @@ int ocn_compute_catke_diffusivities(const ocn_grid *grid, const ocn_model_terms 
                                     double *kappa_u, double *kappa_c, double *kappa_e, void *stream)
 {
     const char *who = "ocn_compute_catke_diffusivities";
-    int st = catke::validate_grid_and_closure(grid, terms, closure, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(catke::validate_grid_and_closure(grid, terms, closure, who));
     OCN_REQUIRE(znodes_f && znodes_c && u && v && e && Jb && kappa_u && kappa_c && kappa_e, "%s: null pointer", who);
     OCN_REQUIRE(kappa_u != kappa_c && kappa_u != kappa_e && kappa_c != kappa_e, "%s: kappa_u, kappa_c and kappa_e must be three different arrays",
                 who);
@@ -454,8 +446,7 @@ int ocn_catke_substep_tke(const ocn_grid *grid, const ocn_model_terms *terms, co
                           const double *Gn_e, double *Gm_e, double *scratch, double dtau, double chi, int32_t solve, void *stream)
 {
     const char *who = "ocn_catke_substep_tke";
-    int st = catke::validate_grid_and_closure(grid, terms, closure, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(catke::validate_grid_and_closure(grid, terms, closure, who));
     OCN_REQUIRE(znodes_f && znodes_c && u_next && v_next && u_prev && v_prev && e && Jb && kappa_u && kappa_c && kappa_e && Le && Gn_e && Gm_e,
                 "%s: null pointer", who);
     OCN_REQUIRE(!solve || scratch, "%s: the solve needs a scratch array of Nx Ny Nz doubles", who);

@@ -196,13 +196,11 @@ int local_run_ops(Comm *c, const ocn_comm_op *ops, int n, const double *const *s
 {
     for (int q = 0; q < n; ++q)
         if (!ops[q].is_recv) {
-            int st = local_send(c, send[ops[q].slot], count, ops[q].peer, stream);
-            if (st != OCN_SUCCESS) return st;
+            OCN_TRY(local_send(c, send[ops[q].slot], count, ops[q].peer, stream));
         }
     for (int q = 0; q < n; ++q)
         if (ops[q].is_recv) {
-            int st = local_recv(c, recv[ops[q].slot], count, ops[q].peer, stream);
-            if (st != OCN_SUCCESS) return st;
+            OCN_TRY(local_recv(c, recv[ops[q].slot], count, ops[q].peer, stream));
         }
     return OCN_SUCCESS;
 }
@@ -232,8 +230,7 @@ int local_allreduce(Comm *c, double *buf, size_t count, int op, hipStream_t stre
     std::vector<double> mine(count);
     OCN_CHECK_HIP(hipMemcpyAsync(mine.data(), buf, count * sizeof(double), hipMemcpyDeviceToHost, stream));
     OCN_CHECK_HIP(hipStreamSynchronize(stream));
-    int st = local_barrier(c);  // the previous reduction's result has been read by everybody
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(local_barrier(c));  // the previous reduction's result has been read by everybody
     {
         std::lock_guard<std::mutex> lk(G->m);
         if (G->red_count == 0) G->red = mine;
@@ -242,15 +239,13 @@ int local_allreduce(Comm *c, double *buf, size_t count, int op, hipStream_t stre
                 G->red[q] = op == 0 ? G->red[q] + mine[q] : op == 1 ? (mine[q] > G->red[q] ? mine[q] : G->red[q]) : (mine[q] < G->red[q] ? mine[q] : G->red[q]);
         ++G->red_count;
     }
-    st = local_barrier(c);  // everybody has contributed
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(local_barrier(c));  // everybody has contributed
     std::vector<double> res;
     {
         std::lock_guard<std::mutex> lk(G->m);
         res = G->red;
     }
-    st = local_barrier(c);  // everybody has read
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(local_barrier(c));  // everybody has read
     {
         std::lock_guard<std::mutex> lk(G->m);
         G->red_count = 0;
@@ -381,8 +376,7 @@ int run_schedule(Comm *c, int kind, const double *const *send, double *const *re
 {
     ocn_comm_op ops[2 * OCN_COMM_MAX_RANKS];
     int n = 0;
-    int st = build_schedule(kind, c->rank, c->nranks, c->self_via_rccl, ops, 2 * OCN_COMM_MAX_RANKS, &n);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(build_schedule(kind, c->rank, c->nranks, c->self_via_rccl, ops, 2 * OCN_COMM_MAX_RANKS, &n));
     if (n == 0) return OCN_SUCCESS;
     if (c->replica) {
         // the k-th receive from peer s pairs with s's k-th send to me (RCCL's rule) = my k-th send to the mirror peer (R - s) mod R
@@ -612,19 +606,16 @@ int ocn_halo_exchange_begin(ocn_comm_t comm, const ocn_grid *grid, double *const
     Comm *c = static_cast<Comm *>(comm);
     OCN_REQUIRE(c, "ocn_halo_exchange_begin: null communicator");
     OCN_REQUIRE(!c->pending, "ocn_halo_exchange_begin: an exchange is already in flight (call ocn_halo_exchange_end first)");
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     FieldTuple ft;
-    st = make_tuple(grid, fields, locs, n, ft);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_tuple(grid, fields, locs, n, ft));
     const size_t count = strip_doubles(grid, locs, n);
-    st = ensure(c, count);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(ensure(c, count));
     hipStream_t s = as_stream(stream);
-    st = launch_halo_pack_x_fields(grid, ft, c->buf[0], c->buf[1], 0, s);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(launch_halo_pack_x_fields(grid, ft, c->buf[0], c->buf[1], 0, s));
     OCN_CHECK_HIP(hipEventRecord(c->ready, s));
     OCN_CHECK_HIP(hipStreamWaitEvent(c->stream, c->ready, 0));
+    int st;
     {
         StatScope sc(c, 0, c->stream);
         st = post_exchange(c, c->buf[0], c->buf[1], c->buf[2], c->buf[3], count);
@@ -645,8 +636,7 @@ int ocn_halo_exchange_buffers(ocn_comm_t comm, const ocn_grid *grid, const int32
     Comm *c = static_cast<Comm *>(comm);
     OCN_REQUIRE(c && locs && send_west && send_east && field_doubles, "ocn_halo_exchange_buffers: null pointer");
     OCN_REQUIRE(!c->pending, "ocn_halo_exchange_buffers: an exchange is in flight");
-    int st = validate_grid(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid(grid));
     OCN_REQUIRE(grid->ty == OCN_PERIODIC && grid->tz == OCN_PERIODIC, "ocn_halo_exchange_buffers: Periodic y and z (the receiver wraps the halo rows)");
     for (int q = 1; q < n; ++q) {
         GridDev g = to_dev(*grid);
@@ -654,8 +644,7 @@ int ocn_halo_exchange_buffers(ocn_comm_t comm, const ocn_grid *grid, const int32
         OCN_REQUIRE(L.sy == L0.sy && L.sz == L0.sz, "ocn_halo_exchange_buffers: fields of one cross-section");
     }
     const size_t count = strip_doubles(grid, locs, n);
-    st = ensure(c, count);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(ensure(c, count));
     *send_west = c->buf[0];
     *send_east = c->buf[1];
     *field_doubles = (int64_t)(count / (size_t)n);
@@ -669,17 +658,16 @@ int ocn_halo_exchange_begin_packed(ocn_comm_t comm, const ocn_grid *grid, double
     Comm *c = static_cast<Comm *>(comm);
     OCN_REQUIRE(c, "ocn_halo_exchange_begin_packed: null communicator");
     OCN_REQUIRE(!c->pending, "ocn_halo_exchange_begin_packed: an exchange is already in flight (call ocn_halo_exchange_end first)");
-    int st = validate_grid(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid(grid));
     OCN_REQUIRE(grid->ty == OCN_PERIODIC && grid->tz == OCN_PERIODIC, "ocn_halo_exchange_begin_packed: Periodic y and z");
     FieldTuple ft;
-    st = make_tuple(grid, fields, locs, n, ft);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_tuple(grid, fields, locs, n, ft));
     const size_t count = strip_doubles(grid, locs, n);
     OCN_REQUIRE(count <= c->cap && c->buf[0], "ocn_halo_exchange_begin_packed: call ocn_halo_exchange_buffers first");
     hipStream_t s = as_stream(stream);
     OCN_CHECK_HIP(hipEventRecord(c->ready, s));
     OCN_CHECK_HIP(hipStreamWaitEvent(c->stream, c->ready, 0));
+    int st;
     {
         StatScope sc(c, 0, c->stream);
         st = post_exchange(c, c->buf[0], c->buf[1], c->buf[2], c->buf[3], count);
@@ -700,15 +688,14 @@ int ocn_halo_exchange_end(ocn_comm_t comm, const ocn_grid *grid, double *const *
     OCN_REQUIRE(c, "ocn_halo_exchange_end: null communicator");
     OCN_REQUIRE(c->pending, "ocn_halo_exchange_end: no exchange in flight");
     FieldTuple ft;
-    int st = make_tuple(grid, fields, locs, n, ft);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_tuple(grid, fields, locs, n, ft));
     OCN_REQUIRE(strip_doubles(grid, locs, n) == c->pending_count, "ocn_halo_exchange_end: not the tuple the exchange was started with");
     hipStream_t s = as_stream(stream);
     {
         StatScope sc(c, 1, s);  // what the caller's stream waits for the exchange
         OCN_CHECK_HIP(hipStreamWaitEvent(s, c->done, 0));
     }
-    st = launch_halo_pack_x_fields(grid, ft, c->buf[2], c->buf[3], c->pending_wrap ? 2 : 1, s);
+    const int st = launch_halo_pack_x_fields(grid, ft, c->buf[2], c->buf[3], c->pending_wrap ? 2 : 1, s);
     if (st == OCN_SUCCESS) c->pending = c->pending_wrap = false;  // a failed unpack leaves the exchange pending: the caller may call _end again
     return st;
 }
@@ -721,8 +708,7 @@ int ocn_halo_exchange_plane(ocn_comm_t comm, const ocn_grid *grid, double *field
     Comm *c = static_cast<Comm *>(comm);
     OCN_REQUIRE(c && field, "ocn_halo_exchange_plane: null pointer");
     OCN_REQUIRE(!c->pending, "ocn_halo_exchange_plane: a strip exchange is in flight");
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     GridDev g = to_dev(*grid);
     Lay L = make_lay(g, loc);
     const size_t count = (size_t)L.sy * L.sz;
@@ -737,16 +723,14 @@ int ocn_halo_exchange_plane(ocn_comm_t comm, const ocn_grid *grid, double *field
     hipStream_t s = as_stream(stream);
     const bool east = side == 0;
     // the plane I need from the east is my east neighbour's WEST interior plane, and vice versa
-    st = launch_halo_plane_x(grid, field, loc, east ? 0 : 1, c->plane[0], 0, s);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(launch_halo_plane_x(grid, field, loc, east ? 0 : 1, c->plane[0], 0, s));
     if (c->nranks == 1 && !c->self_via_rccl)
         return launch_halo_plane_x(grid, field, loc, east ? 1 : 0, c->plane[0], 1, s);  // my own plane is the neighbour's
     {
         const double *snd[2] = {c->plane[0], nullptr};
         double *rcv[2] = {nullptr, c->plane[1]};
         StatScope sc(c, 4, s);
-        st = run_schedule(c, east ? OCN_SCHED_PLANE_EAST : OCN_SCHED_PLANE_WEST, snd, rcv, count, s);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(run_schedule(c, east ? OCN_SCHED_PLANE_EAST : OCN_SCHED_PLANE_WEST, snd, rcv, count, s));
     }
     return launch_halo_plane_x(grid, field, loc, east ? 1 : 0, c->plane[1], 1, s);
 }
@@ -770,8 +754,8 @@ int ocn_halo_exchange_pressure(ocn_comm_t comm, const ocn_grid *grid, double *p,
         }
         c->pcap = count;
     }
-    int st = ocn_halo_pack_pressure(grid, p, u, dt_correct, c->pbuf[0], c->pbuf[1], stream);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(ocn_halo_pack_pressure(grid, p, u, dt_correct, c->pbuf[0], c->pbuf[1], stream));
+    int st;
     {
         StatScope sc(c, 3, as_stream(stream));
         st = ocn_comm_exchange_strips(comm, c->pbuf[0], c->pbuf[1], c->pbuf[2], c->pbuf[3], count, stream);
@@ -856,20 +840,16 @@ int ocn_comm_all_gather(ocn_comm_t comm, const double *send, double *recv, size_
 int ocn_dist_poisson_exchange(ocn_dist_poisson_t handle, ocn_comm_t comm, int32_t direction, void *stream)
 {
     double *yf, *xf, *snd, *rcv;
-    int st = ocn_dist_poisson_buffers(handle, &yf, &xf, &snd, &rcv);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(ocn_dist_poisson_buffers(handle, &yf, &xf, &snd, &rcv));
     int32_t nyt, r2c, fast;
     int64_t nel;
-    st = ocn_dist_poisson_layout(handle, &nyt, &nel, &r2c);
-    if (st != OCN_SUCCESS) return st;
-    st = ocn_dist_poisson_pipeline(handle, &fast);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(ocn_dist_poisson_layout(handle, &nyt, &nel, &r2c));
+    OCN_TRY(ocn_dist_poisson_pipeline(handle, &fast));
     if (fast == 3) {
         if (direction != 0) return OCN_SUCCESS;
         double *gs, *gr;
         int64_t per_rank;
-        st = ocn_dist_poisson_gather_buffers(handle, &gs, &gr, &per_rank);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(ocn_dist_poisson_gather_buffers(handle, &gs, &gr, &per_rank));
         return ocn_comm_all_gather(comm, gs, gr, (size_t)per_rank, stream);
     }
     Comm *c = static_cast<Comm *>(comm);

@@ -297,8 +297,7 @@ struct OpSpace {
 };
 static int op_space(const ocn_grid *grid, int loc, const char *who, OpSpace &S)
 {
-    int st = validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(validate_grid_any(grid));
     OCN_REQUIRE(grid->tx <= OCN_FLAT, "%s: a slab of a partitioned grid (diagnostics on a Distributed architecture are not implemented)", who);
     OCN_REQUIRE(loc >= 0 && loc <= 7, "%s: location mask %d outside 0..7", who, loc);
     const int N[3] = {grid->Nx, grid->Ny, grid->Nz}, H[3] = {grid->Hx, grid->Hy, grid->Hz}, T[3] = {grid->tx, grid->ty, grid->tz};
@@ -349,11 +348,9 @@ static int op_validate(const ocn_grid *grid, const ocn_op_program *p, const char
                        bool tendency_cells = false)
 {
     OCN_REQUIRE(grid && p, "%s: null grid or program", who);
-    int st = op_space(grid, p->loc, who, S);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(op_space(grid, p->loc, who, S));
     if (side) {
-        st = op_plane(S, *side, who);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(op_plane(S, *side, who));
     }
     if (tendency_cells) op_tendency_cells(S, p->loc);
     OCN_REQUIRE(p->n_instructions >= 1 && p->n_instructions <= OCN_OP_MAX_INSTRUCTIONS, "%s: %d instructions outside 1..%d", who,
@@ -469,8 +466,7 @@ int op_compute(const ocn_grid *grid, const ocn_op_program *p, double *out, hipSt
 {
     OpSpace S;
     OpProgramDev D;
-    int st = op_validate(grid, p, "ocn_op_compute", S, D);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(op_validate(grid, p, "ocn_op_compute", S, D));
     OCN_REQUIRE(out, "ocn_op_compute: null output pointer");
     const OpOut O = op_out(S, p->loc, 0);
     const dim3 block(64, 4, 1), nb((S.n[0] + 63) / 64, (S.n[1] + 7) / 8, S.n[2]);
@@ -484,8 +480,7 @@ int op_accumulate(const ocn_grid *grid, const ocn_op_program *p, double *G, hipS
 {
     OpSpace S;
     OpProgramDev D;
-    int st = op_validate(grid, p, "ocn_op_accumulate", S, D, nullptr, true);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(op_validate(grid, p, "ocn_op_accumulate", S, D, nullptr, true));
     OCN_REQUIRE(G, "ocn_op_accumulate: null tendency pointer");
     for (int f = 0; f < p->n_fields; ++f)
         OCN_REQUIRE(G != p->fields[f], "ocn_op_accumulate: the tendency array is field %d of the program (cells would read what others write)", f);
@@ -501,8 +496,7 @@ int op_compute_boundary(const ocn_grid *grid, const ocn_op_program *p, int side,
 {
     OpSpace S;
     OpProgramDev D;
-    int st = op_validate(grid, p, "ocn_op_compute_boundary", S, D, &side);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(op_validate(grid, p, "ocn_op_compute_boundary", S, D, &side));
     OCN_REQUIRE(values, "ocn_op_compute_boundary: null values pointer");
     OpPlane B;
     B.axis = side >> 1;
@@ -521,8 +515,7 @@ int op_reduce_workspace(const ocn_grid *grid, int loc, int dims, long long *n_do
     OCN_REQUIRE(grid && n_doubles, "ocn_op_reduce_workspace: null pointer");
     OCN_REQUIRE(dims >= 1 && dims <= 7, "ocn_op_reduce_workspace: dims mask %d outside 1..7", dims);
     OpSpace S;
-    int st = op_space(grid, loc, "ocn_op_reduce_workspace", S);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(op_space(grid, loc, "ocn_op_reduce_workspace", S));
     long long P;
     const OpReduceGeom G = op_reduce_geometry(S, dims, P);
     *n_doubles = P * G.E;
@@ -534,8 +527,7 @@ int op_reduce(const ocn_grid *grid, const ocn_op_program *p, int dims, double di
 {
     OpSpace S;
     OpProgramDev D;
-    int st = op_validate(grid, p, "ocn_op_reduce", S, D);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(op_validate(grid, p, "ocn_op_reduce", S, D));
     OCN_REQUIRE(dims >= 1 && dims <= 7, "ocn_op_reduce: dims mask %d outside 1..7", dims);
     OCN_REQUIRE(workspace && out, "ocn_op_reduce: null workspace or output pointer");
     OCN_REQUIRE(divisor == divisor && divisor != 0.0, "ocn_op_reduce: divisor %g", divisor);

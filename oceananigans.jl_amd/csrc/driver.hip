@@ -12,22 +12,13 @@
 // bit-identical (tests/test_gpu_model.py::test_c_driver_equals_host_orchestration).
 #include <cstring>
 
-#include "ocn_internal.h"
+#include "ocn_driver_core.h"
 
-using ocn::GridDev;
-using ocn::Lay;
-
-struct ocn_rk3_driver {
+// the two sets of u, v, w and their tendencies, and the handles of the projection (a slab-x rank, ocn_rk3_driver_create_distributed:
+// RCCL communicator + distributed Poisson handle, both borrowed): ocn_driver_core.h
+struct ocn_rk3_driver : ocn::FieldSets<3>, ocn::Projection {
     ocn_grid grid{};
-    ocn_poisson_t solver = nullptr;
-    bool owns_solver = true;
-    double *user[3] = {nullptr, nullptr, nullptr};  // the caller's u, v, w parents
-    double *own[3] = {nullptr, nullptr, nullptr};   // second set
-    double *U[3] = {nullptr, nullptr, nullptr};     // where the velocities are now
-    double *A[3] = {nullptr, nullptr, nullptr};     // where the next fused launch writes
-    double *p = nullptr;                            // the caller's pressure parent
-    double *Gn[3] = {nullptr, nullptr, nullptr}, *Gm[3] = {nullptr, nullptr, nullptr};
-    size_t bytes[3] = {0, 0, 0};
+    double *p = nullptr;          // the caller's pressure parent
     bool pending = false;         // the last compute_tendencies! of the previous step is still due
     bool started = false;         // iteration 0 done
     bool correct_on_load = false;
@@ -37,9 +28,6 @@ struct ocn_rk3_driver {
     bool defer_correction = false;
     bool correction_pending = false;
     double correction_dt = 0.0;
-    // slab-x rank (ocn_rk3_driver_create_distributed): RCCL communicator + distributed Poisson handle, both borrowed
-    ocn_comm_t comm = nullptr;
-    ocn_dist_poisson_t dsolver = nullptr;
     // the last fused launch also wrote the x strips of its stepped velocities into the communicator's send buffers
     // (ocn_compute_momentum_tendencies_rk3_strips): the next exchange of U is posted without a pack launch
     bool use_strips = false, strips_ready = false;
@@ -55,46 +43,18 @@ struct ocn_rk3_driver {
 };
 
 namespace {
-const int32_t LOCS[3] = {OCN_LOC_FCC, OCN_LOC_CFC, OCN_LOC_CCF};
-
 // fill_halo_regions!(velocities): local periodic / wall fills, then -- on a slab -- the x exchange with the neighbours (synchronous)
 int fill_velocities(ocn_rk3_driver *d, int fbnv, void *stream)
 {
     d->strips_ready = false;  // (this exchange packs into the same send buffers)
-    int st = ocn_fill_halo_regions(&d->grid, d->U, LOCS, 3, fbnv, stream);
-    if (st != OCN_SUCCESS || !d->comm) return st;
-    st = ocn_halo_exchange_begin(d->comm, &d->grid, d->U, LOCS, 3, stream);
-    if (st != OCN_SUCCESS) return st;
-    return ocn_halo_exchange_end(d->comm, &d->grid, d->U, LOCS, 3, stream);
+    return ocn::fill_and_exchange(&d->grid, d->comm, d->U, d->locs, nullptr, 3, fbnv, stream);
 }
 
 int fill_pressure(ocn_rk3_driver *d, void *stream)
 {
     const int32_t ploc = OCN_LOC_CCC;
     double *pf[1] = {d->p};
-    int st = ocn_fill_halo_regions(&d->grid, pf, &ploc, 1, 1, stream);
-    if (st != OCN_SUCCESS || !d->comm) return st;
-    st = ocn_halo_exchange_begin(d->comm, &d->grid, pf, &ploc, 1, stream);
-    if (st != OCN_SUCCESS) return st;
-    return ocn_halo_exchange_end(d->comm, &d->grid, pf, &ploc, 1, stream);
-}
-
-// solve_for_pressure!(pNHS, solver, Δt, U) (solve_for_pressure.jl:78-82) on one GPU or on a slab (the slab pipelines of the handle:
-// distributed_fft_based_poisson_solver.jl:141-178 without pack / unpack passes)
-int solve(ocn_rk3_driver *d, double stage_dt, void *stream)
-{
-    if (!d->dsolver) return ocn_solve_for_pressure(d->solver, d->p, d->U[0], d->U[1], d->U[2], stage_dt, stream);
-    int st = ocn_dist_poisson_source_term(d->dsolver, d->U[0], d->U[1], d->U[2], stage_dt, stream);
-    if (st != OCN_SUCCESS) return st;
-    st = ocn_dist_poisson_forward_yz(d->dsolver, stream);
-    if (st != OCN_SUCCESS) return st;
-    st = ocn_dist_poisson_exchange(d->dsolver, d->comm, 0, stream);
-    if (st != OCN_SUCCESS) return st;
-    st = ocn_dist_poisson_solve_x(d->dsolver, stream);
-    if (st != OCN_SUCCESS) return st;
-    st = ocn_dist_poisson_exchange(d->dsolver, d->comm, 1, stream);
-    if (st != OCN_SUCCESS) return st;
-    return ocn_dist_poisson_backward_yz(d->dsolver, d->p, stream);
+    return ocn::fill_and_exchange(&d->grid, d->comm, pf, &ploc, nullptr, 1, 1, stream);
 }
 
 // update_state! + the next rk3_substep! in one launch, then the two velocity sets trade places
@@ -106,8 +66,7 @@ int fused_launch(ocn_rk3_driver *d, double dt, double gamma, double zeta, int ha
     if (d->use_strips && p_correct) {
         double *sw = nullptr, *se = nullptr;
         int64_t per_field = 0;
-        st = ocn_halo_exchange_buffers(d->comm, &d->grid, LOCS, 3, &sw, &se, &per_field);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(ocn_halo_exchange_buffers(d->comm, &d->grid, d->locs, 3, &sw, &se, &per_field));
         st = ocn_compute_momentum_tendencies_rk3_strips(&d->grid, d->U[0], d->U[1], d->U[2], d->Gn[0], d->Gn[1], d->Gn[2], d->Gm[0], d->Gm[1],
                                                         d->Gm[2], d->A[0], d->A[1], d->A[2], dt, gamma, zeta, has_zeta, p_correct, dt_correct,
                                                         sw, se, per_field, stream);
@@ -122,14 +81,9 @@ int fused_launch(ocn_rk3_driver *d, double dt, double gamma, double zeta, int ha
                                                  nullptr, stream);
     }
     if (st != OCN_SUCCESS) return st;
-    for (int f = 0; f < 3; ++f) std::swap(d->U[f], d->A[f]);
+    d->swap_sets();
     d->pending = false;
     return OCN_SUCCESS;
-}
-
-void swap_tendencies(ocn_rk3_driver *d)  // cache_previous_tendencies! (store_tendencies.jl:12-22) as a role swap
-{
-    for (int f = 0; f < 3; ++f) std::swap(d->Gn[f], d->Gm[f]);
 }
 
 // The projection of a stage up to (not including) the correction, for a launch that corrects on load: halos of the uncorrected
@@ -138,24 +92,19 @@ void swap_tendencies(ocn_rk3_driver *d)  // cache_previous_tendencies! (store_te
 // wrapped_loads: no fill at all -- the halos of U stay stale until the next fill_velocities (flush), and nothing reads them before.
 int project_for_load(ocn_rk3_driver *d, double stage_dt, void *stream)
 {
-    int st = d->wrapped_loads ? OCN_SUCCESS : ocn_fill_halo_regions(&d->grid, d->U, LOCS, 3, 1, stream);
-    if (st != OCN_SUCCESS) return st;
+    if (!d->wrapped_loads) OCN_TRY(ocn_fill_halo_regions(&d->grid, d->U, d->locs, 3, 1, stream));
     if (d->comm) {
-        st = ocn_halo_exchange_plane(d->comm, &d->grid, d->U[0], OCN_LOC_FCC, 0, stream);  // u[nx+1] <- east neighbour's u[1]
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(ocn_halo_exchange_plane(d->comm, &d->grid, d->U[0], OCN_LOC_FCC, 0, stream));  // u[nx+1] <- east neighbour's u[1]
         // the strips of u*, v*, w*: already in the send buffers when the last fused launch wrote them (no pack launch), packed here otherwise
-        st = d->strips_ready ? ocn_halo_exchange_begin_packed(d->comm, &d->grid, d->U, LOCS, 3, stream)
-                             : ocn_halo_exchange_begin(d->comm, &d->grid, d->U, LOCS, 3, stream);
+        const int st = d->strips_ready ? ocn_halo_exchange_begin_packed(d->comm, &d->grid, d->U, d->locs, 3, stream)
+                                   : ocn_halo_exchange_begin(d->comm, &d->grid, d->U, d->locs, 3, stream);
         d->strips_ready = false;
         if (st != OCN_SUCCESS) return st;
     }
-    st = solve(d, stage_dt, stream);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(d->solve(d->p, d->U, stage_dt, stream));
     if (d->comm) {
-        st = ocn_halo_exchange_end(d->comm, &d->grid, d->U, LOCS, 3, stream);
-        if (st != OCN_SUCCESS) return st;
-        st = ocn_halo_exchange_pressure(d->comm, &d->grid, d->p, d->U[0], stage_dt, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(ocn_halo_exchange_end(d->comm, &d->grid, d->U, d->locs, 3, stream));
+        OCN_TRY(ocn_halo_exchange_pressure(d->comm, &d->grid, d->p, d->U[0], stage_dt, stream));
     }
     return OCN_SUCCESS;
 }
@@ -163,17 +112,12 @@ int project_for_load(ocn_rk3_driver *d, double stage_dt, void *stream)
 // calculate_pressure_correction! + pressure_correct_velocities! + the halo fill of update_state! (pressure_correction.jl:8-50)
 int project_and_correct(ocn_rk3_driver *d, double stage_dt, bool solve_too, void *stream)
 {
-    int st;
     if (solve_too) {
-        st = fill_velocities(d, 1, stream);
-        if (st != OCN_SUCCESS) return st;
-        st = solve(d, stage_dt, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(fill_velocities(d, 1, stream));
+        OCN_TRY(d->solve(d->p, d->U, stage_dt, stream));
     }
-    st = fill_pressure(d, stream);
-    if (st != OCN_SUCCESS) return st;
-    st = ocn_pressure_correct_velocities(&d->grid, d->U[0], d->U[1], d->U[2], d->p, stage_dt, stream);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(fill_pressure(d, stream));
+    OCN_TRY(ocn_pressure_correct_velocities(&d->grid, d->U[0], d->U[1], d->U[2], d->p, stage_dt, stream));
     return fill_velocities(d, 0, stream);
 }
 
@@ -181,17 +125,14 @@ int project_and_correct(ocn_rk3_driver *d, double stage_dt, bool solve_too, void
 // tendencies pending, so its G^n is dead (skip_g_store).
 int project_and_advance(ocn_rk3_driver *d, double dt, double stage_dt, double gamma_next, double zeta_next, bool last_of_step, void *stream)
 {
-    int st;
     if (d->correct_on_load) {
-        st = project_for_load(d, stage_dt, stream);
-        if (st != OCN_SUCCESS) return st;
-        swap_tendencies(d);
+        OCN_TRY(project_for_load(d, stage_dt, stream));
+        d->swap_tendencies();
         const int32_t flags = (d->wrapped_loads ? OCN_RK3_WRAPPED_LOADS : 0) | (last_of_step && d->skip_g_store ? OCN_RK3_SKIP_G_STORE : 0);
         return fused_launch(d, dt, gamma_next, zeta_next, 1, d->p, stage_dt, flags, stream);
     }
-    st = project_and_correct(d, stage_dt, true, stream);
-    if (st != OCN_SUCCESS) return st;
-    swap_tendencies(d);
+    OCN_TRY(project_and_correct(d, stage_dt, true, stream));
+    d->swap_tendencies();
     return fused_launch(d, dt, gamma_next, zeta_next, 1, nullptr, 0.0, 0, stream);
 }
 }  // namespace
@@ -199,12 +140,8 @@ int project_and_advance(ocn_rk3_driver *d, double dt, double stage_dt, double ga
 extern "C" int ocn_rk3_driver_destroy(ocn_rk3_driver_t d)
 {
     if (!d) return OCN_SUCCESS;
-    if (d->solver && d->owns_solver) ocn_poisson_destroy(d->solver);
-    for (int f = 0; f < 3; ++f) {
-        if (d->own[f]) (void)hipFree(d->own[f]);
-        if (d->Gn[f]) (void)hipFree(d->Gn[f]);
-        if (d->Gm[f]) (void)hipFree(d->Gm[f]);
-    }
+    d->release_solver();
+    d->release();
     delete d;
     return OCN_SUCCESS;
 }
@@ -215,14 +152,12 @@ static int driver_create(ocn_rk3_driver_t *out, const ocn_grid *grid, double *u,
     OCN_REQUIRE(out && grid && u && v && w && p, "ocn_rk3_driver_create: null argument");
     // one GPU: any topology the per-call entry points take -- on grids with walls / Flat directions in x, y the fused launch runs the tiled
     // epilogue on the interior box and the finishing kernel on the wall frames (general.hip), without the correction on load
-    int st = comm ? ocn::validate_grid(grid) : ocn::validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(comm ? ocn::validate_grid(grid) : ocn::validate_grid_any(grid));
     if (comm) {
         OCN_REQUIRE(grid->tx == OCN_FULLY_CONNECTED && grid->ty == OCN_PERIODIC && grid->tz == OCN_PERIODIC && dsolver,
                     "ocn_rk3_driver_create_distributed: a (FullyConnected, Periodic, Periodic) local grid and its distributed Poisson handle");
         int32_t fast = 0;
-        st = ocn_dist_poisson_pipeline(dsolver, &fast);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(ocn_dist_poisson_pipeline(dsolver, &fast));
         if (fast != 1 && fast != 3) {
             ocn::set_error("ocn_rk3_driver_create_distributed: the Poisson handle runs the transposing path (sizes outside the slab "
                            "pipelines): drive it through the per-call entry points");
@@ -231,40 +166,17 @@ static int driver_create(ocn_rk3_driver_t *out, const ocn_grid *grid, double *u,
         OCN_REQUIRE(grid->Nx >= 16 && grid->Nx >= grid->Hx + 1 && grid->Ny >= 8 && grid->Nz >= 4,
                     "ocn_rk3_driver_create_distributed: the local slab must be at least 16 x 8 x 4");
     } else {
-        OCN_REQUIRE(grid->tx == OCN_PERIODIC || grid->tx == OCN_BOUNDED || grid->tx == OCN_FLAT,
-                    "ocn_rk3_driver_create: a partitioned x (topology %d) needs ocn_rk3_driver_create_distributed", grid->tx);
+        OCN_TRY(ocn::require_unpartitioned_x(grid, "ocn_rk3_driver"));
     }
     ocn_rk3_driver *d = new ocn_rk3_driver();
     d->grid = *grid;
-    d->comm = comm;
-    d->dsolver = dsolver;
     d->user[0] = u; d->user[1] = v; d->user[2] = w;
     d->p = p;
-    GridDev g = ocn::to_dev(*grid);
-    for (int f = 0; f < 3; ++f) {
-        const Lay L = ocn::make_lay(g, LOCS[f]);
-        d->bytes[f] = (size_t)L.sx * L.sy * L.sz * sizeof(double);
-        for (double **buf : {&d->own[f], &d->Gn[f], &d->Gm[f]}) {
-            if (hipMalloc((void **)buf, d->bytes[f]) != hipSuccess || hipMemset(*buf, 0, d->bytes[f]) != hipSuccess) {
-                ocn::set_error("ocn_rk3_driver_create: device allocation of %zu bytes failed", d->bytes[f]);
-                ocn_rk3_driver_destroy(d);
-                return OCN_ERR_ALLOC;
-            }
-        }
-        d->U[f] = d->user[f];
-        d->A[f] = d->own[f];
-    }
-    if (comm) {
-        d->owns_solver = false;
-    } else if (solver) {  // the caller's pressure solver for this grid (borrowed)
-        d->solver = solver;
-        d->owns_solver = false;
-    } else {
-        st = ocn_poisson_create(&d->solver, grid);
-        if (st != OCN_SUCCESS) {
-            ocn_rk3_driver_destroy(d);
-            return st;
-        }
+    int st = d->allocate(*grid, "ocn_rk3_driver_create");
+    if (st == OCN_SUCCESS) st = d->adopt_solver(grid, solver, dsolver, comm);  // borrowed, the driver's own, or the slab handle
+    if (st != OCN_SUCCESS) {
+        ocn_rk3_driver_destroy(d);
+        return st;
     }
     // fold the pressure correction into the loads of the fused launch: all-periodic grids the tiled kernel covers, one GPU or a slab.
     // OCN_CORRECT_ON_LOAD=0 (on a slab also OCN_DIST_CORRECT_ON_LOAD=0, the Python host's switch) is the conservative path for a first
@@ -330,17 +242,14 @@ extern "C" int ocn_rk3_driver_configure(ocn_rk3_driver_t d, int32_t defer_correc
 extern "C" int ocn_rk3_driver_time_step(ocn_rk3_driver_t d, double dt, void *stream)
 {
     OCN_REQUIRE(d, "ocn_rk3_driver_time_step: null driver");
-    // γ, ζ each rounded once to Float64 (runge_kutta_3.jl:53-62)
-    const double g1 = 8.0 / 15, g2 = 5.0 / 12, g3 = 3.0 / 4, z2 = -17.0 / 60, z3 = -5.0 / 12;
+    using namespace ocn::rk3;
     int st;
     if (!d->started) {  // iteration 0: update_state!(model) with the tendencies
-        st = fill_velocities(d, 0, stream);
-        if (st != OCN_SUCCESS) return st;
-        st = ocn_compute_momentum_tendencies(&d->grid, d->U[0], d->U[1], d->U[2], d->Gn[0], d->Gn[1], d->Gn[2], nullptr, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(fill_velocities(d, 0, stream));
+        OCN_TRY(ocn_compute_momentum_tendencies(&d->grid, d->U[0], d->U[1], d->U[2], d->Gn[0], d->Gn[1], d->Gn[2], nullptr, stream));
         d->started = true;
     }
-    const double first_stage_dt = g1 * dt, second_stage_dt = (g2 + z2) * dt, third_stage_dt = (g3 + z3) * dt;
+    const StageDt stage = stage_dt(dt);
     // ---- first stage
     if (d->pending) {
         const bool pc = d->correction_pending;  // the previous step's third-stage correction rides on this launch's loads
@@ -348,23 +257,19 @@ extern "C" int ocn_rk3_driver_time_step(ocn_rk3_driver_t d, double dt, void *str
                           pc && d->wrapped_loads ? OCN_RK3_WRAPPED_LOADS : 0, stream);
         d->correction_pending = false;
     } else {
-        st = ocn_rk3_substep(&d->grid, 3, d->U, d->Gn, d->Gm, LOCS, dt, g1, 0.0, 0, stream);
+        st = ocn_rk3_substep(&d->grid, 3, d->U, d->Gn, d->Gm, d->locs, dt, g1, 0.0, 0, stream);
     }
     if (st != OCN_SUCCESS) return st;
-    st = project_and_advance(d, dt, first_stage_dt, g2, z2, false, stream);  // ... ends with the second substep
-    if (st != OCN_SUCCESS) return st;
-    st = project_and_advance(d, dt, second_stage_dt, g3, z3, true, stream);  // ... ends with the third substep (d->pending = true below)
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(project_and_advance(d, dt, stage.first, g2, z2, false, stream));  // ... ends with the second substep
+    OCN_TRY(project_and_advance(d, dt, stage.second, g3, z3, true, stream));  // ... ends with the third substep (d->pending = true below)
     // ---- third stage: projection; its compute_tendencies! is fused into the next step's first substep, and so is -- when the
     //      correction is deferred -- pressure_correct_velocities! itself
     if (d->defer_correction) {
-        st = project_for_load(d, third_stage_dt, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(project_for_load(d, stage.third, stream));
         d->correction_pending = true;
-        d->correction_dt = third_stage_dt;
+        d->correction_dt = stage.third;
     } else {
-        st = project_and_correct(d, third_stage_dt, true, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(project_and_correct(d, stage.third, true, stream));
     }
     d->pending = true;
     d->iteration += 1;
@@ -377,34 +282,23 @@ extern "C" int ocn_rk3_driver_flush(ocn_rk3_driver_t d, void *stream)
     if (d->correction_pending && d->pending && d->fused_flush) {
         // both in one pass: the launch corrects on load, stores the corrected velocities into the other set and G^n of them; then the p
         // halos a caller sees after the separate passes (fill_pressure) and the velocity halos
-        int st = ocn_compute_momentum_tendencies_rk3_flags(&d->grid, d->U[0], d->U[1], d->U[2], d->Gn[0], d->Gn[1], d->Gn[2], nullptr, nullptr,
-                                                           nullptr, d->A[0], d->A[1], d->A[2], 0.0, 0.0, 0.0, 0, d->p, d->correction_dt,
-                                                           OCN_RK3_CORRECT_ONLY | (d->wrapped_loads ? OCN_RK3_WRAPPED_LOADS : 0), stream);
-        if (st != OCN_SUCCESS) return st;
-        for (int f = 0; f < 3; ++f) std::swap(d->U[f], d->A[f]);
+        OCN_TRY(ocn_compute_momentum_tendencies_rk3_flags(&d->grid, d->U[0], d->U[1], d->U[2], d->Gn[0], d->Gn[1], d->Gn[2], nullptr, nullptr,
+                                                          nullptr, d->A[0], d->A[1], d->A[2], 0.0, 0.0, 0.0, 0, d->p, d->correction_dt,
+                                                          OCN_RK3_CORRECT_ONLY | (d->wrapped_loads ? OCN_RK3_WRAPPED_LOADS : 0), stream));
+        d->swap_sets();
         d->correction_pending = d->pending = false;
-        st = fill_pressure(d, stream);
-        if (st != OCN_SUCCESS) return st;
-        st = fill_velocities(d, 0, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(fill_pressure(d, stream));
+        OCN_TRY(fill_velocities(d, 0, stream));
     }
     if (d->correction_pending) {  // the deferred third-stage correction: p halos, pressure_correct_velocities!, velocity halos
-        int st = project_and_correct(d, d->correction_dt, false, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(project_and_correct(d, d->correction_dt, false, stream));
         d->correction_pending = false;
     }
     if (d->pending) {  // complete the deferred compute_tendencies!: G^n of the current state
-        int st = ocn_compute_momentum_tendencies(&d->grid, d->U[0], d->U[1], d->U[2], d->Gn[0], d->Gn[1], d->Gn[2], nullptr, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(ocn_compute_momentum_tendencies(&d->grid, d->U[0], d->U[1], d->U[2], d->Gn[0], d->Gn[1], d->Gn[2], nullptr, stream));
         d->pending = false;
     }
-    if (d->U[0] != d->user[0]) {  // bring the velocities home (an odd number of fused launches since the last flush)
-        for (int f = 0; f < 3; ++f) {
-            OCN_CHECK_HIP(hipMemcpyAsync(d->user[f], d->U[f], d->bytes[f], hipMemcpyDeviceToDevice, ocn::as_stream(stream)));
-            std::swap(d->U[f], d->A[f]);
-        }
-    }
-    return OCN_SUCCESS;
+    return d->bring_home(stream);  // (an odd number of fused launches since the last flush)
 }
 
 extern "C" int ocn_rk3_driver_fields(ocn_rk3_driver_t d, double **u, double **v, double **w, double **Gu, double **Gv, double **Gw)

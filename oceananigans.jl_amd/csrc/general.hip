@@ -618,8 +618,7 @@ int launch_momentum_tendencies_general(const ocn_grid *grid, int centered2, cons
                                        double *Gv, double *Gw, const int32_t *range, hipStream_t stream, const ocn::MomentumFinal *fin)
 {
     gen::GRange r;
-    int st = make_grange(grid, range, r);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_grange(grid, range, r));
     const bool fluxes = fin && (fin->bottom[0].kind || fin->bottom[1].kind || fin->top[0].kind || fin->top[1].kind);
     const bool finish = fin && (fin->sc.on || fluxes);
     const gen::Fields F = make_fields(grid, u, v, w, centered2);
@@ -632,8 +631,7 @@ int launch_momentum_tendencies_general(const ocn_grid *grid, int centered2, cons
             for (int f = 0; f < 3; ++f) { fz.Gm[f] = fin->sub[f].Gm; fz.Uo[f] = fin->sub[f].out; }
             fz.dt = fin->sc.dt; fz.gamma = fin->sc.gamma; fz.zeta = fin->sc.zeta; fz.on = 1; fz.has_zeta = fin->sc.has_zeta;
         }
-        st = launch_momentum_tendencies_box(grid, u, v, w, Gu, Gv, Gw, box, &launched, stream, (fin && fin->sc.on) ? &fz : nullptr, range != nullptr);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(launch_momentum_tendencies_box(grid, u, v, w, Gu, Gv, Gw, box, &launched, stream, (fin && fin->sc.on) ? &fz : nullptr, range != nullptr));
         if (launched) cells = frames_around(grid, box, r);
     }
     OCN_GEN_LAUNCH(momentum_tendencies_general, cells, F, Gu, Gv, Gw);
@@ -649,8 +647,7 @@ int launch_tracer_tendency_general(const ocn_grid *grid, int centered2, const do
                                    double *Gc, const int32_t *range, hipStream_t stream, const ocn::TracerFuse *fuse, const ocn::ForcingDev *forcing)
 {
     gen::GRange r;
-    int st = make_grange(grid, range, r);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_grange(grid, range, r));
     const GridDev gd = ocn::to_dev(*grid);
     ocn::TracerFuse tf{};
     if (fuse) tf = *fuse;
@@ -660,8 +657,7 @@ int launch_tracer_tendency_general(const ocn_grid *grid, int centered2, const do
     int32_t box[4];
     if (interior_box(grid, centered2, range, box)) {
         int launched = 0;
-        st = launch_tracer_tendency_box(grid, u, v, w, c, Gc, box, &launched, stream, fuse ? &tf : nullptr, range != nullptr, forcing);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(launch_tracer_tendency_box(grid, u, v, w, c, Gc, box, &launched, stream, fuse ? &tf : nullptr, range != nullptr, forcing));
         if (launched) cells = frames_around(grid, box, r);
     }
     OCN_GEN_LAUNCH(tracer_tendency_general, cells, F, c, Gc);
@@ -686,16 +682,14 @@ int launch_momentum_extra_general(const ocn_grid *grid, const ocn::TermsDev &t, 
 {
     const bool finish = fin && (fin->sc.on || fin->bottom[0].kind || fin->bottom[1].kind || fin->top[0].kind || fin->top[1].kind);
     gen::GRange r;
-    int st = make_grange(grid, range, r);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_grange(grid, range, r));
     const gen::Fields F = make_fields(grid, u, v, w, 0);
     gen::GFrames cells = whole_range(r);
     // interior box (the tiled finishing pass with per-field layouts: every stress once per face, velocities through LDS) + wall frames
     int32_t box[4];
     if (interior_box(grid, 0, range, box)) {
         int launched = 0;
-        st = launch_momentum_extra_box(grid, t, u, v, w, Gu, Gv, Gw, box, &launched, stream, fin, range != nullptr, stokes, forcing);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(launch_momentum_extra_box(grid, t, u, v, w, Gu, Gv, Gw, box, &launched, stream, fin, range != nullptr, stokes, forcing));
         if (launched) cells = frames_around(grid, box, r);
     }
     ocn::with_extra_descriptors(stokes, forcing, [&](auto... x) {

@@ -361,8 +361,7 @@ int launch_barotropic_mode_walls(const ocn_grid *grid, const double *u, const do
 int launch_barotropic_corrector_walls(const ocn_grid *grid, double *u, double *v, const double *U, const double *V, double *Ub, double *Vb,
                                       double H, hipStream_t stream)
 {
-    int st = launch_barotropic_mode_walls(grid, u, v, Ub, Vb, stream);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(launch_barotropic_mode_walls(grid, u, v, Ub, Vb, stream));
     GridDev g = to_dev(*grid);
     hipLaunchKernelGGL(barotropic_corrector_walls_kernel, xy_blocks(g.Nx, g.Ny, g.Nz), dim3(64, 4, 1), 0, stream, g, u, v, U, V, Ub, Vb, H);
     OCN_CHECK_HIP(hipGetLastError());

@@ -492,8 +492,7 @@ int launch_barotropic_corrector_immersed(const ocn_grid *grid, const double *Hfc
                                          const double *V, double *Ub, double *Vb, hipStream_t stream)
 {
     // integrate_barotropic_mode! (:13-37): on a static grid σ = 1, also where h = 0, and u, v have just been masked: the plain column sums
-    int st = launch_barotropic_mode(grid, u, v, Ub, Vb, stream);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(launch_barotropic_mode(grid, u, v, Ub, Vb, stream));
     GridDev g = to_dev(*grid);
     hipLaunchKernelGGL(corrector_immersed_kernel, xy_blocks(g.Nx, g.Ny, z_chunks(g.Nz)), dim3(64, 4, 1), 0, stream, g, Hfc, Hcf, u, v, U, V, Ub, Vb);
     OCN_CHECK_HIP(hipGetLastError());

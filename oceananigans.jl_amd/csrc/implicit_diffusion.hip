@@ -250,8 +250,7 @@ int launch_ivd_explicit_part(const ocn_grid *grid, double nu, const double *u, c
                              hipStream_t stream)
 {
     ivd::Range r;
-    int st = make_ivd_range(grid, range, r);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_ivd_range(grid, range, r));
     const int wx = r.i1 - r.i0 + 1, wy = r.j1 - r.j0 + 1, wz = r.k1 - r.k0 + 1;
     if (wx < 1 || wy < 1 || wz < 1) return OCN_SUCCESS;
     const dim3 block(64, 4, 1), blocks((wx + 63) / 64, (wy + 3) / 4, wz);

@@ -830,8 +830,7 @@ int launch_barotropic_mode(const ocn_grid *grid, const double *u, const double *
 int launch_barotropic_corrector(const ocn_grid *grid, double *u, double *v, const double *U, const double *V, double *Ub, double *Vb, double H,
                                 hipStream_t stream)
 {
-    int st = launch_barotropic_mode(grid, u, v, Ub, Vb, stream);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(launch_barotropic_mode(grid, u, v, Ub, Vb, stream));
     GridDev g = to_dev(*grid);
     dim3 block(64, 4, 1), nb((g.Nx + 63) / 64, (g.Ny + 3) / 4, g.Nz);
     hipLaunchKernelGGL(barotropic_corrector_kernel, nb, block, 0, stream, g, u, v, U, V, Ub, Vb, H);
@@ -995,8 +994,7 @@ int launch_split_explicit_substeps_blocked(const ocn_grid *grid, int n, const do
     const long long plane = (long long)(g.Nx + 2 * g.Hx) * (g.Ny + 2 * g.Hy);
     double *const set0[3] = {eta, U, V}, *const set1[3] = {work, work + plane, work + 2 * plane};
     PlaneLay P{g.Nx, g.Ny, g.Hx, g.Hy, 0, g.Nx, 1};
-    int st = run_blocked_substeps(g.dx, g.dy, P, 0, n, weights, dtau, grav, H, set0, set1, etab, Ub, Vb, GU, GV, stream);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(run_blocked_substeps(g.dx, g.dy, P, 0, n, weights, dtau, grav, H, set0, set1, etab, Ub, Vb, GU, GV, stream));
     dim3 block(64, 4, 1), nb2((g.Nx + 63) / 64, (g.Ny + 3) / 4, 1);
     hipLaunchKernelGGL(split_explicit_update_state_kernel, nb2, block, 0, stream, g, eta, U, V, etab, Ub, Vb);
     OCN_CHECK_HIP(hipGetLastError());
@@ -1062,9 +1060,8 @@ int launch_split_explicit_dist_run(const ocn_grid *grid, int W, int n, const dou
     OCN_CHECK_HIP(hipGetLastError());
     double *const set0[3] = {work, work + wplane, work + 2 * wplane}, *const set1[3] = {work + 3 * wplane, work + 4 * wplane, work + 5 * wplane};
     PlaneLay P{nx, Ny, W, 0, 0, nx, 0};
-    int st = run_blocked_substeps(grid->dx, grid->dy, P, W, n, weights, dtau, grav, H, set0, set1, work + 8 * wplane, work + 9 * wplane,
-                                  work + 10 * wplane, work + 6 * wplane, work + 7 * wplane, stream);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(run_blocked_substeps(grid->dx, grid->dy, P, W, n, weights, dtau, grav, H, set0, set1, work + 8 * wplane, work + 9 * wplane,
+                                 work + 10 * wplane, work + 6 * wplane, work + 7 * wplane, stream));
     hipLaunchKernelGGL(dist_planes_kernel, dim3((nx + 255) / 256, Ny, 3), dim3(256), 0, stream, nx, Ny, grid->Hx, grid->Hy, W, 2, nullptr, nullptr,
                        nullptr, nullptr, nullptr, work, nullptr, nullptr, eta, U, V);
     OCN_CHECK_HIP(hipGetLastError());

@@ -13,26 +13,19 @@
 #include <cstring>
 
 #include "ocn_buoyancy.h"
-#include "ocn_internal.h"
-
-using ocn::GridDev;
-using ocn::Lay;
+#include "ocn_driver_core.h"
 
 namespace {
 constexpr int NF = 3 + OCN_MODEL_MAX_TRACERS;
 }
 
-struct ocn_model_driver {
+// the two sets of the n = 3 + nt prognostic fields and their tendencies, and the handles of the projection (a slab-x rank,
+// ocn_model_driver_create_distributed: RCCL communicator + distributed Poisson handle, both borrowed): ocn_driver_core.h
+struct ocn_model_driver : ocn::FieldSets<NF>, ocn::Projection {
     ocn_grid grid{};
     ocn_model_terms terms{};
-    ocn_poisson_t solver = nullptr;
-    bool owns_solver = true;
-    int n = 3, nt = 0;            // prognostic fields, tracers
+    int nt = 0;  // tracers
     int tT = -1, tS = -1;
-    int32_t locs[NF] = {OCN_LOC_FCC, OCN_LOC_CFC, OCN_LOC_CCF, OCN_LOC_CCC, OCN_LOC_CCC, OCN_LOC_CCC, OCN_LOC_CCC};
-    double *user[NF] = {}, *own[NF] = {}, *U[NF] = {}, *A[NF] = {};
-    double *Gn[NF] = {}, *Gm[NF] = {};
-    size_t bytes[NF] = {};
     double *p = nullptr, *pHY = nullptr, *nu_e = nullptr, *kappa_e[OCN_MODEL_MAX_TRACERS] = {};
     double kappa[OCN_MODEL_MAX_TRACERS] = {}, Cnu = 0.0, Ck[OCN_MODEL_MAX_TRACERS] = {};
     ocn_field_bcs bcs_store[NF];
@@ -50,9 +43,6 @@ struct ocn_model_driver {
     ocn_smagorinsky smagorinsky{};
     bool has_smagorinsky = false;
     long long iteration = 0;
-    // slab-x rank (ocn_model_driver_create_distributed): RCCL communicator + distributed Poisson handle, both borrowed
-    ocn_comm_t comm = nullptr;
-    ocn_dist_poisson_t dsolver = nullptr;
     // interior / buffer split of a slab's stage boundary (update_state_split): the east buffer strip runs on a side stream
     bool split = false;
     hipStream_t side = nullptr;
@@ -83,54 +73,21 @@ void refresh_terms(ocn_model_driver *d)  // the buoyancy tracers' storage altern
     d->terms.S = d->tS >= 0 ? d->U[3 + d->tS] : nullptr;
 }
 
-// fill_halo_regions!(fields): one launch for the tuple, the fields' own bottom / top Value / Gradient conditions included
-int fill_local(ocn_model_driver *d, double *const *fields, const int32_t *locs, const ocn_field_bcs *const *bcs, int n, int fbnv, void *stream)
-{
-    bool any = false;
-    for (int f = 0; f < n && bcs; ++f) any = any || bcs[f];
-    return any ? ocn_fill_halo_regions_bcs(&d->grid, fields, locs, bcs, n, fbnv, stream) : ocn_fill_halo_regions(&d->grid, fields, locs, n, fbnv, stream);
-}
+// fill_halo_regions!(fields): one launch for the tuple, then -- on a slab -- the x exchange with the neighbours
 int fill(ocn_model_driver *d, double *const *fields, const int32_t *locs, const ocn_field_bcs *const *bcs, int n, int fbnv, void *stream)
 {
-    int st = fill_local(d, fields, locs, bcs, n, fbnv, stream);
-    if (st != OCN_SUCCESS || !d->comm) return st;
-    // a slab: local (y, z) fills first, the x exchange with the neighbours last (fill_halo_regions.jl:148-196); synchronous
-    st = ocn_halo_exchange_begin(d->comm, &d->grid, fields, locs, n, stream);
-    if (st != OCN_SUCCESS) return st;
-    return ocn_halo_exchange_end(d->comm, &d->grid, fields, locs, n, stream);
-}
-
-// solve_for_pressure! on one GPU or on a slab (the slab pipelines of the handle, csrc/poisson_dist.hip)
-int solve(ocn_model_driver *d, double stage_dt, void *stream)
-{
-    if (!d->dsolver) return ocn_solve_for_pressure(d->solver, d->p, d->U[0], d->U[1], d->U[2], stage_dt, stream);
-    int st = ocn_dist_poisson_source_term(d->dsolver, d->U[0], d->U[1], d->U[2], stage_dt, stream);
-    if (st != OCN_SUCCESS) return st;
-    st = ocn_dist_poisson_forward_yz(d->dsolver, stream);
-    if (st != OCN_SUCCESS) return st;
-    st = ocn_dist_poisson_exchange(d->dsolver, d->comm, 0, stream);
-    if (st != OCN_SUCCESS) return st;
-    st = ocn_dist_poisson_solve_x(d->dsolver, stream);
-    if (st != OCN_SUCCESS) return st;
-    st = ocn_dist_poisson_exchange(d->dsolver, d->comm, 1, stream);
-    if (st != OCN_SUCCESS) return st;
-    return ocn_dist_poisson_backward_yz(d->dsolver, d->p, stream);
+    return ocn::fill_and_exchange(&d->grid, d->comm, fields, locs, bcs, n, fbnv, stream);
 }
 
 // compute_auxiliaries! (update_nonhydrostatic_model_state.jl:59-70) + the diffusivity halo fill (:48)
 int compute_auxiliaries(ocn_model_driver *d, void *stream)
 {
-    int st;
     if (d->terms.closure == 2) {
-        st = d->has_smagorinsky
-                 ? ocn_compute_smagorinsky_diffusivities(&d->grid, &d->terms, &d->smagorinsky, d->U[0], d->U[1], d->U[2], d->nu_e, d->kappa_e, stream)
-                 : ocn_compute_amd_diffusivities(&d->grid, d->Cnu, d->U[0], d->U[1], d->U[2], d->nu_e, d->nt, d->Ck, d->U + 3, d->kappa_e, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(d->has_smagorinsky
+                    ? ocn_compute_smagorinsky_diffusivities(&d->grid, &d->terms, &d->smagorinsky, d->U[0], d->U[1], d->U[2], d->nu_e, d->kappa_e, stream)
+                    : ocn_compute_amd_diffusivities(&d->grid, d->Cnu, d->U[0], d->U[1], d->U[2], d->nu_e, d->nt, d->Ck, d->U + 3, d->kappa_e, stream));
     }
-    if (d->pHY) {
-        st = ocn_update_hydrostatic_pressure(&d->grid, &d->terms, d->pHY, stream);
-        if (st != OCN_SUCCESS) return st;
-    }
+    if (d->pHY) OCN_TRY(ocn_update_hydrostatic_pressure(&d->grid, &d->terms, d->pHY, stream));
     if (d->terms.closure == 2) {
         double *f[1 + OCN_MODEL_MAX_TRACERS];
         int32_t l[1 + OCN_MODEL_MAX_TRACERS];
@@ -145,8 +102,7 @@ int compute_auxiliaries(ocn_model_driver *d, void *stream)
             l[nf] = OCN_LOC_CCC;
             nf += 1;
         }
-        st = fill(d, f, l, nullptr, nf, 1, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(fill(d, f, l, nullptr, nf, 1, stream));
     }
     return OCN_SUCCESS;
 }
@@ -154,29 +110,25 @@ int compute_auxiliaries(ocn_model_driver *d, void *stream)
 // update_state!(model; compute_tendencies = false): tupled halo fill (fill_boundary_normal_velocities = false) + auxiliaries
 int update_state(ocn_model_driver *d, void *stream)
 {
-    int st = fill(d, d->U, d->locs, d->bcs, d->n, 0, stream);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(fill(d, d->U, d->locs, d->bcs, d->n, 0, stream));
     return compute_auxiliaries(d, stream);
 }
 
 // compute_tendencies! (compute_nonhydrostatic_tendencies.jl:17-54) with the boundary contributions (:204-213)
 int compute_tendencies(ocn_model_driver *d, void *stream)
 {
-    int st = ocn_compute_momentum_tendencies_terms_forced(&d->grid, &d->terms, d->has_stokes ? &d->stokes : nullptr,
-                                                          d->momentum_forced ? d->forcing : nullptr, d->U[0], d->U[1], d->U[2], d->Gn[0], d->Gn[1],
-                                                          d->Gn[2], nullptr, stream);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(ocn_compute_momentum_tendencies_terms_forced(&d->grid, &d->terms, d->has_stokes ? &d->stokes : nullptr,
+                                                         d->momentum_forced ? d->forcing : nullptr, d->U[0], d->U[1], d->U[2], d->Gn[0], d->Gn[1],
+                                                         d->Gn[2], nullptr, stream));
     for (int t = 0; t < d->nt; ++t) {
-        st = ocn_compute_tracer_tendency_terms_forced(&d->grid, &d->terms, d->terms.closure == 1 ? d->kappa[t] : 0.0,
-                                                      d->terms.closure == 2 ? d->kappa_e[t] : nullptr, d->forcing[3 + t], d->U[0], d->U[1],
-                                                      d->U[2], d->U[3 + t], d->Gn[3 + t], nullptr, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(ocn_compute_tracer_tendency_terms_forced(&d->grid, &d->terms, d->terms.closure == 1 ? d->kappa[t] : 0.0,
+                                                         d->terms.closure == 2 ? d->kappa_e[t] : nullptr, d->forcing[3 + t], d->U[0], d->U[1],
+                                                         d->U[2], d->U[3 + t], d->Gn[3 + t], nullptr, stream));
     }
     if (d->any_flux) {
         const ocn_field_bcs *fb[NF];
         for (int f = 0; f < d->n; ++f) fb[f] = flux_bcs(d, f);
-        st = ocn_apply_flux_bcs(&d->grid, d->Gn, d->U, d->locs, fb, d->n, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(ocn_apply_flux_bcs(&d->grid, d->Gn, d->U, d->locs, fb, d->n, stream));
     }
     d->pending = false;
     return OCN_SUCCESS;
@@ -207,18 +159,16 @@ int launch_tendencies(ocn_model_driver *d, double dt, double gamma, double zeta,
             const double *Gp[2] = {d->Gm[3 + q], d->Gm[4 + q]};
             double *out[2] = {d->A[3 + q], d->A[4 + q]};
             int32_t did = 0;
-            st = ocn_compute_tracer_pair_tendency_terms_rk3(&d->grid, &d->terms, kap, ke, fb, d->U[0], d->U[1], d->U[2], c, G, Gp, out, dt, gamma,
-                                                            zeta, has_zeta, range, &did, stream);
-            if (st != OCN_SUCCESS) return st;
+            OCN_TRY(ocn_compute_tracer_pair_tendency_terms_rk3(&d->grid, &d->terms, kap, ke, fb, d->U[0], d->U[1], d->U[2], c, G, Gp, out, dt, gamma,
+                                                               zeta, has_zeta, range, &did, stream));
             if (did) {
                 q += 2;
                 continue;
             }
         }
-        st = ocn_compute_tracer_tendency_terms_rk3_forced(&d->grid, &d->terms, kap[0], d->terms.closure == 2 ? d->kappa_e[q] : nullptr,
-                                                          d->forcing[3 + q], flux_bcs(d, 3 + q), d->U[0], d->U[1], d->U[2], d->U[3 + q], d->Gn[3 + q],
-                                                          d->Gm[3 + q], d->A[3 + q], dt, gamma, zeta, has_zeta, range, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(ocn_compute_tracer_tendency_terms_rk3_forced(&d->grid, &d->terms, kap[0], d->terms.closure == 2 ? d->kappa_e[q] : nullptr,
+                                                             d->forcing[3 + q], flux_bcs(d, 3 + q), d->U[0], d->U[1], d->U[2], d->U[3 + q], d->Gn[3 + q],
+                                                             d->Gm[3 + q], d->A[3 + q], dt, gamma, zeta, has_zeta, range, stream));
         q += 1;
     }
     return OCN_SUCCESS;
@@ -226,7 +176,7 @@ int launch_tendencies(ocn_model_driver *d, double dt, double gamma, double zeta,
 
 void swap_sets(ocn_model_driver *d)
 {
-    for (int f = 0; f < d->n; ++f) std::swap(d->U[f], d->A[f]);
+    d->swap_sets();
     refresh_terms(d);
     d->pending = false;
 }
@@ -234,8 +184,7 @@ void swap_sets(ocn_model_driver *d)
 // compute_tendencies! + the next rk3_substep! of every prognostic field, then the two sets of arrays trade places
 int fused_launch(ocn_model_driver *d, double dt, double gamma, double zeta, int has_zeta, void *stream)
 {
-    int st = launch_tendencies(d, dt, gamma, zeta, has_zeta, nullptr, stream);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(launch_tendencies(d, dt, gamma, zeta, has_zeta, nullptr, stream));
     swap_sets(d);
     return OCN_SUCCESS;
 }
@@ -261,8 +210,7 @@ int update_state_split(ocn_model_driver *d, double dt, double gamma, double zeta
     auto hydrostatic = [&](int i0, int i1, void *s) {
         return d->pHY ? ocn_update_hydrostatic_pressure_range(&d->grid, &d->terms, d->pHY, i0, i1, s) : OCN_SUCCESS;
     };
-#define OCN_TRY(expr) do { int st_ = (expr); if (st_ != OCN_SUCCESS) return st_; } while (0)
-    OCN_TRY(fill_local(d, d->U, d->locs, d->bcs, d->n, 0, stream));
+    OCN_TRY(ocn::fill_local(&d->grid, d->U, d->locs, d->bcs, d->n, 0, stream));
     OCN_TRY(ocn_halo_exchange_begin(d->comm, &d->grid, d->U, d->locs, d->n, stream));
     // interior: the diffusivities of columns 2 .. nx-1 read u, v, w, c at i-1 .. i+1 (local); pHY' of a column reads that column only
     OCN_TRY(diffusivities(2, nx - 1, stream));
@@ -297,7 +245,6 @@ int update_state_split(ocn_model_driver *d, double dt, double gamma, double zeta
     } else {
         OCN_TRY(launch_tendencies(d, dt, gamma, zeta, has_zeta, west, stream));
     }
-#undef OCN_TRY
     swap_sets(d);
     return OCN_SUCCESS;
 }
@@ -309,26 +256,16 @@ int project(ocn_model_driver *d, double stage_dt, bool minimal, void *stream)
 {
     const int32_t ploc = OCN_LOC_CCC;
     double *pf[1] = {d->p};
-    int st;
     if (d->comm && minimal) {
-        const bool any = d->bcs[0] || d->bcs[1] || d->bcs[2];
-        st = any ? ocn_fill_halo_regions_bcs(&d->grid, d->U, d->locs, d->bcs, 3, 1, stream) : ocn_fill_halo_regions(&d->grid, d->U, d->locs, 3, 1, stream);
-        if (st != OCN_SUCCESS) return st;
-        st = ocn_halo_exchange_plane(d->comm, &d->grid, d->U[0], OCN_LOC_FCC, 0, stream);
-        if (st != OCN_SUCCESS) return st;
-        st = solve(d, stage_dt, stream);
-        if (st != OCN_SUCCESS) return st;
-        st = ocn_fill_halo_regions(&d->grid, pf, &ploc, 1, 1, stream);
-        if (st != OCN_SUCCESS) return st;
-        st = ocn_halo_exchange_plane(d->comm, &d->grid, d->p, OCN_LOC_CCC, 1, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(ocn::fill_local(&d->grid, d->U, d->locs, d->bcs, 3, 1, stream));
+        OCN_TRY(ocn_halo_exchange_plane(d->comm, &d->grid, d->U[0], OCN_LOC_FCC, 0, stream));
+        OCN_TRY(d->solve(d->p, d->U, stage_dt, stream));
+        OCN_TRY(ocn_fill_halo_regions(&d->grid, pf, &ploc, 1, 1, stream));
+        OCN_TRY(ocn_halo_exchange_plane(d->comm, &d->grid, d->p, OCN_LOC_CCC, 1, stream));
     } else {
-        st = fill(d, d->U, d->locs, d->bcs, 3, 1, stream);
-        if (st != OCN_SUCCESS) return st;
-        st = solve(d, stage_dt, stream);
-        if (st != OCN_SUCCESS) return st;
-        st = fill(d, pf, &ploc, nullptr, 1, 1, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(fill(d, d->U, d->locs, d->bcs, 3, 1, stream));
+        OCN_TRY(d->solve(d->p, d->U, stage_dt, stream));
+        OCN_TRY(fill(d, pf, &ploc, nullptr, 1, 1, stream));
     }
     return ocn_pressure_correct_velocities(&d->grid, d->U[0], d->U[1], d->U[2], d->p, stage_dt, stream);
 }
@@ -336,12 +273,10 @@ int project(ocn_model_driver *d, double stage_dt, bool minimal, void *stream)
 // everything between two substeps (runge_kutta_3.jl:103-118)
 int project_and_advance(ocn_model_driver *d, double dt, double stage_dt, double gamma_next, double zeta_next, void *stream)
 {
-    int st = project(d, stage_dt, true, stream);
-    if (st != OCN_SUCCESS) return st;
-    for (int f = 0; f < d->n; ++f) std::swap(d->Gn[f], d->Gm[f]);  // cache_previous_tendencies! as a role swap
+    OCN_TRY(project(d, stage_dt, true, stream));
+    d->swap_tendencies();
     if (d->split) return update_state_split(d, dt, gamma_next, zeta_next, 1, stream);
-    st = update_state(d, stream);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(update_state(d, stream));
     return fused_launch(d, dt, gamma_next, zeta_next, 1, stream);
 }
 }  // namespace
@@ -349,15 +284,11 @@ int project_and_advance(ocn_model_driver *d, double dt, double stage_dt, double 
 extern "C" int ocn_model_driver_destroy(ocn_model_driver_t d)
 {
     if (!d) return OCN_SUCCESS;
-    if (d->solver && d->owns_solver) ocn_poisson_destroy(d->solver);
+    d->release_solver();
     if (d->side) { (void)hipStreamSynchronize(d->side); (void)hipStreamDestroy(d->side); }
     if (d->fork) (void)hipEventDestroy(d->fork);
     if (d->join) (void)hipEventDestroy(d->join);
-    for (int f = 0; f < NF; ++f) {
-        if (d->own[f]) (void)hipFree(d->own[f]);
-        if (d->Gn[f]) (void)hipFree(d->Gn[f]);
-        if (d->Gm[f]) (void)hipFree(d->Gm[f]);
-    }
+    d->release();
     delete d;
     return OCN_SUCCESS;
 }
@@ -368,14 +299,12 @@ static int model_driver_create(ocn_model_driver_t *out, const ocn_grid *grid, co
     OCN_REQUIRE(out && grid && desc && u && v && w && p, "ocn_model_driver_create: null argument");
     // one GPU: any topology the per-call entry points take (walls / Flat directions in x, y since round 4: the fused stage boundaries of
     // general.hip -- tiled epilogues on the interior box, finishing kernels on the wall frames)
-    int st = comm ? ocn::validate_grid(grid) : ocn::validate_grid_any(grid);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(comm ? ocn::validate_grid(grid) : ocn::validate_grid_any(grid));
     if (comm) {
         OCN_REQUIRE(grid->tx == OCN_FULLY_CONNECTED && grid->ty == OCN_PERIODIC && dsolver,
                     "ocn_model_driver_create_distributed: a (FullyConnected, Periodic, *) local grid and its distributed Poisson handle");
         int32_t fast = 0;
-        st = ocn_dist_poisson_pipeline(dsolver, &fast);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(ocn_dist_poisson_pipeline(dsolver, &fast));
         if (fast < 1 || fast > 3) {
             ocn::set_error("ocn_model_driver_create_distributed: the Poisson handle runs the transposing path (sizes outside the slab "
                            "pipelines): drive it through the per-call entry points");
@@ -383,8 +312,7 @@ static int model_driver_create(ocn_model_driver_t *out, const ocn_grid *grid, co
         }
         OCN_REQUIRE(grid->Nx >= grid->Hx, "ocn_model_driver_create_distributed: the local slab must be at least a halo wide");
     } else {
-        OCN_REQUIRE(grid->tx == OCN_PERIODIC || grid->tx == OCN_BOUNDED || grid->tx == OCN_FLAT,
-                    "ocn_model_driver_create: a partitioned x (topology %d) needs ocn_model_driver_create_distributed", grid->tx);
+        OCN_TRY(ocn::require_unpartitioned_x(grid, "ocn_model_driver"));
         if (grid->tx != OCN_PERIODIC || grid->ty != OCN_PERIODIC)
             for (int f = 0; f < 3 + desc->n_tracers && f < 3 + OCN_MODEL_MAX_TRACERS; ++f) {
                 const ocn_field_bcs *b = desc->bcs[f];
@@ -417,8 +345,6 @@ static int model_driver_create(ocn_model_driver_t *out, const ocn_grid *grid, co
     d->tT = needT ? desc->tracer_T : -1;
     d->tS = needS ? desc->tracer_S : -1;
     d->p = p;
-    d->comm = comm;
-    d->dsolver = dsolver;
     d->pHY = desc->pHY;
     d->nu_e = desc->nu_e;
     d->Cnu = desc->C_nu;
@@ -447,23 +373,14 @@ static int model_driver_create(ocn_model_driver_t *out, const ocn_grid *grid, co
     d->momentum_extra = t.coriolis != 0 || t.closure != 0 || t.buoyancy != OCN_BUOYANCY_NONE || t.advection != OCN_ADVECTION_WENO5 ||
                         has_flux(d->bcs[0]) || has_flux(d->bcs[1]);
     d->base_momentum_extra = d->momentum_extra;
-    GridDev g = ocn::to_dev(*grid);
-    for (int f = 0; f < d->n; ++f) {
-        const Lay L = ocn::make_lay(g, d->locs[f]);
-        d->bytes[f] = (size_t)L.sx * L.sy * L.sz * sizeof(double);
-        for (double **buf : {&d->own[f], &d->Gn[f], &d->Gm[f]}) {
-            if (hipMalloc((void **)buf, d->bytes[f]) != hipSuccess || hipMemset(*buf, 0, d->bytes[f]) != hipSuccess) {
-                ocn::set_error("ocn_model_driver_create: device allocation of %zu bytes failed", d->bytes[f]);
-                ocn_model_driver_destroy(d);
-                return OCN_ERR_ALLOC;
-            }
-        }
-        d->U[f] = d->user[f];
-        d->A[f] = d->own[f];
+    int st = d->allocate(*grid, "ocn_model_driver_create");
+    if (st == OCN_SUCCESS) st = d->adopt_solver(grid, solver, dsolver, comm);  // borrowed, the driver's own, or the slab handle
+    if (st != OCN_SUCCESS) {
+        ocn_model_driver_destroy(d);
+        return st;
     }
     refresh_terms(d);
     if (comm) {
-        d->owns_solver = false;
         // interior / buffer split of the stage boundaries (OCN_DIST_GENERAL_OVERLAP=0: every exchange synchronous, as before round 4)
         const char *e = std::getenv("OCN_DIST_GENERAL_OVERLAP");
         d->split = grid->Nx - 2 * grid->Hx >= 1 && grid->Hx >= 2 && !(e && e[0] == '0');
@@ -473,15 +390,6 @@ static int model_driver_create(ocn_model_driver_t *out, const ocn_grid *grid, co
             ocn::set_error("ocn_model_driver_create_distributed: stream / event creation failed");
             ocn_model_driver_destroy(d);
             return OCN_ERR_HIP;
-        }
-    } else if (solver) {
-        d->solver = solver;
-        d->owns_solver = false;
-    } else {
-        st = ocn_poisson_create(&d->solver, grid);
-        if (st != OCN_SUCCESS) {
-            ocn_model_driver_destroy(d);
-            return st;
         }
     }
     st = update_state(d, stream);  // update_state!(model; compute_tendencies = false) of the constructor
@@ -509,31 +417,25 @@ extern "C" int ocn_model_driver_create_distributed(ocn_model_driver_t *out, cons
 extern "C" int ocn_model_driver_time_step(ocn_model_driver_t d, double dt, void *stream)
 {
     OCN_REQUIRE(d, "ocn_model_driver_time_step: null driver");
-    const double g1 = 8.0 / 15, g2 = 5.0 / 12, g3 = 3.0 / 4, z2 = -17.0 / 60, z3 = -5.0 / 12;  // runge_kutta_3.jl:53-62
+    using namespace ocn::rk3;
     int st;
     if (!d->started) {  // iteration 0: update_state!(model) with the tendencies
-        st = update_state(d, stream);
-        if (st != OCN_SUCCESS) return st;
-        st = compute_tendencies(d, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(update_state(d, stream));
+        OCN_TRY(compute_tendencies(d, stream));
         d->started = true;
     }
-    const double first_stage_dt = g1 * dt, second_stage_dt = (g2 + z2) * dt, third_stage_dt = (g3 + z3) * dt;
+    const StageDt stage = stage_dt(dt);
     // ---- first stage
     if (d->pending)
         st = fused_launch(d, dt, g1, 0.0, 0, stream);  // the deferred compute_tendencies! of the last step + this step's first substep
     else
         st = ocn_rk3_substep(&d->grid, d->n, d->U, d->Gn, d->Gm, d->locs, dt, g1, 0.0, 0, stream);
     if (st != OCN_SUCCESS) return st;
-    st = project_and_advance(d, dt, first_stage_dt, g2, z2, stream);   // ... ends with the second substep
-    if (st != OCN_SUCCESS) return st;
-    st = project_and_advance(d, dt, second_stage_dt, g3, z3, stream);  // ... ends with the third substep
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(project_and_advance(d, dt, stage.first, g2, z2, stream));   // ... ends with the second substep
+    OCN_TRY(project_and_advance(d, dt, stage.second, g3, z3, stream));  // ... ends with the third substep
     // ---- third stage: projection, update_state!; its compute_tendencies! is fused into the next step's first substep
-    st = project(d, third_stage_dt, false, stream);
-    if (st != OCN_SUCCESS) return st;
-    st = update_state(d, stream);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(project(d, stage.third, false, stream));
+    OCN_TRY(update_state(d, stream));
     d->pending = true;
     d->iteration += 1;
     return OCN_SUCCESS;
@@ -543,16 +445,10 @@ extern "C" int ocn_model_driver_flush(ocn_model_driver_t d, void *stream)
 {
     OCN_REQUIRE(d, "ocn_model_driver_flush: null driver");
     if (d->pending) {
-        int st = compute_tendencies(d, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(compute_tendencies(d, stream));
     }
-    if (d->U[0] != d->user[0]) {  // an odd number of fused launches since the last flush: bring the fields home
-        for (int f = 0; f < d->n; ++f) {
-            OCN_CHECK_HIP(hipMemcpyAsync(d->user[f], d->U[f], d->bytes[f], hipMemcpyDeviceToDevice, ocn::as_stream(stream)));
-            std::swap(d->U[f], d->A[f]);
-        }
-        refresh_terms(d);
-    }
+    OCN_TRY(d->bring_home(stream));  // (an odd number of fused launches since the last flush)
+    refresh_terms(d);
     return OCN_SUCCESS;
 }
 
@@ -580,8 +476,7 @@ extern "C" int ocn_model_driver_set_forcing(ocn_model_driver_t d, const ocn_forc
     OCN_REQUIRE(!d->pending, "ocn_model_driver_set_forcing: call before the first time step or after ocn_model_driver_flush");
     static const char *names[NF] = {"u", "v", "w", "tracer 0", "tracer 1", "tracer 2", "tracer 3"};
     for (int f = 0; forcing && f < d->n; ++f) {
-        int st = ocn::validate_forcing(&d->grid, forcing[f], "ocn_model_driver_set_forcing", names[f]);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(ocn::validate_forcing(&d->grid, forcing[f], "ocn_model_driver_set_forcing", names[f]));
     }
     d->momentum_forced = false;
     for (int f = 0; f < NF; ++f) {

@@ -32,6 +32,13 @@ void set_error(const char *fmt, ...);
         }                                     \
     } while (0)
 
+// a call that returns a status: the first failure is the enclosing function's result
+#define OCN_TRY(expr)                          \
+    do {                                       \
+        int st_ = (expr);                      \
+        if (st_ != OCN_SUCCESS) return st_;    \
+    } while (0)
+
 // Device-side copy of the grid, plus derived scalars.  Passed by value to kernels.
 struct GridDev {
     int Nx, Ny, Nz, Hx, Hy, Hz, tx, ty, tz;

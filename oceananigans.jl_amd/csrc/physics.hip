@@ -885,8 +885,7 @@ int launch_momentum_centered2(const ocn_grid *grid, const double *u, const doubl
                               double *Gw, const int32_t *range, hipStream_t stream)
 {
     PRange r;
-    int st = make_prange(grid, range, r);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_prange(grid, range, r));
     if (r.i1 < r.i0 || r.j1 < r.j0 || r.k1 < r.k0) return OCN_SUCCESS;
     GridDev g = ocn::to_dev(*grid);
     const dim3 block = ocn::range_block(r.i1 - r.i0 + 1), nb = ocn::range_grid(block, r.i1 - r.i0 + 1, r.j1 - r.j0 + 1, r.k1 - r.k0 + 1);
@@ -898,8 +897,7 @@ int launch_tracer_centered2(const ocn_grid *grid, const double *u, const double 
                             double *Gc, const int32_t *range, hipStream_t stream)
 {
     PRange r;
-    int st = make_prange(grid, range, r);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_prange(grid, range, r));
     if (r.i1 < r.i0 || r.j1 < r.j0 || r.k1 < r.k0) return OCN_SUCCESS;
     GridDev g = ocn::to_dev(*grid);
     const dim3 block = ocn::range_block(r.i1 - r.i0 + 1), nb = ocn::range_grid(block, r.i1 - r.i0 + 1, r.j1 - r.j0 + 1, r.k1 - r.k0 + 1);
@@ -975,8 +973,7 @@ int launch_momentum_extra(const ocn_grid *grid, const TermsDev &t, const double 
                           const ocn::MomentumFinal *fin, const ocn::StokesDev *stokes, const ocn::MomentumForcingDev *forcing)
 {
     PRange r;
-    int st = make_prange(grid, range, r);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_prange(grid, range, r));
     if (r.i1 < r.i0 || r.j1 < r.j0 || r.k1 < r.k0) return OCN_SUCCESS;
     const ocn::MomentumFinal mf = extra_final(fin);
     const GridDev g = ocn::to_dev(*grid);
@@ -1028,8 +1025,7 @@ int launch_tracer_diffusion(const ocn_grid *grid, double kappa, const double *ka
                             const int32_t *range, hipStream_t stream)
 {
     PRange r;
-    int st = make_prange(grid, range, r);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_prange(grid, range, r));
     if (r.i1 < r.i0 || r.j1 < r.j0 || r.k1 < r.k0) return OCN_SUCCESS;
     GridDev g = ocn::to_dev(*grid);
     const dim3 block = ocn::range_block(r.i1 - r.i0 + 1), nb = ocn::range_grid(block, r.i1 - r.i0 + 1, r.j1 - r.j0 + 1, r.k1 - r.k0 + 1);
@@ -1042,8 +1038,7 @@ int launch_tracer_forcing(const ocn_grid *grid, const ocn::ForcingDev &forcing, 
                           const ocn::TracerFuse *fuse, hipStream_t stream)
 {
     PRange r;
-    int st = make_prange(grid, range, r);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_prange(grid, range, r));
     if (r.i1 < r.i0 || r.j1 < r.j0 || r.k1 < r.k0) return OCN_SUCCESS;
     ocn::TracerFuse tf{};
     if (fuse) tf = *fuse;

@@ -611,7 +611,6 @@ extern "C" int ocn_poisson_solve(ocn_poisson_t s, double *p, void *stream_)
 extern "C" int ocn_solve_for_pressure(ocn_poisson_t s, double *p, const double *u, const double *v, const double *w, double dt,
                                       void *stream)
 {
-    int st = ocn_poisson_compute_source_term(s, u, v, w, dt, stream);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(ocn_poisson_compute_source_term(s, u, v, w, dt, stream));
     return ocn_poisson_solve(s, p, stream);
 }

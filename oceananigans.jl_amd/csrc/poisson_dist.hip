@@ -159,8 +159,7 @@ static int dist_create_impl(ocn_dist_poisson_t *out, const ocn_grid *lg, int32_t
         OCN_REQUIRE(!xbounded || (lg->ty == OCN_BOUNDED && lg->tz == OCN_BOUNDED),
                     "ocn_dist_poisson_create: a Bounded x needs Bounded y and z (distributed_fft_based_poisson_solver.jl:62-66)");
     }
-    int st = ocn::validate_grid_any(lg);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(ocn::validate_grid_any(lg));
     OCN_REQUIRE(R >= 1 && rank >= 0 && rank < R, "ocn_dist_poisson_create: bad rank %d of %d", rank, R);
     OCN_REQUIRE(global_Lx > 0, "ocn_dist_poisson_create: global_Lx must be positive");
     // (distributed_fft_based_poisson_solver.jl:62-66: a Periodic z needs a Periodic y)
@@ -485,8 +484,7 @@ static int dist_tri_y_fft(ocn_dist_poisson *s, int inverse, double *a, hipStream
         return ocn::launch_colfft(Ny, inverse ? ocn::ColFFT::Inverse : ocn::ColFFT::Forward, a, nx, (long long)nx * Ny, nx, Nz, s->tw_y, nullptr, nullptr, nullptr, 1.0, 1, stream);
     Plan &P = inverse ? s->byz : s->fyz;
     for (int k = 0; k < Nz; ++k) {
-        int st = P.exec(a + 2 * (size_t)nx * Ny * k, nullptr, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(P.exec(a + 2 * (size_t)nx * Ny * k, nullptr, stream));
     }
     return OCN_SUCCESS;
 }
@@ -498,11 +496,9 @@ static int dist_tri_y_transform(ocn_dist_poisson *s, int inverse, hipStream_t st
     const int nx = s->nx, Ny = s->grid.Ny, Nz = s->grid.Nz;
     const int n[3] = {nx, Ny, Nz};
     using ocn::DctShuffle;
-    int st = inverse ? launch_dct_shuffle(n, 1, DctShuffle::PreTwiddle, s->yfield, s->send, s->ytw, s->ypartner, stream)
-                     : launch_dct_shuffle(n, 1, DctShuffle::Gather, s->yfield, s->send, s->ytw, nullptr, stream);
-    if (st != OCN_SUCCESS) return st;
-    st = dist_tri_y_fft(s, inverse, s->send, stream);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(inverse ? launch_dct_shuffle(n, 1, DctShuffle::PreTwiddle, s->yfield, s->send, s->ytw, s->ypartner, stream)
+                    : launch_dct_shuffle(n, 1, DctShuffle::Gather, s->yfield, s->send, s->ytw, nullptr, stream));
+    OCN_TRY(dist_tri_y_fft(s, inverse, s->send, stream));
     return inverse ? launch_dct_shuffle(n, 1, DctShuffle::Scatter, s->send, s->yfield, s->ytw, nullptr, stream)
                    : launch_dct_shuffle(n, 1, DctShuffle::PostTwiddle, s->send, s->yfield, s->ytw, s->ypartner, stream);
 }
@@ -519,14 +515,12 @@ extern "C" int ocn_dist_poisson_forward_yz(ocn_dist_poisson_t s, void *stream)
     if (s->tri) return dist_tri_y_transform(s, 0, ocn::as_stream(stream));
     if (s->fast) {  // rhs -> A1 (in recv) -> send, ready for the exchange
         const ocn_grid *g = &s->grid;
-        int st = s->src_u ? ocn::launch_realfft_y(g->Ny, 0, nullptr, s->recv, nullptr, 0, 0, s->nx, g->Nz, s->tw_h, s->tw_y,
-                                                   ocn::as_stream(stream), g, s->src_u, s->src_v, s->src_w, s->src_dt)
-                          : ocn::launch_realfft_y(g->Ny, 0, s->rhs, s->recv, nullptr, 0, 0, s->nx, g->Nz, s->tw_h, s->tw_y, ocn::as_stream(stream));
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(s->src_u ? ocn::launch_realfft_y(g->Ny, 0, nullptr, s->recv, nullptr, 0, 0, s->nx, g->Nz, s->tw_h, s->tw_y,
+                                                  ocn::as_stream(stream), g, s->src_u, s->src_v, s->src_w, s->src_dt)
+                         : ocn::launch_realfft_y(g->Ny, 0, s->rhs, s->recv, nullptr, 0, 0, s->nx, g->Nz, s->tw_h, s->tw_y, ocn::as_stream(stream)));
         if (s->xtri) {  // z in place (stage order), then the local x solves; gsend is ready for the all-gather
             const long long cols = (long long)s->nyt * s->nx;
-            st = ocn::launch_colfft(g->Nz, ocn::ColFFT::Forward, s->recv, cols, 0, (int)cols, 1, s->tw_z, nullptr, nullptr, nullptr, 1.0, 1, ocn::as_stream(stream));
-            if (st != OCN_SUCCESS) return st;
+            OCN_TRY(ocn::launch_colfft(g->Nz, ocn::ColFFT::Forward, s->recv, cols, 0, (int)cols, 1, s->tw_z, nullptr, nullptr, nullptr, 1.0, 1, ocn::as_stream(stream)));
             const double scale = 1.0 / ((double)(g->Ny / 2) * g->Nz);
             return ocn::launch_xtri_sweep(s->recv, s->ly, s->lz, s->nyt, s->nx, g->Nz, g->dx, scale, s->gsend, ocn::as_stream(stream));
         }
@@ -543,13 +537,10 @@ extern "C" int ocn_dist_poisson_solve_x(ocn_dist_poisson_t s, void *stream_)
     if (s->fast && s->tri) {  // recv = [xg S + (ky_l + c z)], S = c Nz
         const int Nz = s->grid.Nz, c = s->ny;
         const long long S = (long long)c * Nz;
-        int st = ocn::launch_colfft(s->Nxg, ocn::ColFFT::Forward, s->recv, S, 0, (int)S, 1, s->tw_x, nullptr, nullptr, nullptr, 1.0, 1, stream);
-        if (st != OCN_SUCCESS) return st;
-        st = ocn::launch_tridiag_z_strided(c, s->Nxg, S, c, Nz, s->lower, s->diag, s->lower, s->recv, s->tscr, s->send, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(ocn::launch_colfft(s->Nxg, ocn::ColFFT::Forward, s->recv, S, 0, (int)S, 1, s->tw_x, nullptr, nullptr, nullptr, 1.0, 1, stream));
+        OCN_TRY(ocn::launch_tridiag_z_strided(c, s->Nxg, S, c, Nz, s->lower, s->diag, s->lower, s->recv, s->tscr, s->send, stream));
         if (s->rank == 0) {  // zero-mean gauge on the (kx, ky) = (0, 0) column: stored position 0 of both
-            st = ocn::launch_remove_mean_mode(c, Nz, s->send, stream);
-            if (st != OCN_SUCCESS) return st;
+            OCN_TRY(ocn::launch_remove_mean_mode(c, Nz, s->send, stream));
         }
         return ocn::launch_colfft(s->Nxg, ocn::ColFFT::Inverse, s->send, S, 0, (int)S, 1, s->tw_x, nullptr, nullptr, nullptr, 1.0, 1, stream);
     }
@@ -562,7 +553,6 @@ extern "C" int ocn_dist_poisson_solve_x(ocn_dist_poisson_t s, void *stream_)
         return ocn::launch_colfft(s->Nxg, ocn::ColFFT::Solve, s->recv, S, 0, (int)S, 1, s->tw_x, s->ly, s->lz + (size_t)s->rank * cz, s->lx, scale, NyH,
                                   stream, s->rank == 0);
     }
-    int st;
     // Bounded x: REDFT10 / REDFT01 along the lines of the x-local field (Nxg, ny, Nz) -- gather / twiddle passes of the single-process
     // solver around the same complex line FFTs, out of place between xfield and xsol; the inverse's 1 / Nxg rides on the plan's scale
     using ocn::DctShuffle;
@@ -572,38 +562,29 @@ extern "C" int ocn_dist_poisson_solve_x(ocn_dist_poisson_t s, void *stream_)
     };
     if (s->xbounded) {
         OCN_REQUIRE(s->tri, "ocn_dist_poisson_solve_x: a Bounded x runs the tridiagonal flavour");
-        st = xshuffle(DctShuffle::Gather, s->xfield, s->xsol);
-        if (st != OCN_SUCCESS) return st;
-        st = s->fx.exec(s->xsol, nullptr, stream);
-        if (st != OCN_SUCCESS) return st;
-        st = xshuffle(DctShuffle::PostTwiddle, s->xsol, s->xfield);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(xshuffle(DctShuffle::Gather, s->xfield, s->xsol));
+        OCN_TRY(s->fx.exec(s->xsol, nullptr, stream));
+        OCN_TRY(xshuffle(DctShuffle::PostTwiddle, s->xsol, s->xfield));
     } else {
-        st = s->fx.exec(s->xfield, nullptr, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(s->fx.exec(s->xfield, nullptr, stream));
     }
     if (s->tri) {
         const int Nz = s->grid.Nz;
-        st = ocn::launch_tridiag_z(s->Nxg, s->ny, Nz, s->lower, s->diag, s->lower, s->xfield, s->tscr, s->xsol, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(ocn::launch_tridiag_z(s->Nxg, s->ny, Nz, s->lower, s->diag, s->lower, s->xfield, s->tscr, s->xsol, stream));
         // zero-mean gauge on the (kx, ky) = (0, 0) column, which lives on rank 0 (stored position 0 is wavenumber 0):
         // the single-process solver's ϕ .- mean(ϕ) (fourier_tridiagonal_poisson_solver.jl:142)
         if (s->rank == 0) {
-            st = ocn::launch_remove_mean_mode((long long)s->Nxg * s->ny, Nz, s->xsol, stream);
-            if (st != OCN_SUCCESS) return st;
+            OCN_TRY(ocn::launch_remove_mean_mode((long long)s->Nxg * s->ny, Nz, s->xsol, stream));
         }
         if (s->xbounded) {
-            st = xshuffle(DctShuffle::PreTwiddle, s->xsol, s->xfield);
-            if (st != OCN_SUCCESS) return st;
-            st = s->bx.exec(s->xfield, s->xsol, stream);
-            if (st != OCN_SUCCESS) return st;
+            OCN_TRY(xshuffle(DctShuffle::PreTwiddle, s->xsol, s->xfield));
+            OCN_TRY(s->bx.exec(s->xfield, s->xsol, stream));
             return xshuffle(DctShuffle::Scatter, s->xsol, s->xfield);
         }
         return s->bx.exec(s->xsol, s->xfield, stream);
     }
     // λy partitioned to this rank's j range; rank 0 zeroes mode (1,1,1) (distributed_fft_based_poisson_solver.jl:104-116,162-164)
-    st = ocn::launch_spectral_solve(s->Nxg, s->ny, s->grid.Nz, s->lx, s->ly, s->lz, s->xfield, s->rank == 0, s->rank * s->ny, 0, stream);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(ocn::launch_spectral_solve(s->Nxg, s->ny, s->grid.Nz, s->lx, s->ly, s->lz, s->xfield, s->rank == 0, s->rank * s->ny, 0, stream));
     return s->bx.exec(s->xfield, nullptr, stream);
 }
 
@@ -620,8 +601,7 @@ extern "C" int ocn_dist_poisson_backward_yz(ocn_dist_poisson_t s, double *p, voi
                                      1.0 / ((double)(g->Ny / 2) * s->Nxg));
     }
     if (s->tri) {
-        int st = dist_tri_y_transform(s, 1, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(dist_tri_y_transform(s, 1, stream));
         return ocn::launch_copy_real(&s->grid, s->yfield, p, stream, ocn::CopySource::Complex);
     }
     if (s->fast) {  // send (after the exchange back) -> A1 (in recv) -> real rows of the local pressure interior
@@ -629,9 +609,8 @@ extern "C" int ocn_dist_poisson_backward_yz(ocn_dist_poisson_t s, double *p, voi
         ocn::GridDev gd = ocn::to_dev(*g);
         ocn::Lay Lp = ocn::make_lay(gd, OCN_LOC_CCC);
         const long long cols = (long long)s->nyt * s->nx;
-        int st = s->xtri ? ocn::launch_colfft(g->Nz, ocn::ColFFT::Inverse, s->recv, cols, 0, (int)cols, 1, s->tw_z, nullptr, nullptr, nullptr, 1.0, 1, stream)
-                         : ocn::launch_colfft_slab_z(g->Nz, 1, s->send, s->recv, s->nx, s->nyt, s->R, s->tw_z, stream);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(s->xtri ? ocn::launch_colfft(g->Nz, ocn::ColFFT::Inverse, s->recv, cols, 0, (int)cols, 1, s->tw_z, nullptr, nullptr, nullptr, 1.0, 1, stream)
+                        : ocn::launch_colfft_slab_z(g->Nz, 1, s->send, s->recv, s->nx, s->nyt, s->R, s->tw_z, stream));
         return ocn::launch_realfft_y(g->Ny, 1, nullptr, s->recv, p + Lp.o, Lp.s2, Lp.s3, s->nx, g->Nz, s->tw_h, s->tw_y, stream);
     }
     if (s->r2c) {
@@ -639,8 +618,7 @@ extern "C" int ocn_dist_poisson_backward_yz(ocn_dist_poisson_t s, double *p, voi
         ocn::Lay Lp = ocn::make_lay(gd, OCN_LOC_CCC);
         return s->byz.exec(s->yfield, p + Lp.o, stream);
     }
-    int st = s->byz.exec(s->yfield, nullptr, stream);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(s->byz.exec(s->yfield, nullptr, stream));
     // copy_real_component! into the local pressure interior; the local grid's parent layout
     return ocn::launch_copy_real(&s->grid, s->yfield, p, stream, ocn::CopySource::Complex);
 }

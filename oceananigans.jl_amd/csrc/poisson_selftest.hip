@@ -145,13 +145,11 @@ int plans_self_test(ocn_poisson *s, const PlanCheck &c)
         std::vector<double> cv(2 * n, 0.0);
         for (size_t q = 0; q < n; ++q) cv[2 * q] = in[q];
         OCN_CHECK_HIP(hipMemcpy(s->spec, cv.data(), 2 * n * sizeof(double), hipMemcpyHostToDevice));
-        int st = s->fwd.exec(s->spec, nullptr, nullptr);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(s->fwd.exec(s->spec, nullptr, nullptr));
         OCN_CHECK_HIP(hipDeviceSynchronize());
         OCN_CHECK_HIP(hipMemcpy(cv.data(), s->spec, 2 * n * sizeof(double), hipMemcpyDeviceToHost));
         if (n <= (size_t)1 << 16) ferr = full_spectrum_error(in, cv, Nx, Ny, Nz, Nx, three_d);
-        st = s->bwd.exec(s->spec, nullptr, nullptr);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(s->bwd.exec(s->spec, nullptr, nullptr));
         OCN_CHECK_HIP(hipDeviceSynchronize());
         OCN_CHECK_HIP(hipMemcpy(cv.data(), s->spec, 2 * n * sizeof(double), hipMemcpyDeviceToHost));
         for (size_t q = 0; q < n; ++q) {
@@ -164,8 +162,7 @@ int plans_self_test(ocn_poisson *s, const PlanCheck &c)
             std::fill(cv.begin(), cv.end(), 0.0);
             for (size_t q = 0; q < n; ++q) cv[2 * q] = in[q];
             OCN_CHECK_HIP(hipMemcpy(s->spec, cv.data(), 2 * n * sizeof(double), hipMemcpyHostToDevice));
-            st = s->fwd.exec(s->spec, nullptr, nullptr);
-            if (st != OCN_SUCCESS) return st;
+            OCN_TRY(s->fwd.exec(s->spec, nullptr, nullptr));
             OCN_CHECK_HIP(hipDeviceSynchronize());
             OCN_CHECK_HIP(hipMemcpy(cv.data(), s->spec, 2 * n * sizeof(double), hipMemcpyDeviceToHost));
             ferr = std::fmax(ferr, wave_spectrum_error(cv, W, Nx, Ny, Nz, Nx, three_d));
@@ -177,8 +174,7 @@ int plans_self_test(ocn_poisson *s, const PlanCheck &c)
         const size_t np = (size_t)Lp.sx * Lp.sy * Lp.sz;
         double *tmp = nullptr;
         OCN_CHECK_HIP(hipMemcpy(s->rhs, in.data(), n * sizeof(double), hipMemcpyHostToDevice));
-        int st = s->fwd.exec(s->rhs, s->spec, nullptr);
-        if (st != OCN_SUCCESS) return st;
+        OCN_TRY(s->fwd.exec(s->rhs, s->spec, nullptr));
         {
             OCN_CHECK_HIP(hipDeviceSynchronize());
             std::vector<double> sp((size_t)c.nxh * Ny * Nz * 2);
@@ -188,10 +184,8 @@ int plans_self_test(ocn_poisson *s, const PlanCheck &c)
         if (c.direct_out) {
             OCN_CHECK_HIP(hipMalloc((void **)&tmp, np * sizeof(double)));
             OCN_CHECK_HIP(hipMemset(tmp, 0, np * sizeof(double)));
-            st = s->bwd.exec(s->spec, tmp + Lp.o, nullptr);
-        } else {
-            st = s->bwd.exec(s->spec, s->rhs, nullptr);
         }
+        const int st = c.direct_out ? s->bwd.exec(s->spec, tmp + Lp.o, nullptr) : s->bwd.exec(s->spec, s->rhs, nullptr);
         if (st != OCN_SUCCESS) {
             if (tmp) (void)hipFree(tmp);
             return st;
@@ -214,8 +208,7 @@ int plans_self_test(ocn_poisson *s, const PlanCheck &c)
             const std::vector<Wave> W = test_waves(Nx, Ny, Nz, three_d);
             fill_waves(in, W, Nx, Ny, Nz, three_d);
             OCN_CHECK_HIP(hipMemcpy(s->rhs, in.data(), n * sizeof(double), hipMemcpyHostToDevice));
-            st = s->fwd.exec(s->rhs, s->spec, nullptr);
-            if (st != OCN_SUCCESS) return st;
+            OCN_TRY(s->fwd.exec(s->rhs, s->spec, nullptr));
             OCN_CHECK_HIP(hipDeviceSynchronize());
             std::vector<double> sp((size_t)c.nxh * Ny * Nz * 2);
             OCN_CHECK_HIP(hipMemcpy(sp.data(), s->spec, sp.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -249,8 +242,7 @@ int packed_plans_self_test(ocn_poisson *s)
     }
     OCN_CHECK_HIP(hipMemset(s->spec, 0, n * sizeof(double)));
     OCN_CHECK_HIP(hipMemcpy(s->spec, in.data(), m * sizeof(double), hipMemcpyHostToDevice));
-    int st = s->xr2c.exec(s->spec, s->spec2, nullptr);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(s->xr2c.exec(s->spec, s->spec2, nullptr));
     OCN_CHECK_HIP(hipDeviceSynchronize());
     OCN_CHECK_HIP(hipMemcpy(spec.data(), s->spec2, spec.size() * sizeof(double), hipMemcpyDeviceToHost));
     const double two_pi = 6.283185307179586476925286766559;
@@ -265,8 +257,7 @@ int packed_plans_self_test(ocn_poisson *s)
         err = std::max(err, std::max(std::fabs(re - spec[2 * k]), std::fabs(im - spec[2 * k + 1])));
         scale = std::max(scale, std::max(std::fabs(re), std::fabs(im)));
     }
-    st = s->xc2r.exec(s->spec2, s->spec, nullptr);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(s->xc2r.exec(s->spec2, s->spec, nullptr));
     OCN_CHECK_HIP(hipDeviceSynchronize());
     OCN_CHECK_HIP(hipMemcpy(back.data(), s->spec, m * sizeof(double), hipMemcpyDeviceToHost));
     double rt = 0.0;

@@ -1696,8 +1696,7 @@ struct TendencyPlan {
 static int plan_momentum_tendencies(const ocn_grid *grid, const int32_t *range, ocn::FuseArgs &fz, Range &r, TendencyPlan &pl)
 {
     pl = TendencyPlan{PLAN_NONE, 0, 0, false, false, {dim3(0, 0, 0), 0}};
-    int st = make_range(grid, range, r);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_range(grid, range, r));
     if (r.i1 < r.i0 || r.j1 < r.j0 || r.k1 < r.k0) return OCN_SUCCESS;
     const int wx = r.i1 - r.i0 + 1, wy = r.j1 - r.j0 + 1, wz = r.k1 - r.k0 + 1;
     static const int force_direct = (getenv("OCN_TENDENCY_KERNEL") && !strcmp(getenv("OCN_TENDENCY_KERNEL"), "direct"));
@@ -1786,8 +1785,7 @@ int launch_momentum_tendencies(const ocn_grid *grid, const double *u, const doub
     if (fuse) fz = *fuse;
     Range r;
     TendencyPlan pl;
-    int st = plan_momentum_tendencies(grid, range, fz, r, pl);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(plan_momentum_tendencies(grid, range, fz, r, pl));
     if (pl.kind == PLAN_NONE) return OCN_SUCCESS;
     GridDev g = ocn::to_dev(*grid);
     constexpr int P = OCN_PERIODIC, B = OCN_BOUNDED;
@@ -1830,8 +1828,7 @@ static int launch_tracer_tendency_t(const ocn_grid *grid, const double *u, const
                                     double *Gc, const int32_t *range, hipStream_t stream, const TF &tf)
 {
     Range r;
-    int st = make_range(grid, range, r);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_range(grid, range, r));
     if (r.i1 < r.i0 || r.j1 < r.j0 || r.k1 < r.k0) return OCN_SUCCESS;
     GridDev g = ocn::to_dev(*grid);
     const int wx = r.i1 - r.i0 + 1, wy = r.j1 - r.j0 + 1, wz = r.k1 - r.k0 + 1;
@@ -1879,8 +1876,7 @@ int launch_tracer_pair_tendency(const ocn_grid *grid, const double *u, const dou
 {
     *launched = 0;
     Range r;
-    int st = make_range(grid, range, r);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_range(grid, range, r));
     if (r.i1 < r.i0 || r.j1 < r.j0 || r.k1 < r.k0) { *launched = 1; return OCN_SUCCESS; }
     const int wx = r.i1 - r.i0 + 1, wy = r.j1 - r.j0 + 1, wz = r.k1 - r.k0 + 1;
     // Measured on MI355X (round 2): 192 VGPRs -> 2 waves / SIMD; config 5 11.7 ms / step against 11.3 with two single launches, config 4

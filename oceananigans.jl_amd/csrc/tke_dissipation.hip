@@ -314,15 +314,13 @@ __global__ __launch_bounds__(256) void top_fluxes(GridDev g, ocn_tke_dissipation
 // ---- argument checks: nothing here touches a device -----------------------------------------------------------------------------------
 static int validate_grid_and_closure(const ocn_grid *grid, const ocn_tke_dissipation *c, const char *who)
 {
-    int st = tke::validate_tke_grid(grid, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(tke::validate_tke_grid(grid, who));
     OCN_REQUIRE(c, "%s: null closure", who);
     // every member in front of the four maxima is a coefficient or a constant derived from coefficients (doubles only up to there)
     constexpr size_t n_coefficients = offsetof(ocn_tke_dissipation, maximum_tracer_diffusivity) / sizeof(double);
     static_assert(offsetof(ocn_tke_dissipation, C_eps_eps) == 0 && offsetof(ocn_tke_dissipation, maximum_tracer_diffusivity) % sizeof(double) == 0,
                   "ocn_tke_dissipation: coefficients first, doubles");
-    st = tke::validate_finite_coefficients(reinterpret_cast<const double *>(c), n_coefficients, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(tke::validate_finite_coefficients(reinterpret_cast<const double *>(c), n_coefficients, who));
     OCN_REQUIRE(!std::isnan(c->maximum_tracer_diffusivity) && !std::isnan(c->maximum_tke_diffusivity) &&
                     !std::isnan(c->maximum_dissipation_diffusivity) && !std::isnan(c->maximum_viscosity),
                 "%s: a maximum is a NaN", who);
@@ -357,12 +355,10 @@ int ocn_compute_tke_dissipation_top_fluxes(const ocn_grid *grid, const ocn_tke_d
                                            void *stream)
 {
     const char *who = "ocn_compute_tke_dissipation_top_fluxes";
-    int st = tked::validate_grid_and_closure(grid, closure, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(tked::validate_grid_and_closure(grid, closure, who));
     const ocn_bc *tops[2] = {top_u, top_v};
     const char *names[2] = {"u", "v"};
-    st = tke::validate_top_fluxes(tops, names, 2, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(tke::validate_top_fluxes(tops, names, 2, who));
     OCN_REQUIRE(znodes_c && u && v && e && Qe && Qeps, "%s: null pointer", who);
     OCN_REQUIRE(Qe != Qeps, "%s: Qe and Qeps must be two different planes", who);
     tked::PlaneArgs a{};
@@ -379,10 +375,8 @@ int ocn_compute_tke_dissipation_diffusivities(const ocn_grid *grid, const ocn_mo
                                               double *kappa_c, double *kappa_e, double *kappa_eps, void *stream)
 {
     const char *who = "ocn_compute_tke_dissipation_diffusivities";
-    int st = tked::validate_grid_and_closure(grid, closure, who);
-    if (st != OCN_SUCCESS) return st;
-    st = validate_buoyancy_terms(terms, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(tked::validate_grid_and_closure(grid, closure, who));
+    OCN_TRY(validate_buoyancy_terms(terms, who));
     OCN_REQUIRE(u && v && e && eps && kappa_u && kappa_c && kappa_e && kappa_eps, "%s: null pointer", who);
     OCN_REQUIRE(kappa_u != kappa_c && kappa_u != kappa_e && kappa_u != kappa_eps && kappa_c != kappa_e && kappa_c != kappa_eps &&
                     kappa_e != kappa_eps,
@@ -403,10 +397,8 @@ int ocn_tke_dissipation_substep(const ocn_grid *grid, const ocn_model_terms *ter
                                 int32_t solve, void *stream)
 {
     const char *who = "ocn_tke_dissipation_substep";
-    int st = tked::validate_grid_and_closure(grid, closure, who);
-    if (st != OCN_SUCCESS) return st;
-    st = validate_buoyancy_terms(terms, who);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(tked::validate_grid_and_closure(grid, closure, who));
+    OCN_TRY(validate_buoyancy_terms(terms, who));
     OCN_REQUIRE(u_next && v_next && u_prev && v_prev && e && eps && kappa_u && kappa_c && kappa_e && kappa_eps && Le && Leps && Gn_e && Gm_e &&
                     Gn_eps && Gm_eps,
                 "%s: null pointer", who);

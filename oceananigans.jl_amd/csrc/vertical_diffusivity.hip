@@ -256,8 +256,7 @@ int launch_vertical_diffusivity_fluxes(const ocn_grid *grid, const double *kappa
                                        int boundary_only, const int32_t *range, hipStream_t stream)
 {
     ivd::Range whole;
-    int st = make_ivd_range(grid, range, whole);
-    if (st != OCN_SUCCESS) return st;
+    OCN_TRY(make_ivd_range(grid, range, whole));
     const GridDev gd = to_dev(*grid);
     // boundary_only: the planes k = 1 and k = Nz that lie in the range (one plane when Nz == 1); else one launch over all of it
     const int planes[2] = {1, grid->Nz};

@@ -976,7 +976,63 @@ def _adopt_driver_tendencies(model, pointers):
     model._pending_tendencies = False
 
 
-class RK3Driver:
+class _LibraryDriver:
+    """What RK3Driver and ModelRK3Driver share: the refusal of what only the Python host evaluates, the handles of a slab-x rank, and the
+    calls of the entry points <_prefix>_time_step / _flush / _destroy.  A subclass adds its own refusals, creates the handle self._h and
+    lists the device pointers of the library's G^n (tendency_pointers)."""
+
+    _prefix = None  # "ocn_rk3_driver" / "ocn_model_driver"
+
+    def __init__(self, model):
+        name = type(self).__name__
+        require_regular_xy(model.grid, name)
+        if any(p is not None for p in getattr(model, "_forcing_programs", ())):
+            raise NotImplementedError(f"{name}: a model with a ContinuousForcing needs the Python host (time_step(model, dt)): the library's "
+                                      "time step does not evaluate forcing programs")
+        if getattr(model, "_boundary_functions", None):
+            raise NotImplementedError(f"{name}: a model with boundary conditions that have field_dependencies needs the Python host "
+                                      "(time_step(model, dt)): the library's time step does not evaluate them")
+        if getattr(model, "_implicit", False):
+            raise NotImplementedError(f"{name}: a model with a VerticallyImplicitTimeDiscretization closure needs the Python host "
+                                      "(time_step(model, dt)): the library's time step has no implicit step")
+        if getattr(model, "particles", None) is not None:
+            raise NotImplementedError(f"{name}: a model with particles needs the Python host (time_step(model, dt)): the library's time step "
+                                      "does not step LagrangianParticles")
+
+    def _distributed_handles(self, model):
+        """(RCCL communicator, distributed Poisson handle) of a model on a Distributed architecture; (None, None) on one GPU"""
+        arch = model.grid.architecture
+        if not hasattr(arch, "partition"):
+            return None, None
+        comm = getattr(arch.fabric, "_h", None)
+        impl = getattr(model.pressure_solver, "impl", None)
+        if comm is None or getattr(impl, "_h", None) is None:
+            raise NotImplementedError(f"{type(self).__name__} on a Distributed architecture needs the RCCL transport (make_distributed) and the "
+                                      "library's distributed Poisson handle")
+        return comm, impl._h
+
+    def time_step(self, dt):
+        _lib.call(self._prefix + "_time_step", self._h, float(dt), stream_ptr())
+        _advance_clock_one_rk3_step(self.model, dt)
+
+    def flush(self):
+        """every prognostic field back in the model's arrays, deferred tendencies completed -- in the driver's own G^n arrays, which are copied
+        into the model's time stepper so that the state is the one `time_step(model, dt)` + flush_tendencies leaves: a following
+        ocn.time_step(model, dt) or write_checkpoint sees the current G^n, not the values from before the driver took over."""
+        _lib.call(self._prefix + "_flush", self._h, stream_ptr())
+        _adopt_driver_tendencies(self.model, self.tendency_pointers())
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                getattr(_lib.lib(), self._prefix + "_destroy")(h)
+            except Exception:
+                pass
+            self._h = None
+
+
+class RK3Driver(_LibraryDriver):
     """The whole RK3 time_step! behind ONE entry point of the C ABI (ocn_rk3_driver_*, csrc/driver.hip): what a Julia host binds
     when it wants the fused stage boundaries without managing alternating array roles itself.  Wraps the velocity and pressure
     fields of a plain WENO model (no tracers, no extra terms) on one GPU or on ONE RANK of a slab-x run with the RCCL transport
@@ -985,20 +1041,10 @@ class RK3Driver:
     defer_correction (default: the library's, on for all-periodic grids): the third stage's pressure correction rides on the next
     step's first fused launch; between time_step() and flush() the model's velocity fields are then NOT the corrected ones."""
 
+    _prefix = "ocn_rk3_driver"
+
     def __init__(self, model, own_solver=False, defer_correction=None):
-        require_regular_xy(model.grid, "RK3Driver")
-        if any(p is not None for p in getattr(model, "_forcing_programs", ())):
-            raise NotImplementedError("RK3Driver: a model with a ContinuousForcing needs the Python host (time_step(model, dt)): the library's "
-                                      "time step does not evaluate forcing programs")
-        if getattr(model, "_boundary_functions", None):
-            raise NotImplementedError("RK3Driver: a model with boundary conditions that have field_dependencies needs the Python host "
-                                      "(time_step(model, dt)): the library's time step does not evaluate them")
-        if getattr(model, "_implicit", False):
-            raise NotImplementedError("RK3Driver: a model with a VerticallyImplicitTimeDiscretization closure needs the Python host "
-                                      "(time_step(model, dt)): the library's time step has no implicit step")
-        if getattr(model, "particles", None) is not None:
-            raise NotImplementedError("RK3Driver: a model with particles needs the Python host (time_step(model, dt)): the library's time step "
-                                      "does not step LagrangianParticles")
+        super().__init__(model)
         if model.tracers or model.general_terms:
             raise NotImplementedError("RK3Driver: WENO advection only (no tracers / extra terms)")
         if not isinstance(model.timestepper, RungeKutta3TimeStepper) or not isinstance(model.advection, WENO):
@@ -1006,48 +1052,23 @@ class RK3Driver:
         flush_tendencies(model)
         self.model = model
         self._h = C.c_void_p()
-        arch = model.grid.architecture
-        if hasattr(arch, "partition"):
-            comm = getattr(arch.fabric, "_h", None)
-            impl = getattr(model.pressure_solver, "impl", None)
-            if comm is None or getattr(impl, "_h", None) is None:
-                raise NotImplementedError("RK3Driver on a Distributed architecture needs the RCCL transport (make_distributed) and the library's "
-                                          "distributed Poisson handle")
+        comm, dsolver = self._distributed_handles(model)
+        if comm is not None:
             _lib.call("ocn_rk3_driver_create_distributed", C.byref(self._h), model.grid.cref, model.u.ptr, model.v.ptr, model.w.ptr,
-                      model.pNHS.ptr, impl._h, comm, stream_ptr())
+                      model.pNHS.ptr, dsolver, comm, stream_ptr())
         else:
             _lib.call("ocn_rk3_driver_create", C.byref(self._h), model.grid.cref, model.u.ptr, model.v.ptr, model.w.ptr, model.pNHS.ptr,
                       None if own_solver else model.pressure_solver._h, stream_ptr())  # borrows the model's solver handle by default
         if defer_correction is not None:
             _lib.call("ocn_rk3_driver_configure", self._h, int(bool(defer_correction)))
 
-    def time_step(self, dt):
-        _lib.call("ocn_rk3_driver_time_step", self._h, float(dt), stream_ptr())
-        _advance_clock_one_rk3_step(self.model, dt)
-
-    def flush(self):
-        """velocities back in the model's fields, deferred tendencies completed -- in the driver's own G^n arrays, which are copied into the
-        model's time stepper so that the state is the one `time_step(model, dt)` + flush_tendencies leaves: a following
-        ocn.time_step(model, dt) or write_checkpoint sees the current G^n, not the values from before the driver took over."""
-        _lib.call("ocn_rk3_driver_flush", self._h, stream_ptr())
-        _adopt_driver_tendencies(self.model, self.tendency_pointers())
-
     def tendency_pointers(self):
         ptrs = [C.c_void_p() for _ in range(6)]
         _lib.call("ocn_rk3_driver_fields", self._h, *[C.byref(p) for p in ptrs])
         return [p.value for p in ptrs[3:]]
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                _lib.lib().ocn_rk3_driver_destroy(h)
-            except Exception:
-                pass
-            self._h = None
 
-
-class ModelRK3Driver:
+class ModelRK3Driver(_LibraryDriver):
     """time_step!(model, Δt) of a model WITH tracers and the §8(f) terms (config 4's term set) behind ONE entry point of the C ABI
     (ocn_model_driver_*, csrc/model_driver.hip): halo fills, compute_auxiliaries!, the fused tendency / substep launches and the pressure
     projection are issued by the library in the order `time_step(model, dt)` issues them on the general fused path, so after flush() the
@@ -1056,34 +1077,17 @@ class ModelRK3Driver:
     synchronous, without the interior / buffer split of distributed.py); WENO or UpwindBiased advection, RungeKutta3; number- or
     array-valued boundary conditions (functions of time are refused)."""
 
+    _prefix = "ocn_model_driver"
+
     def __init__(self, model, own_solver=False):
-        require_regular_xy(model.grid, "ModelRK3Driver")
-        if any(p is not None for p in getattr(model, "_forcing_programs", ())):
-            raise NotImplementedError("ModelRK3Driver: a model with a ContinuousForcing needs the Python host (time_step(model, dt)): the library's "
-                                      "time step does not evaluate forcing programs")
-        if getattr(model, "_boundary_functions", None):
-            raise NotImplementedError("ModelRK3Driver: a model with boundary conditions that have field_dependencies needs the Python host "
-                                      "(time_step(model, dt)): the library's time step does not evaluate them")
-        if getattr(model, "_implicit", False):
-            raise NotImplementedError("ModelRK3Driver: a model with a VerticallyImplicitTimeDiscretization closure needs the Python host "
-                                      "(time_step(model, dt)): the library's time step has no implicit step")
-        if getattr(model, "particles", None) is not None:
-            raise NotImplementedError("ModelRK3Driver: a model with particles needs the Python host (time_step(model, dt)): the library's time "
-                                      "step does not step LagrangianParticles")
+        super().__init__(model)
         if not isinstance(model.timestepper, RungeKutta3TimeStepper):
             raise NotImplementedError("ModelRK3Driver: RungeKutta3")
         xy_periodic = model.grid.topology[0] in ("Periodic", "FullyConnected") and model.grid.topology[1] == "Periodic"
         if not (model.fuse_stage_boundaries and model._general_fused and (xy_periodic or not hasattr(model.grid.architecture, "partition"))):
             raise NotImplementedError("ModelRK3Driver: a model on the general fused path (tracers and / or extra terms, WENO / UpwindBiased "
                                       "advection; on a Distributed architecture Periodic x and y); plain WENO models take RK3Driver")
-        arch = model.grid.architecture
-        comm = impl = None
-        if hasattr(arch, "partition"):
-            comm = getattr(arch.fabric, "_h", None)
-            impl = getattr(model.pressure_solver, "impl", None)
-            if comm is None or getattr(impl, "_h", None) is None:
-                raise NotImplementedError("ModelRK3Driver on a Distributed architecture needs the RCCL transport (make_distributed) and the "
-                                          "library's distributed Poisson handle")
+        comm, dsolver = self._distributed_handles(model)
         nt = len(model.tracers)
         if nt > _lib.MODEL_MAX_TRACERS:
             raise NotImplementedError(f"ModelRK3Driver: at most {_lib.MODEL_MAX_TRACERS} tracers")
@@ -1139,11 +1143,11 @@ class ModelRK3Driver:
                 desc.bcs[n] = C.pointer(self._bcs[-1])
         self._h = C.c_void_p()
         if comm is not None:
-            finish = getattr(arch, "finish_halo_exchange", None)
+            finish = getattr(model.grid.architecture, "finish_halo_exchange", None)
             if finish is not None:
                 finish()
             _lib.call("ocn_model_driver_create_distributed", C.byref(self._h), model.grid.cref, C.byref(desc), model.u.ptr, model.v.ptr,
-                      model.w.ptr, model.pNHS.ptr, impl._h, comm, stream_ptr())
+                      model.w.ptr, model.pNHS.ptr, dsolver, comm, stream_ptr())
         else:
             _lib.call("ocn_model_driver_create", C.byref(self._h), model.grid.cref, C.byref(desc), model.u.ptr, model.v.ptr, model.w.ptr,
                       model.pNHS.ptr, None if own_solver else model.pressure_solver._h, stream_ptr())
@@ -1157,26 +1161,10 @@ class ModelRK3Driver:
         if any(f is not None for f in model._forcing):  # steady terms: the device vectors / arrays stay the model's
             _lib.call("ocn_model_driver_set_forcing", self._h, _lib.forcing_array(model._forcing_refs), 0)
 
-    def time_step(self, dt):
-        _lib.call("ocn_model_driver_time_step", self._h, float(dt), stream_ptr())
-        _advance_clock_one_rk3_step(self.model, dt)
-
-    def flush(self):
-        """every prognostic field back in the model's arrays, deferred tendencies completed and copied into the model's time stepper
-        (see RK3Driver.flush)"""
-        _lib.call("ocn_model_driver_flush", self._h, stream_ptr())
-        _adopt_driver_tendencies(self.model, [self.tendency_pointer(n) for n in range(len(self.model.prognostic_fields()))])
+    def tendency_pointers(self):
+        return [self.tendency_pointer(n) for n in range(len(self.model.prognostic_fields()))]
 
     def tendency_pointer(self, n):
         f, G = C.c_void_p(), C.c_void_p()
         _lib.call("ocn_model_driver_field", self._h, int(n), C.byref(f), C.byref(G))
         return G.value
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                _lib.lib().ocn_model_driver_destroy(h)
-            except Exception:
-                pass
-            self._h = None
