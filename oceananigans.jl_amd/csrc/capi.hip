@@ -521,7 +521,7 @@ int ocn_add_momentum_terms(const ocn_grid *grid, const ocn_model_terms *terms, c
     return OCN_LAUNCH(grid, launch_momentum_extra, grid, t, u, v, w, Gu, Gv, Gw, range, as_stream(stream));
 }
 
-// the grids of hydrostatic_walls.hip: walls in y (a channel) or in x and y (a closed basin), regular and not partitioned
+// the wall grids of hydrostatic_surface.hip: walls in y (a channel) or in x and y (a closed basin), regular and not partitioned
 static bool hydrostatic_walls(const ocn_grid *grid)
 {
     return (grid->tx == OCN_PERIODIC || grid->tx == OCN_BOUNDED) && grid->ty == OCN_BOUNDED && grid->tz == OCN_BOUNDED;
@@ -552,8 +552,7 @@ int ocn_compute_vector_invariant_momentum_tendencies(const ocn_grid *grid, const
     OCN_TRY(validate_hydrostatic(grid, "ocn_compute_vector_invariant_momentum_tendencies", true));
     OCN_REQUIRE(u && v && w && Gu && Gv, "ocn_compute_vector_invariant_momentum_tendencies: null field pointer");
     OCN_REQUIRE(grid->Hz >= 1, "ocn_compute_vector_invariant_momentum_tendencies: needs a z halo");
-    if (hydrostatic_walls(grid)) return launch_vector_invariant_walls(grid, u, v, w, Gu, Gv, eta, gravitational_acceleration, as_stream(stream));
-    return launch_vector_invariant(grid, u, v, w, Gu, Gv, as_stream(stream), eta, gravitational_acceleration);
+    return launch_vector_invariant(grid, u, v, w, Gu, Gv, eta, gravitational_acceleration, as_stream(stream));
 }
 int ocn_compute_vector_invariant_weno_momentum_tendencies(const ocn_grid *grid, int32_t scheme_flags, const double *u, const double *v,
                                                           const double *w, double *Gu, double *Gv, const double *eta,
@@ -577,7 +576,6 @@ int ocn_split_explicit_forcing(const ocn_grid *grid, const double *Gu, const dou
 {
     OCN_TRY(validate_hydrostatic(grid, "ocn_split_explicit_forcing", true));
     OCN_REQUIRE(Gu && Gu_previous && Gv && Gv_previous && GU && GV, "ocn_split_explicit_forcing: null pointer");
-    if (hydrostatic_walls(grid)) return launch_split_explicit_forcing_walls(grid, Gu, Gu_previous, Gv, Gv_previous, chi, GU, GV, as_stream(stream));
     return launch_split_explicit_forcing(grid, Gu, Gu_previous, Gv, Gv_previous, chi, GU, GV, as_stream(stream));
 }
 int ocn_split_explicit_substeps(const ocn_grid *grid, int32_t n, const double *weights, double dtau, double gravitational_acceleration,
@@ -588,9 +586,6 @@ int ocn_split_explicit_substeps(const ocn_grid *grid, int32_t n, const double *w
     OCN_REQUIRE(grid->tx != OCN_FULLY_CONNECTED, "ocn_split_explicit_substeps wraps x periodically: not for a partitioned (FullyConnected) x");
     OCN_REQUIRE(n >= 1 && weights, "ocn_split_explicit_substeps: needs n >= 1 averaging weights (host array)");
     OCN_REQUIRE(eta && U && V && eta_filtered && U_filtered && V_filtered && GU && GV, "ocn_split_explicit_substeps: null pointer");
-    if (hydrostatic_walls(grid))
-        return launch_split_explicit_substeps_walls(grid, n, weights, dtau, gravitational_acceleration, column_depth, eta, U, V, eta_filtered,
-                                                    U_filtered, V_filtered, GU, GV, as_stream(stream));
     return launch_split_explicit_substeps(grid, n, weights, dtau, gravitational_acceleration, column_depth, eta, U, V, eta_filtered, U_filtered,
                                           V_filtered, GU, GV, as_stream(stream));
 }
@@ -598,7 +593,6 @@ int ocn_compute_barotropic_mode(const ocn_grid *grid, const double *u, const dou
 {
     OCN_TRY(validate_hydrostatic(grid, "ocn_compute_barotropic_mode", true));
     OCN_REQUIRE(u && v && U && V, "ocn_compute_barotropic_mode: null pointer");
-    if (hydrostatic_walls(grid)) return launch_barotropic_mode_walls(grid, u, v, U, V, as_stream(stream));
     return launch_barotropic_mode(grid, u, v, U, V, as_stream(stream));
 }
 int ocn_barotropic_split_explicit_corrector(const ocn_grid *grid, double *u, double *v, const double *U, const double *V, double *U_filtered,
@@ -606,22 +600,18 @@ int ocn_barotropic_split_explicit_corrector(const ocn_grid *grid, double *u, dou
 {
     OCN_TRY(validate_hydrostatic(grid, "ocn_barotropic_split_explicit_corrector", true));
     OCN_REQUIRE(u && v && U && V && U_filtered && V_filtered, "ocn_barotropic_split_explicit_corrector: null pointer");
-    if (hydrostatic_walls(grid))
-        return launch_barotropic_corrector_walls(grid, u, v, U, V, U_filtered, V_filtered, column_depth, as_stream(stream));
     return launch_barotropic_corrector(grid, u, v, U, V, U_filtered, V_filtered, column_depth, as_stream(stream));
 }
 int ocn_fill_free_surface_halos(const ocn_grid *grid, double *eta, void *stream)
 {
     OCN_TRY(validate_hydrostatic(grid, "ocn_fill_free_surface_halos", true));
     OCN_REQUIRE(eta, "ocn_fill_free_surface_halos: null pointer");
-    if (hydrostatic_walls(grid)) return launch_plane_halo_walls(grid, eta, as_stream(stream));
     return launch_plane_halo(grid, eta, as_stream(stream));
 }
 int ocn_compute_w_from_continuity(const ocn_grid *grid, const double *u, const double *v, double *w, void *stream)
 {
     OCN_TRY(validate_hydrostatic(grid, "ocn_compute_w_from_continuity", true));
     OCN_REQUIRE(u && v && w, "ocn_compute_w_from_continuity: null field pointer");
-    if (hydrostatic_walls(grid)) return launch_w_from_continuity_walls(grid, u, v, w, as_stream(stream));
     return launch_w_from_continuity(grid, u, v, w, as_stream(stream));
 }
 int ocn_add_barotropic_pressure_gradient(const ocn_grid *grid, double gravitational_acceleration, const double *eta, double *Gu, double *Gv,
@@ -629,7 +619,6 @@ int ocn_add_barotropic_pressure_gradient(const ocn_grid *grid, double gravitatio
 {
     OCN_TRY(validate_hydrostatic(grid, "ocn_add_barotropic_pressure_gradient", true));
     OCN_REQUIRE(eta && Gu && Gv, "ocn_add_barotropic_pressure_gradient: null pointer");
-    if (hydrostatic_walls(grid)) return launch_barotropic_gradient_walls(grid, gravitational_acceleration, eta, Gu, Gv, as_stream(stream));
     return launch_barotropic_gradient(grid, gravitational_acceleration, eta, Gu, Gv, as_stream(stream));
 }
 int ocn_explicit_free_surface_ab2_step(const ocn_grid *grid, const double *w, double *eta, double *G_eta, const double *G_eta_previous,
@@ -1177,8 +1166,6 @@ int ocn_implicit_free_surface_rhs(const ocn_grid *grid, const double *u, const d
     OCN_REQUIRE(grid->tx != OCN_FULLY_CONNECTED, "ocn_implicit_free_surface_rhs wraps x periodically: not for a partitioned (FullyConnected) x");
     OCN_REQUIRE(u && v && eta && Qu && Qv && rhs, "ocn_implicit_free_surface_rhs: null pointer");
     OCN_REQUIRE(dt > 0, "ocn_implicit_free_surface_rhs: dt must be positive");
-    if (hydrostatic_walls(grid))
-        return launch_implicit_free_surface_rhs_walls(grid, u, v, eta, gravitational_acceleration, dt, Qu, Qv, rhs, as_stream(stream));
     return launch_implicit_free_surface_rhs(grid, u, v, eta, gravitational_acceleration, dt, Qu, Qv, rhs, as_stream(stream));
 }
 int ocn_barotropic_pressure_correction(const ocn_grid *grid, double *u, double *v, const double *eta, double gravitational_acceleration,
@@ -1186,8 +1173,6 @@ int ocn_barotropic_pressure_correction(const ocn_grid *grid, double *u, double *
 {
     OCN_TRY(validate_hydrostatic(grid, "ocn_barotropic_pressure_correction", true));
     OCN_REQUIRE(u && v && eta, "ocn_barotropic_pressure_correction: null pointer");
-    if (hydrostatic_walls(grid))
-        return launch_barotropic_pressure_correction_walls(grid, u, v, eta, gravitational_acceleration, dt, as_stream(stream));
     return launch_barotropic_pressure_correction(grid, u, v, eta, gravitational_acceleration, dt, as_stream(stream));
 }
 

@@ -1,5 +1,5 @@
 // immersed.hip -- HydrostaticFreeSurfaceModel on ImmersedBoundaryGrid(grid, GridFittedBottom(h)): (Periodic, Periodic, Bounded) underlying
-// grid, regular x and y, one GPU.  The kernels are the periodic hydrostatic kernels of kernels.hip / physics.hip with the
+// grid, regular x and y, one GPU.  The kernels are the periodic hydrostatic kernels of hydrostatic_surface.hip / physics.hip with the
 // reference's immersed rules applied, in the same evaluation order, so that over a flat bottom they return the same bits:
 //
 //   * conditional differences   ImmersedBoundaries/conditional_differences.jl:25-77: a difference is 0 when one of its two nodes is an
@@ -38,13 +38,6 @@ __device__ __forceinline__ bool inactive_f_top(int kb, int Nz) { return ic(kb, N
 
 __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
 __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
-__device__ __forceinline__ double dz_c(const GridDev &g, int k) { return g.dzc ? uniform_load(g.dzc, k + g.Hz - 1) : g.dz; }
-__device__ __forceinline__ double dz_f(const GridDev &g, int k) { return g.dzf ? uniform_load(g.dzf, k + g.Hz - 1) : g.dz; }
-__device__ __forceinline__ long long plane_at(const GridDev &g, int i, int j)  // 1-based interior (i, j) of a plane shaped like η
-{
-    return (i - 1 + g.Hx) + (long long)(g.Nx + 2 * g.Hx) * (j - 1 + g.Hy);
-}
-inline dim3 xy_blocks(int nx, int ny, int nz = 1) { return dim3((nx + 63) / 64, (ny + 3) / 4, nz); }
 inline int z_chunks(int Nz) { return (Nz + KZ - 1) / KZ; }
 
 // kbot of the 3 x 3 columns around (i, j): kb[1 + a][1 + b] is column (i + a, j + b)
@@ -134,7 +127,7 @@ __global__ __launch_bounds__(256) void mask_kernel(GridDev g, const int32_t *__r
     }
 }
 
-// ---- vector_invariant_kernel of kernels.hip with the conditional differences: the two differences of ζ₃ᶠᶠᶜ, ∂z u / ∂z v of the vertical
+// ---- vector_invariant_kernel of hydrostatic_surface.hip with the conditional differences: the two differences of ζ₃ᶠᶠᶜ, ∂z u / ∂z v of the vertical
 // advection, ∂x / ∂y of Kh.  g ∂x η is taken at k = Nz + 1, where the centre node is inactive on the underlying grid as well: never zeroed.
 __global__ __launch_bounds__(256) void vector_invariant_immersed_kernel(GridDev g, const int32_t *__restrict__ kbot, const double *__restrict__ u,
                                                                         const double *__restrict__ v, const double *__restrict__ w,
@@ -162,7 +155,7 @@ __global__ __launch_bounds__(256) void vector_invariant_immersed_kernel(GridDev 
     }
     for (int k = k0; k <= k1; ++k) {
         const long long o = at(L, i, j, k);
-        const double dzf0 = dz_f(g, k), dzf1 = dz_f(g, k + 1);
+        const double dzf0 = dz_face(g, k), dzf1 = dz_face(g, k + 1);
         const double *pu = u + o, *pv = v + o, *pw = w + o;
 #define U_(a, b, c) pu[(a) + (b)*s2 + (c)*s3]
 #define V_(a, b, c) pv[(a) + (b)*s2 + (c)*s3]
@@ -235,7 +228,7 @@ __global__ __launch_bounds__(256) void viscosity_immersed_kernel(GridDev g, cons
     const double dx = g.dx, dy = g.dy, Az = dx * dy;
     for (int k = k0; k <= k1; ++k) {
         const long long o = at(L, i, j, k);
-        const double dzc = dz_c(g, k), dzf = dz_f(g, k), dzf1 = dz_f(g, k + 1);
+        const double dzc = dz_centre(g, k), dzf = dz_face(g, k), dzf1 = dz_face(g, k + 1);
         const double Axc = dy * dzc, Ayc = dx * dzc;
         const double *pu = u + o, *pv = v + o, *pw = w + o;
 #define DX(a, b) (((a) - (b)) / dx)
@@ -292,7 +285,7 @@ __global__ __launch_bounds__(256) void tracer_immersed_kernel(GridDev g, const i
     const double dx = g.dx, dy = g.dy, Az = dx * dy;
     for (int k = k0; k <= k1; ++k) {
         const long long o = at(L, i, j, k);
-        const double dzc = dz_c(g, k), dzf = dz_f(g, k), dzf1 = dz_f(g, k + 1);
+        const double dzc = dz_centre(g, k), dzf = dz_face(g, k), dzf1 = dz_face(g, k + 1);
         const double Ax = dy * dzc, Ay = dx * dzc;
         const double *pu = u + o, *pv = v + o, *pw = w + o, *pc = cc + o;
 #define C_(a, b, q) pc[(a) + (b)*s2 + (q)*s3]
@@ -339,7 +332,7 @@ __global__ __launch_bounds__(256) void forcing_immersed_kernel(GridDev g, const 
     long long o = at(L, i, j, 1);
     double aU = 0.0, aV = 0.0;
     for (int k = 1; k <= Nz; ++k) {
-        const double dz = dz_c(g, k);
+        const double dz = dz_centre(g, k);
         const double tu = dz * (ic(mxu, k, Nz) ? 0.0 : C1 * Gun[o] - C2 * Gum[o] * ne);
         const double tv = dz * (ic(mxv, k, Nz) ? 0.0 : C1 * Gvn[o] - C2 * Gvm[o] * ne);
         aU = k == 1 ? tu : aU + tu;

@@ -412,274 +412,9 @@ int launch_hydrostatic_pressure(const ocn_grid *grid, const TermsDev &t, double 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// HydrostaticFreeSurfaceModel, first slice: explicit free surface on a static (Periodic, Periodic, Bounded) grid
+// HydrostaticFreeSurfaceModel: the variants of the free-surface kernels that exist for a (Periodic, Periodic, Bounded) static grid only
+// (SURVEY 8(f) rank 4).  The kernels of every topology are in hydrostatic_surface.hip.  All 2-D quantities are (sx, sy) planes like η.
 // ---------------------------------------------------------------------------------------------------
-// _compute_w_from_continuity! (src/Models/HydrostaticFreeSurfaceModels/compute_w_from_continuity.jl:31-40): w[i,j,1] = 0,
-// w[i,j,k] = w[i,j,k-1] - (flux_div_xyᶜᶜᶜ(i,j,k-1,u,v) / Azᶜᶜᶜ + 0) for every column whose east / north neighbours exist in the
-// parent (a superset of w_kernel_parameters, :43-51).  One thread per column, i across the lanes.
-__global__ __launch_bounds__(256) void w_from_continuity_kernel(GridDev g, const double *__restrict__ u, const double *__restrict__ v,
-                                                                double *__restrict__ w)
-{
-    const int i = 1 - g.Hx + blockIdx.x * blockDim.x + threadIdx.x, j = 1 - g.Hy + blockIdx.y * blockDim.y + threadIdx.y;
-    if (i > g.Nx + g.Hx - 1 || j > g.Ny + g.Hy - 1) return;
-    const Lay L = make_lay(g, OCN_LOC_CCC);  // x, y Periodic: u, v, w share strides and offset (w only has one more plane)
-    long long o = at(L, i, j, 1);
-    const double Az = g.dx * g.dy;
-    double wk = 0.0;
-    w[o] = wk;
-    for (int k = 1; k <= g.Nz; ++k) {
-        const double dzc = g.dzc ? uniform_load(g.dzc, k + g.Hz - 1) : g.dz;
-        const double Ax = g.dy * dzc, Ay = g.dx * dzc;
-        const double dxu = Ax * u[o + 1] - Ax * u[o];
-        const double dyv = Ay * v[o + L.s2] - Ay * v[o];
-        const double dh = (dxu + dyv) / Az;
-        wk = wk - (dh + 0.0);
-        o += L.s3;
-        w[o] = wk;
-    }
-}
-int launch_w_from_continuity(const ocn_grid *grid, const double *u, const double *v, double *w, hipStream_t stream)
-{
-    GridDev g = to_dev(*grid);
-    const int nx = g.Nx + 2 * g.Hx - 1, ny = g.Ny + 2 * g.Hy - 1;
-    dim3 block(64, 4, 1), nb((nx + 63) / 64, (ny + 3) / 4, 1);
-    hipLaunchKernelGGL(w_from_continuity_kernel, nb, block, 0, stream, g, u, v, w);
-    OCN_CHECK_HIP(hipGetLastError());
-    return OCN_SUCCESS;
-}
-
-// Gu = -U_dot_∇u, Gv = -U_dot_∇v of the reference's default VectorInvariant() scheme (Advection/vector_invariant_advection.jl:
-// 269-275): EnstrophyConserving vorticity flux (:360-361, ζ₃ᶠᶠᶜ of Operators/vorticity_operators.jl:4-11), EnergyConserving
-// vertical advection (:315-319) and kinetic-energy gradient (:304-308).  ℑ = 0.5 (a + b), δ = a - b, ∂ = δ / Δ; one thread per cell.
-// eta != NULL: the barotropic pressure gradient - g ∇η (barotropic_gradient_kernel below) is subtracted in the same pass.
-__global__ __launch_bounds__(256) void vector_invariant_kernel(GridDev g, const double *__restrict__ u, const double *__restrict__ v,
-                                                               const double *__restrict__ w, double *__restrict__ Gu,
-                                                               double *__restrict__ Gv, const double *__restrict__ eta, double grav)
-{
-    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y, k = 1 + blockIdx.z;
-    if (i > g.Nx || j > g.Ny) return;
-    const Lay L = make_lay(g, OCN_LOC_CCC);
-    const long long o = at(L, i, j, k), s2 = L.s2, s3 = L.s3;
-    const double dx = g.dx, dy = g.dy, Az = dx * dy;
-    const double dzf0 = g.dzf ? uniform_load(g.dzf, k + g.Hz - 1) : g.dz, dzf1 = g.dzf ? uniform_load(g.dzf, k + g.Hz) : g.dz;  // Δzᶠ at faces k, k+1
-    const double *pu = u + o, *pv = v + o, *pw = w + o;
-#define U_(a, b, c) pu[(a) + (b)*s2 + (c)*s3]
-#define V_(a, b, c) pv[(a) + (b)*s2 + (c)*s3]
-#define W_(a, b, c) pw[(a) + (b)*s2 + (c)*s3]
-    auto zeta = [&](int a, int b) {  // ζ₃ᶠᶠᶜ at (i + a, j + b)
-        const double gam = (dy * V_(a, b, 0) - dy * V_(a - 1, b, 0)) - (dx * U_(a, b, 0) - dx * U_(a, b - 1, 0));
-        return gam / Az;
-    };
-    auto Kh = [&](int a, int b) {    // Khᶜᶜᶜ at (i + a, j + b)
-        return (0.5 * (U_(a, b, 0) * U_(a, b, 0) + U_(a + 1, b, 0) * U_(a + 1, b, 0)) +
-                0.5 * (V_(a, b, 0) * V_(a, b, 0) + V_(a, b + 1, 0) * V_(a, b + 1, 0))) / 2;
-    };
-    {   // ---- u
-        auto m = [&](int a) { return 0.5 * (dx * V_(a, 0, 0) + dx * V_(a, 1, 0)); };  // ℑyᵃᶜᵃ(Δx_qᶜᶠᶜ v) at (i + a, j)
-        const double hadv = -(0.5 * (zeta(0, 0) + zeta(0, 1))) * (0.5 * (m(-1) + m(0))) / dx;
-        auto Z = [&](int c, double dzf) { return (0.5 * (Az * W_(-1, 0, c) + Az * W_(0, 0, c))) * ((U_(0, 0, c) - U_(0, 0, c - 1)) / dzf); };
-        const double vadv = (0.5 * (Z(0, dzf0) + Z(1, dzf1))) / Az;
-        const double bern = (Kh(0, 0) - Kh(-1, 0)) / dx;
-        double G = -((hadv + vadv) + bern);
-        if (eta) {
-            const long long e = (i - 1 + g.Hx) + (long long)L.sx * (j - 1 + g.Hy);
-            G -= grav * ((eta[e] - eta[e - 1]) / g.dx);
-        }
-        Gu[o] = G;
-    }
-    {   // ---- v
-        auto n = [&](int b) { return 0.5 * (dy * U_(0, b, 0) + dy * U_(1, b, 0)); };  // ℑxᶜᵃᵃ(Δy_qᶠᶜᶜ u) at (i, j + b)
-        const double hadv = (0.5 * (zeta(0, 0) + zeta(1, 0))) * (0.5 * (n(-1) + n(0))) / dy;
-        auto Z = [&](int c, double dzf) { return (0.5 * (Az * W_(0, -1, c) + Az * W_(0, 0, c))) * ((V_(0, 0, c) - V_(0, 0, c - 1)) / dzf); };
-        const double vadv = (0.5 * (Z(0, dzf0) + Z(1, dzf1))) / Az;
-        const double bern = (Kh(0, 0) - Kh(0, -1)) / dy;
-        double G = -((hadv + vadv) + bern);
-        if (eta) {
-            const long long e = (i - 1 + g.Hx) + (long long)L.sx * (j - 1 + g.Hy);
-            G -= grav * ((eta[e] - eta[e - L.sx]) / g.dy);
-        }
-        Gv[o] = G;
-    }
-#undef U_
-#undef V_
-#undef W_
-}
-int launch_vector_invariant(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu, double *Gv,
-                            hipStream_t stream, const double *eta, double grav)
-{
-    GridDev g = to_dev(*grid);
-    dim3 block(64, 4, 1), nb((g.Nx + 63) / 64, (g.Ny + 3) / 4, g.Nz);
-    hipLaunchKernelGGL(vector_invariant_kernel, nb, block, 0, stream, g, u, v, w, Gu, Gv, eta, grav);
-    OCN_CHECK_HIP(hipGetLastError());
-    return OCN_SUCCESS;
-}
-
-// - explicit_barotropic_pressure_x/y_gradient (explicit_free_surface.jl:36-40): Gu -= g ∂xᶠᶜᶜ η, Gv -= g ∂yᶜᶠᶜ η at every k; η is the
-// (sx, sy) plane k = Nz+1 of the reference's reduced field, halos filled.
-__global__ __launch_bounds__(256) void barotropic_gradient_kernel(GridDev g, double grav, const double *__restrict__ eta,
-                                                                  double *__restrict__ Gu, double *__restrict__ Gv)
-{
-    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y, k = 1 + blockIdx.z;
-    if (i > g.Nx || j > g.Ny) return;
-    const Lay L = make_lay(g, OCN_LOC_CCC);
-    const long long e = (i - 1 + g.Hx) + (long long)L.sx * (j - 1 + g.Hy);
-    const long long o = at(L, i, j, k);
-    Gu[o] -= grav * ((eta[e] - eta[e - 1]) / g.dx);
-    Gv[o] -= grav * ((eta[e] - eta[e - L.sx]) / g.dy);
-}
-int launch_barotropic_gradient(const ocn_grid *grid, double grav, const double *eta, double *Gu, double *Gv, hipStream_t stream)
-{
-    GridDev g = to_dev(*grid);
-    dim3 block(64, 4, 1), nb((g.Nx + 63) / 64, (g.Ny + 3) / 4, g.Nz);
-    hipLaunchKernelGGL(barotropic_gradient_kernel, nb, block, 0, stream, g, grav, eta, Gu, Gv);
-    OCN_CHECK_HIP(hipGetLastError());
-    return OCN_SUCCESS;
-}
-
-// periodic x, y halos of the free-surface plane (the fill_halo_regions! of η in update_state!): every halo cell copies from the
-// interior cell it wraps to, corners included
-__global__ void plane_halo_kernel(int Nx, int Ny, int Hx, int Hy, double *__restrict__ e)
-{
-    const int sx = Nx + 2 * Hx, sy = Ny + 2 * Hy;
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long long)sx * sy) return;
-    const int I = (int)(t % sx), J = (int)(t / sx);
-    if (I >= Hx && I < Hx + Nx && J >= Hy && J < Hy + Ny) return;
-    const int si = Hx + ((I - Hx) % Nx + Nx) % Nx, sj = Hy + ((J - Hy) % Ny + Ny) % Ny;
-    e[t] = e[si + (long long)sx * sj];
-}
-int launch_plane_halo(const ocn_grid *grid, double *plane, hipStream_t stream)
-{
-    const long long n = (long long)(grid->Nx + 2 * grid->Hx) * (grid->Ny + 2 * grid->Hy);
-    hipLaunchKernelGGL(plane_halo_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, grid->Nx, grid->Ny, grid->Hx, grid->Hy, plane);
-    OCN_CHECK_HIP(hipGetLastError());
-    return OCN_SUCCESS;
-}
-
-// ---- SplitExplicitFreeSurface (SplitExplicitFreeSurfaces/*.jl), ForwardBackwardScheme, (Periodic, Periodic) static grid of column
-// depth H.  All 2-D quantities are (sx, sy) planes like η; only their interiors are used (indices wrap as in δxTᶜᵃᵃ / ∂xTᶠᶜᶠ).
-__device__ __forceinline__ long long plane_at(const GridDev &g, int i, int j)  // 1-based interior (i, j)
-{
-    return (i - 1 + g.Hx) + (long long)(g.Nx + 2 * g.Hx) * (j - 1 + g.Hy);
-}
-// compute_split_explicit_forcing! (compute_slow_tendencies.jl:12-32): Gᵁ = Σₖ Δz ((3/2 + χ) Guⁿ - (1/2 + χ) Gu⁻ not_euler)
-__global__ __launch_bounds__(256) void barotropic_forcing_kernel(GridDev g, const double *__restrict__ Gun, const double *__restrict__ Gum,
-                                                                 const double *__restrict__ Gvn, const double *__restrict__ Gvm, double chi,
-                                                                 double *__restrict__ GU, double *__restrict__ GV)
-{
-    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
-    if (i > g.Nx || j > g.Ny) return;
-    const Lay L = make_lay(g, OCN_LOC_CCC);
-    const double C1 = 3 * 1.0 / 2 + chi, C2 = 1.0 / 2 + chi, ne = (C2 != 0) ? 1.0 : 0.0;
-    long long o = at(L, i, j, 1);
-    double dz = g.dzc ? uniform_load(g.dzc, g.Hz) : g.dz;
-    double aU = dz * (C1 * Gun[o] - C2 * Gum[o] * ne), aV = dz * (C1 * Gvn[o] - C2 * Gvm[o] * ne);
-    for (int k = 2; k <= g.Nz; ++k) {
-        o += L.s3;
-        dz = g.dzc ? uniform_load(g.dzc, k + g.Hz - 1) : g.dz;
-        aU = aU + dz * (C1 * Gun[o] - C2 * Gum[o] * ne);
-        aV = aV + dz * (C1 * Gvn[o] - C2 * Gvm[o] * ne);
-    }
-    GU[plane_at(g, i, j)] = aU;
-    GV[plane_at(g, i, j)] = aV;
-}
-// _split_explicit_free_surface! (step_split_explicit_free_surface.jl:3-11): η -= Δτ (δx(Δy U) + δy(Δx V)) / Az
-__global__ __launch_bounds__(256) void split_explicit_eta_kernel(GridDev g, double dtau, double *__restrict__ eta, const double *__restrict__ U,
-                                                                 const double *__restrict__ V)
-{
-    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
-    if (i > g.Nx || j > g.Ny) return;
-    const int ip = i == g.Nx ? 1 : i + 1, jp = j == g.Ny ? 1 : j + 1;
-    const double dx = g.dx, dy = g.dy, Az = dx * dy;
-    const long long e = plane_at(g, i, j);
-    eta[e] = eta[e] - dtau * ((dy * U[plane_at(g, ip, j)] - dy * U[e]) + (dx * V[plane_at(g, i, jp)] - dx * V[e])) / Az;
-}
-// _split_explicit_barotropic_velocity! (:13-46): U += Δτ (-g H ∂x η + Gᵁ), V likewise; the filtered state accumulates weight x (η, U, V)
-__global__ __launch_bounds__(256) void split_explicit_velocity_kernel(GridDev g, double w, double dtau, double grav, double H,
-                                                                      const double *__restrict__ eta, double *__restrict__ U,
-                                                                      double *__restrict__ V, double *__restrict__ etab,
-                                                                      double *__restrict__ Ub, double *__restrict__ Vb,
-                                                                      const double *__restrict__ GU, const double *__restrict__ GV)
-{
-    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
-    if (i > g.Nx || j > g.Ny) return;
-    const int im = i == 1 ? g.Nx : i - 1, jm = j == 1 ? g.Ny : j - 1;
-    const long long e = plane_at(g, i, j);
-    const double et = eta[e];
-    const double Un = U[e] + dtau * (-grav * H * ((et - eta[plane_at(g, im, j)]) / g.dx) + GU[e]);
-    const double Vn = V[e] + dtau * (-grav * H * ((et - eta[plane_at(g, i, jm)]) / g.dy) + GV[e]);
-    etab[e] += w * et;
-    Ub[e] += w * Un;
-    Vb[e] += w * Vn;
-    U[e] = Un;
-    V[e] = Vn;
-}
-// ---- ImplicitFreeSurface with the FFT solver (implicit_free_surface.jl:112-145, fft_based_implicit_free_surface_solver.jl:76-115,
-// barotropic_pressure_correction.jl:21-47) on a (Periodic, Periodic, Bounded) static grid of constant depth Lz.
-// compute_vertically_integrated_volume_flux! (compute_vertically_integrated_variables.jl:34-41): Qu = Σₖ Axᶠᶜᶜ u, Qv = Σₖ Ayᶜᶠᶜ v
-// (sum! accumulates k ascending from zero)
-__global__ __launch_bounds__(256) void volume_flux_kernel(GridDev g, const double *__restrict__ u, const double *__restrict__ v,
-                                                          double *__restrict__ Qu, double *__restrict__ Qv)
-{
-    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
-    if (i > g.Nx || j > g.Ny) return;
-    const Lay L = make_lay(g, OCN_LOC_CCC);
-    long long o = at(L, i, j, 1);
-    double aU = 0.0, aV = 0.0;
-#pragma unroll 8
-    for (int k = 1; k <= g.Nz; ++k) {
-        const double dz = g.dzc ? uniform_load(g.dzc, k + g.Hz - 1) : g.dz;
-        aU = aU + (g.dy * dz) * u[o];
-        aV = aV + (g.dx * dz) * v[o];
-        o += L.s3;
-    }
-    Qu[plane_at(g, i, j)] = aU;
-    Qv[plane_at(g, i, j)] = aV;
-}
-// fft_implicit_free_surface_right_hand_side!: rhs = (δx Qu + δy Qv - Az η / Δt) / (g Lz Δt Az) into a halo-free (Nx, Ny) array
-__global__ __launch_bounds__(256) void implicit_rhs_kernel(GridDev g, double grav, double Lz, double dt, const double *__restrict__ Qu,
-                                                           const double *__restrict__ Qv, const double *__restrict__ eta,
-                                                           double *__restrict__ rhs)
-{
-    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
-    if (i > g.Nx || j > g.Ny) return;
-    const int ip = i == g.Nx ? 1 : i + 1, jp = j == g.Ny ? 1 : j + 1;
-    const long long e = plane_at(g, i, j);
-    const double Az = g.dx * g.dy;
-    const double dQ = (Qu[plane_at(g, ip, j)] - Qu[e]) + (Qv[plane_at(g, i, jp)] - Qv[e]);
-    rhs[(i - 1) + (long long)g.Nx * (j - 1)] = (dQ - Az * eta[e] / dt) / (grav * Lz * dt * Az);
-}
-// _barotropic_pressure_correction!: u -= g Δt ∂xᶠᶜᶠ η, v -= g Δt ∂yᶜᶠᶠ η at every level (η halos filled)
-__global__ __launch_bounds__(256) void barotropic_pressure_correction_kernel(GridDev g, double *__restrict__ u, double *__restrict__ v,
-                                                                             const double *__restrict__ eta, double grav, double dt)
-{
-    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y, k = 1 + blockIdx.z;
-    if (i > g.Nx || j > g.Ny) return;
-    const Lay L = make_lay(g, OCN_LOC_CCC);
-    const long long o = at(L, i, j, k), e = (i - 1 + g.Hx) + (long long)L.sx * (j - 1 + g.Hy);
-    u[o] -= grav * dt * ((eta[e] - eta[e - 1]) / g.dx);
-    v[o] -= grav * dt * ((eta[e] - eta[e - L.sx]) / g.dy);
-}
-int launch_implicit_free_surface_rhs(const ocn_grid *grid, const double *u, const double *v, const double *eta, double grav, double dt,
-                                     double *Qu, double *Qv, double *rhs, hipStream_t stream)
-{
-    GridDev g = to_dev(*grid);
-    dim3 block(64, 4, 1), nb((g.Nx + 63) / 64, (g.Ny + 3) / 4, 1);
-    hipLaunchKernelGGL(volume_flux_kernel, nb, block, 0, stream, g, u, v, Qu, Qv);
-    hipLaunchKernelGGL(implicit_rhs_kernel, nb, block, 0, stream, g, grav, grid->Lz, dt, Qu, Qv, eta, rhs);
-    OCN_CHECK_HIP(hipGetLastError());
-    return OCN_SUCCESS;
-}
-int launch_barotropic_pressure_correction(const ocn_grid *grid, double *u, double *v, const double *eta, double grav, double dt,
-                                          hipStream_t stream)
-{
-    GridDev g = to_dev(*grid);
-    dim3 block(64, 4, 1), nb((g.Nx + 63) / 64, (g.Ny + 3) / 4, g.Nz);
-    hipLaunchKernelGGL(barotropic_pressure_correction_kernel, nb, block, 0, stream, g, u, v, eta, grav, dt);
-    OCN_CHECK_HIP(hipGetLastError());
-    return OCN_SUCCESS;
-}
-
 // ---- AdamsBashforth3Scheme of the substepping (split_explicit_timesteppers.jl:19-159): the reference's two kernels per substep with the
 // AB3 extrapolations U★ = α Uᵐ + θ Uᵐ⁻¹ + β Uᵐ⁻² and η★ = δ ηᵐ⁺¹ + μ ηᵐ + γ ηᵐ⁻¹ + ϵ ηᵐ⁻² and their history updates
 // (cache_previous_free_surface! / cache_previous_velocities!).  A non-default option: kept in the reference's launch shape.
@@ -760,90 +495,12 @@ int launch_split_explicit_substeps_ab3(const ocn_grid *grid, int n, const double
     return OCN_SUCCESS;
 }
 
-// integrate_barotropic_mode! on a static grid (σ = 1): Σₖ Δz u σ (barotropic_split_explicit_corrector.jl:13-32)
-__global__ __launch_bounds__(256) void barotropic_mode_kernel(GridDev g, const double *__restrict__ u, const double *__restrict__ v,
-                                                              double *__restrict__ U, double *__restrict__ V)
-{
-    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
-    if (i > g.Nx || j > g.Ny) return;
-    const Lay L = make_lay(g, OCN_LOC_CCC);
-    long long o = at(L, i, j, 1);
-    double dz = g.dzc ? uniform_load(g.dzc, g.Hz) : g.dz;
-    double aU = dz * u[o] * 1.0, aV = dz * v[o] * 1.0;
-    for (int k = 2; k <= g.Nz; ++k) {
-        o += L.s3;
-        dz = g.dzc ? uniform_load(g.dzc, k + g.Hz - 1) : g.dz;
-        aU = aU + dz * u[o] * 1.0;
-        aV = aV + dz * v[o] * 1.0;
-    }
-    U[plane_at(g, i, j)] = aU;
-    V[plane_at(g, i, j)] = aV;
-}
-// _barotropic_split_explicit_corrector! (:57-71): u += (U - U̅) / H at every level
-__global__ __launch_bounds__(256) void barotropic_corrector_kernel(GridDev g, double *__restrict__ u, double *__restrict__ v,
-                                                                   const double *__restrict__ U, const double *__restrict__ V,
-                                                                   const double *__restrict__ Ub, const double *__restrict__ Vb, double H)
-{
-    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y, k = 1 + blockIdx.z;
-    if (i > g.Nx || j > g.Ny) return;
-    const Lay L = make_lay(g, OCN_LOC_CCC);
-    const long long o = at(L, i, j, k), e = plane_at(g, i, j);
-    u[o] = u[o] + (U[e] - Ub[e]) / H;
-    v[o] = v[o] + (V[e] - Vb[e]) / H;
-}
-int launch_split_explicit_forcing(const ocn_grid *grid, const double *Gun, const double *Gum, const double *Gvn, const double *Gvm, double chi,
-                                  double *GU, double *GV, hipStream_t stream)
-{
-    GridDev g = to_dev(*grid);
-    dim3 block(64, 4, 1), nb((g.Nx + 63) / 64, (g.Ny + 3) / 4, 1);
-    hipLaunchKernelGGL(barotropic_forcing_kernel, nb, block, 0, stream, g, Gun, Gum, Gvn, Gvm, chi, GU, GV);
-    OCN_CHECK_HIP(hipGetLastError());
-    return OCN_SUCCESS;
-}
-int launch_split_explicit_substeps(const ocn_grid *grid, int n, const double *weights, double dtau, double grav, double H, double *eta,
-                                   double *U, double *V, double *etab, double *Ub, double *Vb, const double *GU, const double *GV,
-                                   hipStream_t stream)
-{
-    GridDev g = to_dev(*grid);
-    const size_t bytes = (size_t)(g.Nx + 2 * g.Hx) * (g.Ny + 2 * g.Hy) * sizeof(double);
-    for (double *f : {etab, Ub, Vb}) OCN_CHECK_HIP(hipMemsetAsync(f, 0, bytes, stream));  // initialize_free_surface_state!
-    dim3 block(64, 4, 1), nb((g.Nx + 63) / 64, (g.Ny + 3) / 4, 1);
-    for (int m = 0; m < n; ++m) {
-        hipLaunchKernelGGL(split_explicit_eta_kernel, nb, block, 0, stream, g, dtau, eta, U, V);
-        hipLaunchKernelGGL(split_explicit_velocity_kernel, nb, block, 0, stream, g, weights[m], dtau, grav, H, eta, U, V, etab, Ub, Vb, GU, GV);
-    }
-    OCN_CHECK_HIP(hipGetLastError());
-    // _update_split_explicit_state!: η, U, V <- their averages (the halos of these planes are not used by the substepping)
-    OCN_CHECK_HIP(hipMemcpyAsync(eta, etab, bytes, hipMemcpyDeviceToDevice, stream));
-    OCN_CHECK_HIP(hipMemcpyAsync(U, Ub, bytes, hipMemcpyDeviceToDevice, stream));
-    OCN_CHECK_HIP(hipMemcpyAsync(V, Vb, bytes, hipMemcpyDeviceToDevice, stream));
-    return OCN_SUCCESS;
-}
-int launch_barotropic_mode(const ocn_grid *grid, const double *u, const double *v, double *U, double *V, hipStream_t stream)
-{
-    GridDev g = to_dev(*grid);
-    dim3 block(64, 4, 1), nb((g.Nx + 63) / 64, (g.Ny + 3) / 4, 1);
-    hipLaunchKernelGGL(barotropic_mode_kernel, nb, block, 0, stream, g, u, v, U, V);
-    OCN_CHECK_HIP(hipGetLastError());
-    return OCN_SUCCESS;
-}
-int launch_barotropic_corrector(const ocn_grid *grid, double *u, double *v, const double *U, const double *V, double *Ub, double *Vb, double H,
-                                hipStream_t stream)
-{
-    OCN_TRY(launch_barotropic_mode(grid, u, v, Ub, Vb, stream));
-    GridDev g = to_dev(*grid);
-    dim3 block(64, 4, 1), nb((g.Nx + 63) / 64, (g.Ny + 3) / 4, g.Nz);
-    hipLaunchKernelGGL(barotropic_corrector_kernel, nb, block, 0, stream, g, u, v, U, V, Ub, Vb, H);
-    OCN_CHECK_HIP(hipGetLastError());
-    return OCN_SUCCESS;
-}
-
 // ---- the substep loop, temporally blocked ------------------------------------------------------------------------------------------
 // iterate_split_explicit! launches 2 tiny kernels per substep (the reference notes it is bound by launch latency,
 // step_split_explicit_free_surface.jl:84-88; its distributed variant already trades halo width for communication,
 // split_explicit_free_surface.jl:283-300).  Here a workgroup loads a (TXO + 2 SH) x (TYO + 2 SH) patch of η, U, V, Gᵁ, Gⱽ into LDS
 // (periodic wrap on load; Gᵁ, Gⱽ in registers) and runs up to SH substeps on it: each substep invalidates one more ring of the patch, the TXO x TYO
-// centre stays exact.  Every cell is updated with the text of split_explicit_eta_kernel / split_explicit_velocity_kernel, so the
+// centre stays exact.  Every cell is updated with the text of split_explicit_eta_kernel<false, false> / split_explicit_velocity_kernel<false, false> (hydrostatic_surface.hip), so the
 // result is bit-identical; the filtered state accumulates in registers for the centre cells in substep order.  Launches
 // ping-pong between (η, U, V) and a workspace because neighbouring workgroups read each other's centre cells at load time.
 // The (η, U, V, Gᵁ, Gⱽ, filtered state) planes the kernel works on: nx x ny interior cells with x / y halos hx / hy (row stride nx + 2 hx).
@@ -1073,7 +730,7 @@ int launch_split_explicit_dist_run(const ocn_grid *grid, int W, int n, const dou
 // hydrostatic_momentum_tiled); Us, Vs: their vertical integrals Σ Δz u* (the reference recomputes them into the filtered-state
 // arrays here).  u = u* + (U - U̅*) / H is written into the model's arrays, and w integrates the divergence of the CORRECTED
 // velocities upwards from w[k = 1] = 0; the east / north neighbours are corrected on the fly with wrapped indices (x, y Periodic),
-// so the interior of w equals what w_from_continuity_kernel computes after the halo fill, bit for bit.  40 B per cell instead of
+// so the interior of w equals what w_from_continuity_kernel (hydrostatic_surface.hip) computes after the halo fill, bit for bit.  40 B per cell instead of
 // 32 (corrector) + 16 (barotropic mode) + 24 (w).
 __global__ __launch_bounds__(256) void barotropic_correct_w_kernel(GridDev g, const double *__restrict__ us, const double *__restrict__ vs,
                                                                    double *__restrict__ u, double *__restrict__ v, double *__restrict__ w,

@@ -136,6 +136,22 @@ __host__ __device__ inline long long at(const Lay &L, int i, int j, int k)
     return L.o + (i - 1) + L.s2 * (j - 1) + L.s3 * (k - 1);
 }
 
+// x-y planes of the hydrostatic layer (η, U, V, ...: parent x / y extents of their location, no z): the offset of the 1-based interior
+// (i, j) of a plane whose rows are as long as layout L's, and of one shaped like η (Center, Center)
+__device__ __forceinline__ long long plane_at(const GridDev &g, const Lay &L, int i, int j)
+{
+    return (i - 1 + g.Hx) + (long long)L.sx * (j - 1 + g.Hy);
+}
+__device__ __forceinline__ long long plane_at(const GridDev &g, int i, int j)
+{
+    return (i - 1 + g.Hx) + (long long)(g.Nx + 2 * g.Hx) * (j - 1 + g.Hy);
+}
+// Δzᵃᵃᶜ / Δzᵃᵃᶠ at level / face k (wave-uniform)
+__device__ __forceinline__ double dz_centre(const GridDev &g, int k) { return g.dzc ? uniform_load(g.dzc, k + g.Hz - 1) : g.dz; }
+__device__ __forceinline__ double dz_face(const GridDev &g, int k) { return g.dzf ? uniform_load(g.dzf, k + g.Hz - 1) : g.dz; }
+// launch grid of 64 x 4 blocks, one thread per column (or per cell: nz planes)
+inline dim3 xy_blocks(int nx, int ny, int nz = 1) { return dim3((nx + 63) / 64, (ny + 3) / 4, nz); }
+
 // Optional epilogue of the tendency launch: the NEXT RK3 substep  Uo = U + dt*(gamma*G + zeta*Gm)  (runge_kutta_3.jl:194-200)
 struct FuseArgs {
     const double *Gm[3];

@@ -120,10 +120,6 @@ int launch_set_source(int Nx, int Ny, int Nz, const double *R, const double *dzc
                       long long ld1, long long ld2, hipStream_t stream);
 int launch_spectral_solve(int nxh, int Ny, int Nz, const double *lx, const double *ly, const double *lz, double *b,
                           int zero_mode_here, int joff, int koff, hipStream_t stream, double m = 0.0, int shifted = 0);
-int launch_implicit_free_surface_rhs(const ocn_grid *grid, const double *u, const double *v, const double *eta, double grav, double dt,
-                                     double *Qu, double *Qv, double *rhs, hipStream_t stream);
-int launch_barotropic_pressure_correction(const ocn_grid *grid, double *u, double *v, const double *eta, double grav, double dt,
-                                          hipStream_t stream);
 int launch_copy_real(const ocn_grid *grid, const double *phi, double *p, hipStream_t stream, CopySource source, int perm_dim = -1);
 int launch_pressure_correct(const ocn_grid *grid, double *u, double *v, double *w, const double *p, double dt, hipStream_t stream);
 int launch_main_diagonal(const ocn_grid *grid, int nxh, const double *lx, const double *ly, double *D, hipStream_t stream);
@@ -171,15 +167,8 @@ int launch_xtri_sweep(double *a1, const double *ly, const double *lz, int NyH, i
                       hipStream_t stream);
 int launch_xtri_finish(double *a1, const double *ly, const double *lz, int NyH, int nx, int Nz, double dx, const double *grecv, int rank,
                        int R, hipStream_t stream);
-int launch_vector_invariant(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu, double *Gv,
-                            hipStream_t stream, const double *eta = nullptr, double grav = 0.0);
 int launch_vector_invariant_weno(const ocn_grid *grid, int scheme_flags, const double *u, const double *v, const double *w, double *Gu,
                                  double *Gv, const double *eta, double grav, hipStream_t stream);  // vector_invariant_weno.hip
-int launch_split_explicit_forcing(const ocn_grid *grid, const double *Gun, const double *Gum, const double *Gvn, const double *Gvm, double chi,
-                                  double *GU, double *GV, hipStream_t stream);
-int launch_split_explicit_substeps(const ocn_grid *grid, int n, const double *weights, double dtau, double grav, double H, double *eta,
-                                   double *U, double *V, double *etab, double *Ub, double *Vb, const double *GU, const double *GV,
-                                   hipStream_t stream);
 int launch_split_explicit_substeps_blocked(const ocn_grid *grid, int n, const double *weights, double dtau, double grav, double H, double *eta,
                                            double *U, double *V, double *etab, double *Ub, double *Vb, const double *GU, const double *GV,
                                            double *work, hipStream_t stream);
@@ -192,32 +181,27 @@ int launch_split_explicit_dist_run(const ocn_grid *grid, int W, int n, const dou
                                    double *U, double *V, double *work, const double *recv_west, const double *recv_east, hipStream_t stream);
 int launch_barotropic_correct_w(const ocn_grid *grid, const double *us, const double *vs, double *u, double *v, double *w, const double *U,
                                 const double *V, const double *Us, const double *Vs, double H, hipStream_t stream);
+int launch_free_surface_ab2(const ocn_grid *grid, const double *w, double *eta, double *Gn, const double *Gm, double dt, double chi,
+                            hipStream_t stream);
+// the hydrostatic kernels of every horizontal topology -- (Periodic, Periodic | Bounded, Bounded), (Bounded, Bounded, Bounded) --
+// (hydrostatic_surface.hip): per-location parent layouts and planes
+int launch_w_from_continuity(const ocn_grid *grid, const double *u, const double *v, double *w, hipStream_t stream);
+int launch_vector_invariant(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu, double *Gv, const double *eta,
+                            double grav, hipStream_t stream);
+int launch_barotropic_gradient(const ocn_grid *grid, double grav, const double *eta, double *Gu, double *Gv, hipStream_t stream);
+int launch_implicit_free_surface_rhs(const ocn_grid *grid, const double *u, const double *v, const double *eta, double grav, double dt,
+                                     double *Qu, double *Qv, double *rhs, hipStream_t stream);
+int launch_barotropic_pressure_correction(const ocn_grid *grid, double *u, double *v, const double *eta, double grav, double dt,
+                                          hipStream_t stream);
+int launch_plane_halo(const ocn_grid *grid, double *plane, hipStream_t stream);
+int launch_split_explicit_forcing(const ocn_grid *grid, const double *Gun, const double *Gum, const double *Gvn, const double *Gvm, double chi,
+                                  double *GU, double *GV, hipStream_t stream);
+int launch_split_explicit_substeps(const ocn_grid *grid, int n, const double *weights, double dtau, double grav, double H, double *eta,
+                                   double *U, double *V, double *etab, double *Ub, double *Vb, const double *GU, const double *GV,
+                                   hipStream_t stream);
 int launch_barotropic_mode(const ocn_grid *grid, const double *u, const double *v, double *U, double *V, hipStream_t stream);
 int launch_barotropic_corrector(const ocn_grid *grid, double *u, double *v, const double *U, const double *V, double *Ub, double *Vb, double H,
                                 hipStream_t stream);
-int launch_plane_halo(const ocn_grid *grid, double *plane, hipStream_t stream);
-int launch_w_from_continuity(const ocn_grid *grid, const double *u, const double *v, double *w, hipStream_t stream);
-int launch_barotropic_gradient(const ocn_grid *grid, double grav, const double *eta, double *Gu, double *Gv, hipStream_t stream);
-int launch_free_surface_ab2(const ocn_grid *grid, const double *w, double *eta, double *Gn, const double *Gm, double dt, double chi,
-                            hipStream_t stream);
-// the hydrostatic kernels on grids with walls in y or in x and y (hydrostatic_walls.hip): per-location parent layouts and planes
-int launch_w_from_continuity_walls(const ocn_grid *grid, const double *u, const double *v, double *w, hipStream_t stream);
-int launch_vector_invariant_walls(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu, double *Gv,
-                                  const double *eta, double grav, hipStream_t stream);
-int launch_barotropic_gradient_walls(const ocn_grid *grid, double grav, const double *eta, double *Gu, double *Gv, hipStream_t stream);
-int launch_barotropic_pressure_correction_walls(const ocn_grid *grid, double *u, double *v, const double *eta, double grav, double dt,
-                                                hipStream_t stream);
-int launch_plane_halo_walls(const ocn_grid *grid, double *plane, hipStream_t stream);
-int launch_split_explicit_forcing_walls(const ocn_grid *grid, const double *Gun, const double *Gum, const double *Gvn, const double *Gvm,
-                                        double chi, double *GU, double *GV, hipStream_t stream);
-int launch_barotropic_mode_walls(const ocn_grid *grid, const double *u, const double *v, double *U, double *V, hipStream_t stream);
-int launch_barotropic_corrector_walls(const ocn_grid *grid, double *u, double *v, const double *U, const double *V, double *Ub, double *Vb,
-                                      double H, hipStream_t stream);
-int launch_split_explicit_substeps_walls(const ocn_grid *grid, int n, const double *weights, double dtau, double grav, double H, double *eta,
-                                         double *U, double *V, double *etab, double *Ub, double *Vb, const double *GU, const double *GV,
-                                         hipStream_t stream);
-int launch_implicit_free_surface_rhs_walls(const ocn_grid *grid, const double *u, const double *v, const double *eta, double grav, double dt,
-                                           double *Qu, double *Qv, double *rhs, hipStream_t stream);
 // the hydrostatic kernels on ImmersedBoundaryGrid(grid, GridFittedBottom(h)) (immersed.hip): kbot is the int32 plane of immersed cells per column
 int launch_immersed_bottom(const ocn_grid *grid, int interface_condition, const double *h, const double *zc, const double *zf, double *bottom,
                            int32_t *kbot, double *Hcc, double *Hfc, double *Hcf, hipStream_t stream);

@@ -654,7 +654,7 @@ __global__ __launch_bounds__(256, SH ? 3 : 4) void momentum_extra_tiled(GridDev 
 // one-cell rim (every stencil of the vector-invariant form and of the stress divergence fits), pHY′, G⁻ are touched once per cell.
 // The column sums ride along in registers in the reference's order (k ascending, first term assigned), so the strict build is
 // bit-identical to the unfused kernels (vector_invariant_kernel, momentum_extra_kernel, stepper_kernel<2>,
-// barotropic_forcing_kernel, barotropic_mode_kernel).  HBM per cell: read u, v, w, pHY′, G⁻u, G⁻v; write Gu, Gv, u*, v* = 80 B
+// column_sum_kernel<..., 1 / 0> of hydrostatic_surface.hip).  HBM per cell: read u, v, w, pHY′, G⁻u, G⁻v; write Gu, Gv, u*, v* = 80 B
 // (the five launches it replaces: 264 B).
 // ---------------------------------------------------------------------------------------------------
 template <class FU, class FV, class FW>

@@ -1,6 +1,6 @@
 """First slice of the reference's HydrostaticFreeSurfaceModel on the HIP backend: ExplicitFreeSurface,
 flux-form momentum advection, QuasiAdamsBashforth2, static (Periodic, Periodic, Bounded) RectilinearGrid, one GPU.  (Periodic, Bounded, Bounded)
-channels and (Bounded, Bounded, Bounded) basins run the reference's launch sequence on the kernels of csrc/hydrostatic_walls.hip (what they
+channels and (Bounded, Bounded, Bounded) basins run the reference's launch sequence on the kernels of csrc/hydrostatic_surface.hip (what they
 take and refuse: `_refuse_on_walls`).  On ImmersedBoundaryGrid(grid, GridFittedBottom(h)) the model steps over a stepped bottom with
 the kernels of csrc/immersed.hip, again in the reference's launch sequence (`_refuse_on_immersed`).
 
@@ -372,7 +372,7 @@ class HydrostaticFreeSurfaceModel:
         arch = grid.architecture
         self._dist = arch if (hasattr(arch, "partition") and arch.communicates) else None   # a slab-x rank (distributed.py)
         topology = tuple(grid.topology)
-        # a channel or a closed basin: per-location layouts and planes, csrc/hydrostatic_walls.hip
+        # a channel or a closed basin: per-location layouts and planes, csrc/hydrostatic_surface.hip
         self._walls = self._dist is None and topology in ((Periodic, Bounded, Bounded), (Bounded, Bounded, Bounded))
         if not self._walls and topology != (FullyConnected if self._dist is not None else Periodic, Periodic, Bounded):
             raise NotImplementedError("HydrostaticFreeSurfaceModel: (Periodic, Periodic, Bounded), (Periodic, Bounded, Bounded) and (Bounded, Bounded, "

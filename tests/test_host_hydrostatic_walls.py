@@ -196,6 +196,65 @@ def test_a_resting_stratified_state_stays_at_rest(oracle, shape, surface, moment
     assert np.abs(og.interior_N(m.tracers[0]) - T0).max() > 0
 
 
+# ---- 3b. without walls the restatement is the periodic oracle ----------------------------------------------------------------------
+@pytest.mark.parametrize("size, halo", [((16, 12, 7), (3, 3, 3)), ((67, 6, 3), (4, 5, 3))])
+def test_the_restatement_on_a_periodic_grid_is_the_oracle(oracle, size, halo):
+    """On (Periodic, Periodic, Bounded) the per-direction restatement functions must return the bits of what oracle/hydrostatic.py itself
+    computes with: the GPU entry-point tests on PPB (test_gpu_hydrostatic_walls.py) compare against the restatement, and through this test
+    against the oracle.  A split-explicit model two steps in supplies fields with filled halos and both tendency levels."""
+    from oracle import hydrostatic as Hy
+    O = oracle
+    g = _grid(O, size, "PPB", halo=halo)
+    m = Hy.HydrostaticFreeSurfaceModel(g, tracers=("T", "S"), momentum_advection="VectorInvariant", coriolis_f=1e-4, closure=(1e-2, 2e-3),
+                                       buoyancy=("SeawaterBuoyancy", G_EARTH, 2e-4, 8e-4), split_explicit_substeps=5)
+    rng = np.random.default_rng(11)
+    init = _random_state(g, rng)
+    init["T"], init["S"] = 20 + 1e-2 * rng.uniform(-1, 1, size), 35 + 1e-2 * rng.uniform(-1, 1, size)
+    m.set(**init)
+    for _ in range(2):
+        m.time_step(20.0)
+    same = np.testing.assert_array_equal
+    # the η fill: NaN halos, so a cell the fill does not reach would show
+    e = np.full_like(m.eta, np.nan)
+    ii, jj = slice(g.Hx, g.Hx + g.Nx), slice(g.Hy, g.Hy + g.Ny)
+    e[ii, jj] = rng.uniform(-1, 1, (g.Nx, g.Ny))
+    mine, m.eta = e.copy(), e
+    HW.fill_eta(g, mine)
+    m._fill_eta()
+    same(mine, m.eta)
+    assert np.isfinite(mine).all()
+    # w from continuity (the oracle also zeroes the bottom face of the last parent row / column, which has no neighbour)
+    w_mine, w_oracle = (np.full_like(m.w, 777.0) for _ in range(2))
+    HW.compute_w_from_continuity(g, m.u, m.v, w_mine)
+    Hy.compute_w_from_continuity(g, m.u, m.v, w_oracle)
+    same(w_mine[:-1, :-1], w_oracle[:-1, :-1])
+    # the barotropic mode and the forcing sums, AB2 and Euler coefficients
+    same(HW.barotropic_mode(g, m.u), m._barotropic_mode(m.u))
+    same(HW.barotropic_mode(g, m.v), m._barotropic_mode(m.v))
+    for chi in (0.1, -0.5):
+        m._split_explicit_step(20.0, chi)
+        same(HW.split_explicit_forcing(g, m.Gn[0], m.Gm[0], chi), m.GU)
+        same(HW.split_explicit_forcing(g, m.Gn[1], m.Gm[1], chi), m.GV)
+        assert np.abs(m.GU).max() > 0 and np.abs(m.GV).max() > 0
+    # the substep iteration
+    state = [a.copy() for a in (m.eta[ii, jj], m.U, m.V)]
+    dtau, weights = m.frac_dt * 20.0, m.weights
+    runs = []
+    for iterate, topo in ((HW.iterate_split_explicit, (False, False)), (Hy.iterate_split_explicit, ())):
+        s = [a.copy() for a in state] + [np.zeros((g.Nx, g.Ny)) for _ in range(3)]
+        iterate(*s, m.GU, m.GV, dtau, weights, G_EARTH, g.Lz, g.dx, g.dy, *topo)
+        runs.append(s)
+    for a, b in zip(*runs):
+        same(a, b)
+    assert np.abs(runs[0][3] - state[0]).max() > 0
+    # the corrector
+    u0, v0 = m.u.copy(), m.v.copy()
+    Ub, Vb = HW.barotropic_corrector(g, u0, v0, m.U, m.V)
+    m._barotropic_corrector()
+    for a, b in ((u0, m.u), (v0, m.v), (Ub, m.Ub), (Vb, m.Vb)):
+        same(a, b)
+
+
 # ---- 4. the product's constructor -----------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def pkg():

@@ -6,7 +6,7 @@ one process, the three topologies alternating:
   tools/bench_hydrostatic_walls.py [Nx] [Nz] [steps]
 
 1. the unfused step (fused = False: the reference's launch sequence, the only one on wall grids) on (Periodic, Periodic, Bounded) -- the
-   yardstick: its kernels are the ones it had before the wall kernels existed --, (Periodic, Bounded, Bounded) and (Bounded, Bounded, Bounded);
+   yardstick: the <false, false> instantiation of the same kernels (csrc/hydrostatic_surface.hip) --, (Periodic, Bounded, Bounded) and (Bounded, Bounded, Bounded);
 2. every hydrostatic-specific entry point alone on each topology (a device-event pair around each launch after a warm-up);
 3. the tendency entry points shared with NonhydrostaticModel, which are known to cost more on wall grids, reported apart.
 Two rounds of repeats; per round the median (minimum to maximum).  Prints one line per figure and topology."""
