@@ -552,7 +552,7 @@ int ocn_compute_vector_invariant_momentum_tendencies(const ocn_grid *grid, const
     OCN_TRY(validate_hydrostatic(grid, "ocn_compute_vector_invariant_momentum_tendencies", true));
     OCN_REQUIRE(u && v && w && Gu && Gv, "ocn_compute_vector_invariant_momentum_tendencies: null field pointer");
     OCN_REQUIRE(grid->Hz >= 1, "ocn_compute_vector_invariant_momentum_tendencies: needs a z halo");
-    return launch_vector_invariant(grid, u, v, w, Gu, Gv, eta, gravitational_acceleration, as_stream(stream));
+    return launch_vector_invariant(grid, Bottom{}, u, v, w, Gu, Gv, eta, gravitational_acceleration, as_stream(stream));
 }
 int ocn_compute_vector_invariant_weno_momentum_tendencies(const ocn_grid *grid, int32_t scheme_flags, const double *u, const double *v,
                                                           const double *w, double *Gu, double *Gv, const double *eta,
@@ -576,7 +576,7 @@ int ocn_split_explicit_forcing(const ocn_grid *grid, const double *Gu, const dou
 {
     OCN_TRY(validate_hydrostatic(grid, "ocn_split_explicit_forcing", true));
     OCN_REQUIRE(Gu && Gu_previous && Gv && Gv_previous && GU && GV, "ocn_split_explicit_forcing: null pointer");
-    return launch_split_explicit_forcing(grid, Gu, Gu_previous, Gv, Gv_previous, chi, GU, GV, as_stream(stream));
+    return launch_split_explicit_forcing(grid, Bottom{}, Gu, Gu_previous, Gv, Gv_previous, chi, GU, GV, as_stream(stream));
 }
 int ocn_split_explicit_substeps(const ocn_grid *grid, int32_t n, const double *weights, double dtau, double gravitational_acceleration,
                                 double column_depth, double *eta, double *U, double *V, double *eta_filtered, double *U_filtered,
@@ -586,7 +586,7 @@ int ocn_split_explicit_substeps(const ocn_grid *grid, int32_t n, const double *w
     OCN_REQUIRE(grid->tx != OCN_FULLY_CONNECTED, "ocn_split_explicit_substeps wraps x periodically: not for a partitioned (FullyConnected) x");
     OCN_REQUIRE(n >= 1 && weights, "ocn_split_explicit_substeps: needs n >= 1 averaging weights (host array)");
     OCN_REQUIRE(eta && U && V && eta_filtered && U_filtered && V_filtered && GU && GV, "ocn_split_explicit_substeps: null pointer");
-    return launch_split_explicit_substeps(grid, n, weights, dtau, gravitational_acceleration, column_depth, eta, U, V, eta_filtered, U_filtered,
+    return launch_split_explicit_substeps(grid, Bottom{}, n, weights, dtau, gravitational_acceleration, column_depth, eta, U, V, eta_filtered, U_filtered,
                                           V_filtered, GU, GV, as_stream(stream));
 }
 int ocn_compute_barotropic_mode(const ocn_grid *grid, const double *u, const double *v, double *U, double *V, void *stream)
@@ -600,7 +600,7 @@ int ocn_barotropic_split_explicit_corrector(const ocn_grid *grid, double *u, dou
 {
     OCN_TRY(validate_hydrostatic(grid, "ocn_barotropic_split_explicit_corrector", true));
     OCN_REQUIRE(u && v && U && V && U_filtered && V_filtered, "ocn_barotropic_split_explicit_corrector: null pointer");
-    return launch_barotropic_corrector(grid, u, v, U, V, U_filtered, V_filtered, column_depth, as_stream(stream));
+    return launch_barotropic_corrector(grid, Bottom{}, u, v, U, V, U_filtered, V_filtered, column_depth, as_stream(stream));
 }
 int ocn_fill_free_surface_halos(const ocn_grid *grid, double *eta, void *stream)
 {
@@ -666,7 +666,7 @@ int ocn_immersed_vector_invariant_momentum_tendencies(const ocn_grid *grid, cons
 {
     OCN_TRY(validate_immersed(grid, "ocn_immersed_vector_invariant_momentum_tendencies"));
     OCN_REQUIRE(kbot && u && v && w && Gu && Gv, "ocn_immersed_vector_invariant_momentum_tendencies: null pointer");
-    return launch_vector_invariant_immersed(grid, kbot, u, v, w, Gu, Gv, eta, gravitational_acceleration, as_stream(stream));
+    return launch_vector_invariant(grid, Bottom{kbot}, u, v, w, Gu, Gv, eta, gravitational_acceleration, as_stream(stream));
 }
 int ocn_immersed_add_viscous_terms(const ocn_grid *grid, const int32_t *kbot, double nu, const double *u, const double *v, const double *w,
                                    double *Gu, double *Gv, void *stream)
@@ -690,7 +690,7 @@ int ocn_immersed_split_explicit_forcing(const ocn_grid *grid, const int32_t *kbo
 {
     OCN_TRY(validate_immersed(grid, "ocn_immersed_split_explicit_forcing"));
     OCN_REQUIRE(kbot && Gu && Gu_previous && Gv && Gv_previous && GU && GV, "ocn_immersed_split_explicit_forcing: null pointer");
-    return launch_split_explicit_forcing_immersed(grid, kbot, Gu, Gu_previous, Gv, Gv_previous, chi, GU, GV, as_stream(stream));
+    return launch_split_explicit_forcing(grid, Bottom{kbot}, Gu, Gu_previous, Gv, Gv_previous, chi, GU, GV, as_stream(stream));
 }
 int ocn_immersed_split_explicit_substeps(const ocn_grid *grid, const int32_t *kbot, const double *Hfc, const double *Hcf, int32_t n,
                                          const double *weights, double dtau, double gravitational_acceleration, double *eta, double *U,
@@ -701,15 +701,15 @@ int ocn_immersed_split_explicit_substeps(const ocn_grid *grid, const int32_t *kb
     OCN_REQUIRE(n >= 1 && weights, "ocn_immersed_split_explicit_substeps: needs n >= 1 averaging weights (host array)");
     OCN_REQUIRE(kbot && Hfc && Hcf && eta && U && V && eta_filtered && U_filtered && V_filtered && GU && GV,
                 "ocn_immersed_split_explicit_substeps: null pointer");
-    return launch_split_explicit_substeps_immersed(grid, kbot, Hfc, Hcf, n, weights, dtau, gravitational_acceleration, eta, U, V, eta_filtered,
-                                                   U_filtered, V_filtered, GU, GV, as_stream(stream));
+    return launch_split_explicit_substeps(grid, Bottom{kbot, Hfc, Hcf}, n, weights, dtau, gravitational_acceleration, 0.0, eta, U, V, eta_filtered,
+                                          U_filtered, V_filtered, GU, GV, as_stream(stream));
 }
 int ocn_immersed_barotropic_corrector(const ocn_grid *grid, const double *Hfc, const double *Hcf, double *u, double *v, const double *U,
                                       const double *V, double *U_filtered, double *V_filtered, void *stream)
 {
     OCN_TRY(validate_immersed(grid, "ocn_immersed_barotropic_corrector"));
     OCN_REQUIRE(Hfc && Hcf && u && v && U && V && U_filtered && V_filtered, "ocn_immersed_barotropic_corrector: null pointer");
-    return launch_barotropic_corrector_immersed(grid, Hfc, Hcf, u, v, U, V, U_filtered, V_filtered, as_stream(stream));
+    return launch_barotropic_corrector(grid, Bottom{nullptr, Hfc, Hcf}, u, v, U, V, U_filtered, V_filtered, 0.0, as_stream(stream));
 }
 
 static int validate_amd(const ocn_grid *grid)

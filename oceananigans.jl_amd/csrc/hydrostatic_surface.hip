@@ -12,9 +12,19 @@
 // the WEST / SOUTH wall face (index 1) and not the east / north one (index N + 1).  The wall-normal velocity on both wall faces is reset
 // by the halo fill of update_state! (fill_open_boundary_regions!, fill_halo_regions_open.jl:65-70), not here.
 // The differences across a wall are the topology-aware operators of Operators/topology_aware_operators.jl:40-56.
+//
+// The bottom is a second compile-time parameter of the five kernels that meet it, next to <BX, BY>: the pack B is empty over
+// a flat bottom -- the kernel then has no argument for it, every predicate is a compile-time false and the column depth is the number H --
+// or it is Bottom, the GridFittedBottom of an ImmersedBoundaryGrid, whose kernel takes the kbot and depth planes as one more argument and
+// applies the reference's immersed rules in the same evaluation order, so that over a flat bottom both return the same bits:
+//   * conditional differences   ImmersedBoundaries/conditional_differences.jl:25-90: a difference is 0 when one of its two nodes is an
+//                               immersed_inactive_node, otherwise the underlying grid's
+//   * split-explicit surface    SplitExplicitFreeSurfaces/*.jl with static_column_depth (grid_fitted_bottom.jl:147-150)
+// Only <false, false, Bottom> is instantiated: bathymetry on a (Periodic, Periodic, Bounded) grid (validate_immersed of capi.hip).
 #include <type_traits>
 
 #include "ocn_common.h"
+#include "ocn_immersed.h"
 #include "ocn_internal.h"
 
 namespace ocn {
@@ -45,6 +55,59 @@ inline void dispatch_walls(const ocn_grid *grid, F f)
     if (grid->ty != OCN_BOUNDED) f(std::false_type{}, std::false_type{});
     else if (grid->tx == OCN_BOUNDED) f(std::true_type{}, std::true_type{});
     else f(std::false_type{}, std::true_type{});
+}
+// ... and of the bottom: F also takes the pack of kernel arguments that the bottom adds, none or the Bottom (kernel<bx, by, decltype(b)...>)
+template <class F>
+inline void dispatch_bottom(const ocn_grid *grid, const Bottom &bottom, F f)
+{
+    if (bottom.fitted()) f(std::false_type{}, std::false_type{}, bottom);
+    else dispatch_walls(grid, f);
+}
+
+// What a thread knows of the bottom under the 3 x 3 columns around its own: the node predicates of the immersed rules, at the u node
+// (Face, Center), the v node (Center, Face) or the cell of column (i + a, j + b) and level k.  Over a flat bottom nothing, and every
+// predicate is a compile-time false: zero_if(false, x) is x.
+struct FlatColumns {
+    static constexpr bool inactive_u(int, int, int) { return false; }
+    static constexpr bool inactive_v(int, int, int) { return false; }
+    static constexpr bool inactive_cell(int, int, int) { return false; }
+    static constexpr bool peripheral_u(int, int, int) { return false; }
+    static constexpr bool peripheral_v(int, int, int) { return false; }
+    static constexpr bool dry(int, int) { return false; }
+};
+// Over a fitted bottom kbot of the nine columns, in registers; this is the only place where the min / max combinations are formed
+struct FittedColumns {
+    Cols c;
+    int Nz;
+    __device__ __forceinline__ bool inactive_u(int a, int b, int k) const { return inactive_c(imin(c(a - 1, b), c(a, b)), k, Nz); }
+    __device__ __forceinline__ bool inactive_v(int a, int b, int k) const { return inactive_c(imin(c(a, b - 1), c(a, b)), k, Nz); }
+    __device__ __forceinline__ bool inactive_cell(int a, int b, int k) const { return inactive_c(c(a, b), k, Nz); }
+    // (at 1 <= k <= Nz, where the kernels ask: inactive_cell of the immersed grid alone)
+    __device__ __forceinline__ bool peripheral_u(int a, int b, int k) const { return ic(imax(c(a - 1, b), c(a, b)), k, Nz); }
+    __device__ __forceinline__ bool peripheral_v(int a, int b, int k) const { return ic(imax(c(a, b - 1), c(a, b)), k, Nz); }
+    __device__ __forceinline__ bool dry(int a, int b) const { return inactive_f_top(c(a, b), Nz); }
+};
+__device__ __forceinline__ FlatColumns columns(const GridDev &, int, int) { return {}; }
+__device__ __forceinline__ FittedColumns columns(const GridDev &g, int i, int j, const Bottom &b) { return {load_cols(g, b.kbot, i, j), g.Nz}; }
+__device__ __forceinline__ double zero_if(bool p, double x) { return p ? 0.0 : x; }
+// static_column_depthᶠᶜᵃ / ᶜᶠᵃ at plane index e: the number H over a flat bottom, the planes Hᶠᶜ, Hᶜᶠ of a fitted one
+__device__ __forceinline__ double depth_fc(double H, long long) { return H; }
+__device__ __forceinline__ double depth_cf(double H, long long) { return H; }
+__device__ __forceinline__ double depth_fc(double, long long e, const Bottom &b) { return b.Hfc[e]; }
+__device__ __forceinline__ double depth_cf(double, long long e, const Bottom &b) { return b.Hcf[e]; }
+// The levels of a thread: the one of its block over a flat bottom; over a fitted one KZ levels, with the columns' kbot in registers:
+//     int k = first_level<B...>();  [before the thread may leave]  ...  do { the cell at level k } while (next_level<B...>(g, k));
+// (over a flat bottom the condition is a compile-time false and the body straight-line code, as it always was: around a lambda, an inlined
+// function or a for loop of one iteration the compiler orders the flat kernels' code differently)
+template <class... B>
+constexpr int levels_per_thread = sizeof...(B) ? KZ : 1;
+template <class... B>
+__device__ __forceinline__ int first_level() { return 1 + blockIdx.z * levels_per_thread<B...>; }
+template <class... B>
+__device__ __forceinline__ bool next_level(const GridDev &g, int &k)
+{
+    if constexpr (levels_per_thread<B...> == 1) return false;
+    else return k % KZ != 0 && ++k <= g.Nz;
 }
 
 // _compute_w_from_continuity! (src/Models/HydrostaticFreeSurfaceModels/compute_w_from_continuity.jl:31-40): w[i,j,1] = 0,
@@ -79,58 +142,73 @@ __global__ __launch_bounds__(256) void w_from_continuity_kernel(GridDev g, const
 // ζ at the wall corners and the interpolations next to a wall read the filled halos of u and v (no-flux / Value halos of the tangential
 // component, zero wall faces of the normal one), as the reference's operators do on a Bounded grid.
 // eta != NULL: the barotropic pressure gradient - g ∇η (eta_gradient_kernel below) is subtracted in the same pass.
-template <bool BX, bool BY>
-__global__ __launch_bounds__(256) void vector_invariant_kernel(GridDev g, const double *__restrict__ u, const double *__restrict__ v,
+// Over a fitted bottom the conditional differences: the two differences of ζ₃ᶠᶠᶜ, ∂z u / ∂z v of the vertical advection, ∂x / ∂y of Kh.
+// g ∂x η is taken at k = Nz + 1, where the centre node is inactive on the underlying grid as well: never zeroed.
+template <bool BX, bool BY, class... B>
+__global__ __launch_bounds__(256) void vector_invariant_kernel(GridDev g, B... bottom, const double *__restrict__ u, const double *__restrict__ v,
                                                                const double *__restrict__ w, double *__restrict__ Gu,
                                                                double *__restrict__ Gv, const double *__restrict__ eta, double grav)
 {
-    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y, k = 1 + blockIdx.z;
+    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
+    int k = first_level<B...>();
     if (i > g.Nx || j > g.Ny) return;
+    const auto col = columns(g, i, j, bottom...);
     const HLay<BX, BY> L = hlay<BX, BY>(g);
-    const long long ou = at(L.u, i, j, k), ov = at(L.v, i, j, k);
-    const double dx = g.dx, dy = g.dy, Az = dx * dy;
-    const double dzf0 = dz_face(g, k), dzf1 = dz_face(g, k + 1);  // Δzᶠ at faces k, k+1
-    const double *pu = u + ou, *pv = v + ov, *pw = w + at(L.c, i, j, k);
-#define U_(a, b, c) pu[(a) + (b)*L.u.s2 + (c)*L.u.s3]
-#define V_(a, b, c) pv[(a) + (b)*L.v.s2 + (c)*L.v.s3]
-#define W_(a, b, c) pw[(a) + (b)*L.c.s2 + (c)*L.c.s3]
-    auto zeta = [&](int a, int b) {  // ζ₃ᶠᶠᶜ at (i + a, j + b)
-        const double gam = (dy * V_(a, b, 0) - dy * V_(a - 1, b, 0)) - (dx * U_(a, b, 0) - dx * U_(a, b - 1, 0));
-        return gam / Az;
-    };
-    auto Kh = [&](int a, int b) {    // Khᶜᶜᶜ at (i + a, j + b)
-        return (0.5 * (U_(a, b, 0) * U_(a, b, 0) + U_(a + 1, b, 0) * U_(a + 1, b, 0)) +
-                0.5 * (V_(a, b, 0) * V_(a, b, 0) + V_(a, b + 1, 0) * V_(a, b + 1, 0))) / 2;
-    };
-    {   // ---- u
-        auto m = [&](int a) { return 0.5 * (dx * V_(a, 0, 0) + dx * V_(a, 1, 0)); };  // ℑyᵃᶜᵃ(Δx_qᶜᶠᶜ v) at (i + a, j)
-        const double hadv = -(0.5 * (zeta(0, 0) + zeta(0, 1))) * (0.5 * (m(-1) + m(0))) / dx;
-        auto Z = [&](int c, double dzf) { return (0.5 * (Az * W_(-1, 0, c) + Az * W_(0, 0, c))) * ((U_(0, 0, c) - U_(0, 0, c - 1)) / dzf); };
-        const double vadv = (0.5 * (Z(0, dzf0) + Z(1, dzf1))) / Az;
-        const double bern = (Kh(0, 0) - Kh(-1, 0)) / dx;
-        double G = -((hadv + vadv) + bern);
-        if (eta) {  // (the plane index where it is used, not up front: it would be live, in registers, across both halves)
-            const long long e = plane_at(g, L.c, i, j);
-            G -= grav * ((eta[e] - eta[e - 1]) / g.dx);
+    do {
+        const long long ou = at(L.u, i, j, k), ov = at(L.v, i, j, k);
+        const double dx = g.dx, dy = g.dy, Az = dx * dy;
+        const double dzf0 = dz_face(g, k), dzf1 = dz_face(g, k + 1);  // Δzᶠ at faces k, k+1
+        const double *pu = u + ou, *pv = v + ov, *pw = w + at(L.c, i, j, k);
+#define U_(a, b, q) pu[(a) + (b)*L.u.s2 + (q)*L.u.s3]
+#define V_(a, b, q) pv[(a) + (b)*L.v.s2 + (q)*L.v.s3]
+#define W_(a, b, q) pw[(a) + (b)*L.c.s2 + (q)*L.c.s3]
+        // ζ₃ᶠᶠᶜ at (i + a, j + b): δxᶠᶠᶜ(Δy v) is 0 when one of its two v nodes is inactive, δyᶠᶠᶜ(Δx u) when one of its two u nodes is
+        auto zeta = [&](int a, int b) {
+            const double dv = zero_if(col.inactive_v(a, b, k) || col.inactive_v(a - 1, b, k), dy * V_(a, b, 0) - dy * V_(a - 1, b, 0));
+            const double du = zero_if(col.inactive_u(a, b, k) || col.inactive_u(a, b - 1, k), dx * U_(a, b, 0) - dx * U_(a, b - 1, 0));
+            const double gam = dv - du;
+            return gam / Az;
+        };
+        auto Kh = [&](int a, int b) {    // Khᶜᶜᶜ at (i + a, j + b)
+            return (0.5 * (U_(a, b, 0) * U_(a, b, 0) + U_(a + 1, b, 0) * U_(a + 1, b, 0)) +
+                    0.5 * (V_(a, b, 0) * V_(a, b, 0) + V_(a, b + 1, 0) * V_(a, b + 1, 0))) / 2;
+        };
+        {   // ---- u
+            auto m = [&](int a) { return 0.5 * (dx * V_(a, 0, 0) + dx * V_(a, 1, 0)); };  // ℑyᵃᶜᵃ(Δx_qᶜᶠᶜ v) at (i + a, j)
+            const double hadv = -(0.5 * (zeta(0, 0) + zeta(0, 1))) * (0.5 * (m(-1) + m(0))) / dx;
+            auto Z = [&](int q, double dzf) {  // ζ₂wᶠᶜᶠ at face k + q: ∂zᶠᶜᶠ u is 0 when u at k + q or at k + q - 1 is inactive
+                const bool zz = col.inactive_u(0, 0, k + q) || col.inactive_u(0, 0, k + q - 1);
+                return (0.5 * (Az * W_(-1, 0, q) + Az * W_(0, 0, q))) * (zero_if(zz, U_(0, 0, q) - U_(0, 0, q - 1)) / dzf);
+            };
+            const double vadv = (0.5 * (Z(0, dzf0) + Z(1, dzf1))) / Az;
+            const double bern = zero_if(col.inactive_cell(0, 0, k) || col.inactive_cell(-1, 0, k), Kh(0, 0) - Kh(-1, 0)) / dx;
+            double G = -((hadv + vadv) + bern);
+            if (eta) {  // (the plane index where it is used, not up front: it would be live, in registers, across both halves)
+                const long long e = plane_at(g, L.c, i, j);
+                G -= grav * ((eta[e] - eta[e - 1]) / g.dx);
+            }
+            Gu[ou] = G;
         }
-        Gu[ou] = G;
-    }
-    {   // ---- v
-        auto n = [&](int b) { return 0.5 * (dy * U_(0, b, 0) + dy * U_(1, b, 0)); };  // ℑxᶜᵃᵃ(Δy_qᶠᶜᶜ u) at (i, j + b)
-        const double hadv = (0.5 * (zeta(0, 0) + zeta(1, 0))) * (0.5 * (n(-1) + n(0))) / dy;
-        auto Z = [&](int c, double dzf) { return (0.5 * (Az * W_(0, -1, c) + Az * W_(0, 0, c))) * ((V_(0, 0, c) - V_(0, 0, c - 1)) / dzf); };
-        const double vadv = (0.5 * (Z(0, dzf0) + Z(1, dzf1))) / Az;
-        const double bern = (Kh(0, 0) - Kh(0, -1)) / dy;
-        double G = -((hadv + vadv) + bern);
-        if (eta) {
-            const long long e = plane_at(g, L.c, i, j);
-            G -= grav * ((eta[e] - eta[e - L.c.sx]) / g.dy);
+        {   // ---- v
+            auto n = [&](int b) { return 0.5 * (dy * U_(0, b, 0) + dy * U_(1, b, 0)); };  // ℑxᶜᵃᵃ(Δy_qᶠᶜᶜ u) at (i, j + b)
+            const double hadv = (0.5 * (zeta(0, 0) + zeta(1, 0))) * (0.5 * (n(-1) + n(0))) / dy;
+            auto Z = [&](int q, double dzf) {
+                const bool zz = col.inactive_v(0, 0, k + q) || col.inactive_v(0, 0, k + q - 1);
+                return (0.5 * (Az * W_(0, -1, q) + Az * W_(0, 0, q))) * (zero_if(zz, V_(0, 0, q) - V_(0, 0, q - 1)) / dzf);
+            };
+            const double vadv = (0.5 * (Z(0, dzf0) + Z(1, dzf1))) / Az;
+            const double bern = zero_if(col.inactive_cell(0, 0, k) || col.inactive_cell(0, -1, k), Kh(0, 0) - Kh(0, -1)) / dy;
+            double G = -((hadv + vadv) + bern);
+            if (eta) {
+                const long long e = plane_at(g, L.c, i, j);
+                G -= grav * ((eta[e] - eta[e - L.c.sx]) / g.dy);
+            }
+            Gv[ov] = G;
         }
-        Gv[ov] = G;
-    }
 #undef U_
 #undef V_
 #undef W_
+    } while (next_level<B...>(g, k));
 }
 
 // Gu -= g ∂xᶠᶜᶜ η, Gv -= g ∂yᶜᶠᶜ η at every k (explicit_free_surface.jl:36-40); MODE 1: u -= g Δt ∂xᶠᶜᶠ η
@@ -196,21 +274,25 @@ __global__ void plane_halo_kernel(int Nx, int Ny, int Hx, int Hy, double *__rest
 // compute_split_explicit_forcing! (compute_slow_tendencies.jl:12-32), FORCING = 1: Gᵁ = Σₖ Δz ((3/2 + χ) Guⁿ - (1/2 + χ) Gu⁻ not_euler);
 // integrate_barotropic_mode! on a static grid (σ = 1, barotropic_split_explicit_corrector.jl:13-32), FORCING = 0: Σₖ Δz u σ.
 // A u-shaped and a v-shaped field into their planes; the first level starts the sum (no 0 + ...).
-template <bool BX, bool BY, int FORCING>
-__global__ __launch_bounds__(256) void column_sum_kernel(GridDev g, const double *__restrict__ un, const double *__restrict__ um,
+// Over a fitted bottom (compute_slow_tendencies.jl:17-42): Σₖ Δz ifelse(peripheral_node, 0, ab2 G).
+template <bool BX, bool BY, int FORCING, class... B>
+__global__ __launch_bounds__(256) void column_sum_kernel(GridDev g, B... bottom, const double *__restrict__ un, const double *__restrict__ um,
                                                          const double *__restrict__ vn, const double *__restrict__ vm, double chi,
                                                          double *__restrict__ U, double *__restrict__ V)
 {
     const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
     if (i > g.Nx || j > g.Ny) return;
+    const auto col = columns(g, i, j, bottom...);
     const HLay<BX, BY> L = hlay<BX, BY>(g);
     const double C1 = 3 * 1.0 / 2 + chi, C2 = 1.0 / 2 + chi, ne = (C2 != 0) ? 1.0 : 0.0;
     long long ou = at(L.u, i, j, 1), ov = at(L.v, i, j, 1);
     double aU = 0.0, aV = 0.0;
     for (int k = 1; k <= g.Nz; ++k) {
         const double dz = dz_centre(g, k);
-        const double tu = FORCING ? dz * (C1 * un[ou] - C2 * um[ou] * ne) : dz * un[ou] * 1.0;
-        const double tv = FORCING ? dz * (C1 * vn[ov] - C2 * vm[ov] * ne) : dz * vn[ov] * 1.0;
+        // (not zero_if: the conditional operator keeps the two loads of a peripheral node behind a branch, and the column sum over a
+        // fitted bottom is 6 % faster with the branch than with loads and a select: DESIGN §5.2v)
+        const double tu = FORCING ? dz * (col.peripheral_u(0, 0, k) ? 0.0 : C1 * un[ou] - C2 * um[ou] * ne) : dz * un[ou] * 1.0;
+        const double tv = FORCING ? dz * (col.peripheral_v(0, 0, k) ? 0.0 : C1 * vn[ov] - C2 * vm[ov] * ne) : dz * vn[ov] * 1.0;
         aU = k == 1 ? tu : aU + tu;
         aV = k == 1 ? tv : aV + tv;
         ou += L.u.s3; ov += L.v.s3;
@@ -223,9 +305,10 @@ __global__ __launch_bounds__(256) void column_sum_kernel(GridDev g, const double
 // of the planes are used: indices wrap along a Periodic direction, and across a wall the operators are δxTᶜᵃᵃ / δyTᵃᶜᵃ and ∂xTᶠᶜᶠ / ∂yTᶜᶠᶠ.
 // _split_explicit_free_surface! (step_split_explicit_free_surface.jl:12-20): η -= Δτ (δx(Δy U) + δy(Δx V)) / Az.  Across a wall
 // (topology_aware_operators.jl:35-56) the transport is zero -- at i = Nx the difference is -f(Nx), at i = 1 it is f(2) -- whatever the
-// wall faces of U hold
-template <bool BX, bool BY>
-__global__ __launch_bounds__(256) void split_explicit_eta_kernel(GridDev g, double dtau, double *__restrict__ eta,
+// wall faces of U hold.  Over a fitted bottom the transports go through conditional_U_fcc / V_cfc (conditional_differences.jl:83-90): 0 on
+// a peripheral node at k = Nz (a dry column on either side)
+template <bool BX, bool BY, class... B>
+__global__ __launch_bounds__(256) void split_explicit_eta_kernel(GridDev g, B... bottom, double dtau, double *__restrict__ eta,
                                                                  const double *__restrict__ U, const double *__restrict__ V)
 {
     const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
@@ -233,17 +316,23 @@ __global__ __launch_bounds__(256) void split_explicit_eta_kernel(GridDev g, doub
     const HLay<BX, BY> L = hlay<BX, BY>(g);
     const double dx = g.dx, dy = g.dy, Az = dx * dy;
     const long long e = plane_at(g, L.c, i, j), eu = plane_at(g, L.u, i, j), ev = plane_at(g, L.v, i, j);
+    const auto col = columns(g, i, j, bottom...);
+    auto Uw = [&] { return zero_if(col.peripheral_u(0, 0, g.Nz), dy * U[eu]); };  // the transports through the four faces of the column
+    auto Ue = [&](long long east) { return zero_if(col.peripheral_u(1, 0, g.Nz), dy * U[east]); };
+    auto Vs = [&] { return zero_if(col.peripheral_v(0, 0, g.Nz), dx * V[ev]); };
+    auto Vn = [&](long long north) { return zero_if(col.peripheral_v(0, 1, g.Nz), dx * V[north]); };
     double dU, dV;
-    if (BX) dU = i == g.Nx ? -(dy * U[eu]) : (i == 1 ? dy * U[eu + 1] : dy * U[eu + 1] - dy * U[eu]);
-    else dU = dy * U[plane_at(g, L.u, i == g.Nx ? 1 : i + 1, j)] - dy * U[eu];
-    if (BY) dV = j == g.Ny ? -(dx * V[ev]) : (j == 1 ? dx * V[ev + L.v.sx] : dx * V[ev + L.v.sx] - dx * V[ev]);
-    else dV = dx * V[plane_at(g, L.v, i, j == g.Ny ? 1 : j + 1)] - dx * V[ev];
+    if (BX) dU = i == g.Nx ? -Uw() : (i == 1 ? Ue(eu + 1) : Ue(eu + 1) - Uw());
+    else dU = Ue(plane_at(g, L.u, i == g.Nx ? 1 : i + 1, j)) - Uw();
+    if (BY) dV = j == g.Ny ? -Vs() : (j == 1 ? Vn(ev + L.v.sx) : Vn(ev + L.v.sx) - Vs());
+    else dV = Vn(plane_at(g, L.v, i, j == g.Ny ? 1 : j + 1)) - Vs();
     eta[e] = eta[e] - dtau * (dU + dV) / Az;
 }
 // _split_explicit_barotropic_velocity! (:22-46): U += Δτ (-g H ∂x η + Gᵁ), V likewise; the filtered state accumulates weight x (η, U, V).
-// ∂xTᶠᶜᶠ / ∂yTᶜᶠᶠ (topology_aware_operators.jl:32-44, 66-67) are zero on a wall face
-template <bool BX, bool BY>
-__global__ __launch_bounds__(256) void split_explicit_velocity_kernel(GridDev g, double w, double dtau, double grav, double H,
+// ∂xTᶠᶜᶠ / ∂yTᶜᶠᶠ (topology_aware_operators.jl:32-44, 66-67) are zero on a wall face, and over a fitted bottom when one of the two
+// (c, c, f) nodes at k = Nz + 1 is inactive (conditional_differences.jl:86-87): a dry column; the column depths are then the planes Hᶠᶜ, Hᶜᶠ
+template <bool BX, bool BY, class... B>
+__global__ __launch_bounds__(256) void split_explicit_velocity_kernel(GridDev g, B... bottom, double w, double dtau, double grav, double H,
                                                                       const double *__restrict__ eta, double *__restrict__ U,
                                                                       double *__restrict__ V, double *__restrict__ etab,
                                                                       double *__restrict__ Ub, double *__restrict__ Vb,
@@ -259,8 +348,11 @@ __global__ __launch_bounds__(256) void split_explicit_velocity_kernel(GridDev g,
     else dex = et - eta[plane_at(g, L.c, i == 1 ? g.Nx : i - 1, j)];
     if (BY) dey = j == 1 ? 0.0 : et - eta[e - L.c.sx];
     else dey = et - eta[plane_at(g, L.c, i, j == 1 ? g.Ny : j - 1)];
-    const double Un = U[eu] + dtau * (-grav * H * (dex / g.dx) + GU[eu]);
-    const double Vn = V[ev] + dtau * (-grav * H * (dey / g.dy) + GV[ev]);
+    const auto col = columns(g, i, j, bottom...);
+    dex = zero_if(col.dry(0, 0) || col.dry(-1, 0), dex);
+    dey = zero_if(col.dry(0, 0) || col.dry(0, -1), dey);
+    const double Un = U[eu] + dtau * (-grav * depth_fc(H, eu, bottom...) * (dex / g.dx) + GU[eu]);
+    const double Vn = V[ev] + dtau * (-grav * depth_cf(H, ev, bottom...) * (dey / g.dy) + GV[ev]);
     etab[e] += w * et;
     Ub[eu] += w * Un;
     Vb[ev] += w * Vn;
@@ -268,18 +360,22 @@ __global__ __launch_bounds__(256) void split_explicit_velocity_kernel(GridDev g,
     V[ev] = Vn;
 }
 
-// _barotropic_split_explicit_corrector! (barotropic_split_explicit_corrector.jl:57-71): u += (U - U̅) / H at every level
-template <bool BX, bool BY>
-__global__ __launch_bounds__(256) void barotropic_corrector_kernel(GridDev g, double *__restrict__ u, double *__restrict__ v,
+// _barotropic_split_explicit_corrector! (barotropic_split_explicit_corrector.jl:57-81): u += (U - U̅) / Hᶠᶜ at every level.  On a dry face
+// of a fitted bottom Hᶠᶜ = 0 and U = U̅ = 0: the reference writes 0 / 0 there, and so does this; the face is peripheral, the next mask removes it
+template <bool BX, bool BY, class... B>
+__global__ __launch_bounds__(256) void barotropic_corrector_kernel(GridDev g, B... bottom, double *__restrict__ u, double *__restrict__ v,
                                                                    const double *__restrict__ U, const double *__restrict__ V,
                                                                    const double *__restrict__ Ub, const double *__restrict__ Vb, double H)
 {
-    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y, k = 1 + blockIdx.z;
+    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
+    int k = first_level<B...>();
     if (i > g.Nx || j > g.Ny) return;
     const HLay<BX, BY> L = hlay<BX, BY>(g);
-    const long long ou = at(L.u, i, j, k), ov = at(L.v, i, j, k), eu = plane_at(g, L.u, i, j), ev = plane_at(g, L.v, i, j);
-    u[ou] = u[ou] + (U[eu] - Ub[eu]) / H;
-    v[ov] = v[ov] + (V[ev] - Vb[ev]) / H;
+    do {  // (the division does not depend on k: over a fitted bottom once per column)
+        const long long ou = at(L.u, i, j, k), ov = at(L.v, i, j, k), eu = plane_at(g, L.u, i, j), ev = plane_at(g, L.v, i, j);
+        u[ou] = u[ou] + (U[eu] - Ub[eu]) / depth_fc(H, eu, bottom...);
+        v[ov] = v[ov] + (V[ev] - Vb[ev]) / depth_cf(H, ev, bottom...);
+    } while (next_level<B...>(g, k));
 }
 
 // ---- ImplicitFreeSurface with the FFT solver (implicit_free_surface.jl:112-145, fft_based_implicit_free_surface_solver.jl:76-115,
@@ -324,6 +420,8 @@ __global__ __launch_bounds__(256) void implicit_rhs_kernel(GridDev g, double gra
 }
 
 inline size_t plane_bytes(const Lay &L) { return (size_t)L.sx * L.sy * sizeof(double); }
+// blocks along z of a launch over every level: one per level, or one per KZ levels over a fitted bottom (first_level)
+inline int z_blocks(const GridDev &g, const Bottom &bottom) { return bottom.fitted() ? z_chunks(g.Nz) : g.Nz; }
 
 }  // namespace
 
@@ -337,12 +435,13 @@ int launch_w_from_continuity(const ocn_grid *grid, const double *u, const double
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
 }
-int launch_vector_invariant(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu, double *Gv, const double *eta,
-                            double grav, hipStream_t stream)
+int launch_vector_invariant(const ocn_grid *grid, const Bottom &bottom, const double *u, const double *v, const double *w, double *Gu, double *Gv,
+                            const double *eta, double grav, hipStream_t stream)
 {
     GridDev g = to_dev(*grid);
-    dispatch_walls(grid, [&](auto bx, auto by) {
-        hipLaunchKernelGGL((vector_invariant_kernel<bx, by>), xy_blocks(g.Nx, g.Ny, g.Nz), dim3(64, 4, 1), 0, stream, g, u, v, w, Gu, Gv, eta, grav);
+    const dim3 nb = xy_blocks(g.Nx, g.Ny, z_blocks(g, bottom));
+    dispatch_bottom(grid, bottom, [&](auto bx, auto by, auto... b) {
+        hipLaunchKernelGGL((vector_invariant_kernel<bx, by, decltype(b)...>), nb, dim3(64, 4, 1), 0, stream, g, b..., u, v, w, Gu, Gv, eta, grav);
     });
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
@@ -376,12 +475,13 @@ int launch_plane_halo(const ocn_grid *grid, double *plane, hipStream_t stream)
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
 }
-int launch_split_explicit_forcing(const ocn_grid *grid, const double *Gun, const double *Gum, const double *Gvn, const double *Gvm, double chi,
-                                  double *GU, double *GV, hipStream_t stream)
+int launch_split_explicit_forcing(const ocn_grid *grid, const Bottom &bottom, const double *Gun, const double *Gum, const double *Gvn,
+                                  const double *Gvm, double chi, double *GU, double *GV, hipStream_t stream)
 {
     GridDev g = to_dev(*grid);
-    dispatch_walls(grid, [&](auto bx, auto by) {
-        hipLaunchKernelGGL((column_sum_kernel<bx, by, 1>), xy_blocks(g.Nx, g.Ny), dim3(64, 4, 1), 0, stream, g, Gun, Gum, Gvn, Gvm, chi, GU, GV);
+    dispatch_bottom(grid, bottom, [&](auto bx, auto by, auto... b) {
+        hipLaunchKernelGGL((column_sum_kernel<bx, by, 1, decltype(b)...>), xy_blocks(g.Nx, g.Ny), dim3(64, 4, 1), 0, stream, g, b..., Gun, Gum, Gvn,
+                           Gvm, chi, GU, GV);
     });
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
@@ -395,19 +495,22 @@ int launch_barotropic_mode(const ocn_grid *grid, const double *u, const double *
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
 }
-int launch_barotropic_corrector(const ocn_grid *grid, double *u, double *v, const double *U, const double *V, double *Ub, double *Vb, double H,
-                                hipStream_t stream)
+int launch_barotropic_corrector(const ocn_grid *grid, const Bottom &bottom, double *u, double *v, const double *U, const double *V, double *Ub,
+                                double *Vb, double H, hipStream_t stream)
 {
+    // integrate_barotropic_mode! (:13-37): on a static grid σ = 1, also where h = 0, and over a fitted bottom u, v have just been masked:
+    // the plain column sums
     OCN_TRY(launch_barotropic_mode(grid, u, v, Ub, Vb, stream));
     GridDev g = to_dev(*grid);
-    dispatch_walls(grid, [&](auto bx, auto by) {
-        hipLaunchKernelGGL((barotropic_corrector_kernel<bx, by>), xy_blocks(g.Nx, g.Ny, g.Nz), dim3(64, 4, 1), 0, stream, g, u, v, U, V, Ub, Vb, H);
+    const dim3 nb = xy_blocks(g.Nx, g.Ny, z_blocks(g, bottom));
+    dispatch_bottom(grid, bottom, [&](auto bx, auto by, auto... b) {
+        hipLaunchKernelGGL((barotropic_corrector_kernel<bx, by, decltype(b)...>), nb, dim3(64, 4, 1), 0, stream, g, b..., u, v, U, V, Ub, Vb, H);
     });
     OCN_CHECK_HIP(hipGetLastError());
     return OCN_SUCCESS;
 }
-int launch_split_explicit_substeps(const ocn_grid *grid, int n, const double *weights, double dtau, double grav, double H, double *eta,
-                                   double *U, double *V, double *etab, double *Ub, double *Vb, const double *GU, const double *GV,
+int launch_split_explicit_substeps(const ocn_grid *grid, const Bottom &bottom, int n, const double *weights, double dtau, double grav, double H,
+                                   double *eta, double *U, double *V, double *etab, double *Ub, double *Vb, const double *GU, const double *GV,
                                    hipStream_t stream)
 {
     GridDev g = to_dev(*grid);
@@ -417,11 +520,11 @@ int launch_split_explicit_substeps(const ocn_grid *grid, int n, const double *we
     OCN_CHECK_HIP(hipMemsetAsync(Ub, 0, bu, stream));
     OCN_CHECK_HIP(hipMemsetAsync(Vb, 0, bv, stream));
     const dim3 block(64, 4, 1), nb = xy_blocks(g.Nx, g.Ny);
-    dispatch_walls(grid, [&](auto bx, auto by) {
+    dispatch_bottom(grid, bottom, [&](auto bx, auto by, auto... b) {
         for (int m = 0; m < n; ++m) {
-            hipLaunchKernelGGL((split_explicit_eta_kernel<bx, by>), nb, block, 0, stream, g, dtau, eta, U, V);
-            hipLaunchKernelGGL((split_explicit_velocity_kernel<bx, by>), nb, block, 0, stream, g, weights[m], dtau, grav, H, eta, U, V, etab, Ub, Vb,
-                               GU, GV);
+            hipLaunchKernelGGL((split_explicit_eta_kernel<bx, by, decltype(b)...>), nb, block, 0, stream, g, b..., dtau, eta, U, V);
+            hipLaunchKernelGGL((split_explicit_velocity_kernel<bx, by, decltype(b)...>), nb, block, 0, stream, g, b..., weights[m], dtau, grav, H, eta,
+                               U, V, etab, Ub, Vb, GU, GV);
         }
     });
     OCN_CHECK_HIP(hipGetLastError());

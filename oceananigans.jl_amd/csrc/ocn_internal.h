@@ -184,42 +184,40 @@ int launch_barotropic_correct_w(const ocn_grid *grid, const double *us, const do
 int launch_free_surface_ab2(const ocn_grid *grid, const double *w, double *eta, double *Gn, const double *Gm, double dt, double chi,
                             hipStream_t stream);
 // the hydrostatic kernels of every horizontal topology -- (Periodic, Periodic | Bounded, Bounded), (Bounded, Bounded, Bounded) --
-// (hydrostatic_surface.hip): per-location parent layouts and planes
+// (hydrostatic_surface.hip): per-location parent layouts and planes.  Bottom: the GridFittedBottom of an ImmersedBoundaryGrid as the
+// kernels see it -- kbot, the int32 plane of immersed cells per column, and the column depths at the u and v points; all null: a flat bottom
+struct Bottom {
+    const int32_t *kbot = nullptr;
+    const double *Hfc = nullptr, *Hcf = nullptr;
+    bool fitted() const { return kbot || Hfc || Hcf; }
+};
 int launch_w_from_continuity(const ocn_grid *grid, const double *u, const double *v, double *w, hipStream_t stream);
-int launch_vector_invariant(const ocn_grid *grid, const double *u, const double *v, const double *w, double *Gu, double *Gv, const double *eta,
-                            double grav, hipStream_t stream);
+int launch_vector_invariant(const ocn_grid *grid, const Bottom &bottom, const double *u, const double *v, const double *w, double *Gu, double *Gv,
+                            const double *eta, double grav, hipStream_t stream);
 int launch_barotropic_gradient(const ocn_grid *grid, double grav, const double *eta, double *Gu, double *Gv, hipStream_t stream);
 int launch_implicit_free_surface_rhs(const ocn_grid *grid, const double *u, const double *v, const double *eta, double grav, double dt,
                                      double *Qu, double *Qv, double *rhs, hipStream_t stream);
 int launch_barotropic_pressure_correction(const ocn_grid *grid, double *u, double *v, const double *eta, double grav, double dt,
                                           hipStream_t stream);
 int launch_plane_halo(const ocn_grid *grid, double *plane, hipStream_t stream);
-int launch_split_explicit_forcing(const ocn_grid *grid, const double *Gun, const double *Gum, const double *Gvn, const double *Gvm, double chi,
-                                  double *GU, double *GV, hipStream_t stream);
-int launch_split_explicit_substeps(const ocn_grid *grid, int n, const double *weights, double dtau, double grav, double H, double *eta,
-                                   double *U, double *V, double *etab, double *Ub, double *Vb, const double *GU, const double *GV,
+int launch_split_explicit_forcing(const ocn_grid *grid, const Bottom &bottom, const double *Gun, const double *Gum, const double *Gvn,
+                                  const double *Gvm, double chi, double *GU, double *GV, hipStream_t stream);
+// (H: the column depth over a flat bottom; a fitted one brings its depths)
+int launch_split_explicit_substeps(const ocn_grid *grid, const Bottom &bottom, int n, const double *weights, double dtau, double grav, double H,
+                                   double *eta, double *U, double *V, double *etab, double *Ub, double *Vb, const double *GU, const double *GV,
                                    hipStream_t stream);
 int launch_barotropic_mode(const ocn_grid *grid, const double *u, const double *v, double *U, double *V, hipStream_t stream);
-int launch_barotropic_corrector(const ocn_grid *grid, double *u, double *v, const double *U, const double *V, double *Ub, double *Vb, double H,
-                                hipStream_t stream);
-// the hydrostatic kernels on ImmersedBoundaryGrid(grid, GridFittedBottom(h)) (immersed.hip): kbot is the int32 plane of immersed cells per column
+int launch_barotropic_corrector(const ocn_grid *grid, const Bottom &bottom, double *u, double *v, const double *U, const double *V, double *Ub,
+                                double *Vb, double H, hipStream_t stream);
+// the kernels over a GridFittedBottom that have no flat twin above (immersed.hip)
 int launch_immersed_bottom(const ocn_grid *grid, int interface_condition, const double *h, const double *zc, const double *zf, double *bottom,
                            int32_t *kbot, double *Hcc, double *Hfc, double *Hcf, hipStream_t stream);
 int launch_immersed_mask(const ocn_grid *grid, const int32_t *kbot, const FieldTuple &f, double value, double *eta, double *U, double *V,
                          hipStream_t stream);
-int launch_vector_invariant_immersed(const ocn_grid *grid, const int32_t *kbot, const double *u, const double *v, const double *w, double *Gu,
-                                     double *Gv, const double *eta, double grav, hipStream_t stream);
 int launch_viscosity_immersed(const ocn_grid *grid, const int32_t *kbot, double nu, const double *u, const double *v, const double *w,
                               double *Gu, double *Gv, hipStream_t stream);
 int launch_tracer_immersed(const ocn_grid *grid, const int32_t *kbot, int diffuse, double kappa, const double *u, const double *v,
                            const double *w, const double *c, double *Gc, hipStream_t stream);
-int launch_split_explicit_forcing_immersed(const ocn_grid *grid, const int32_t *kbot, const double *Gun, const double *Gum, const double *Gvn,
-                                           const double *Gvm, double chi, double *GU, double *GV, hipStream_t stream);
-int launch_split_explicit_substeps_immersed(const ocn_grid *grid, const int32_t *kbot, const double *Hfc, const double *Hcf, int n,
-                                            const double *weights, double dtau, double grav, double *eta, double *U, double *V, double *etab,
-                                            double *Ub, double *Vb, const double *GU, const double *GV, hipStream_t stream);
-int launch_barotropic_corrector_immersed(const ocn_grid *grid, const double *Hfc, const double *Hcf, double *u, double *v, const double *U,
-                                         const double *V, double *Ub, double *Vb, hipStream_t stream);
 int launch_halo_plane_x(const ocn_grid *grid, double *field, int loc, int which, double *buf, int unpack, hipStream_t stream);
 int launch_halo_pack_x_fields(const ocn_grid *grid, const FieldTuple &ft, double *west, double *east, int unpack, hipStream_t stream);
 int launch_rowdct(int Nx, int Ny, int Nz, RowDCT mode, double *data, const double *tw, const double *wd, const double *lx, const double *ly,

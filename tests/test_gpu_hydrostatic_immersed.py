@@ -9,8 +9,9 @@ from helpers import from_dev, stretched_faces, to_dev
 
 pytestmark = pytest.mark.gpu
 
-# (16, 12, 7) with halo 3; (67, 6, 5) with halo (4, 5, 3): across the 64-lane block edge in x, a partial block in y, unequal halos
-SHAPES = [((16, 12, 7), (3, 3, 3)), ((67, 6, 5), (4, 5, 3))]
+# (16, 12, 7) with halo 3; (67, 6, 5) with halo (4, 5, 3): across the 64-lane block edge in x, a partial block in y, unequal halos;
+# (16, 12, 10) with halo 3: more levels than the 8 a thread of the z-walking kernels takes, so a second, partial chunk in z
+SHAPES = [((16, 12, 7), (3, 3, 3)), ((67, 6, 5), (4, 5, 3)), ((16, 12, 10), (3, 3, 3))]
 LX, LY, LZ = 2.0e3, 1.5e3, 40.0
 GRAV = 9.80665
 UNWRITTEN = 777.0   # what outputs hold before a launch: a cell the kernel should not write still holds it afterwards
@@ -26,7 +27,9 @@ def bathymetry(og):
       * a plateau two cells high next to untouched columns (a step of more than one level), across the 64-lane edge when Nx > 64;
       * a 3 x 3 block of dry columns around one wet column;
       * two ridges three cells high with a one-cell-wide trench between them, running through the periodic seam in y;
-      * a dry column and a raised one on the periodic seam in x.
+      * a dry column and a raised one on the periodic seam in x;
+      * when Nz > 8, next to an untouched column: a column with 8 immersed cells, whose bottom lies on the edge between the two z chunks
+        of a thread, and beside it one with 9.
     Heights are cell-centre values, so each is also the case `h exactly at a centre`."""
     Nx, Ny, Nz = og.Nx, og.Ny, og.Nz
     zc = np.asarray(og.nodes(2, False))[:Nz]
@@ -41,6 +44,9 @@ def bathymetry(og):
     h[14, :] = level(3)
     h[0, Ny - 1] = level(Nz)
     h[Nx - 1, 0] = level(1)
+    if Nz > 8:
+        h[5, 7] = level(8)
+        h[6, 7] = level(9)
     return h
 
 
@@ -122,6 +128,8 @@ def test_the_bathymetry_holds_every_feature(case):
     assert (kb[12] == 3).all() and (kb[14] == 3).all() and (kb[13] == 0).all()            # a one-cell-wide trench, through the seam in y
     assert kb[2, 1] - kb[1, 1] == 2                                                       # a step of more than one level
     assert dry[0, -1] and kb[-1, 0] == 1                                                  # on the seam in x
+    if Nz > 8:
+        assert kb[4, 7] == 0 and kb[5, 7] == 8 and kb[6, 7] == 9                          # a bottom on the z-chunk edge, one past it
 
 
 # ---- the entry points -------------------------------------------------------------------------------------------------------------------

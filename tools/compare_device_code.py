@@ -9,7 +9,8 @@ bundle where the compiler wrote one, and compared.  One line per object:
 
     identical                       the two code objects are the same bytes
     kernels -N: <names>             B lacks N kernels of A (or has +N more); every kernel both have disassembles to the same text
-    kernels renamed N: <names>      N kernels have another symbol (the types of their arguments were renamed); all disassemble to the same text
+    kernels renamed N: <names>      N kernels have another symbol (the types of their arguments were renamed, or their template argument
+                                    list grew at its end); all disassemble to the same text.  With -N / +N for the kernels left unpaired
     DIFFERENT: ...                  anything else
 
 Whole code objects and the disassembly text of whole kernels are compared; nothing looks for particular instructions.
@@ -90,7 +91,24 @@ def demangle(names):
     if not names or not tool:
         return list(names)
     out = subprocess.run([tool] + list(names), check=True, capture_output=True, text=True).stdout
-    return [re.sub(r"\(.*", "", n) for n in out.splitlines()]
+    return [without_parameters(n) for n in out.splitlines()]
+
+
+def without_parameters(name):
+    """a demangled function name without its parameter list: the text before the parenthesis that the last one closes"""
+    if not name.endswith(")"):
+        return name
+    depth = 0
+    for at in range(len(name) - 1, -1, -1):
+        depth += {")": 1, "(": -1}.get(name[at], 0)
+        if depth == 0:
+            return name[:at]
+    return name
+
+
+def same_kernel(da, db):
+    """demangled names without parameters: equal, or b is a with further trailing template arguments"""
+    return da == db or (da.endswith(">") and db.endswith(">") and db.startswith(da[:-1] + ", "))
 
 
 def compare(a, b):
@@ -102,14 +120,26 @@ def compare(a, b):
     if changed:
         return False, f"DIFFERENT: the disassembly of {len(changed)} kernels differs: " + ", ".join(demangle(changed)[:4])
     gone, new = sorted(ka.keys() - kb.keys()), sorted(kb.keys() - ka.keys())
-    # a kernel whose argument types were renamed (a struct moved to another namespace) has another symbol: pair such kernels by their
-    # demangled name without the parameter list and compare their text with the kernel's own symbol taken out
-    renamed = {n: m for n, dn in zip(gone, demangle(gone)) for m, dm in zip(new, demangle(new)) if dn == dm}
-    if renamed and len(renamed) == len(gone) == len(new):
+    # a kernel whose argument types were renamed (a struct moved to another namespace) or whose template argument list grew at its end has
+    # another symbol: pair such kernels by their demangled name without the parameter list (the equal name before the longer one) and
+    # compare their text with the kernel's own symbol taken out
+    named_gone, named_new = list(zip(gone, demangle(gone))), list(zip(new, demangle(new)))
+    renamed = {}
+    for exact in (True, False):
+        for n, dn in named_gone:
+            free = [m for m, dm in named_new if m not in renamed.values() and (dn == dm if exact else same_kernel(dn, dm))]
+            if free and n not in renamed:
+                renamed[n] = free[0]
+    if renamed:
         changed = sorted(n for n, m in renamed.items() if ka[n].replace(n, "") != kb[m].replace(m, ""))
         if changed:
             return False, f"DIFFERENT: {len(renamed)} kernels renamed, the disassembly of {len(changed)} differs: " + ", ".join(demangle(changed)[:4])
-        return True, f"kernels renamed {len(renamed)}: " + ", ".join(demangle(gone)) + f"; all {len(ka)} kernels disassemble to the same text"
+        line = f"kernels renamed {len(renamed)}: " + ", ".join(demangle(sorted(renamed)))
+        gone, new = [n for n in gone if n not in renamed], [m for m in new if m not in renamed.values()]
+        for sign, rest in (("-", gone), ("+", new)):
+            if rest:
+                line += f"; kernels {sign}{len(rest)}: " + ", ".join(demangle(rest))
+        return True, line + f"; all {len(ka) - len(gone)} kernels both have disassemble to the same text"
     if not gone and not new:
         return False, "DIFFERENT: same kernels with the same disassembly, other bytes (data, metadata)"
     parts = ([f"kernels -{len(gone)}: " + ", ".join(demangle(gone))] if gone else []) + ([f"kernels +{len(new)}: " + ", ".join(demangle(new))] if new else [])
